@@ -306,7 +306,8 @@ def compact_line(full, detail_path=None):
     out["config"]["mode"] = _short(cfg.get("mode", ""), 48)
     if "resident" in cfg:
         out["config"]["resident"] = _pick(cfg["resident"], ("matches", "gave_up"))
-    out["roofline"] = _pick(full.get("roofline", {}), _ROOF_KEYS)
+    if "roofline" in full:  # (a plain run's record is the headline alone: no roofline, parity or legs)
+        out["roofline"] = _pick(full["roofline"], _ROOF_KEYS)
     rv = full.get("roofline_valu")
     if isinstance(rv, dict):
         out["roofline"]["valu_issue_frac"] = rv.get("valu_issue_frac")
@@ -322,10 +323,11 @@ def compact_line(full, detail_path=None):
     c = _cpu_digest(full.get("cpu_baseline"))
     if c is not None:
         out["cpu_baseline"] = c
-    par = full.get("parity", {})
-    out["parity"] = _pick(par, ("scenes", "traces_equal", "filtered_counts_equal", "max_rel_score", "scenes_differing"))
-    if "note" in par:
-        out["parity"]["note"] = _short(par["note"], 100)
+    par = full.get("parity")
+    if isinstance(par, dict):
+        out["parity"] = _pick(par, ("scenes", "traces_equal", "filtered_counts_equal", "max_rel_score", "scenes_differing"))
+        if "note" in par:
+            out["parity"]["note"] = _short(par["note"], 100)
     legs = {}
     pf = full.get("particle_filter")
     if isinstance(pf, dict):
@@ -365,7 +367,8 @@ def compact_line(full, detail_path=None):
                                 "by_K": [[r_["K"], r_.get("ms_per_call"), r_.get("value"),
                                           (r_.get("roofline") or {}).get("frac")] for r_ in rep.get("by_K", [])],
                                 "columns": ["K", "ms_per_call", "value", "frac"]}
-    out["legs"] = legs
+    if "roofline" in full:
+        out["legs"] = legs
     if detail_path:
         out["detail"] = detail_path
     top = {k: out[k] for k in ("value", "ms_per_step") if k in out}  # the driver's own figures keep every digit
@@ -376,7 +379,7 @@ def compact_line(full, detail_path=None):
     for victim in ("replicas", "world_loop_viny", "world_loop", "brute_force", "cfg5", "monte_carlo", "particle_filter"):
         if len(line) <= LINE_TARGET:
             break
-        if victim in out["legs"]:
+        if victim in out.get("legs", {}):
             out["legs"][victim] = {"see": "detail"}
             line = json.dumps(out, separators=(",", ":"))
     if len(line) > LINE_LIMIT:

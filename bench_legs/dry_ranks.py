@@ -23,7 +23,7 @@ def dry_ranks_main(args):
     dist.init_process_group("gloo")
     import __graft_entry__ as ge
     pkg = ge.load_package()
-    # the two forms `bench.py --gpus N` runs the filter in: STRONG -- --particles particles over the
+    # the two forms `bench.py --full --gpus N` runs the filter in: STRONG -- --particles particles over the
     # ranks -- and WEAK -- --particles particles PER rank
     strong = _walk(args, pkg, torch, dist, rank, world, args.particles)
     weak = _walk(args, pkg, torch, dist, rank, world, args.particles * world)

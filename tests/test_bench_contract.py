@@ -10,7 +10,7 @@ import os
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the driver's command (`python bench.py`: every leg, CPU baselines) and the headline alone (`--legs none`)
+# the driver's full command (`python bench.py --full`: every leg, CPU baselines) and the headline alone (`--full --legs none`)
 DEFAULT = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_default_bench_unprofiled.json")))
 HEADLINE = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hc_bench_unprofiled.json")))
 

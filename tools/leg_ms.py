@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """ms per step of the secondary legs of a bench.py line read from stdin (pf, pf_update, pf_maps, cfg5, world) -- a
-helper for A/B runs on the GPU box: python bench.py --legs pf_update ... | python tools/leg_ms.py"""
+helper for A/B runs on the GPU box: python bench.py --full --legs pf_update ... | python tools/leg_ms.py"""
 import json
 import sys
 

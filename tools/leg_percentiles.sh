@@ -2,9 +2,10 @@
 # tools/leg_percentiles.sh <leg> <kernel-substring> [...] -- rocprofv3 kernel trace of one bench.py leg on the GPU box,
 # duration percentiles (us) of the named kernels (a mean hides a tail: k_mu_lines' p50 4 us, p90 80 us)
 LEG=$1; shift
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/lp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/lp -o lp -- python3 $GRAFT_REPO_ROOT/bench.py --legs $LEG --steps 3 --warmup 1 --no-cpu > /tmp/lp.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/lp -o lp -- python3 $ROOT/bench.py --full --legs $LEG --steps 3 --warmup 1 --no-cpu > /tmp/lp.log 2>&1
 python3 - "$@" <<'PY'
 import csv, glob, sys
 import numpy as np

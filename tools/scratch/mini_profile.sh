@@ -6,10 +6,10 @@ mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 run() {
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o $name -- python3 $ROOT/bench.py --detail-out $OUT/$name.bench.json "$@" > $OUT/$name.bench.log 2>&1
-  python3 $ROOT/bench.py --detail-out $OUT/$name.plain.json "$@" 2> /dev/null | grep '^{"metric' | tail -1 > $OUT/$name.line.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o $name -- python3 $ROOT/bench.py --full --detail-out $OUT/$name.bench.json "$@" > $OUT/$name.bench.log 2>&1
+  python3 $ROOT/bench.py --full --detail-out $OUT/$name.plain.json "$@" 2> /dev/null | grep '^{"metric' | tail -1 > $OUT/$name.line.json
 }
-python3 $ROOT/bench.py --steps 20 --warmup 5 --detail-out $OUT/default.plain.json > $OUT/default.stdout 2> $OUT/default.err
+python3 $ROOT/bench.py --full --steps 20 --warmup 5 --detail-out $OUT/default.plain.json > $OUT/default.stdout 2> $OUT/default.err
 tail -n 1 $OUT/default.stdout > $OUT/default.line.json
 run world --legs world --steps 3 --warmup 1 --no-cpu
 run world_viny --legs world_viny --steps 3 --warmup 1 --no-cpu
