@@ -1,5 +1,6 @@
 // matchers.cpp -- C-ABI of the matcher tier (include/slamhip.h): MC / HC / BF process_scan over the
-// speculative drivers of matchers.h.
+// speculative drivers of matchers.h, and the host drivers of the device accept chains: ONE lone-chain driver
+// (hill climbing, Monte Carlo) and ONE many-chains driver (K matches per call, one chain per particle).
 
 #include <cstdlib>
 #include <limits>
@@ -10,89 +11,221 @@
 #include "hc_shape.h"
 #include "mc_chain_device.h"
 #include "matchers.h"
+#include "resident_policy.h"
+
+namespace slamhip {
+
+// A hipMalloc / hipHostMalloc block and its owner: freed when the owner goes, so that no error return between an
+// allocation and the store of its pointer can leak it.  Move-only; nothing else.
+template <class T, bool kPinned>
+class HipBlock {
+  T *p_ = nullptr;
+
+ public:
+  HipBlock() = default;
+  HipBlock(const HipBlock &) = delete;
+  HipBlock &operator=(const HipBlock &) = delete;
+  HipBlock(HipBlock &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  HipBlock &operator=(HipBlock &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_;
+      o.p_ = nullptr;
+    }
+    return *this;
+  }
+  ~HipBlock() { reset(); }
+  T *get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+  void reset() {
+    if (p_) {
+      if constexpr (kPinned) hipHostFree(p_);
+      else hipFree(p_);
+    }
+    p_ = nullptr;
+  }
+  // `count` elements in place of what was held (a failed allocation leaves the owner empty)
+  hipError_t alloc(size_t count, unsigned pinned_flags = 0) {
+    reset();
+    if constexpr (kPinned) return hipHostMalloc(&p_, sizeof(T) * count, pinned_flags);
+    else return hipMalloc(&p_, sizeof(T) * count);
+  }
+};
+template <class T>
+using DeviceBuf = HipBlock<T, false>;
+template <class T>
+using PinnedBuf = HipBlock<T, true>;
+constexpr unsigned kPinnedCoherent = hipHostMallocMapped | hipHostMallocCoherent;
+
+// {chains-done counter (0), initial poses, a table with one Entry per chain}: one block per side that ONE pull kernel
+// moves in front of a launch (launch_block_pull)
+template <class Entry>
+struct StageBlock {
+  PinnedBuf<char> h;
+  DeviceBuf<char> d;
+  size_t table_at = 0;
+  int alloc(int cap, hipStream_t stream) {
+    // [0, 16): the chains-done counter; then the initial poses; then the table (a pull copies the front of the
+    // block up to the last entry in use)
+    table_at = 16 + ((sizeof(double) * 3 * (size_t)cap + 15) & ~(size_t)15);
+    const size_t bytes = table_at + ((sizeof(Entry) * (size_t)cap + 15) & ~(size_t)15);
+    SLAMHIP_CHECK(h.alloc(bytes, hipHostMallocMapped));
+    std::memset(h.get(), 0, bytes);
+    SLAMHIP_CHECK(d.alloc(bytes));
+    SLAMHIP_CHECK(hipMemsetAsync(d.get(), 0, bytes, stream));
+    return SLAMHIP_OK;
+  }
+  unsigned *d_n_done() const { return reinterpret_cast<unsigned *>(d.get()); }
+  double *h_inits() const { return reinterpret_cast<double *>(h.get() + 16); }
+  double *d_inits() const { return reinterpret_cast<double *>(d.get() + 16); }
+  Entry *h_table() const { return reinterpret_cast<Entry *>(h.get() + table_at); }
+  Entry *d_table() const { return reinterpret_cast<Entry *>(d.get() + table_at); }
+  size_t bytes_upto_inits(int n) const { return 16 + sizeof(double) * 3 * (size_t)n; }
+  size_t bytes_upto_table(int n) const { return table_at + sizeof(Entry) * (size_t)n; }
+};
+
+// the speculation-tree shapes of a driver: instances per shape, instances of the largest one (grid size of a super-step)
+struct ShapeSizes {
+  int n_inst[kHcShapes] = {0};
+  int max_inst = 1;
+  unsigned long long packed() const {  // (HcChainArgs::n_inst)
+    unsigned long long v = 0;
+    for (int b = 0; b < kHcShapes; ++b) v |= (unsigned long long)(n_inst[b] & 0xff) << (8 * b);
+    return v;
+  }
+};
+
+// What the many-chains driver (run_many_chains) owns for its caller: per-chain control / result blocks, the staging
+// block, the shapes, the co-resident form's exchange blocks.  `Rctl` is the exchange block of a chain, `Entry` what the
+// staging table holds per chain.
+template <class Rctl, class Entry>
+struct ChainSet {
+  int cap = 0;
+  DeviceBuf<HcChainCtl> d_ctl;
+  PinnedBuf<HcHostOut> h_out;  // one per chain
+  StageBlock<Entry> stage;
+  DeviceBuf<HcShape> d_shapes;
+  ShapeSizes shapes;
+  int built_inst = 0, nt = 256;
+  PinnedBuf<unsigned> h_done_count;
+  DeviceBuf<Rctl> d_rctl;            // co-resident form: one exchange block per chain (cap of them)
+  PinnedBuf<unsigned> h_all_done;    // the last chain to end stores the epoch here
+  int rctl_grid = 0, rctl_chains = 0;  // slots per chain / chains of the last co-resident launch
+  unsigned rctl_launches = 0;          // co-resident launches on d_rctl (hc_tag)
+  unsigned epoch = 0;
+  double steps_avg;
+  explicit ChainSet(double steps_avg0) : steps_avg(steps_avg0) {}
+};
+
+}  // namespace slamhip
+
+struct BatchJobResult {
+  double pose[3] = {0, 0, 0}, prob = 0;
+  long long calls = 0, evaluated = 0, rescored = 0;
+  int steps = 0, error = 0;
+  bool on_chain = false;
+};
+// slamhip_matcher_process_scan_batch: blocks of the last batch (hc_batch_run); the staging table is the job table
+struct HcBatch : slamhip::ChainSet<slamhip::HcResidentCtl, slamhip::HcJobView> {
+  HcBatch() : ChainSet(16.0) {}
+  bool resident_call = false;  // hc_resident_asked() of the call in flight, asked once
+  slamhip::PinnedBuf<double> h_scan;  // the batch's scans: per match five arrays of its beam count
+  slamhip::DeviceBuf<double> d_scan;
+  size_t scan_cap = 0;  // doubles
+  bool pair = false;    // the co-resident launch's workgroups (512 threads) score two poses per super-step
+  int cus = 0;          // CUs of the device (sizes the pair form's trees)
+  slamhip::PinnedBuf<slamhip::HcTraceEntry> h_trace;  // cap x trace_per entries (observer attached only)
+  int trace_per = 0, trace_chains = 0;
+  long long kernels = 0;
+  std::vector<BatchJobResult> res;
+};
 
 struct slamhip_matcher {
+  // ---- what every kind of matcher has
   slamhip_ctx *ctx = nullptr;
   slamhip_spe_cfg cfg{};
   std::unique_ptr<slamhip::PoseEnumerator> pe;
   slamhip_observer obs{};
   bool has_obs = false;
+  bool is_hc = false, is_mc = false, is_bf = false;
   int max_batch = 0;
   double p_accept0 = 0.25;  // prior per-candidate acceptance rate of a fresh match
   slamhip::MatchJob job;
   double t_stage_us = 0, t_score_us = 0;
-  // hill climbing kept on the device (hc_chain.h): parameters of the enumerator, device / pinned blocks
-  bool is_hc = false;
   int device = 0;
-  unsigned hc_max_failed = 0;
-  double hc_dt = 0, hc_dr = 0;
-  slamhip::HcChainCtl *d_chain = nullptr;
-  slamhip::HcShape *d_shapes = nullptr;
-  slamhip::HcHostOut *h_chain = nullptr;
-  slamhip::HcTraceEntry *h_trace = nullptr;
-  int trace_cap = 0;
-  int shape_n_inst[slamhip::kHcShapes] = {0};
-  unsigned chain_epoch = 0;
-  double chain_steps_avg = 12.0;
-  int chain_mode = -1;  // -1 = decide at the first match, 0 off, 1 the chain of kernels, 2 one co-resident launch
-  bool chain_mode_explicit = false;  // set through slamhip_matcher_set_device_chain (not the default)
-  int chain_nt = 1024, chain_ahead = 3;
-  // the co-resident form (hc_resident.hip): exchange block, workgroups the device keeps resident (by workgroup
-  // size; 0 = not asked yet), matches that gave up in a row / in total (bounded spin ran out: kernel chain instead)
-  slamhip::HcResidentCtl *d_rctl = nullptr;
-  slamhip::HcResidentGmCtl *d_rctl_gm = nullptr;
-  slamhip::McResidentCtl *d_mc_rctl = nullptr;
-  int mc_rctl_grid = 0;  // workgroups of the last co-resident Monte-Carlo launch
-  unsigned rctl_launches = 0;  // co-resident launches on this matcher's exchange block: the epoch bits of the tags (hc_tag)
-  // answers of the occupancy query so far, keyed by everything the answer depends on (kernel instantiation: cell model,
-  // workgroup size, lone / batch / window form, sweep width via max_inst; dynamic LDS: scan length, beam constants)
-  struct ResidentCap {
-    int cell_model, nt, form, n_beams, lds_consts, max_inst, cap, per_cu;
-  };
-  std::vector<ResidentCap> resident_caps;
-  double resident_us_max = 0;      // the longest co-resident match / batch seen (decaying): sizes the kernels' spin bound
-  int chain_matches_since_off = 0;  // kernel-chain matches since the co-resident form switched itself off (re-arm)
-  int resident_gave_up_row = 0;
-  int debug_resident_mute = 0;  // testing (slamhip_matcher_debug_resident_mute)
-  long long resident_gave_up = 0, resident_matches = 0;
-  int chain_max_inst = slamhip::kHcMaxInst;  // instances of the largest shape (grid size of a super-step)
   int tie_check = -1;  // checked default mode: -1 = not set yet (on), 0, 1 (slamhip_matcher_set_tie_check)
   long long chain_rescored = 0;  // super-steps (device chain) / batches (host-driven) of the last match scored twice
   long long tail_calls = 0;      // scorer calls of the last match / batch the co-resident chain reported in closed form
   long long rescored_poses = 0;
   std::vector<double> keep_scores;
   std::vector<unsigned long long> keep_fprints;
+  // ---- the device chains (lone HC, lone MC, the HC batch): mode, epochs, the co-resident policy they share
+  int chain_mode = -1;  // -1 = decide at the first match, 0 off, 1 the chain of kernels, 2 one co-resident launch
+  bool chain_mode_explicit = false;  // set through slamhip_matcher_set_device_chain (not the default)
+  int chain_nt = 1024, chain_ahead = 3;
+  unsigned chain_epoch = 0;
+  double chain_steps_avg = 12.0;
   long long chain_launched = 0;  // kernels launched by the last process_scan (steps + run-ahead)
-  long long *d_stamps = nullptr;  // debugging (slamhip_matcher_debug_stamps)
-  int debug_trace_cap = 0;        // testing (slamhip_matcher_debug_trace_cap): pretend the trace buffer is this small
-  int debug_fail_next = 0;        // testing (slamhip_matcher_debug_fail_next): injected failures left
-  struct HcBatch *batch = nullptr;  // slamhip_matcher_process_scan_batch: blocks of the last batch (hc_batch_*)
-  // brute force as one flat sweep + a device arg-max (bf_device.hip)
-  bool is_bf = false;
-  double bf_r[9] = {0};
-  std::vector<double> bf_off;  // x offsets, y offsets, theta offsets as the enumerator accumulates them
-  int bf_nx = 0, bf_ny = 0, bf_nt = 0;
-  double *d_bf_off = nullptr, *d_bf_poses = nullptr, *d_bf_scores = nullptr;
-  unsigned long long *d_bf_fp = nullptr;
-  long long *d_bf_pidx = nullptr, *d_bf_agg_i = nullptr;
-  double *d_bf_agg_s = nullptr;
-  unsigned *d_bf_counters = nullptr;
-  slamhip::BfHostOut *h_bf = nullptr;
-  long long bf_cap = 0;
-  unsigned bf_seq = 0;
-  std::vector<double> bf_scores_host;
-  // Monte Carlo kept on the device (mc_chain.h)
-  bool is_mc = false;
-  slamhip::McChainCtl *d_mc = nullptr;
-  slamhip::McHostOut *h_mc = nullptr;
-  slamhip::McPair *d_tape = nullptr;
-  double *h_tape = nullptr;  // pinned staging of the tape window
-  size_t tape_cap = 0;       // pairs d_tape / h_tape hold
-  size_t tape_base = 0;      // absolute tape position of d_tape[0]
-  size_t tape_filled = 0;    // pairs of the window already in HBM (or on their way, see tape_ready)
-  hipStream_t tape_stream = nullptr;  // uploads the next match's pairs while this match's chain runs
-  hipEvent_t tape_ready = nullptr;
-  int mc_slots = 0;
+  unsigned rctl_launches = 0;  // co-resident launches on this matcher's exchange block: the epoch bits of the tags (hc_tag)
+  slamhip::ResidentPolicy resident;  // bounded spins that ran out: the kernel chain instead (resident_policy.h)
+  // answers of the occupancy query so far, keyed by everything the answer depends on (kernel instantiation: cell model,
+  // workgroup size, lone / batch / window form, sweep width via max_inst; dynamic LDS: scan length, beam constants)
+  struct ResidentCap {
+    int cell_model, nt, form, n_beams, lds_consts, max_inst, cap, per_cu;
+  };
+  std::vector<ResidentCap> resident_caps;
+  slamhip::PinnedBuf<slamhip::HcTraceEntry> h_trace;  // the observer's trace of a lone chain (HC and MC)
+  int trace_cap = 0;
+  slamhip::DeviceBuf<long long> d_stamps;  // debugging (slamhip_matcher_debug_stamps)
+  int debug_resident_mute = 0;  // testing (slamhip_matcher_debug_resident_mute)
+  int debug_trace_cap = 0;      // testing (slamhip_matcher_debug_trace_cap): pretend the trace buffer is this small
+  int debug_fail_next = 0;      // testing (slamhip_matcher_debug_fail_next): injected failures left
+  // ---- hill climbing kept on the device (hc_chain.h): parameters of the enumerator, device / pinned blocks
+  struct HcChain {
+    unsigned max_failed = 0;
+    double dt = 0, dr = 0;
+    slamhip::DeviceBuf<slamhip::HcChainCtl> d_chain;
+    slamhip::DeviceBuf<slamhip::HcShape> d_shapes;
+    slamhip::PinnedBuf<slamhip::HcHostOut> h_chain;
+    slamhip::ShapeSizes shapes;
+    // the co-resident form (hc_resident.hip, hc_resident_gm.hip): exchange block
+    slamhip::DeviceBuf<slamhip::HcResidentCtl> d_rctl;
+    slamhip::DeviceBuf<slamhip::HcResidentGmCtl> d_rctl_gm;
+  } hc;
+  std::unique_ptr<HcBatch> batch;  // K matches per call
+  // ---- Monte Carlo kept on the device (mc_chain.h)
+  struct McChain {
+    slamhip::DeviceBuf<slamhip::McChainCtl> d_mc;
+    slamhip::PinnedBuf<slamhip::McHostOut> h_mc;
+    slamhip::DeviceBuf<slamhip::McResidentCtl> d_rctl;
+    int rctl_grid = 0;  // workgroups of the last co-resident Monte-Carlo launch
+    slamhip::DeviceBuf<slamhip::McPair> d_tape;
+    slamhip::PinnedBuf<double> h_tape;  // staging of the tape window
+    size_t tape_cap = 0;                // pairs d_tape / h_tape hold
+    size_t tape_base = 0;               // absolute tape position of d_tape[0]
+    size_t tape_filled = 0;             // pairs of the window already in HBM (or on their way, see tape_ready)
+    hipStream_t tape_stream = nullptr;  // uploads the next match's pairs while this match's chain runs
+    hipEvent_t tape_ready = nullptr;
+    int slots = 0;
+    ~McChain() {
+      if (tape_stream) hipStreamDestroy(tape_stream);
+      if (tape_ready) hipEventDestroy(tape_ready);
+    }
+  } mc;
+  // ---- brute force as one flat sweep + a device arg-max (bf_device.hip)
+  struct BfSweep {
+    double r[9] = {0};
+    std::vector<double> off;  // x offsets, y offsets, theta offsets as the enumerator accumulates them
+    int nx = 0, ny = 0, nt = 0;
+    slamhip::DeviceBuf<double> d_off, d_poses, d_scores, d_agg_s;
+    slamhip::DeviceBuf<unsigned long long> d_fp;
+    slamhip::DeviceBuf<long long> d_pidx, d_agg_i;
+    slamhip::DeviceBuf<unsigned> d_counters;
+    slamhip::PinnedBuf<slamhip::BfHostOut> h_out;
+    long long cap = 0;
+    unsigned seq = 0;
+    std::vector<double> scores_host;
+  } bf;
 };
 
 using namespace slamhip;
@@ -117,90 +250,56 @@ int make_matcher(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, std::unique_ptr<P
   return SLAMHIP_OK;
 }
 
-// ---- hill climbing on the device ------------------------------------------------------------------
-}  // namespace
-
-namespace slamhip {
-
-}  // namespace slamhip
-
-namespace {
-
 constexpr int kChainNeedsHost = 1;  // internal: positive, never leaves the library
-constexpr int kResidentGaveUp = 2;  // internal: the co-resident launch left without a result, the kernel chain redoes the match
 // internal: a GMapping-OOPE chain met a comparison its tree sums (device exp) cannot settle the reference's way; nothing
 // has been reported: the match is redone in the exact mode (call order, beam-order sums, glibc's exp: exact_kernels.hip)
 constexpr int kChainUnsettled = 3;
 constexpr int kChainDefaultMode = 2;  // device chains: 1 = a kernel per super-step, 2 = one co-resident launch where it applies
-// after three give-ups in a row a matcher stops asking for the co-resident form; 64 matches later it asks again (the
-// other tenant of the device may be gone)
-constexpr int kResidentRearmAfter = 64;
 
+// ---- pieces every driver uses ----------------------------------------------------------------------
 
-void hc_batch_free(slamhip_matcher *m);
-int chain_release(slamhip_matcher *m) {
-  hc_batch_free(m);
-  if (m->d_chain) hipFree(m->d_chain);
-  if (m->d_rctl) hipFree(m->d_rctl);
-  m->d_rctl = nullptr;
-  if (m->d_rctl_gm) hipFree(m->d_rctl_gm);
-  m->d_rctl_gm = nullptr;
-  if (m->d_mc_rctl) hipFree(m->d_mc_rctl);
-  m->d_mc_rctl = nullptr;
-  if (m->d_shapes) hipFree(m->d_shapes);
-  if (m->h_chain) hipHostFree(m->h_chain);
-  if (m->h_trace) hipHostFree(m->h_trace);
-  if (m->d_stamps) hipFree(m->d_stamps);
-  if (m->d_bf_off) hipFree(m->d_bf_off);
-  if (m->d_bf_poses) hipFree(m->d_bf_poses);
-  if (m->d_bf_scores) hipFree(m->d_bf_scores);
-  if (m->d_bf_fp) hipFree(m->d_bf_fp);
-  if (m->d_bf_pidx) hipFree(m->d_bf_pidx);
-  if (m->d_bf_agg_i) hipFree(m->d_bf_agg_i);
-  if (m->d_bf_agg_s) hipFree(m->d_bf_agg_s);
-  if (m->d_bf_counters) hipFree(m->d_bf_counters);
-  m->d_bf_pidx = m->d_bf_agg_i = nullptr;
-  m->d_bf_agg_s = nullptr;
-  m->d_bf_counters = nullptr;
-  if (m->h_bf) hipHostFree(m->h_bf);
-  m->d_bf_off = m->d_bf_poses = m->d_bf_scores = nullptr;
-  m->d_bf_fp = nullptr;
-  m->h_bf = nullptr;
-  m->bf_cap = 0;
-  if (m->d_mc) hipFree(m->d_mc);
-  if (m->d_tape) hipFree(m->d_tape);
-  if (m->h_mc) hipHostFree(m->h_mc);
-  if (m->h_tape) hipHostFree(m->h_tape);
-  if (m->tape_stream) hipStreamDestroy(m->tape_stream);
-  if (m->tape_ready) hipEventDestroy(m->tape_ready);
-  m->tape_stream = nullptr;
-  m->tape_ready = nullptr;
-  m->d_mc = nullptr;
-  m->d_tape = nullptr;
-  m->h_mc = nullptr;
-  m->h_tape = nullptr;
-  m->d_stamps = nullptr;
-  m->d_chain = nullptr;
-  m->d_shapes = nullptr;
-  m->h_chain = nullptr;
-  m->h_trace = nullptr;
+// the next value of an epoch / sequence counter; 0 is never handed out (it is what cleared memory holds)
+unsigned next_epoch(unsigned &counter) {
+  if (++counter == 0) ++counter;
+  return counter;
+}
+
+// the observer's events of a device chain, from its pinned trace, in call order
+void replay_trace(const slamhip_observer &obs, const HcTraceEntry *entries, long long calls) {
+  for (long long i = 0; i < calls; ++i) {
+    const HcTraceEntry &e = entries[i];
+    const double p3[3] = {e.x, e.y, e.theta};
+    if (obs.on_scan_test) obs.on_scan_test(obs.user, p3, e.score);
+    if (e.accepted && obs.on_pose_update) obs.on_pose_update(obs.user, p3, e.score);
+  }
+}
+
+// the speculation-tree shapes for at most `want` round instances, built and uploaded; `reach`: the probability of
+// being on the walked path below which no instance is added (repeated outcomes weigh 1.0)
+int build_shapes(int want, double reach, HcShape *d_shapes, ShapeSizes *sizes) {
+  std::vector<HcShape> shapes(kHcShapes);
+  sizes->max_inst = 1;
+  for (int b = 0; b < kHcShapes; ++b) {
+    hc_build_shape(hc_bucket_rate(b), 1.0, reach, want, &shapes[b]);
+    sizes->n_inst[b] = shapes[b].n_inst;
+    sizes->max_inst = std::max(sizes->max_inst, shapes[b].n_inst);
+  }
+  SLAMHIP_CHECK(hipMemcpy(d_shapes, shapes.data(), sizeof(HcShape) * kHcShapes, hipMemcpyHostToDevice));
   return SLAMHIP_OK;
 }
 
-// the chain covers what the shipped single-hypothesis configurations use: hill climbing over the 1-cell
-// OOPE in the default mode; everything else (strict order, host trigonometry, window OOPEs, GMapping,
-// staged copies) keeps the host-driven path
+// ---- hill climbing on the device ------------------------------------------------------------------
 // Failed-round limits the device chains cover.  A chain halves both steps once per failed round -- as ONE exact
 // multiplication by 2^-f per walked segment (hc_chain.h) where the reference halves f times: the two agree as long as
 // no intermediate is subnormal, i.e. as long as step * 2^-(limit + 1) is a normal double (limit <= 1000 keeps 2^-f
 // itself representable).  r01-r03 stopped at 250 for no better reason than the size of a byte.
 bool hc_limit_on_device(const slamhip_matcher *m) {
-  if (m->hc_max_failed == 0 || m->hc_max_failed > 1000) return false;  // (also: 16 bits in HcNextEntry::counts)
-  for (double step : {m->hc_dt, m->hc_dr}) {
+  if (m->hc.max_failed == 0 || m->hc.max_failed > 1000) return false;  // (also: 16 bits in HcNextEntry::counts)
+  for (double step : {m->hc.dt, m->hc.dr}) {
     if (step == 0.0) continue;  // (a zero step stays zero either way)
     int e = 0;
     (void)std::frexp(std::fabs(step), &e);
-    if (!std::isfinite(step) || e - 1 - (int)m->hc_max_failed - 1 < -1021) return false;
+    if (!std::isfinite(step) || e - 1 - (int)m->hc.max_failed - 1 < -1021) return false;
   }
   return true;
 }
@@ -214,6 +313,9 @@ bool tie_check_default(slamhip_matcher *m) {
   return m->tie_check == 1;
 }
 
+// The device chain covers hill climbing over the 1-cell, the window and the GMapping OOPEs with device pose
+// trigonometry on the zero-copy path; everything else (strict order, host trigonometry, staged copies, small
+// batches) keeps the host-driven path.
 bool chain_eligible(slamhip_matcher *m) {
   if (!m->is_hc || !hc_limit_on_device(m)) return false;
   const bool gm = m->cfg.oope == SLAMHIP_OOPE_GMAPPING;
@@ -230,28 +332,24 @@ bool chain_eligible(slamhip_matcher *m) {
   return m->chain_mode >= 1;
 }
 
-// Can this match run as ONE launch of co-resident workgroups?  The 1-cell OOPE only (the GMapping OOPE's super-steps
-// hand side outputs of every pose to the replay: kernel chain), and the grid must fit the device at once.
-bool resident_wanted(slamhip_matcher *m) {
+// Is this hill-climbing call asked to run as ONE launch of co-resident workgroups?  (Whether the grid fits the device
+// at once is the driver's question.)  Asks the policy, so: once per call.
+bool hc_resident_asked(slamhip_matcher *m) {
   // A LONE chain over the GMapping OOPE is co-resident only when asked for (mode 2 set explicitly): measured on
   // MI355X it is no faster than the chain of kernels (r05: 12.46 against 12.40 us per super-step,
   // profiles/r05_resident_stamps.txt / r05_chain_stamps.txt; the shared-map filter step 12.9 against 13.0 ms) -- four
   // granules per pose instead of one, a second workgroup barrier per super-step -- while a filter step's MANY chains
   // in one launch are (gm_multi_chain_run: 0.58 -> 0.44 ms per 100 particles).
   const bool gm = m->cfg.oope == SLAMHIP_OOPE_GMAPPING && m->chain_mode_explicit;
-  if (m->resident_gave_up_row >= 3 && ++m->chain_matches_since_off >= kResidentRearmAfter) {
-    m->resident_gave_up_row = 0;  // (re-armed: the device may be ours again)
-    m->chain_matches_since_off = 0;
-  }
-  return m->chain_mode == 2 && (m->cfg.oope == SLAMHIP_OOPE_OBSTACLE || is_window_oope(m->cfg.oope) || gm) &&
-         m->resident_gave_up_row < 3;
+  const bool armed = m->resident.armed();
+  return m->chain_mode == 2 && (m->cfg.oope == SLAMHIP_OOPE_OBSTACLE || is_window_oope(m->cfg.oope) || gm) && armed;
 }
 // ---- co-resident launches of ONE process on one device (two contexts -- two robots -- on a GPU).
 // A co-resident grid only runs when ALL its workgroups are on the chip; two such grids launched at once can each get
 // half and wait for the other's slots until their spin bounds run out.  Within a process the library knows who is
 // resident: a launch takes its CUs' worth of slots from this per-device ledger for as long as its host call lasts
 // (process_scan is synchronous) and, when they are not there, runs as the chain of kernels AT ONCE -- nobody stalls.
-// (Across processes only the bounded spins help: sized from the matches seen, spin_limit_for below.)
+// (Across processes only the bounded spins help: sized from the matches seen, ResidentPolicy::spin_limit.)
 std::mutex g_resident_mu;
 int g_resident_cus[64] = {0};
 int g_device_cus[64] = {0};
@@ -280,16 +378,6 @@ struct ResidentLease {
   }
   ~ResidentLease() { release(); }
 };
-
-// polls a sweep may take before a chain gives up: ten times the longest match seen (a poll is ~0.4 us), never less
-// than 2^12 (1.6 ms) nor more than 2^17 (~55 ms: the bound of a matcher's first launches)
-unsigned spin_limit_for(double us_max) {
-  constexpr unsigned kMax = 1u << 17, kMin = 1u << 12;
-  if (!(us_max > 0)) return kMax;
-  const double polls = 25.0 * us_max;
-  return polls >= (double)kMax ? kMax : (polls <= (double)kMin ? kMin : (unsigned)polls);
-}
-void note_resident_time(double *us_max, double us) { *us_max = std::max(0.98 * *us_max, us); }
 
 // form: 0 a lone chain, 1 a batch (job table), 2 a window OOPE, 3 Monte Carlo, 4 a batch whose workgroups score two poses
 int resident_capacity(slamhip_matcher *m, int cell_model, int nt, int form, int n_beams, bool lds_consts, int max_inst,
@@ -328,40 +416,178 @@ int resident_capacity_pick(slamhip_matcher *m, int cell_model, int nt, int form,
   return resident_capacity(m, cell_model, nt, form, n_beams, false, max_inst, wgs, per_cu);
 }
 
+// ---- the lone-chain driver (hill climbing, Monte Carlo) -----------------------------------------------
+struct LoneChainText {  // what the messages call the chain
+  const char *resident_ended, *resident, *no_end, *step;
+};
+
+// Waits on pinned memory until the chain has published its result under `epoch`.  kResident: ONE launch is running;
+// else the chain of kernels, which the host keeps `ahead` launches in front of the step the GPU reports (a launch
+// costs the host ~3.5 us, a super-step the GPU ~5 us).  `idle` is what the host does between two polls: at least a
+// pause.  Every 2^20 polls the stream is asked whether something went wrong.
+template <bool kResident, class HostOut, class LaunchOne, class Idle>
+int lone_chain_wait(slamhip_ctx *ctx, volatile HostOut *h, unsigned epoch, int ahead, const int &launched,
+                    LaunchOne &&launch_one, Idle &&idle, const LoneChainText &text) {
+  unsigned long long spins = 0;
+  while (h->done_seq != epoch) {
+    if constexpr (!kResident) {
+      const int started = (int)h->progress;
+      if (launched - started < ahead) {
+        if (launched >= (1 << 20)) {
+          set_error(text.no_end);
+          return SLAMHIP_ERR_STATE;
+        }
+        const int rc = launch_one();
+        if (rc) return rc;
+        continue;
+      }
+    }
+    const int rc = idle();
+    if (rc) return rc;
+    if ((++spins & 0xfffffull) == 0) {
+      hipError_t qe = hipStreamQuery(ctx->stream);
+      if (kResident && qe == hipSuccess && h->done_seq != epoch) {
+        set_error(text.resident_ended);
+        return SLAMHIP_ERR_STATE;
+      }
+      if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, kResident ? text.resident : text.step);
+    }
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  return SLAMHIP_OK;
+}
+
+// One match as one chain.  `resident`: try the co-resident form first --
+//   fit(lease, &fits)           capacity, the lease, the exchange block (allocated / cleared on the context's stream):
+//                               the kind's own; fits = false: the chain of kernels at once
+//   launch_resident(e0, e1)     the ONE launch
+//   fail_over(gave_up)          the co-resident form did not run (gave_up: it was launched and left without a result,
+//                               the stream has been drained): the kind prepares `a` for the chain of kernels
+//   launch_step(step, e0, e1)   one kernel of the chain
+// On return the result is in *h (acquire fence passed), *t0 is the start of the form that ran.
+template <class Args, class HostOut, class Fit, class LaunchResident, class FailOver, class LaunchStep, class Idle>
+int run_lone_chain(slamhip_matcher *m, Args &a, volatile HostOut *h, bool resident, const double &t0, int *launched_out,
+                   Fit &&fit, LaunchResident &&launch_resident, FailOver &&fail_over, LaunchStep &&launch_step,
+                   Idle &&idle, const LoneChainText &text) {
+  slamhip_ctx *ctx = m->ctx;
+  int launched = 0, rc = SLAMHIP_OK;
+  auto launch_one = [&]() -> int {
+    hipEvent_t e0, e1;
+    int r = profile_event_pair(ctx, &e0, &e1);
+    if (r) return r;
+    SLAMHIP_CHECK(launch_step(launched, e0, e1));
+    ++launched;
+    return SLAMHIP_OK;
+  };
+  bool ran_resident = false;
+  if (resident) {
+    // ---- ONE launch: every workgroup of the tree stays on the chip for the whole match
+    ResidentLease lease;
+    bool fits = false, gave_up = false;
+    rc = fit(lease, &fits);
+    if (rc) return rc;
+    if (fits) {
+      a.spin_limit = m->resident.spin_limit();
+      a.tag_epoch = ++m->rctl_launches;
+      a.debug_mute = m->debug_resident_mute;
+      hipEvent_t e0, e1;
+      rc = profile_event_pair(ctx, &e0, &e1);
+      if (rc) return rc;
+      SLAMHIP_CHECK(launch_resident(e0, e1));
+      launched = 1;
+      m->resident.note_launch();
+      rc = lone_chain_wait<true>(ctx, h, a.epoch, 0, launched, launch_one, idle, text);
+      if (rc) return rc;
+      if (h->error == 4 || h->error == 5) {
+        // a workgroup was not resident with the others (the bounded sweep ran out), or the chain is longer than a
+        // tag counts: nothing has been reported; wait for the stragglers to leave, then the kernel chain runs the match
+        SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (h->error == 4) m->resident.note_give_up();
+        h->error = 0;
+        launched = 0;
+        gave_up = true;
+      } else {
+        m->resident.note_success(MatchJob::now_us() - t0);
+        ran_resident = true;
+      }
+    }
+    if (!ran_resident) {
+      rc = fail_over(gave_up);
+      if (rc) return rc;
+    }
+  }
+  if (!ran_resident) {
+    // the expected number of super-steps goes out at once; afterwards the host stays a few launches ahead
+    const int first = std::max(2, std::min(256, (int)(m->chain_steps_avg * 0.75)));
+    for (int i = 0; i < first; ++i) {
+      rc = launch_one();
+      if (rc) return rc;
+    }
+    rc = lone_chain_wait<false>(ctx, h, a.epoch, m->chain_ahead, launched, launch_one, idle, text);
+    if (rc) return rc;
+  }
+  *launched_out = launched;
+  return SLAMHIP_OK;
+}
+
+// a lone chain's result into the matcher and out to the caller / the observer (the kind has mapped h->error already)
+template <class HostOut>
+int lone_chain_report(slamhip_matcher *m, volatile HostOut *h, int launched, int scan_n, double t0,
+                      const double init_pose[3], double out_delta[3], double *out_prob) {
+  slamhip_ctx *ctx = m->ctx;
+  MatchJob &job = m->job;
+  job.scorer_calls = h->calls;
+  job.poses_evaluated = h->evaluated;
+  job.launches = h->steps;
+  job.t_build_us = job.t_replay_us = 0;
+  m->chain_launched = launched;
+  m->chain_rescored = h->rescored;
+  m->chain_steps_avg = 0.75 * m->chain_steps_avg + 0.25 * (double)h->steps;
+  if (ctx->profile) {
+    // every kernel launched carries an event pair, the run-ahead ones that found the chain finished too
+    // (rocprofv3 counts them as dispatches of the same kernel)
+    ctx->prof_launches += launched;
+    ctx->prof_units += h->evaluated * (long long)scan_n;
+  }
+  out_delta[0] = h->pose[0] - init_pose[0];
+  out_delta[1] = h->pose[1] - init_pose[1];
+  out_delta[2] = h->pose[2] - init_pose[2];
+  *out_prob = h->best_prob;
+  m->t_score_us = MatchJob::now_us() - t0;
+  if (m->has_obs) {
+    const double t1 = MatchJob::now_us();
+    replay_trace(m->obs, m->h_trace.get(), h->calls);
+    job.t_replay_us = MatchJob::now_us() - t1;
+    if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, out_delta, *out_prob);
+  }
+  return SLAMHIP_OK;
+}
+
 int chain_prepare(slamhip_matcher *m) {
-  if (m->d_chain) return SLAMHIP_OK;
-  SLAMHIP_CHECK(hipMalloc(&m->d_chain, sizeof(HcChainCtl)));
+  slamhip_matcher::HcChain &hc = m->hc;
+  if (hc.d_chain) return SLAMHIP_OK;
+  SLAMHIP_CHECK(hc.d_chain.alloc(1));
   // (every clearing of a fresh device block goes on the context's own stream: that stream is non-blocking, a hipMemset
   // on the null stream is asynchronous for device memory and NOT ordered with it -- the block's first user could run
   // ahead of the memset and have its staged data zeroed under it: r05, a sharded step that started from pose 0 once
   // in fifteen runs with three contexts on one device)
-  SLAMHIP_CHECK(hipMemsetAsync(m->d_chain, 0, sizeof(HcChainCtl), m->ctx->stream));
-  SLAMHIP_CHECK(hipMalloc(&m->d_shapes, sizeof(HcShape) * kHcShapes));
-  std::vector<HcShape> shapes(kHcShapes);
-  const double boost = 1.0, reach = 0.002;  // (shape building: weight of repeated outcomes, reach below which no instance is added)
-  const bool gm = m->cfg.oope == SLAMHIP_OOPE_GMAPPING;
+  SLAMHIP_CHECK(hipMemsetAsync(hc.d_chain.get(), 0, sizeof(HcChainCtl), m->ctx->stream));
+  SLAMHIP_CHECK(hc.d_shapes.alloc(kHcShapes));
   // 42 instances = 253 workgroups of 1024 threads: ONE per CU, all resident at once.  Measured against 64
   // instances x 512 threads (two workgroups per CU, a tree half as large again): cfg2 0.149 -> 0.138 ms per match
   // (one more super-step, each 0.8 us shorter), the shared-map filter step 4.3 k -> 5.0 k particles/s (K3's one-pose
   // body 10.7 -> 7 us); 32 or 52 instances, or 512 threads with 42, are slower again.
-  const int max_inst = kHcDefaultInst;
-  (void)gm;
-  m->chain_max_inst = 1;
-  for (int b = 0; b < kHcShapes; ++b) {
-    hc_build_shape(hc_bucket_rate(b), boost, reach, max_inst, &shapes[b]);
-    m->shape_n_inst[b] = shapes[b].n_inst;
-    m->chain_max_inst = std::max(m->chain_max_inst, shapes[b].n_inst);
-  }
-  SLAMHIP_CHECK(hipMemcpy(m->d_shapes, shapes.data(), sizeof(HcShape) * kHcShapes, hipMemcpyHostToDevice));
-  const unsigned pinned = hipHostMallocMapped | hipHostMallocCoherent;
-  SLAMHIP_CHECK(hipHostMalloc(&m->h_chain, sizeof(HcHostOut), pinned));
-  std::memset(m->h_chain, 0, sizeof(HcHostOut));
+  const int rc = build_shapes(kHcDefaultInst, 0.002, hc.d_shapes.get(), &hc.shapes);
+  if (rc) return rc;
+  SLAMHIP_CHECK(hc.h_chain.alloc(1, kPinnedCoherent));
+  std::memset(hc.h_chain.get(), 0, sizeof(HcHostOut));
   return SLAMHIP_OK;
 }
 
 int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
                        double *out_prob, bool resident) {
   slamhip_ctx *ctx = m->ctx;
+  slamhip_matcher::HcChain &hc = m->hc;
   int rc = chain_prepare(m);
   if (rc) return rc;
   HcChainArgs a;
@@ -373,14 +599,14 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
   if (rc) return rc;
   if (m->has_obs && !m->h_trace) {
     m->trace_cap = 1 << 16;
-    SLAMHIP_CHECK(hipHostMalloc(&m->h_trace, sizeof(HcTraceEntry) * m->trace_cap,
-                                hipHostMallocMapped | hipHostMallocCoherent));
+    SLAMHIP_CHECK(m->h_trace.alloc(m->trace_cap, kPinnedCoherent));
   }
+  const bool win = is_window_oope(m->cfg.oope), gm = m->cfg.oope == SLAMHIP_OOPE_GMAPPING;
   a.oie = oie_eff;
-  a.oope = is_window_oope(m->cfg.oope) ? m->cfg.oope : SLAMHIP_OOPE_OBSTACLE;
+  a.oope = win ? m->cfg.oope : SLAMHIP_OOPE_OBSTACLE;
   for (int k = 0; k < 4; ++k) a.area[k] = m->cfg.area[k];
-  if (is_window_oope(m->cfg.oope) && !resident) return kChainNeedsHost;  // (no kernel-chain form: host-driven batches)
-  a.max_inst = m->chain_max_inst;
+  if (win && !resident) return kChainNeedsHost;  // (no kernel-chain form: host-driven batches)
+  a.max_inst = hc.shapes.max_inst;
   a.gm.fullness_th = m->cfg.gm_fullness_th;
   a.gm.window = m->cfg.gm_window;
   a.gm_cx = ctx->gm_cx;
@@ -393,123 +619,78 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
   // -- error 7 -- and the match redone in the exact mode)
   a.verify = (tie_check_default(m) && !a.seq) ? 1 : 0;
   a.inert_tail = ctx->inert_tail;
-  a.ctl = m->d_chain;
-  a.shapes = m->d_shapes;
-  a.n_inst = 0;
-  for (int b = 0; b < kHcShapes; ++b) a.n_inst |= (unsigned long long)(m->shape_n_inst[b] & 0xff) << (8 * b);
+  a.ctl = hc.d_chain.get();
+  a.shapes = hc.d_shapes.get();
+  a.n_inst = hc.shapes.packed();
   for (int k = 0; k < 3; ++k) a.init[k] = init_pose[k];
-  a.dt0 = m->hc_dt;
-  a.dr0 = m->hc_dr;
-  a.max_failed = m->hc_max_failed;
+  a.dt0 = hc.dt;
+  a.dr0 = hc.dr;
+  a.max_failed = hc.max_failed;
   a.shape0 = hc_bucket_of(m->p_accept0);
-  unsigned epoch = ++m->chain_epoch;
-  if (epoch == 0) epoch = ++m->chain_epoch;
-  a.epoch = epoch;
-  a.host = m->h_chain;
-  a.trace = m->has_obs ? m->h_trace : nullptr;
+  a.epoch = next_epoch(m->chain_epoch);
+  a.host = hc.h_chain.get();
+  a.trace = m->has_obs ? m->h_trace.get() : nullptr;
   a.trace_cap = m->has_obs ? m->trace_cap : 0;
   if (m->has_obs && m->debug_trace_cap > 0) a.trace_cap = std::min(a.trace_cap, m->debug_trace_cap);
-  a.stamps = m->d_stamps;
-  volatile HcHostOut *h = m->h_chain;
+  a.stamps = m->d_stamps.get();
+  volatile HcHostOut *h = hc.h_chain.get();
   h->error = 0;
   h->progress = 0;
   h->tail_calls = 0;
-  const double t0 = MatchJob::now_us();
+  double t0 = MatchJob::now_us();
+  const HcChainArgs a_chain = a;  // (what the chain of kernels gets: nothing of the co-resident attempt)
+  const int grid = 6 * a.max_inst + 1;
   int launched = 0;
-  if (resident) {
-    // ---- ONE launch (hc_resident.hip): every workgroup of the tree stays on the chip for the whole match
-    const bool gm_res = m->cfg.oope == SLAMHIP_OOPE_GMAPPING;
-    int cap = 0, per_cu = 0;
-    if (gm_res) SLAMHIP_CHECK(hc_resident_gm_capacity(m->chain_nt, a.scan.n, &cap, &per_cu));
-    else rc = resident_capacity_pick(m, cell_model, m->chain_nt, is_window_oope(m->cfg.oope) ? 2 : 0, a.scan.n, a.max_inst,
-                                     6 * a.max_inst + 1, !is_window_oope(m->cfg.oope), &a.lds_consts, &cap, &per_cu);
-    if (rc) return rc;
-    if (6 * a.max_inst + 1 > cap) return kResidentGaveUp;  // (not counted: this matcher's grid never fits)
-    // (another context of this process holds the device's resident slots: the chain of kernels at once, no stall)
-    ResidentLease lease;
-    if (!lease.take(m->device, 6 * a.max_inst + 1, per_cu)) return kResidentGaveUp;
-    a.spin_limit = spin_limit_for(m->resident_us_max);
-    if (gm_res && !m->d_rctl_gm) {
-      SLAMHIP_CHECK(hipMalloc(&m->d_rctl_gm, sizeof(HcResidentGmCtl)));
-      SLAMHIP_CHECK(hipMemsetAsync(m->d_rctl_gm, 0, sizeof(HcResidentGmCtl), ctx->stream));
-    }
-    if (!gm_res && !m->d_rctl) {
-      SLAMHIP_CHECK(hipMalloc(&m->d_rctl, sizeof(HcResidentCtl)));
-      SLAMHIP_CHECK(hipMemsetAsync(m->d_rctl, 0, sizeof(HcResidentCtl), ctx->stream));  // (ordered with the launch)
-    }
-    // (every workgroup clears its own granules when a match starts, and this matcher's grid never changes: nothing
-    // stale can carry a current tag -- hc_tag in hc_resident.hip)
-    a.rctl = m->d_rctl;
-    a.rctl_gm = m->d_rctl_gm;
-    a.tag_epoch = ++m->rctl_launches;
-    a.debug_mute = m->debug_resident_mute;
-    hipEvent_t e0, e1;
-    rc = profile_event_pair(ctx, &e0, &e1);
-    if (rc) return rc;
-    if (gm_res) SLAMHIP_CHECK(launch_hc_chain_resident_gm(a, m->chain_nt, ctx->stream, e0, e1));
-    else SLAMHIP_CHECK(launch_hc_chain_resident(a, cell_model, m->chain_nt, ctx->stream, e0, e1));
-    launched = 1;
-    ++m->resident_matches;
-    unsigned long long spins = 0;
-    while (h->done_seq != epoch) {
-      __builtin_ia32_pause();
-      if ((++spins & 0xfffffull) == 0) {
-        hipError_t qe = hipStreamQuery(ctx->stream);
-        if (qe == hipSuccess && h->done_seq != epoch) {
-          set_error("internal: the co-resident chain ended without publishing a result");
-          return SLAMHIP_ERR_STATE;
+  rc = run_lone_chain(
+      m, a, h, resident, t0, &launched,
+      [&](ResidentLease &lease, bool *fits) -> int {
+        int cap = 0, per_cu = 0, r = SLAMHIP_OK;
+        if (gm) SLAMHIP_CHECK(hc_resident_gm_capacity(m->chain_nt, a.scan.n, &cap, &per_cu));
+        else r = resident_capacity_pick(m, cell_model, m->chain_nt, win ? 2 : 0, a.scan.n, a.max_inst, grid, !win,
+                                        &a.lds_consts, &cap, &per_cu);
+        if (r) return r;
+        // (not counted as a give-up: this matcher's grid never fits / another context of this process holds the
+        // device's resident slots: the chain of kernels at once, no stall)
+        if (grid > cap || !lease.take(m->device, grid, per_cu)) return SLAMHIP_OK;
+        if (gm && !hc.d_rctl_gm) {
+          SLAMHIP_CHECK(hc.d_rctl_gm.alloc(1));
+          SLAMHIP_CHECK(hipMemsetAsync(hc.d_rctl_gm.get(), 0, sizeof(HcResidentGmCtl), ctx->stream));
         }
-        if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, "co-resident hill-climbing chain");
-      }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    if (h->error == 4 || h->error == 5) {
-      // a workgroup was not resident with the others (the bounded sweep ran out), or the chain is longer than a
-      // tag counts: nothing has been reported; wait for the stragglers to leave, then the kernel chain runs the match
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (h->error == 4) {
-        ++m->resident_gave_up_row;
-        ++m->resident_gave_up;
-      }
-      return kResidentGaveUp;
-    }
-    m->resident_gave_up_row = 0;
-    note_resident_time(&m->resident_us_max, MatchJob::now_us() - t0);
-  }
-  auto launch_one = [&]() -> int {
-    hipEvent_t e0, e1;
-    int r = profile_event_pair(ctx, &e0, &e1);
-    if (r) return r;
-    SLAMHIP_CHECK(launch_hc_chain_step(a, cell_model, launched, m->chain_nt, ctx->stream, e0, e1));
-    ++launched;
-    return SLAMHIP_OK;
-  };
-  // the expected number of super-steps goes out at once; afterwards the host stays a few launches ahead of
-  // the step the GPU reports (a launch costs the host ~3.5 us, a super-step the GPU ~5 us)
-  const int first = resident ? 0 : std::max(2, std::min(256, (int)(m->chain_steps_avg * 0.75)));
-  for (int i = 0; i < first; ++i) {
-    rc = launch_one();
-    if (rc) return rc;
-  }
-  unsigned long long spins = 0;
-  while (h->done_seq != epoch) {
-    const int started = (int)h->progress;
-    if (launched - started < m->chain_ahead) {
-      if (launched >= (1 << 20)) {
-        set_error("hill-climbing chain did not end");
-        return SLAMHIP_ERR_STATE;
-      }
-      rc = launch_one();
-      if (rc) return rc;
-      continue;
-    }
-    __builtin_ia32_pause();
-    if ((++spins & 0xfffffull) == 0) {
-      hipError_t qe = hipStreamQuery(ctx->stream);
-      if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, "hill-climbing chain kernel");
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        if (!gm && !hc.d_rctl) {
+          SLAMHIP_CHECK(hc.d_rctl.alloc(1));
+          SLAMHIP_CHECK(hipMemsetAsync(hc.d_rctl.get(), 0, sizeof(HcResidentCtl), ctx->stream));  // (ordered with the launch)
+        }
+        // (every workgroup clears its own granules when a match starts, and this matcher's grid never changes: nothing
+        // stale can carry a current tag -- hc_tag in hc_resident.hip)
+        a.rctl = hc.d_rctl.get();
+        a.rctl_gm = hc.d_rctl_gm.get();
+        *fits = true;
+        return SLAMHIP_OK;
+      },
+      [&](hipEvent_t e0, hipEvent_t e1) {
+        return gm ? launch_hc_chain_resident_gm(a, m->chain_nt, ctx->stream, e0, e1)
+                  : launch_hc_chain_resident(a, cell_model, m->chain_nt, ctx->stream, e0, e1);
+      },
+      [&](bool) -> int {
+        // the kernel chain redoes the match from its start, under an epoch of its own
+        if (win) return kChainNeedsHost;
+        a = a_chain;
+        a.epoch = next_epoch(m->chain_epoch);
+        h->progress = 0;
+        h->tail_calls = 0;
+        t0 = MatchJob::now_us();
+        return SLAMHIP_OK;
+      },
+      [&](int step, hipEvent_t e0, hipEvent_t e1) {
+        return launch_hc_chain_step(a, cell_model, step, m->chain_nt, ctx->stream, e0, e1);
+      },
+      []() -> int {
+        __builtin_ia32_pause();
+        return SLAMHIP_OK;
+      },
+      LoneChainText{"internal: the co-resident chain ended without publishing a result", "co-resident hill-climbing chain",
+                    "hill-climbing chain did not end", "hill-climbing chain kernel"});
+  if (rc) return rc;
   m->chain_launched = launched;
   if (h->error == 1) {
     set_error("internal: the device replay found no terminal round (hill-climbing chain bug)");
@@ -520,45 +701,206 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
   // redoes the match.
   if (h->error == 7) return kChainUnsettled;
   if (h->error == 2 || h->error == 3) return kChainNeedsHost;
-  if (m->cfg.oope == SLAMHIP_OOPE_GMAPPING) {
+  if (gm) {
     ctx->gm_cx = h->gm_cx;
     ctx->gm_cy = h->gm_cy;
     ctx->gm_prob = h->gm_prob;
   }
-  MatchJob &job = m->job;
-  job.scorer_calls = h->calls;
-  job.poses_evaluated = h->evaluated;
-  job.launches = h->steps;
-  job.t_build_us = job.t_replay_us = 0;
-  m->chain_launched = launched;
-  m->chain_rescored = h->rescored;
   m->tail_calls = h->tail_calls;
-  m->chain_steps_avg = 0.75 * m->chain_steps_avg + 0.25 * (double)h->steps;
-  if (ctx->profile) {
-    // every kernel launched carries an event pair, the run-ahead ones that found the chain finished too
-    // (rocprofv3 counts them as dispatches of the same kernel)
-    ctx->prof_launches += launched;
-    ctx->prof_units += h->evaluated * (long long)a.scan.n;
+  return lone_chain_report(m, h, launched, a.scan.n, t0, init_pose, out_delta, out_prob);
+}
+
+// ---- the many-chains driver (K matches per call, one chain per particle) ------------------------------
+// All chains advance one super-step per kernel (grid.y = chain); a chain that has ended leaves the launch at
+// once.  The host queues the kernels in bursts, each closed by a one-thread marker that reports how many chains
+// are through, and always has the next burst queued before it waits for a marker.  Where all chains' workgroups fit the
+// device at once, ONE co-resident launch runs them instead: the chains then advance independently -- no chain waits at
+// a kernel boundary for the slowest one of its super-step.
+struct ManyChainsText {
+  const char *resident, *no_end;
+};
+inline void set_rctl(HcChainArgs &a, HcResidentCtl *p) { a.rctl = p; }
+inline void set_rctl(HcChainArgs &a, HcResidentGmCtl *p) { a.rctl_gm = p; }
+
+// the blocks of `s` made ready for n chains: the trees for at most `want` round instances (shape `reach`: build_shapes),
+// room for n chains (capacities double from `cap0`)
+template <class Set>
+int many_chains_prepare(slamhip_ctx *ctx, Set &s, int n, int want, double reach, int cap0) {
+  if (want != s.built_inst) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const int rc = build_shapes(want, reach, s.d_shapes.get(), &s.shapes);
+    if (rc) return rc;
+    s.built_inst = want;
   }
-  out_delta[0] = h->pose[0] - init_pose[0];
-  out_delta[1] = h->pose[1] - init_pose[1];
-  out_delta[2] = h->pose[2] - init_pose[2];
-  *out_prob = h->best_prob;
-  m->t_score_us = MatchJob::now_us() - t0;
-  if (m->has_obs) {
-    const double t1 = MatchJob::now_us();
-    for (long long i = 0; i < h->calls; ++i) {
-      const HcTraceEntry &e = m->h_trace[i];
-      const double p3[3] = {e.x, e.y, e.theta};
-      if (m->obs.on_scan_test) m->obs.on_scan_test(m->obs.user, p3, e.score);
-      if (e.accepted && m->obs.on_pose_update) m->obs.on_pose_update(m->obs.user, p3, e.score);
-    }
-    job.t_replay_us = MatchJob::now_us() - t1;
-    if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, out_delta, *out_prob);
+  const int total = n * (6 * s.shapes.max_inst + 1);
+  s.nt = total <= 256 ? 1024 : (total <= 512 ? 512 : 256);
+  if (n > s.cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    s.d_rctl.reset();
+    s.rctl_grid = s.rctl_chains = 0;
+    int cap = cap0;
+    while (cap < n) cap *= 2;
+    SLAMHIP_CHECK(s.d_ctl.alloc(cap));
+    SLAMHIP_CHECK(hipMemsetAsync(s.d_ctl.get(), 0, sizeof(HcChainCtl) * cap, ctx->stream));
+    SLAMHIP_CHECK(s.h_out.alloc(cap, kPinnedCoherent));
+    std::memset(s.h_out.get(), 0, sizeof(HcHostOut) * cap);
+    const int rc = s.stage.alloc(cap, ctx->stream);
+    if (rc) return rc;
+    s.cap = cap;
   }
   return SLAMHIP_OK;
 }
 
+// what every many-chains call puts into its arguments: blocks, shapes, a new epoch; the chains' result blocks re-armed
+template <class Set>
+void many_chains_args(Set &s, int n, HcChainArgs &a) {
+  a.max_inst = s.shapes.max_inst;
+  a.ctl = s.d_ctl.get();
+  a.inits = s.stage.d_inits();
+  a.n_done = s.stage.d_n_done();
+  a.shapes = s.d_shapes.get();
+  a.n_inst = s.shapes.packed();
+  a.epoch = next_epoch(s.epoch);
+  a.host = s.h_out.get();
+  volatile HcHostOut *h = s.h_out.get();
+  for (int c = 0; c < n; ++c) {
+    h[c].error = 0;
+    h[c].progress = 0;
+    h[c].tail_calls = 0;
+  }
+}
+
+//   fit(lease, &fits)            capacity and the lease: the caller's own; fits = false: the kernel chains at once
+//   launch_resident(e0, e1)      the ONE launch
+//   launch_step(step, e0, e1)    one kernel of the chains
+//   collect(c, h)                chain c's result (published under this call's epoch, no replay error)
+// first_burst: the share of the expected super-steps that goes out at once.
+template <class Set, class Fit, class LaunchResident, class LaunchStep, class Collect>
+int run_many_chains(slamhip_ctx *ctx, ResidentPolicy &policy, Set &s, HcChainArgs &a, int n, bool resident,
+                    double first_burst, bool *ran_resident_out, int *launched_out, Fit &&fit,
+                    LaunchResident &&launch_resident, LaunchStep &&launch_step, Collect &&collect,
+                    const ManyChainsText &text) {
+  hipStream_t st = ctx->stream;
+  volatile HcHostOut *h_out = s.h_out.get();
+  int launched = 0, rc = SLAMHIP_OK;
+  bool ran_resident = false;
+  if (resident) {
+    ResidentLease lease;  // (the device's resident slots may be another context's: the kernel chains at once then)
+    bool fits = false;
+    rc = fit(lease, &fits);
+    if (rc) return rc;
+    if (fits) {
+      const double t_res0 = MatchJob::now_us();
+      a.spin_limit = policy.spin_limit();
+      if (!s.d_rctl) {
+        SLAMHIP_CHECK(s.d_rctl.alloc(s.cap));
+        SLAMHIP_CHECK(hipMemsetAsync(s.d_rctl.get(), 0, sizeof(*s.d_rctl.get()) * s.cap, st));  // (ordered with the launch)
+      }
+      if (!s.h_all_done) {
+        SLAMHIP_CHECK(s.h_all_done.alloc(1, kPinnedCoherent));
+        *s.h_all_done.get() = 0;
+      }
+      // a launch with more slots per chain than the one before meets granules no workgroup has cleared since an
+      // older launch of that size: clear the block (queued in front of the launch)
+      if (6 * s.shapes.max_inst + 1 > s.rctl_grid || n > s.rctl_chains)
+        SLAMHIP_CHECK(hipMemsetAsync(s.d_rctl.get(), 0, sizeof(*s.d_rctl.get()) * s.cap, st));
+      s.rctl_grid = 6 * s.shapes.max_inst + 1;
+      s.rctl_chains = n;
+      set_rctl(a, s.d_rctl.get());
+      a.tag_epoch = ++s.rctl_launches;
+      a.h_all_done = s.h_all_done.get();
+      hipEvent_t e0, e1;
+      rc = profile_event_pair(ctx, &e0, &e1);
+      if (rc) return rc;
+      SLAMHIP_CHECK(launch_resident(e0, e1));
+      launched = 1;
+      policy.note_launch();
+      volatile unsigned *all_done = s.h_all_done.get();
+      unsigned long long spins = 0;
+      bool gave_up = false;
+      for (;;) {
+        if (*all_done == a.epoch) break;
+        __builtin_ia32_pause();
+        if ((++spins & 0xffffull) == 0) {
+          // a chain that gave up publishes its own done_seq with error 4 / 5 and never counts as ended
+          for (int c = 0; c < n && !gave_up; ++c)
+            gave_up = h_out[c].done_seq == a.epoch && (h_out[c].error == 4 || h_out[c].error == 5);
+          if (gave_up) break;
+          hipError_t qe = hipStreamQuery(st);
+          if (qe == hipSuccess && *all_done != a.epoch) {
+            gave_up = true;  // (every workgroup has left and the chains are not through: treated like a give-up)
+            break;
+          }
+          if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, text.resident);
+        }
+      }
+      if (gave_up) {
+        // nothing of this call has been reported: wait for the stragglers, then the kernel chains redo it
+        SLAMHIP_CHECK(hipStreamSynchronize(st));
+        policy.note_give_up();
+        SLAMHIP_CHECK(hipMemsetAsync(s.stage.d_n_done(), 0, sizeof(unsigned), st));
+        for (int c = 0; c < n; ++c) h_out[c].error = 0;
+        a.rctl = nullptr;
+        a.rctl_gm = nullptr;
+        a.h_all_done = nullptr;
+        a.debug_mute = 0;
+        launched = 0;
+        a.epoch = next_epoch(s.epoch);
+      } else {
+        ran_resident = true;
+        policy.note_success(MatchJob::now_us() - t_res0);
+      }
+    }
+  }
+  auto burst = [&](int count, unsigned *seq_out) -> int {
+    for (int i = 0; i < count; ++i) {
+      hipEvent_t e0, e1;
+      int r = profile_event_pair(ctx, &e0, &e1);
+      if (r) return r;
+      SLAMHIP_CHECK(launch_step(launched, e0, e1));
+      ++launched;
+    }
+    const unsigned seq = next_epoch(ctx->seq);
+    SLAMHIP_CHECK(launch_chain_marker(s.stage.d_n_done(), s.h_done_count.get(), ctx->h_done_flag, seq, st));
+    *seq_out = seq;
+    return SLAMHIP_OK;
+  };
+  unsigned seq_prev = 0, seq_next = 0;
+  if (!ran_resident) rc = burst(std::max(3, (int)(s.steps_avg * first_burst)), &seq_prev);
+  if (rc) return rc;
+  while (!ran_resident) {
+    rc = burst(3, &seq_next);  // queued before the wait: the GPU never runs dry
+    if (rc) return rc;
+    rc = score_wait(ctx, seq_prev);
+    if (rc) return rc;
+    if (*(volatile unsigned *)s.h_done_count.get() >= (unsigned)n) break;
+    if (launched >= (1 << 16)) {
+      set_error(text.no_end);
+      return SLAMHIP_ERR_STATE;
+    }
+    seq_prev = seq_next;
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  int max_steps = 0;
+  for (int c = 0; c < n; ++c) {
+    const volatile HcHostOut *h = &h_out[c];
+    if (h->done_seq != a.epoch) {
+      set_error("internal: a chain was counted as finished without publishing its result");
+      return SLAMHIP_ERR_STATE;
+    }
+    if (h->error == 1) {
+      set_error("internal: the device replay found no terminal round (hill-climbing chain bug)");
+      return SLAMHIP_ERR_STATE;
+    }
+    collect(c, h);
+    max_steps = std::max(max_steps, (int)h->steps);
+  }
+  s.steps_avg = 0.75 * s.steps_avg + 0.25 * (double)max_steps;
+  if (ctx->profile) ctx->prof_launches += launched;
+  *ran_resident_out = ran_resident;
+  *launched_out = launched;
+  return SLAMHIP_OK;
+}
 
 // ---- K independent hill-climbing matches in shared launches ---------------------------------------
 // PoseEnumerationScanMatcher::process_scan once per robot (pose_enumeration_scan_matcher.h:31-77; SURVEY 8e
@@ -568,63 +910,6 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
 // one scan).  A lone match is latency-bound: 253 one-pose workgroups, one per CU, 15-18 dependent kernels.  K of them
 // fill the chip: the tree of a chain shrinks with K (about kBatchWgs scoring workgroups per super-step over all
 // chains), workgroups get narrower, and several chains' poses are resident per CU.
-}  // namespace
-struct BatchJobResult {
-  double pose[3] = {0, 0, 0}, prob = 0;
-  long long calls = 0, evaluated = 0, rescored = 0;
-  int steps = 0, error = 0;
-  bool on_chain = false;
-};
-struct HcBatch {
-  int cap = 0;
-  slamhip::HcChainCtl *d_ctl = nullptr;
-  slamhip::HcHostOut *h_out = nullptr;     // pinned, one per chain
-  // one block per side -- {chains-done counter (0), initial poses, job table} -- that ONE pull kernel moves in front of a
-  // launch (launch_block_pull); the pointers below point into it
-  char *h_stage = nullptr, *d_stage = nullptr;
-  size_t stage_jobs_at = 0;
-  slamhip::HcJobView *h_jobs = nullptr, *d_jobs = nullptr;  // pinned staging / HBM
-  bool resident_call = false;  // resident_wanted() of the call in flight, asked once
-  double *h_inits = nullptr, *d_inits = nullptr;
-  double *h_scan = nullptr, *d_scan = nullptr;  // the batch's scans: per match five arrays of its beam count
-  size_t scan_cap = 0;                     // doubles
-  slamhip::HcShape *d_shapes = nullptr;
-  int built_inst = 0, max_inst = 1, nt = 256;
-  bool pair = false;  // the co-resident launch's workgroups (512 threads) score two poses per super-step
-  int cus = 0;        // CUs of the device (sizes the pair form's trees)
-  int shape_n_inst[slamhip::kHcShapes] = {0};
-  unsigned *d_n_done = nullptr, *h_done_count = nullptr;
-  slamhip::HcResidentCtl *d_rctl = nullptr;  // co-resident form: one exchange block per chain (cap of them)
-  unsigned *h_all_done = nullptr;            // pinned: the last chain to end stores the epoch here
-  int rctl_grid = 0, rctl_chains = 0;        // slots per chain / chains of the last co-resident launch
-  unsigned rctl_launches = 0;                // co-resident launches on d_rctl (hc_tag)
-  bool ran_resident = false;
-  slamhip::HcTraceEntry *h_trace = nullptr;  // pinned: cap x trace_per entries (observer attached only)
-  int trace_per = 0, trace_chains = 0;
-  unsigned epoch = 0;
-  double steps_avg = 16.0;
-  long long kernels = 0;
-  std::vector<BatchJobResult> res;
-};
-namespace {
-
-void hc_batch_free(slamhip_matcher *m) {
-  HcBatch *b = m->batch;
-  if (!b) return;
-  if (b->d_ctl) hipFree(b->d_ctl);
-  if (b->h_out) hipHostFree(b->h_out);
-  if (b->h_stage) hipHostFree(b->h_stage);
-  if (b->d_stage) hipFree(b->d_stage);
-  if (b->h_scan) hipHostFree(b->h_scan);
-  if (b->d_scan) hipFree(b->d_scan);
-  if (b->d_shapes) hipFree(b->d_shapes);
-  if (b->h_done_count) hipHostFree(b->h_done_count);
-  if (b->d_rctl) hipFree(b->d_rctl);
-  if (b->h_all_done) hipHostFree(b->h_all_done);
-  if (b->h_trace) hipHostFree(b->h_trace);
-  delete b;
-  m->batch = nullptr;
-}
 
 // the matcher-level conditions of chain_eligible (the per-scan ones are tested job by job)
 bool batch_chain_eligible(slamhip_matcher *m) {
@@ -644,11 +929,10 @@ constexpr int kBatchTracePer = 1 << 14;  // trace entries per chain (a longer ma
 
 int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
   slamhip_ctx *ctx = m->ctx;
-  const unsigned pinned = hipHostMallocMapped | hipHostMallocCoherent;
-  HcBatch *b = m->batch;
+  HcBatch *b = m->batch.get();
   if (!b->d_shapes) {
-    SLAMHIP_CHECK(hipMalloc(&b->d_shapes, sizeof(HcShape) * kHcShapes));
-    SLAMHIP_CHECK(hipHostMalloc(&b->h_done_count, sizeof(unsigned), pinned));
+    SLAMHIP_CHECK(b->d_shapes.alloc(kHcShapes));
+    SLAMHIP_CHECK(b->h_done_count.alloc(1, kPinnedCoherent));
   }
   {
     // Trees and workgroups.  Up to two chains: one pose per workgroup of 1024 / 512 threads (a lone chain's form).
@@ -664,70 +948,18 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
     // the sweep, the replay and the table are made once for two poses), but two workgroups per CU with a CU to spare
     // leave room for 20 instead of 21 round instances per chain at K = 8 and 10 instead of 10 at K = 16, where the
     // narrower workgroups' finer interleaving wins: pairs up to eight chains)
-    // (resident_wanted counts the matches towards its re-arm, so it is asked ONCE per call: the trees are sized
+    // (the policy counts the calls towards its re-arm, so it is asked ONCE per call: the trees are sized
     // for the form the call will run in)
-    b->resident_call = resident_wanted(m);
+    b->resident_call = hc_resident_asked(m);
     b->pair = n * (6 * want + 1) > 512 && n <= 8 && b->resident_call && m->cfg.sum_order != SLAMHIP_SUM_SEQUENTIAL;
     if (b->pair) want = std::min(kHcDefaultInst, std::max(1, (2 * (b->cus - 1) / n - 1) / 3));
-    if (want != b->built_inst) {
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      std::vector<HcShape> shapes(kHcShapes);
-      b->max_inst = 1;
-      for (int s = 0; s < kHcShapes; ++s) {
-        hc_build_shape(hc_bucket_rate(s), 1.0, 0.002, want, &shapes[s]);
-        b->shape_n_inst[s] = shapes[s].n_inst;
-        b->max_inst = std::max(b->max_inst, shapes[s].n_inst);
-      }
-      SLAMHIP_CHECK(hipMemcpy(b->d_shapes, shapes.data(), sizeof(HcShape) * kHcShapes, hipMemcpyHostToDevice));
-      b->built_inst = want;
-    }
-    const int total = n * (6 * b->max_inst + 1);
-    b->nt = total <= 256 ? 1024 : (total <= 512 ? 512 : 256);
-  }
-  if (n > b->cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (b->d_ctl) hipFree(b->d_ctl);
-    if (b->h_out) hipHostFree(b->h_out);
-    if (b->h_stage) hipHostFree(b->h_stage);
-    if (b->d_stage) hipFree(b->d_stage);
-    if (b->d_rctl) hipFree(b->d_rctl);
-    b->d_rctl = nullptr;
-    b->rctl_grid = b->rctl_chains = 0;
-    b->d_ctl = nullptr;
-    b->h_out = nullptr;
-    b->h_stage = b->d_stage = nullptr;
-    b->h_jobs = b->d_jobs = nullptr;
-    b->h_inits = b->d_inits = nullptr;
-    b->d_n_done = nullptr;
-    int cap = 8;
-    while (cap < n) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&b->d_ctl, sizeof(HcChainCtl) * cap));
-    SLAMHIP_CHECK(hipMemsetAsync(b->d_ctl, 0, sizeof(HcChainCtl) * cap, ctx->stream));
-    SLAMHIP_CHECK(hipHostMalloc(&b->h_out, sizeof(HcHostOut) * cap, pinned));
-    std::memset(b->h_out, 0, sizeof(HcHostOut) * cap);
-    {
-      // [0, 16): the chains-done counter; then the initial poses; then the job table (a pull copies the front of the
-      // block up to the last job in use)
-      b->stage_jobs_at = 16 + ((sizeof(double) * 3 * (size_t)cap + 15) & ~(size_t)15);
-      const size_t bytes = b->stage_jobs_at + ((sizeof(HcJobView) * (size_t)cap + 15) & ~(size_t)15);
-      SLAMHIP_CHECK(hipHostMalloc(&b->h_stage, bytes, hipHostMallocMapped));
-      std::memset(b->h_stage, 0, bytes);
-      SLAMHIP_CHECK(hipMalloc(&b->d_stage, bytes));
-      SLAMHIP_CHECK(hipMemsetAsync(b->d_stage, 0, bytes, ctx->stream));
-      b->d_n_done = reinterpret_cast<unsigned *>(b->d_stage);
-      b->h_inits = reinterpret_cast<double *>(b->h_stage + 16);
-      b->d_inits = reinterpret_cast<double *>(b->d_stage + 16);
-      b->h_jobs = reinterpret_cast<HcJobView *>(b->h_stage + b->stage_jobs_at);
-      b->d_jobs = reinterpret_cast<HcJobView *>(b->d_stage + b->stage_jobs_at);
-    }
-    b->cap = cap;
+    const int rc = many_chains_prepare(ctx, *b, n, want, 0.002, 8);
+    if (rc) return rc;
   }
   if (m->has_obs && b->trace_chains < b->cap) {
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (b->h_trace) hipHostFree(b->h_trace);
-    b->h_trace = nullptr;
     b->trace_per = kBatchTracePer;
-    SLAMHIP_CHECK(hipHostMalloc(&b->h_trace, sizeof(HcTraceEntry) * (size_t)b->trace_per * b->cap, pinned));
+    SLAMHIP_CHECK(b->h_trace.alloc((size_t)b->trace_per * b->cap, kPinnedCoherent));
     b->trace_chains = b->cap;
   }
   // ---- the batch's scans: stored scans are read where they lie; scans handed over as host arrays go into one
@@ -742,13 +974,10 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
   }
   if (doubles > b->scan_cap) {
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (b->h_scan) hipHostFree(b->h_scan);
-    if (b->d_scan) hipFree(b->d_scan);
-    b->h_scan = b->d_scan = nullptr;
     size_t cap = 1 << 14;
     while (cap < doubles) cap *= 2;
-    SLAMHIP_CHECK(hipHostMalloc(&b->h_scan, sizeof(double) * cap, hipHostMallocDefault));
-    SLAMHIP_CHECK(hipMalloc(&b->d_scan, sizeof(double) * cap));
+    SLAMHIP_CHECK(b->h_scan.alloc(cap, hipHostMallocDefault));
+    SLAMHIP_CHECK(b->d_scan.alloc(cap));
     b->scan_cap = cap;
   }
   int cell_model = -1;
@@ -760,7 +989,7 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
     if (dm->cell_model == SLAMHIP_CELL_GMAPPING) return invalid_arg("the batch form covers the 1-cell OOPE (OCC / TBM cells)");
     if (cell_model >= 0 && dm->cell_model != cell_model) return invalid_arg("the maps of one batch must share a cell model");
     cell_model = dm->cell_model;
-    HcJobView &v = b->h_jobs[c];
+    HcJobView &v = b->stage.h_table()[c];
     v.map.payload = dm->d_payload;
     v.map.width = dm->width;
     v.map.height = dm->height;
@@ -780,7 +1009,7 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
       v.scan.tot_w = sl.tot_w;
     } else {
       stride = (size_t)((j.n + 7) & ~7);
-      double *hs = b->h_scan + at;
+      double *hs = b->h_scan.get() + at;
       const size_t bytes = sizeof(double) * (size_t)j.n;
       std::memcpy(hs, j.range, bytes);
       std::memcpy(hs + stride, j.cos_a, bytes);
@@ -790,7 +1019,7 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
       else for (int i = 0; i < j.n; ++i) hs[4 * stride + i] = 1.0;
       double tot_w = 0;  // in beam order, pose independent (weighted_mean_point_probability_spe.h:125)
       for (int i = 0; i < j.n; ++i) tot_w += j.weight[i];
-      ds = b->d_scan + at;
+      ds = b->d_scan.get() + at;
       v.scan.n = j.n;
       v.scan.tot_w = tot_w;
       at += 5 * stride;
@@ -800,190 +1029,70 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
     v.scan.sin_a = ds + 2 * stride;
     v.scan.weight = ds + 3 * stride;
     v.scan.factor = ds + 4 * stride;
-    for (int q = 0; q < 3; ++q) b->h_inits[3 * c + q] = j.init_pose[q];
+    for (int q = 0; q < 3; ++q) b->stage.h_inits()[3 * c + q] = j.init_pose[q];
   }
   hipStream_t st = ctx->stream;
-  if (at) SLAMHIP_CHECK(hipMemcpyAsync(b->d_scan, b->h_scan, sizeof(double) * at, hipMemcpyHostToDevice, st));
+  if (at) SLAMHIP_CHECK(hipMemcpyAsync(b->d_scan.get(), b->h_scan.get(), sizeof(double) * at, hipMemcpyHostToDevice, st));
   // (counter = 0, initial poses, job table: one pull of the pinned block)
-  SLAMHIP_CHECK(launch_block_pull(b->h_stage, b->d_stage, b->stage_jobs_at + sizeof(HcJobView) * (size_t)n, st));
+  SLAMHIP_CHECK(launch_block_pull(b->stage.h.get(), b->stage.d.get(), b->stage.bytes_upto_table(n), st));
   HcChainArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.jobs = b->d_jobs;
+  a.jobs = b->stage.d_table();
   a.scan.n = max_n;  // (the launch's LDS size)
   a.oie = m->cfg.oie;
-  a.max_inst = b->max_inst;
   a.gm_cx = a.gm_cy = -1;
   a.gm_prob = -1.0;
   a.verify = tie_check_default(m) ? 1 : 0;
   a.inert_tail = ctx->inert_tail;
-  a.ctl = b->d_ctl;
-  a.inits = b->d_inits;
-  a.n_done = b->d_n_done;
-  a.stamps = m->d_stamps;  // (debugging: chain 0's workgroup 1)
-  a.shapes = b->d_shapes;
-  for (int s = 0; s < kHcShapes; ++s) a.n_inst |= (unsigned long long)(b->shape_n_inst[s] & 0xff) << (8 * s);
-  a.dt0 = m->hc_dt;
-  a.dr0 = m->hc_dr;
-  a.max_failed = m->hc_max_failed;
+  a.stamps = m->d_stamps.get();  // (debugging: chain 0's workgroup 1)
+  a.dt0 = m->hc.dt;
+  a.dr0 = m->hc.dr;
+  a.max_failed = m->hc.max_failed;
   a.shape0 = hc_bucket_of(m->p_accept0);
-  unsigned epoch = ++b->epoch;
-  if (epoch == 0) epoch = ++b->epoch;
-  a.epoch = epoch;
-  a.host = b->h_out;
-  a.trace = m->has_obs ? b->h_trace : nullptr;
+  a.trace = m->has_obs ? b->h_trace.get() : nullptr;
   a.trace_cap = m->has_obs ? b->trace_per : 0;
   a.trace_stride = b->trace_per;
   if (m->has_obs && m->debug_trace_cap > 0) a.trace_cap = std::min(a.trace_cap, m->debug_trace_cap);
-  for (int c = 0; c < n; ++c) {
-    ((volatile HcHostOut *)b->h_out)[c].error = 0;
-    ((volatile HcHostOut *)b->h_out)[c].progress = 0;
-    ((volatile HcHostOut *)b->h_out)[c].tail_calls = 0;
-  }
+  many_chains_args(*b, n, a);
   m->tail_calls = 0;
-  int launched = 0;
-  // ---- ONE launch for the whole batch (hc_resident.hip) when all chains' workgroups fit the device at once: the
-  // chains then advance independently -- no chain waits at a kernel boundary for the slowest one of its super-step
-  b->ran_resident = false;
-  if (b->resident_call && !a.seq) {
-    int cap_wgs = 0, per_cu = 0;
-    const int res_nt = b->pair ? 512 : b->nt;
-    const int res_wgs = n * (b->pair ? 3 * b->max_inst + 1 : 6 * b->max_inst + 1);
-    int rc0 = resident_capacity_pick(m, cell_model, res_nt, b->pair ? 4 : 1, max_n, b->max_inst, res_wgs, true,
-                                     &a.lds_consts, &cap_wgs, &per_cu);
-    if (rc0) return rc0;
-    ResidentLease lease;  // (the device's resident slots may be another context's: the kernel chains at once then)
-    if (res_wgs <= cap_wgs && lease.take(m->device, res_wgs, per_cu)) {
-      a.pair = b->pair ? 1 : 0;
-      const double t_res0 = MatchJob::now_us();
-      a.spin_limit = spin_limit_for(m->resident_us_max);
-      if (!b->d_rctl) {
-        SLAMHIP_CHECK(hipMalloc(&b->d_rctl, sizeof(HcResidentCtl) * b->cap));
-        SLAMHIP_CHECK(hipMemsetAsync(b->d_rctl, 0, sizeof(HcResidentCtl) * b->cap, st));  // (ordered with the launch)
-      }
-      if (!b->h_all_done) {
-        SLAMHIP_CHECK(hipHostMalloc(&b->h_all_done, sizeof(unsigned), pinned));
-        *b->h_all_done = 0;
-      }
-      // a launch with more slots per chain than the one before meets granules no workgroup has cleared since an
-      // older launch of that size: clear the block (queued in front of the launch)
-      if (6 * b->max_inst + 1 > b->rctl_grid || n > b->rctl_chains)
-        SLAMHIP_CHECK(hipMemsetAsync(b->d_rctl, 0, sizeof(HcResidentCtl) * b->cap, st));
-      b->rctl_grid = 6 * b->max_inst + 1;
-      b->rctl_chains = n;
-      a.rctl = b->d_rctl;
-      a.tag_epoch = ++b->rctl_launches;
-      a.h_all_done = b->h_all_done;
-      a.debug_mute = m->debug_resident_mute;
-      hipEvent_t e0, e1;
-      rc0 = profile_event_pair(ctx, &e0, &e1);
-      if (rc0) return rc0;
-      SLAMHIP_CHECK(launch_hc_chain_resident(a, cell_model, res_nt, st, e0, e1, n));
-      launched = 1;
-      ++m->resident_matches;
-      volatile unsigned *all_done = b->h_all_done;
-      unsigned long long spins = 0;
-      bool gave_up = false;
-      for (;;) {
-        if (*all_done == epoch) break;
-        __builtin_ia32_pause();
-        if ((++spins & 0xffffull) == 0) {
-          // a chain that gave up publishes its own done_seq with error 4 / 5 and never counts as ended
-          for (int c = 0; c < n && !gave_up; ++c) {
-            const volatile HcHostOut *hc = &b->h_out[c];
-            gave_up = hc->done_seq == epoch && (hc->error == 4 || hc->error == 5);
-          }
-          if (gave_up) break;
-          hipError_t qe = hipStreamQuery(st);
-          if (qe == hipSuccess && *all_done != epoch) {
-            gave_up = true;  // (every workgroup has left and the batch is not through: treated like a give-up)
-            break;
-          }
-          if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, "co-resident hill-climbing chains");
-        }
-      }
-      if (gave_up) {
-        // nothing of this batch has been reported: wait for the stragglers, then the kernel chains redo it
-        SLAMHIP_CHECK(hipStreamSynchronize(st));
-        ++m->resident_gave_up_row;
-        ++m->resident_gave_up;
-        SLAMHIP_CHECK(hipMemsetAsync(b->d_n_done, 0, sizeof(unsigned), st));
-        for (int c = 0; c < n; ++c) ((volatile HcHostOut *)b->h_out)[c].error = 0;
-        a.rctl = nullptr;
-        a.h_all_done = nullptr;
-        a.debug_mute = 0;
-        launched = 0;
-        epoch = ++b->epoch;
-        if (epoch == 0) epoch = ++b->epoch;
-        a.epoch = epoch;
-      } else {
-        m->resident_gave_up_row = 0;
-        b->ran_resident = true;
-        note_resident_time(&m->resident_us_max, MatchJob::now_us() - t_res0);
-      }
-    }
-  }
-  auto burst = [&](int count, unsigned *seq_out) -> int {
-    for (int i = 0; i < count; ++i) {
-      hipEvent_t e0, e1;
-      int r = profile_event_pair(ctx, &e0, &e1);
-      if (r) return r;
-      SLAMHIP_CHECK(launch_hc_chain_step(a, cell_model, launched, b->nt, st, e0, e1, n));
-      ++launched;
-    }
-    unsigned seq = ++ctx->seq;
-    if (seq == 0) seq = ++ctx->seq;
-    SLAMHIP_CHECK(launch_chain_marker(b->d_n_done, b->h_done_count, ctx->h_done_flag, seq, st));
-    *seq_out = seq;
-    return SLAMHIP_OK;
-  };
-  unsigned seq_prev = 0, seq_next = 0;
-  int rc = SLAMHIP_OK;
-  if (!b->ran_resident) rc = burst(std::max(3, (int)(b->steps_avg * 0.9)), &seq_prev);
-  if (rc) return rc;
-  while (!b->ran_resident) {
-    rc = burst(3, &seq_next);  // queued before the wait: the GPU never runs dry
-    if (rc) return rc;
-    rc = score_wait(ctx, seq_prev);
-    if (rc) return rc;
-    if (*(volatile unsigned *)b->h_done_count >= (unsigned)n) break;
-    if (launched >= (1 << 16)) {
-      set_error("the batch's hill-climbing chains did not end");
-      return SLAMHIP_ERR_STATE;
-    }
-    seq_prev = seq_next;
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  int max_steps = 0;
+  const int res_nt = b->pair ? 512 : b->nt;
+  const int res_wgs = n * (b->pair ? 3 * b->shapes.max_inst + 1 : 6 * b->shapes.max_inst + 1);
   long long units = 0;
-  for (int c = 0; c < n; ++c) {
-    const volatile HcHostOut *h = &b->h_out[c];
-    if (h->done_seq != epoch) {
-      set_error("internal: a chain was counted as finished without publishing its result");
-      return SLAMHIP_ERR_STATE;
-    }
-    if (h->error == 1) {
-      set_error("internal: the device replay found no terminal round (hill-climbing chain bug)");
-      return SLAMHIP_ERR_STATE;
-    }
-    BatchJobResult &r = b->res[c];
-    r.error = h->error;
-    r.on_chain = h->error == 0;
-    for (int q = 0; q < 3; ++q) r.pose[q] = h->pose[q];
-    r.prob = h->best_prob;
-    r.calls = h->calls;
-    r.evaluated = h->evaluated;
-    r.rescored = h->rescored;
-    r.steps = h->steps;
-    m->tail_calls += h->tail_calls;
-    max_steps = std::max(max_steps, (int)h->steps);
-    units += h->evaluated * (long long)beams_of(jobs[c]);
-  }
-  b->steps_avg = 0.75 * b->steps_avg + 0.25 * (double)max_steps;
+  bool ran_resident = false;
+  int launched = 0;
+  const int rc = run_many_chains(
+      ctx, m->resident, *b, a, n, b->resident_call && !a.seq, 0.9, &ran_resident, &launched,
+      [&](ResidentLease &lease, bool *fits) -> int {
+        int cap_wgs = 0, per_cu = 0;
+        const int r = resident_capacity_pick(m, cell_model, res_nt, b->pair ? 4 : 1, max_n, b->shapes.max_inst, res_wgs, true,
+                                             &a.lds_consts, &cap_wgs, &per_cu);
+        if (r) return r;
+        if (res_wgs <= cap_wgs && lease.take(m->device, res_wgs, per_cu)) {
+          a.pair = b->pair ? 1 : 0;
+          a.debug_mute = m->debug_resident_mute;
+          *fits = true;
+        }
+        return SLAMHIP_OK;
+      },
+      [&](hipEvent_t e0, hipEvent_t e1) { return launch_hc_chain_resident(a, cell_model, res_nt, st, e0, e1, n); },
+      [&](int step, hipEvent_t e0, hipEvent_t e1) { return launch_hc_chain_step(a, cell_model, step, b->nt, st, e0, e1, n); },
+      [&](int c, const volatile HcHostOut *h) {
+        BatchJobResult &r = b->res[c];
+        r.error = h->error;
+        r.on_chain = h->error == 0;
+        for (int q = 0; q < 3; ++q) r.pose[q] = h->pose[q];
+        r.prob = h->best_prob;
+        r.calls = h->calls;
+        r.evaluated = h->evaluated;
+        r.rescored = h->rescored;
+        r.steps = h->steps;
+        m->tail_calls += h->tail_calls;
+        units += h->evaluated * (long long)beams_of(jobs[c]);
+      },
+      ManyChainsText{"co-resident hill-climbing chains", "the batch's hill-climbing chains did not end"});
+  if (rc) return rc;
   b->kernels = launched;
-  if (ctx->profile) {
-    ctx->prof_launches += launched;
-    ctx->prof_units += units;
-  }
+  if (ctx->profile) ctx->prof_units += units;
   return SLAMHIP_OK;
 }
 
@@ -991,50 +1100,20 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
 
 namespace slamhip {
 
-struct GmMultiChain {
-  int cap = 0, device = 0;
-  HcChainCtl *d_ctl = nullptr;
-  HcShape *d_shapes = nullptr;
-  HcHostOut *h_out = nullptr;    // pinned, one per chain
-  double *h_inits = nullptr;     // pinned staging of the initial poses
-  double *d_inits = nullptr;
-  int *d_slots = nullptr;        // tile-pool slot of every chain (per-particle maps)
-  // {chains-done counter (0), initial poses, slots}: one pinned block, one pull kernel in front of a launch
-  char *h_stage = nullptr, *d_stage = nullptr;
-  size_t stage_slots_at = 0;
-  int *h_slots = nullptr;
-  HcResidentGmCtl *d_rctl = nullptr;  // co-resident form: one exchange block per chain
-  unsigned *h_all_done = nullptr;     // pinned: the last chain to end stores the epoch here
-  int rctl_grid = 0, rctl_chains = 0, gave_up_row = 0;
-  unsigned rctl_launches = 0;  // co-resident launches on d_rctl (hc_tag)
-  double resident_us_max = 0;  // the longest co-resident step seen (decaying): sizes the spin bound
-  int steps_since_off = 0;     // steps since the co-resident form switched itself off (re-arm)
-  unsigned *d_n_done = nullptr;
-  unsigned *h_done_count = nullptr;  // pinned
-  int shape_n_inst[kHcShapes] = {0};
-  int max_inst = 1, nt = 256, built_inst = 0;
-  unsigned epoch = 0;
-  double steps_avg = 14.0;
+// one chain per particle over the GMapping OOPE; the staging table holds the chains' tile-pool slots (per-particle maps)
+struct GmMultiChain : ChainSet<HcResidentGmCtl, int> {
+  GmMultiChain() : ChainSet(14.0) {}
+  int device = 0;
+  ResidentPolicy resident;  // (the filter's own: not a matcher's)
 };
 
 void gm_multi_chain_free(GmMultiChain *s) {
   if (!s) return;
   hipSetDevice(s->device);
   hipDeviceSynchronize();
-  if (s->d_rctl) hipFree(s->d_rctl);
-  if (s->h_all_done) hipHostFree(s->h_all_done);
-  if (s->d_ctl) hipFree(s->d_ctl);
-  if (s->d_shapes) hipFree(s->d_shapes);
-  if (s->h_out) hipHostFree(s->h_out);
-  if (s->h_stage) hipHostFree(s->h_stage);
-  if (s->d_stage) hipFree(s->d_stage);
-  if (s->h_done_count) hipHostFree(s->h_done_count);
   delete s;
 }
 
-// All chains advance one super-step per kernel (grid.y = chain); a chain that has ended leaves the launch at
-// once.  The host queues the kernels in bursts, each closed by a one-thread marker that reports how many chains
-// are through, and always has the next burst queued before it waits for a marker.
 // (the same sizing as gm_multi_chain_run's: one round instance per chain from 47 chains on, 256-thread workgroups)
 bool gm_multi_chain_fits_resident(slamhip_ctx *ctx, int n) {
   if (!ctx->resident_chains || n <= 0 || ctx->scan_n > 1280) return false;
@@ -1051,13 +1130,12 @@ int gm_multi_chain_run(slamhip_ctx *ctx, GmMultiChain **scratch, int map_id, con
                        long long *kernels_launched, const TiledTarget *tiled, const int *slots) {
   if (n <= 0) return SLAMHIP_OK;
   if (tiled && !slots) return SLAMHIP_ERR_INVALID;
-  const unsigned pinned = hipHostMallocMapped | hipHostMallocCoherent;
   if (!*scratch) {
     GmMultiChain *s = new GmMultiChain;
     s->device = ctx->device;
     *scratch = s;
-    SLAMHIP_CHECK(hipMalloc(&s->d_shapes, sizeof(HcShape) * kHcShapes));
-    SLAMHIP_CHECK(hipHostMalloc(&s->h_done_count, sizeof(unsigned), pinned));
+    SLAMHIP_CHECK(s->d_shapes.alloc(kHcShapes));
+    SLAMHIP_CHECK(s->h_done_count.alloc(1, kPinnedCoherent));
   }
   GmMultiChain *s = *scratch;
   {
@@ -1071,59 +1149,8 @@ int gm_multi_chain_run(slamhip_ctx *ctx, GmMultiChain **scratch, int map_id, con
     // for a 13-particle shard and 0.443 / 0.445 / 0.477 / 0.510 for 50 -- deeper trees cost more per pose than the
     // super-steps they save here too)
     constexpr int wgs = 280;
-    const int want = std::min(kHcDefaultInst, std::max(1, wgs / (6 * n)));
-    if (want != s->built_inst) {
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      std::vector<HcShape> shapes(kHcShapes);
-      const double reach = 0.01;
-      s->max_inst = 1;
-      for (int b = 0; b < kHcShapes; ++b) {
-        hc_build_shape(hc_bucket_rate(b), 1.0, reach, want, &shapes[b]);
-        s->shape_n_inst[b] = shapes[b].n_inst;
-        s->max_inst = std::max(s->max_inst, shapes[b].n_inst);
-      }
-      SLAMHIP_CHECK(hipMemcpy(s->d_shapes, shapes.data(), sizeof(HcShape) * kHcShapes, hipMemcpyHostToDevice));
-      s->built_inst = want;
-    }
-    const int total = n * (6 * s->max_inst + 1);
-    s->nt = total <= 256 ? 1024 : (total <= 512 ? 512 : 256);
-  }
-  if (n > s->cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (s->d_ctl) hipFree(s->d_ctl);
-    if (s->h_out) hipHostFree(s->h_out);
-    if (s->h_stage) hipHostFree(s->h_stage);
-    if (s->d_stage) hipFree(s->d_stage);
-    if (s->d_rctl) hipFree(s->d_rctl);
-    s->d_rctl = nullptr;
-    s->rctl_grid = s->rctl_chains = 0;
-    s->h_stage = s->d_stage = nullptr;
-    s->d_slots = s->h_slots = nullptr;
-    s->d_n_done = nullptr;
-    s->d_ctl = nullptr;
-    s->h_out = nullptr;
-    s->h_inits = nullptr;
-    s->d_inits = nullptr;
-    int cap = 16;
-    while (cap < n) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&s->d_ctl, sizeof(HcChainCtl) * cap));
-    SLAMHIP_CHECK(hipMemsetAsync(s->d_ctl, 0, sizeof(HcChainCtl) * cap, ctx->stream));
-    SLAMHIP_CHECK(hipHostMalloc(&s->h_out, sizeof(HcHostOut) * cap, pinned));
-    std::memset(s->h_out, 0, sizeof(HcHostOut) * cap);
-    {
-      s->stage_slots_at = 16 + ((sizeof(double) * 3 * (size_t)cap + 15) & ~(size_t)15);
-      const size_t bytes = s->stage_slots_at + ((sizeof(int) * (size_t)cap + 15) & ~(size_t)15);
-      SLAMHIP_CHECK(hipHostMalloc(&s->h_stage, bytes, hipHostMallocMapped));
-      std::memset(s->h_stage, 0, bytes);
-      SLAMHIP_CHECK(hipMalloc(&s->d_stage, bytes));
-      SLAMHIP_CHECK(hipMemsetAsync(s->d_stage, 0, bytes, ctx->stream));
-      s->d_n_done = reinterpret_cast<unsigned *>(s->d_stage);
-      s->h_inits = reinterpret_cast<double *>(s->h_stage + 16);
-      s->d_inits = reinterpret_cast<double *>(s->d_stage + 16);
-      s->h_slots = reinterpret_cast<int *>(s->h_stage + s->stage_slots_at);
-      s->d_slots = reinterpret_cast<int *>(s->d_stage + s->stage_slots_at);
-    }
-    s->cap = cap;
+    const int rc = many_chains_prepare(ctx, *s, n, std::min(kHcDefaultInst, std::max(1, wgs / (6 * n))), 0.01, 16);
+    if (rc) return rc;
   }
   HcChainArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1133,173 +1160,61 @@ int gm_multi_chain_run(slamhip_ctx *ctx, GmMultiChain **scratch, int map_id, con
   if (tiled) {
     a.tables = tiled->tables;
     a.table_stride = tiled->table_stride;
-    a.slots = s->d_slots;
-    std::memcpy(s->h_slots, slots, sizeof(int) * n);
+    a.slots = s->stage.d_table();
+    std::memcpy(s->stage.h_table(), slots, sizeof(int) * n);
   }
   a.oie = cfg->oie;
-  a.max_inst = s->max_inst;
   a.gm.fullness_th = cfg->gm_fullness_th;
   a.gm.window = cfg->gm_window;
   a.gm_cx = a.gm_cy = -1;  // every chain starts without a carry-in (the filter checks the hand-overs afterwards)
   a.gm_prob = -1.0;
-  a.ctl = s->d_ctl;
-  a.inits = s->d_inits;
-  a.n_done = s->d_n_done;
-  a.shapes = s->d_shapes;
-  for (int b = 0; b < kHcShapes; ++b) a.n_inst |= (unsigned long long)(s->shape_n_inst[b] & 0xff) << (8 * b);
   a.dt0 = dt;
   a.dr0 = dr;
   a.max_failed = max_failed;
   a.shape0 = hc_bucket_of(0.25);
-  unsigned epoch = ++s->epoch;
-  if (epoch == 0) epoch = ++s->epoch;
-  a.epoch = epoch;
-  a.host = s->h_out;
-  std::memcpy(s->h_inits, inits, sizeof(double) * 3 * n);
-  for (int c = 0; c < n; ++c) {
-    ((volatile HcHostOut *)s->h_out)[c].error = 0;
-    ((volatile HcHostOut *)s->h_out)[c].progress = 0;
-  }
+  many_chains_args(*s, n, a);
+  std::memcpy(s->stage.h_inits(), inits, sizeof(double) * 3 * n);
   // (counter = 0, initial poses, tile-pool slots: one pull of the pinned block)
-  SLAMHIP_CHECK(launch_block_pull(s->h_stage, s->d_stage,
-                                  tiled ? s->stage_slots_at + sizeof(int) * (size_t)n : 16 + sizeof(double) * 3 * (size_t)n,
-                                  ctx->stream));
-  int launched = 0;
+  SLAMHIP_CHECK(launch_block_pull(s->stage.h.get(), s->stage.d.get(),
+                                  tiled ? s->stage.bytes_upto_table(n) : s->stage.bytes_upto_inits(n), ctx->stream));
   // ---- ONE launch for all chains (hc_resident_gm.hip) when their workgroups fit the device at once: every
   // particle's chain then advances at its own pace instead of in lock-step launches
-  bool ran_resident = false;
-  if (s->gave_up_row >= 3 && ++s->steps_since_off >= kResidentRearmAfter) {
-    s->gave_up_row = 0;  // (re-armed)
-    s->steps_since_off = 0;
-  }
-  if (ctx->resident_chains && s->gave_up_row < 3 && a.scan.n <= 1280) {
-    int cap_wgs = 0, per_cu = 0;
-    SLAMHIP_CHECK(hc_resident_gm_capacity(s->nt, a.scan.n, &cap_wgs, &per_cu));
-    ResidentLease lease;
-    if (n * (6 * s->max_inst + 1) <= cap_wgs && lease.take(s->device, n * (6 * s->max_inst + 1), per_cu)) {
-      const double t_res0 = MatchJob::now_us();
-      a.spin_limit = spin_limit_for(s->resident_us_max);
-      if (!s->d_rctl) {
-        SLAMHIP_CHECK(hipMalloc(&s->d_rctl, sizeof(HcResidentGmCtl) * s->cap));
-        SLAMHIP_CHECK(hipMemsetAsync(s->d_rctl, 0, sizeof(HcResidentGmCtl) * s->cap, ctx->stream));
-      }
-      if (!s->h_all_done) {
-        SLAMHIP_CHECK(hipHostMalloc(&s->h_all_done, sizeof(unsigned), pinned));
-        *s->h_all_done = 0;
-      }
-      if (6 * s->max_inst + 1 > s->rctl_grid || n > s->rctl_chains)
-        SLAMHIP_CHECK(hipMemsetAsync(s->d_rctl, 0, sizeof(HcResidentGmCtl) * s->cap, ctx->stream));
-      s->rctl_grid = 6 * s->max_inst + 1;
-      s->rctl_chains = n;
-      a.rctl_gm = s->d_rctl;
-      a.tag_epoch = ++s->rctl_launches;
-      a.h_all_done = s->h_all_done;
-      hipEvent_t e0, e1;
-      rc = profile_event_pair(ctx, &e0, &e1);
-      if (rc) return rc;
-      SLAMHIP_CHECK(launch_hc_chain_resident_gm(a, s->nt, ctx->stream, e0, e1, n));
-      launched = 1;
-      volatile unsigned *all_done = s->h_all_done;
-      unsigned long long spins = 0;
-      bool gave_up = false;
-      for (;;) {
-        if (*all_done == epoch) break;
-        __builtin_ia32_pause();
-        if ((++spins & 0xffffull) == 0) {
-          for (int c = 0; c < n && !gave_up; ++c) {
-            const volatile HcHostOut *hc = &s->h_out[c];
-            gave_up = hc->done_seq == epoch && (hc->error == 4 || hc->error == 5);
-          }
-          if (gave_up) break;
-          hipError_t qe = hipStreamQuery(ctx->stream);
-          if (qe == hipSuccess && *all_done != epoch) {
-            gave_up = true;
-            break;
-          }
-          if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, "co-resident GMapping chains");
-        }
-      }
-      if (gave_up) {
-        SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-        ++s->gave_up_row;
-        SLAMHIP_CHECK(hipMemsetAsync(s->d_n_done, 0, sizeof(unsigned), ctx->stream));
-        for (int c = 0; c < n; ++c) ((volatile HcHostOut *)s->h_out)[c].error = 0;
-        a.rctl_gm = nullptr;
-        a.h_all_done = nullptr;
-        launched = 0;
-        epoch = ++s->epoch;
-        if (epoch == 0) epoch = ++s->epoch;
-        a.epoch = epoch;
-      } else {
-        s->gave_up_row = 0;
-        ran_resident = true;
-        note_resident_time(&s->resident_us_max, MatchJob::now_us() - t_res0);
-      }
-    }
-  }
-  auto burst = [&](int count, unsigned *seq_out) -> int {
-    for (int i = 0; i < count; ++i) {
-      hipEvent_t e0, e1;
-      int r = profile_event_pair(ctx, &e0, &e1);
-      if (r) return r;
-      SLAMHIP_CHECK(launch_hc_chain_step(a, cell_model, launched, s->nt, ctx->stream, e0, e1, n));
-      ++launched;
-    }
-    unsigned seq = ++ctx->seq;
-    if (seq == 0) seq = ++ctx->seq;
-    SLAMHIP_CHECK(launch_chain_marker(s->d_n_done, s->h_done_count, ctx->h_done_flag, seq, ctx->stream));
-    *seq_out = seq;
-    return SLAMHIP_OK;
-  };
-  unsigned seq_prev = 0, seq_next = 0;
-  if (!ran_resident) rc = burst(std::max(3, (int)(s->steps_avg * 0.8)), &seq_prev);
-  if (rc) return rc;
-  while (!ran_resident) {
-    rc = burst(3, &seq_next);  // queued before the wait: the GPU never runs dry
-    if (rc) return rc;
-    rc = score_wait(ctx, seq_prev);
-    if (rc) return rc;
-    if (*(volatile unsigned *)s->h_done_count >= (unsigned)n) break;
-    if (launched >= (1 << 16)) {
-      set_error("the filter's hill-climbing chains did not end");
-      return SLAMHIP_ERR_STATE;
-    }
-    seq_prev = seq_next;
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  int max_steps = 0;
+  const bool armed = s->resident.armed();
+  const int grid = n * (6 * s->shapes.max_inst + 1);
   long long evaluated = 0;
-  for (int c = 0; c < n; ++c) {
-    const volatile HcHostOut *h = &s->h_out[c];
-    if (h->done_seq != epoch) {
-      set_error("internal: a chain was counted as finished without publishing its result");
-      return SLAMHIP_ERR_STATE;
-    }
-    GmChainResult &r = out[c];
-    r.error = h->error;
-    if (h->error == 1) {
-      set_error("internal: the device replay found no terminal round (hill-climbing chain bug)");
-      return SLAMHIP_ERR_STATE;
-    }
-    for (int k = 0; k < 3; ++k) r.pose[k] = h->pose[k];
-    r.prob = h->best_prob;
-    r.calls = h->calls;
-    r.evaluated = h->evaluated;
-    r.steps = h->steps;
-    r.cx = h->gm_cx;
-    r.cy = h->gm_cy;
-    r.cprob = h->gm_prob;
-    std::memcpy(&r.first_info, const_cast<const GmPoseInfo *>(&h->first_info), sizeof(GmPoseInfo));
-    r.first_raw = h->first_raw;
-    max_steps = std::max(max_steps, (int)h->steps);
-    evaluated += h->evaluated;
-  }
-  s->steps_avg = 0.75 * s->steps_avg + 0.25 * (double)max_steps;
+  bool ran_resident = false;
+  int launched = 0;
+  rc = run_many_chains(
+      ctx, s->resident, *s, a, n, ctx->resident_chains && armed && a.scan.n <= 1280, 0.8, &ran_resident, &launched,
+      [&](ResidentLease &lease, bool *fits) -> int {
+        int cap_wgs = 0, per_cu = 0;
+        SLAMHIP_CHECK(hc_resident_gm_capacity(s->nt, a.scan.n, &cap_wgs, &per_cu));
+        *fits = grid <= cap_wgs && lease.take(s->device, grid, per_cu);
+        return SLAMHIP_OK;
+      },
+      [&](hipEvent_t e0, hipEvent_t e1) { return launch_hc_chain_resident_gm(a, s->nt, ctx->stream, e0, e1, n); },
+      [&](int step, hipEvent_t e0, hipEvent_t e1) {
+        return launch_hc_chain_step(a, cell_model, step, s->nt, ctx->stream, e0, e1, n);
+      },
+      [&](int c, const volatile HcHostOut *h) {
+        GmChainResult &r = out[c];
+        r.error = h->error;
+        for (int k = 0; k < 3; ++k) r.pose[k] = h->pose[k];
+        r.prob = h->best_prob;
+        r.calls = h->calls;
+        r.evaluated = h->evaluated;
+        r.steps = h->steps;
+        r.cx = h->gm_cx;
+        r.cy = h->gm_cy;
+        r.cprob = h->gm_prob;
+        std::memcpy(&r.first_info, const_cast<const GmPoseInfo *>(&h->first_info), sizeof(GmPoseInfo));
+        r.first_raw = h->first_raw;
+        evaluated += h->evaluated;
+      },
+      ManyChainsText{"co-resident GMapping chains", "the filter's hill-climbing chains did not end"});
+  if (rc) return rc;
   if (kernels_launched) *kernels_launched = launched;
-  if (ctx->profile) {
-    ctx->prof_launches += launched;
-    ctx->prof_units += evaluated * (long long)a.scan.n;
-  }
+  if (ctx->profile) ctx->prof_units += evaluated * (long long)a.scan.n;
   return SLAMHIP_OK;
 }
 
@@ -1322,10 +1237,11 @@ bool bf_device_eligible(slamhip_matcher *m) {
 int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
                            double *out_prob) {
   slamhip_ctx *ctx = m->ctx;
-  if (m->bf_off.empty()) {
+  slamhip_matcher::BfSweep &bf = m->bf;
+  if (bf.off.empty()) {
     // the enumerator's offsets, made by ITS additions (feedback(): x fastest, then y, then theta; each axis
     // accumulates `+= step` from `from` while the value is still below `to`; theta while t <= to)
-    const double *r = m->bf_r;
+    const double *r = bf.r;
     std::vector<double> xs, ys, ts;
     for (double x = r[0];; x += r[2]) {
       xs.push_back(x);
@@ -1337,46 +1253,37 @@ int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pos
     }
     for (double t = r[6]; t <= r[7] && ts.size() <= (1u << 22); t += r[8]) ts.push_back(t);
     if (xs.size() > (1u << 22) || ys.size() > (1u << 22) || ts.size() > (1u << 22)) return kChainNeedsHost;
-    m->bf_nx = (int)xs.size();
-    m->bf_ny = (int)ys.size();
-    m->bf_nt = (int)ts.size();
-    m->bf_off = xs;
-    m->bf_off.insert(m->bf_off.end(), ys.begin(), ys.end());
-    m->bf_off.insert(m->bf_off.end(), ts.begin(), ts.end());
-    if (m->bf_off.empty()) m->bf_off.push_back(0.0);
-    SLAMHIP_CHECK(hipMalloc(&m->d_bf_off, sizeof(double) * m->bf_off.size()));
-    SLAMHIP_CHECK(hipMemcpyAsync(m->d_bf_off, m->bf_off.data(), sizeof(double) * m->bf_off.size(), hipMemcpyHostToDevice,
+    bf.nx = (int)xs.size();
+    bf.ny = (int)ys.size();
+    bf.nt = (int)ts.size();
+    bf.off = xs;
+    bf.off.insert(bf.off.end(), ys.begin(), ys.end());
+    bf.off.insert(bf.off.end(), ts.begin(), ts.end());
+    if (bf.off.empty()) bf.off.push_back(0.0);
+    SLAMHIP_CHECK(bf.d_off.alloc(bf.off.size()));
+    SLAMHIP_CHECK(hipMemcpyAsync(bf.d_off.get(), bf.off.data(), sizeof(double) * bf.off.size(), hipMemcpyHostToDevice,
                                  ctx->stream));
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    SLAMHIP_CHECK(hipHostMalloc(&m->h_bf, sizeof(BfHostOut), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(m->h_bf, 0, sizeof(BfHostOut));
+    SLAMHIP_CHECK(bf.h_out.alloc(1, kPinnedCoherent));
+    std::memset(bf.h_out.get(), 0, sizeof(BfHostOut));
   }
-  const long long n = 1 + (long long)m->bf_nx * m->bf_ny * m->bf_nt;
+  const long long n = 1 + (long long)bf.nx * bf.ny * bf.nt;
   if (n > (1ll << 26)) return kChainNeedsHost;
-  if (n > m->bf_cap) {
+  if (n > bf.cap) {
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (m->d_bf_poses) hipFree(m->d_bf_poses);
-    if (m->d_bf_scores) hipFree(m->d_bf_scores);
-    if (m->d_bf_fp) hipFree(m->d_bf_fp);
-    if (m->d_bf_pidx) hipFree(m->d_bf_pidx);
-    if (m->d_bf_agg_i) hipFree(m->d_bf_agg_i);
-    if (m->d_bf_agg_s) hipFree(m->d_bf_agg_s);
-    m->d_bf_poses = m->d_bf_scores = m->d_bf_agg_s = nullptr;
-    m->d_bf_fp = nullptr;
-    m->d_bf_pidx = m->d_bf_agg_i = nullptr;
-    m->bf_cap = 0;
+    bf.cap = 0;
     const long long blocks = (n + 1023) / 1024;
-    SLAMHIP_CHECK(hipMalloc(&m->d_bf_poses, sizeof(double) * 3 * n));
-    SLAMHIP_CHECK(hipMalloc(&m->d_bf_scores, sizeof(double) * n));
-    SLAMHIP_CHECK(hipMalloc(&m->d_bf_fp, sizeof(unsigned long long) * n));
-    SLAMHIP_CHECK(hipMalloc(&m->d_bf_pidx, sizeof(long long) * n));
-    SLAMHIP_CHECK(hipMalloc(&m->d_bf_agg_s, sizeof(double) * blocks));
-    SLAMHIP_CHECK(hipMalloc(&m->d_bf_agg_i, sizeof(long long) * blocks));
-    if (!m->d_bf_counters) {
-      SLAMHIP_CHECK(hipMalloc(&m->d_bf_counters, sizeof(unsigned) * 4));
-      SLAMHIP_CHECK(hipMemsetAsync(m->d_bf_counters, 0, sizeof(unsigned) * 4, ctx->stream));
+    SLAMHIP_CHECK(bf.d_poses.alloc(3 * n));
+    SLAMHIP_CHECK(bf.d_scores.alloc(n));
+    SLAMHIP_CHECK(bf.d_fp.alloc(n));
+    SLAMHIP_CHECK(bf.d_pidx.alloc(n));
+    SLAMHIP_CHECK(bf.d_agg_s.alloc(blocks));
+    SLAMHIP_CHECK(bf.d_agg_i.alloc(blocks));
+    if (!bf.d_counters) {
+      SLAMHIP_CHECK(bf.d_counters.alloc(4));
+      SLAMHIP_CHECK(hipMemsetAsync(bf.d_counters.get(), 0, sizeof(unsigned) * 4, ctx->stream));
     }
-    m->bf_cap = n;
+    bf.cap = n;
   }
   ScoreArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1395,46 +1302,45 @@ int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pos
     pa.init[k] = init_pose[k];
     pa.base[k] = base3[k];
   }
-  pa.off = m->d_bf_off;
-  pa.nx = m->bf_nx;
-  pa.ny = m->bf_ny;
-  pa.nt = m->bf_nt;
+  pa.off = bf.d_off.get();
+  pa.nx = bf.nx;
+  pa.ny = bf.ny;
+  pa.nt = bf.nt;
   pa.n = n;
-  pa.poses = m->d_bf_poses;
+  pa.poses = bf.d_poses.get();
   SLAMHIP_CHECK(launch_bf_poses(pa, ctx->stream));
-  a.poses = m->d_bf_poses;
-  a.scores = m->d_bf_scores;
+  a.poses = bf.d_poses.get();
+  a.scores = bf.d_scores.get();
   a.n_poses = (int)n;
   a.oie = oie_eff;
   for (int k = 0; k < 4; ++k) a.area[k] = m->cfg.area[k];
   a.gm.fullness_th = m->cfg.gm_fullness_th;
   a.gm.window = m->cfg.gm_window;
-  a.fprints = verify ? m->d_bf_fp : nullptr;
+  a.fprints = verify ? bf.d_fp.get() : nullptr;
   hipEvent_t e0, e1;
   rc = profile_event_pair(ctx, &e0, &e1);
   if (rc) return rc;
   SLAMHIP_CHECK(launch_score(a, cell_model, m->cfg.oope, m->cfg.sum_order, ctx->stream, e0, e1));
-  unsigned seq = ++m->bf_seq;
-  if (seq == 0) seq = ++m->bf_seq;
+  const unsigned seq = next_epoch(bf.seq);
   BfArgmaxArgs ga;
-  ga.scores = m->d_bf_scores;
-  ga.fprints = verify ? m->d_bf_fp : nullptr;
+  ga.scores = bf.d_scores.get();
+  ga.fprints = verify ? bf.d_fp.get() : nullptr;
   ga.n = n;
   ga.verify = verify ? 1 : 0;
-  ga.out = m->h_bf;
+  ga.out = bf.h_out.get();
   ga.seq = seq;
-  ga.pidx = m->d_bf_pidx;
-  ga.agg_s = m->d_bf_agg_s;
-  ga.agg_i = m->d_bf_agg_i;
-  ga.counters = m->d_bf_counters;
+  ga.pidx = bf.d_pidx.get();
+  ga.agg_s = bf.d_agg_s.get();
+  ga.agg_i = bf.d_agg_i.get();
+  ga.counters = bf.d_counters.get();
   if (n < 2) return kChainNeedsHost;  // (no candidate at all: nothing for the sweep to do)
   SLAMHIP_CHECK(launch_bf_argmax(ga, ctx->stream));
   if (m->has_obs) {
-    m->bf_scores_host.resize((size_t)n);
-    SLAMHIP_CHECK(hipMemcpyAsync(m->bf_scores_host.data(), m->d_bf_scores, sizeof(double) * n, hipMemcpyDeviceToHost,
+    bf.scores_host.resize((size_t)n);
+    SLAMHIP_CHECK(hipMemcpyAsync(bf.scores_host.data(), bf.d_scores.get(), sizeof(double) * n, hipMemcpyDeviceToHost,
                                  ctx->stream));
   }
-  volatile BfHostOut *h = m->h_bf;
+  volatile BfHostOut *h = bf.h_out.get();
   unsigned long long spins = 0;
   while (h->seq != seq) {
     __builtin_ia32_pause();
@@ -1456,12 +1362,12 @@ int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pos
     p3[2] = init_pose[2];
     if (i > 0) {
       const long long j = i - 1;
-      const int ix = (int)(j % m->bf_nx);
-      const long long r = j / m->bf_nx;
-      const int iy = (int)(r % m->bf_ny), it = (int)(r / m->bf_ny);
-      p3[0] = base3[0] + m->bf_off[ix];
-      p3[1] = base3[1] + m->bf_off[m->bf_nx + iy];
-      p3[2] = base3[2] + m->bf_off[m->bf_nx + m->bf_ny + it];
+      const int ix = (int)(j % bf.nx);
+      const long long r = j / bf.nx;
+      const int iy = (int)(r % bf.ny), it = (int)(r / bf.ny);
+      p3[0] = base3[0] + bf.off[ix];
+      p3[1] = base3[1] + bf.off[bf.nx + iy];
+      p3[2] = base3[2] + bf.off[bf.nx + bf.ny + it];
     }
   };
   double best[3];
@@ -1481,7 +1387,7 @@ int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pos
   if (m->has_obs) {
     // the observer's events in the reference's order, from the score array (:43-46, :53-60)
     const double t1 = MatchJob::now_us();
-    const double *sc = m->bf_scores_host.data();
+    const double *sc = bf.scores_host.data();
     double b = sc[0];
     double p3[3];
     pose_of(0, p3);
@@ -1516,19 +1422,19 @@ bool mc_chain_eligible(slamhip_matcher *m) {
 int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
                           double *out_prob) {
   slamhip_ctx *ctx = m->ctx;
+  slamhip_matcher::McChain &mc = m->mc;
   auto *pe = static_cast<GaussianPoseEnumerator *>(m->pe.get());
-  const unsigned pinned = hipHostMallocMapped | hipHostMallocCoherent;
-  if (!m->d_mc) {
-    SLAMHIP_CHECK(hipMalloc(&m->d_mc, sizeof(McChainCtl)));
-    SLAMHIP_CHECK(hipMemsetAsync(m->d_mc, 0, sizeof(McChainCtl), ctx->stream));
-    SLAMHIP_CHECK(hipHostMalloc(&m->h_mc, sizeof(McHostOut), pinned));
-    std::memset(m->h_mc, 0, sizeof(McHostOut));
+  if (!mc.d_mc) {
+    SLAMHIP_CHECK(mc.d_mc.alloc(1));
+    SLAMHIP_CHECK(hipMemsetAsync(mc.d_mc.get(), 0, sizeof(McChainCtl), ctx->stream));
+    SLAMHIP_CHECK(mc.h_mc.alloc(1, kPinnedCoherent));
+    std::memset(mc.h_mc.get(), 0, sizeof(McHostOut));
   }
   // 511 candidates per super-step in workgroups of 512 threads (with the bookkeeping workgroup two on EVERY CU): a
   // Monte-Carlo chain is a long run of rejections, so the larger tree pays (r03: 384 x 512 threads against 252 x 1024,
   // 16 super-steps of 7.2 us against 21 of 6.5; r05: 511 against 384, mc_chain_device.h).  slamhip_matcher_set_batch
   // caps it (at least 64: mc_chain_eligible).
-  m->mc_slots = std::min(kMcSlots, m->max_batch);
+  mc.slots = std::min(kMcSlots, m->max_batch);
   McChainArgs a;
   std::memset(&a, 0, sizeof(a));
   int cell_model = 0, oie_eff = m->cfg.oie;
@@ -1546,72 +1452,64 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
   // so a match in steady state starts without touching the tape.  The window is restarted when it runs out.
   const double t0 = MatchJob::now_us();
   const size_t pos = pe->tape_pos();
-  if (!m->tape_stream) {
-    SLAMHIP_CHECK(hipStreamCreateWithFlags(&m->tape_stream, hipStreamNonBlocking));
-    SLAMHIP_CHECK(hipEventCreateWithFlags(&m->tape_ready, hipEventDisableTiming));
+  if (!mc.tape_stream) {
+    SLAMHIP_CHECK(hipStreamCreateWithFlags(&mc.tape_stream, hipStreamNonBlocking));
+    SLAMHIP_CHECK(hipEventCreateWithFlags(&mc.tape_ready, hipEventDisableTiming));
   }
   auto upload_upto = [&](size_t abs_end) -> int {  // pairs [tape_base + tape_filled, abs_end) -> HBM, asynchronously
-    const size_t have = m->tape_base + m->tape_filled;
+    const size_t have = mc.tape_base + mc.tape_filled;
     if (abs_end <= have) return SLAMHIP_OK;
     const size_t cnt = abs_end - have;
-    double *dst = m->h_tape + 2 * m->tape_filled;
+    double *dst = mc.h_tape.get() + 2 * mc.tape_filled;
     pe->copy_tape_abs(have, cnt, dst);
-    SLAMHIP_CHECK(hipMemcpyAsync(m->d_tape + m->tape_filled, dst, sizeof(McPair) * cnt, hipMemcpyHostToDevice,
-                                 m->tape_stream));
-    SLAMHIP_CHECK(hipEventRecord(m->tape_ready, m->tape_stream));
-    m->tape_filled += cnt;
+    SLAMHIP_CHECK(hipMemcpyAsync(mc.d_tape.get() + mc.tape_filled, dst, sizeof(McPair) * cnt, hipMemcpyHostToDevice,
+                                 mc.tape_stream));
+    SLAMHIP_CHECK(hipEventRecord(mc.tape_ready, mc.tape_stream));
+    mc.tape_filled += cnt;
     return SLAMHIP_OK;
   };
-  if (!m->d_tape || pos < m->tape_base || pos + need > m->tape_base + m->tape_cap) {
+  if (!mc.d_tape || pos < mc.tape_base || pos + need > mc.tape_base + mc.tape_cap) {
     // (re)start the window at the current position
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    SLAMHIP_CHECK(hipStreamSynchronize(m->tape_stream));
+    SLAMHIP_CHECK(hipStreamSynchronize(mc.tape_stream));
     const size_t cap = std::max<size_t>(64 * need, 1 << 16);
-    if (cap > m->tape_cap) {
-      if (m->d_tape) hipFree(m->d_tape);
-      if (m->h_tape) hipHostFree(m->h_tape);
-      m->d_tape = nullptr;
-      m->h_tape = nullptr;
-      SLAMHIP_CHECK(hipMalloc(&m->d_tape, sizeof(McPair) * cap));
-      SLAMHIP_CHECK(hipHostMalloc(&m->h_tape, sizeof(McPair) * cap, hipHostMallocDefault));
-      m->tape_cap = cap;
+    if (cap > mc.tape_cap) {
+      static_assert(sizeof(McPair) == 2 * sizeof(double), "the pinned staging holds pairs as two doubles");
+      SLAMHIP_CHECK(mc.d_tape.alloc(cap));
+      SLAMHIP_CHECK(mc.h_tape.alloc(2 * cap, hipHostMallocDefault));
+      mc.tape_cap = cap;
     }
-    m->tape_base = pos;
-    m->tape_filled = 0;
+    mc.tape_base = pos;
+    mc.tape_filled = 0;
   }
   rc = upload_upto(pos + need);  // nothing to do when the last match filled ahead
   if (rc) return rc;
-  SLAMHIP_CHECK(hipStreamWaitEvent(ctx->stream, m->tape_ready, 0));
+  SLAMHIP_CHECK(hipStreamWaitEvent(ctx->stream, mc.tape_ready, 0));
   m->t_stage_us = MatchJob::now_us() - t0;
   const size_t trace_need = max_poses + 2;
   if (m->has_obs && (!m->h_trace || (size_t)m->trace_cap < trace_need)) {
-    if (m->h_trace) hipHostFree(m->h_trace);
-    m->h_trace = nullptr;
     m->trace_cap = (int)std::max<size_t>(1 << 16, trace_need);
-    SLAMHIP_CHECK(hipHostMalloc(&m->h_trace, sizeof(HcTraceEntry) * m->trace_cap, pinned));
+    SLAMHIP_CHECK(m->h_trace.alloc(m->trace_cap, kPinnedCoherent));
   }
   static_assert(sizeof(McTraceEntry) == sizeof(HcTraceEntry), "one trace buffer serves both chains");
   a.oie = oie_eff;
   a.seq = m->cfg.sum_order == SLAMHIP_SUM_SEQUENTIAL ? 1 : 0;
   a.verify = (tie_check_default(m) && !a.seq) ? 1 : 0;
-  a.ctl = m->d_mc;
-  a.tape = m->d_tape + (pos - m->tape_base);
-  a.n_slots = m->mc_slots;
+  a.ctl = mc.d_mc.get();
+  a.tape = mc.d_tape.get() + (pos - mc.tape_base);
+  a.n_slots = mc.slots;
   for (int k = 0; k < 3; ++k) a.init[k] = init_pose[k];
   a.td0 = pe->base_td();
   a.rd0 = pe->base_rd();
   a.max_failed = pe->max_failed();
   a.max_poses = pe->max_poses();
-  unsigned epoch = ++m->chain_epoch;
-  if (epoch == 0) epoch = ++m->chain_epoch;
-  a.epoch = epoch;
-  a.host = m->h_mc;
-  a.trace = m->has_obs ? reinterpret_cast<McTraceEntry *>(m->h_trace) : nullptr;
+  a.epoch = next_epoch(m->chain_epoch);
+  a.host = mc.h_mc.get();
+  a.trace = m->has_obs ? reinterpret_cast<McTraceEntry *>(m->h_trace.get()) : nullptr;
   a.trace_cap = m->has_obs ? m->trace_cap : 0;
-  volatile McHostOut *h = m->h_mc;
+  volatile McHostOut *h = mc.h_mc.get();
   h->error = 0;
   h->progress = 0;
-  int launched = 0;
   bool ahead_done = false;
   // polar pairs of the next match while this one runs: generated a few at a time, uploaded once they are there
   auto fill_ahead = [&]() -> int {
@@ -1621,7 +1519,7 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
     }
     pe->prefetch_ahead(2 * need, 32);
     if (pe->tape_generated_upto() >= pos + 2 * need) {
-      if (pos + 2 * need <= m->tape_base + m->tape_cap) {
+      if (pos + 2 * need <= mc.tape_base + mc.tape_cap) {
         int r = upload_upto(pos + 2 * need);
         if (r) return r;
       }
@@ -1629,124 +1527,61 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
     }
     return SLAMHIP_OK;
   };
-  // ---- ONE launch (mc_resident.hip): every workgroup of the super-step stays on the chip for the whole match
-  bool ran_resident = false;
-  if (m->resident_gave_up_row >= 3 && ++m->chain_matches_since_off >= kResidentRearmAfter) {
-    m->resident_gave_up_row = 0;  // (re-armed)
-    m->chain_matches_since_off = 0;
-  }
-  if (m->chain_mode == 2 && m->resident_gave_up_row < 3) {
-    int cap = 0, per_cu = 0;
-    // (1024-thread workgroups are resident one per CU: 252 candidates per super-step then, like the hill-climbing tree)
-    if (m->chain_nt == 1024) a.n_slots = std::min(a.n_slots, 252);
-    a.lds_consts = 1;
-    rc = resident_capacity(m, cell_model, m->chain_nt, 3, a.scan.n, true, 0, &cap, &per_cu);
-    if (rc) return rc;
-    if (a.n_slots + 1 > cap) {  // (fewer workgroups fit with the beam constants in LDS than without?)
-      int cap_plain = 0, pc_plain = 0;
-      rc = resident_capacity(m, cell_model, m->chain_nt, 3, a.scan.n, false, 0, &cap_plain, &pc_plain);
-      if (rc) return rc;
-      if (cap_plain > cap) {
-        a.lds_consts = 0;
-        cap = cap_plain;
-        per_cu = pc_plain;
-      }
-    }
-    // (the capacity leaves one CU's worth of workgroups free: 509 candidates + the bookkeeping workgroup on an MI355X)
-    a.n_slots = std::min(a.n_slots, cap - 1);
-    ResidentLease lease;
-    if (a.n_slots >= 64 && lease.take(m->device, a.n_slots + 1, per_cu)) {
-      a.spin_limit = spin_limit_for(m->resident_us_max);
-      if (!m->d_mc_rctl) {
-        SLAMHIP_CHECK(hipMalloc(&m->d_mc_rctl, sizeof(McResidentCtl)));
-        SLAMHIP_CHECK(hipMemsetAsync(m->d_mc_rctl, 0, sizeof(McResidentCtl), ctx->stream));  // (ordered with the launch)
-      }
-      // (every workgroup clears its own granules when a match starts; a launch with MORE slots than the one before --
-      // the workgroup size or the batch limit was changed -- could meet what a slot held sixteen launches ago before
-      // its owner has started: the block is cleared then, hc_tag in hc_resident_device.h)
-      if (a.n_slots + 1 > m->mc_rctl_grid && m->mc_rctl_grid > 0)
-        SLAMHIP_CHECK(hipMemsetAsync(m->d_mc_rctl, 0, sizeof(McResidentCtl), ctx->stream));
-      m->mc_rctl_grid = a.n_slots + 1;
-      a.rctl = m->d_mc_rctl;
-      a.tag_epoch = ++m->rctl_launches;
-      a.debug_mute = m->debug_resident_mute;
-      a.stamps = m->d_stamps;
-      hipEvent_t e0, e1;
-      rc = profile_event_pair(ctx, &e0, &e1);
-      if (rc) return rc;
-      SLAMHIP_CHECK(launch_mc_chain_resident(a, cell_model, m->chain_nt, ctx->stream, e0, e1));
-      launched = 1;
-      ++m->resident_matches;
-      unsigned long long rspins = 0;
-      while (h->done_seq != epoch) {
-        rc = fill_ahead();
-        if (rc) return rc;
-        if ((++rspins & 0xfffffull) == 0) {
-          hipError_t qe = hipStreamQuery(ctx->stream);
-          if (qe == hipSuccess && h->done_seq != epoch) {
-            set_error("internal: the co-resident Monte-Carlo chain ended without publishing a result");
-            return SLAMHIP_ERR_STATE;
+  // (the policy is asked once per match, whatever the mode: every match counts towards the re-arm)
+  const bool armed = m->resident.armed();
+  int launched = 0;
+  rc = run_lone_chain(
+      m, a, h, m->chain_mode == 2 && armed, t0, &launched,
+      [&](ResidentLease &lease, bool *fits) -> int {
+        int cap = 0, per_cu = 0;
+        // (1024-thread workgroups are resident one per CU: 252 candidates per super-step then, like the hill-climbing tree)
+        if (m->chain_nt == 1024) a.n_slots = std::min(a.n_slots, 252);
+        a.lds_consts = 1;
+        int r = resident_capacity(m, cell_model, m->chain_nt, 3, a.scan.n, true, 0, &cap, &per_cu);
+        if (r) return r;
+        if (a.n_slots + 1 > cap) {  // (fewer workgroups fit with the beam constants in LDS than without?)
+          int cap_plain = 0, pc_plain = 0;
+          r = resident_capacity(m, cell_model, m->chain_nt, 3, a.scan.n, false, 0, &cap_plain, &pc_plain);
+          if (r) return r;
+          if (cap_plain > cap) {
+            a.lds_consts = 0;
+            cap = cap_plain;
+            per_cu = pc_plain;
           }
-          if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, "co-resident Monte-Carlo chain");
         }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      if (h->error == 4 || h->error == 5) {
-        // a workgroup was not resident with the others (the bounded sweep ran out), or the chain is longer than a tag
-        // counts: nothing has been reported and the enumerator has not been touched; wait for the stragglers to
-        // leave, then the chain of kernels runs the match under a new epoch
-        SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (h->error == 4) {
-          ++m->resident_gave_up_row;
-          ++m->resident_gave_up;
+        // (the capacity leaves one CU's worth of workgroups free: 509 candidates + the bookkeeping workgroup on an MI355X)
+        a.n_slots = std::min(a.n_slots, cap - 1);
+        if (a.n_slots < 64 || !lease.take(m->device, a.n_slots + 1, per_cu)) return SLAMHIP_OK;
+        if (!mc.d_rctl) {
+          SLAMHIP_CHECK(mc.d_rctl.alloc(1));
+          SLAMHIP_CHECK(hipMemsetAsync(mc.d_rctl.get(), 0, sizeof(McResidentCtl), ctx->stream));  // (ordered with the launch)
         }
-        epoch = ++m->chain_epoch;
-        if (epoch == 0) epoch = ++m->chain_epoch;
-        a.epoch = epoch;
-        a.n_slots = m->mc_slots;
-        h->error = 0;
-        launched = 0;
-      } else {
-        m->resident_gave_up_row = 0;
-        ran_resident = true;
-        note_resident_time(&m->resident_us_max, MatchJob::now_us() - t0);
-      }
-    }
-    if (!ran_resident) a.n_slots = m->mc_slots;  // (the chain of kernels: the matcher's own candidate count)
-  }
-  auto launch_one = [&]() -> int {
-    hipEvent_t e0, e1;
-    int r = profile_event_pair(ctx, &e0, &e1);
-    if (r) return r;
-    SLAMHIP_CHECK(launch_mc_chain_step(a, cell_model, launched, m->chain_nt, ctx->stream, e0, e1));
-    ++launched;
-    return SLAMHIP_OK;
-  };
-  const int first = ran_resident ? 0 : std::max(2, std::min(256, (int)(m->chain_steps_avg * 0.75)));
-  for (int i = 0; i < first; ++i) {
-    rc = launch_one();
-    if (rc) return rc;
-  }
-  unsigned long long spins = 0;
-  while (h->done_seq != epoch) {
-    const int started = (int)h->progress;
-    if (launched - started < m->chain_ahead) {
-      if (launched >= (1 << 20)) {
-        set_error("Monte-Carlo chain did not end");
-        return SLAMHIP_ERR_STATE;
-      }
-      rc = launch_one();
-      if (rc) return rc;
-      continue;
-    }
-    rc = fill_ahead();
-    if (rc) return rc;
-    if ((++spins & 0xfffffull) == 0) {
-      hipError_t qe = hipStreamQuery(ctx->stream);
-      if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, "Monte-Carlo chain kernel");
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        // (every workgroup clears its own granules when a match starts; a launch with MORE slots than the one before --
+        // the workgroup size or the batch limit was changed -- could meet what a slot held sixteen launches ago before
+        // its owner has started: the block is cleared then, hc_tag in hc_resident_device.h)
+        if (a.n_slots + 1 > mc.rctl_grid && mc.rctl_grid > 0)
+          SLAMHIP_CHECK(hipMemsetAsync(mc.d_rctl.get(), 0, sizeof(McResidentCtl), ctx->stream));
+        mc.rctl_grid = a.n_slots + 1;
+        a.rctl = mc.d_rctl.get();
+        a.stamps = m->d_stamps.get();
+        *fits = true;
+        return SLAMHIP_OK;
+      },
+      [&](hipEvent_t e0, hipEvent_t e1) { return launch_mc_chain_resident(a, cell_model, m->chain_nt, ctx->stream, e0, e1); },
+      [&](bool gave_up) -> int {
+        // nothing has been reported and the enumerator has not been touched: the chain of kernels runs the match with
+        // the matcher's own candidate count -- after a launch that gave up, under a new epoch
+        if (gave_up) a.epoch = next_epoch(m->chain_epoch);
+        a.n_slots = mc.slots;
+        return SLAMHIP_OK;
+      },
+      [&](int step, hipEvent_t e0, hipEvent_t e1) {
+        return launch_mc_chain_step(a, cell_model, step, m->chain_nt, ctx->stream, e0, e1);
+      },
+      fill_ahead,
+      LoneChainText{"internal: the co-resident Monte-Carlo chain ended without publishing a result",
+                    "co-resident Monte-Carlo chain", "Monte-Carlo chain did not end", "Monte-Carlo chain kernel"});
+  if (rc) return rc;
   // the observer's trace outgrew its buffer: the enumerator has not been touched yet (set_chain_result below),
   // the host-driven path redoes the match from the same engine position
   if (h->error == 2) return kChainNeedsHost;
@@ -1759,36 +1594,8 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
     pe->set_chain_result((size_t)h->tape_pos, h->failed, h->poses, h->td, h->rd, h->has_saved != 0, saved);
     pe->trim();
   }
-  MatchJob &job = m->job;
-  job.scorer_calls = h->calls;
-  job.poses_evaluated = h->evaluated;
-  job.launches = h->steps;
-  job.t_build_us = job.t_replay_us = 0;
-  m->chain_launched = launched;
-  m->chain_rescored = h->rescored;
   m->tail_calls = 0;
-  m->chain_steps_avg = 0.75 * m->chain_steps_avg + 0.25 * (double)h->steps;
-  if (ctx->profile) {
-    ctx->prof_launches += launched;
-    ctx->prof_units += h->evaluated * (long long)a.scan.n;
-  }
-  out_delta[0] = h->pose[0] - init_pose[0];
-  out_delta[1] = h->pose[1] - init_pose[1];
-  out_delta[2] = h->pose[2] - init_pose[2];
-  *out_prob = h->best_prob;
-  m->t_score_us = MatchJob::now_us() - t0;
-  if (m->has_obs) {
-    const double t1 = MatchJob::now_us();
-    for (long long i = 0; i < h->calls; ++i) {
-      const HcTraceEntry &e = m->h_trace[i];
-      const double p3[3] = {e.x, e.y, e.theta};
-      if (m->obs.on_scan_test) m->obs.on_scan_test(m->obs.user, p3, e.score);
-      if (e.accepted && m->obs.on_pose_update) m->obs.on_pose_update(m->obs.user, p3, e.score);
-    }
-    job.t_replay_us = MatchJob::now_us() - t1;
-    if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, out_delta, *out_prob);
-  }
-  return SLAMHIP_OK;
+  return lone_chain_report(m, h, launched, a.scan.n, t0, init_pose, out_delta, out_prob);
 }
 
 }  // namespace
@@ -1814,9 +1621,9 @@ int slamhip_matcher_create_hc(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, unsi
                         1024, out);
   if (rc) return rc;
   (*out)->is_hc = true;
-  (*out)->hc_max_failed = failed_rounds_limit;
-  (*out)->hc_dt = dt;
-  (*out)->hc_dr = dr;
+  (*out)->hc.max_failed = failed_rounds_limit;
+  (*out)->hc.dt = dt;
+  (*out)->hc.dr = dr;
   return SLAMHIP_OK;
 }
 
@@ -1829,21 +1636,20 @@ int slamhip_matcher_create_bf(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, cons
   const int rc = make_matcher(ctx, cfg, std::make_unique<BruteForcePoseEnumerator>(range9), 8192, out);
   if (rc) return rc;
   (*out)->is_bf = true;
-  std::memcpy((*out)->bf_r, range9, sizeof((*out)->bf_r));
+  std::memcpy((*out)->bf.r, range9, sizeof((*out)->bf.r));
   return SLAMHIP_OK;
 }
 
 int slamhip_matcher_destroy(slamhip_matcher *m) {
   if (m) {
-    if (m->d_chain || m->batch || m->d_bf_poses) {
+    if (m->hc.d_chain || m->batch || m->bf.d_poses) {
       // run-ahead kernels of the last chain may still read the blocks; the context may already be gone
       // (destroying it synchronised its stream), so wait on the device, not on the context's stream
       hipSetDevice(m->device);
       hipDeviceSynchronize();
     }
-    chain_release(m);
   }
-  delete m;
+  delete m;  // (the blocks go with their owners)
   return SLAMHIP_OK;
 }
 
@@ -1872,7 +1678,7 @@ int slamhip_matcher_set_device_chain(slamhip_matcher *m, int mode, int threads) 
   (void)chain_eligible(m);  // defaults first, then the explicit setting
   m->chain_mode = mode;
   m->chain_mode_explicit = true;
-  m->resident_gave_up_row = 0;
+  m->resident.reset();
   if (threads) m->chain_nt = threads;
   return SLAMHIP_OK;
 }
@@ -1890,13 +1696,13 @@ int slamhip_matcher_set_tie_check(slamhip_matcher *m, int on) {
 int slamhip_matcher_debug_stamps(slamhip_matcher *m, long long *out512) {
   if (!m) return invalid_arg("null matcher");
   if (!m->d_stamps) {
-    SLAMHIP_CHECK(hipMalloc(&m->d_stamps, sizeof(long long) * 512));
-    SLAMHIP_CHECK(hipMemset(m->d_stamps, 0, sizeof(long long) * 512));
+    SLAMHIP_CHECK(m->d_stamps.alloc(512));
+    SLAMHIP_CHECK(hipMemset(m->d_stamps.get(), 0, sizeof(long long) * 512));
     SLAMHIP_CHECK(hipDeviceSynchronize());  // (hipMemset of device memory does not wait: the next match would race it)
     return SLAMHIP_OK;
   }
   SLAMHIP_CHECK(hipDeviceSynchronize());
-  if (out512) SLAMHIP_CHECK(hipMemcpy(out512, m->d_stamps, sizeof(long long) * 512, hipMemcpyDeviceToHost));
+  if (out512) SLAMHIP_CHECK(hipMemcpy(out512, m->d_stamps.get(), sizeof(long long) * 512, hipMemcpyDeviceToHost));
   return SLAMHIP_OK;
 }
 #endif  // SLAMHIP_TESTING
@@ -1916,8 +1722,8 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
     }
   }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  if (!m->batch) m->batch = new HcBatch;
-  HcBatch *b = m->batch;
+  if (!m->batch) m->batch = std::make_unique<HcBatch>();
+  HcBatch *b = m->batch.get();
   b->res.assign(n_jobs, BatchJobResult{});
   b->kernels = 0;
   bool chains = n_jobs > 1 && batch_chain_eligible(m);
@@ -1948,13 +1754,7 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
       for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
       out_probs[c] = r.prob;
       if (m->has_obs) {
-        const HcTraceEntry *tr = b->h_trace + (size_t)c * b->trace_per;
-        for (long long i = 0; i < r.calls; ++i) {
-          const HcTraceEntry &e = tr[i];
-          const double p3[3] = {e.x, e.y, e.theta};
-          if (m->obs.on_scan_test) m->obs.on_scan_test(m->obs.user, p3, e.score);
-          if (e.accepted && m->obs.on_pose_update) m->obs.on_pose_update(m->obs.user, p3, e.score);
-        }
+        replay_trace(m->obs, b->h_trace.get() + (size_t)c * b->trace_per, r.calls);
         if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
       }
     } else {
@@ -2088,13 +1888,13 @@ int slamhip_map_debug_nbr_masks(slamhip_ctx *ctx, int map_id, int *valid, long l
   if (mismatches) *mismatches = 0;
   if (!dm.nbr_ok || !mismatches) return SLAMHIP_OK;
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  unsigned long long *d_count = nullptr, h_count = 0;
-  SLAMHIP_CHECK(hipMalloc(&d_count, sizeof(unsigned long long)));
-  SLAMHIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), ctx->stream));
-  SLAMHIP_CHECK(launch_nbr_check(dm.d_payload, dm.width, dm.height, dm.pitch, dm.nbr_th, d_count, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, ctx->stream));
+  DeviceBuf<unsigned long long> d_count;
+  unsigned long long h_count = 0;
+  SLAMHIP_CHECK(d_count.alloc(1));
+  SLAMHIP_CHECK(hipMemsetAsync(d_count.get(), 0, sizeof(unsigned long long), ctx->stream));
+  SLAMHIP_CHECK(launch_nbr_check(dm.d_payload, dm.width, dm.height, dm.pitch, dm.nbr_th, d_count.get(), ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(&h_count, d_count.get(), sizeof(h_count), hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  hipFree(d_count);
   *mismatches = (long long)h_count;
   return SLAMHIP_OK;
 }
@@ -2106,13 +1906,13 @@ int slamhip_map_debug_prob_plane(slamhip_ctx *ctx, int map_id, int *valid, long 
   if (valid) *valid = dm.prob_ok ? 1 : 0;
   if (mismatches) *mismatches = 0;
   if (!dm.prob_ok || !mismatches) return SLAMHIP_OK;
-  unsigned long long *d_count = nullptr, h_count = 0;
-  SLAMHIP_CHECK(hipMalloc(&d_count, sizeof(unsigned long long)));
-  SLAMHIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), ctx->stream));
-  SLAMHIP_CHECK(launch_prob_check(dm.d_payload, dm.d_prob, dm.width, dm.height, dm.pitch, d_count, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, ctx->stream));
+  DeviceBuf<unsigned long long> d_count;
+  unsigned long long h_count = 0;
+  SLAMHIP_CHECK(d_count.alloc(1));
+  SLAMHIP_CHECK(hipMemsetAsync(d_count.get(), 0, sizeof(unsigned long long), ctx->stream));
+  SLAMHIP_CHECK(launch_prob_check(dm.d_payload, dm.d_prob, dm.width, dm.height, dm.pitch, d_count.get(), ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(&h_count, d_count.get(), sizeof(h_count), hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  hipFree(d_count);
   *mismatches = (long long)h_count;
   return SLAMHIP_OK;
 }
@@ -2120,8 +1920,8 @@ int slamhip_map_debug_prob_plane(slamhip_ctx *ctx, int map_id, int *valid, long 
 
 int slamhip_matcher_resident_stats(slamhip_matcher *m, long long *matches, long long *gave_up) {
   if (!m) return invalid_arg("null matcher");
-  if (matches) *matches = m->resident_matches;
-  if (gave_up) *gave_up = m->resident_gave_up;
+  if (matches) *matches = m->resident.matches;
+  if (gave_up) *gave_up = m->resident.gave_up;
   return SLAMHIP_OK;
 }
 
@@ -2151,9 +1951,8 @@ int slamhip_matcher_process_scan(slamhip_matcher *m, int map_id, const double in
   // before anything has been shown to an observer; the match is then redone below in the exact mode
   bool force_exact = false;
   if (chain_eligible(m)) {
-    int crc = kResidentGaveUp;
-    if (resident_wanted(m)) crc = chain_process_scan(m, map_id, init_pose, out_delta, out_prob, true);
-    if (crc == kResidentGaveUp) crc = chain_process_scan(m, map_id, init_pose, out_delta, out_prob, false);
+    // (one co-resident launch where that is asked for and fits; else, or when it gives up, the chain of kernels)
+    const int crc = chain_process_scan(m, map_id, init_pose, out_delta, out_prob, hc_resident_asked(m));
     if (crc == kChainUnsettled) force_exact = true;
     else if (crc != kChainNeedsHost) return crc;
   }

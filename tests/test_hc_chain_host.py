@@ -129,3 +129,20 @@ def test_pair_tape_is_std_normal_distribution(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("ok")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
+def test_resident_policy_switch_off_and_rearm(tmp_path):
+    """csrc/resident_policy.h -- the one owner of "three give-ups in a row switch the co-resident form off, the 64th
+    call after that asks again" for the lone hill-climbing / Monte-Carlo drivers, the K-matches driver and the filter's
+    one-chain-per-particle driver (tests/native/resident_policy_test.cpp): the switch-off, the automatic re-arm, the
+    reset by slamhip_matcher_set_device_chain (the calls counted so far stay counted), the spin bound, and 360 000
+    random driver calls against the rule as the drivers spelled it out field by field."""
+    exe = str(tmp_path / "resident_policy_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-fno-omit-frame-pointer", "-ffp-contract=off", "-I" + os.path.join(ROOT, "slam-constructor_amd", "csrc"),
+           os.path.join(ROOT, "tests", "native", "resident_policy_test.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok 360000 driver calls")
