@@ -45,8 +45,14 @@ typedef enum {
  *                                        (src/core/maps/grid_cell.h:33-35, naive_grid_cells.h:6-44)
  *  TBM      4 x f64  (u, e, o, c)        TbmBaseCell belief (src/core/maps/tbm_grid_cells.h:21-35)
  *  GMAPPING 3 x f64  (prob_occ, obst.x, obst.y)  GmappingBaseCell
- *                                        (src/slams/gmapping/gmapping_grid_cell.h:9-43) */
-enum { SLAMHIP_CELL_OCC = 0, SLAMHIP_CELL_TBM = 1, SLAMHIP_CELL_GMAPPING = 2 };
+ *                                        (src/slams/gmapping/gmapping_grid_cell.h:9-43)
+ *  CREDIBILIST 4 x f64 (u, e, o, c)     CredibilistCell belief (src/slams/credibilist/grid_cell.h:10-68): the TBM
+ *                                        payload, host stride and unknown_payload, updated by SLAMHIP_RULE_TBM
+ *                                        (its operator+= is TbmBaseCell's, operation for operation), but SCORED by
+ *                                        its own rule: discrepancy = 1 - disjunctive(observation, belief).occupied()
+ *                                        (grid_cell.h:31-40, transferable_belief_model.h:145-162).  Like TBM it takes
+ *                                        the discrepancy OIE only and never the GMapping OOPE. */
+enum { SLAMHIP_CELL_OCC = 0, SLAMHIP_CELL_TBM = 1, SLAMHIP_CELL_GMAPPING = 2, SLAMHIP_CELL_CREDIBILIST = 3 };
 /* OccupancyObservationProbabilityEstimator kinds
  * (src/core/scan_matchers/occupancy_observation_probability.h:12-99,
  *  src/slams/gmapping/gmapping_occupancy_observation_pe.h:11-45) */
@@ -116,7 +122,8 @@ enum {
                                   * probability -- a pure function of the cell (tbm_grid_cells.h:21-35 with the fixed
                                   * observation of the scorer) -- from an 8-byte plane every writer of the map keeps,
                                   * instead of the 32-byte cell and its belief arithmetic per (pose, beam); 0: from the
-                                  * cell.  The same operations either way: the same bits. */
+                                  * cell.  The same operations either way: the same bits.  Governs
+                                  * SLAMHIP_CELL_CREDIBILIST maps too (their plane holds that model's probability). */
   SLAMHIP_OPT_INERT_TAIL = 8     /* the tail of a hill-climbing chain on the device (1-cell OOPE).  The reference's enumerator
                                   * stops at a count of failed rounds, not at convergence
                                   * (hill_climbing_scan_matcher.h:83-101), the steps halved at every failure.
@@ -179,7 +186,8 @@ int slamhip_map_download_window(slamhip_ctx *ctx, int map_id, int x0, int y0, in
 enum { SLAMHIP_RULE_LAST = 0,     /* GridCell::operator+= (grid_cell.h:27-30): last write wins */
        SLAMHIP_RULE_AFFINE = 1,   /* AffineQualityMergeCell (naive_grid_cells.h:14-20) */
        SLAMHIP_RULE_MEAN = 2,     /* MeanProbabilityCell (naive_grid_cells.h:33-40) */
-       SLAMHIP_RULE_TBM = 3,      /* TbmBaseCell (tbm_grid_cells.h:12-19) */
+       SLAMHIP_RULE_TBM = 3,      /* TbmBaseCell (tbm_grid_cells.h:12-19); also CredibilistCell
+                                   * (slams/credibilist/grid_cell.h:23-29) on a SLAMHIP_CELL_CREDIBILIST map */
        SLAMHIP_RULE_GMAPPING = 4  /* GmappingBaseCell (gmapping_grid_cell.h:20-33) */ };
 typedef struct {
   int rule;

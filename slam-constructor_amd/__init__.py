@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libslamhip.so")
 TESTING_LIB_PATH = os.path.join(PKG_DIR, "libslamhip_testing.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 
-CELL_OCC, CELL_TBM, CELL_GMAPPING = 0, 1, 2
+CELL_OCC, CELL_TBM, CELL_GMAPPING, CELL_CREDIBILIST = 0, 1, 2, 3
 OOPE_OBSTACLE, OOPE_MAX, OOPE_MEAN, OOPE_OVERLAP, OOPE_GMAPPING = range(5)
 OIE_DISCREPANCY, OIE_OCCUPANCY = 0, 1
 SUM_TREE256, SUM_SEQUENTIAL = 0, 1
@@ -30,7 +30,7 @@ POSE_TRIG_DEVICE, POSE_TRIG_HOST, POSE_TRIG_RAW_EXACT = 0, 1, 2
 (OPT_LOW_LATENCY, OPT_STAGE_POSES, OPT_FILTER_CHAINS, OPT_K6_PATH, OPT_K6_BATCH_FAST, OPT_K6_BATCH_KEY64,
  OPT_RESIDENT_CHAINS, OPT_TBM_PLANE, OPT_INERT_TAIL) = range(9)
 TRIG_RAW, TRIG_CACHED = 0, 1
-STRIDE = {CELL_OCC: 1, CELL_TBM: 4, CELL_GMAPPING: 3}
+STRIDE = {CELL_OCC: 1, CELL_TBM: 4, CELL_GMAPPING: 3, CELL_CREDIBILIST: 4}
 
 EXPORTS = """slamhip_last_error slamhip_device_count slamhip_ctx_create slamhip_ctx_destroy
 slamhip_ctx_synchronize slamhip_ctx_stream slamhip_ctx_set_option slamhip_ctx_get_option slamhip_map_bind slamhip_map_upload_window

@@ -68,7 +68,7 @@ __device__ __forceinline__ double hc_gm_fix(double score, HcCarry &cr, const GmP
   return score;
 }
 
-// MODEL: SLAMHIP_CELL_OCC / _TBM = the 1-cell OOPE (k_score_point's arithmetic), SLAMHIP_CELL_GMAPPING = the
+// MODEL: SLAMHIP_CELL_OCC / _TBM / _CREDIBILIST = the 1-cell OOPE (k_score_point's arithmetic), SLAMHIP_CELL_GMAPPING = the
 // GMapping OOPE (K3's one-pose body, KB = ceil(beams / 256))
 // BATCH: grid.y independent matches, each with its own map and scan (HcChainArgs::jobs)
 template <int MODEL, int NT, bool SEQ, int KB, bool BATCH>
@@ -673,6 +673,7 @@ hipError_t launch_hc_chain_step(const HcChainArgs &a, int cell_model, int k, int
     if (a.seq) return hipErrorInvalidValue;
     if (cell_model == SLAMHIP_CELL_OCC) return launch_nt<SLAMHIP_CELL_OCC, false, true>(a, k, nt, stream, e0, e1, n_chains);
     if (cell_model == SLAMHIP_CELL_TBM) return launch_nt<SLAMHIP_CELL_TBM, false, true>(a, k, nt, stream, e0, e1, n_chains);
+    if (cell_model == SLAMHIP_CELL_CREDIBILIST) return launch_nt<SLAMHIP_CELL_CREDIBILIST, false, true>(a, k, nt, stream, e0, e1, n_chains);
     return hipErrorInvalidValue;
   }
   if (cell_model == SLAMHIP_CELL_OCC)
@@ -681,6 +682,9 @@ hipError_t launch_hc_chain_step(const HcChainArgs &a, int cell_model, int k, int
   if (cell_model == SLAMHIP_CELL_TBM)
     return a.seq ? launch_nt<SLAMHIP_CELL_TBM, true, false>(a, k, nt, stream, e0, e1, n_chains)
                  : launch_nt<SLAMHIP_CELL_TBM, false, false>(a, k, nt, stream, e0, e1, n_chains);
+  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
+    return a.seq ? launch_nt<SLAMHIP_CELL_CREDIBILIST, true, false>(a, k, nt, stream, e0, e1, n_chains)
+                 : launch_nt<SLAMHIP_CELL_CREDIBILIST, false, false>(a, k, nt, stream, e0, e1, n_chains);
   if (cell_model == SLAMHIP_CELL_GMAPPING && !a.seq) {
     switch ((a.scan.n + 255) / 256) {
       case 1: return launch_gm<1>(a, k, nt, stream, e0, e1, n_chains);

@@ -87,7 +87,7 @@ constexpr int kSelRescore = -1;  // the same tree once more (an unsettled compar
 constexpr int kSelFirst = -2;    // the first super-step: the prologue's pose
 constexpr int kSelStop = -3;     // leave: the replay found no terminal round (a bug, reported) or the chain gave up
 
-// MODEL: SLAMHIP_CELL_OCC / _TBM (the 1-cell OOPE); SEQ: the reference's beam-order sum; BATCH: grid.y independent
+// MODEL: SLAMHIP_CELL_OCC / _TBM / _CREDIBILIST (the 1-cell OOPE); SEQ: the reference's beam-order sum; BATCH: grid.y independent
 // matches, each with its own map and scan (HcChainArgs::jobs); G: granules per lane of the sweeping wave, i.e. the
 // grid has at most 64 G workgroups (2, 4 or 7); WIN: the window OOPEs (max / mean / overlap, K2's per-beam value) in
 // place of the 1-cell one
@@ -970,12 +970,14 @@ hipError_t launch_hc_chain_resident(const HcChainArgs &a, int cell_model, int nt
     if (a.jobs || a.seq) return hipErrorInvalidValue;
     if (cell_model == SLAMHIP_CELL_OCC) return launch_res_win<SLAMHIP_CELL_OCC>(a, nt, stream, e0, e1, n_chains);
     if (cell_model == SLAMHIP_CELL_TBM) return launch_res_win<SLAMHIP_CELL_TBM>(a, nt, stream, e0, e1, n_chains);
+    if (cell_model == SLAMHIP_CELL_CREDIBILIST) return launch_res_win<SLAMHIP_CELL_CREDIBILIST>(a, nt, stream, e0, e1, n_chains);
     return hipErrorInvalidValue;
   }
   if (a.jobs) {
     if (a.seq) return hipErrorInvalidValue;
     if (cell_model == SLAMHIP_CELL_OCC) return launch_res<SLAMHIP_CELL_OCC, false, true>(a, nt, stream, e0, e1, n_chains);
     if (cell_model == SLAMHIP_CELL_TBM) return launch_res<SLAMHIP_CELL_TBM, false, true>(a, nt, stream, e0, e1, n_chains);
+    if (cell_model == SLAMHIP_CELL_CREDIBILIST) return launch_res<SLAMHIP_CELL_CREDIBILIST, false, true>(a, nt, stream, e0, e1, n_chains);
     return hipErrorInvalidValue;
   }
   if (cell_model == SLAMHIP_CELL_OCC)
@@ -984,6 +986,9 @@ hipError_t launch_hc_chain_resident(const HcChainArgs &a, int cell_model, int nt
   if (cell_model == SLAMHIP_CELL_TBM)
     return a.seq ? launch_res<SLAMHIP_CELL_TBM, true, false>(a, nt, stream, e0, e1, n_chains)
                  : launch_res<SLAMHIP_CELL_TBM, false, false>(a, nt, stream, e0, e1, n_chains);
+  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
+    return a.seq ? launch_res<SLAMHIP_CELL_CREDIBILIST, true, false>(a, nt, stream, e0, e1, n_chains)
+                 : launch_res<SLAMHIP_CELL_CREDIBILIST, false, false>(a, nt, stream, e0, e1, n_chains);
   return hipErrorInvalidValue;
 }
 
@@ -1029,10 +1034,18 @@ hipError_t hc_resident_capacity(int cell_model, int nt, bool batch, bool window,
   if (e != hipSuccess) return e;
   const void *fn = nullptr;
   const int g = window ? 4 : gran_per_lane(6 * max_inst + 1);
-  if (window) fn = cell_model == SLAMHIP_CELL_TBM ? res_fn_win<SLAMHIP_CELL_TBM>(nt) : res_fn_win<SLAMHIP_CELL_OCC>(nt);
-  else if (batch && pair) fn = cell_model == SLAMHIP_CELL_TBM ? res_fn_pair<SLAMHIP_CELL_TBM>(g) : res_fn_pair<SLAMHIP_CELL_OCC>(g);
-  else if (batch) fn = cell_model == SLAMHIP_CELL_TBM ? res_fn<SLAMHIP_CELL_TBM, true>(nt, g) : res_fn<SLAMHIP_CELL_OCC, true>(nt, g);
-  else fn = cell_model == SLAMHIP_CELL_TBM ? res_fn<SLAMHIP_CELL_TBM, false>(nt, g) : res_fn<SLAMHIP_CELL_OCC, false>(nt, g);
+  // (a model the kernels are not instantiated for leaves fn null: an error, never another model's kernel)
+#define HCR_FN(M)                                             \
+  do {                                                        \
+    if (window) fn = res_fn_win<M>(nt);                       \
+    else if (batch && pair) fn = res_fn_pair<M>(g);           \
+    else if (batch) fn = res_fn<M, true>(nt, g);              \
+    else fn = res_fn<M, false>(nt, g);                        \
+  } while (0)
+  if (cell_model == SLAMHIP_CELL_OCC) HCR_FN(SLAMHIP_CELL_OCC);
+  else if (cell_model == SLAMHIP_CELL_TBM) HCR_FN(SLAMHIP_CELL_TBM);
+  else if (cell_model == SLAMHIP_CELL_CREDIBILIST) HCR_FN(SLAMHIP_CELL_CREDIBILIST);
+#undef HCR_FN
   if (!fn) return hipErrorInvalidValue;
   e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, lds_bytes);
   if (e != hipSuccess) return e;

@@ -332,7 +332,7 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   const int rule = cfg->rule;
   if (rule < SLAMHIP_RULE_LAST || rule > SLAMHIP_RULE_GMAPPING) return fail("unknown cell update rule");
   if (cfg->occupancy_estimator != 0 && cfg->occupancy_estimator != 1) return fail("unknown occupancy estimator");
-  const bool ok_model = (rule == SLAMHIP_RULE_TBM && m.cell_model == SLAMHIP_CELL_TBM) ||
+  const bool ok_model = (rule == SLAMHIP_RULE_TBM && cell_is_belief(m.cell_model)) ||
                         (rule == SLAMHIP_RULE_GMAPPING && m.cell_model == SLAMHIP_CELL_GMAPPING) ||
                         (rule <= SLAMHIP_RULE_MEAN && m.cell_model == SLAMHIP_CELL_OCC);
   if (!ok_model) return fail("cell update rule does not fit the map's payload model");
@@ -453,7 +453,8 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
     // (a window that grew a moment ago has no masks: its next GMapping scorer call derives them)
     a.nbr_on = (m.nbr_ok && m.cell_model == SLAMHIP_CELL_GMAPPING) ? 1 : 0;
     a.nbr_th = m.nbr_th;
-    a.prob = (m.prob_ok && m.cell_model == SLAMHIP_CELL_TBM) ? m.d_prob : nullptr;  // (gone after a re-bind, like the masks)
+    a.prob = (m.prob_ok && cell_is_belief(m.cell_model)) ? m.d_prob : nullptr;  // (gone after a re-bind, like the masks)
+    a.prob_model = m.cell_model;
   };
   fill_map();
   a.cell_dbl = cell_doubles(m.cell_model);

@@ -1910,7 +1910,7 @@ int slamhip_map_debug_prob_plane(slamhip_ctx *ctx, int map_id, int *valid, long 
   unsigned long long h_count = 0;
   SLAMHIP_CHECK(d_count.alloc(1));
   SLAMHIP_CHECK(hipMemsetAsync(d_count.get(), 0, sizeof(unsigned long long), ctx->stream));
-  SLAMHIP_CHECK(launch_prob_check(dm.d_payload, dm.d_prob, dm.width, dm.height, dm.pitch, d_count.get(), ctx->stream));
+  SLAMHIP_CHECK(launch_prob_check(dm.cell_model, dm.d_payload, dm.d_prob, dm.width, dm.height, dm.pitch, d_count.get(), ctx->stream));
   SLAMHIP_CHECK(hipMemcpyAsync(&h_count, d_count.get(), sizeof(h_count), hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   *mismatches = (long long)h_count;

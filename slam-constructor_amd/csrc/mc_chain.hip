@@ -337,6 +337,9 @@ hipError_t launch_mc_chain_step(const McChainArgs &a, int cell_model, int k, int
   if (cell_model == SLAMHIP_CELL_TBM)
     return a.seq ? launch_nt<SLAMHIP_CELL_TBM, true>(a, k, nt, stream, e0, e1)
                  : launch_nt<SLAMHIP_CELL_TBM, false>(a, k, nt, stream, e0, e1);
+  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
+    return a.seq ? launch_nt<SLAMHIP_CELL_CREDIBILIST, true>(a, k, nt, stream, e0, e1)
+                 : launch_nt<SLAMHIP_CELL_CREDIBILIST, false>(a, k, nt, stream, e0, e1);
   return hipErrorInvalidValue;
 }
 

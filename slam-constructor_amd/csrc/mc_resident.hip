@@ -477,6 +477,9 @@ hipError_t launch_mc_chain_resident(const McChainArgs &a, int cell_model, int nt
   if (cell_model == SLAMHIP_CELL_TBM)
     return a.seq ? launch_mcr<SLAMHIP_CELL_TBM, true>(a, nt, stream, e0, e1)
                  : launch_mcr<SLAMHIP_CELL_TBM, false>(a, nt, stream, e0, e1);
+  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
+    return a.seq ? launch_mcr<SLAMHIP_CELL_CREDIBILIST, true>(a, nt, stream, e0, e1)
+                 : launch_mcr<SLAMHIP_CELL_CREDIBILIST, false>(a, nt, stream, e0, e1);
   return hipErrorInvalidValue;
 }
 
@@ -491,9 +494,14 @@ hipError_t mc_resident_capacity(int cell_model, int nt, int n_beams, bool lds_co
   if (cell_model == SLAMHIP_CELL_TBM)
     fn = nt == 1024 ? (const void *)k_mc_chain_resident<SLAMHIP_CELL_TBM, 1024, false>
                     : (const void *)k_mc_chain_resident<SLAMHIP_CELL_TBM, 512, false>;
-  else
+  else if (cell_model == SLAMHIP_CELL_CREDIBILIST)
+    fn = nt == 1024 ? (const void *)k_mc_chain_resident<SLAMHIP_CELL_CREDIBILIST, 1024, false>
+                    : (const void *)k_mc_chain_resident<SLAMHIP_CELL_CREDIBILIST, 512, false>;
+  else if (cell_model == SLAMHIP_CELL_OCC)
     fn = nt == 1024 ? (const void *)k_mc_chain_resident<SLAMHIP_CELL_OCC, 1024, false>
                     : (const void *)k_mc_chain_resident<SLAMHIP_CELL_OCC, 512, false>;
+  else
+    return hipErrorInvalidValue;  // (never another model's kernel)
   e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, mc_resident_lds_bytes(nt, n_beams, lds_consts));
   if (e != hipSuccess) return e;
   const int by_waves = 2048 / nt;  // 128-VGPR waves: four per SIMD

@@ -7,6 +7,8 @@
 //   GridCell::discrepancy                  src/core/maps/grid_cell.h:33-35
 //   TbmBaseCell::discrepancy + conjunctive src/core/maps/tbm_grid_cells.h:21-35,
 //                                          src/core/maps/transferable_belief_model.h:102-143
+//   CredibilistCell::discrepancy + disjunctive src/slams/credibilist/grid_cell.h:31-40,
+//                                          src/core/maps/transferable_belief_model.h:145-162
 #pragma once
 
 #include "slamhip_internal.h"
@@ -123,6 +125,8 @@ __device__ __forceinline__ double cell_probability(int oie, const double4 &v) {
     const double occ = v.x;
     if (oie == SLAMHIP_OIE_OCCUPANCY) return occ;
     return 1.0 - fabs(occ - 1.0);
+  } else if (MODEL == SLAMHIP_CELL_CREDIBILIST) {
+    return credibilist_probability(v.x, v.y, v.z, v.w);
   } else {
     return tbm_discrepancy_probability(v.x, v.y, v.z, v.w);
   }

@@ -617,6 +617,8 @@ hipError_t launch_score(const ScoreArgs &args, int cell_model, int oope, int sum
       SLAMHIP_LAUNCH((k_score_window<SLAMHIP_CELL_OCC>), grid, dim3(kBlock), 0, stream, ev_start, stop1, a, oope);
     else if (cell_model == SLAMHIP_CELL_TBM)
       SLAMHIP_LAUNCH((k_score_window<SLAMHIP_CELL_TBM>), grid, dim3(kBlock), 0, stream, ev_start, stop1, a, oope);
+    else if (cell_model == SLAMHIP_CELL_CREDIBILIST)
+      SLAMHIP_LAUNCH((k_score_window<SLAMHIP_CELL_CREDIBILIST>), grid, dim3(kBlock), 0, stream, ev_start, stop1, a, oope);
     else
       return hipErrorInvalidValue;
     e = hipGetLastError();
@@ -628,6 +630,10 @@ hipError_t launch_score(const ScoreArgs &args, int cell_model, int oope, int sum
     e = wt ? launch_point_kb<SLAMHIP_CELL_TBM, true>(a, kb, grid, stream, ev_start, stop1)
            : (a.fprints ? launch_point_kb<SLAMHIP_CELL_TBM, false, true>(a, kb, grid, stream, ev_start, stop1)
                         : launch_point_kb<SLAMHIP_CELL_TBM, false>(a, kb, grid, stream, ev_start, stop1));
+  } else if (cell_model == SLAMHIP_CELL_CREDIBILIST) {
+    e = wt ? launch_point_kb<SLAMHIP_CELL_CREDIBILIST, true>(a, kb, grid, stream, ev_start, stop1)
+           : (a.fprints ? launch_point_kb<SLAMHIP_CELL_CREDIBILIST, false, true>(a, kb, grid, stream, ev_start, stop1)
+                        : launch_point_kb<SLAMHIP_CELL_CREDIBILIST, false>(a, kb, grid, stream, ev_start, stop1));
   } else {
     return hipErrorInvalidValue;
   }
@@ -750,15 +756,17 @@ hipError_t launch_nbr_check(const double *payload, int width, int height, int pi
   return hipGetLastError();
 }
 
-// ---- the probability plane of a TBM map (DeviceMap::d_prob) ---------------------------------------------------
+// ---- the probability plane of a TBM / CREDIBILIST map (DeviceMap::d_prob) ---------------------------------------------------
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_prob_build(const double4 *__restrict__ cells, double *__restrict__ prob, int pitch, int x0,
                                                    int y0, int w, int h) {
   const int x = x0 + (int)(blockIdx.x * 256 + threadIdx.x), y = y0 + (int)blockIdx.y;
   if (x >= x0 + w || y >= y0 + h) return;
   const size_t at = (size_t)y * pitch + x;
   const double4 v = cells[at];
-  prob[at] = tbm_discrepancy_probability(v.x, v.y, v.z, v.w);
+  prob[at] = cell_probability<MODEL>(SLAMHIP_OIE_DISCREPANCY, v);
 }
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_prob_cells(const double4 *__restrict__ cells, double *__restrict__ prob, int width, int height,
                                                    int pitch, int n, const int *__restrict__ coords) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -767,36 +775,43 @@ __global__ __launch_bounds__(256) void k_prob_cells(const double4 *__restrict__ 
   if ((unsigned)x >= (unsigned)width || (unsigned)y >= (unsigned)height) return;
   const size_t at = (size_t)y * pitch + x;
   const double4 v = cells[at];
-  prob[at] = tbm_discrepancy_probability(v.x, v.y, v.z, v.w);
+  prob[at] = cell_probability<MODEL>(SLAMHIP_OIE_DISCREPANCY, v);
 }
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_prob_check(const double4 *__restrict__ cells, const double *__restrict__ prob, int width,
                                                    int pitch, unsigned long long *count) {
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (x >= width) return;
   const size_t at = (size_t)y * pitch + x;
   const double4 v = cells[at];
-  const double want = tbm_discrepancy_probability(v.x, v.y, v.z, v.w);
+  const double want = cell_probability<MODEL>(SLAMHIP_OIE_DISCREPANCY, v);
   if (__double_as_longlong(want) != __double_as_longlong(prob[at])) atomicAdd(count, 1ull);
 }
-hipError_t launch_prob_build(const double *payload, double *prob, int width, int height, int pitch, int x0, int y0, int w, int h,
+hipError_t launch_prob_build(int model, const double *payload, double *prob, int width, int height, int pitch, int x0, int y0, int w, int h,
                              hipStream_t stream) {
   const int xa = x0 < 0 ? 0 : x0, ya = y0 < 0 ? 0 : y0;
   const int xb = x0 + w > width ? width : x0 + w, yb = y0 + h > height ? height : y0 + h;
   if (xb <= xa || yb <= ya) return hipSuccess;
-  hipLaunchKernelGGL(k_prob_build, dim3((xb - xa + 255) / 256, yb - ya), dim3(256), 0, stream,
+  if (!cell_is_belief(model)) return hipErrorInvalidValue;
+  const auto k = model == SLAMHIP_CELL_CREDIBILIST ? k_prob_build<SLAMHIP_CELL_CREDIBILIST> : k_prob_build<SLAMHIP_CELL_TBM>;
+  hipLaunchKernelGGL(k, dim3((xb - xa + 255) / 256, yb - ya), dim3(256), 0, stream,
                      reinterpret_cast<const double4 *>(payload), prob, pitch, xa, ya, xb - xa, yb - ya);
   return hipGetLastError();
 }
-hipError_t launch_prob_cells(const double *payload, double *prob, int width, int height, int pitch, int n, const int *d_coords,
+hipError_t launch_prob_cells(int model, const double *payload, double *prob, int width, int height, int pitch, int n, const int *d_coords,
                              hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_prob_cells, dim3((n + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const double4 *>(payload), prob,
+  if (!cell_is_belief(model)) return hipErrorInvalidValue;
+  const auto k = model == SLAMHIP_CELL_CREDIBILIST ? k_prob_cells<SLAMHIP_CELL_CREDIBILIST> : k_prob_cells<SLAMHIP_CELL_TBM>;
+  hipLaunchKernelGGL(k, dim3((n + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const double4 *>(payload), prob,
                      width, height, pitch, n, d_coords);
   return hipGetLastError();
 }
-hipError_t launch_prob_check(const double *payload, const double *prob, int width, int height, int pitch,
+hipError_t launch_prob_check(int model, const double *payload, const double *prob, int width, int height, int pitch,
                              unsigned long long *d_count, hipStream_t stream) {
-  hipLaunchKernelGGL(k_prob_check, dim3((width + 255) / 256, height), dim3(256), 0, stream,
+  if (!cell_is_belief(model)) return hipErrorInvalidValue;
+  const auto k = model == SLAMHIP_CELL_CREDIBILIST ? k_prob_check<SLAMHIP_CELL_CREDIBILIST> : k_prob_check<SLAMHIP_CELL_TBM>;
+  hipLaunchKernelGGL(k, dim3((width + 255) / 256, height), dim3(256), 0, stream,
                      reinterpret_cast<const double4 *>(payload), prob, width, pitch, d_count);
   return hipGetLastError();
 }

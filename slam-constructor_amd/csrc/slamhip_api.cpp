@@ -106,7 +106,7 @@ static int check_cfg(const DeviceMap &m, const slamhip_spe_cfg *cfg) {
   }
   if (m.cell_model == SLAMHIP_CELL_GMAPPING)
     return invalid("obstacle OOPE over a GMAPPING payload: upload prob_occ as an OCC map");
-  if (m.cell_model == SLAMHIP_CELL_TBM && cfg->oie != SLAMHIP_OIE_DISCREPANCY)
+  if (cell_is_belief(m.cell_model) && cfg->oie != SLAMHIP_OIE_DISCREPANCY)
     return invalid("OccupancyOIE over TBM cells: upload occupancy().prob_occ as an OCC map");
   return SLAMHIP_OK;
 }
@@ -124,20 +124,20 @@ static int map_nbr_masks(slamhip_ctx *ctx, DeviceMap &m, double th) {
   return SLAMHIP_OK;
 }
 
-// The probability plane of a dense TBM window (DeviceMap::d_prob): derived on the context's stream by the first
+// The probability plane of a dense TBM / CREDIBILIST window (DeviceMap::d_prob): derived on the context's stream by the first
 // 1-cell scorer call that finds none, and waited for (like the masks above); from then on the map's writers keep it.
 static int map_prob_plane(slamhip_ctx *ctx, DeviceMap &m) {
   if (m.prob_ok) return SLAMHIP_OK;
   if (!m.d_prob) SLAMHIP_CHECK(hipMalloc(&m.d_prob, sizeof(double) * (size_t)m.pitch * m.height));
-  SLAMHIP_CHECK(launch_prob_build(m.d_payload, m.d_prob, m.width, m.height, m.pitch, 0, 0, m.width, m.height, ctx->stream));
+  SLAMHIP_CHECK(launch_prob_build(m.cell_model, m.d_payload, m.d_prob, m.width, m.height, m.pitch, 0, 0, m.width, m.height, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   m.prob_ok = true;
   return SLAMHIP_OK;
 }
 // whether a scorer configuration over this map reads the plane: the obstacle OOPE under the discrepancy OIE (the only
-// OIE a TBM map is scored with, check_cfg) on a dense TBM window, unless SLAMHIP_OPT_TBM_PLANE is off
+// OIE a TBM or CREDIBILIST map is scored with, check_cfg) on a dense window of such cells, unless SLAMHIP_OPT_TBM_PLANE is off
 static bool wants_prob_plane(const slamhip_ctx *ctx, const DeviceMap &m, const slamhip_spe_cfg *cfg) {
-  return ctx->tbm_plane && m.cell_model == SLAMHIP_CELL_TBM && m.bytes > 0 && cfg->oope == SLAMHIP_OOPE_OBSTACLE &&
+  return ctx->tbm_plane && cell_is_belief(m.cell_model) && m.bytes > 0 && cfg->oope == SLAMHIP_OOPE_OBSTACLE &&
          cfg->oie == SLAMHIP_OIE_DISCREPANCY;
 }
 
@@ -202,7 +202,7 @@ static int fill_args(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cfg,
     const int rc = map_prob_plane(ctx, m);
     if (rc) return rc;
     a->map.payload = m.d_prob;
-    a->map.unknown[0] = tbm_discrepancy_probability(m.unknown[0], m.unknown[1], m.unknown[2], m.unknown[3]);
+    a->map.unknown[0] = belief_probability(m.cell_model, m.unknown[0], m.unknown[1], m.unknown[2], m.unknown[3]);
     a->oie = SLAMHIP_OIE_OCCUPANCY;
     a->model_override = SLAMHIP_CELL_OCC;
   }
@@ -823,7 +823,7 @@ int slamhip_map_bind(slamhip_ctx *ctx, int map_id, int cell_model, int width, in
                      int origin_x, int origin_y, double scale, const double *unknown_payload) {
   if (!ctx) return invalid("null ctx");
   if (map_id < 0 || map_id > 4095) return invalid("map_id out of range [0, 4095]");
-  if (cell_model < SLAMHIP_CELL_OCC || cell_model > SLAMHIP_CELL_GMAPPING)
+  if (cell_model < SLAMHIP_CELL_OCC || cell_model > SLAMHIP_CELL_CREDIBILIST)
     return invalid("unknown cell model");
   if (width <= 0 || height <= 0 || !(scale > 0) || !unknown_payload)
     return invalid("bad map geometry");
@@ -963,7 +963,7 @@ int slamhip_map_upload_window(slamhip_ctx *ctx, int map_id, int x0, int y0, int 
   if (e == hipSuccess && m->nbr_ok)  // the masks of the written cells and of the ring around them
     e = launch_nbr_build(m->d_payload, m->width, m->height, m->pitch, m->nbr_th, x0 - 1, y0 - 1, w + 2, h + 2, ctx->stream);
   if (e == hipSuccess && m->prob_ok)  // the probability plane of the written cells
-    e = launch_prob_build(m->d_payload, m->d_prob, m->width, m->height, m->pitch, x0, y0, w, h, ctx->stream);
+    e = launch_prob_build(m->cell_model, m->d_payload, m->d_prob, m->width, m->height, m->pitch, x0, y0, w, h, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   hipFree(d_tmp);
   if (e != hipSuccess) return hip_fail(e, "map_upload_window");
@@ -1020,7 +1020,7 @@ int slamhip_map_apply_dirty(slamhip_ctx *ctx, int map_id, int n, const int *coor
   if (m->nbr_ok)
     SLAMHIP_CHECK(launch_nbr_cells(m->d_payload, m->width, m->height, m->pitch, m->nbr_th, n, ctx->d_dirty_xy, ctx->stream));
   if (m->prob_ok)
-    SLAMHIP_CHECK(launch_prob_cells(m->d_payload, m->d_prob, m->width, m->height, m->pitch, n, ctx->d_dirty_xy, ctx->stream));
+    SLAMHIP_CHECK(launch_prob_cells(m->cell_model, m->d_payload, m->d_prob, m->width, m->height, m->pitch, n, ctx->d_dirty_xy, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return SLAMHIP_OK;
 }

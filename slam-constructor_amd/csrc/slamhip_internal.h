@@ -59,6 +59,25 @@ __host__ __device__ inline double tbm_discrepancy_probability(double U, double E
   return 1.0 - (unknown / 2 + known_discrepancy);
 }
 
+// CredibilistCell::discrepancy of the same observation, 1 - it (slams/credibilist/grid_cell.h:31-40): the per-beam
+// probability of a CREDIBILIST cell.  disjunctive((0,0,1,0), cell) before normalisation = (U+E, 0, O+C, 0)
+// (transferable_belief_model.h:145-162: the products with the observation's zero masses add 0.0), normalize() divides by
+// the total mass or resets a massless belief to (1,0,0,0), whose occupied() is 0.  The outer 1 - (1 - s) is the cell's
+// `1.0 - score` under DiscrepancyOIE's `1.0 - discrepancy`: not s in floating point.
+__host__ __device__ inline double credibilist_probability(double U, double E, double O, double Cc) {
+  const double t0 = U + E, t2 = O + Cc;
+  const double tot = ((t0 + 0.0) + t2) + 0.0;
+  const double s = (tot == 0.0) ? 0.0 : t2 / tot;
+  return 1.0 - (1.0 - s);
+}
+// whether a cell model's payload is a (u, e, o, c) belief; the probability of such a cell under the discrepancy OIE
+__host__ __device__ inline bool cell_is_belief(int model) {
+  return model == SLAMHIP_CELL_TBM || model == SLAMHIP_CELL_CREDIBILIST;
+}
+__host__ __device__ inline double belief_probability(int model, double U, double E, double O, double Cc) {
+  return model == SLAMHIP_CELL_CREDIBILIST ? credibilist_probability(U, E, O, Cc) : tbm_discrepancy_probability(U, E, O, Cc);
+}
+
 // Filtered scan, structure-of-arrays (coalesced per-beam loads), tot_w = sequential sum of
 // weights in beam order computed once on the host (pose independent).
 struct ScanView {
@@ -125,7 +144,7 @@ __host__ __device__ inline unsigned mu_settle_class(double c0, long long unknown
 
 inline int cell_doubles(int model) { return model == SLAMHIP_CELL_OCC ? 1 : 4; }
 inline int cell_stride_host(int model) {
-  return model == SLAMHIP_CELL_TBM ? 4 : (model == SLAMHIP_CELL_GMAPPING ? 3 : 1);
+  return cell_is_belief(model) ? 4 : (model == SLAMHIP_CELL_GMAPPING ? 3 : 1);
 }
 
 // ---- launchers (score_kernels.hip) ---------------------------------------------------------
@@ -180,20 +199,21 @@ struct DeviceMap {
   bool nbr_ok = false;
   double nbr_th = 0.0;
   double nbr_other_th = 0.0;  // the last threshold a scorer asked for that was NOT the masks' (fill_args)
-  // TBM maps: the PROBABILITY PLANE -- one double per cell = tbm_discrepancy_probability of the cell (r06, VERDICT r5
+  // TBM / CREDIBILIST maps: the PROBABILITY PLANE -- one double per cell = belief_probability of the cell (r06, VERDICT r5
   // item 5).  The 1-cell scorers gather 8 bytes from it instead of the 32-byte cell and ~16 flops + a division per
   // (pose, beam); derived by the first scorer call that finds none (map_prob_plane), then kept by every writer: K6's
   // mu_cell_store (MuArgs::prob), uploads and the dirty log re-derive what they wrote; a re-bind drops it.
   double *d_prob = nullptr;
   bool prob_ok = false;
 };
-// (re)derives the plane over [x0, x0 + w) x [y0, y0 + h) (clipped) / over n listed cells (d_coords: x, y pairs)
-hipError_t launch_prob_build(const double *payload, double *prob, int width, int height, int pitch, int x0, int y0, int w, int h,
+// (re)derives the plane over [x0, x0 + w) x [y0, y0 + h) (clipped) / over n listed cells (d_coords: x, y pairs);
+// model: SLAMHIP_CELL_TBM / _CREDIBILIST = which of the two functions the map's plane holds (anything else is an error)
+hipError_t launch_prob_build(int model, const double *payload, double *prob, int width, int height, int pitch, int x0, int y0, int w, int h,
                              hipStream_t stream);
-hipError_t launch_prob_cells(const double *payload, double *prob, int width, int height, int pitch, int n, const int *d_coords,
+hipError_t launch_prob_cells(int model, const double *payload, double *prob, int width, int height, int pitch, int n, const int *d_coords,
                              hipStream_t stream);
 // cells whose stored value differs from the derived one (testing), added to *d_count
-hipError_t launch_prob_check(const double *payload, const double *prob, int width, int height, int pitch,
+hipError_t launch_prob_check(int model, const double *payload, const double *prob, int width, int height, int pitch,
                              unsigned long long *d_count, hipStream_t stream);
 // (re)derives the masks of the cells of [x0, x0 + w) x [y0, y0 + h) (clipped to the window) from the occupancies
 hipError_t launch_nbr_build(double *payload, int width, int height, int pitch, double th, int x0, int y0, int w, int h,

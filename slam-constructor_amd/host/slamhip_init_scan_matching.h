@@ -14,8 +14,12 @@
 #include "utils/init_scan_matching.h"
 #include "slamhip_reference_adapter.h"
 
+// cell_model >= 0: the payload model of the map instead of the one "slam/mapping/grid/area/type" names (a world whose
+// cell class is fixed by its factory: slamhip_credibilist_slam.h), with the reader of its cells' belief masses
 inline std::shared_ptr<GridScanMatcher> init_hip_scan_matcher(const PropertiesProvider &props,
-                                                              slamhip_ctx *ctx = nullptr, int map_id = 0) {
+                                                              slamhip_ctx *ctx = nullptr, int map_id = 0,
+                                                              int cell_model = -1,
+                                                              HipMapMirror::BeliefReader belief_reader = nullptr) {
   if (!ctx) slamhip_or_die(slamhip_ctx_create(props.get_int("slam/scmtch/hip/device", 0), &ctx), "ctx_create");
   // the reference's own SPE: still does filter_scan on the host and prints "Used OIE/OOPE/SWP"
   auto spe = init_spe(props);
@@ -64,13 +68,15 @@ inline std::shared_ptr<GridScanMatcher> init_hip_scan_matcher(const PropertiesPr
   const auto area = props.get_str("slam/mapping/grid/area/type", "<undefined>");
   // TBM cells score through their belief masses; every other model (and the occupancy OIE) through
   // occupancy().prob_occ
-  const int model = (area.rfind("tbm", 0) == 0 && cfg.oie == SLAMHIP_OIE_DISCREPANCY) ? SLAMHIP_CELL_TBM
+  const int model = cell_model >= 0 ? cell_model
+                    : (area.rfind("tbm", 0) == 0 && cfg.oie == SLAMHIP_OIE_DISCREPANCY) ? SLAMHIP_CELL_TBM
                                                                                         : SLAMHIP_CELL_OCC;
   const auto w = props.get_str(Slam_SM_NS + "spe/wmpp/weighting/type", "even");
   const int weighting = w == "viny" ? 1 : (w == "ahr" ? 2 : 0);
   const auto gm = props.get_str("slam/mapping/grid/type", "<undefined>");
   const bool bounded = gm == "plain" || gm == "lazy_tiled";
   auto mirror = std::make_shared<HipMapMirror>(ctx, map_id, model, bounded);
+  mirror->set_belief_reader(belief_reader);
   auto gsm = std::make_shared<HipGridScanMatcher>(spe, ctx, m, mirror, weighting);
   if (props.get_str(Slam_SM_NS + "spe/type", "<undefined>") == "wmpp")  // (init_spe's own parameters, :99-100)
     gsm->set_filter_params(props.get_uint(Slam_SM_NS + "spe/wmpp/sp_skip_rate", 0),

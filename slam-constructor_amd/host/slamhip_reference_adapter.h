@@ -167,6 +167,13 @@ public:
   HipMapMirror(slamhip_ctx *ctx, int map_id, int cell_model, bool bounded)
       : _ctx{ctx}, _id{map_id}, _model{cell_model}, _bounded{bounded} {}
 
+  // SLAMHIP_CELL_CREDIBILIST: the belief masses (u, e, o, c) of a cell.  CredibilistCell is no TbmBaseCell, and its
+  // header (slams/credibilist/grid_cell.h) pulls in TBM_prob_conversion.h, which DEFINES non-inline functions -- it may
+  // be included by one translation unit only, so this header does not: slamhip_credibilist_slam.h, which does,
+  // hands the reader over.
+  using BeliefReader = void (*)(const GridCell &, double *out4);
+  void set_belief_reader(BeliefReader r) { _belief_reader = r; }
+
   int id() const { return _id; }
   bool bounded() const { return _bounded; }
   // counters for tests / logs: full uploads, re-binds on growth, cells sent through the dirty path
@@ -234,9 +241,15 @@ public:
   }
 
 private:
-  int stride() const { return _model == SLAMHIP_CELL_TBM ? 4 : (_model == SLAMHIP_CELL_GMAPPING ? 3 : 1); }
+  int stride() const {
+    return (_model == SLAMHIP_CELL_TBM || _model == SLAMHIP_CELL_CREDIBILIST) ? 4 : (_model == SLAMHIP_CELL_GMAPPING ? 3 : 1);
+  }
   void payload(const GridCell &c, double *out) const {
-    if (_model == SLAMHIP_CELL_TBM) {
+    if (_model == SLAMHIP_CELL_CREDIBILIST) {
+      if (!_belief_reader)
+        slamhip_or_die(SLAMHIP_ERR_UNSUPPORTED, "credibilist cells: no belief reader (include slamhip_credibilist_slam.h)");
+      _belief_reader(c, out);
+    } else if (_model == SLAMHIP_CELL_TBM) {
       const auto &b = static_cast<const TbmBaseCell &>(c).belief();
       out[0] = b.unknown(); out[1] = b.empty(); out[2] = b.occupied(); out[3] = b.conflict();
     } else if (_model == SLAMHIP_CELL_GMAPPING) {
@@ -296,6 +309,7 @@ private:
   }
   slamhip_ctx *_ctx;
   int _id, _model;
+  BeliefReader _belief_reader = nullptr;
   bool _bounded;
   bool _resident = false;
   int _w = -1, _h = -1, _ox = 0, _oy = 0;
@@ -586,7 +600,7 @@ private:
   void refresh_geometry() {
     int model = 0;
     slamhip_or_die(slamhip_map_info(_ctx, _id, &model, &_w, &_h, &_ox, &_oy, nullptr, nullptr), "map_info");
-    _stride = model == SLAMHIP_CELL_TBM ? 4 : (model == SLAMHIP_CELL_GMAPPING ? 3 : 1);
+    _stride = (model == SLAMHIP_CELL_TBM || model == SLAMHIP_CELL_CREDIBILIST) ? 4 : (model == SLAMHIP_CELL_GMAPPING ? 3 : 1);
     set_width(_w);
     set_height(_h);
   }

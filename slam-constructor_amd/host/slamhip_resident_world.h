@@ -138,6 +138,32 @@ private:
   std::vector<int> _occ;
 };
 
+// the scan adder's half of a resident world's configuration: init_occ_estimator / init_omqe / init_scan_adder
+// (init_occupancy_mapping.h:38-92) and whether the strict mode takes the raw provider's end points
+inline void slamhip_init_resident_adder(const PropertiesProvider &props, HipResidentWorld::Config &cfg) {
+  cfg.adder.base_occupied_prob = props.get_dbl("slam/occupancy_estimator/base_occupied/prob", 0.95);
+  cfg.adder.base_occupied_qual = props.get_dbl("slam/occupancy_estimator/base_occupied/qual", 1.0);
+  cfg.adder.base_empty_prob = props.get_dbl("slam/occupancy_estimator/base_empty/prob", 0.01);
+  cfg.adder.base_empty_qual = props.get_dbl("slam/occupancy_estimator/base_empty/qual", 1.0);
+  const auto est = props.get_str("slam/occupancy_estimator/type", "const");
+  if (est != "const" && est != "area") {
+    std::cerr << "Unknown estimator type: " << est << std::endl;
+    std::exit(-1);
+  }
+  cfg.adder.occupancy_estimator = est == "area" ? 1 : 0;
+  // init_omqe (init_occupancy_mapping.h:64-80; the key really ends in "typetype")
+  const auto omqe = props.get_str("slam/mapping/observation_quality_estimator/typetype", "idle");
+  if (omqe != "idle" && omqe != "ahr") {
+    std::cerr << "[ERROR] Unknown OMQE type: " << omqe << std::endl;
+    std::exit(-1);
+  }
+  cfg.omqe = omqe == "ahr" ? 1 : 0;
+  cfg.adder.blur = props.get_dbl("slam/mapping/blur", 0.0);
+  cfg.adder.max_range = props.get_dbl("slam/mapping/max_range", std::numeric_limits<double>::infinity());
+  cfg.adder.scan_quality = 1.0;
+  cfg.raw_exact = props.get_bool(Slam_SM_NS + "hip/strict", false) && !props.get_bool(Slam_SM_NS + "hip/trig_cache", false);
+}
+
 // the factory next to init_1h_slam (src/utils/init_slam.h:12-25): same properties
 inline std::shared_ptr<HipResidentWorld> init_hip_resident_1h_slam(const PropertiesProvider &props,
                                                                    slamhip_ctx *ctx = nullptr, int map_id = 0) {
@@ -172,28 +198,7 @@ inline std::shared_ptr<HipResidentWorld> init_hip_resident_1h_slam(const Propert
     std::cerr << "Unknown occupied area type: " << area << std::endl;
     std::exit(-1);
   }
-  // init_occ_estimator / init_scan_adder (init_occupancy_mapping.h:38-92)
-  cfg.adder.base_occupied_prob = props.get_dbl("slam/occupancy_estimator/base_occupied/prob", 0.95);
-  cfg.adder.base_occupied_qual = props.get_dbl("slam/occupancy_estimator/base_occupied/qual", 1.0);
-  cfg.adder.base_empty_prob = props.get_dbl("slam/occupancy_estimator/base_empty/prob", 0.01);
-  cfg.adder.base_empty_qual = props.get_dbl("slam/occupancy_estimator/base_empty/qual", 1.0);
-  const auto est = props.get_str("slam/occupancy_estimator/type", "const");
-  if (est != "const" && est != "area") {
-    std::cerr << "Unknown estimator type: " << est << std::endl;
-    std::exit(-1);
-  }
-  cfg.adder.occupancy_estimator = est == "area" ? 1 : 0;
-  // init_omqe (init_occupancy_mapping.h:64-80; the key really ends in "typetype")
-  const auto omqe = props.get_str("slam/mapping/observation_quality_estimator/typetype", "idle");
-  if (omqe != "idle" && omqe != "ahr") {
-    std::cerr << "[ERROR] Unknown OMQE type: " << omqe << std::endl;
-    std::exit(-1);
-  }
-  cfg.omqe = omqe == "ahr" ? 1 : 0;
-  cfg.adder.blur = props.get_dbl("slam/mapping/blur", 0.0);
-  cfg.adder.max_range = props.get_dbl("slam/mapping/max_range", std::numeric_limits<double>::infinity());
-  cfg.adder.scan_quality = 1.0;
-  cfg.raw_exact = props.get_bool(Slam_SM_NS + "hip/strict", false) && !props.get_bool(Slam_SM_NS + "hip/trig_cache", false);
+  slamhip_init_resident_adder(props, cfg);
   auto gsm = std::dynamic_pointer_cast<HipGridScanMatcher>(init_hip_scan_matcher(props, ctx, map_id));
   gsm->set_resident_map(true);
   return std::make_shared<HipResidentWorld>(ctx, gsm, cfg);
