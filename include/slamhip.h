@@ -176,6 +176,43 @@ int slamhip_map_info(slamhip_ctx *ctx, int map_id, int *cell_model, int *width, 
 int slamhip_map_download_window(slamhip_ctx *ctx, int map_id, int x0, int y0, int w, int h,
                                 double *payload_out);
 
+/* ---------------------------------------------------------------- map render (csrc/map_render.hip)
+ * A resident map as the bytes its consumers take, one byte per cell, converted ON THE DEVICE: a kernel reads the
+ * cells (8 or 32 bytes each) and writes w * h bytes into a buffer the context owns, ONE asynchronous copy and one wait
+ * bring them to `out` -- instead of the whole payload over PCIe and a conversion on the host.
+ *   SLAMHIP_RENDER_OCCGRID  int8, rows bottom-up (y ascending): nav_msgs::OccupancyGrid::data as
+ *                           OccupancyGridPublisher::on_map_update fills it (src/ros/occupancy_grid_publisher.h:37-46):
+ *                           value == -1 ? -1 : (int)(value * 100).  The reference's conversion is undefined for a
+ *                           value that is not finite: such a cell reads -1 here (a finite value whose hundredfold
+ *                           leaves the range of int saturates there before it is narrowed).
+ *   SLAMHIP_RENDER_PGM      uint8, rows top-down (largest y first), pixels only, no header: what
+ *                           GridMapToPgmDumber::dump_map writes behind its header (src/utils/map_dumpers.h:78-87):
+ *                           (unsigned char)(255 * (1 - (occ == -1 ? 0.5 : bound_value(0, occ, 1)))); a NaN occupancy
+ *                           clamps to 1 as in the reference.
+ * value / occ = the cell's GridCell::occupancy().prob_occ: the payload's first double for OCC and GMAPPING cells (a
+ * never-observed GMAPPING cell holds -1); for CREDIBILIST o + 0.5 u (TBM_to_O, slams/credibilist/
+ * TBM_prob_conversion.h:8-10); for TBM the conversion of the cell CLASS, which the payload does not name -- occ_kind:
+ *   SLAMHIP_OCC_TBM_CONSISTENT    TbmOccConsistentCell (tbm_grid_cells.h:89-93): o / (o + e); a cell with the
+ *                                 never-updated payload (1, 0, 0) reads 0.5 (the prototype's occupancy).  The
+ *                                 reference's cell has that payload too after updates of zero quality only, and reads
+ *                                 0 / 0 then: the one case where this value is not the reference's.
+ *   SLAMHIP_OCC_TBM_UNKNOWN_EVEN  TbmUnknownEvenOccCell (:104-106): o + 0.5 u
+ * occ_kind must be 0 for every other model. */
+enum { SLAMHIP_RENDER_OCCGRID = 0, SLAMHIP_RENDER_PGM = 1 };
+enum { SLAMHIP_OCC_TBM_CONSISTENT = 0, SLAMHIP_OCC_TBM_UNKNOWN_EVEN = 1 };
+/* Window [x0, x0 + w) x [y0, y0 + h) in INTERNAL coordinates of a bound map (like slamhip_map_download_window), out:
+ * w * h bytes.  Replaces the cell loops of occupancy_grid_publisher.h:40-46 and map_dumpers.h:78-87 over
+ * HipResidentMapView::operator[].  Queued on the context's stream, hence behind every deferred map update; writes
+ * nothing to the map.  SLAMHIP_ERR_INVALID (nothing is launched): null out, unknown format, a non-zero occ_kind on a
+ * map that is not TBM (or one that is neither kind on a TBM map), a window outside the bound map, an unbound map.
+ * While slamhip_profile_enable is on, the kernel's own time is added to slamhip_profile_read's kernel_ms_total. */
+int slamhip_map_render(slamhip_ctx *ctx, int map_id, int format, int occ_kind, int x0, int y0, int w, int h,
+                       void *out);
+/* Host only, no GPU: the same conversion over n cells, payload = n x host stride doubles of cell_model (OCC 1, TBM and
+ * CREDIBILIST 4, GMAPPING 3), out = n bytes in cell order.  The kernels and this entry share one definition of the
+ * occupancy and of the two byte rules. */
+int slamhip_render_cells(int cell_model, int occ_kind, int format, int n, const double *payload, void *out);
+
 /* ---------------------------------------------------------------- map update (kernel K6)
  * Replaces GridMapScanAdder::append_scan (src/core/maps/grid_map_scan_adders.h:54-75) with
  * WallDistanceBlurringScanAdder::handle_scan_point (:138-172) and ConstOccupancyEstimator
@@ -558,6 +595,14 @@ int slamhip_gmapping_enable_particle_maps(slamhip_gmapping *g, int map_id, const
  * aux2 = (hits, tries) per cell; either may be NULL */
 int slamhip_gmapping_particle_map_download(slamhip_gmapping *g, int particle, int x0, int y0, int w, int h,
                                            double *payload3, double *aux2);
+/* The same EXTERNAL window of one particle's map as slamhip_map_render's bytes (format as there; the cells are
+ * GMAPPING cells), out: w * h bytes: the map observers' cell loops (occupancy_grid_publisher.h:40-46,
+ * map_dumpers.h:78-87) over a particle's LazyTiledGridMap, 1 byte per cell to the host instead of the download's 40.
+ * Cells outside the pool's extent read as the never-observed cell: -1 / 127.  Only prob_occ is read; the update
+ * counters do not enter.  SLAMHIP_ERR_INVALID: a filter without particle maps, an unknown particle, null out, unknown
+ * format, an empty window. */
+int slamhip_gmapping_particle_map_render(slamhip_gmapping *g, int particle, int format, int x0, int y0, int w, int h,
+                                         void *out);
 /* The append half of GmappingWorld::handle_observation (gmapping_world.h:93-97) for a set of local
  * particles at once: the raw scan is appended to the map of particle particles[k] from poses3[3k..3k+2] --
  * ONE batched K6 over all (particle, beam) pairs, copy-on-write first.  The filter step does this itself for

@@ -30,6 +30,8 @@ POSE_TRIG_DEVICE, POSE_TRIG_HOST, POSE_TRIG_RAW_EXACT = 0, 1, 2
 (OPT_LOW_LATENCY, OPT_STAGE_POSES, OPT_FILTER_CHAINS, OPT_K6_PATH, OPT_K6_BATCH_FAST, OPT_K6_BATCH_KEY64,
  OPT_RESIDENT_CHAINS, OPT_TBM_PLANE, OPT_INERT_TAIL) = range(9)
 TRIG_RAW, TRIG_CACHED = 0, 1
+RENDER_OCCGRID, RENDER_PGM = 0, 1  # slamhip_map_render formats: int8 rows bottom-up / uint8 grey rows top-down
+OCC_TBM_CONSISTENT, OCC_TBM_UNKNOWN_EVEN = 0, 1  # the TBM cell class whose tbm2occ a render applies
 STRIDE = {CELL_OCC: 1, CELL_TBM: 4, CELL_GMAPPING: 3, CELL_CREDIBILIST: 4}
 
 EXPORTS = """slamhip_last_error slamhip_device_count slamhip_ctx_create slamhip_ctx_destroy
@@ -54,7 +56,8 @@ slamhip_gmapping_carry_fix slamhip_gmapping_carry_commit slamhip_gmapping_match_
 slamhip_gmapping_step_sharded slamhip_matcher_process_scan_batch slamhip_matcher_batch_stats slamhip_scan_store slamhip_scan_select
 slamhip_shard_attach slamhip_shard_exchange slamhip_shard_p2p_stats slamhip_shard_set_timeout slamhip_gmapping_match_abort
 slamhip_gmapping_migration_stats slamhip_map_append_scan_q slamhip_omqe_quality slamhip_scan_filter_upload
-slamhip_scan_set_angles slamhip_libm_variant slamhip_libm_eval slamhip_map_append_scan_raw""".split()
+slamhip_scan_set_angles slamhip_libm_variant slamhip_libm_eval slamhip_map_append_scan_raw
+slamhip_map_render slamhip_gmapping_particle_map_render slamhip_render_cells""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -260,6 +263,9 @@ def load(testing=False):
     L.slamhip_gmapping_carry_commit.argtypes = [vp, C.POINTER(CarryRecord), i]
     L.slamhip_gmapping_match_finish.argtypes = [vp, _dp]
     L.slamhip_gmapping_step_sharded.argtypes = [vp, i, i, _dp, _dp, _ip, _dp, C.c_uint32, _ip, up]
+    L.slamhip_map_render.argtypes = [vp, i, i, i, i, i, i, i, vp]
+    L.slamhip_gmapping_particle_map_render.argtypes = [vp, i, i, i, i, i, i, vp]
+    L.slamhip_render_cells.argtypes = [i, i, i, i, _dp, vp]
     _libs[testing] = L
     return L
 
@@ -385,6 +391,23 @@ def pf_heaviest(w):
     r = C.c_int(0)
     _check(load().slamhip_pf_heaviest(w.size, _d(w), C.byref(r)))
     return r.value
+
+
+def _render_dtype(fmt):
+    return np.uint8 if fmt == RENDER_PGM else np.int8
+
+
+def render_cells(cell_model, payload, fmt, occ_kind=0):
+    """slamhip_render_cells, on the host: payload[..., STRIDE[cell_model]] -> one byte per cell (int8 for
+    RENDER_OCCGRID, uint8 for RENDER_PGM) in the payload's cell order and shape -- the conversion the render kernels
+    apply, without the row flip of a PGM."""
+    p = _f64(payload)
+    stride = STRIDE.get(cell_model, 1)
+    if p.ndim == 0 or p.shape[-1] != stride:
+        p = p.reshape(-1, stride)
+    out = np.zeros(p.shape[:-1], dtype=_render_dtype(fmt))
+    _check(load().slamhip_render_cells(int(cell_model), int(occ_kind), int(fmt), out.size, _d(p), out.ctypes.data))
+    return out
 
 
 # ---- GPU objects ---------------------------------------------------------------------------------
@@ -516,6 +539,23 @@ class Context:
         _check(self.L.slamhip_map_info(self.h, map_id, *[C.byref(x) for x in v], C.byref(scale), C.byref(grown)))
         return dict(cell_model=v[0].value, width=v[1].value, height=v[2].value, origin=(v[3].value, v[4].value),
                     scale=scale.value, times_grown=grown.value)
+
+    def map_render(self, map_id, fmt, occ_kind=0, window=None):
+        """The map as its consumers' bytes, converted on the device (slamhip_map_render): an (h, w) int8 array with
+        rows bottom-up for RENDER_OCCGRID (nav_msgs::OccupancyGrid::data), uint8 with rows top-down for RENDER_PGM.
+        window = (x0, y0, w, h) in internal coordinates; None = the whole bound map."""
+        if window is None:
+            info = self.map_info(map_id)
+            window = (0, 0, info["width"], info["height"])
+        x0, y0, w, h = (int(v) for v in window)
+        out = np.zeros((max(h, 0), max(w, 0)), dtype=_render_dtype(fmt))
+        _check(self.L.slamhip_map_render(self.h, map_id, int(fmt), int(occ_kind), x0, y0, w, h, out.ctypes.data))
+        return out
+
+    def map_render_pgm(self, map_id, occ_kind=0):
+        """The complete PGM file of the whole map as GridMapToPgmDumber::dump_map writes it (fixtures.pgm_bytes' header)."""
+        img = self.map_render(map_id, RENDER_PGM, occ_kind)
+        return b"P5\n%d\n%d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes()
 
     def upload_map(self, map_id, m):
         """m: any object with cell_model, payload[h,w,stride], origin, scale, unknown."""
@@ -1111,6 +1151,13 @@ class GmappingFilter:
         pay, aux = np.zeros((h, w, 3)), np.zeros((h, w, 2))
         _check(self.L.slamhip_gmapping_particle_map_download(self.h, particle, x0, y0, w, h, _d(pay), _d(aux)))
         return pay, aux
+
+    def particle_map_render(self, particle, fmt, x0, y0, w, h):
+        """The external window of one particle's map as Context.map_render's bytes (slamhip_gmapping_particle_map_render);
+        cells outside the pool's extent read as never observed (-1 / 127)."""
+        out = np.zeros((max(h, 0), max(w, 0)), dtype=_render_dtype(fmt))
+        _check(self.L.slamhip_gmapping_particle_map_render(self.h, particle, int(fmt), x0, y0, w, h, out.ctypes.data))
+        return out
 
     def export_particle_map(self, particle):
         """The LOCAL particle's map as one uint8 array (tile positions + tiles) for another rank."""

@@ -915,6 +915,13 @@ int slamhip_gmapping_particle_map_download(slamhip_gmapping *g, int particle, in
   return tile_pool_download(g->tp, particle, x0, y0, w, h, payload3, aux2);
 }
 
+int slamhip_gmapping_particle_map_render(slamhip_gmapping *g, int particle, int format, int x0, int y0, int w, int h,
+                                         void *out) {
+  if (!g || !g->tp) return bad("per-particle maps are not enabled");
+  if (particle < 0 || particle >= g->count) return bad("particle index out of range");
+  return tile_pool_render(g->tp, particle, format, x0, y0, w, h, out);
+}
+
 int slamhip_gmapping_particle_maps_append(slamhip_gmapping *g, int n_jobs, const int *particles,
                                           const double *poses3, int n_raw, const double *range,
                                           const double *angle, const int *is_occ, long long *n_updates) {

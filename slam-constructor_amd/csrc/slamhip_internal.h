@@ -78,6 +78,54 @@ __host__ __device__ inline double belief_probability(int model, double U, double
   return model == SLAMHIP_CELL_CREDIBILIST ? credibilist_probability(U, E, O, Cc) : tbm_discrepancy_probability(U, E, O, Cc);
 }
 
+// A cell's OCCUPANCY: what the reference's (double)map[c] / map.occupancy(c) -- GridCell::occupancy().prob_occ -- holds
+// for the cell whose payload starts (p0, p1, p2).  One definition for the render kernels (map_render.hip) and the host
+// (slamhip_render_cells), the reference's operations in its order:
+//   OCC          p0
+//   GMAPPING     p0 (a never-observed cell holds -1, gmapping_grid_cell.h:14)
+//   TBM, kind 0  TbmOccConsistentCell::tbm2occ (tbm_grid_cells.h:89-93): o / (o + e)
+//   TBM, kind 1  TbmUnknownEvenOccCell::tbm2occ (:104-106): o + 0.5 * u
+//   CREDIBILIST  TBM_to_O (slams/credibilist/TBM_prob_conversion.h:8-10): o + 0.5 * u
+// A TBM cell of kind 0 with the never-updated payload (u, e, o) == (1, 0, 0) reports 0.5: the reference's cell keeps
+// its prototype's Occupancy{0.5, 1} until the first valid observation (tbm_grid_cells.h:10-19), the rule
+// HipResidentMapView::set_cell uses.  The reference's cell holds the SAME payload after being updated only by
+// observations of zero quality, and then reports 0 / 0 = NaN: there this value departs from the reference (the payload
+// does not tell the two cells apart).  occ_kind is 0 for every model but TBM (the callers check).
+__host__ __device__ inline double cell_occupancy(int model, int occ_kind, double p0, double p1, double p2) {
+  if (model == SLAMHIP_CELL_TBM && occ_kind == SLAMHIP_OCC_TBM_CONSISTENT) {
+    if (p0 == 1.0 && p1 == 0.0 && p2 == 0.0) return 0.5;
+    const double qual = p2 + p1;
+    return p2 / qual;
+  }
+  if (cell_is_belief(model)) return p2 + 0.5 * p0;
+  return p0;
+}
+// OccupancyGridPublisher::on_map_update's cell (src/ros/occupancy_grid_publisher.h:42-44): `int cell_value =
+// value == -1 ? -1 : value * 100`, pushed into an int8 vector.  The reference's conversion is undefined for a value
+// that is not finite or whose hundredfold leaves the range of int; here a non-finite occupancy writes -1 (unknown) and a
+// finite one saturates at the ends of int before it is narrowed, the same on the host and the device.
+__host__ __device__ inline signed char render_occgrid(double v) {
+  if (v == -1) return (signed char)-1;
+  const double t = v * 100;
+  if (!(t - t == 0.0)) return (signed char)-1;  // NaN, +-inf
+  const int c = t >= 2147483647.0 ? 2147483647 : (t <= -2147483648.0 ? (-2147483647 - 1) : (int)t);
+  return (signed char)c;
+}
+// GridMapToPgmDumber::dump_map's pixel (src/utils/map_dumpers.h:80-82): bound_value is std::max(left, std::min(right,
+// v)) (math_utils.h:33-35), i.e. the two compares below -- a NaN occupancy clamps to 1 and paints black, as there.
+__host__ __device__ inline unsigned char render_pgm(double v) {
+  double b = 0.5;
+  if (!(v == -1)) {
+    const double m = (v < 1.0) ? v : 1.0;  // std::min(1.0, v)
+    b = (0.0 < m) ? m : 0.0;               // std::max(0.0, m)
+  }
+  const double value = 1.0 - b;
+  return (unsigned char)(255 * value);
+}
+__host__ __device__ inline unsigned char render_byte(int format, double v) {
+  return format == SLAMHIP_RENDER_PGM ? render_pgm(v) : (unsigned char)render_occgrid(v);
+}
+
 // Filtered scan, structure-of-arrays (coalesced per-beam loads), tot_w = sequential sum of
 // weights in beam order computed once on the host (pose independent).
 struct ScanView {
@@ -230,6 +278,7 @@ bool mu_set_deferred(slamhip_ctx *ctx, bool on);      // map_update.hip: queue p
 int mu_drain(slamhip_ctx *ctx, long long *n_updates, int *err);
 void mu_release(slamhip_ctx *ctx);                    // map_update.hip: frees the context's K6 scratch
 void shard_release(slamhip_ctx *ctx);                 // shard.cpp: leaves the RCCL group, frees its staging
+void render_release(slamhip_ctx *ctx);                // map_render.hip: frees the context's render buffer
 void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 
@@ -319,6 +368,8 @@ struct slamhip_ctx {
   hipEvent_t ev_fork = nullptr;
   void *shard = nullptr;  // RCCL group of the context (shard.cpp), or null
   void *mu_scratch = nullptr, *mu_bscratch = nullptr;  // K6 work buffers (map_update.hip), owned by the context
+  unsigned char *d_render = nullptr;  // the render kernels' output (map_render.hip): grows on demand, freed with the context
+  size_t render_cap = 0;
   bool low_latency = true;
   bool stage_poses = false;  // copy poses to HBM first instead of reading them over PCIe
   // slamhip_ctx_set_option: equivalent execution paths (defaults = what is measured)

@@ -104,6 +104,9 @@ int tile_pool_assign_mixed_split(TilePool *tp, const int *src, int n_remote, con
 // external window [x0, x0+w) x [y0, y0+h) of a slot: payload (3 doubles per cell: prob, obst.x, obst.y)
 // and counters (2 per cell: hits, tries); either may be null
 int tile_pool_download(TilePool *tp, int slot, int x0, int y0, int w, int h, double *payload3, double *aux2);
+// the same external window as w * h bytes (map_render.hip; format: SLAMHIP_RENDER_*): reads prob_occ only, cells outside
+// the extent read as the unknown cell
+int tile_pool_render(TilePool *tp, int slot, int format, int x0, int y0, int w, int h, void *out);
 // derives the masks of every tile in use for threshold th, unless they are there (waited for).  Leaves nbr_ok false
 // where the masks cannot be kept by the writers: th <= 0 or an unknown cell that counts as full.
 int tile_pool_nbr_masks(TilePool *tp, double th);

@@ -583,6 +583,16 @@ public:
     _chunks.clear();
     refresh_geometry();
   }
+  // The whole window as a map consumer's bytes in ONE call (slamhip_map_render: converted on the device, width() *
+  // height() bytes to the host): format SLAMHIP_RENDER_OCCGRID = the int8 cells of OccupancyGridPublisher::on_map_update
+  // (src/ros/occupancy_grid_publisher.h:40-46, rows bottom-up), SLAMHIP_RENDER_PGM = the pixels of
+  // GridMapToPgmDumber::dump_map (src/utils/map_dumpers.h:78-87, rows top-down), with the TBM conversion this view was
+  // configured with.  What a walk over operator[] yields chunk by chunk; host/slamhip_map_observers.h uses it.
+  void render(int format, std::vector<unsigned char> &out) const {
+    out.resize((size_t)_w * _h);
+    slamhip_or_die(slamhip_map_render(_ctx, _id, format, _model == SLAMHIP_CELL_TBM ? _tbm_kind : 0, 0, 0, _w, _h, out.data()),
+                   "map_render");
+  }
 
 private:
   void set_cell(Cell &c, const double *p) const {
@@ -600,6 +610,7 @@ private:
   void refresh_geometry() {
     int model = 0;
     slamhip_or_die(slamhip_map_info(_ctx, _id, &model, &_w, &_h, &_ox, &_oy, nullptr, nullptr), "map_info");
+    _model = model;
     _stride = (model == SLAMHIP_CELL_TBM || model == SLAMHIP_CELL_CREDIBILIST) ? 4 : (model == SLAMHIP_CELL_GMAPPING ? 3 : 1);
     set_width(_w);
     set_height(_h);
@@ -610,7 +621,7 @@ private:
   int _id;
   double _unknown;
   int _tbm_kind;
-  int _w = 0, _h = 0, _ox = 0, _oy = 0, _stride = 1;
+  int _w = 0, _h = 0, _ox = 0, _oy = 0, _stride = 1, _model = 0;
   mutable std::unordered_map<long long, std::vector<Cell>> _chunks;
 };
 
