@@ -213,6 +213,58 @@ int slamhip_map_render(slamhip_ctx *ctx, int map_id, int format, int occ_kind, i
  * occupancy and of the two byte rules. */
 int slamhip_render_cells(int cell_model, int occ_kind, int format, int n, const double *payload, void *out);
 
+/* ---------------------------------------------------------------- scan generation (csrc/scan_generate.hip)
+ * LaserScanGenerator::laser_scan_2D (src/utils/data_generation/laser_scan_generator.h:35-80): laser scans ray-cast
+ * from a grid map.  For a pose (x, y, theta), a beam angle a, max_dist and occ_threshold:
+ *   beam_dir = max_dist * (cos, sin)(a + theta) with the raw provider's libm as the COMPILED reference calls it: the
+ *              compiler fuses the cos and the sin of one argument into ONE call of glibc's sincos, whose sine differs
+ *              from sin's in the last place now and then (0.855469 <= |x| < 2.426265), and which x86-64 glibc 2.35
+ *              does not pick per CPU as it picks sin and cos: restated in csrc/libm_exact.h (sincos_), `variant`
+ *              naming the build (0 plain, 1 with FMA contractions) -- slamhip_scan_gen_libm_variant of the host whose
+ *              bits are wanted, which need not be its slamhip_libm_variant;
+ *   cells    = world_to_cells({robot, robot + beam_dir}), the reference's COMPLETE list (regular_squares_grid.h:56-101):
+ *              the 4-connected walk with its tie rule, or Bresenham's list from the start when the walk has not
+ *              arrived on the end cell within cells_nm cells -- a hit found early on a walk that later goes astray is
+ *              no hit;
+ *   in list order, cells with double(map[cell]) < occ_threshold are passed over (cells outside the window are the
+ *              prototype cell; a never-observed GMAPPING cell holds -1; the comparison is the reference's, so a NaN
+ *              occupancy is NOT below any threshold); the ray is intersected with the bounds of each remaining cell
+ *              (Rectangle::find_intersections): 1 intersection = a touch, the list goes on; 2 = the hit, at their
+ *              midpoint, range = sqrt(dist_sq(robot, midpoint)).
+ * Per beam one status byte and one range (0 unless the status is 1):
+ *   0  no hit: the beam adds no point to the scan
+ *   1  hit: the scan point (range, a, occupied)
+ *   2  the reference would fail an assertion there and stop: another number of intersections
+ *      (geometry_primitives.h:392, laser_scan_generator.h:64), or a scan point that world_to_cell(move_origin(...))
+ *      does not put back into its cell (:71-74).  No point.
+ * The reference's opening assertion (robot on the lower or left boundary of its cell under are_equal, :42-44) is
+ * checked on the host for every pose: SLAMHIP_ERR_INVALID for the whole call, nothing is launched.  Also INVALID:
+ * poses, angles or max_dist that are not finite, a pose beyond 2^29 cells from the origin, max_dist beyond 2^20 cells,
+ * more than 2^26 beams, an occ_kind the map's model does not take (as slamhip_map_render), a variant other than 0 / 1.
+ * The host entry and the kernels run ONE per-beam routine (csrc/scan_generate_device.h): equal bits. */
+enum { SLAMHIP_SCAN_GEN_SEQUENTIAL = 1 }; /* flags: every beam by the one-thread-per-beam form (the two forms agree
+                                           * bit for bit; the default is one wave per beam, 64 walk steps a round) */
+/* Which build of glibc's sincos this host's libm runs: 1 FMA, 0 plain, -1 neither (another libm).  Host only. */
+int slamhip_scan_gen_libm_variant(int *variant);
+/* The generator's angle list (laser_scan_generator.h:47-48): a starts at -half_sector and ACCUMULATES a += angle_inc
+ * while a <= half_sector, stopping early when 2 pi <= half_sector + a.  Host only, pose independent.  Writes the first
+ * min(*n, cap) angles; *n = the length of the whole list (cap 0, angles NULL: ask for the length). */
+int slamhip_scan_gen_angles(double half_sector, double angle_inc, int cap, double *angles, int *n);
+/* n_poses x n_angles beams over a bound dense map in one launch; range_out[n_poses][n_angles] doubles, status_out one
+ * byte per beam in the same order.  Queued on the context's stream, hence behind every deferred map update; writes
+ * nothing to the map; one copy back.  While slamhip_profile_enable is on, the kernel's own time is added to
+ * slamhip_profile_read's kernel_ms_total. */
+int slamhip_map_generate_scans(slamhip_ctx *ctx, int map_id, int occ_kind, int variant, int flags, int n_poses,
+                               const double *poses_xyt, int n_angles, const double *angles, double max_dist,
+                               double occ_threshold, double *range_out, unsigned char *status_out);
+/* Host only, no GPU: the same beams over a map on the host -- payload[height][width] cells of the model's host stride
+ * (OCC 1, TBM and CREDIBILIST 4, GMAPPING 3), unknown_payload = the prototype cell, (origin_x, origin_y) = the internal
+ * coordinates of external cell (0, 0). */
+int slamhip_scan_generate_host(int cell_model, int occ_kind, int variant, int width, int height, int origin_x, int origin_y,
+                               double scale, const double *unknown_payload, const double *payload, int n_poses,
+                               const double *poses_xyt, int n_angles, const double *angles, double max_dist,
+                               double occ_threshold, double *range_out, unsigned char *status_out);
+
 /* ---------------------------------------------------------------- map update (kernel K6)
  * Replaces GridMapScanAdder::append_scan (src/core/maps/grid_map_scan_adders.h:54-75) with
  * WallDistanceBlurringScanAdder::handle_scan_point (:138-172) and ConstOccupancyEstimator

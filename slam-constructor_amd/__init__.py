@@ -32,6 +32,8 @@ POSE_TRIG_DEVICE, POSE_TRIG_HOST, POSE_TRIG_RAW_EXACT = 0, 1, 2
 TRIG_RAW, TRIG_CACHED = 0, 1
 RENDER_OCCGRID, RENDER_PGM = 0, 1  # slamhip_map_render formats: int8 rows bottom-up / uint8 grey rows top-down
 OCC_TBM_CONSISTENT, OCC_TBM_UNKNOWN_EVEN = 0, 1  # the TBM cell class whose tbm2occ a render applies
+SCAN_GEN_SEQUENTIAL = 1  # slamhip_map_generate_scans flag: one thread per beam instead of one wave per beam
+SCAN_NO_HIT, SCAN_HIT, SCAN_ASSERT = 0, 1, 2  # its per-beam status bytes
 STRIDE = {CELL_OCC: 1, CELL_TBM: 4, CELL_GMAPPING: 3, CELL_CREDIBILIST: 4}
 
 EXPORTS = """slamhip_last_error slamhip_device_count slamhip_ctx_create slamhip_ctx_destroy
@@ -57,7 +59,8 @@ slamhip_gmapping_step_sharded slamhip_matcher_process_scan_batch slamhip_matcher
 slamhip_shard_attach slamhip_shard_exchange slamhip_shard_p2p_stats slamhip_shard_set_timeout slamhip_gmapping_match_abort
 slamhip_gmapping_migration_stats slamhip_map_append_scan_q slamhip_omqe_quality slamhip_scan_filter_upload
 slamhip_scan_set_angles slamhip_libm_variant slamhip_libm_eval slamhip_map_append_scan_raw
-slamhip_map_render slamhip_gmapping_particle_map_render slamhip_render_cells""".split()
+slamhip_map_render slamhip_gmapping_particle_map_render slamhip_render_cells
+slamhip_scan_gen_angles slamhip_scan_gen_libm_variant slamhip_map_generate_scans slamhip_scan_generate_host""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -266,6 +269,10 @@ def load(testing=False):
     L.slamhip_map_render.argtypes = [vp, i, i, i, i, i, i, i, vp]
     L.slamhip_gmapping_particle_map_render.argtypes = [vp, i, i, i, i, i, i, vp]
     L.slamhip_render_cells.argtypes = [i, i, i, i, _dp, vp]
+    L.slamhip_scan_gen_angles.argtypes = [d, d, i, _dp, _ip]
+    L.slamhip_scan_gen_libm_variant.argtypes = [_ip]
+    L.slamhip_map_generate_scans.argtypes = [vp, i, i, i, i, i, _dp, i, _dp, d, d, _dp, vp]
+    L.slamhip_scan_generate_host.argtypes = [i, i, i, i, i, i, i, d, _dp, _dp, i, _dp, i, _dp, d, d, _dp, vp]
     _libs[testing] = L
     return L
 
@@ -410,6 +417,74 @@ def render_cells(cell_model, payload, fmt, occ_kind=0):
     return out
 
 
+# ---- scan generation (LaserScanGenerator::laser_scan_2D) -------------------------------------------
+def to_lsp(max_dist, fov_deg, pts_nm):
+    """The reference's to_lsp (laser_scan_generator.h:26-29): (max_dist, angle_inc, half_sector), deg2rad(v) =
+    v * pi / 180 in its operation order."""
+    return float(max_dist), (float(fov_deg) / pts_nm) * np.pi / 180, (float(fov_deg) / 2.0) * np.pi / 180
+
+
+def scan_gen_libm_variant(strict=True):
+    """The build of glibc's sincos this host's libm runs (slamhip_scan_gen_libm_variant): what the compiled reference's
+    generator computes its beam directions with.  1 FMA, 0 plain; not necessarily libm_variant().  A libm that is
+    neither build raises (strict=False: returns -1): name the variant whose bits are wanted instead."""
+    v = C.c_int(0)
+    _check(load().slamhip_scan_gen_libm_variant(C.byref(v)))
+    if v.value < 0 and strict:
+        raise SlamHipError("this host's libm runs neither build of glibc's sincos restated in csrc/libm_exact.h: pass "
+                           "variant=0 or variant=1 to generate_scans / generate_scans_host explicitly")
+    return v.value
+
+
+def scan_gen_angles(half_sector, angle_inc):
+    """The generator's beam angles (slamhip_scan_gen_angles): accumulated from -half_sector, with the 2 pi break."""
+    L = load()
+    n = C.c_int(0)
+    _check(L.slamhip_scan_gen_angles(float(half_sector), float(angle_inc), 0, None, C.byref(n)))
+    out = np.zeros(n.value)
+    _check(L.slamhip_scan_gen_angles(float(half_sector), float(angle_inc), out.size, _d(out), C.byref(n)))
+    return out
+
+
+def _scan_gen_args(poses, angles):
+    poses = _f64(poses).reshape(-1, 3)
+    angles = _f64(angles).ravel()
+    return poses, angles, np.zeros((poses.shape[0], angles.size)), np.zeros((poses.shape[0], angles.size), np.uint8)
+
+
+def generate_scans_host(m, poses, angles, max_dist, occ_threshold=1.0, occ_kind=0, variant=None):
+    """slamhip_scan_generate_host, no GPU: the kernels' per-beam routine over a map on the host.  m: any object with
+    cell_model, payload[h, w, stride], origin, scale, unknown (what Context.upload_map takes); poses [K, 3].
+    Returns (range[K, B], status[K, B]); variant None = this host's sincos (scan_gen_libm_variant())."""
+    poses, angles, rng, status = _scan_gen_args(poses, angles)
+    variant = scan_gen_libm_variant() if variant is None else variant
+    stride = STRIDE[m.cell_model]
+    payload = _f64(m.payload)
+    h, w = payload.shape[:2]
+    unk = np.zeros(4)
+    unk[:stride] = np.asarray(m.unknown, dtype=np.float64).ravel()[:stride]
+    _check(load().slamhip_scan_generate_host(int(m.cell_model), int(occ_kind), int(variant), w, h, int(m.origin[0]),
+                                             int(m.origin[1]), float(m.scale), _d(unk), _d(payload), poses.shape[0],
+                                             _d(poses), angles.size, _d(angles), float(max_dist), float(occ_threshold),
+                                             _d(rng), status.ctypes.data))
+    return rng, status
+
+
+def compact_scans(rng, status, angles):
+    """The reference's scans from generate_scans' arrays: per pose the (range, angle, is_occ) lists of the beams that
+    hit, in beam order -- LaserScan2D::points() of laser_scan_2D.  A pose with a status-2 beam has no scan in the
+    reference (its assertion stops the process): None."""
+    angles = _f64(angles).ravel()
+    out = []
+    for r, s in zip(np.atleast_2d(rng), np.atleast_2d(status)):
+        if np.any(s == SCAN_ASSERT):
+            out.append(None)
+            continue
+        hit = s == SCAN_HIT
+        out.append((r[hit].copy(), angles[hit].copy(), np.ones(int(hit.sum()), dtype=bool)))
+    return out
+
+
 # ---- GPU objects ---------------------------------------------------------------------------------
 class Context:
     """One GPU + one HIP stream (slamhip_ctx)."""
@@ -551,6 +626,20 @@ class Context:
         out = np.zeros((max(h, 0), max(w, 0)), dtype=_render_dtype(fmt))
         _check(self.L.slamhip_map_render(self.h, map_id, int(fmt), int(occ_kind), x0, y0, w, h, out.ctypes.data))
         return out
+
+    def generate_scans(self, map_id, poses, angles, max_dist, occ_threshold=1.0, occ_kind=0, variant=None,
+                       sequential=False):
+        """LaserScanGenerator::laser_scan_2D for K poses x B angles over a resident map in one launch
+        (slamhip_map_generate_scans).  Returns (range[K, B], status[K, B]): status SCAN_NO_HIT / SCAN_HIT /
+        SCAN_ASSERT, range 0 where there is no hit; compact_scans() turns them into the reference's point lists.
+        variant: the build of glibc's sincos whose bits are wanted (None = this host's, scan_gen_libm_variant()); sequential: one thread per beam."""
+        poses, angles, rng, status = _scan_gen_args(poses, angles)
+        variant = scan_gen_libm_variant() if variant is None else variant
+        _check(self.L.slamhip_map_generate_scans(self.h, map_id, int(occ_kind), int(variant),
+                                                 SCAN_GEN_SEQUENTIAL if sequential else 0, poses.shape[0], _d(poses),
+                                                 angles.size, _d(angles), float(max_dist), float(occ_threshold), _d(rng),
+                                                 status.ctypes.data))
+        return rng, status
 
     def map_render_pgm(self, map_id, occ_kind=0):
         """The complete PGM file of the whole map as GridMapToPgmDumber::dump_map writes it (fixtures.pgm_bytes' header)."""

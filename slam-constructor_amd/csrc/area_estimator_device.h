@@ -10,6 +10,14 @@
 // the CPU path.  Invalid occupancy = (NaN, NaN): the cell update skips it.
 #pragma once
 
+// Host and device alike under hipcc (the scan generator's per-beam routine, scan_generate_device.h, runs on both and
+// intersects its ray through ae_rect_ray); a plain C++ compiler sees ordinary inline functions.
+#if defined(__HIPCC__)
+#define SLAMHIP_AE_FN __host__ __device__ static __forceinline__
+#else
+#define SLAMHIP_AE_FN static inline
+#endif
+
 namespace slamhip {
 namespace ae {
 struct ae_pt { double x, y; };
@@ -18,17 +26,17 @@ struct ae_rect { double bot, top, left, right; };
 /* edges are named 0 Bot, 1 Left, 2 Top, 3 Right (`loc`) */
 struct ae_occ { double prob, qual; };
 
-__device__ static __forceinline__ int ae_equal(double a, double b) {
+SLAMHIP_AE_FN int ae_equal(double a, double b) {
   double m = fabs(a) > fabs(b) ? fabs(a) : fabs(b);
   double s = 1.0 > m ? 1.0 : m;
   return fabs(a - b) <= 1e-7 * s;
 }
-__device__ static __forceinline__ int ae_less(double a, double b) { return a < b + 2.220446049250313e-16; }
-__device__ static __forceinline__ int ae_le(double a, double b) { return ae_equal(a, b) || ae_less(a, b); }
-__device__ static __forceinline__ int ae_ordered(double a, double b, double c) { return ae_le(a, b) && ae_le(b, c); }
-__device__ static __forceinline__ int ae_pt_equal(ae_pt a, ae_pt b) { return ae_equal(a.x, b.x) && ae_equal(a.y, b.y); }
+SLAMHIP_AE_FN int ae_less(double a, double b) { return a < b + 2.220446049250313e-16; }
+SLAMHIP_AE_FN int ae_le(double a, double b) { return ae_equal(a, b) || ae_less(a, b); }
+SLAMHIP_AE_FN int ae_ordered(double a, double b, double c) { return ae_le(a, b) && ae_le(b, c); }
+SLAMHIP_AE_FN int ae_pt_equal(ae_pt a, ae_pt b) { return ae_equal(a.x, b.x) && ae_equal(a.y, b.y); }
 
-__device__ static __forceinline__ ae_seg ae_make_seg(ae_pt b, ae_pt e) {
+SLAMHIP_AE_FN ae_seg ae_make_seg(ae_pt b, ae_pt e) {
   ae_seg s;
   s.beg = b;
   s.end = e;
@@ -38,21 +46,21 @@ __device__ static __forceinline__ ae_seg ae_make_seg(ae_pt b, ae_pt e) {
   return s;
 }
 /* Segment2D::contains (axis-aligned segments only) */
-__device__ static __forceinline__ int ae_seg_contains(ae_seg s, ae_pt p) {
+SLAMHIP_AE_FN int ae_seg_contains(ae_seg s, ae_pt p) {
   if (s.is_horiz) return ae_equal(p.y, s.beg.y) && ae_ordered(s.beg.x, p.x, s.end.x);
   if (s.is_vert) return ae_equal(p.x, s.beg.x) && ae_ordered(s.beg.y, p.y, s.end.y);
   return 0;
 }
-__device__ static __forceinline__ int ae_seg_contains_intersection(ae_seg s, ae_pt p) {
+SLAMHIP_AE_FN int ae_seg_contains_intersection(ae_seg s, ae_pt p) {
   int xin = ae_ordered(s.beg.x, p.x, s.end.x) || ae_ordered(s.end.x, p.x, s.beg.x);
   int yin = ae_ordered(s.beg.y, p.y, s.end.y) || ae_ordered(s.end.y, p.y, s.beg.y);
   return xin && yin;
 }
-__device__ static __forceinline__ int ae_rect_contains(ae_rect r, ae_pt p) {
+SLAMHIP_AE_FN int ae_rect_contains(ae_rect r, ae_pt p) {
   return ae_ordered(r.left, p.x, r.right) && ae_ordered(r.bot, p.y, r.top);
 }
 /* edges in Rectangle order: 0 bot, 1 top, 2 left, 3 right */
-__device__ static __forceinline__ ae_seg ae_edge(ae_rect r, int i) {
+SLAMHIP_AE_FN ae_seg ae_edge(ae_rect r, int i) {
   ae_pt lb = {r.left, r.bot}, rb = {r.right, r.bot}, lt = {r.left, r.top}, rt = {r.right, r.top};
   switch (i) {
     case 0: return ae_make_seg(lb, rb);
@@ -62,13 +70,13 @@ __device__ static __forceinline__ ae_seg ae_edge(ae_rect r, int i) {
   }
 }
 /* Rectangle::has_on_edge_line */
-__device__ static __forceinline__ int ae_on_edge_line(ae_rect r, ae_seg s) {
+SLAMHIP_AE_FN int ae_on_edge_line(ae_rect r, ae_seg s) {
   if (s.is_vert) return ae_equal(s.beg.x, r.left) || ae_equal(s.beg.x, r.right);
   if (s.is_horiz) return ae_equal(s.beg.y, r.bot) || ae_equal(s.beg.y, r.top);
   return 0;
 }
 /* Rectangle::find_containing_edge -> 1 if some edge contains p */
-__device__ static __forceinline__ int ae_on_some_edge(ae_rect r, ae_pt p) {
+SLAMHIP_AE_FN int ae_on_some_edge(ae_rect r, ae_pt p) {
   for (int i = 0; i < 4; ++i)
     if (ae_seg_contains(ae_edge(r, i), p)) return 1;
   return 0;
@@ -82,10 +90,10 @@ struct ae_hits {
   ae_pt p[4];
   int ok[4];
 };
-__device__ static __forceinline__ int ae_slot_loc(int slot) { return slot == 0 ? 2 : (slot == 1 ? 1 : (slot == 2 ? 0 : 3)); }
+SLAMHIP_AE_FN int ae_slot_loc(int slot) { return slot == 0 ? 2 : (slot == 1 ? 1 : (slot == 2 ? 0 : 3)); }
 
 /* Ray::intersect with one edge; ray = beg + alpha * delta */
-__device__ static __forceinline__ void ae_ray_edge(ae_pt rb, ae_pt rd, ae_seg e, ae_pt *p, int *ok) {
+SLAMHIP_AE_FN void ae_ray_edge(ae_pt rb, ae_pt rd, ae_seg e, ae_pt *p, int *ok) {
   *ok = 0;
   p->x = p->y = 0.0;
   if (e.is_horiz) {
@@ -108,9 +116,9 @@ __device__ static __forceinline__ void ae_ray_edge(ae_pt rb, ae_pt rd, ae_seg e,
     *ok = 1;
   }
 }
-__device__ static __forceinline__ int ae_count(const ae_hits &h) { return h.ok[0] + h.ok[1] + h.ok[2] + h.ok[3]; }
+SLAMHIP_AE_FN int ae_count(const ae_hits &h) { return h.ok[0] + h.ok[1] + h.ok[2] + h.ok[3]; }
 /* Rectangle::find_intersections(Ray): order top, left, bot, right; vertex duplicates removed */
-__device__ static __forceinline__ void ae_rect_ray(ae_rect r, ae_pt rb, ae_pt rd, ae_hits &h) {
+SLAMHIP_AE_FN void ae_rect_ray(ae_rect r, ae_pt rb, ae_pt rd, ae_hits &h) {
   ae_ray_edge(rb, rd, ae_edge(r, 1), &h.p[0], &h.ok[0]);
   ae_ray_edge(rb, rd, ae_edge(r, 2), &h.p[1], &h.ok[1]);
   ae_ray_edge(rb, rd, ae_edge(r, 0), &h.p[2], &h.ok[2]);
@@ -142,7 +150,7 @@ __device__ static __forceinline__ void ae_rect_ray(ae_rect r, ae_pt rb, ae_pt rd
   }
 }
 /* Rectangle::find_intersections(Segment2D) */
-__device__ static __forceinline__ void ae_rect_seg(ae_rect r, ae_seg s, ae_hits &h) {
+SLAMHIP_AE_FN void ae_rect_seg(ae_rect r, ae_seg s, ae_hits &h) {
   ae_pt d = {s.end.x - s.beg.x, s.end.y - s.beg.y};
   ae_rect_ray(r, s.beg, d, h);
 #pragma unroll
@@ -155,7 +163,7 @@ struct ae_two {
   ae_pt p0, p1;
   int loc0, loc1;
 };
-__device__ static __forceinline__ ae_two ae_first_two(const ae_hits &h) {
+SLAMHIP_AE_FN ae_two ae_first_two(const ae_hits &h) {
   ae_two t;
   t.p0 = t.p1 = ae_pt{0.0, 0.0};
   t.loc0 = t.loc1 = 0;
@@ -174,9 +182,9 @@ __device__ static __forceinline__ ae_two ae_first_two(const ae_hits &h) {
   }
   return t;
 }
-__device__ static __forceinline__ int ae_loc_is_horiz(int loc) { return loc == 0 || loc == 2; }
+SLAMHIP_AE_FN int ae_loc_is_horiz(int loc) { return loc == 0 || loc == 2; }
 
-__device__ static __forceinline__ ae_occ ae_area_rate(double chunk, double total, int is_occ, const double *base4) {
+SLAMHIP_AE_FN ae_occ ae_area_rate(double chunk, double total, int is_occ, const double *base4) {
   double rate = chunk / total;
   ae_occ o;
   if (is_occ) {
@@ -193,7 +201,7 @@ __device__ static __forceinline__ ae_occ ae_area_rate(double chunk, double total
 /* AreaOccupancyEstimator::estimate_occupancy.  shift_amount = the function-local static of
  * ensure_segment_not_on_edge (low_qual 0.01 x side of the FIRST cell ever estimated, Q27);
  * unknown_qual = 0.5.  Invalid occupancy = (NaN, NaN). */
-__device__ static __forceinline__ ae_occ ae_estimate(ae_pt beg, ae_pt end, ae_rect cell, int is_occ, const double *base4,
+SLAMHIP_AE_FN ae_occ ae_estimate(ae_pt beg, ae_pt end, ae_rect cell, int is_occ, const double *base4,
                          double shift_amount) {
   const ae_occ invalid = {__builtin_nan(""), __builtin_nan("")};
   const double unknown_qual = 0.5;

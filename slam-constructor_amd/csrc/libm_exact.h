@@ -209,6 +209,42 @@ SLAMHIP_LIBM_HD double cos_(double x) {
   return huge_cos(x);
 }
 
+// __sincos (s_sincos.c:30-103): what a compiler that fuses cos(x) and sin(x) of one argument into ONE call runs (GCC does
+// at -O1 and above; LaserScanGenerator's beam direction, laser_scan_generator.h:49-50, is such a pair).  The cosine is
+// __cos's in every range; the SINE differs from __sin's in the range 0.855469 <= |x| < 2.426265, where __sin hands
+// do_cos the pair (pi/2 - |x|, hp1) and __sincos the renormalised pair (a, da): the last place differs now and then.
+template <bool FMA>
+SLAMHIP_LIBM_HD void sincos_(double x, double *sn, double *cs) {
+  const int k = (int)(uint32_t)(bits_of(x) >> 32) & 0x7fffffff;
+  if (k < 0x3e400000) {
+    *sn = x;
+    *cs = 1.0;
+    return;
+  }
+  if (k < 0x3feb6000) {
+    *sn = do_sin<FMA>(x, 0.0);
+    *cs = do_cos<FMA>(x, 0.0);
+    return;
+  }
+  if (k < 0x400368fd) {
+    const double y = kHp0 - __builtin_fabs(x);
+    const double a = y + kHp1;
+    const double da = (y - a) + kHp1;
+    *sn = __builtin_copysign(do_cos<FMA>(a, da), x);
+    *cs = do_sin<FMA>(a, da);
+    return;
+  }
+  if (k < 0x419921FB) {
+    double a, da;
+    const int n = reduce_sincos<FMA>(x, a, da);
+    *sn = do_sincos<FMA>(a, da, n);
+    *cs = do_sincos<FMA>(a, da, n + 1);
+    return;
+  }
+  *sn = huge_sin(x);
+  *cs = huge_cos(x);
+}
+
 // ---- exp (e_exp.c) ---------------------------------------------------------------------------------------------------
 constexpr double kInvLn2N = 0x1.71547652b82fep+7, kShift = 0x1.8p52, kNegLn2hiN = -0x1.62e42fefa0000p-8,
                  kNegLn2loN = -0x1.cf79abc9e3b3ap-47;

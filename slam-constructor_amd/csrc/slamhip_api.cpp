@@ -805,6 +805,7 @@ int slamhip_ctx_destroy(slamhip_ctx *ctx) {
   }
   mu_release(ctx);
   render_release(ctx);
+  scan_gen_release(ctx);
   shard_release(ctx);
   hipStreamDestroy(ctx->stream);
   delete ctx;

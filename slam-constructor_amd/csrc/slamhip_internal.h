@@ -279,6 +279,7 @@ int mu_drain(slamhip_ctx *ctx, long long *n_updates, int *err);
 void mu_release(slamhip_ctx *ctx);                    // map_update.hip: frees the context's K6 scratch
 void shard_release(slamhip_ctx *ctx);                 // shard.cpp: leaves the RCCL group, frees its staging
 void render_release(slamhip_ctx *ctx);                // map_render.hip: frees the context's render buffer
+void scan_gen_release(slamhip_ctx *ctx);              // scan_generate.hip: frees the context's scan-generation block
 void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 
@@ -370,6 +371,9 @@ struct slamhip_ctx {
   void *mu_scratch = nullptr, *mu_bscratch = nullptr;  // K6 work buffers (map_update.hip), owned by the context
   unsigned char *d_render = nullptr;  // the render kernels' output (map_render.hip): grows on demand, freed with the context
   size_t render_cap = 0;
+  void *d_scan_gen = nullptr;  // slamhip_map_generate_scans' block in HBM (scan_generate.hip): grows on demand, freed with the context
+  size_t scan_gen_cap = 0;
+  std::vector<double> scan_gen_stage;  // ... and its host side: what goes up and what comes back, one copy each
   bool low_latency = true;
   bool stage_poses = false;  // copy poses to HBM first instead of reading them over PCIe
   // slamhip_ctx_set_option: equivalent execution paths (defaults = what is measured)

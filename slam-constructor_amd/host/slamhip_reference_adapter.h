@@ -593,6 +593,15 @@ public:
     slamhip_or_die(slamhip_map_render(_ctx, _id, format, _model == SLAMHIP_CELL_TBM ? _tbm_kind : 0, 0, 0, _w, _h, out.data()),
                    "map_render");
   }
+  // LaserScanGenerator::laser_scan_2D's beams for n_poses poses x n_angles angles, ray-cast on the device over this
+  // window (slamhip_map_generate_scans, with the TBM conversion this view was configured with): range[n_poses][n_angles],
+  // one status byte per beam (0 no hit, 1 hit, 2 the reference's assertion).  host/slamhip_scan_generator.h uses it.
+  void generate_scans(int variant, int n_poses, const double *poses_xyt, int n_angles, const double *angles, double max_dist,
+                      double occ_threshold, double *range, unsigned char *status) const {
+    slamhip_or_die(slamhip_map_generate_scans(_ctx, _id, _model == SLAMHIP_CELL_TBM ? _tbm_kind : 0, variant, 0, n_poses, poses_xyt,
+                                              n_angles, angles, max_dist, occ_threshold, range, status),
+                   "map_generate_scans");
+  }
 
 private:
   void set_cell(Cell &c, const double *p) const {

@@ -11,7 +11,10 @@ tests/golden/make_golden_search_space.py; the scenes are therefore taken from a 
 by call through the compiled reference.)
 
     p2d_ss_evaluator_hip.py [--fixture tests/golden/search_space.npz] [--scene closed|open|several|all]
-                            [--out DIR]
+                            [--out DIR] [--generate-scan]
+
+--generate-scan: the scan is not read from the fixture but ray-cast on the device from the uploaded map, with the
+reference CLI's scanner (to_lsp(100, 270, 1000), pose2D_search_space_evaluator.cpp:159) and occupancy threshold 1.
 
 Needs a GPU: there is no CPU fallback.
 """
@@ -42,11 +45,26 @@ class Window:
         self.unknown = np.array([0.5, 0.0, 0.0, 0.0])
 
 
-def evaluate(sh, fx, ctx, g, scene, strict=True):
+def generate_scan(sh, ctx, map_id, pose):
+    """LaserScanGenerator{to_lsp(100, 270, 1000)}.laser_scan_2D(map, pose) on the device -> (range, angle, is_occ)"""
+    max_dist, inc, hs = sh.to_lsp(100, 270, 1000)
+    angles = sh.scan_gen_angles(hs, inc)
+    rng, status = ctx.generate_scans(map_id, [pose], angles, max_dist, 1.0)
+    scan = sh.compact_scans(rng, status, angles)[0]
+    if scan is None:
+        raise RuntimeError("the reference's scan generator would fail an assertion at this pose")
+    return scan
+
+
+def evaluate(sh, fx, ctx, g, scene, strict=True, generate=False):
     """-> dict(scores, poses, prob, delta, n_calls, seconds, sss_prob, sss_geometry)"""
     m = Window(g[scene + "_map_payload"], g[scene + "_map_origin"], 0.1)
-    rng, ang, occ = g[scene + "_scan"]
     pose, res = g["pose"], float(g["resolution"])
+    if generate:
+        ctx.upload_map(0, m)
+        rng, ang, occ = generate_scan(sh, ctx, 0, pose)
+    else:
+        rng, ang, occ = g[scene + "_scan"]
     geom = dict(width=m.width, height=m.height, origin=m.origin, scale=m.scale, bounded=False)
     kept = sh.filter_scan(rng, ang, occ.astype(np.int32), pose, geom)
     f_rng, f_ang = rng[kept], ang[kept]
@@ -82,6 +100,7 @@ def main():
     ap.add_argument("--scene", default="all")
     ap.add_argument("--out", default=".")
     ap.add_argument("--default-mode", action="store_true", help="tree sum + device sincos instead of strict")
+    ap.add_argument("--generate-scan", action="store_true", help="ray-cast the scan on the device instead of reading it")
     args = ap.parse_args()
     sh = _pkg()
     from importlib import import_module
@@ -91,7 +110,7 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     for scene in (["closed", "open", "several"] if args.scene == "all" else [args.scene]):
         print(TITLES[scene])
-        t = evaluate(sh, fx, ctx, g, scene, strict=not args.default_mode)
+        t = evaluate(sh, fx, ctx, g, scene, strict=not args.default_mode, generate=args.generate_scan)
         print("BF: %g" % t["seconds"])
         with open(os.path.join(args.out, "input_map_0.pgm"), "wb") as f:
             f.write(fx.pgm_bytes(t["input_prob"]))
