@@ -4,7 +4,7 @@
 //   GmappingBaseCell::discrepancy          src/slams/gmapping/gmapping_grid_cell.h:35-38
 #pragma once
 
-#include "score_device.h"
+#include <hip/hip_runtime.h>
 
 namespace slamhip {
 
@@ -12,6 +12,20 @@ static constexpr int kGmBlock = 256;  // the canonical layout of run resolution 
 // dynamic LDS of gm_score_pose_wide behind its int arrays: one double per thread for the helper lanes' distances
 template <int NT>
 constexpr size_t kGmHelperDoubles = NT >= 512 ? (size_t)NT : 0;
+// dynamic LDS of a workgroup of `nt` threads that scores one pose over kb x 256 beams with gm_score_pose_wide (the
+// chains: hc_chain.hip, hc_resident_gm.hip; K3's 1024-thread form): K3's arrays (a double per beam, an int2 and an int
+// per wave of beams), the wide form's two ints per beam, and the helper lanes' doubles
+constexpr size_t gm_chain_lds_bytes(int kb, int nt) {
+  return (size_t)kb * kGmBlock * sizeof(double) + 4 * (size_t)kb * sizeof(int2) + 4 * (size_t)kb * sizeof(int) +
+         2 * (size_t)kb * kGmBlock * sizeof(int) + (nt >= 512 ? (size_t)nt * sizeof(double) : 0);
+}
+
+}  // namespace slamhip
+
+#ifdef __HIPCC__  // (the sizes above are the host's as well: tests/native/kernel_pick_test.cpp; the rest is device code)
+#include "score_device.h"
+
+namespace slamhip {
 
 // ---- K3: GMapping OOPE -------------------------------------------------------------------------
 // value of one endpoint: max over the (2w+1)^2 window of cells with prob_occ >= th of
@@ -626,3 +640,4 @@ __device__ __forceinline__ void gm_score_pose_wide(const MapView &map, const Sca
 }
 
 }  // namespace slamhip
+#endif  // __HIPCC__

@@ -12,7 +12,6 @@
 //                     so its bits equal the host-driven matcher's
 // Kernels launched past the end of the chain see `done_epoch == epoch` and return.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include "gm_score_device.h"
 #include "hc_chain_device.h"
@@ -614,48 +613,6 @@ __global__ __launch_bounds__(NT) void k_hc_chain_step(HcChainArgs a, int k) {
   }
 }
 
-// e0 / e1 (optional): HIP events attached to the dispatch (kernel begin .. end), see SLAMHIP_LAUNCH in
-// score_kernels.hip
-#define HC_LAUNCH(NTV)                                                                                          \
-  do {                                                                                                          \
-    if (e0 || e1)                                                                                               \
-      hipExtLaunchKernelGGL((k_hc_chain_step<MODEL, NTV, SEQ, KB, BATCH>), dim3(grid, n_chains), dim3(NTV), shm, stream, e0, e1, 0, a, k); \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_hc_chain_step<MODEL, NTV, SEQ, KB, BATCH>), dim3(grid, n_chains), dim3(NTV), shm, stream, a, k);     \
-  } while (0)
-
-template <int MODEL, bool SEQ, bool BATCH>
-static hipError_t launch_nt(const HcChainArgs &a, int k, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
-                            int n_chains) {
-  constexpr int KB = 0;
-  const int grid = 6 * a.max_inst + 1;
-  const size_t shm = sizeof(double) * (size_t)(a.scan.n > 0 ? a.scan.n : 1);
-  switch (nt) {
-    case 256: HC_LAUNCH(256); break;
-    case 1024: HC_LAUNCH(1024); break;
-    default: HC_LAUNCH(512); break;
-  }
-  return hipGetLastError();
-}
-
-// GMapping OOPE: 512 threads per pose (two workgroups per CU: all slots of a 64-instance super-step resident at
-// once) or 1024 (one per CU: trees of at most 42 instances)
-template <int KB>
-static hipError_t launch_gm(const HcChainArgs &a, int k, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
-                            int n_chains) {
-  constexpr int MODEL = SLAMHIP_CELL_GMAPPING;
-  constexpr bool SEQ = false, BATCH = false;
-  const int grid = 6 * a.max_inst + 1;
-  // (+ one double per thread for the helper lanes of gm_score_pose_wide: its 512- and 1024-thread forms)
-  const size_t shm = (size_t)KB * 256 * sizeof(double) + 4 * KB * sizeof(int2) + 4 * KB * sizeof(int) +
-                     2 * (size_t)KB * 256 * sizeof(int) + (nt >= 512 ? (size_t)nt * sizeof(double) : 0);
-  if (nt == 1024) HC_LAUNCH(1024);
-  else if (nt == 256) HC_LAUNCH(256);
-  else HC_LAUNCH(512);
-  return hipGetLastError();
-}
-#undef HC_LAUNCH
-
 __global__ void k_chain_marker(const unsigned *n_done, unsigned *h_done_count, unsigned *flag, unsigned seq) {
   *h_done_count = *n_done;
   __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -667,35 +624,40 @@ hipError_t launch_chain_marker(const unsigned *n_done, unsigned *h_done_count, u
   return hipGetLastError();
 }
 
+// e0 / e1 (optional): HIP events attached to the dispatch (kernel begin .. end), see launch_kernel in kernel_pick.h
 hipError_t launch_hc_chain_step(const HcChainArgs &a, int cell_model, int k, int nt, hipStream_t stream,
                                 hipEvent_t e0, hipEvent_t e1, int n_chains) {
-  if (a.jobs) {  // a batch of independent matches: the default (canonical-sum) mode of the 1-cell OOPE
-    if (a.seq) return hipErrorInvalidValue;
-    if (cell_model == SLAMHIP_CELL_OCC) return launch_nt<SLAMHIP_CELL_OCC, false, true>(a, k, nt, stream, e0, e1, n_chains);
-    if (cell_model == SLAMHIP_CELL_TBM) return launch_nt<SLAMHIP_CELL_TBM, false, true>(a, k, nt, stream, e0, e1, n_chains);
-    if (cell_model == SLAMHIP_CELL_CREDIBILIST) return launch_nt<SLAMHIP_CELL_CREDIBILIST, false, true>(a, k, nt, stream, e0, e1, n_chains);
-    return hipErrorInvalidValue;
+  typedef void (*Kernel)(HcChainArgs, int);
+  const dim3 grid(6 * a.max_inst + 1, n_chains), block(hc_nt_of(nt));
+  if (cell_model == SLAMHIP_CELL_GMAPPING) {
+    // GMapping OOPE: 512 threads per pose (two workgroups per CU: all slots of a 64-instance super-step resident at
+    // once) or 1024 (one per CU: trees of at most 42 instances)
+    if (a.seq || a.jobs) return hipErrorInvalidValue;
+    const int kb = (a.scan.n + 255) / 256;
+    const Kernel kernel = pick_hc_nt(nt, [&](auto nt_c) -> Kernel {
+      constexpr int NT = decltype(nt_c)::value;
+      switch (kb) {
+        case 1: return k_hc_chain_step<SLAMHIP_CELL_GMAPPING, NT, false, 1, false>;
+        case 2: return k_hc_chain_step<SLAMHIP_CELL_GMAPPING, NT, false, 2, false>;
+        case 3: return k_hc_chain_step<SLAMHIP_CELL_GMAPPING, NT, false, 3, false>;
+        case 4: return k_hc_chain_step<SLAMHIP_CELL_GMAPPING, NT, false, 4, false>;
+        case 5: return k_hc_chain_step<SLAMHIP_CELL_GMAPPING, NT, false, 5, false>;
+        default: return nullptr;
+      }
+    });
+    return launch_kernel(kernel, grid, block, gm_chain_lds_bytes(kb, nt), stream, e0, e1, a, k);
   }
-  if (cell_model == SLAMHIP_CELL_OCC)
-    return a.seq ? launch_nt<SLAMHIP_CELL_OCC, true, false>(a, k, nt, stream, e0, e1, n_chains)
-                 : launch_nt<SLAMHIP_CELL_OCC, false, false>(a, k, nt, stream, e0, e1, n_chains);
-  if (cell_model == SLAMHIP_CELL_TBM)
-    return a.seq ? launch_nt<SLAMHIP_CELL_TBM, true, false>(a, k, nt, stream, e0, e1, n_chains)
-                 : launch_nt<SLAMHIP_CELL_TBM, false, false>(a, k, nt, stream, e0, e1, n_chains);
-  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
-    return a.seq ? launch_nt<SLAMHIP_CELL_CREDIBILIST, true, false>(a, k, nt, stream, e0, e1, n_chains)
-                 : launch_nt<SLAMHIP_CELL_CREDIBILIST, false, false>(a, k, nt, stream, e0, e1, n_chains);
-  if (cell_model == SLAMHIP_CELL_GMAPPING && !a.seq) {
-    switch ((a.scan.n + 255) / 256) {
-      case 1: return launch_gm<1>(a, k, nt, stream, e0, e1, n_chains);
-      case 2: return launch_gm<2>(a, k, nt, stream, e0, e1, n_chains);
-      case 3: return launch_gm<3>(a, k, nt, stream, e0, e1, n_chains);
-      case 4: return launch_gm<4>(a, k, nt, stream, e0, e1, n_chains);
-      case 5: return launch_gm<5>(a, k, nt, stream, e0, e1, n_chains);
-      default: break;
-    }
-  }
-  return hipErrorInvalidValue;
+  // the 1-cell OOPE: the default (canonical-sum) or the beam-order mode, or a batch of independent matches (default mode)
+  if (a.jobs && a.seq) return hipErrorInvalidValue;
+  const Kernel kernel = pick_cell_model(cell_model, [&](auto model) -> Kernel {
+    constexpr int M = decltype(model)::value;
+    return pick_hc_nt(nt, [&](auto nt_c) -> Kernel {
+      constexpr int NT = decltype(nt_c)::value;
+      if (a.jobs) return k_hc_chain_step<M, NT, false, 0, true>;
+      return a.seq ? k_hc_chain_step<M, NT, true, 0, false> : k_hc_chain_step<M, NT, false, 0, false>;
+    });
+  });
+  return launch_kernel(kernel, grid, block, sizeof(double) * (size_t)(a.scan.n > 0 ? a.scan.n : 1), stream, e0, e1, a, k);
 }
 
 }  // namespace slamhip

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "hc_chain.h"
+#include "kernel_pick.h"
 #include "slamhip_internal.h"
 
 namespace slamhip {
@@ -140,8 +141,8 @@ hipError_t launch_hc_chain_step(const HcChainArgs &a, int cell_model, int k, int
 // than a tag counts -- either way nothing was reported, the kernel chain redoes the match
 hipError_t launch_hc_chain_resident(const HcChainArgs &a, int cell_model, int nt, hipStream_t stream,
                                     hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int n_chains = 1);
-hipError_t hc_resident_capacity(int cell_model, int nt, bool batch, bool window, int n_beams, bool lds_consts, int max_inst,
-                                int *out_wgs, int *out_per_cu = nullptr, bool pair = false);
+hipError_t hc_resident_capacity(int cell_model, HcResidentKey key, int n_beams, bool lds_consts, int *out_wgs,
+                                int *out_per_cu = nullptr);
 size_t hc_resident_lds_bytes(int nt, int n_beams, bool lds_consts, int max_inst, bool pair = false);
 // the GMapping OOPE's co-resident form (hc_resident_gm.hip): one chain, or n_chains of a filter step (grid.y = chain:
 // HcChainArgs::inits / n_done / h_all_done / tables / slots as in launch_hc_chain_step)

@@ -33,7 +33,6 @@
 // is the LAST dword of the granule.  Everything else a workgroup reads during the loop is read-only for the match
 // (map, scan, shapes) or its own LDS.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include "hc_chain_device.h"
 #include "hc_resident_device.h"
@@ -883,178 +882,61 @@ size_t hc_resident_lds_bytes(int nt, int n_beams, bool lds_consts, int max_inst,
          (pair ? sizeof(HcNextEntryT<2>) : sizeof(HcNextEntryT<1>)) * 7 * (size_t)max_inst;
 }
 
-#define HCR_LAUNCH(NTV, GV)                                                                                     \
-  do {                                                                                                          \
-    if (e0 || e1)                                                                                               \
-      hipExtLaunchKernelGGL((k_hc_chain_resident<MODEL, NTV, SEQ, BATCH, GV>), dim3(grid, n_chains), dim3(NTV), shm, stream, e0, e1, 0, a); \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_hc_chain_resident<MODEL, NTV, SEQ, BATCH, GV>), dim3(grid, n_chains), dim3(NTV), shm, stream, a);     \
-  } while (0)
-
-#define HCR_LAUNCH_PAIR(GV)                                                                                     \
-  do {                                                                                                          \
-    if (e0 || e1)                                                                                               \
-      hipExtLaunchKernelGGL((k_hc_chain_resident<MODEL, 512, false, BATCH, GV, false, BATCH>), dim3(grid, n_chains), dim3(512), shm, stream, e0, e1, 0, a); \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_hc_chain_resident<MODEL, 512, false, BATCH, GV, false, BATCH>), dim3(grid, n_chains), dim3(512), shm, stream, a);     \
-  } while (0)
-
-// granules per sweeping lane for a grid of `grid` workgroups
-static int gran_per_lane(int grid) { return grid <= 128 ? 2 : (grid <= 256 ? 4 : 7); }
-
-#define HCR_LAUNCH_WIN(NTV)                                                                                      \
-  do {                                                                                                          \
-    if (e0 || e1)                                                                                               \
-      hipExtLaunchKernelGGL((k_hc_chain_resident<MODEL, NTV, false, false, 4, true>), dim3(grid, n_chains), dim3(NTV), shm, stream, e0, e1, 0, a); \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_hc_chain_resident<MODEL, NTV, false, false, 4, true>), dim3(grid, n_chains), dim3(NTV), shm, stream, a);     \
-  } while (0)
-
-// the window OOPEs: lone chains of at most 256 workgroups, default sum order
-template <int MODEL>
-static hipError_t launch_res_win(const HcChainArgs &a_in, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
-                                 int n_chains) {
-  HcChainArgs a = a_in;
-  const int grid = 6 * a.max_inst + 1;
-  if (grid > 256) return hipErrorInvalidValue;
-  const size_t shm = hc_resident_lds_bytes(nt, a.scan.n, false, a.max_inst, false);  // (the window form keeps no beam constants in LDS)
-  a.tab_offset = (int)hc_resident_tab_offset(nt, a.scan.n, false, false);
-  if (nt == 1024) HCR_LAUNCH_WIN(1024);
-  else if (nt == 256) HCR_LAUNCH_WIN(256);
-  else HCR_LAUNCH_WIN(512);
-  return hipGetLastError();
+// The ONE table of instantiations: the kernel of a variant (hc_resident_variant, kernel_pick.h, says which exist and
+// normalises workgroup size and sweep width), or null.  The launch and the capacity query both pick here.
+// (workgroup sizes and sweep widths that go together: a lone chain is 253 x 1024 threads, a batch's chains are
+// narrower trees of narrower workgroups)
+typedef void (*HcResidentKernel)(HcChainArgs);
+static HcResidentKernel hc_resident_kernel(int cell_model, const HcResidentKey &key) {
+  int nt_v = 0, g_v = 0;
+  if (!hc_resident_variant(key, &nt_v, &g_v)) return nullptr;
+  return pick_cell_model(cell_model, [&](auto model) -> HcResidentKernel {
+    constexpr int M = decltype(model)::value;
+    return pick_hc_nt(nt_v, [&](auto nt) -> HcResidentKernel {
+      constexpr int NT = decltype(nt)::value;
+      if (key.window) return k_hc_chain_resident<M, NT, false, false, 4, true>;
+      const auto sweep = [&](auto g) -> HcResidentKernel {
+        constexpr int G = decltype(g)::value;
+        if constexpr (NT == 512)
+          if (key.batch && key.pair) return k_hc_chain_resident<M, 512, false, true, G, false, true>;
+        if (key.batch) return k_hc_chain_resident<M, NT, false, true, G>;
+        return key.seq ? k_hc_chain_resident<M, NT, true, false, G> : k_hc_chain_resident<M, NT, false, false, G>;
+      };
+      if (g_v == 2) return sweep(int_c<2>{});
+      if (g_v == 4) return sweep(int_c<4>{});
+      if constexpr (NT != 1024) return sweep(int_c<7>{});
+      return nullptr;  // (refused by hc_resident_variant)
+    });
+  });
 }
-#undef HCR_LAUNCH_WIN
 
-template <int MODEL, bool SEQ, bool BATCH>
-static hipError_t launch_res(const HcChainArgs &a_in, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
-                             int n_chains) {
-  HcChainArgs a = a_in;
-  const bool pair = BATCH && a.pair != 0;
-  const int slots = 6 * a.max_inst + 1;
-  const int grid = pair ? 3 * a.max_inst + 1 : slots;  // (a pair: two scoring slots per workgroup + the bookkeeping one)
-  const size_t shm = hc_resident_lds_bytes(nt, a.scan.n, a.lds_consts != 0, a.max_inst, pair);
-  a.tab_offset = (int)hc_resident_tab_offset(nt, a.scan.n, a.lds_consts != 0, pair);
-  const int g = gran_per_lane(slots);
-  if (pair) {
-    if (nt != 512) return hipErrorInvalidValue;
-    if (g == 2) HCR_LAUNCH_PAIR(2);
-    else if (g == 4) HCR_LAUNCH_PAIR(4);
-    else HCR_LAUNCH_PAIR(7);
-    return hipGetLastError();
-  }
-  // (workgroup sizes and sweep widths that go together: a lone chain is 253 x 1024 threads, a batch's chains are
-  // narrower trees of narrower workgroups)
-  if (nt == 1024) {
-    if (g == 2) HCR_LAUNCH(1024, 2);
-    else if (g == 4) HCR_LAUNCH(1024, 4);
-    else return hipErrorInvalidValue;  // 385 workgroups of 1024 threads are not resident together
-  } else if (nt == 256) {
-    if (g == 2) HCR_LAUNCH(256, 2);
-    else if (g == 4) HCR_LAUNCH(256, 4);
-    else HCR_LAUNCH(256, 7);
-  } else {
-    if (g == 2) HCR_LAUNCH(512, 2);
-    else if (g == 4) HCR_LAUNCH(512, 4);
-    else HCR_LAUNCH(512, 7);
-  }
-  return hipGetLastError();
+static HcResidentKey key_of(const HcChainArgs &a, int nt) {
+  return {nt, a.max_inst, a.seq != 0, a.jobs != nullptr, a.pair != 0, a.oope != SLAMHIP_OOPE_OBSTACLE};
 }
-#undef HCR_LAUNCH
-#undef HCR_LAUNCH_PAIR
 
-hipError_t launch_hc_chain_resident(const HcChainArgs &a, int cell_model, int nt, hipStream_t stream, hipEvent_t e0,
+hipError_t launch_hc_chain_resident(const HcChainArgs &a_in, int cell_model, int nt, hipStream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, int n_chains) {
-  if (!a.rctl) return hipErrorInvalidValue;
-  if (a.oope != SLAMHIP_OOPE_OBSTACLE) {
-    if (a.jobs || a.seq) return hipErrorInvalidValue;
-    if (cell_model == SLAMHIP_CELL_OCC) return launch_res_win<SLAMHIP_CELL_OCC>(a, nt, stream, e0, e1, n_chains);
-    if (cell_model == SLAMHIP_CELL_TBM) return launch_res_win<SLAMHIP_CELL_TBM>(a, nt, stream, e0, e1, n_chains);
-    if (cell_model == SLAMHIP_CELL_CREDIBILIST) return launch_res_win<SLAMHIP_CELL_CREDIBILIST>(a, nt, stream, e0, e1, n_chains);
-    return hipErrorInvalidValue;
-  }
-  if (a.jobs) {
-    if (a.seq) return hipErrorInvalidValue;
-    if (cell_model == SLAMHIP_CELL_OCC) return launch_res<SLAMHIP_CELL_OCC, false, true>(a, nt, stream, e0, e1, n_chains);
-    if (cell_model == SLAMHIP_CELL_TBM) return launch_res<SLAMHIP_CELL_TBM, false, true>(a, nt, stream, e0, e1, n_chains);
-    if (cell_model == SLAMHIP_CELL_CREDIBILIST) return launch_res<SLAMHIP_CELL_CREDIBILIST, false, true>(a, nt, stream, e0, e1, n_chains);
-    return hipErrorInvalidValue;
-  }
-  if (cell_model == SLAMHIP_CELL_OCC)
-    return a.seq ? launch_res<SLAMHIP_CELL_OCC, true, false>(a, nt, stream, e0, e1, n_chains)
-                 : launch_res<SLAMHIP_CELL_OCC, false, false>(a, nt, stream, e0, e1, n_chains);
-  if (cell_model == SLAMHIP_CELL_TBM)
-    return a.seq ? launch_res<SLAMHIP_CELL_TBM, true, false>(a, nt, stream, e0, e1, n_chains)
-                 : launch_res<SLAMHIP_CELL_TBM, false, false>(a, nt, stream, e0, e1, n_chains);
-  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
-    return a.seq ? launch_res<SLAMHIP_CELL_CREDIBILIST, true, false>(a, nt, stream, e0, e1, n_chains)
-                 : launch_res<SLAMHIP_CELL_CREDIBILIST, false, false>(a, nt, stream, e0, e1, n_chains);
-  return hipErrorInvalidValue;
+  if (!a_in.rctl) return hipErrorInvalidValue;
+  HcChainArgs a = a_in;
+  const HcResidentKey key = key_of(a, nt);
+  const bool pair = key.batch && key.pair;
+  const bool ldsc = !key.window && a.lds_consts != 0;  // (the window form keeps no beam constants in LDS)
+  const int grid = pair ? 3 * a.max_inst + 1 : 6 * a.max_inst + 1;  // (a pair: two scoring slots per workgroup + the bookkeeping one)
+  a.tab_offset = (int)hc_resident_tab_offset(nt, a.scan.n, ldsc, pair);
+  return launch_kernel(hc_resident_kernel(cell_model, key), dim3(grid, n_chains), dim3(hc_nt_of(nt)),
+                       hc_resident_lds_bytes(nt, a.scan.n, ldsc, a.max_inst, pair), stream, e0, e1, a);
 }
 
-// the instantiation launch_res / launch_res_win pick for a workgroup size and a sweep width
-template <int M, bool B>
-static const void *res_fn(int nt, int g) {
-  if (nt == 1024)
-    return g == 2 ? (const void *)k_hc_chain_resident<M, 1024, false, B, 2>
-                  : (g == 4 ? (const void *)k_hc_chain_resident<M, 1024, false, B, 4> : nullptr);
-  if (nt == 256)
-    return g == 2 ? (const void *)k_hc_chain_resident<M, 256, false, B, 2>
-                  : (g == 4 ? (const void *)k_hc_chain_resident<M, 256, false, B, 4>
-                            : (const void *)k_hc_chain_resident<M, 256, false, B, 7>);
-  return g == 2 ? (const void *)k_hc_chain_resident<M, 512, false, B, 2>
-                : (g == 4 ? (const void *)k_hc_chain_resident<M, 512, false, B, 4>
-                          : (const void *)k_hc_chain_resident<M, 512, false, B, 7>);
-}
-template <int M>
-static const void *res_fn_pair(int g) {
-  return g == 2 ? (const void *)k_hc_chain_resident<M, 512, false, true, 2, false, true>
-                : (g == 4 ? (const void *)k_hc_chain_resident<M, 512, false, true, 4, false, true>
-                          : (const void *)k_hc_chain_resident<M, 512, false, true, 7, false, true>);
-}
-template <int M>
-static const void *res_fn_win(int nt) {
-  return nt == 1024 ? (const void *)k_hc_chain_resident<M, 1024, false, false, 4, true>
-                    : (nt == 256 ? (const void *)k_hc_chain_resident<M, 256, false, false, 4, true>
-                                 : (const void *)k_hc_chain_resident<M, 512, false, false, 4, true>);
-}
-
-// Workgroups of `nt` threads (scoring `n_beams`, trees of `max_inst` round instances: hc_resident_lds_bytes of dynamic
-// LDS) the device keeps resident at once: the occupancy query of the instantiation that will be LAUNCHED, the
-// register-file rule of MI355X_MICROARCH.md ("Residency and cooperative launch": the API can be one block per CU high
-// above 80 SGPRs; this kernel's waves also need <= 128 VGPRs at 1024 threads), minus ONE CU's worth of workgroups of
-// margin -- a grid that needs every slot of the chip waits for any other kernel's last workgroup to leave.
-hipError_t hc_resident_capacity(int cell_model, int nt, bool batch, bool window, int n_beams, bool lds_consts, int max_inst,
-                                int *out_wgs, int *out_per_cu, bool pair) {
-  const size_t lds_bytes = hc_resident_lds_bytes(nt, n_beams, lds_consts, max_inst, pair);
-  int dev = 0, cus = 0, per_cu = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return e;
-  const void *fn = nullptr;
-  const int g = window ? 4 : gran_per_lane(6 * max_inst + 1);
-  // (a model the kernels are not instantiated for leaves fn null: an error, never another model's kernel)
-#define HCR_FN(M)                                             \
-  do {                                                        \
-    if (window) fn = res_fn_win<M>(nt);                       \
-    else if (batch && pair) fn = res_fn_pair<M>(g);           \
-    else if (batch) fn = res_fn<M, true>(nt, g);              \
-    else fn = res_fn<M, false>(nt, g);                        \
-  } while (0)
-  if (cell_model == SLAMHIP_CELL_OCC) HCR_FN(SLAMHIP_CELL_OCC);
-  else if (cell_model == SLAMHIP_CELL_TBM) HCR_FN(SLAMHIP_CELL_TBM);
-  else if (cell_model == SLAMHIP_CELL_CREDIBILIST) HCR_FN(SLAMHIP_CELL_CREDIBILIST);
-#undef HCR_FN
-  if (!fn) return hipErrorInvalidValue;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, lds_bytes);
-  if (e != hipSuccess) return e;
-  const int by_waves = 2048 / nt;  // 128-VGPR waves: four per SIMD
-  per_cu = per_cu < by_waves ? per_cu : by_waves;
-  if (per_cu > 6) per_cu = 6;      // floor(800 / (ceil(sgpr / 16) * 16 + 16)) at ~106 SGPRs
-  *out_wgs = per_cu * (cus - 1);
-  if (out_per_cu) *out_per_cu = per_cu;
-  return hipSuccess;
+// Workgroups of `key.nt` threads (scoring `n_beams`, trees of `key.max_inst` round instances: hc_resident_lds_bytes of
+// dynamic LDS) the device keeps resident at once: resident_capacity_of (kernel_pick.h) the instantiation that will be
+// LAUNCHED -- at ~106 SGPRs, floor(800 / (ceil(sgpr / 16) * 16 + 16)) = 6 workgroups per CU at most.
+hipError_t hc_resident_capacity(int cell_model, HcResidentKey key, int n_beams, bool lds_consts, int *out_wgs,
+                                int *out_per_cu) {
+  // the ONE departure from "what is launched": a beam-order chain has always been sized by the default order's kernel
+  key.seq = false;
+  return resident_capacity_of((const void *)hc_resident_kernel(cell_model, key), key.nt,
+                              hc_resident_lds_bytes(key.nt, n_beams, lds_consts, key.max_inst, key.batch && key.pair),
+                              2048 / key.nt /* 128-VGPR waves: four per SIMD */, 6, out_wgs, out_per_cu);
 }
 
 }  // namespace slamhip

@@ -14,7 +14,6 @@
 // line.  Scoring is K3's one-pose body (gm_score_pose_wide): same bits as every other path.
 // Bounded waits, fail-over and tags: hc_resident.hip / hc_resident_device.h.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include "gm_score_device.h"
 #include "hc_chain_device.h"
@@ -483,72 +482,42 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 3 : 4)) void k_hc_chain_resident_g
   }
 }
 
-#define HCRG_LAUNCH(NTV)                                                                                        \
-  do {                                                                                                          \
-    if (grid <= 64) {                                                                                           \
-      if (e0 || e1)                                                                                             \
-        hipExtLaunchKernelGGL((k_hc_chain_resident_gm<NTV, KB, 1>), dim3(grid, n_chains), dim3(NTV), shm, stream, e0, e1, 0, a); \
-      else                                                                                                      \
-        hipLaunchKernelGGL((k_hc_chain_resident_gm<NTV, KB, 1>), dim3(grid, n_chains), dim3(NTV), shm, stream, a);   \
-    } else {                                                                                                    \
-      if (e0 || e1)                                                                                             \
-        hipExtLaunchKernelGGL((k_hc_chain_resident_gm<NTV, KB, 4>), dim3(grid, n_chains), dim3(NTV), shm, stream, e0, e1, 0, a); \
-      else                                                                                                      \
-        hipLaunchKernelGGL((k_hc_chain_resident_gm<NTV, KB, 4>), dim3(grid, n_chains), dim3(NTV), shm, stream, a);   \
-    }                                                                                                           \
-  } while (0)
-
-template <int KB>
-static hipError_t launch_res_gm(const HcChainArgs &a, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
-                                int n_chains) {
-  const int grid = 6 * a.max_inst + 1;
-  if (grid > 256) return hipErrorInvalidValue;
-  // (the dynamic LDS of hc_chain.hip's launch_gm: K3's arrays + one double per thread for the helper lanes)
-  const size_t shm = (size_t)KB * 256 * sizeof(double) + 4 * KB * sizeof(int2) + 4 * KB * sizeof(int) +
-                     2 * (size_t)KB * 256 * sizeof(int) + (nt >= 512 ? (size_t)nt * sizeof(double) : 0);
-  if (nt == 1024) HCRG_LAUNCH(1024);
-  else if (nt == 256) HCRG_LAUNCH(256);
-  else HCRG_LAUNCH(512);
-  return hipGetLastError();
+// The ONE table of instantiations: workgroup size (256, 1024, anything else is 512), KB x 256 beams, and the sweeping
+// lanes' granules -- one for a grid of at most 64 workgroups, four up to 256.  Null: no such kernel.
+typedef void (*HcResidentGmKernel)(HcChainArgs);
+static HcResidentGmKernel hc_resident_gm_kernel(int nt, int kb, int grid) {
+  if (grid > 256) return nullptr;
+  return pick_hc_nt(nt, [&](auto nt_c) -> HcResidentGmKernel {
+    constexpr int NT = decltype(nt_c)::value;
+    const auto sweep = [&](auto kb_c) -> HcResidentGmKernel {
+      constexpr int KB = decltype(kb_c)::value;
+      return grid <= 64 ? k_hc_chain_resident_gm<NT, KB, 1> : k_hc_chain_resident_gm<NT, KB, 4>;
+    };
+    switch (kb) {
+      case 1: return sweep(int_c<1>{});
+      case 2: return sweep(int_c<2>{});
+      case 3: return sweep(int_c<3>{});
+      case 4: return sweep(int_c<4>{});
+      case 5: return sweep(int_c<5>{});
+      default: return nullptr;
+    }
+  });
 }
-#undef HCRG_LAUNCH
 
 hipError_t launch_hc_chain_resident_gm(const HcChainArgs &a, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
                                        int n_chains) {
   if (!a.rctl_gm || a.seq || a.jobs) return hipErrorInvalidValue;
-  switch ((a.scan.n + 255) / 256) {
-    case 1: return launch_res_gm<1>(a, nt, stream, e0, e1, n_chains);
-    case 2: return launch_res_gm<2>(a, nt, stream, e0, e1, n_chains);
-    case 3: return launch_res_gm<3>(a, nt, stream, e0, e1, n_chains);
-    case 4: return launch_res_gm<4>(a, nt, stream, e0, e1, n_chains);
-    case 5: return launch_res_gm<5>(a, nt, stream, e0, e1, n_chains);
-    default: break;
-  }
-  return hipErrorInvalidValue;
+  const int grid = 6 * a.max_inst + 1, kb = (a.scan.n + 255) / 256;
+  return launch_kernel(hc_resident_gm_kernel(nt, kb, grid), dim3(grid, n_chains), dim3(hc_nt_of(nt)),
+                       gm_chain_lds_bytes(kb, nt), stream, e0, e1, a);
 }
 
-// workgroups of `nt` threads the device keeps resident at once (see hc_resident_capacity)
+// workgroups of `nt` threads the device keeps resident at once (resident_capacity_of, kernel_pick.h): three 168-VGPR
+// waves per SIMD at 256 threads, four 128-VGPR ones else
 hipError_t hc_resident_gm_capacity(int nt, int n_beams, int *out_wgs, int *out_per_cu) {
-  int dev = 0, cus = 0, per_cu = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return e;
-  const int kb = (n_beams + 255) / 256;
-  const size_t shm = (size_t)kb * 256 * sizeof(double) + 4 * kb * sizeof(int2) + 4 * kb * sizeof(int) +
-                     2 * (size_t)kb * 256 * sizeof(int) + (nt >= 512 ? (size_t)nt * sizeof(double) : 0);
-  const void *fn = nt == 1024 ? (const void *)k_hc_chain_resident_gm<1024, 5, 4>
-                              : (nt == 256 ? (const void *)k_hc_chain_resident_gm<256, 5, 4>
-                                           : (const void *)k_hc_chain_resident_gm<512, 5, 4>);
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, shm);
-  if (e != hipSuccess) return e;
-  const int by_waves = nt == 256 ? 6 : 2048 / nt;  // (three 168-VGPR waves per SIMD at 256 threads, four 128-VGPR ones else)
-  per_cu = per_cu < by_waves ? per_cu : by_waves;
-  if (nt == 256 && per_cu > 3) per_cu = 3;
-  if (per_cu > 6) per_cu = 6;
-  *out_wgs = per_cu * (cus - 1);  // (one CU's worth of margin: hc_resident_capacity)
-  if (out_per_cu) *out_per_cu = per_cu;
-  return hipSuccess;
+  // the query is about <nt, 5, 4> -- the longest scan, the wide sweep -- whatever KB and sweep width are launched
+  return resident_capacity_of((const void *)hc_resident_gm_kernel(nt, 5, 256), nt, gm_chain_lds_bytes((n_beams + 255) / 256, nt),
+                              nt == 256 ? 6 : 2048 / nt, nt == 256 ? 3 : 6, out_wgs, out_per_cu);
 }
 
 }  // namespace slamhip

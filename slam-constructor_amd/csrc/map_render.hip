@@ -137,10 +137,6 @@ int render_invalid(const char *msg) {
 }
 
 bool format_ok(int format) { return format == SLAMHIP_RENDER_OCCGRID || format == SLAMHIP_RENDER_PGM; }
-bool occ_kind_ok(int model, int occ_kind) {
-  if (model == SLAMHIP_CELL_TBM) return occ_kind == SLAMHIP_OCC_TBM_CONSISTENT || occ_kind == SLAMHIP_OCC_TBM_UNKNOWN_EVEN;
-  return occ_kind == 0;
-}
 
 // room for `bytes` in the context's render buffer (kept between calls; a larger request replaces it)
 int render_reserve(slamhip_ctx *ctx, size_t bytes) {

@@ -170,8 +170,11 @@ struct slamhip_matcher {
   slamhip::ResidentPolicy resident;  // bounded spins that ran out: the kernel chain instead (resident_policy.h)
   // answers of the occupancy query so far, keyed by everything the answer depends on (kernel instantiation: cell model,
   // workgroup size, lone / batch / window form, sweep width via max_inst; dynamic LDS: scan length, beam constants)
+  enum class ResidentForm { Lone, Batch, Window, MonteCarlo, Pair };  // (Pair: a batch whose workgroups score two poses)
   struct ResidentCap {
-    int cell_model, nt, form, n_beams, lds_consts, max_inst, cap, per_cu;
+    int cell_model, nt;
+    ResidentForm form;
+    int n_beams, lds_consts, max_inst, cap, per_cu;
   };
   std::vector<ResidentCap> resident_caps;
   slamhip::PinnedBuf<slamhip::HcTraceEntry> h_trace;  // the observer's trace of a lone chain (HC and MC)
@@ -379,8 +382,8 @@ struct ResidentLease {
   ~ResidentLease() { release(); }
 };
 
-// form: 0 a lone chain, 1 a batch (job table), 2 a window OOPE, 3 Monte Carlo, 4 a batch whose workgroups score two poses
-int resident_capacity(slamhip_matcher *m, int cell_model, int nt, int form, int n_beams, bool lds_consts, int max_inst,
+using ResidentForm = slamhip_matcher::ResidentForm;
+int resident_capacity(slamhip_matcher *m, int cell_model, int nt, ResidentForm form, int n_beams, bool lds_consts, int max_inst,
                       int *wgs, int *per_cu = nullptr) {
   for (const auto &c : m->resident_caps)
     if (c.cell_model == cell_model && c.nt == nt && c.form == form && c.n_beams == n_beams &&
@@ -390,9 +393,13 @@ int resident_capacity(slamhip_matcher *m, int cell_model, int nt, int form, int 
       return SLAMHIP_OK;
     }
   int cap = 0, pc = 0;
-  if (form == 3) SLAMHIP_CHECK(mc_resident_capacity(cell_model, nt, n_beams, lds_consts, &cap, &pc));
-  else SLAMHIP_CHECK(hc_resident_capacity(cell_model, nt, form == 1 || form == 4, form == 2, n_beams, lds_consts, max_inst, &cap,
-                                          &pc, form == 4));
+  if (form == ResidentForm::MonteCarlo) {
+    SLAMHIP_CHECK(mc_resident_capacity(cell_model, nt, n_beams, lds_consts, &cap, &pc));
+  } else {
+    const bool pair = form == ResidentForm::Pair;
+    const HcResidentKey key{nt, max_inst, false, pair || form == ResidentForm::Batch, pair, form == ResidentForm::Window};
+    SLAMHIP_CHECK(hc_resident_capacity(cell_model, key, n_beams, lds_consts, &cap, &pc));
+  }
   if (cap < 0) cap = 0;
   if (m->resident_caps.size() >= 64) m->resident_caps.clear();  // (scans of ever-changing lengths: start over)
   m->resident_caps.push_back({cell_model, nt, form, n_beams, lds_consts ? 1 : 0, max_inst, cap, pc});
@@ -402,7 +409,7 @@ int resident_capacity(slamhip_matcher *m, int cell_model, int nt, int form, int 
 }
 // the 1-cell form keeps the further beams' constants in LDS (HcChainArgs::lds_consts) when `wgs_needed` workgroups
 // are resident together with that much LDS each
-int resident_capacity_pick(slamhip_matcher *m, int cell_model, int nt, int form, int n_beams, int max_inst, int wgs_needed,
+int resident_capacity_pick(slamhip_matcher *m, int cell_model, int nt, ResidentForm form, int n_beams, int max_inst, int wgs_needed,
                            bool may_lds_consts, int *lds_consts, int *wgs, int *per_cu = nullptr) {
   *lds_consts = 0;
   if (may_lds_consts) {
@@ -646,8 +653,8 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
       [&](ResidentLease &lease, bool *fits) -> int {
         int cap = 0, per_cu = 0, r = SLAMHIP_OK;
         if (gm) SLAMHIP_CHECK(hc_resident_gm_capacity(m->chain_nt, a.scan.n, &cap, &per_cu));
-        else r = resident_capacity_pick(m, cell_model, m->chain_nt, win ? 2 : 0, a.scan.n, a.max_inst, grid, !win,
-                                        &a.lds_consts, &cap, &per_cu);
+        else r = resident_capacity_pick(m, cell_model, m->chain_nt, win ? ResidentForm::Window : ResidentForm::Lone, a.scan.n,
+                                        a.max_inst, grid, !win, &a.lds_consts, &cap, &per_cu);
         if (r) return r;
         // (not counted as a give-up: this matcher's grid never fits / another context of this process holds the
         // device's resident slots: the chain of kernels at once, no stall)
@@ -1064,8 +1071,8 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
       ctx, m->resident, *b, a, n, b->resident_call && !a.seq, 0.9, &ran_resident, &launched,
       [&](ResidentLease &lease, bool *fits) -> int {
         int cap_wgs = 0, per_cu = 0;
-        const int r = resident_capacity_pick(m, cell_model, res_nt, b->pair ? 4 : 1, max_n, b->shapes.max_inst, res_wgs, true,
-                                             &a.lds_consts, &cap_wgs, &per_cu);
+        const int r = resident_capacity_pick(m, cell_model, res_nt, b->pair ? ResidentForm::Pair : ResidentForm::Batch, max_n,
+                                             b->shapes.max_inst, res_wgs, true, &a.lds_consts, &cap_wgs, &per_cu);
         if (r) return r;
         if (res_wgs <= cap_wgs && lease.take(m->device, res_wgs, per_cu)) {
           a.pair = b->pair ? 1 : 0;
@@ -1537,11 +1544,11 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
         // (1024-thread workgroups are resident one per CU: 252 candidates per super-step then, like the hill-climbing tree)
         if (m->chain_nt == 1024) a.n_slots = std::min(a.n_slots, 252);
         a.lds_consts = 1;
-        int r = resident_capacity(m, cell_model, m->chain_nt, 3, a.scan.n, true, 0, &cap, &per_cu);
+        int r = resident_capacity(m, cell_model, m->chain_nt, ResidentForm::MonteCarlo, a.scan.n, true, 0, &cap, &per_cu);
         if (r) return r;
         if (a.n_slots + 1 > cap) {  // (fewer workgroups fit with the beam constants in LDS than without?)
           int cap_plain = 0, pc_plain = 0;
-          r = resident_capacity(m, cell_model, m->chain_nt, 3, a.scan.n, false, 0, &cap_plain, &pc_plain);
+          r = resident_capacity(m, cell_model, m->chain_nt, ResidentForm::MonteCarlo, a.scan.n, false, 0, &cap_plain, &pc_plain);
           if (r) return r;
           if (cap_plain > cap) {
             a.lds_consts = 0;

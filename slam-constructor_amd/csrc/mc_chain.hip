@@ -11,7 +11,6 @@
 //                     first super-step, the best pose when a super-step is scored twice) with k_score_point's
 //                     arithmetic and canonical sum, so its bits equal the host-driven matcher's.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include "mc_chain_device.h"
 #include "score_device.h"
@@ -310,37 +309,19 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
   }
 }
 
-#define MC_LAUNCH(NTV)                                                                                             \
-  do {                                                                                                             \
-    if (e0 || e1)                                                                                                  \
-      hipExtLaunchKernelGGL((k_mc_chain_step<MODEL, NTV, SEQ>), dim3(grid), dim3(NTV), shm, stream, e0, e1, 0, a, k); \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_mc_chain_step<MODEL, NTV, SEQ>), dim3(grid), dim3(NTV), shm, stream, a, k);            \
-  } while (0)
-
-template <int MODEL, bool SEQ>
-static hipError_t launch_nt(const McChainArgs &a, int k, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-  const int grid = a.n_slots + 1;
-  const size_t shm = sizeof(double) * (size_t)(a.scan.n > 0 ? a.scan.n : 1);
-  if (nt == 512) MC_LAUNCH(512);
-  else MC_LAUNCH(1024);
-  return hipGetLastError();
-}
-#undef MC_LAUNCH
-
 hipError_t launch_mc_chain_step(const McChainArgs &a, int cell_model, int k, int nt, hipStream_t stream,
                                 hipEvent_t e0, hipEvent_t e1) {
   if (a.n_slots < 1 || a.n_slots > kMcSlots) return hipErrorInvalidValue;
-  if (cell_model == SLAMHIP_CELL_OCC)
-    return a.seq ? launch_nt<SLAMHIP_CELL_OCC, true>(a, k, nt, stream, e0, e1)
-                 : launch_nt<SLAMHIP_CELL_OCC, false>(a, k, nt, stream, e0, e1);
-  if (cell_model == SLAMHIP_CELL_TBM)
-    return a.seq ? launch_nt<SLAMHIP_CELL_TBM, true>(a, k, nt, stream, e0, e1)
-                 : launch_nt<SLAMHIP_CELL_TBM, false>(a, k, nt, stream, e0, e1);
-  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
-    return a.seq ? launch_nt<SLAMHIP_CELL_CREDIBILIST, true>(a, k, nt, stream, e0, e1)
-                 : launch_nt<SLAMHIP_CELL_CREDIBILIST, false>(a, k, nt, stream, e0, e1);
-  return hipErrorInvalidValue;
+  typedef void (*Kernel)(McChainArgs, int);
+  const Kernel kernel = pick_cell_model(cell_model, [&](auto model) -> Kernel {
+    return pick_mc_nt(nt, [&](auto nt_c) -> Kernel {
+      return pick_bool(a.seq != 0, [](auto seq_c) -> Kernel {
+        return k_mc_chain_step<decltype(model)::value, decltype(nt_c)::value, decltype(seq_c)::value>;
+      });
+    });
+  });
+  return launch_kernel(kernel, dim3(a.n_slots + 1), dim3(mc_nt_of(nt)), sizeof(double) * (size_t)(a.scan.n > 0 ? a.scan.n : 1),
+                       stream, e0, e1, a, k);
 }
 
 }  // namespace slamhip

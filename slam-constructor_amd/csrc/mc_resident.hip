@@ -15,7 +15,6 @@
 // complete stores the match's epoch in HcResidentCtl::fail_epoch, reports error 4 and leaves; the host then runs the
 // match as the chain of kernels.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include "hc_resident_device.h"
 #include "mc_chain_device.h"
@@ -450,65 +449,31 @@ size_t mc_resident_lds_bytes(int nt, int n_beams, bool lds_consts) {
   return sizeof(double) * (n + 3 * more);
 }
 
-#define MCR_LAUNCH(NTV)                                                                                            \
-  do {                                                                                                             \
-    if (e0 || e1)                                                                                                  \
-      hipExtLaunchKernelGGL((k_mc_chain_resident<MODEL, NTV, SEQ>), dim3(grid), dim3(NTV), shm, stream, e0, e1, 0, a); \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_mc_chain_resident<MODEL, NTV, SEQ>), dim3(grid), dim3(NTV), shm, stream, a);            \
-  } while (0)
-
-template <int MODEL, bool SEQ>
-static hipError_t launch_mcr(const McChainArgs &a, int nt, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-  const int grid = a.n_slots + 1;
-  const size_t shm = mc_resident_lds_bytes(nt, a.scan.n, a.lds_consts != 0);
-  if (nt == 512) MCR_LAUNCH(512);
-  else MCR_LAUNCH(1024);
-  return hipGetLastError();
+// The ONE table of instantiations (the launch and the capacity query both pick here); null: no such kernel
+typedef void (*McResidentKernel)(McChainArgs);
+static McResidentKernel mc_resident_kernel(int cell_model, int nt, bool seq) {
+  return pick_cell_model(cell_model, [&](auto model) -> McResidentKernel {
+    return pick_mc_nt(nt, [&](auto nt_c) -> McResidentKernel {
+      return pick_bool(seq, [](auto seq_c) -> McResidentKernel {
+        return k_mc_chain_resident<decltype(model)::value, decltype(nt_c)::value, decltype(seq_c)::value>;
+      });
+    });
+  });
 }
-#undef MCR_LAUNCH
 
 hipError_t launch_mc_chain_resident(const McChainArgs &a, int cell_model, int nt, hipStream_t stream, hipEvent_t e0,
                                     hipEvent_t e1) {
   if (!a.rctl || a.n_slots < 1 || a.n_slots > kMcSlots) return hipErrorInvalidValue;
-  if (cell_model == SLAMHIP_CELL_OCC)
-    return a.seq ? launch_mcr<SLAMHIP_CELL_OCC, true>(a, nt, stream, e0, e1)
-                 : launch_mcr<SLAMHIP_CELL_OCC, false>(a, nt, stream, e0, e1);
-  if (cell_model == SLAMHIP_CELL_TBM)
-    return a.seq ? launch_mcr<SLAMHIP_CELL_TBM, true>(a, nt, stream, e0, e1)
-                 : launch_mcr<SLAMHIP_CELL_TBM, false>(a, nt, stream, e0, e1);
-  if (cell_model == SLAMHIP_CELL_CREDIBILIST)
-    return a.seq ? launch_mcr<SLAMHIP_CELL_CREDIBILIST, true>(a, nt, stream, e0, e1)
-                 : launch_mcr<SLAMHIP_CELL_CREDIBILIST, false>(a, nt, stream, e0, e1);
-  return hipErrorInvalidValue;
+  return launch_kernel(mc_resident_kernel(cell_model, nt, a.seq != 0), dim3(a.n_slots + 1), dim3(mc_nt_of(nt)),
+                       mc_resident_lds_bytes(nt, a.scan.n, a.lds_consts != 0), stream, e0, e1, a);
 }
 
-// workgroups of `nt` threads the device keeps resident at once (hc_resident_capacity's rule)
+// workgroups of `nt` threads the device keeps resident at once (resident_capacity_of, kernel_pick.h)
 hipError_t mc_resident_capacity(int cell_model, int nt, int n_beams, bool lds_consts, int *out_wgs, int *out_per_cu) {
-  int dev = 0, cus = 0, per_cu = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return e;
-  const void *fn = nullptr;
-  if (cell_model == SLAMHIP_CELL_TBM)
-    fn = nt == 1024 ? (const void *)k_mc_chain_resident<SLAMHIP_CELL_TBM, 1024, false>
-                    : (const void *)k_mc_chain_resident<SLAMHIP_CELL_TBM, 512, false>;
-  else if (cell_model == SLAMHIP_CELL_CREDIBILIST)
-    fn = nt == 1024 ? (const void *)k_mc_chain_resident<SLAMHIP_CELL_CREDIBILIST, 1024, false>
-                    : (const void *)k_mc_chain_resident<SLAMHIP_CELL_CREDIBILIST, 512, false>;
-  else if (cell_model == SLAMHIP_CELL_OCC)
-    fn = nt == 1024 ? (const void *)k_mc_chain_resident<SLAMHIP_CELL_OCC, 1024, false>
-                    : (const void *)k_mc_chain_resident<SLAMHIP_CELL_OCC, 512, false>;
-  else
-    return hipErrorInvalidValue;  // (never another model's kernel)
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, mc_resident_lds_bytes(nt, n_beams, lds_consts));
-  if (e != hipSuccess) return e;
-  const int by_waves = 2048 / nt;  // 128-VGPR waves: four per SIMD
-  per_cu = per_cu < by_waves ? per_cu : by_waves;
-  *out_wgs = per_cu * (cus - 1);  // (one CU's worth of margin: hc_resident_capacity)
-  if (out_per_cu) *out_per_cu = per_cu;
-  return hipSuccess;
+  // (the query is about the default sum order's kernel, whichever order is launched -- as for the hill-climbing chain)
+  return resident_capacity_of((const void *)mc_resident_kernel(cell_model, nt, false), nt,
+                              mc_resident_lds_bytes(nt, n_beams, lds_consts), 2048 / nt /* 128-VGPR waves: four per SIMD */,
+                              0, out_wgs, out_per_cu);
 }
 
 }  // namespace slamhip

@@ -133,17 +133,12 @@ int sg_invalid(const char *msg) {
   return SLAMHIP_ERR_INVALID;
 }
 
-bool sg_occ_kind_ok(int model, int occ_kind) {
-  if (model == SLAMHIP_CELL_TBM) return occ_kind == SLAMHIP_OCC_TBM_CONSISTENT || occ_kind == SLAMHIP_OCC_TBM_UNKNOWN_EVEN;
-  return occ_kind == 0;
-}
-
 constexpr int kSgMaxBeams = 1 << 26;
 
 // the checks the device entry and the host entry share; null = fine
 const char *sg_check_call(int model, int occ_kind, int variant, int n_poses, const double *poses_xyt, int n_angles,
                           const double *angles, const double *range_out, const unsigned char *status_out) {
-  if (!sg_occ_kind_ok(model, occ_kind)) return "occ_kind names a TBM cell class: 0 or 1 on a TBM map, 0 on every other";
+  if (!occ_kind_ok(model, occ_kind)) return "occ_kind names a TBM cell class: 0 or 1 on a TBM map, 0 on every other";
   if (variant != 0 && variant != 1) return "variant: 0 = glibc's plain build of sin / cos, 1 = its FMA build";
   if (n_poses < 0 || n_angles < 0) return "negative count";
   if ((long long)n_poses * n_angles > kSgMaxBeams) return "more than 2^26 beams in one call";

@@ -35,11 +35,11 @@
 //  * map window = pitched row-major HBM array; out-of-window reads return the prototype payload
 //    (UnboundedPlainGridMap::operator[], src/core/maps/plain_grid_map.h:69-73).
 
-#include <hip/hip_ext.h>
 
 #include <algorithm>
 
 #include "gm_score_device.h"
+#include "kernel_pick.h"
 #include "score_device.h"
 
 namespace slamhip {
@@ -522,31 +522,18 @@ __global__ __launch_bounds__(kBlock) void k_score_window(ScoreArgs a, int oope) 
 }
 
 // ---- launch ------------------------------------------------------------------------------------
-// Scoring launches go through hipExtLaunchKernelGGL so that slamhip_profile_* can attach its
-// HIP events to the dispatch itself: the elapsed time is then the kernel's own begin..end (what
-// rocprofv3 --kernel-trace reports), not record-to-record on an idle stream which adds ~4 us of
-// queue processing per isolated launch (tools/event_probe.hip).  Without events the ordinary launch
-// is used.
-#define SLAMHIP_LAUNCH(kernel, grid, block, shm, st, e0, e1, ...)                          \
-  do {                                                                                     \
-    if ((e0) || (e1))                                                                      \
-      hipExtLaunchKernelGGL(kernel, grid, block, shm, st, e0, e1, 0, __VA_ARGS__);         \
-    else                                                                                   \
-      hipLaunchKernelGGL(kernel, grid, block, shm, st, __VA_ARGS__);                       \
-  } while (0)
-
-template <int MODEL, bool WT, bool FP = false>
-static hipError_t launch_point_kb(const ScoreArgs &a, int kb, dim3 grid, hipStream_t st,
-                                  hipEvent_t e0, hipEvent_t e1) {
+// (every launch below is launch_kernel, kernel_pick.h: events, when given, ride on the dispatch itself)
+typedef void (*ScoreKernel)(ScoreArgs);
+template <int MODEL, bool WT, bool FP>
+static ScoreKernel point_kernel(int kb) {
   switch (kb) {
-    case 1: SLAMHIP_LAUNCH((k_score_point<MODEL, 1, WT, FP>), grid, dim3(kBlock), 0, st, e0, e1, a); break;
-    case 2: SLAMHIP_LAUNCH((k_score_point<MODEL, 2, WT, FP>), grid, dim3(kBlock), 0, st, e0, e1, a); break;
-    case 3: SLAMHIP_LAUNCH((k_score_point<MODEL, 3, WT, FP>), grid, dim3(kBlock), 0, st, e0, e1, a); break;
-    case 4: SLAMHIP_LAUNCH((k_score_point<MODEL, 4, WT, FP>), grid, dim3(kBlock), 0, st, e0, e1, a); break;
-    case 5: SLAMHIP_LAUNCH((k_score_point<MODEL, 5, WT, FP>), grid, dim3(kBlock), 0, st, e0, e1, a); break;
-    default: SLAMHIP_LAUNCH((k_score_point<MODEL, 0, WT, FP>), grid, dim3(kBlock), 0, st, e0, e1, a); break;
+    case 1: return k_score_point<MODEL, 1, WT, FP>;
+    case 2: return k_score_point<MODEL, 2, WT, FP>;
+    case 3: return k_score_point<MODEL, 3, WT, FP>;
+    case 4: return k_score_point<MODEL, 4, WT, FP>;
+    case 5: return k_score_point<MODEL, 5, WT, FP>;
+    default: return k_score_point<MODEL, 0, WT, FP>;
   }
-  return hipGetLastError();
 }
 
 static int pick_poses_per_block(int n_poses) {
@@ -589,59 +576,49 @@ hipError_t launch_score(const ScoreArgs &args, int cell_model, int oope, int sum
     // 1024 threads per pose for launches of at most 160 poses
     constexpr int wide_below = 160;
     const int wide = a.n_poses <= wide_below ? 1024 : 0;
-    const size_t shm_wide = shm + 2 * (size_t)kb * kBlock * sizeof(int) + kGmHelperDoubles<1024> * sizeof(double);
+    const size_t shm_wide = gm_chain_lds_bytes(kb, 1024);
     dim3 grid_gm = grid;  // k_score_gmapping only: the XCD-chunked block order (see the kernel)
     if (a.tables && !xcd_off && grid.x >= 16 && !(a.poses_per_block == 1 && wide)) {
       a.xcd_blocks = (int)grid.x;
       grid_gm.x = (grid.x + 7) / 8 * 8;
     }
-#define GM_CASE(K)                                                                                            \
-  case K:                                                                                                     \
-    if (a.poses_per_block == 1 && wide == 1024)                                                               \
-      SLAMHIP_LAUNCH((k_score_gmapping_wide<K, 1024>), grid, dim3(1024), shm_wide, stream, ev_start, ev_stop, a); \
-    else if (a.poses_per_block == 1)                                                                          \
-      SLAMHIP_LAUNCH((k_score_gmapping<K, true>), grid_gm, dim3(kBlock), shm, stream, ev_start, ev_stop, a);  \
-    else                                                                                                      \
-      SLAMHIP_LAUNCH((k_score_gmapping<K, false>), grid_gm, dim3(kBlock), shm, stream, ev_start, ev_stop, a); \
-    break;
+    const auto gm_kernel = [&](auto kb_c) {
+      constexpr int K = decltype(kb_c)::value;
+      if (a.poses_per_block == 1 && wide == 1024)
+        return launch_kernel(k_score_gmapping_wide<K, 1024>, grid, dim3(1024), shm_wide, stream, ev_start, ev_stop, a);
+      if (a.poses_per_block == 1)
+        return launch_kernel(k_score_gmapping<K, true>, grid_gm, dim3(kBlock), shm, stream, ev_start, ev_stop, a);
+      return launch_kernel(k_score_gmapping<K, false>, grid_gm, dim3(kBlock), shm, stream, ev_start, ev_stop, a);
+    };
     switch (kb < 1 ? 1 : kb) {
-      GM_CASE(1) GM_CASE(2) GM_CASE(3) GM_CASE(4) GM_CASE(5) GM_CASE(6) GM_CASE(7) GM_CASE(8)
+      case 1: return gm_kernel(int_c<1>{});
+      case 2: return gm_kernel(int_c<2>{});
+      case 3: return gm_kernel(int_c<3>{});
+      case 4: return gm_kernel(int_c<4>{});
+      case 5: return gm_kernel(int_c<5>{});
+      case 6: return gm_kernel(int_c<6>{});
+      case 7: return gm_kernel(int_c<7>{});
+      default: return gm_kernel(int_c<8>{});
     }
-#undef GM_CASE
-    return hipGetLastError();
   }
   if (oope == SLAMHIP_OOPE_MAX || oope == SLAMHIP_OOPE_MEAN || oope == SLAMHIP_OOPE_OVERLAP) {
     if (!wt) a.terms = nullptr;
     if (wt) a.fprints = nullptr;
-    if (cell_model == SLAMHIP_CELL_OCC)
-      SLAMHIP_LAUNCH((k_score_window<SLAMHIP_CELL_OCC>), grid, dim3(kBlock), 0, stream, ev_start, stop1, a, oope);
-    else if (cell_model == SLAMHIP_CELL_TBM)
-      SLAMHIP_LAUNCH((k_score_window<SLAMHIP_CELL_TBM>), grid, dim3(kBlock), 0, stream, ev_start, stop1, a, oope);
-    else if (cell_model == SLAMHIP_CELL_CREDIBILIST)
-      SLAMHIP_LAUNCH((k_score_window<SLAMHIP_CELL_CREDIBILIST>), grid, dim3(kBlock), 0, stream, ev_start, stop1, a, oope);
-    else
-      return hipErrorInvalidValue;
-    e = hipGetLastError();
-  } else if (cell_model == SLAMHIP_CELL_OCC) {
-    e = wt ? launch_point_kb<SLAMHIP_CELL_OCC, true>(a, kb, grid, stream, ev_start, stop1)
-           : (a.fprints ? launch_point_kb<SLAMHIP_CELL_OCC, false, true>(a, kb, grid, stream, ev_start, stop1)
-                        : launch_point_kb<SLAMHIP_CELL_OCC, false>(a, kb, grid, stream, ev_start, stop1));
-  } else if (cell_model == SLAMHIP_CELL_TBM) {
-    e = wt ? launch_point_kb<SLAMHIP_CELL_TBM, true>(a, kb, grid, stream, ev_start, stop1)
-           : (a.fprints ? launch_point_kb<SLAMHIP_CELL_TBM, false, true>(a, kb, grid, stream, ev_start, stop1)
-                        : launch_point_kb<SLAMHIP_CELL_TBM, false>(a, kb, grid, stream, ev_start, stop1));
-  } else if (cell_model == SLAMHIP_CELL_CREDIBILIST) {
-    e = wt ? launch_point_kb<SLAMHIP_CELL_CREDIBILIST, true>(a, kb, grid, stream, ev_start, stop1)
-           : (a.fprints ? launch_point_kb<SLAMHIP_CELL_CREDIBILIST, false, true>(a, kb, grid, stream, ev_start, stop1)
-                        : launch_point_kb<SLAMHIP_CELL_CREDIBILIST, false>(a, kb, grid, stream, ev_start, stop1));
+    typedef void (*Kernel)(ScoreArgs, int);
+    e = launch_kernel(pick_cell_model(cell_model, [](auto m) -> Kernel { return k_score_window<decltype(m)::value>; }), grid,
+                      dim3(kBlock), 0, stream, ev_start, stop1, a, oope);
   } else {
-    return hipErrorInvalidValue;
+    const ScoreKernel kernel = pick_cell_model(cell_model, [&](auto m) -> ScoreKernel {
+      constexpr int M = decltype(m)::value;
+      return wt ? point_kernel<M, true, false>(kb)
+                : (a.fprints ? point_kernel<M, false, true>(kb) : point_kernel<M, false, false>(kb));
+    });
+    e = launch_kernel(kernel, grid, dim3(kBlock), 0, stream, ev_start, stop1, a);
   }
   if (e != hipSuccess) return e;
   if (wt) {  // strict order is two kernels: the caller times the pair with recorded events instead
-    SLAMHIP_LAUNCH(k_sum_sequential, dim3((a.n_poses + 63) / 64), dim3(64), 0, stream, (hipEvent_t) nullptr,
-                   (hipEvent_t) nullptr, a.terms, a.n_poses, a.scan.n, a.scan.tot_w, a.scores);
-    e = hipGetLastError();
+    e = launch_kernel(k_sum_sequential, dim3((a.n_poses + 63) / 64), dim3(64), 0, stream, nullptr, nullptr, a.terms, a.n_poses,
+                      a.scan.n, a.scan.tot_w, a.scores);
   }
   return e;
 }
@@ -792,28 +769,22 @@ hipError_t launch_prob_build(int model, const double *payload, double *prob, int
   const int xa = x0 < 0 ? 0 : x0, ya = y0 < 0 ? 0 : y0;
   const int xb = x0 + w > width ? width : x0 + w, yb = y0 + h > height ? height : y0 + h;
   if (xb <= xa || yb <= ya) return hipSuccess;
-  if (!cell_is_belief(model)) return hipErrorInvalidValue;
-  const auto k = model == SLAMHIP_CELL_CREDIBILIST ? k_prob_build<SLAMHIP_CELL_CREDIBILIST> : k_prob_build<SLAMHIP_CELL_TBM>;
-  hipLaunchKernelGGL(k, dim3((xb - xa + 255) / 256, yb - ya), dim3(256), 0, stream,
-                     reinterpret_cast<const double4 *>(payload), prob, pitch, xa, ya, xb - xa, yb - ya);
-  return hipGetLastError();
+  const auto k = pick_belief_model(model, [](auto m) { return &k_prob_build<decltype(m)::value>; });
+  return launch_kernel(k, dim3((xb - xa + 255) / 256, yb - ya), dim3(256), 0, stream, nullptr, nullptr,
+                       reinterpret_cast<const double4 *>(payload), prob, pitch, xa, ya, xb - xa, yb - ya);
 }
 hipError_t launch_prob_cells(int model, const double *payload, double *prob, int width, int height, int pitch, int n, const int *d_coords,
                              hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  if (!cell_is_belief(model)) return hipErrorInvalidValue;
-  const auto k = model == SLAMHIP_CELL_CREDIBILIST ? k_prob_cells<SLAMHIP_CELL_CREDIBILIST> : k_prob_cells<SLAMHIP_CELL_TBM>;
-  hipLaunchKernelGGL(k, dim3((n + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const double4 *>(payload), prob,
-                     width, height, pitch, n, d_coords);
-  return hipGetLastError();
+  const auto k = pick_belief_model(model, [](auto m) { return &k_prob_cells<decltype(m)::value>; });
+  return launch_kernel(k, dim3((n + 255) / 256), dim3(256), 0, stream, nullptr, nullptr,
+                       reinterpret_cast<const double4 *>(payload), prob, width, height, pitch, n, d_coords);
 }
 hipError_t launch_prob_check(int model, const double *payload, const double *prob, int width, int height, int pitch,
                              unsigned long long *d_count, hipStream_t stream) {
-  if (!cell_is_belief(model)) return hipErrorInvalidValue;
-  const auto k = model == SLAMHIP_CELL_CREDIBILIST ? k_prob_check<SLAMHIP_CELL_CREDIBILIST> : k_prob_check<SLAMHIP_CELL_TBM>;
-  hipLaunchKernelGGL(k, dim3((width + 255) / 256, height), dim3(256), 0, stream,
-                     reinterpret_cast<const double4 *>(payload), prob, width, pitch, d_count);
-  return hipGetLastError();
+  const auto k = pick_belief_model(model, [](auto m) { return &k_prob_check<decltype(m)::value>; });
+  return launch_kernel(k, dim3((width + 255) / 256, height), dim3(256), 0, stream, nullptr, nullptr,
+                       reinterpret_cast<const double4 *>(payload), prob, width, pitch, d_count);
 }
 
 hipError_t launch_fill_cells(double *dst, size_t n_cells, int cell_dbl, const double *u,

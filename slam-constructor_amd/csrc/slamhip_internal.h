@@ -100,6 +100,11 @@ __host__ __device__ inline double cell_occupancy(int model, int occ_kind, double
   if (cell_is_belief(model)) return p2 + 0.5 * p0;
   return p0;
 }
+// occ_kind names a TBM cell class: 0 or 1 on a TBM map, 0 on every other
+inline bool occ_kind_ok(int model, int occ_kind) {
+  if (model == SLAMHIP_CELL_TBM) return occ_kind == SLAMHIP_OCC_TBM_CONSISTENT || occ_kind == SLAMHIP_OCC_TBM_UNKNOWN_EVEN;
+  return occ_kind == 0;
+}
 // OccupancyGridPublisher::on_map_update's cell (src/ros/occupancy_grid_publisher.h:42-44): `int cell_value =
 // value == -1 ? -1 : value * 100`, pushed into an int8 vector.  The reference's conversion is undefined for a value
 // that is not finite or whose hundredfold leaves the range of int; here a non-finite occupancy writes -1 (unknown) and a

@@ -146,3 +146,25 @@ def test_resident_policy_switch_off_and_rearm(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("ok 360000 driver calls")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
+def test_kernel_pick_table(tmp_path):
+    """csrc/kernel_pick.h -- the one table the chain launchers AND the capacity queries pick their template instantiation
+    from (tests/native/kernel_pick_test.cpp): the cell-model dispatcher calls its lambda once with the matching constant
+    for OCC, TBM and CREDIBILIST and reports "no kernel" for GMAPPING, -1 and 4 without calling it; the normalisation of a
+    co-resident hill-climbing variant agrees, over 4 workgroup sizes x 64 tree sizes x batch / pair / window / seq, with
+    the accept / refuse and (nt, G) table the launchers had (1570 of the 4096 are accepted: 2 x 42 x 4 window, 64 pair,
+    5 x (3 x 64 + 42) plain); gm_chain_lds_bytes is the expression the GMapping chain's launcher had."""
+    exe = str(tmp_path / "kernel_pick_test")
+    hip_inc = "/opt/rocm/include"
+    if not os.path.exists(os.path.join(hip_inc, "hip", "hip_runtime.h")):
+        pytest.skip("HIP headers not found")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-fno-omit-frame-pointer", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + hip_inc,
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "slam-constructor_amd", "csrc"),
+           os.path.join(ROOT, "tests", "native", "kernel_pick_test.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok 1570 of 4096 co-resident variants accepted")
