@@ -265,6 +265,85 @@ int slamhip_scan_generate_host(int cell_model, int occ_kind, int variant, int wi
                                const double *poses_xyt, int n_angles, const double *angles, double max_dist,
                                double occ_threshold, double *range_out, unsigned char *status_out);
 
+/* ---------------------------------------------------------------- map pyramid (csrc/map_pyramid.hip)
+ * The two data-parallel parts of the many-to-many multi-resolution matcher (BF_M3RSM, Olson 2015):
+ * M3RSMRescalableGridMap (src/core/scan_matchers/m3rsm_engine.h:17-131 over RescalableCachingGridMap,
+ * src/core/maps/rescalable_caching_grid_map.h) and Match::prob_upper_bound (m3rsm_engine.h:156-180).  The best-first
+ * engine (M3RSMEngine, :238-382) is not here.
+ *
+ * LEVELS.  Over a bound dense map of model OCC, TBM or CREDIBILIST (the "fine" map, level 0) the pyramid keeps levels
+ * 1 .. K, each an ORDINARY bound map with its own map id (first_level_map_id + k - 1), the fine map's cell model and
+ * unknown payload, and scale = fine scale doubled k times: slamhip_score_poses, slamhip_map_download_window,
+ * slamhip_map_render, ... take a level's id as they take any map's.  Level K is the reference's one cell of infinite
+ * scale (rescalable_caching_grid_map.h:35-38): 1 x 1, external cell (0, 0).
+ *   The coarse cell at EXTERNAL (X, Y) of level k < K covers the fine external cells (x, y) with floor(x / 2^k) == X and
+ *   floor(y / 2^k) == Y (a floor: negative coordinates too); the cell of level K covers every fine cell.  It holds a COPY
+ *   of the payload of the known fine cell of largest impact = estimate_obstacle_impact = the per-beam probability of
+ *   the scorer for that cell under `oie` (TBM and CREDIBILIST cells: the discrepancy OIE only, as in
+ *   slamhip_score_poses); a block without a known fine cell holds the unknown payload.  Equal impacts: the smallest
+ *   fine x, then y.  Impacts are compared as numbers, -0 below +0 (NaN impacts, which no valid map holds, by their bits):
+ *   a total order, so the result does not depend on how a block is reduced, and two builds give the same bits.
+ *   KNOWN means: the payload is not bit-equal to the map's unknown payload.  The resident map has no _is_unknown flag
+ *   (grid_cell.h), so a cell that WAS observed and still -- or again -- holds exactly the prototype's payload counts as
+ *   unknown here and as known in the reference: the one case where a level cell can differ from the invariant the
+ *   reference checks (validate(), m3rsm_engine.h:36-60).
+ *   The list of levels is the one ensure_map_cache_is_continuous (rescalable_caching_grid_map.h:171-194) ends with for
+ *   a fine map of the same extent whose cells have all been written: levels are added until the last one before the
+ *   1 x 1 level is at most 2 x 2 cells, centred on external (0, 0) -- K - 1 = the smallest k >= 0 with
+ *   2^k >= max(origin_x, width - origin_x, origin_y, height - origin_y).  A level's window is the tight one around its
+ *   blocks (the reference's level windows are centred and grow by Expansion_Rate: supersets, the same cells).
+ * Two deliberate differences from the reference:
+ *   - the reference never LOWERS a coarse cell (m3rsm_engine.h:96, a TODO): after a fine cell's impact has gone down
+ *     its levels keep the old maximum.  The levels here are tight after any history -- a valid and sharper bound;
+ *   - the reference skips a propagation when the new impact exceeds the level's by less than ~1e-7 (less_or_equal,
+ *     :117-119), so its levels can sit that far below the true maximum.  The levels here hold the exact maximum.
+ *
+ * create plans and binds the levels (the ids must be free; SLAMHIP_ERR_INVALID for a GMAPPING or unbound fine map, a
+ * bad oie, ids out of range) and queues the whole build on the context's stream.  rebuild queues it again -- and plans
+ * and binds the levels anew when the fine map has been re-bound (grown) since.  refresh recomputes only the coarse
+ * cells whose blocks meet the fine window [x0, x0 + w) x [y0, y0 + h) (INTERNAL coordinates): call it after
+ * slamhip_map_append_scan* / slamhip_map_apply_dirty with the window they wrote.  Both are queued on the context's
+ * stream, hence behind deferred map updates, and return without waiting.  refresh and the scorer below fail with
+ * SLAMHIP_ERR_STATE when the fine map or a level has been re-bound or released behind the pyramid's back.
+ * destroy releases the levels and their ids. */
+typedef struct slamhip_pyramid slamhip_pyramid;
+int slamhip_pyramid_create(slamhip_ctx *ctx, int fine_map_id, int oie, int first_level_map_id, slamhip_pyramid **out);
+int slamhip_pyramid_destroy(slamhip_pyramid *pyr);
+/* *n_levels = K; entry k - 1 of each array (room for `cap` entries; any pointer may be NULL) = level k */
+int slamhip_pyramid_info(slamhip_pyramid *pyr, int *n_levels, int cap, int *map_id, int *width, int *height,
+                         int *origin_x, int *origin_y, double *scale);
+int slamhip_pyramid_rebuild(slamhip_pyramid *pyr);
+int slamhip_pyramid_refresh(slamhip_pyramid *pyr, int x0, int y0, int w, int h);
+/* Host only, no GPU: the same levels over a map on the host (payload[height][width] cells of 1 (OCC) or 4 doubles,
+ * (origin_x, origin_y) = the internal coordinates of external cell (0, 0)) by the definition the kernels share
+ * (csrc/map_pyramid_device.h).  *n_levels = K; the geometry arrays (room for level_cap entries, any may be NULL) as in
+ * slamhip_pyramid_info; payload_out (may be NULL: geometry only) receives the levels one after the other, level 1
+ * first, each row-major [height_k][width_k][stride]; *payload_need (may be NULL) = the doubles that takes. */
+int slamhip_pyramid_build_host(int cell_model, int oie, int width, int height, int origin_x, int origin_y, double scale,
+                               const double *unknown_payload, const double *payload, int level_cap, int *n_levels,
+                               int *level_width, int *level_height, int *level_origin_x, int *level_origin_y,
+                               double *level_scale, size_t payload_cap, double *payload_out, size_t *payload_need);
+/* BOUNDS.  Match::prob_upper_bound for n candidates in ONE launch, on the context's current scan.  Candidate i =
+ * (rotation[i], rect[i] = bot, top, left, right: its translation rectangle):
+ *   level_out[i] = the first k (0 = the fine map) with max(top - bot, right - left) <= scale_k
+ *                  (RescalableCachingGridMap::rescale, rescalable_caching_grid_map.h:79-91);
+ *   score_out[i] = the scan's probability at pose (x + c.x, y + c.y, rotation[i] + theta), (x, y, theta) = base_pose,
+ *                  c = LightWeightRectangle::center() = (left + (right - left) / 2, bot + (top - bot) / 2), on that
+ *                  level, with sp_analysis_area = rect[i].
+ * cfg->oope must be a window OOPE (max / mean / overlap), cfg->oie the pyramid's; cfg->area is ignored (the rule of
+ * cfg->area, at most 10^4 cells per beam, holds by construction: a rectangle is at most one cell of its level wide).
+ * Both sum orders; pose_trig DEVICE or HOST.  The value is BIT-EQUAL to slamhip_score_poses on level_out[i]'s map id
+ * with cfg.area = rect[i] and that pose: the same per-beam functions, the same canonical sums.
+ * SLAMHIP_ERR_INVALID: a rotation, rectangle or base pose that is not finite, bot > top or left > right.
+ * _device: rotation, rect, score_out, level_out in HBM, asynchronous on the context's stream, pose_trig DEVICE only;
+ * a candidate whose rectangle is not finite or is reversed gets NaN and level -1 there. */
+int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *pyr, const slamhip_spe_cfg *cfg,
+                                  const double base_pose[3], int n, const double *rotation, const double *rect,
+                                  double *score_out, int *level_out);
+int slamhip_pyramid_score_matches_device(slamhip_ctx *ctx, slamhip_pyramid *pyr, const slamhip_spe_cfg *cfg,
+                                         const double base_pose[3], int n, const double *d_rotation, const double *d_rect,
+                                         double *d_score_out, int *d_level_out);
+
 /* ---------------------------------------------------------------- map update (kernel K6)
  * Replaces GridMapScanAdder::append_scan (src/core/maps/grid_map_scan_adders.h:54-75) with
  * WallDistanceBlurringScanAdder::handle_scan_point (:138-172) and ConstOccupancyEstimator

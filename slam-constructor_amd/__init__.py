@@ -60,7 +60,9 @@ slamhip_shard_attach slamhip_shard_exchange slamhip_shard_p2p_stats slamhip_shar
 slamhip_gmapping_migration_stats slamhip_map_append_scan_q slamhip_omqe_quality slamhip_scan_filter_upload
 slamhip_scan_set_angles slamhip_libm_variant slamhip_libm_eval slamhip_map_append_scan_raw
 slamhip_map_render slamhip_gmapping_particle_map_render slamhip_render_cells
-slamhip_scan_gen_angles slamhip_scan_gen_libm_variant slamhip_map_generate_scans slamhip_scan_generate_host""".split()
+slamhip_scan_gen_angles slamhip_scan_gen_libm_variant slamhip_map_generate_scans slamhip_scan_generate_host
+slamhip_pyramid_create slamhip_pyramid_destroy slamhip_pyramid_info slamhip_pyramid_rebuild slamhip_pyramid_refresh
+slamhip_pyramid_build_host slamhip_pyramid_score_matches slamhip_pyramid_score_matches_device""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -273,6 +275,15 @@ def load(testing=False):
     L.slamhip_scan_gen_libm_variant.argtypes = [_ip]
     L.slamhip_map_generate_scans.argtypes = [vp, i, i, i, i, i, _dp, i, _dp, d, d, _dp, vp]
     L.slamhip_scan_generate_host.argtypes = [i, i, i, i, i, i, i, d, _dp, _dp, i, _dp, i, _dp, d, d, _dp, vp]
+    L.slamhip_pyramid_create.argtypes = [vp, i, i, i, C.POINTER(vp)]
+    L.slamhip_pyramid_destroy.argtypes = [vp]
+    L.slamhip_pyramid_info.argtypes = [vp, _ip, i, _ip, _ip, _ip, _ip, _ip, _dp]
+    L.slamhip_pyramid_rebuild.argtypes = [vp]
+    L.slamhip_pyramid_refresh.argtypes = [vp, i, i, i, i]
+    L.slamhip_pyramid_build_host.argtypes = [i, i, i, i, i, i, d, _dp, _dp, i, _ip, _ip, _ip, _ip, _ip, _dp, C.c_size_t, _dp,
+                                             C.POINTER(C.c_size_t)]
+    L.slamhip_pyramid_score_matches.argtypes = [vp, vp, C.POINTER(SpeCfg), _dp, i, _dp, _dp, _dp, _ip]
+    L.slamhip_pyramid_score_matches_device.argtypes = [vp, vp, C.POINTER(SpeCfg), _dp, i, vp, vp, vp, vp]
     _libs[testing] = L
     return L
 
@@ -1080,6 +1091,142 @@ class Matcher:
         a, b = C.c_longlong(), C.c_longlong()
         _check(self.L.slamhip_matcher_resident_stats(self.h, C.byref(a), C.byref(b)))
         return dict(matches=a.value, gave_up=b.value)
+
+
+# ---- map pyramid (M3RSMRescalableGridMap, Match::prob_upper_bound) ----------------------------------
+PYRAMID_MAX_LEVELS = 34
+
+
+def pyramid_build_host(m, oie=OIE_DISCREPANCY):
+    """slamhip_pyramid_build_host, no GPU: the max-impact levels over a map on the host by the definition the kernels
+    share.  m: any object with cell_model, payload[h, w, stride], origin, scale, unknown.  Returns a list, level 1 first,
+    of dicts width, height, origin (x, y), scale, payload[height, width, stride]; the last is the 1 x 1 level of
+    infinite scale."""
+    stride = STRIDE[m.cell_model]
+    payload = _f64(m.payload)
+    h, w = payload.shape[:2]
+    payload = payload.reshape(h, w, -1)
+    unk = np.zeros(4)
+    unk[:stride] = np.asarray(m.unknown, dtype=np.float64).ravel()[:stride]
+    cap = PYRAMID_MAX_LEVELS
+    n = C.c_int(0)
+    geo = [np.zeros(cap, np.int32) for _ in range(4)]
+    scale = np.zeros(cap)
+    need = C.c_size_t(0)
+    L = load()
+
+    def call(cap_doubles, out):
+        _check(L.slamhip_pyramid_build_host(int(m.cell_model), int(oie), w, h, int(m.origin[0]), int(m.origin[1]),
+                                            float(m.scale), _d(unk), _d(payload), cap, C.byref(n),
+                                            *[g.ctypes.data_as(_ip) for g in geo], _d(scale), cap_doubles,
+                                            None if out is None else _d(out), C.byref(need)))
+
+    call(0, None)
+    flat = np.zeros(need.value)
+    call(flat.size, flat)
+    levels, at = [], 0
+    for k in range(n.value):
+        lw, lh = int(geo[0][k]), int(geo[1][k])
+        levels.append(dict(width=lw, height=lh, origin=(int(geo[2][k]), int(geo[3][k])), scale=float(scale[k]),
+                           payload=flat[at:at + lw * lh * stride].reshape(lh, lw, stride).copy()))
+        at += lw * lh * stride
+    return levels
+
+
+def m3rsm_root_candidates(limits, ang_step):
+    """The root layer of M3RSMEngine::add_scan_matching_request (m3rsm_engine.h:291-316) for limits = (max_x_error,
+    max_y_error, rotation_sector) and the rotation step: (rotation[n], rect[n, 4]) in the order the reference makes its
+    matches -- rotation_drift = 0, step, 2 step, ... (accumulated) while 2 drift <= sector under less_or_equal
+    (math_utils.h), per drift the rotations of std::set{drift, -drift} (ascending: -drift first, 0 once), per rotation the
+    empty rectangle and then the entire one (bot, top, left, right) = (-max_y, max_y, -max_x, max_x)."""
+    max_x, max_y, sector = (float(v) for v in limits)
+    step = float(ang_step)
+    if not step > 0:
+        raise ValueError("the rotation step must be positive")
+
+    def are_equal(a, b, eps=1e-7):
+        return abs(a - b) <= eps * max(1.0, max(abs(a), abs(b)))
+
+    def less_or_equal(a, b):
+        return are_equal(a, b) or a < b + 2.220446049250313e-16
+
+    rot, rect, drift = [], [], 0.0
+    while less_or_equal(2 * drift, sector):
+        for r in sorted({drift, -drift}):
+            for box in ((0.0, 0.0, 0.0, 0.0), (-max_y, max_y, -max_x, max_x)):
+                rot.append(r)
+                rect.append(box)
+        drift += step
+    return np.asarray(rot, dtype=np.float64), np.asarray(rect, dtype=np.float64).reshape(-1, 4)
+
+
+class Pyramid:
+    """slamhip_pyramid: max-impact levels 1 .. K over the bound dense map `fine_map_id` of a Context, each an ordinary
+    bound map (ids first_level_map_id ...), and the per-candidate bound scorer over them."""
+
+    def __init__(self, ctx, fine_map_id, oie=OIE_DISCREPANCY, first_level_map_id=None):
+        self.ctx, self.L = ctx, ctx.L
+        self.fine_map_id = int(fine_map_id)
+        first = self.fine_map_id + 1 if first_level_map_id is None else int(first_level_map_id)
+        h = C.c_void_p()
+        _check(self.L.slamhip_pyramid_create(ctx.h, self.fine_map_id, int(oie), first, C.byref(h)))
+        self.h = h
+        _live["dep"].add(self)
+        ctx._deps.add(self)
+
+    @classmethod
+    def create(cls, ctx, fine_map_id, oie=OIE_DISCREPANCY, first_level_map_id=None):
+        return cls(ctx, fine_map_id, oie, first_level_map_id)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.slamhip_pyramid_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """Levels 1 .. K: a list of dicts map_id, width, height, origin (x, y), scale."""
+        cap = PYRAMID_MAX_LEVELS
+        n = C.c_int(0)
+        a = [np.zeros(cap, np.int32) for _ in range(5)]
+        scale = np.zeros(cap)
+        _check(self.L.slamhip_pyramid_info(self.h, C.byref(n), cap, *[v.ctypes.data_as(_ip) for v in a], _d(scale)))
+        return [dict(map_id=int(a[0][k]), width=int(a[1][k]), height=int(a[2][k]), origin=(int(a[3][k]), int(a[4][k])),
+                     scale=float(scale[k])) for k in range(n.value)]
+
+    def level_map_ids(self):
+        """map ids by level, the fine map's first: what level_out of score_matches indexes"""
+        return [self.fine_map_id] + [lv["map_id"] for lv in self.info()]
+
+    def rebuild(self):
+        _check(self.L.slamhip_pyramid_rebuild(self.h))
+
+    def refresh(self, x0, y0, w, h):
+        _check(self.L.slamhip_pyramid_refresh(self.h, int(x0), int(y0), int(w), int(h)))
+
+    def score_matches(self, cfg, base_pose, rotation, rect):
+        """Match::prob_upper_bound of every candidate (rotation[i], rect[i] = bot, top, left, right) in one launch:
+        (scores[n], levels[n])."""
+        rotation = _f64(rotation).ravel()
+        rect = _f64(rect).reshape(-1, 4)
+        if rect.shape[0] != rotation.size:
+            raise ValueError("one rectangle per rotation")
+        base = _f64(base_pose).ravel()
+        scores, levels = np.zeros(rotation.size), np.zeros(rotation.size, np.int32)
+        _check(self.L.slamhip_pyramid_score_matches(self.ctx.h, self.h, C.byref(cfg), _d(base), rotation.size, _d(rotation),
+                                                    _d(rect), _d(scores), levels.ctypes.data_as(_ip)))
+        return scores, levels
+
+    def score_matches_device(self, cfg, base_pose, n, d_rotation_ptr, d_rect_ptr, d_scores_ptr, d_levels_ptr):
+        base = _f64(base_pose).ravel()
+        _check(self.L.slamhip_pyramid_score_matches_device(self.ctx.h, self.h, C.byref(cfg), _d(base), int(n),
+                                                           C.c_void_p(d_rotation_ptr), C.c_void_p(d_rect_ptr),
+                                                           C.c_void_p(d_scores_ptr), C.c_void_p(d_levels_ptr)))
 
 
 class RawScan(C.Structure):

@@ -1,0 +1,577 @@
+// map_pyramid.hip -- max-impact levels over a resident map and the bound scorer that reads them
+// (include/slamhip.h "map pyramid"; the level definition: map_pyramid_device.h).
+//
+// What it replaces (paths relative to the reference root):
+//   M3RSMRescalableGridMap::update_coarser_maps   src/core/scan_matchers/m3rsm_engine.h:101-127 -- per updated fine
+//                                                 cell a walk up the levels, inside GridMap::update
+//   Match::Match (prob_upper_bound)               src/core/scan_matchers/m3rsm_engine.h:156-180 -- rescale() to the
+//                                                 level of the translation rectangle, then one scorer call
+//
+// Build: level k is made from level k - 1 (level 1 from the fine map), one thread per coarse cell reading the 2 x 2
+// cells under it and writing the winner's payload and the fine coordinate it came from (pyr::reduce_cell); the kernels
+// of the levels follow each other on the context's stream.  A refresh runs the same kernel over the coarse cells whose
+// blocks meet the changed fine window.  Bandwidth bound: the fine map is read once, level k written once and read once.
+//
+// Score: one workgroup of 256 threads per candidate.  It picks the candidate's level from its rectangle, takes that
+// level's MapView from a table in HBM and runs k_score_window's body (score_kernels.hip) for one pose: thread t adds the
+// beams t, t + 256, ... in ascending order, the wave butterfly, (g0 + g1) + (g2 + g3) -- the canonical sum, hence the
+// bits slamhip_score_poses gives for that pose on that level's map with cfg.area = the rectangle.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "kernel_pick.h"
+#include "map_pyramid_device.h"
+#include "score_device.h"
+
+struct slamhip_pyramid {
+  slamhip_ctx *ctx = nullptr;  // null once the context has gone
+  int fine_id = -1, first_id = -1, oie = 0;
+  int cell_model = 0;
+  // the fine map the levels were planned for: a re-bound (grown) fine map needs slamhip_pyramid_rebuild
+  int fine_w = 0, fine_h = 0, fine_ox = 0, fine_oy = 0;
+  const double *fine_payload = nullptr;
+  slamhip::pyr::Plan plan{};
+  std::vector<int *> d_coord;               // per level: the fine coordinate of every cell's winner (x, y)
+  std::vector<const double *> lv_payload;   // per level: the payload the table below points at
+  slamhip::MapView *d_views = nullptr;      // plan.n + 1 views, the fine map first
+  // slamhip_pyramid_score_matches' staging in HBM: rotation | rect | sin, cos per candidate; scores; levels; terms
+  double *d_in = nullptr, *d_scores = nullptr, *d_terms = nullptr;
+  int *d_levels = nullptr;
+  int in_cap = 0;
+  size_t terms_cap = 0;
+};
+
+namespace slamhip {
+namespace {
+
+constexpr int kPyrThreads = 256;
+constexpr int kMaxGridY = 65535;
+
+int pyr_invalid(const char *msg) {
+  set_error(msg);
+  return SLAMHIP_ERR_INVALID;
+}
+int pyr_state(const char *msg) {
+  set_error(msg);
+  return SLAMHIP_ERR_STATE;
+}
+
+DeviceMap *bound_map(slamhip_ctx *ctx, int map_id) {
+  if (!ctx || map_id < 0 || map_id >= (int)ctx->maps.size() || !ctx->maps[map_id].bound) return nullptr;
+  return &ctx->maps[map_id];
+}
+
+// ---- build ---------------------------------------------------------------------------------------
+// cells [cx0, cx0 + cw) x [cy0, cy0 + ch) of dst (inside its window: the launcher clips)
+template <int CD>
+__global__ __launch_bounds__(kPyrThreads) void k_pyr_reduce(pyr::Level src, pyr::Level dst, int bias_x, int bias_y, int model,
+                                                            int oie, double u0, double u1, double u2, double u3, int cx0,
+                                                            int cy0, int cw, int ch) {
+  const int x = (int)(blockIdx.x * kPyrThreads + threadIdx.x);
+  if (x >= cw) return;
+  const double unknown[4] = {u0, u1, u2, u3};
+  for (int y = (int)blockIdx.y; y < ch; y += (int)gridDim.y)
+    pyr::reduce_cell<CD>(src, dst, bias_x, bias_y, model, oie, unknown, cx0 + x, cy0 + y);
+}
+
+pyr::Level level_of(const DeviceMap &m, int *coord) {
+  return pyr::Level{m.d_payload, coord, m.width, m.height, m.pitch, m.origin_x, m.origin_y};
+}
+
+// the levels' kernels over the fine window [x0, x0 + w) x [y0, y0 + h), queued on the context's stream
+int queue_levels(slamhip_pyramid *p, int x0, int y0, int w, int h) {
+  slamhip_ctx *ctx = p->ctx;
+  const pyr::Plan &pl = p->plan;
+  ProfilePairGuard prof;  // (while profiling is on: the levels' kernels, first to last, in kernel_ms_total)
+  int rc = prof.open(ctx, ctx->stream, 0);
+  if (rc) return rc;
+  for (int lv = 1; lv <= pl.n; ++lv) {
+    const DeviceMap &src = ctx->maps[lv == 1 ? p->fine_id : p->first_id + lv - 2];
+    DeviceMap &dst = ctx->maps[p->first_id + lv - 1];
+    int cx0, cy0, cx1, cy1;
+    pyr::level_window(pl, p->fine_ox, p->fine_oy, lv, x0, y0, w, h, &cx0, &cy0, &cx1, &cy1);
+    cx0 = std::max(cx0, 0);
+    cy0 = std::max(cy0, 0);
+    cx1 = std::min(cx1, dst.width - 1);
+    cy1 = std::min(cy1, dst.height - 1);
+    if (cx1 < cx0 || cy1 < cy0) return pyr_invalid("internal: a level window outside its level");
+    const int cw = cx1 - cx0 + 1, ch = cy1 - cy0 + 1;
+    const bool top = lv == pl.n;
+    const int bias_x = top ? 0 : src.origin_x - 2 * dst.origin_x, bias_y = top ? 0 : src.origin_y - 2 * dst.origin_y;
+    const pyr::Level s = level_of(src, lv == 1 ? nullptr : p->d_coord[lv - 2]), d = level_of(dst, p->d_coord[lv - 1]);
+    const dim3 grid((cw + kPyrThreads - 1) / kPyrThreads, std::min(ch, kMaxGridY));
+    const auto kernel = cell_doubles(p->cell_model) == 1 ? k_pyr_reduce<1> : k_pyr_reduce<4>;
+    SLAMHIP_CHECK(launch_kernel(kernel, grid, dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, s, d, bias_x, bias_y,
+                                p->cell_model, p->oie, dst.unknown[0], dst.unknown[1], dst.unknown[2], dst.unknown[3], cx0, cy0,
+                                cw, ch));
+    if (dst.prob_ok)  // a level somebody has scored with the 1-cell OOPE: its probability plane follows its cells
+      SLAMHIP_CHECK(launch_prob_build(dst.cell_model, dst.d_payload, dst.d_prob, dst.width, dst.height, dst.pitch, cx0, cy0, cw,
+                                      ch, ctx->stream));
+  }
+  rc = prof.close();
+  if (rc) return rc;
+  if (ctx->profile) ctx->prof_launches += 1;
+  return SLAMHIP_OK;
+}
+
+void free_levels(slamhip_pyramid *p, bool release_maps) {
+  slamhip_ctx *ctx = p->ctx;
+  if (ctx) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (release_maps)
+      for (int lv = 1; lv <= (int)p->lv_payload.size() - 1; ++lv) {
+        // (only what is still the map this pyramid bound: an id the caller has re-bound since is the caller's)
+        DeviceMap *m = bound_map(ctx, p->first_id + lv - 1);
+        if (m && m->d_payload == p->lv_payload[lv]) (void)slamhip_map_release(ctx, p->first_id + lv - 1);
+      }
+  }
+  for (int *c : p->d_coord)
+    if (c) (void)hipFree(c);
+  p->d_coord.clear();
+  p->lv_payload.clear();
+  if (p->d_views) (void)hipFree(p->d_views);
+  p->d_views = nullptr;
+  p->plan.n = 0;
+}
+
+MapView view_of(const DeviceMap &m) {
+  MapView v;
+  std::memset(&v, 0, sizeof(v));
+  v.payload = m.d_payload;
+  v.width = m.width;
+  v.height = m.height;
+  v.pitch = m.pitch;
+  v.origin_x = m.origin_x;
+  v.origin_y = m.origin_y;
+  v.scale = m.scale;
+  v.inv_scale = 1.0 / m.scale;
+  for (int k = 0; k < 4; ++k) v.unknown[k] = m.unknown[k];
+  return v;
+}
+
+// plans the levels over the fine map as it is bound now, binds them and queues the whole build
+int make_levels(slamhip_pyramid *p) {
+  slamhip_ctx *ctx = p->ctx;
+  DeviceMap *fine = bound_map(ctx, p->fine_id);
+  if (!fine) return pyr_invalid("the fine map is not bound");
+  if (fine->bytes == 0 || fine->cell_model == SLAMHIP_CELL_GMAPPING)
+    return pyr_invalid("a pyramid stands over a dense OCC, TBM or CREDIBILIST map");
+  if (!pyr::check_oie(fine->cell_model, p->oie))
+    return pyr_invalid("unknown OIE, or OccupancyOIE over belief cells (they are scored under the discrepancy OIE only)");
+  pyr::Plan pl;
+  if (!pyr::plan_levels(fine->width, fine->height, fine->origin_x, fine->origin_y, fine->scale, &pl))
+    return pyr_invalid("the fine map reaches beyond 2^30 cells from its origin");
+  if (p->first_id < 0 || p->first_id + pl.n - 1 > 4095) return pyr_invalid("level map ids out of range [0, 4095]");
+  if (p->fine_id >= p->first_id && p->fine_id < p->first_id + pl.n) return pyr_invalid("the level ids include the fine map's");
+  for (int lv = 1; lv <= pl.n; ++lv)
+    if (bound_map(ctx, p->first_id + lv - 1)) return pyr_invalid("a level map id is already bound");
+  const int model = fine->cell_model;
+  double unknown[4];
+  for (int k = 0; k < 4; ++k) unknown[k] = fine->unknown[k];
+  p->cell_model = model;
+  p->plan = pl;
+  p->d_coord.assign(pl.n, nullptr);
+  p->lv_payload.assign(pl.n + 1, nullptr);
+  for (int lv = 1; lv <= pl.n; ++lv) {
+    const int rc = slamhip_map_bind(ctx, p->first_id + lv - 1, model, pl.width[lv - 1], pl.height[lv - 1], pl.origin_x[lv - 1],
+                                    pl.origin_y[lv - 1], pl.scale[lv - 1], unknown);
+    if (rc) return rc;
+    const DeviceMap &m = ctx->maps[p->first_id + lv - 1];
+    p->lv_payload[lv] = m.d_payload;
+    SLAMHIP_CHECK(hipMalloc(&p->d_coord[lv - 1], sizeof(int) * 2 * (size_t)m.pitch * m.height));
+  }
+  fine = bound_map(ctx, p->fine_id);  // (binding may have moved the context's map table)
+  p->fine_w = fine->width;
+  p->fine_h = fine->height;
+  p->fine_ox = fine->origin_x;
+  p->fine_oy = fine->origin_y;
+  p->fine_payload = p->lv_payload[0] = fine->d_payload;
+  std::vector<MapView> views(pl.n + 1);
+  views[0] = view_of(*fine);
+  for (int lv = 1; lv <= pl.n; ++lv) views[lv] = view_of(ctx->maps[p->first_id + lv - 1]);
+  SLAMHIP_CHECK(hipMalloc(&p->d_views, sizeof(MapView) * views.size()));
+  SLAMHIP_CHECK(hipMemcpy(p->d_views, views.data(), sizeof(MapView) * views.size(), hipMemcpyHostToDevice));
+  return queue_levels(p, 0, 0, p->fine_w, p->fine_h);
+}
+
+// the maps are still the ones the levels were made over and of
+int check_fresh(const slamhip_pyramid *p) {
+  if (!p || !p->ctx) return pyr_invalid("null pyramid, or one whose context has been destroyed");
+  if (p->plan.n <= 0) return pyr_state("the pyramid has no levels (a failed rebuild): slamhip_pyramid_rebuild");
+  const DeviceMap *fine = bound_map(p->ctx, p->fine_id);
+  if (!fine || fine->d_payload != p->fine_payload || fine->width != p->fine_w || fine->height != p->fine_h ||
+      fine->origin_x != p->fine_ox || fine->origin_y != p->fine_oy)
+    return pyr_state("the fine map has been re-bound since the levels were made: slamhip_pyramid_rebuild");
+  for (int lv = 1; lv <= p->plan.n; ++lv) {
+    const DeviceMap *m = bound_map(p->ctx, p->first_id + lv - 1);
+    if (!m || m->d_payload != p->lv_payload[lv]) return pyr_state("a level map has been released or re-bound by the caller");
+  }
+  return SLAMHIP_OK;
+}
+
+// ---- score ---------------------------------------------------------------------------------------
+struct MatchArgs {
+  const MapView *levels;  // n_levels views, the fine map first
+  int n_levels;
+  ScanView scan;
+  const double *rotation;  // n
+  const double *rect;      // n x (bot, top, left, right)
+  const double *pose_sc;   // optional n x (sin, cos) of rotation + heading from the host; null = device sincos
+  double base[3];
+  double *scores;
+  int *level_out;
+  double *terms;  // beam-order sum only: n x scan.n
+  int n, oie, oope;
+};
+
+template <int MODEL>
+__global__ __launch_bounds__(kPyrThreads) void k_pyr_score(MatchArgs a) {
+  __shared__ double s_trig[2];
+  __shared__ double s_part[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int i = blockIdx.x;
+  const int n = a.scan.n;
+  const double bot = a.rect[4 * i], top = a.rect[4 * i + 1], left = a.rect[4 * i + 2], right = a.rect[4 * i + 3];
+  const double vside = top - bot, hside = right - left;
+  // (a rectangle that is no rectangle -- NaN, infinite or reversed -- has no level and no window: NaN, level -1)
+  if (!(vside >= 0.0 && hside >= 0.0 && vside < __builtin_inf() && hside < __builtin_inf())) {
+    if (t == 0) {
+      a.scores[i] = __builtin_nan("");
+      a.level_out[i] = -1;
+    }
+    return;
+  }
+  // RescalableCachingGridMap::rescale(std::max(vside, hside)): the first level whose scale holds the target
+  const double target = vside < hside ? hside : vside;
+  int lv = 0;
+  while (lv < a.n_levels - 1 && !(target <= a.levels[lv].scale)) ++lv;
+  const MapView map = a.levels[lv];
+  // LightWeightRectangle::center() added to the pose
+  const double x = a.base[0] + (left + hside / 2), y = a.base[1] + (bot + vside / 2);
+  if (t == 0) {
+    double sn, cs;
+    if (a.pose_sc) {
+      sn = a.pose_sc[2 * i];
+      cs = a.pose_sc[2 * i + 1];
+    } else {
+      sincos(a.rotation[i] + a.base[2], &sn, &cs);
+    }
+    s_trig[0] = sn;
+    s_trig[1] = cs;
+  }
+  __syncthreads();
+  const double sn = s_trig[0], cs = s_trig[1];
+  const double half_v = (top - bot) / 2, half_h = (right - left) / 2;
+  double acc = 0.0;
+  for (int b = t; b < n; b += kPyrThreads) {
+    const double ca = a.scan.cos_a[b], sa = a.scan.sin_a[b], r = a.scan.range[b];
+    const double c = cs * ca - sn * sa;
+    const double s = sn * ca + cs * sa;
+    const double ox = x + r * c, oy = y + r * s;
+    const double pr = window_probability<MODEL>(map, a.oie, a.oope, half_v, half_h, ox, oy);
+    const double term = pr * a.scan.weight[b] * a.scan.factor[b];
+    if (a.terms) a.terms[(size_t)i * n + b] = term;
+    acc = acc + term;
+  }
+  acc = wave_xor_sum(acc);
+  if (lane == 0) s_part[wave] = acc;
+  __syncthreads();
+  if (t == 0) {
+    const double total = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+    a.scores[i] = (a.scan.tot_w == 0.0) ? __builtin_nan("") : total / a.scan.tot_w;
+    a.level_out[i] = lv;
+  }
+}
+
+// the reference's beam-order sum over the terms (k_sum_sequential's loop), one lane per candidate that has a level
+__global__ __launch_bounds__(64) void k_pyr_sum_sequential(const double *terms, const int *level, int n_cand, int n, double tot_w,
+                                                           double *scores) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= n_cand || level[p] < 0) return;
+  const double *row = terms + (size_t)p * n;
+  double acc = 0.0;
+  for (int b = 0; b < n; ++b) acc = acc + row[b];
+  scores[p] = (tot_w == 0.0) ? __builtin_nan("") : acc / tot_w;
+}
+
+int check_score_cfg(const slamhip_pyramid *p, const slamhip_spe_cfg *cfg) {
+  if (!cfg) return pyr_invalid("null spe cfg");
+  if (cfg->oope != SLAMHIP_OOPE_MAX && cfg->oope != SLAMHIP_OOPE_MEAN && cfg->oope != SLAMHIP_OOPE_OVERLAP)
+    return pyr_invalid("bounds are scored with a window OOPE (max / mean / overlap)");
+  if (cfg->oie != p->oie) return pyr_invalid("the scorer's OIE is not the one the levels were built with");
+  if (cfg->sum_order != SLAMHIP_SUM_TREE256 && cfg->sum_order != SLAMHIP_SUM_SEQUENTIAL) return pyr_invalid("unknown sum order");
+  return SLAMHIP_OK;
+}
+
+// queues the scoring of n candidates whose arrays are in HBM (pose_sc may be null)
+int queue_score(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base[3], int n, const double *d_rotation,
+                const double *d_rect, const double *d_pose_sc, double *d_scores, int *d_levels) {
+  slamhip_ctx *ctx = p->ctx;
+  if (ctx->scan_n <= 0) return pyr_state("no scan uploaded");
+  MatchArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.levels = p->d_views;
+  a.n_levels = p->plan.n + 1;
+  const size_t c = ctx->scan_stride;
+  a.scan.range = ctx->scan_ptr;
+  a.scan.cos_a = ctx->scan_ptr + c;
+  a.scan.sin_a = ctx->scan_ptr + 2 * c;
+  a.scan.weight = ctx->scan_ptr + 3 * c;
+  a.scan.factor = ctx->scan_ptr + 4 * c;
+  a.scan.n = ctx->scan_n;
+  a.scan.tot_w = ctx->scan_tot_w;
+  a.rotation = d_rotation;
+  a.rect = d_rect;
+  a.pose_sc = d_pose_sc;
+  for (int k = 0; k < 3; ++k) a.base[k] = base[k];
+  a.scores = d_scores;
+  a.level_out = d_levels;
+  a.n = n;
+  a.oie = cfg->oie;
+  a.oope = cfg->oope;
+  const bool seq = cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL;
+  if (seq) {
+    const size_t need = (size_t)n * ctx->scan_n;
+    if (need > p->terms_cap) {
+      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+      if (p->d_terms) (void)hipFree(p->d_terms);
+      p->d_terms = nullptr;
+      p->terms_cap = 0;
+      SLAMHIP_CHECK(hipMalloc(&p->d_terms, sizeof(double) * need));
+      p->terms_cap = need;
+    }
+    a.terms = p->d_terms;
+  }
+  ProfilePairGuard prof;
+  int rc = prof.open(ctx, ctx->stream, 0);
+  if (rc) return rc;
+  typedef void (*Kernel)(MatchArgs);
+  const Kernel kernel = pick_cell_model(p->cell_model, [](auto m) -> Kernel { return k_pyr_score<decltype(m)::value>; });
+  SLAMHIP_CHECK(launch_kernel(kernel, dim3(n), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
+  if (seq)
+    SLAMHIP_CHECK(launch_kernel(k_pyr_sum_sequential, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, nullptr, nullptr,
+                                (const double *)a.terms, (const int *)d_levels, n, a.scan.n, a.scan.tot_w, d_scores));
+  rc = prof.close();
+  if (rc) return rc;
+  if (ctx->profile) {
+    ctx->prof_launches += 1;
+    ctx->prof_units += (long long)n * a.scan.n;
+  }
+  return SLAMHIP_OK;
+}
+
+}  // namespace
+
+void pyramids_release(slamhip_ctx *ctx) {
+  for (void *v : ctx->pyramids) {
+    slamhip_pyramid *p = static_cast<slamhip_pyramid *>(v);
+    free_levels(p, false);  // (the context frees its maps itself)
+    if (p->d_in) (void)hipFree(p->d_in);
+    if (p->d_scores) (void)hipFree(p->d_scores);
+    if (p->d_levels) (void)hipFree(p->d_levels);
+    if (p->d_terms) (void)hipFree(p->d_terms);
+    p->d_in = p->d_scores = p->d_terms = nullptr;
+    p->d_levels = nullptr;
+    p->ctx = nullptr;
+  }
+  ctx->pyramids.clear();
+}
+
+}  // namespace slamhip
+
+using namespace slamhip;
+
+int slamhip_pyramid_create(slamhip_ctx *ctx, int fine_map_id, int oie, int first_level_map_id, slamhip_pyramid **out) {
+  if (!ctx || !out) return pyr_invalid("null context or output");
+  *out = nullptr;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  slamhip_pyramid *p = new slamhip_pyramid;
+  p->ctx = ctx;
+  p->fine_id = fine_map_id;
+  p->first_id = first_level_map_id;
+  p->oie = oie;
+  const int rc = make_levels(p);
+  if (rc) {
+    free_levels(p, true);
+    delete p;
+    return rc;
+  }
+  ctx->pyramids.push_back(p);
+  *out = p;
+  return SLAMHIP_OK;
+}
+
+int slamhip_pyramid_destroy(slamhip_pyramid *p) {
+  if (!p) return SLAMHIP_OK;
+  if (p->ctx) {
+    slamhip_ctx *ctx = p->ctx;
+    free_levels(p, true);
+    if (p->d_in) (void)hipFree(p->d_in);
+    if (p->d_scores) (void)hipFree(p->d_scores);
+    if (p->d_levels) (void)hipFree(p->d_levels);
+    if (p->d_terms) (void)hipFree(p->d_terms);
+    ctx->pyramids.erase(std::remove(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)p), ctx->pyramids.end());
+  }
+  delete p;
+  return SLAMHIP_OK;
+}
+
+int slamhip_pyramid_info(slamhip_pyramid *p, int *n_levels, int cap, int *map_id, int *width, int *height, int *origin_x,
+                         int *origin_y, double *scale) {
+  if (!p || !p->ctx) return pyr_invalid("null pyramid, or one whose context has been destroyed");
+  if (cap < 0) return pyr_invalid("negative capacity");
+  if (n_levels) *n_levels = p->plan.n;
+  for (int k = 0; k < std::min(cap, p->plan.n); ++k) {
+    if (map_id) map_id[k] = p->first_id + k;
+    if (width) width[k] = p->plan.width[k];
+    if (height) height[k] = p->plan.height[k];
+    if (origin_x) origin_x[k] = p->plan.origin_x[k];
+    if (origin_y) origin_y[k] = p->plan.origin_y[k];
+    if (scale) scale[k] = p->plan.scale[k];
+  }
+  return SLAMHIP_OK;
+}
+
+int slamhip_pyramid_rebuild(slamhip_pyramid *p) {
+  if (!p || !p->ctx) return pyr_invalid("null pyramid, or one whose context has been destroyed");
+  SLAMHIP_CHECK(hipSetDevice(p->ctx->device));
+  if (check_fresh(p) == SLAMHIP_OK) return queue_levels(p, 0, 0, p->fine_w, p->fine_h);
+  // the fine map has moved or grown: the levels are planned and bound anew under the same ids
+  free_levels(p, true);
+  const int rc = make_levels(p);
+  if (rc) free_levels(p, true);
+  else set_error("");  // (check_fresh's finding has been dealt with)
+  return rc;
+}
+
+int slamhip_pyramid_refresh(slamhip_pyramid *p, int x0, int y0, int w, int h) {
+  int rc = check_fresh(p);
+  if (rc) return rc;
+  if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || (long long)x0 + w > p->fine_w || (long long)y0 + h > p->fine_h)
+    return pyr_invalid("window outside the fine map");
+  SLAMHIP_CHECK(hipSetDevice(p->ctx->device));
+  return queue_levels(p, x0, y0, w, h);
+}
+
+int slamhip_pyramid_score_matches_device(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cfg,
+                                         const double base_pose[3], int n, const double *d_rotation, const double *d_rect,
+                                         double *d_score_out, int *d_level_out) {
+  int rc = check_fresh(p);
+  if (rc) return rc;
+  if (ctx != p->ctx) return pyr_invalid("the pyramid belongs to another context");
+  rc = check_score_cfg(p, cfg);
+  if (rc) return rc;
+  if (n < 0 || !base_pose) return pyr_invalid("bad candidate batch");
+  if (n == 0) return SLAMHIP_OK;
+  if (!d_rotation || !d_rect || !d_score_out || !d_level_out) return pyr_invalid("null device buffers");
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE)
+    return pyr_invalid("device-resident candidates use device sincos (pose_trig = DEVICE): the host-trig mode takes host arrays");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(base_pose[k])) return pyr_invalid("the base pose is not finite");
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  return queue_score(p, cfg, base_pose, n, d_rotation, d_rect, nullptr, d_score_out, d_level_out);
+}
+
+int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base_pose[3],
+                                  int n, const double *rotation, const double *rect, double *score_out, int *level_out) {
+  int rc = check_fresh(p);
+  if (rc) return rc;
+  if (ctx != p->ctx) return pyr_invalid("the pyramid belongs to another context");
+  rc = check_score_cfg(p, cfg);
+  if (rc) return rc;
+  if (n < 0 || !base_pose) return pyr_invalid("bad candidate batch");
+  if (n == 0) return SLAMHIP_OK;
+  if (!rotation || !rect || !score_out || !level_out) return pyr_invalid("null candidate arrays");
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
+    return pyr_invalid("pose_trig: DEVICE or HOST");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(base_pose[k])) return pyr_invalid("the base pose is not finite");
+  for (int i = 0; i < n; ++i) {
+    const double *r = rect + 4 * (size_t)i;
+    if (!std::isfinite(rotation[i]) || !std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]) ||
+        !std::isfinite(r[3]) || !(r[0] <= r[1] && r[2] <= r[3]))
+      return pyr_invalid("a candidate's rotation or rectangle is not finite, or not bot <= top and left <= right");
+    // (the rule of cfg->area -- at most 10^4 cells per beam -- holds by construction: the rectangle is at most one
+    // cell of its level wide, so a beam's window is at most 3 x 3 cells)
+  }
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  if (n > p->in_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (p->d_in) (void)hipFree(p->d_in);
+    if (p->d_scores) (void)hipFree(p->d_scores);
+    if (p->d_levels) (void)hipFree(p->d_levels);
+    p->d_in = p->d_scores = nullptr;
+    p->d_levels = nullptr;
+    p->in_cap = 0;
+    int cap = 256;
+    while (cap < n) cap *= 2;
+    SLAMHIP_CHECK(hipMalloc(&p->d_in, sizeof(double) * 7 * cap));
+    SLAMHIP_CHECK(hipMalloc(&p->d_scores, sizeof(double) * cap));
+    SLAMHIP_CHECK(hipMalloc(&p->d_levels, sizeof(int) * cap));
+    p->in_cap = cap;
+  }
+  const bool host_trig = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST;
+  std::vector<double> stage((size_t)n * 7);
+  std::memcpy(stage.data(), rotation, sizeof(double) * n);
+  std::memcpy(stage.data() + n, rect, sizeof(double) * 4 * n);
+  if (host_trig)  // (one sincos call per pose, as slamhip_score_poses' host mode makes it)
+    for (int i = 0; i < n; ++i) ::sincos(rotation[i] + base_pose[2], &stage[5 * (size_t)n + 2 * i], &stage[5 * (size_t)n + 2 * i + 1]);
+  SLAMHIP_CHECK(hipMemcpyAsync(p->d_in, stage.data(), sizeof(double) * (host_trig ? 7 : 5) * n, hipMemcpyHostToDevice, ctx->stream));
+  rc = queue_score(p, cfg, base_pose, n, p->d_in, p->d_in + n, host_trig ? p->d_in + 5 * (size_t)n : nullptr, p->d_scores,
+                   p->d_levels);
+  if (rc) return rc;
+  SLAMHIP_CHECK(hipMemcpyAsync(score_out, p->d_scores, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(level_out, p->d_levels, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return SLAMHIP_OK;
+}
+
+int slamhip_pyramid_build_host(int cell_model, int oie, int width, int height, int origin_x, int origin_y, double scale,
+                               const double *unknown_payload, const double *payload, int level_cap, int *n_levels,
+                               int *level_width, int *level_height, int *level_origin_x, int *level_origin_y,
+                               double *level_scale, size_t payload_cap, double *payload_out, size_t *payload_need) {
+  if (cell_model != SLAMHIP_CELL_OCC && !cell_is_belief(cell_model))
+    return pyr_invalid("a pyramid stands over OCC, TBM or CREDIBILIST cells");
+  if (!pyr::check_oie(cell_model, oie))
+    return pyr_invalid("unknown OIE, or OccupancyOIE over belief cells (they are scored under the discrepancy OIE only)");
+  if (!(scale > 0) || !unknown_payload || !payload || level_cap < 0 || !n_levels) return pyr_invalid("bad arguments");
+  pyr::Plan pl;
+  if (!pyr::plan_levels(width, height, origin_x, origin_y, scale, &pl)) return pyr_invalid("bad map geometry");
+  const int cd = cell_stride_host(cell_model);  // (OCC 1, beliefs 4: the stride in HBM too)
+  *n_levels = pl.n;
+  size_t need = 0;
+  for (int k = 0; k < pl.n; ++k) need += (size_t)pl.width[k] * pl.height[k] * cd;
+  if (payload_need) *payload_need = need;
+  for (int k = 0; k < std::min(level_cap, pl.n); ++k) {
+    if (level_width) level_width[k] = pl.width[k];
+    if (level_height) level_height[k] = pl.height[k];
+    if (level_origin_x) level_origin_x[k] = pl.origin_x[k];
+    if (level_origin_y) level_origin_y[k] = pl.origin_y[k];
+    if (level_scale) level_scale[k] = pl.scale[k];
+  }
+  if (!payload_out) return SLAMHIP_OK;  // geometry only
+  if (payload_cap < need) return pyr_invalid("payload_out is too small (payload_need says how many doubles)");
+  double unknown[4] = {0, 0, 0, 0};
+  for (int k = 0; k < cd; ++k) unknown[k] = unknown_payload[k];
+  std::vector<std::vector<int>> coord(pl.n);
+  pyr::Level src{const_cast<double *>(payload), nullptr, width, height, width, origin_x, origin_y};
+  double *at = payload_out;
+  for (int lv = 1; lv <= pl.n; ++lv) {
+    const int w = pl.width[lv - 1], h = pl.height[lv - 1];
+    coord[lv - 1].assign((size_t)2 * w * h, 0);
+    pyr::Level dst{at, coord[lv - 1].data(), w, h, w, pl.origin_x[lv - 1], pl.origin_y[lv - 1]};
+    const bool top = lv == pl.n;
+    const int bias_x = top ? 0 : src.origin_x - 2 * dst.origin_x, bias_y = top ? 0 : src.origin_y - 2 * dst.origin_y;
+    for (int iy = 0; iy < h; ++iy)
+      for (int ix = 0; ix < w; ++ix) {
+        if (cd == 1) pyr::reduce_cell<1>(src, dst, bias_x, bias_y, cell_model, oie, unknown, ix, iy);
+        else pyr::reduce_cell<4>(src, dst, bias_x, bias_y, cell_model, oie, unknown, ix, iy);
+      }
+    src = dst;
+    at += (size_t)w * h * cd;
+  }
+  return SLAMHIP_OK;
+}

@@ -764,6 +764,7 @@ int slamhip_ctx_destroy(slamhip_ctx *ctx) {
   if (!ctx) return SLAMHIP_OK;
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
+  pyramids_release(ctx);
   for (auto &m : ctx->maps) {
     if (m.d_payload) hipFree(m.d_payload);
     if (m.d_aux) hipFree(m.d_aux);

@@ -285,6 +285,7 @@ void mu_release(slamhip_ctx *ctx);                    // map_update.hip: frees t
 void shard_release(slamhip_ctx *ctx);                 // shard.cpp: leaves the RCCL group, frees its staging
 void render_release(slamhip_ctx *ctx);                // map_render.hip: frees the context's render buffer
 void scan_gen_release(slamhip_ctx *ctx);              // scan_generate.hip: frees the context's scan-generation block
+void pyramids_release(slamhip_ctx *ctx);              // map_pyramid.hip: frees what the context's pyramids hold in HBM
 void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 
@@ -379,6 +380,7 @@ struct slamhip_ctx {
   void *d_scan_gen = nullptr;  // slamhip_map_generate_scans' block in HBM (scan_generate.hip): grows on demand, freed with the context
   size_t scan_gen_cap = 0;
   std::vector<double> scan_gen_stage;  // ... and its host side: what goes up and what comes back, one copy each
+  std::vector<void *> pyramids;  // the slamhip_pyramid objects made over this context's maps (map_pyramid.hip)
   bool low_latency = true;
   bool stage_poses = false;  // copy poses to HBM first instead of reading them over PCIe
   // slamhip_ctx_set_option: equivalent execution paths (defaults = what is measured)

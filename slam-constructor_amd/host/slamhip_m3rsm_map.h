@@ -1,0 +1,93 @@
+// slamhip_m3rsm_map.h -- a resident map with its max-impact levels: the device counterpart of
+// M3RSMRescalableGridMap<UnboundedPlainGridMap> (src/core/scan_matchers/m3rsm_engine.h:17-131).
+//
+// The reference keeps the coarse levels up to date inside GridMap::update, cell by cell.  Here the fine map lives in
+// HBM (HipResidentMapView reads it back for the map's consumers), the levels are a slamhip_pyramid over it, and
+// append_scan refreshes the levels behind every scan it writes -- queued on the context's stream, so the caller does
+// not wait for either.  bounds() is Match::prob_upper_bound (:156-180) for a batch of candidates.
+// The best-first engine (M3RSMEngine) is not part of the device path yet: a caller drives the priority queue itself.
+// Compiled only with the reference headers on the include path; contains no reference code.
+#ifndef SLAMHIP_M3RSM_MAP_H
+#define SLAMHIP_M3RSM_MAP_H
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "slamhip_reference_adapter.h"
+
+class HipM3rsmMap {
+public:
+  // map_id: the fine map, already bound (slamhip_map_bind) with cell model OCC, TBM or CREDIBILIST; the levels take
+  // the ids first_level_map_id, first_level_map_id + 1, ...
+  HipM3rsmMap(slamhip_ctx *ctx, int map_id, int oie, int first_level_map_id, const GridMapParams &params,
+              double unknown_prob = 0.5, int tbm_kind = 0)
+      : _ctx{ctx}, _map_id{map_id} {
+    slamhip_or_die(slamhip_pyramid_create(ctx, map_id, oie, first_level_map_id, &_pyr), "pyramid_create");
+    _view = std::make_shared<HipResidentMapView>(ctx, map_id, params, unknown_prob, tbm_kind);
+  }
+  ~HipM3rsmMap() { slamhip_pyramid_destroy(_pyr); }
+  HipM3rsmMap(const HipM3rsmMap &) = delete;
+  HipM3rsmMap &operator=(const HipM3rsmMap &) = delete;
+
+  const GridMap &map() const { return *_view; }
+  slamhip_pyramid *pyramid() { return _pyr; }
+
+  // GridMapScanAdder::append_scan on the fine map (slamhip_map_append_scan_q), then the levels over what it wrote:
+  // the cells within the longest beam (plus the blur) of the pose -- or everything, when the window has grown
+  void append_scan(const slamhip_scan_adder_cfg &adder, const RobotPose &pose, int n, const double *range,
+                   const double *cos_a, const double *sin_a, const int *is_occ, const double *quality = nullptr) {
+    int w0 = 0, h0 = 0, ox0 = 0, oy0 = 0;
+    slamhip_or_die(slamhip_map_info(_ctx, _map_id, nullptr, &w0, &h0, &ox0, &oy0, nullptr, nullptr), "map_info");
+    const double p3[3] = {pose.x, pose.y, pose.theta};
+    long long nu = 0;
+    slamhip_or_die(slamhip_map_append_scan_q(_ctx, _map_id, &adder, p3, n, range, cos_a, sin_a, is_occ, quality, &nu),
+                   "map_append_scan");
+    _view->invalidate();
+    int w = 0, h = 0, ox = 0, oy = 0;
+    double scale = 1.0;
+    slamhip_or_die(slamhip_map_info(_ctx, _map_id, nullptr, &w, &h, &ox, &oy, &scale, nullptr), "map_info");
+    if (w != w0 || h != h0 || ox != ox0 || oy != oy0) {
+      slamhip_or_die(slamhip_pyramid_rebuild(_pyr), "pyramid_rebuild");
+      return;
+    }
+    double reach = 0.0;
+    for (int i = 0; i < n; ++i) reach = std::max(reach, std::isfinite(range[i]) ? range[i] : 0.0);
+    if (std::isfinite(adder.max_range)) reach = std::min(reach, adder.max_range);
+    reach += std::fabs(adder.blur) + 2 * scale;  // (a dynamic blur is a fraction of the beam: inside twice the reach)
+    if (adder.blur < 0) reach *= 2;
+    const int x0 = std::max(0, (int)std::floor((pose.x - reach) / scale) + ox);
+    const int y0 = std::max(0, (int)std::floor((pose.y - reach) / scale) + oy);
+    const int x1 = std::min(w - 1, (int)std::floor((pose.x + reach) / scale) + ox);
+    const int y1 = std::min(h - 1, (int)std::floor((pose.y + reach) / scale) + oy);
+    if (x1 < x0 || y1 < y0) return;
+    slamhip_or_die(slamhip_pyramid_refresh(_pyr, x0, y0, x1 - x0 + 1, y1 - y0 + 1), "pyramid_refresh");
+  }
+
+  // Match::prob_upper_bound of n candidates (rotation, translation rectangle) around `pose` on the context's scan
+  void bounds(const slamhip_spe_cfg &cfg, const RobotPose &pose, const std::vector<double> &rotation,
+              const std::vector<LightWeightRectangle> &drift, std::vector<double> &prob_upper_bound, std::vector<int> &level) {
+    const int n = (int)rotation.size();
+    std::vector<double> rect(4 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+      rect[4 * i] = drift[i].bot();
+      rect[4 * i + 1] = drift[i].top();
+      rect[4 * i + 2] = drift[i].left();
+      rect[4 * i + 3] = drift[i].right();
+    }
+    prob_upper_bound.resize(n);
+    level.resize(n);
+    const double p3[3] = {pose.x, pose.y, pose.theta};
+    slamhip_or_die(slamhip_pyramid_score_matches(_ctx, _pyr, &cfg, p3, n, rotation.data(), rect.data(),
+                                                 prob_upper_bound.data(), level.data()), "pyramid_score_matches");
+  }
+
+private:
+  slamhip_ctx *_ctx;
+  int _map_id;
+  slamhip_pyramid *_pyr = nullptr;
+  std::shared_ptr<HipResidentMapView> _view;
+};
+
+#endif  // SLAMHIP_M3RSM_MAP_H

@@ -1,0 +1,258 @@
+"""CPU suite: the max-impact map pyramid on the host (slamhip_pyramid_build_host -- the level definition the kernels of
+csrc/map_pyramid.hip share, csrc/map_pyramid_device.h) against tests/golden/pyramid.npz, the levels of the compiled
+reference's M3RSMRescalableGridMap (tests/golden/make_golden_pyramid.py), bit for bit; the definition's edge cases against
+a brute-force statement of it; the root layer of M3RSMEngine::add_scan_matching_request."""
+import os
+import shutil
+import subprocess
+import types
+
+import numpy as np
+import pytest
+from pyramid_cases import N_MAPS, N_SETS, assert_levels_are, assert_same_level, bits, brute_levels, golden_map, golden_set
+
+import __graft_entry__ as ge
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    p = ge.load_package()
+    if not os.path.exists(p.LIB_PATH):
+        p.build()
+    return p
+
+
+def occ_map(payload, origin, unknown=0.5, scale=0.1, model=0):
+    p = np.asarray(payload, dtype=np.float64)
+    if p.ndim == 2:
+        p = p[..., None]
+    return types.SimpleNamespace(cell_model=model, payload=p, origin=origin, scale=scale, unknown=np.atleast_1d(np.float64(unknown)))
+
+
+def disc(p):
+    return 1.0 - abs(p[0] - 1.0)
+
+
+@pytest.mark.parametrize("i", range(N_MAPS))
+def test_host_levels_equal_the_references(pkg, i):
+    m = golden_map(i)
+    levels = pkg.pyramid_build_host(m, m.oie)
+    assert len(levels) == len(m.levels)  # the list ensure_map_cache_is_continuous ended with
+    for k, (got, want) in enumerate(zip(levels, m.levels), 1):
+        assert got["scale"] == want["scale"]
+        assert_same_level(got["payload"], got["origin"], want["payload"], want["origin"], m.unknown, "%s level %d" % (m.cls, k))
+    assert np.isinf(levels[-1]["scale"]) and levels[-1]["payload"].shape[:2] == (1, 1) and levels[-1]["origin"] == (0, 0)
+    scale = m.scale
+    for lv in levels[:-1]:
+        scale = scale * 2  # repeated doubling
+        assert lv["scale"] == scale
+    if len(levels) > 1:
+        assert levels[-2]["width"] <= 2 and levels[-2]["height"] <= 2
+
+
+def test_the_golden_holds_the_cases():
+    maps = [golden_map(i) for i in range(N_MAPS)]
+    assert {(m.width, m.height) for m in maps} == {(16, 16), (15, 3), (3, 15), (33, 33), (1, 16), (37, 29)}
+    assert {m.scale for m in maps} == {1.0, 0.1, 0.05}
+    assert {(m.cell_model, m.oie) for m in maps} == {(0, 0), (0, 1), (1, 0), (3, 0)}
+    assert any(m.origin == (11, 20) for m in maps) and any(m.origin == (2, 3) for m in maps)
+    # the off-centre 16 x 16 map has one level more than the centred one: the reference added it while the map was filled
+    n16 = {m.origin: len(m.levels) for m in maps if (m.width, m.height) == (16, 16)}
+    assert n16[(2, 3)] == n16[(8, 8)] + 1
+    for m in maps:  # about a third of the cells never updated
+        unknown = np.all(bits(m.payload) == bits(m.unknown), axis=-1)
+        assert 0.15 < unknown.mean() < 0.55 or m.payload.shape[0] * m.payload.shape[1] < 64
+
+
+def test_floor_rule_on_negative_coordinates(pkg):
+    rs = np.random.RandomState(5)
+    # external x in [-13, 7), y in [-5, 4): blocks of negative coordinates at every level
+    payload = np.where(rs.rand(9, 20) < 0.4, 0.5, rs.randint(0, 64, (9, 20)) / 64.0)
+    m = occ_map(payload, (13, 5))
+    levels = pkg.pyramid_build_host(m, pkg.OIE_DISCREPANCY)
+    assert_levels_are(levels, brute_levels(m.payload, m.origin, m.unknown, disc), m.unknown)
+    # one known cell at external (-1, -1): block (-1, -1) of every halving level, never block 0
+    one = np.full((4, 4), 0.5)
+    one[1, 1] = 0.9  # origin (2, 2): internal (1, 1) is external (-1, -1)
+    for lv in pkg.pyramid_build_host(occ_map(one, (2, 2)), pkg.OIE_DISCREPANCY)[:-1]:
+        o = lv["origin"]
+        assert lv["payload"][-1 + o[1], -1 + o[0], 0] == 0.9
+        assert np.sum(lv["payload"] != 0.5) == 1
+    # an origin outside the window (external (0, 0) is not a cell of the map)
+    far = occ_map(payload, (-6, 31))
+    assert_levels_are(pkg.pyramid_build_host(far, pkg.OIE_DISCREPANCY), brute_levels(far.payload, far.origin, far.unknown, disc), far.unknown)
+
+
+def test_ties_resolve_by_coordinate(pkg):
+    # 0.75 and 1.25 have the same impact 1 - |p - 1| = 0.75, bit for bit, and different payloads
+    p = np.full((4, 4), 0.5)
+    p[3, 0], p[0, 3], p[2, 2] = 1.25, 0.75, 1.25  # internal (x, y) = (0, 3), (3, 0), (2, 2); origin (0, 0)
+    levels = pkg.pyramid_build_host(occ_map(p, (0, 0)), pkg.OIE_DISCREPANCY)
+    assert [lv["payload"].shape[:2] for lv in levels] == [(2, 2), (1, 1), (1, 1)]
+    assert levels[0]["payload"][..., 0].tolist() == [[0.5, 0.75], [1.25, 1.25]]
+    assert levels[1]["payload"][0, 0, 0] == 1.25 and levels[2]["payload"][0, 0, 0] == 1.25  # x = 0 beats x = 2 and x = 3
+    # same x: the smaller y
+    p = np.full((4, 4), 0.5)
+    p[3, 1], p[0, 1] = 1.25, 0.75
+    assert pkg.pyramid_build_host(occ_map(p, (0, 0)), pkg.OIE_DISCREPANCY)[1]["payload"][0, 0, 0] == 0.75
+    # the winner's FINE coordinate decides, not its block's: (3, 0) holds 0.75, (2, 3) holds 1.25 -- both in level-1
+    # blocks of x = 1; over the whole map x = 2 wins although its level-1 block (1, 1) comes after (1, 0)
+    p = np.full((4, 4), 0.5)
+    p[0, 3], p[3, 2] = 0.75, 1.25
+    assert pkg.pyramid_build_host(occ_map(p, (0, 0)), pkg.OIE_DISCREPANCY)[1]["payload"][0, 0, 0] == 1.25
+    # under the occupancy OIE the two are no tie: 1.25 is larger
+    p[0, 0] = 0.75
+    assert pkg.pyramid_build_host(occ_map(p, (0, 0)), pkg.OIE_OCCUPANCY)[2]["payload"][0, 0, 0] == 1.25
+
+
+def test_unknown_blocks_and_the_prototype_payload(pkg):
+    p = np.full((8, 8), -1.0)
+    p[6, 6] = 0.3
+    p[1, 1] = -1.0  # "observed", but bit-equal to the unknown payload: unknown
+    levels = pkg.pyramid_build_host(occ_map(p, (4, 4), unknown=-1.0), pkg.OIE_OCCUPANCY)
+    assert levels[0]["payload"].shape[:2] == (4, 4)
+    assert np.sum(levels[0]["payload"] != -1.0) == 1 and levels[0]["payload"][3, 3, 0] == 0.3
+    assert levels[-1]["payload"][0, 0, 0] == 0.3
+    # a known cell of impact BELOW the unknown payload's still wins its block: unknown cells do not take part
+    p = np.full((2, 2), 0.9)
+    p[0, 1] = 0.1
+    assert pkg.pyramid_build_host(occ_map(p, (1, 1), unknown=0.9), pkg.OIE_OCCUPANCY)[-1]["payload"][0, 0, 0] == 0.1
+    # nothing known at all
+    empty = pkg.pyramid_build_host(occ_map(np.full((5, 3), 0.5), (2, 1)), pkg.OIE_DISCREPANCY)
+    assert all(np.all(lv["payload"] == 0.5) for lv in empty)
+    # -0.0 is not bit-equal to an unknown payload of +0.0: known, and below +0 in the order of impacts
+    z = np.array([[0.0, -0.0]])
+    assert np.signbit(pkg.pyramid_build_host(occ_map(z, (1, 0), unknown=0.0), pkg.OIE_OCCUPANCY)[-1]["payload"][0, 0, 0])
+
+
+@pytest.mark.parametrize("i", [0, 38, 61, 83])
+def test_the_infinite_level_holds_the_argmax_of_the_map(pkg, i):
+    m = golden_map(i)
+    levels = pkg.pyramid_build_host(m, m.oie)
+    if m.cell_model == pkg.CELL_OCC:
+        impact = disc if m.oie == pkg.OIE_DISCREPANCY else (lambda p: p[0])
+    else:
+        impact = lambda p: belief_impact(pkg, m.cell_model, p)
+    want = brute_levels(m.payload, m.origin, m.unknown, impact)
+    assert_levels_are(levels, want, m.unknown)
+    np.testing.assert_array_equal(bits(levels[-1]["payload"][0, 0]), bits(want[-1][(0, 0)]))
+
+
+def belief_impact(pkg, model, p):
+    """the scorer's per-beam probability of a belief cell, restated (csrc/slamhip_internal.h)"""
+    u, e, o, c = (float(v) for v in p)
+    if model == pkg.CELL_CREDIBILIST:
+        t0, t2 = u + e, o + c
+        tot = ((t0 + 0.0) + t2) + 0.0
+        return 1.0 - (1.0 - (0.0 if tot == 0.0 else t2 / tot))
+    d_occ = abs(1.0 - o)
+    t2, t3 = u + o, e + c
+    tot = t2 + t3
+    conflict = 0.0 if tot == 0.0 else t3 / tot
+    unknown = u / 2.0
+    return 1.0 - (unknown / 2 + (1 - unknown) * (conflict + d_occ) / 2.0)
+
+
+def test_invalid_arguments(pkg):
+    ok = occ_map(np.full((3, 3), 0.25), (1, 1))
+    assert len(pkg.pyramid_build_host(ok, pkg.OIE_DISCREPANCY)) == 2
+    for bad_model in (pkg.CELL_GMAPPING, 7, -1):
+        bad = types.SimpleNamespace(**vars(ok))
+        bad.cell_model = bad_model
+        if bad_model == pkg.CELL_GMAPPING:
+            bad.payload, bad.unknown = np.zeros((3, 3, 3)), np.zeros(3)
+        with pytest.raises((pkg.SlamHipError, KeyError)):
+            pkg.pyramid_build_host(bad, pkg.OIE_DISCREPANCY)
+    with pytest.raises(pkg.SlamHipError, match="-1"):
+        pkg.pyramid_build_host(ok, 2)  # unknown OIE
+    tbm = types.SimpleNamespace(cell_model=pkg.CELL_TBM, payload=np.tile([1.0, 0, 0, 0], (3, 3, 1)), origin=(1, 1), scale=0.1,
+                                unknown=np.array([1.0, 0, 0, 0]))
+    assert len(pkg.pyramid_build_host(tbm, pkg.OIE_DISCREPANCY)) == 2
+    with pytest.raises(pkg.SlamHipError, match="-1"):
+        pkg.pyramid_build_host(tbm, pkg.OIE_OCCUPANCY)  # belief cells: the discrepancy OIE only
+    for scale in (0.0, -1.0, float("nan")):
+        bad = types.SimpleNamespace(**vars(ok))
+        bad.scale = scale
+        with pytest.raises(pkg.SlamHipError, match="-1"):
+            pkg.pyramid_build_host(bad, pkg.OIE_DISCREPANCY)
+    # the C entry itself: null pointers, a payload buffer that is too small
+    import ctypes as C
+    L = pkg.load()
+    n, need = C.c_int(0), C.c_size_t(0)
+    unk, pay, out = np.array([0.5, 0, 0, 0]), np.full(9, 0.25), np.zeros(1)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    args = lambda payload, cap, outp: (0, 0, 3, 3, 1, 1, 0.1, dp(unk), payload, 0, C.byref(n), None, None, None, None, None, cap, outp,
+                                       C.byref(need))
+    assert L.slamhip_pyramid_build_host(*args(dp(pay), 0, None)) == 0 and n.value == 2 and need.value == 5
+    assert L.slamhip_pyramid_build_host(*args(None, 0, None)) == -1
+    for bad_model in (pkg.CELL_GMAPPING, 7, -1):  # the C entry's own answer, not the Python wrapper's
+        a = list(args(dp(pay), 0, None))
+        a[0] = bad_model
+        assert L.slamhip_pyramid_build_host(*a) == -1
+    a = list(args(dp(pay), 0, None))
+    a[0], a[1] = pkg.CELL_TBM, pkg.OIE_OCCUPANCY
+    assert L.slamhip_pyramid_build_host(*a) == -1
+    assert L.slamhip_pyramid_build_host(*args(dp(pay), 1, dp(out))) == -1
+
+
+@pytest.mark.parametrize("j", range(0, N_SETS, 7))
+def test_root_candidates_are_the_references(pkg, j):
+    s = golden_set(j)
+    rot, rect = pkg.m3rsm_root_candidates((s.limits[0], s.limits[1], s.limits[2]), s.limits[3])
+    assert rot.size == s.n_roots == 22
+    # the order of add_scan_matching_request, as its scorer calls were recorded: the heading of every call, bit for bit
+    np.testing.assert_array_equal(rot + s.pose[2], s.cand[:s.n_roots, 8])
+    np.testing.assert_array_equal(rect, s.cand[:s.n_roots, 1:5])
+    assert np.all(s.cand[:s.n_roots, 5] == -1) and np.all(s.cand[s.n_roots:s.n_roots + 40, 5] >= 0)
+
+
+def test_root_candidates_of_the_documented_limits(pkg):
+    # config/common/bf_m3rsm.properties: limit 0.087 rad either way, step 0.0017 rad: 2 x 103 matches
+    rot, rect = pkg.m3rsm_root_candidates((1.0, 1.0, 2 * 0.087), 0.0017)
+    assert rot.size == 206 and rot[0] == 0.0 and rot[1] == 0.0 and rot[2] == -0.0017 and rot[4] == 0.0017
+    assert rect[0].tolist() == [0, 0, 0, 0] and rect[1].tolist() == [-1, 1, -1, 1]
+    with pytest.raises(ValueError):
+        pkg.m3rsm_root_candidates((1, 1, 0.1), 0.0)
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
+def test_level_definition_under_sanitizers(tmp_path):
+    """tests/native/pyramid_test.cpp under -fsanitize=address,undefined: the shared header over random windows of every
+    small shape and origin in exactly-sized heap buffers -- levels made one from the other equal a direct scan of every
+    block, refreshing the named cells equals building anew."""
+    hip_inc = "/opt/rocm/include"
+    if not os.path.exists(os.path.join(hip_inc, "hip", "hip_runtime.h")):
+        pytest.skip("HIP headers not found")
+    exe = str(tmp_path / "pyramid_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-I" + hip_inc, "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(ROOT, "slam-constructor_amd", "csrc"), os.path.join(ROOT, "tests", "native", "pyramid_test.cpp"),
+           "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok ")
+
+
+REFERENCE = os.environ.get("REFERENCE", "/root/reference")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
+def test_m3rsm_map_header_compiles_against_the_reference(tmp_path):
+    """host/slamhip_m3rsm_map.h against the unmodified reference headers, its members instantiated"""
+    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "m3rsm_engine.h")):
+        pytest.skip("reference tree not present")
+    tu = tmp_path / "tu.cpp"
+    tu.write_text('#include "slamhip_m3rsm_map.h"\n'
+                  "void use(slamhip_ctx *ctx, const slamhip_scan_adder_cfg &adder, const slamhip_spe_cfg &cfg, const RobotPose &pose) {\n"
+                  "  HipM3rsmMap m(ctx, 0, SLAMHIP_OIE_DISCREPANCY, 1, GridMapParams{100, 100, 0.1});\n"
+                  "  std::vector<double> r(3), c(3), s(3), rot(2), bound;\n  std::vector<int> occ(3), level;\n"
+                  "  m.append_scan(adder, pose, 3, r.data(), c.data(), s.data(), occ.data());\n"
+                  "  std::vector<LightWeightRectangle> drift(2, LightWeightRectangle{0, 0, 0, 0});\n"
+                  "  m.bounds(cfg, pose, rot, drift, bound, level);\n  (void)m.map().width();\n  (void)m.pyramid();\n}\n")
+    cmd = ["g++", "-std=c++14", "-fsyntax-only", "-w", "-I" + os.path.join(REFERENCE, "src"), "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(ROOT, "slam-constructor_amd", "host"), str(tu)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
