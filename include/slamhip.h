@@ -464,6 +464,15 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
                                const int *is_occ, const double *factor, int trig_mode, double a_min, double a_max,
                                double a_inc, const double pose[3], unsigned skip_rate, double max_range, int bounded,
                                int weighting, int *kept_n, int *kept_idx);
+/* How slamhip_scan_filter_upload moves a scan: the per-beam quantities it keeps (cos, sin, the viny weighting's angular
+ * factor) are resident in HBM as well, uploaded when the angle array or the trig mode changes; a scan brings its kept
+ * ranges, the kept indices where a beam was dropped, and factors / ahr weights where there are any, and a kernel
+ * assembles the scan from both.  *uploads = how often the context has uploaded the per-beam tables so far. */
+int slamhip_scan_table_uploads(slamhip_ctx *ctx, long long *uploads);
+/* The CURRENT scan as the scorers read it, back from HBM (waits for the context's stream): *n = its point count; out5
+ * (room for 5 x cap doubles, cap >= *n) receives range, cos, sin, weight, factor as five rows of cap doubles.  With
+ * cap 0 only *n is returned. */
+int slamhip_scan_download(slamhip_ctx *ctx, int cap, double *out5, int *n);
 /* ScanPointWeighting::weight for a filtered scan: kind 0 even, 1 viny, 2 ahr */
 int slamhip_scan_weights(int kind, int n, const double *range, const double *angle, double *out);
 

@@ -62,7 +62,8 @@ slamhip_scan_set_angles slamhip_libm_variant slamhip_libm_eval slamhip_map_appen
 slamhip_map_render slamhip_gmapping_particle_map_render slamhip_render_cells
 slamhip_scan_gen_angles slamhip_scan_gen_libm_variant slamhip_map_generate_scans slamhip_scan_generate_host
 slamhip_pyramid_create slamhip_pyramid_destroy slamhip_pyramid_info slamhip_pyramid_rebuild slamhip_pyramid_refresh
-slamhip_pyramid_build_host slamhip_pyramid_score_matches slamhip_pyramid_score_matches_device""".split()
+slamhip_pyramid_build_host slamhip_pyramid_score_matches slamhip_pyramid_score_matches_device
+slamhip_scan_table_uploads slamhip_scan_download""".split()
 
 SHARD_ID_BYTES = 128
 

@@ -2026,7 +2026,7 @@ int slamhip_matcher_process_scan(slamhip_matcher *m, int map_id, const double in
       // to the context (slamhip_scan_set_angles / slamhip_scan_filter_upload), else the cached provider's angle addition
       // with the host's sincos of the heading
       run_cfg.sum_order = SLAMHIP_SUM_SEQUENTIAL;
-      run_cfg.pose_trig = (int)ctx->h_scan_angle.size() == ctx->scan_n ? SLAMHIP_POSE_TRIG_RAW_EXACT : SLAMHIP_POSE_TRIG_HOST;
+      run_cfg.pose_trig = scan_angles_known(ctx) ? SLAMHIP_POSE_TRIG_RAW_EXACT : SLAMHIP_POSE_TRIG_HOST;
     }
     const int budget = gm_exact ? 1 : (m->max_batch > 0 ? m->max_batch : 256);
     int rc = ensure_pose_capacity(ctx, budget + 2);  // + the initial pose, + the best pose of a batch scored twice

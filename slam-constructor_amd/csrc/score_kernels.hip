@@ -100,6 +100,48 @@ hipError_t launch_scan_pull(const double *h_src, double *d_dst, size_t n_doubles
   return hipGetLastError();
 }
 
+// The RAW scan's way to HBM (slamhip_scan_filter_upload): only what is new with every scan comes over PCIe -- the kept
+// beams' ranges, their raw indices where the filter dropped any, factors and weights where the caller / the weighting
+// makes them per scan (8.6 KB of k_scan_pull's 43 at 1080 beams).  What depends on the scanner's ANGLES alone (cos,
+// sin, the viny weighting's angular factor: ScanTables, indexed by raw beam) is resident and gathered here.  One thread
+// per point of the scan block's stride; the block comes out as k_scan_pull leaves it (the rows' pads hold zeros
+// instead of whatever the staging buffer held), and the staging buffer is handed back the same way.
+__global__ __launch_bounds__(256) void k_scan_assemble(ScanAssembleArgs a, unsigned *counter, unsigned *h_flag, unsigned seq) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q < (int)a.stride) {
+    double r = 0.0, c = 0.0, s = 0.0, w = 0.0, f = 0.0;
+    if (q < a.n) {
+      r = a.h_range[q];
+      const int i = a.h_kept ? a.h_kept[q] : q;
+      c = a.tab_cos[i];
+      s = a.tab_sin[i];
+      // weighting 0: the host's 1.0 / k; 1: the host's own product, operand for operand (f64 sqrt is correctly rounded
+      // on both sides, the one multiplication has nothing to contract with); 2: made on the host
+      w = a.h_weight ? a.h_weight[q] : (a.tab_viny ? a.tab_viny[i] * sqrt(r) : a.w_even);
+      f = a.h_factor ? a.h_factor[q] : 1.0;
+    }
+    a.dst[q] = r;
+    a.dst[a.stride + q] = c;
+    a.dst[2 * a.stride + q] = s;
+    a.dst[3 * a.stride + q] = w;
+    a.dst[4 * a.stride + q] = f;
+  }
+  __syncthreads();  // (every load of the workgroup from the staging buffer has returned: its values went into stores)
+  if (threadIdx.x == 0) {
+    const unsigned before = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (before + 1u == gridDim.x) {
+      __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(h_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+hipError_t launch_scan_assemble(const ScanAssembleArgs &a, unsigned *counter, unsigned *h_flag, unsigned seq,
+                                hipStream_t stream) {
+  hipLaunchKernelGGL(k_scan_assemble, dim3(((int)a.stride + 255) / 256), dim3(256), 0, stream, a, counter, h_flag, seq);
+  return hipGetLastError();
+}
+
 // The same for a launch's small argument blocks (job tables, initial poses, a zeroed counter): ONE pull of the pinned
 // block in front of the launch instead of several hipMemcpyAsync / hipMemsetAsync calls (each ~6 us of host time and
 // ~10 us of stream time, see above).  The host rewrites the block only after the launch that follows has reported its

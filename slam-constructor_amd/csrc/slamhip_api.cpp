@@ -452,9 +452,18 @@ int libm_variant() {
   return variant;
 }
 
+void scan_angles_materialise(slamhip_ctx *ctx) {
+  if (!ctx->scan_angle_lazy) return;
+  const slamhip_ctx::ScanPrep &sp = ctx->scan_prep;
+  ctx->h_scan_angle.resize(sp.kept.size());
+  for (size_t q = 0; q < sp.kept.size(); ++q) ctx->h_scan_angle[q] = sp.angle[sp.kept[q]];
+  ctx->scan_angle_lazy = false;
+}
+
 // the beam angles of the current scan in HBM (uploaded on first use)
 static int exact_angles(slamhip_ctx *ctx, const double **d_angle) {
   const int n = ctx->scan_n;
+  scan_angles_materialise(ctx);
   if ((int)ctx->h_scan_angle.size() != n) {
     set_error("SLAMHIP_POSE_TRIG_RAW_EXACT needs the angles of the current scan's points: slamhip_scan_set_angles (or "
               "slamhip_scan_filter_upload) after the scan upload");
@@ -771,6 +780,7 @@ int slamhip_ctx_destroy(slamhip_ctx *ctx) {
     if (m.d_prob) hipFree(m.d_prob);
   }
   if (ctx->d_scan) hipFree(ctx->d_scan);
+  if (ctx->d_scan_tab) hipFree(ctx->d_scan_tab);
   if (ctx->d_scan_angle) hipFree(ctx->d_scan_angle);
   if (ctx->d_exact_trig) hipFree(ctx->d_exact_trig);
   if (ctx->d_gm_exact_cache) hipFree(ctx->d_gm_exact_cache);
@@ -1085,33 +1095,67 @@ static int scan_stage_acquire(slamhip_ctx *ctx, int n_max, double **st, size_t *
   return SLAMHIP_OK;
 }
 
-static int scan_stage_commit(slamhip_ctx *ctx, int n, double *st, size_t stride) {
-  const double *weight = st + 3 * stride, *factor = st + 4 * stride;
-  ctx->h_weight.assign(weight, weight + n);
-  ctx->h_factor.assign(factor, factor + n);
-  // total_weight accumulates in beam order and does not depend on the pose
-  // (weighted_mean_point_probability_spe.h:125)
+// total_weight accumulates in beam order and does not depend on the pose
+// (weighted_mean_point_probability_spe.h:125)
+static double scan_total_weight(const double *weight, int n) {
   double tot_w = 0;
   for (int i = 0; i < n; ++i) tot_w += weight[i];
+  return tot_w;
+}
+
+// ... of EvenSPW's k weights 1.0 / k: the same k additions in the same order, made once per k -- the value depends on
+// nothing else, and the chain of k dependent additions was the longest single item of the raw scan's host half (about
+// 1.3 us at 1080 beams by the additions' latency).  Per thread, as slamhip_beam_trig_cached keeps its table.
+static double scan_total_weight_even(int k, double w) {
+  static thread_local std::vector<double> memo;  // [k] = the sum, 0.0 = not made yet (a sum of positive weights is not 0)
+  if ((int)memo.size() <= k) memo.resize((size_t)k + 1, 0.0);
+  if (memo[k] == 0.0) {
+    double tot_w = 0;
+    for (int i = 0; i < k; ++i) tot_w += w;
+    memo[k] = tot_w;
+  }
+  return memo[k];
+}
+
+// commit in three steps, shared by the packed upload and the raw scan's assembly.  (1) the host's record of the new
+// current scan -- n points whose weights / factors are in ctx->h_weight / h_factor already -- and the staging buffer's
+// turn: returns the sequence number the kernel that reads the buffer reports back with ...
+static unsigned scan_stage_turnover(slamhip_ctx *ctx, int n, size_t stride, double tot_w, int *turn_out) {
   ctx->scan_tot_w = tot_w;
   ctx->scan_n = n;
   ctx->scan_ptr = ctx->d_scan;
   ctx->scan_stride = stride;
   ctx->h_scan_angle.clear();  // (the angles of the scan before: slamhip_scan_set_angles)
+  ctx->scan_angle_lazy = false;
   ctx->scan_angle_on_device = false;
   const int turn = ctx->scan_stage_turn;
   ctx->scan_stage_turn ^= 1;
   unsigned seq = ++ctx->scan_pull_next;
   if (seq == 0) seq = ++ctx->scan_pull_next;
   ctx->scan_pull_seq[turn] = seq;
-  // (one pull over the five stretches, gaps included: 5 x stride doubles are 43 KB at 1080 beams)
-  SLAMHIP_CHECK(launch_scan_pull(st, ctx->d_scan, 4 * stride + (size_t)n, ctx->d_scan_pull_count,
-                                 ctx->h_scan_pulled + turn, seq, ctx->stream));
-  if (ctx->stream_b) {  // the second launch lane waits for the scan
+  *turn_out = turn;
+  return seq;
+}
+
+// ... (2) that kernel, queued by the caller; (3) the second launch lane waits for the scan
+static int scan_stage_fork(slamhip_ctx *ctx, int turn) {
+  if (ctx->stream_b) {
     SLAMHIP_CHECK(hipEventRecord(ctx->scan_stage_done[turn], ctx->stream));
     SLAMHIP_CHECK(hipStreamWaitEvent(ctx->stream_b, ctx->scan_stage_done[turn], 0));
   }
   return SLAMHIP_OK;
+}
+
+static int scan_stage_commit(slamhip_ctx *ctx, int n, double *st, size_t stride) {
+  const double *weight = st + 3 * stride, *factor = st + 4 * stride;
+  ctx->h_weight.assign(weight, weight + n);
+  ctx->h_factor.assign(factor, factor + n);
+  int turn = 0;
+  const unsigned seq = scan_stage_turnover(ctx, n, stride, scan_total_weight(weight, n), &turn);
+  // (one pull over the five stretches, gaps included: 5 x stride doubles are 43 KB at 1080 beams)
+  SLAMHIP_CHECK(launch_scan_pull(st, ctx->d_scan, 4 * stride + (size_t)n, ctx->d_scan_pull_count,
+                                 ctx->h_scan_pulled + turn, seq, ctx->stream));
+  return scan_stage_fork(ctx, turn);
 }
 
 int slamhip_scan_upload(slamhip_ctx *ctx, int n, const double *range, const double *cos_a,
@@ -1185,6 +1229,7 @@ int slamhip_scan_select(slamhip_ctx *ctx, int slot) {
   ctx->scan_stride = (size_t)sl.cap;
   ctx->scan_n = sl.n;
   ctx->h_scan_angle.clear();
+  ctx->scan_angle_lazy = false;
   ctx->scan_angle_on_device = false;
   ctx->scan_tot_w = sl.tot_w;
   ctx->h_weight.assign(sl.w.begin(), sl.w.end());
@@ -1318,6 +1363,32 @@ int slamhip_scan_weights(int kind, int n, const double *range, const double *ang
   return invalid("unknown weighting kind");
 }
 
+// scan_prep's per-beam arrays (cos, sin, viny_f) to the context's block in HBM, where k_scan_assemble gathers them: on
+// the context's stream, behind every assembly that still reads the old ones.  Only when scan_prep has recomputed them
+// -- a scanner's angles do not change --, so the call waits for the copies instead of keeping the sources alive.
+static int scan_tables_upload(slamhip_ctx *ctx) {
+  const slamhip_ctx::ScanPrep &sp = ctx->scan_prep;
+  const int n = (int)sp.cos_a.size();
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  if (n > ctx->scan_tab_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->d_scan_tab) hipFree(ctx->d_scan_tab);
+    ctx->d_scan_tab = nullptr;
+    ctx->scan_tab_cap = 0;
+    int cap = 2048;
+    while (cap < n) cap *= 2;
+    SLAMHIP_CHECK(hipMalloc(&ctx->d_scan_tab, sizeof(double) * 3 * cap));
+    ctx->scan_tab_cap = cap;
+  }
+  const size_t cap = (size_t)ctx->scan_tab_cap, bytes = sizeof(double) * n;
+  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_scan_tab, sp.cos_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_scan_tab + cap, sp.sin_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_scan_tab + 2 * cap, sp.viny_f.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ++ctx->scan_tab_uploads;
+  return SLAMHIP_OK;
+}
+
 // The per-scan host half of a match in one call, from the RAW scan: WeightedMeanPointProbabilitySPE::filter_scan
 // (weighted_mean_point_probability_spe.h:75-95,136-141) at the initial pose, the scan-point weights of the filtered
 // scan (:21-60), the beams' cos / sin as the scan's trig provider tabulates them, and the upload.  Through the adapter
@@ -1338,6 +1409,7 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
   const bool same = (int)sp.angle.size() == n && sp.trig_mode == trig_mode && sp.a_min == a_min && sp.a_max == a_max &&
                     sp.a_inc == a_inc && std::memcmp(sp.angle.data(), angle, sizeof(double) * n) == 0;
   if (!same) {
+    scan_angles_materialise(ctx);  // (the current scan's angles are entries of the array that goes away here)
     sp.angle.assign(angle, angle + n);
     sp.trig_mode = trig_mode;
     sp.a_min = a_min;
@@ -1363,17 +1435,24 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
       else if (0.8 < ac) w = 2;
       sp.viny_f[i] = w;
     }
+    rc = scan_tables_upload(ctx);
+    if (rc) {
+      sp.angle.clear();
+      return rc;
+    }
   }
   // ---- filter_scan: keeps point i iff (skip_rate == 0 or i % skip_rate == 0), occupied, its end point's cell in the
   // map, and not beyond the usable range (Q8 - Q10)
   constexpr double eps = std::numeric_limits<double>::epsilon();
-  sp.kept.clear();
+  std::vector<int> &kept = sp.kept_next;  // (sp.kept stays the current scan's until this one has taken its place)
+  kept.clear();
+  const bool cut = 0.0 < max_range + eps;  // (a usable range is set at all)
   double sb = 0, cb = 1;
   if (bounded) ::sincos(pose[2], &sb, &cb);
   for (int i = 0; i < n; ++i) {
     if (skip_rate && (unsigned(i) % skip_rate)) continue;
     if (is_occ && !is_occ[i]) continue;
-    const bool too_far = (0.0 < max_range + eps) && (max_range < range[i] + eps);
+    const bool too_far = cut && (max_range < range[i] + eps);
     if (too_far) continue;
     if (bounded) {
       double c, s;
@@ -1387,47 +1466,79 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
       const int ix = (int)std::floor(wx / m->scale) + m->origin_x, iy = (int)std::floor(wy / m->scale) + m->origin_y;
       if (!(0 <= ix && ix < m->width && 0 <= iy && iy < m->height)) continue;
     }
-    sp.kept.push_back(i);
+    kept.push_back(i);
   }
-  const int k = (int)sp.kept.size();
+  const int k = (int)kept.size();
   if (kept_n) *kept_n = k;
-  if (kept_idx) std::memcpy(kept_idx, sp.kept.data(), sizeof(int) * k);
+  if (kept_idx) std::memcpy(kept_idx, kept.data(), sizeof(int) * k);
   if (k == 0) {
     ctx->scan_n = 0;  // (scoring without a scan fails; the reference scores NaN: the adapter handles an empty scan itself)
+    ctx->scan_angle_lazy = false;
     return SLAMHIP_OK;
   }
-  // straight into the pinned staging buffer the pull kernel reads (no intermediate arrays)
+  // Into the pinned staging buffer goes what is new with THIS scan and nothing else (k_scan_assemble gathers the rest
+  // from the resident tables): the kept ranges; the kept indices where a beam was dropped; factors where the caller
+  // has any; weights where the weighting makes them from the scan's shape (ahr).  Rows of the buffer as the packed
+  // upload uses them: 0 range, 1 indices (int32), 2 factor, 3 weight.
   double *st = nullptr;
   size_t c = 0;
   int rc = scan_stage_acquire(ctx, k, &st, &c);
   if (rc) return rc;
-  double *r_ = st, *c_ = st + c, *s_ = st + 2 * c, *w_ = st + 3 * c, *f_ = st + 4 * c;
-  for (int q = 0; q < k; ++q) {
-    const int i = sp.kept[q];
-    r_[q] = range[i];
-    c_[q] = sp.cos_a[i];
-    s_[q] = sp.sin_a[i];
-    f_[q] = factor ? factor[i] : 1.0;
+  ScanAssembleArgs as{};
+  double *r_ = st;
+  as.h_range = r_;
+  if (k == n) {
+    std::memcpy(r_, range, sizeof(double) * k);
+  } else {
+    int *k_ = reinterpret_cast<int *>(st + c);
+    for (int q = 0; q < k; ++q) r_[q] = range[kept[q]];
+    std::memcpy(k_, kept.data(), sizeof(int) * k);
+    as.h_kept = k_;
   }
+  // ... and the host's own copies of weights and factors (what the commit records; the device makes the same bits),
+  // touched only once nothing can fail any more that would leave the scan before as the current one
   if (weighting == 0) {
-    const double w = 1.0 / k;  // EvenSPW (:21-32)
-    for (int q = 0; q < k; ++q) w_[q] = w;
+    as.w_even = 1.0 / k;  // EvenSPW (:21-32)
+    ctx->h_weight.assign(k, as.w_even);
   } else if (weighting == 1) {
-    for (int q = 0; q < k; ++q) w_[q] = sp.viny_f[sp.kept[q]] * std::sqrt(r_[q]);
+    ctx->h_weight.resize(k);
+    for (int q = 0; q < k; ++q) ctx->h_weight[q] = sp.viny_f[kept[q]] * std::sqrt(r_[q]);
+    as.tab_viny = ctx->d_scan_tab + 2 * (size_t)ctx->scan_tab_cap;
   } else {
     sp.a.resize(k);
     sp.r.assign(r_, r_ + k);
     sp.w.resize(k);
-    for (int q = 0; q < k; ++q) sp.a[q] = angle[sp.kept[q]];
+    for (int q = 0; q < k; ++q) sp.a[q] = angle[kept[q]];
     rc = slamhip_scan_weights(2, k, sp.r.data(), sp.a.data(), sp.w.data());
     if (rc) return rc;
+    double *w_ = st + 3 * c;
     std::memcpy(w_, sp.w.data(), sizeof(double) * k);
+    ctx->h_weight.assign(w_, w_ + k);
+    as.h_weight = w_;
   }
-  rc = scan_stage_commit(ctx, k, st, c);
+  if (factor) {
+    double *f_ = st + 2 * c;
+    for (int q = 0; q < k; ++q) f_[q] = factor[kept[q]];
+    ctx->h_factor.assign(f_, f_ + k);
+    as.h_factor = f_;
+  } else {
+    ctx->h_factor.assign(k, 1.0);
+  }
+  as.tab_cos = ctx->d_scan_tab;
+  as.tab_sin = ctx->d_scan_tab + (size_t)ctx->scan_tab_cap;
+  as.dst = ctx->d_scan;
+  as.stride = c;
+  as.n = k;
+  int turn = 0;
+  const double tot_w = weighting == 0 ? scan_total_weight_even(k, as.w_even) : scan_total_weight(ctx->h_weight.data(), k);
+  const unsigned seq = scan_stage_turnover(ctx, k, c, tot_w, &turn);
+  SLAMHIP_CHECK(launch_scan_assemble(as, ctx->d_scan_pull_count, ctx->h_scan_pulled + turn, seq, ctx->stream));
+  rc = scan_stage_fork(ctx, turn);
   if (rc) return rc;
-  // the kept points' angles, for SLAMHIP_POSE_TRIG_RAW_EXACT (host side only: they go to HBM when an exact call asks)
-  ctx->h_scan_angle.resize(k);
-  for (int q = 0; q < k; ++q) ctx->h_scan_angle[q] = angle[sp.kept[q]];
+  // the kept points' angles, for SLAMHIP_POSE_TRIG_RAW_EXACT: sp.angle[sp.kept[q]], written out when an exact call asks
+  // (scan_angles_materialise); slamhip_scan_set_angles replaces them
+  sp.kept.swap(kept);
+  ctx->scan_angle_lazy = true;
   return SLAMHIP_OK;
 }
 
@@ -1435,7 +1546,26 @@ int slamhip_scan_set_angles(slamhip_ctx *ctx, int n, const double *angle) {
   if (!ctx || !angle) return invalid("bad arguments");
   if (n != ctx->scan_n || n <= 0) return invalid("slamhip_scan_set_angles: n is not the current scan's point count");
   ctx->h_scan_angle.assign(angle, angle + n);
+  ctx->scan_angle_lazy = false;
   ctx->scan_angle_on_device = false;
+  return SLAMHIP_OK;
+}
+
+int slamhip_scan_table_uploads(slamhip_ctx *ctx, long long *uploads) {
+  if (!ctx || !uploads) return invalid("null argument");
+  *uploads = ctx->scan_tab_uploads;
+  return SLAMHIP_OK;
+}
+
+int slamhip_scan_download(slamhip_ctx *ctx, int cap, double *out5, int *n) {
+  if (!ctx || !n || cap < 0 || (cap > 0 && !out5)) return invalid("bad arguments");
+  *n = ctx->scan_n;
+  if (cap == 0 || ctx->scan_n <= 0 || !ctx->scan_ptr) return SLAMHIP_OK;
+  if (cap < ctx->scan_n) return invalid("slamhip_scan_download: room for fewer points than the current scan has");
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  SLAMHIP_CHECK(hipMemcpy2DAsync(out5, sizeof(double) * cap, ctx->scan_ptr, sizeof(double) * ctx->scan_stride,
+                                 sizeof(double) * ctx->scan_n, 5, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return SLAMHIP_OK;
 }
 

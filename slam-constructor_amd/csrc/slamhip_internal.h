@@ -222,6 +222,22 @@ hipError_t launch_stall(int ms, hipStream_t stream);  // testing
 hipError_t launch_block_pull(const void *h_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_scan_pull(const double *h_src, double *d_dst, size_t n_doubles, unsigned *counter, unsigned *h_flag,
                             unsigned seq, hipStream_t stream);
+// k_scan_assemble: the scan block `dst` (five rows of `stride` doubles) from n kept points' ranges in pinned memory and
+// the context's resident per-beam tables; h_kept (raw index per point) null = every beam kept, h_factor null = 1.0,
+// h_weight null = tab_viny[i] * sqrt(range) where tab_viny is given, else w_even.  *h_flag = seq once the pinned
+// arrays have been read.
+struct ScanAssembleArgs {
+  const double *h_range;
+  const int *h_kept;
+  const double *h_factor, *h_weight;
+  const double *tab_cos, *tab_sin, *tab_viny;
+  double *dst;
+  size_t stride;
+  int n;
+  double w_even;
+};
+hipError_t launch_scan_assemble(const ScanAssembleArgs &a, unsigned *counter, unsigned *h_flag, unsigned seq,
+                                hipStream_t stream);
 // (both uploads write the host's stride_host doubles of a cell and leave the rest of it alone -- a GMAPPING cell's pad)
 hipError_t launch_scatter_cells(double *payload, int pitch, int cell_dbl, int stride_host, int n,
                                 const int *d_coords, const double *d_vals, hipStream_t stream);
@@ -333,13 +349,22 @@ struct slamhip_ctx {
     int trig_mode = -1;
     double a_min = 0, a_max = 0, a_inc = 0;
     std::vector<double> r, a, c, s, w, f;
-    std::vector<int> kept;
+    std::vector<int> kept;       // raw indices of the CURRENT scan's points (of the last call that uploaded one)
+    std::vector<int> kept_next;  // ... of the call under way: becomes `kept` once its scan is the current one
   } scan_prep;
+  // ... and the same three per-beam arrays resident in HBM (cos | sin | viny_f, scan_tab_cap doubles each), where
+  // k_scan_assemble gathers them: uploaded when scan_prep recomputes, never by a context that is not given raw scans
+  double *d_scan_tab = nullptr;
+  int scan_tab_cap = 0;
+  long long scan_tab_uploads = 0;
   std::vector<double> h_weight, h_factor;  // host copies for GMapping carry-in fix-ups
   // the libm-exact modes (exact_kernels.hip): the beam ANGLES of the current scan (slamhip_scan_set_angles, or the kept
   // angles of slamhip_scan_filter_upload) -- on the host until an exact scoring call needs them in HBM --, the
   // per-pose trig tables, the reference's one GMapping cache object on the device
   std::vector<double> h_scan_angle;
+  // after slamhip_scan_filter_upload they are scan_prep.angle[scan_prep.kept[q]] and are written out only when somebody
+  // asks (slamhip::scan_angles_materialise): the default scoring modes never do
+  bool scan_angle_lazy = false;
   double *d_scan_angle = nullptr;
   int scan_angle_cap = 0;
   bool scan_angle_on_device = false;
@@ -399,6 +424,12 @@ struct slamhip_ctx {
 };
 
 namespace slamhip {
+// the context knows the angles of the current scan's points (what SLAMHIP_POSE_TRIG_RAW_EXACT needs) ...
+inline bool scan_angles_known(const slamhip_ctx *ctx) {
+  return ctx->scan_angle_lazy || (int)ctx->h_scan_angle.size() == ctx->scan_n;
+}
+// ... and has them in h_scan_angle (slamhip_api.cpp)
+void scan_angles_materialise(slamhip_ctx *ctx);
 // scoring target made of per-slot copy-on-write maps (tile_pool.h) instead of a bound dense window;
 // pose p reads the map of slot ctx->h_pose_slot[p]
 struct TiledTarget {
