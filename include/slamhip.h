@@ -480,7 +480,9 @@ int slamhip_scan_weights(int kind, int n, const double *range, const double *ang
  * Replaces ScanProbabilityEstimator::estimate_scan_probability
  * (src/core/scan_matchers/grid_scan_matcher.h:128-131; WMPP implementation
  * weighted_mean_point_probability_spe.h:97-133) for a BATCH of poses: poses_xyt = n_poses x
- * (x, y, theta) host doubles, scores_out n_poses host doubles (NaN when sum of weights is 0). */
+ * (x, y, theta) host doubles, scores_out n_poses host doubles (NaN when sum of weights is 0).
+ * SLAMHIP_OOPE_GMAPPING scores scans of at most 2048 filtered points (with SLAMHIP_POSE_TRIG_RAW_EXACT: 3840); a longer
+ * one is SLAMHIP_ERR_INVALID, "the GMapping kernel holds at most 2048 filtered beams per scan". */
 int slamhip_score_poses(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, int n_poses,
                         const double *poses_xyt, double *scores_out);
 /* Same with device-resident poses/scores, asynchronous on the context stream (sweep mode) */

@@ -611,8 +611,7 @@ hipError_t launch_score(const ScoreArgs &args, int cell_model, int oope, int sum
   hipError_t e = hipSuccess;
   if (oope == SLAMHIP_OOPE_GMAPPING) {
     if (kb > 8) {
-      set_error("the GMapping kernel holds at most 2048 filtered beams per scan");
-      return hipErrorInvalidValue;
+      return refuse_launch("the GMapping kernel holds at most 2048 filtered beams per scan");
     }
     const size_t shm = (size_t)kb * kBlock * sizeof(double) + 4 * kb * sizeof(int2) + 4 * kb * sizeof(int);
     // 1024 threads per pose for launches of at most 160 poses

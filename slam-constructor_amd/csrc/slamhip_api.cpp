@@ -21,8 +21,21 @@ static thread_local std::string g_last_error;
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
+// A launcher that turns its arguments down itself says why before it returns hipErrorInvalidValue; the SLAMHIP_CHECK
+// around its call used to overwrite that with the call's text alone ("launch_score(...): invalid argument").
+static thread_local std::string g_refusal;
+
+hipError_t refuse_launch(const char *why) {
+  g_refusal = why;
+  return hipErrorInvalidValue;
+}
+
 int hip_fail(hipError_t e, const char *what) {
   g_last_error = std::string(what) + ": " + hipGetErrorString(e);
+  if (!g_refusal.empty()) {
+    if (e == hipErrorInvalidValue) g_last_error += ": " + g_refusal;
+    g_refusal.clear();
+  }
   return e == hipErrorNoDevice ? SLAMHIP_ERR_NO_DEVICE : SLAMHIP_ERR_HIP;
 }
 
@@ -225,6 +238,10 @@ static int fill_args(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cfg,
 static int launch_timed(slamhip_ctx *ctx, const ScoreArgs &a, const DeviceMap &m,
                         const slamhip_spe_cfg *cfg, hipStream_t stream) {
   const int order = cfg->oope == SLAMHIP_OOPE_GMAPPING ? SLAMHIP_SUM_TREE256 : cfg->sum_order;
+  // (K3 keeps a scan's values in LDS, eight blocks of 256 beams at the most: launch_score turns a longer scan down with
+  // hipErrorInvalidValue, which SLAMHIP_CHECK would report as the call's text alone)
+  if (cfg->oope == SLAMHIP_OOPE_GMAPPING && a.scan.n > 2048)
+    return invalid("the GMapping kernel holds at most 2048 filtered beams per scan");
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ctx->profile) {
     // event pairs are only RECORDED here; elapsed times are read in slamhip_profile_read so the

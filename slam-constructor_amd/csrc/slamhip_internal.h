@@ -304,6 +304,7 @@ void scan_gen_release(slamhip_ctx *ctx);              // scan_generate.hip: free
 void pyramids_release(slamhip_ctx *ctx);              // map_pyramid.hip: frees what the context's pyramids hold in HBM
 void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
+hipError_t refuse_launch(const char *why);  // hipErrorInvalidValue; hip_fail appends `why` to the failed call's text
 
 }  // namespace slamhip
 
