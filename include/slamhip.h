@@ -124,6 +124,15 @@ enum {
                                   * instead of the 32-byte cell and its belief arithmetic per (pose, beam); 0: from the
                                   * cell.  The same operations either way: the same bits.  Governs
                                   * SLAMHIP_CELL_CREDIBILIST maps too (their plane holds that model's probability). */
+  SLAMHIP_OPT_RAW_PROLOGUE = 9,  /* slamhip_matcher_process_raw_scan, a lone hill-climbing match that runs as ONE launch of
+                                  * co-resident workgroups (1-cell OOPE, default sum order).  1 (default): the filtered scan
+                                  * is not assembled in HBM by a kernel in front of the match; every workgroup of the
+                                  * chain makes its beams' constants itself from the staged scan and the resident
+                                  * per-beam tables, and the chain writes the scan block for whoever comes after it
+                                  * (csrc/hc_resident.hip, RAW).  0: the assembly kernel, then the chain.  Every other
+                                  * match is behind the assembly kernel either way.  The same bits in both. */
+  SLAMHIP_OPT_RAW_PROLOGUE_MATCHES = 10, /* read-only (slamhip_ctx_get_option): matches of this context so far whose
+                                          * chain assembled the scan itself and reported a result */
   SLAMHIP_OPT_INERT_TAIL = 8     /* the tail of a hill-climbing chain on the device (1-cell OOPE).  The reference's enumerator
                                   * stops at a count of failed rounds, not at convergence
                                   * (hill_climbing_scan_matcher.h:83-101), the steps halved at every failure.

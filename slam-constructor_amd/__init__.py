@@ -28,7 +28,7 @@ OIE_DISCREPANCY, OIE_OCCUPANCY = 0, 1
 SUM_TREE256, SUM_SEQUENTIAL = 0, 1
 POSE_TRIG_DEVICE, POSE_TRIG_HOST, POSE_TRIG_RAW_EXACT = 0, 1, 2
 (OPT_LOW_LATENCY, OPT_STAGE_POSES, OPT_FILTER_CHAINS, OPT_K6_PATH, OPT_K6_BATCH_FAST, OPT_K6_BATCH_KEY64,
- OPT_RESIDENT_CHAINS, OPT_TBM_PLANE, OPT_INERT_TAIL) = range(9)
+ OPT_RESIDENT_CHAINS, OPT_TBM_PLANE, OPT_INERT_TAIL, OPT_RAW_PROLOGUE, OPT_RAW_PROLOGUE_MATCHES) = range(11)
 TRIG_RAW, TRIG_CACHED = 0, 1
 RENDER_OCCGRID, RENDER_PGM = 0, 1  # slamhip_map_render formats: int8 rows bottom-up / uint8 grey rows top-down
 OCC_TBM_CONSISTENT, OCC_TBM_UNKNOWN_EVEN = 0, 1  # the TBM cell class whose tbm2occ a render applies

@@ -131,6 +131,9 @@ struct HcChainArgs {
                          // its own pose (hc_inert) ends the chain in closed form instead of being scored
                          // 6 x (limit - failed) + 1 more times; 2: so does a root the bookkeeping workgroup has CERTIFIED
                          // for the next steps (1-cell form; hc_resident.hip "certificate")
+  ScanAssembleArgs raw;  // lone co-resident 1-cell form straight behind the raw scan's filter (h_range != null: the RAW
+                         // kernels of hc_resident.hip): what k_scan_assemble would have been launched with -- the
+                         // workgroups assemble their beams themselves, the bookkeeping one writes raw.dst
 };
 
 // threads per workgroup: 256, 512 or 1024; n_chains > 1: the multi-chain form (see HcChainArgs::inits)
@@ -143,7 +146,8 @@ hipError_t launch_hc_chain_resident(const HcChainArgs &a, int cell_model, int nt
                                     hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int n_chains = 1);
 hipError_t hc_resident_capacity(int cell_model, HcResidentKey key, int n_beams, bool lds_consts, int *out_wgs,
                                 int *out_per_cu = nullptr);
-size_t hc_resident_lds_bytes(int nt, int n_beams, bool lds_consts, int max_inst, bool pair = false);
+// (lds_consts: 0 none, 1 range / cosine / sine, 2 -- the RAW form -- weight and factor too)
+size_t hc_resident_lds_bytes(int nt, int n_beams, int lds_consts, int max_inst, bool pair = false);
 // the GMapping OOPE's co-resident form (hc_resident_gm.hip): one chain, or n_chains of a filter step (grid.y = chain:
 // HcChainArgs::inits / n_done / h_all_done / tables / slots as in launch_hc_chain_step)
 hipError_t launch_hc_chain_resident_gm(const HcChainArgs &a, int nt, hipStream_t stream, hipEvent_t ev_start = nullptr,

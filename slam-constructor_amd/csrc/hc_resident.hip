@@ -36,6 +36,7 @@
 
 #include "hc_chain_device.h"
 #include "hc_resident_device.h"
+#include "scan_assemble_device.h"
 #include "score_device.h"
 
 namespace slamhip {
@@ -96,8 +97,17 @@ constexpr int kSelStop = -3;     // leave: the replay found no terminal round (a
 // every workgroup does for itself besides its terms -- polling the granules, the replay, the table of next poses -- is
 // ~45 % on top of them; the pair halves that share, and its two poses share the beam constants in LDS, which then fit
 // again beside the table (K = 8).
-template <int MODEL, int NT, bool SEQ, bool BATCH, int G, bool WIN = false, bool PAIR = false>
+// RAW (a lone chain in the default sum order, straight behind the raw scan's filter: slamhip_matcher_process_raw_scan):
+// nobody has assembled the scan block yet.  Every workgroup makes its beams' constants itself, the way k_scan_assemble
+// makes them (scan_assemble_point: the staged ranges / indices / factors / weights from pinned memory -- one PCIe read
+// per XCD, the other workgroups' loads hit its L2: tools/probes/host_read_probe.hip --, cosine / sine / the viny factor
+// from the resident tables), keeps ALL FIVE constants of the beams behind a thread's first one in LDS, and reads
+// nothing of the scan block; the bookkeeping workgroup, idle behind the first super-step, writes the block for
+// whoever comes after this launch.  The assembly kernel and the kernel boundary behind it leave the match's critical
+// path; no workgroup waits for another one's scan data.
+template <int MODEL, int NT, bool SEQ, bool BATCH, int G, bool WIN = false, bool PAIR = false, bool RAW = false>
 __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
+  static_assert(!RAW || (!SEQ && !BATCH && !WIN && !PAIR), "RAW: the lone 1-cell chain in the default sum order only");
   constexpr int H = PAIR ? 2 : 1;    // poses per workgroup
   constexpr int NTH = NT / H;        // threads per pose
   constexpr bool CERT = !WIN;        // the 1-cell OOPE: a beam's term is a function of its cell alone (see "certificate")
@@ -117,6 +127,8 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
   __shared__ unsigned long long s_hpart[H][4];
   __shared__ double s_cert[2][16];  // the bookkeeping workgroup's certificate: per-wave minima (see "certificate" below)
   __shared__ int s_cert_end;        // the replay's verdict: the chain ends on a certified root
+  // (testing builds: the kernel's first instruction on the wall clock -- spare stamp 6 of super-step 0: what the prologue costs)
+  const long long t_kernel_begin = SLAMHIP_STAMPS_ON(a.stamps != nullptr) ? (long long)wall_clock64() : 0ll;
   const int t = threadIdx.x, wave = t >> 6;
   const int half = PAIR ? (t >= NTH ? 1 : 0) : 0;  // which of the workgroup's poses this thread works on
   const int tl = t - half * NTH, lwave = tl >> 6;  // ... and its place among that pose's threads
@@ -153,30 +165,61 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
   const int n = scan.n;
   // this thread's first beam: its constants stay in registers for the whole match
   double br = 0.0, bc = 0.0, bs = 0.0, bw = 0.0, bf = 0.0;
-  if (tl < n) {
+  if (!RAW && tl < n) {
     br = scan.range[tl];
     bc = scan.cos_a[tl];
     bs = scan.sin_a[tl];
     bw = scan.weight[tl];
     bf = scan.factor[tl];
   }
-  if (lwave == 1 && (t & 63) < kHcShapes && !init_slot && exists) {
+  // RAW: this thread's beams, assembled from the staged scan and the resident tables.  The staged arrays come over
+  // PCIe (~2 us more than HBM, tools/probes/host_read_probe.hip) and nothing in the prologue needs them: they are asked
+  // for HERE and first touched at the barrier that ends the prologue, with the exchange block's set-up and the serial
+  // derivation of the first pose in between.  A wave's loads return in the order they were issued, so whatever the
+  // prologue does wait for -- the word read at entry, this workgroup's round instances -- is asked for in FRONT of them.
+  // The first further beam's constants wait in registers (1080 beams on 1024 threads: those threads are the very wave
+  // that derives the pose); where a thread has more than one further beam, the others follow behind the pose.
+  const bool mine_here = lwave == 1 && (t & 63) < kHcShapes && !init_slot && exists;
+  constexpr int kMineQ = (int)(sizeof(HcInst) / 16);
+  uint4 mine_regs[kMineQ];
+  ScanPoint raw_more{0.0, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (RAW) {
+    if (mine_here) {
+      const uint4 *src = reinterpret_cast<const uint4 *>(&a.shapes[t & 63].inst[inst_of_slot]);
+#pragma unroll
+      for (int q = 0; q < kMineQ; ++q) mine_regs[q] = src[q];
+    }
+    asm volatile("" ::: "memory");  // (issue order: the instances' loads, then the beams')
+    if (tl < n) {
+      const ScanPoint p = scan_assemble_point(a.raw, tl);
+      br = p.range;
+      bc = p.cos_a;
+      bs = p.sin_a;
+      bw = p.weight;
+      bf = p.factor;
+    }
+    if (NTH + t < n) raw_more = scan_assemble_point(a.raw, NTH + t);
+    asm volatile("" ::: "memory");
+  }
+  if (mine_here) {
     const uint4 *src = reinterpret_cast<const uint4 *>(&a.shapes[t & 63].inst[inst_of_slot]);
     uint4 *dst = reinterpret_cast<uint4 *>(&s_mine[half][t & 63]);
 #pragma unroll
-    for (int q = 0; q < (int)(sizeof(HcInst) / 16); ++q) dst[q] = src[q];
+    for (int q = 0; q < kMineQ; ++q) dst[q] = RAW ? mine_regs[q] : src[q];
   }
   // A thread scores up to five beams, and 1080 beams on 1024 threads give the first 56 threads a second one.  What
   // the cell ADDRESS of those further beams depends on -- range, cosine, sine -- is kept in LDS for the whole match
   // (the host asks for it when the workgroups still fit the device with that much LDS, HcChainArgs::lds_consts): read
   // from memory, as weight and factor still are, it was a round trip in front of the gathers' own in every
   // super-step (r04, super-step of a lone chain, us: 256 threads 7.3 -> 6.6, 512 6.3 -> 6.1).
-  const bool ldsc = !WIN && a.lds_consts != 0;
+  // (RAW: always, and weight and factor too -- this launch reads nothing of the scan block)
+  const bool ldsc = RAW || (!WIN && a.lds_consts != 0);
   const int n_more = n > NTH ? n - NTH : 0;
   // (a pair: two term vectors, a.scan.n -- the launch's longest scan -- apart; the constants behind them are shared)
   double *const my_term = s_term + (PAIR ? half * a.scan.n : 0);
   double *const s_r = s_term + (PAIR ? 2 * a.scan.n : n) - NTH, *const s_ca = s_r + n_more, *const s_sa = s_ca + n_more;  // (indexed by beam >= NTH)
-  if (ldsc) {
+  double *const s_w = s_sa + n_more, *const s_f = s_w + n_more;  // (RAW only: hc_resident_tab_offset)
+  if (!RAW && ldsc) {
     for (int b = NTH + t; b < n; b += NT) {
       s_r[b] = scan.range[b];
       s_ca[b] = scan.cos_a[b];
@@ -194,6 +237,7 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
   }
   const bool verify = a.verify != 0;
   const bool stamp = SLAMHIP_STAMPS_ON(a.stamps && slot == 1 && tl == 0 && blockIdx.y == 0);
+  if (stamp) a.stamps[6] = t_kernel_begin;
   HcGranule *const gran = &rc->gran[0][0];
   HcGranule *const gseq = &rc->seq[0][0];
   constexpr int kGranRow = kHcSlots + 7;
@@ -243,8 +287,46 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
       s_cur_go[half] = go ? 1 : 0;
     }
   }
+  if constexpr (RAW) {
+    for (int b = NTH + t; b < n; b += NT) {
+      const ScanPoint p = b == NTH + t ? raw_more : scan_assemble_point(a.raw, b);
+      s_r[b] = p.range;
+      s_ca[b] = p.cos_a;
+      s_sa[b] = p.sin_a;
+      s_w[b] = p.weight;
+      s_f[b] = p.factor;
+    }
+  }
   __syncthreads();
 
+  // RAW ---- the scan block for whoever comes after this launch (the map update, a download, a later match on the
+  // resident scan), as k_scan_assemble leaves it, pads zeroed: by the bookkeeping workgroup, which scores nothing behind
+  // the first super-step -- in super-step 1, once its granule is out (nobody waits for these stores).  Plain stores;
+  // stream order makes them visible; nobody of THIS launch reads them.  (A chain that gives up before it gets here is
+  // redone by the host behind an assembly kernel.)
+  auto write_scan_block = [&](int t, double *dst, int stride) __attribute__((always_inline)) {
+    for (int q = t; q < stride; q += NT) {
+      double r_ = 0.0, ca = 0.0, sa = 0.0, w = 0.0, f = 0.0;
+      if (q < NT && q < n) {  // (q == t: this thread's first beam)
+        r_ = br;
+        ca = bc;
+        sa = bs;
+        w = bw;
+        f = bf;
+      } else if (q < n) {
+        r_ = s_r[q];
+        ca = s_ca[q];
+        sa = s_sa[q];
+        w = s_w[q];
+        f = s_f[q];
+      }
+      dst[q] = r_;
+      dst[stride + q] = ca;
+      dst[2 * stride + q] = sa;
+      dst[3 * stride + q] = w;
+      dst[4 * stride + q] = f;
+    }
+  };
   const int t_entry = t;
   for (int k = 0;; ++k) {
     const int pk = k & 1;
@@ -363,6 +445,9 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
             __hip_atomic_store(ap->h_all_done, ap->epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       }
+      if constexpr (RAW) {
+        if (done && init_slot && k == 1) write_scan_block(t, ap->raw.dst, (int)ap->raw.stride);  // (a chain of ONE super-step)
+      }
       if (done) break;  // (uniform: every thread read the same entry)
     } else {
       if (sel == kSelRescore && init_slot) {
@@ -435,8 +520,8 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
               r_ = ldsc ? s_r[bc_] : scan.range[bc_];
               ca = ldsc ? s_ca[bc_] : scan.cos_a[bc_];
               sa = ldsc ? s_sa[bc_] : scan.sin_a[bc_];
-              w_[j] = scan.weight[bc_];
-              f_[j] = scan.factor[bc_];
+              w_[j] = RAW ? s_w[bc_] : scan.weight[bc_];
+              f_[j] = RAW ? s_f[bc_] : scan.factor[bc_];
             }
             cell[j] = beam_cell<MODEL>(map, px, py, sn, cs, r_, ca, sa);
           }
@@ -562,6 +647,9 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
       gran_store(&gran[pk * kGranRow + slot], cert_here ? cert_t : 0.0,
                  cert_here ? (unsigned long long)__double_as_longlong(cert_r) >> 16 : 0ull, tag);
       if (verify && mode) gran_store(&gseq[pk * kGranRow + slot], 0.0, 0ull, tag);
+    }
+    if constexpr (RAW) {
+      if (init_slot && k == 1) write_scan_block(t, ap->raw.dst, (int)ap->raw.stride);
     }
 
     if (wave != 0) {
@@ -870,14 +958,15 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
 }
 
 // dynamic LDS of a workgroup: the beams' terms, with lds_consts range, cosine and sine of the beams behind every
-// thread's first one, and the table of next poses (7 entries per round instance of the largest shape)
-size_t hc_resident_tab_offset(int nt, int n_beams, bool lds_consts, bool pair) {  // (in doubles)
+// thread's first one (lds_consts 2, the RAW form: weight and factor as well), and the table of next poses (7 entries
+// per round instance of the largest shape)
+size_t hc_resident_tab_offset(int nt, int n_beams, int lds_consts, bool pair) {  // (in doubles)
   const size_t n = (size_t)(n_beams > 0 ? n_beams : 1);
   const size_t nth = (size_t)(pair ? nt / 2 : nt);  // threads per pose
   const size_t more = lds_consts && n > nth ? n - nth : 0;
-  return (pair ? 2 : 1) * n + 3 * more;
+  return (pair ? 2 : 1) * n + (lds_consts > 1 ? 5 : 3) * more;
 }
-size_t hc_resident_lds_bytes(int nt, int n_beams, bool lds_consts, int max_inst, bool pair) {
+size_t hc_resident_lds_bytes(int nt, int n_beams, int lds_consts, int max_inst, bool pair) {
   return sizeof(double) * hc_resident_tab_offset(nt, n_beams, lds_consts, pair) +
          (pair ? sizeof(HcNextEntryT<2>) : sizeof(HcNextEntryT<1>)) * 7 * (size_t)max_inst;
 }
@@ -900,6 +989,9 @@ static HcResidentKernel hc_resident_kernel(int cell_model, const HcResidentKey &
         if constexpr (NT == 512)
           if (key.batch && key.pair) return k_hc_chain_resident<M, 512, false, true, G, false, true>;
         if (key.batch) return k_hc_chain_resident<M, NT, false, true, G>;
+        if constexpr (G == 4)  // (a lone matcher's tree: 253 workgroups)
+          if (key.raw) return k_hc_chain_resident<M, NT, false, false, 4, false, false, true>;
+        if (key.raw) return nullptr;  // (refused by hc_resident_variant)
         return key.seq ? k_hc_chain_resident<M, NT, true, false, G> : k_hc_chain_resident<M, NT, false, false, G>;
       };
       if (g_v == 2) return sweep(int_c<2>{});
@@ -911,7 +1003,8 @@ static HcResidentKernel hc_resident_kernel(int cell_model, const HcResidentKey &
 }
 
 static HcResidentKey key_of(const HcChainArgs &a, int nt) {
-  return {nt, a.max_inst, a.seq != 0, a.jobs != nullptr, a.pair != 0, a.oope != SLAMHIP_OOPE_OBSTACLE};
+  return {nt, a.max_inst, a.seq != 0, a.jobs != nullptr, a.pair != 0, a.oope != SLAMHIP_OOPE_OBSTACLE,
+          a.raw.h_range != nullptr};
 }
 
 hipError_t launch_hc_chain_resident(const HcChainArgs &a_in, int cell_model, int nt, hipStream_t stream, hipEvent_t e0,
@@ -920,7 +1013,9 @@ hipError_t launch_hc_chain_resident(const HcChainArgs &a_in, int cell_model, int
   HcChainArgs a = a_in;
   const HcResidentKey key = key_of(a, nt);
   const bool pair = key.batch && key.pair;
-  const bool ldsc = !key.window && a.lds_consts != 0;  // (the window form keeps no beam constants in LDS)
+  // (the window form keeps no beam constants in LDS; the RAW form all five of them)
+  const int ldsc = key.window ? 0 : (key.raw ? 2 : (a.lds_consts != 0 ? 1 : 0));
+  if (key.raw && a.raw.n != a.scan.n) return hipErrorInvalidValue;
   const int grid = pair ? 3 * a.max_inst + 1 : 6 * a.max_inst + 1;  // (a pair: two scoring slots per workgroup + the bookkeeping one)
   a.tab_offset = (int)hc_resident_tab_offset(nt, a.scan.n, ldsc, pair);
   return launch_kernel(hc_resident_kernel(cell_model, key), dim3(grid, n_chains), dim3(hc_nt_of(nt)),
@@ -935,7 +1030,8 @@ hipError_t hc_resident_capacity(int cell_model, HcResidentKey key, int n_beams, 
   // the ONE departure from "what is launched": a beam-order chain has always been sized by the default order's kernel
   key.seq = false;
   return resident_capacity_of((const void *)hc_resident_kernel(cell_model, key), key.nt,
-                              hc_resident_lds_bytes(key.nt, n_beams, lds_consts, key.max_inst, key.batch && key.pair),
+                              hc_resident_lds_bytes(key.nt, n_beams, key.raw ? 2 : (lds_consts ? 1 : 0), key.max_inst,
+                                                    key.batch && key.pair),
                               2048 / key.nt /* 128-VGPR waves: four per SIMD */, 6, out_wgs, out_per_cu);
 }
 

@@ -83,17 +83,20 @@ constexpr int hc_gran_per_lane(int grid) { return grid <= 128 ? 2 : (grid <= 256
 struct HcResidentKey {
   int nt, max_inst;
   bool seq, batch, pair, window;
+  bool raw = false;  // the workgroups assemble the raw scan's beams themselves (HcChainArgs::raw)
 };
 // ... and what is instantiated for it: workgroup size and sweep width; false: no such kernel.
 //   window  256 / 512 / 1024 threads, lone chains of at most 256 workgroups in the default sum order, G = 4
 //   pair    512 threads, G = 2 / 4 / 7
 //   plain   256 / 512 / 1024 threads, the default or the beam-order sum or a batch, G = 2 / 4 / 7 -- but 385 workgroups
 //           of 1024 threads are not resident together
+//   raw     the plain form's lone chains in the default sum order, G = 4
 inline bool hc_resident_variant(const HcResidentKey &k, int *nt, int *g) {
   const int slots = 6 * k.max_inst + 1;
   *nt = hc_nt_of(k.nt);
   *g = k.window ? 4 : hc_gran_per_lane(slots);
   if (k.seq && k.batch) return false;
+  if (k.raw && (k.seq || k.batch || k.window || *g != 4)) return false;
   if (k.window) return !k.seq && !k.batch && slots <= 256;
   if (k.batch && k.pair) return k.nt == 512;
   return !(*nt == 1024 && *g == 7);

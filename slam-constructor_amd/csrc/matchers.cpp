@@ -170,7 +170,8 @@ struct slamhip_matcher {
   slamhip::ResidentPolicy resident;  // bounded spins that ran out: the kernel chain instead (resident_policy.h)
   // answers of the occupancy query so far, keyed by everything the answer depends on (kernel instantiation: cell model,
   // workgroup size, lone / batch / window form, sweep width via max_inst; dynamic LDS: scan length, beam constants)
-  enum class ResidentForm { Lone, Batch, Window, MonteCarlo, Pair };  // (Pair: a batch whose workgroups score two poses)
+  // (Pair: a batch whose workgroups score two poses; LoneRaw: a lone chain that assembles the raw scan itself)
+  enum class ResidentForm { Lone, Batch, Window, MonteCarlo, Pair, LoneRaw };
   struct ResidentCap {
     int cell_model, nt;
     ResidentForm form;
@@ -397,7 +398,8 @@ int resident_capacity(slamhip_matcher *m, int cell_model, int nt, ResidentForm f
     SLAMHIP_CHECK(mc_resident_capacity(cell_model, nt, n_beams, lds_consts, &cap, &pc));
   } else {
     const bool pair = form == ResidentForm::Pair;
-    const HcResidentKey key{nt, max_inst, false, pair || form == ResidentForm::Batch, pair, form == ResidentForm::Window};
+    const HcResidentKey key{nt, max_inst, false, pair || form == ResidentForm::Batch, pair, form == ResidentForm::Window,
+                            form == ResidentForm::LoneRaw};
     SLAMHIP_CHECK(hc_resident_capacity(cell_model, key, n_beams, lds_consts, &cap, &pc));
   }
   if (cap < 0) cap = 0;
@@ -609,6 +611,13 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
     SLAMHIP_CHECK(m->h_trace.alloc(m->trace_cap, kPinnedCoherent));
   }
   const bool win = is_window_oope(m->cfg.oope), gm = m->cfg.oope == SLAMHIP_OOPE_GMAPPING;
+  // A raw scan whose block nobody has assembled yet (slamhip_matcher_process_raw_scan): the lone co-resident 1-cell
+  // chain in the default sum order takes the assembly into its own launch, once it is known to fit (below);
+  // everything else reads the block
+  if (!resident || win || gm || m->cfg.sum_order == SLAMHIP_SUM_SEQUENTIAL || !ctx->raw_prologue) {
+    rc = scan_assemble_now(ctx);
+    if (rc) return rc;
+  }
   a.oie = oie_eff;
   a.oope = win ? m->cfg.oope : SLAMHIP_OOPE_OBSTACLE;
   for (int k = 0; k < 4; ++k) a.area[k] = m->cfg.area[k];
@@ -671,14 +680,37 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
         // stale can carry a current tag -- hc_tag in hc_resident.hip)
         a.rctl = hc.d_rctl.get();
         a.rctl_gm = hc.d_rctl_gm.get();
+        if (ctx->scan_pending.active) {
+          // the RAW kernel keeps five constants per further beam in LDS where the plain one keeps three: its own query
+          bool fuse = false;
+          int nt_v = 0, g_v = 0;
+          if (a.lds_consts && hc_resident_variant(HcResidentKey{m->chain_nt, a.max_inst, false, false, false, false, true}, &nt_v, &g_v)) {
+            int cap_raw = 0;
+            r = resident_capacity(m, cell_model, m->chain_nt, ResidentForm::LoneRaw, a.scan.n, true, a.max_inst, &cap_raw);
+            if (r) return r;
+            fuse = grid <= cap_raw;
+          }
+          if (fuse) {
+            a.raw = ctx->scan_pending.as;
+          } else {
+            r = scan_assemble_now(ctx);
+            if (r) return r;
+          }
+        }
         *fits = true;
         return SLAMHIP_OK;
       },
       [&](hipEvent_t e0, hipEvent_t e1) {
-        return gm ? launch_hc_chain_resident_gm(a, m->chain_nt, ctx->stream, e0, e1)
-                  : launch_hc_chain_resident(a, cell_model, m->chain_nt, ctx->stream, e0, e1);
+        const hipError_t e = gm ? launch_hc_chain_resident_gm(a, m->chain_nt, ctx->stream, e0, e1)
+                                : launch_hc_chain_resident(a, cell_model, m->chain_nt, ctx->stream, e0, e1);
+        scan_record_finish(ctx);  // (the host's copies of the raw scan's weights / factors: while the GPU runs)
+        return e;
       },
       [&](bool) -> int {
+        // (a raw scan the co-resident launch was to assemble -- no fit, no lease, or it gave up: the assembly kernel
+        // first, as on the plain path)
+        const int arc = scan_assemble_now(ctx);
+        if (arc) return arc;
         // the kernel chain redoes the match from its start, under an epoch of its own
         if (win) return kChainNeedsHost;
         a = a_chain;
@@ -697,6 +729,13 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
       },
       LoneChainText{"internal: the co-resident chain ended without publishing a result", "co-resident hill-climbing chain",
                     "hill-climbing chain did not end", "hill-climbing chain kernel"});
+  if (ctx->scan_pending.active) {
+    // the RAW launch has reported: every workgroup read its beams before its first granule, the result needed every
+    // granule, and the bookkeeping workgroup wrote the block behind the first super-step -- the staging buffer's turn is
+    // over.  (Anything else -- an error on the way, a replay that stopped: the assembly kernel)
+    const int src = (rc == SLAMHIP_OK && h->error != 1) ? scan_fused_done(ctx) : scan_assemble_now(ctx);
+    if (!rc) rc = src;
+  }
   if (rc) return rc;
   m->chain_launched = launched;
   if (h->error == 1) {
@@ -1844,9 +1883,12 @@ int slamhip_matcher_process_raw_scan(slamhip_matcher *m, int map_id, const slamh
                                      double out_delta[3], double *out_prob, int *kept_n) {
   if (!m || !scan || !init_pose || !out_delta || !out_prob) return invalid_arg("null argument");
   int kept = 0;
-  const int rc = slamhip_scan_filter_upload(m->ctx, map_id, scan->n, scan->range, scan->angle, scan->is_occ, scan->factor,
-                                            scan->trig_mode, scan->a_min, scan->a_max, scan->a_inc, init_pose, scan->skip_rate,
-                                            scan->max_range, scan->bounded, scan->weighting, &kept, nullptr);
+  // the first half of slamhip_scan_filter_upload: filter and staging.  Who writes the scan block is decided where the
+  // match is launched: the lone co-resident hill-climbing chain does it itself (chain_process_scan), every other path
+  // goes through scan_assemble_now before its first kernel.
+  int rc = scan_filter_stage(m->ctx, map_id, scan->n, scan->range, scan->angle, scan->is_occ, scan->factor, scan->trig_mode,
+                             scan->a_min, scan->a_max, scan->a_inc, init_pose, scan->skip_rate, scan->max_range,
+                             scan->bounded, scan->weighting, &kept, nullptr);
   if (kept_n) *kept_n = kept;
   if (rc) return rc;
   if (kept == 0) {  // 0 / 0 for every candidate (weighted_mean_point_probability_spe.h:126-132): nothing is accepted
@@ -1854,7 +1896,10 @@ int slamhip_matcher_process_raw_scan(slamhip_matcher *m, int map_id, const slamh
     *out_prob = std::numeric_limits<double>::quiet_NaN();
     return SLAMHIP_OK;
   }
-  return slamhip_matcher_process_scan(m, map_id, init_pose, out_delta, out_prob);
+  rc = slamhip_matcher_process_scan(m, map_id, init_pose, out_delta, out_prob);
+  // (a match that failed before it launched anything: the scan is the current one all the same, its block gets written)
+  const int arc = scan_assemble_now(m->ctx);
+  return rc ? rc : arc;
 }
 
 int slamhip_matcher_tail_stats(slamhip_matcher *m, long long *calls_closed_form) {
@@ -1962,6 +2007,11 @@ int slamhip_matcher_process_scan(slamhip_matcher *m, int map_id, const double in
     const int crc = chain_process_scan(m, map_id, init_pose, out_delta, out_prob, hc_resident_asked(m));
     if (crc == kChainUnsettled) force_exact = true;
     else if (crc != kChainNeedsHost) return crc;
+  }
+  {
+    // (a raw scan whose block is still to be assembled, slamhip_matcher_process_raw_scan: everything below reads it)
+    const int arc = scan_assemble_now(ctx);
+    if (arc) return arc;
   }
   if (!force_exact && mc_chain_eligible(m)) {
     const int crc = mc_chain_process_scan(m, map_id, init_pose, out_delta, out_prob);

@@ -40,6 +40,7 @@
 
 #include "gm_score_device.h"
 #include "kernel_pick.h"
+#include "scan_assemble_device.h"
 #include "score_device.h"
 
 namespace slamhip {
@@ -109,22 +110,13 @@ hipError_t launch_scan_pull(const double *h_src, double *d_dst, size_t n_doubles
 __global__ __launch_bounds__(256) void k_scan_assemble(ScanAssembleArgs a, unsigned *counter, unsigned *h_flag, unsigned seq) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q < (int)a.stride) {
-    double r = 0.0, c = 0.0, s = 0.0, w = 0.0, f = 0.0;
-    if (q < a.n) {
-      r = a.h_range[q];
-      const int i = a.h_kept ? a.h_kept[q] : q;
-      c = a.tab_cos[i];
-      s = a.tab_sin[i];
-      // weighting 0: the host's 1.0 / k; 1: the host's own product, operand for operand (f64 sqrt is correctly rounded
-      // on both sides, the one multiplication has nothing to contract with); 2: made on the host
-      w = a.h_weight ? a.h_weight[q] : (a.tab_viny ? a.tab_viny[i] * sqrt(r) : a.w_even);
-      f = a.h_factor ? a.h_factor[q] : 1.0;
-    }
-    a.dst[q] = r;
-    a.dst[a.stride + q] = c;
-    a.dst[2 * a.stride + q] = s;
-    a.dst[3 * a.stride + q] = w;
-    a.dst[4 * a.stride + q] = f;
+    ScanPoint p{0.0, 0.0, 0.0, 0.0, 0.0};
+    if (q < a.n) p = scan_assemble_point(a, q);  // (scan_assemble_device.h: shared with the chain that assembles for itself)
+    a.dst[q] = p.range;
+    a.dst[a.stride + q] = p.cos_a;
+    a.dst[2 * a.stride + q] = p.sin_a;
+    a.dst[3 * a.stride + q] = p.weight;
+    a.dst[4 * a.stride + q] = p.factor;
   }
   __syncthreads();  // (every load of the workgroup from the staging buffer has returned: its values went into stores)
   if (threadIdx.x == 0) {

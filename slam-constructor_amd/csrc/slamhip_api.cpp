@@ -760,6 +760,8 @@ int slamhip_ctx_set_option(slamhip_ctx *ctx, int option, int value) {
     case SLAMHIP_OPT_K6_BATCH_KEY64: ctx->k6_batch_key64 = value != 0; break;
     case SLAMHIP_OPT_RESIDENT_CHAINS: ctx->resident_chains = value != 0; break;
     case SLAMHIP_OPT_TBM_PLANE: ctx->tbm_plane = value != 0; break;
+    case SLAMHIP_OPT_RAW_PROLOGUE: ctx->raw_prologue = value != 0; break;
+    case SLAMHIP_OPT_RAW_PROLOGUE_MATCHES: return invalid("SLAMHIP_OPT_RAW_PROLOGUE_MATCHES is read-only");
     case SLAMHIP_OPT_INERT_TAIL:
       if (value < 0 || value > 2) return invalid("SLAMHIP_OPT_INERT_TAIL: 0 (off), 1 (identical poses) or 2 (default: certified poses too)");
       ctx->inert_tail = value;
@@ -781,6 +783,8 @@ int slamhip_ctx_get_option(slamhip_ctx *ctx, int option, int *value) {
     case SLAMHIP_OPT_RESIDENT_CHAINS: *value = ctx->resident_chains; break;
     case SLAMHIP_OPT_TBM_PLANE: *value = ctx->tbm_plane; break;
     case SLAMHIP_OPT_INERT_TAIL: *value = ctx->inert_tail; break;
+    case SLAMHIP_OPT_RAW_PROLOGUE: *value = ctx->raw_prologue; break;
+    case SLAMHIP_OPT_RAW_PROLOGUE_MATCHES: *value = (int)(ctx->raw_prologue_matches & 0x7fffffff); break;
     default: return invalid("unknown option");
   }
   return SLAMHIP_OK;
@@ -1418,7 +1422,58 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
                                const int *is_occ, const double *factor, int trig_mode, double a_min, double a_max,
                                double a_inc, const double pose[3], unsigned skip_rate, double max_range, int bounded,
                                int weighting, int *kept_n, int *kept_idx) {
+  const int rc = slamhip::scan_filter_stage(ctx, map_id, n, range, angle, is_occ, factor, trig_mode, a_min, a_max, a_inc,
+                                            pose, skip_rate, max_range, bounded, weighting, kept_n, kept_idx);
+  return rc ? rc : slamhip::scan_assemble_now(ctx);
+}
+
+}  // extern "C"
+
+namespace slamhip {
+
+void scan_record_finish(slamhip_ctx *ctx) {
+  slamhip_ctx::ScanPending &sp = ctx->scan_pending;
+  if (!sp.record_due) return;
+  sp.record_due = false;
+  const int k = sp.as.n;
+  // (weighting 1 made its weights in front of the launch: the total weight needs them)
+  if (sp.weighting == 0) ctx->h_weight.assign(k, sp.as.w_even);
+  else if (sp.weighting == 2) ctx->h_weight.assign(sp.as.h_weight, sp.as.h_weight + k);
+  if (sp.as.h_factor) ctx->h_factor.assign(sp.as.h_factor, sp.as.h_factor + k);
+  else ctx->h_factor.assign(k, 1.0);
+}
+
+int scan_assemble_now(slamhip_ctx *ctx) {
+  slamhip_ctx::ScanPending &sp = ctx->scan_pending;
+  if (!sp.active) return SLAMHIP_OK;
+  sp.active = false;
+  const hipError_t e = launch_scan_assemble(sp.as, ctx->d_scan_pull_count, ctx->h_scan_pulled + sp.turn, sp.seq, ctx->stream);
+  scan_record_finish(ctx);
+  SLAMHIP_CHECK(e);
+  return scan_stage_fork(ctx, sp.turn);
+}
+
+int scan_fused_done(slamhip_ctx *ctx) {
+  slamhip_ctx::ScanPending &sp = ctx->scan_pending;
+  if (!sp.active) return SLAMHIP_OK;
+  sp.active = false;
+  ++ctx->raw_prologue_matches;
+  scan_record_finish(ctx);
+  // the staging buffer has been read: what the assembly kernel's last workgroup would have told scan_stage_acquire
+  __atomic_store_n(ctx->h_scan_pulled + sp.turn, sp.seq, __ATOMIC_RELAXED);
+  return scan_stage_fork(ctx, sp.turn);
+}
+
+int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, const double *angle, const int *is_occ,
+                      const double *factor, int trig_mode, double a_min, double a_max, double a_inc, const double pose[3],
+                      unsigned skip_rate, double max_range, int bounded, int weighting, int *kept_n, int *kept_idx) {
   if (!ctx || n <= 0 || !range || !angle || !pose) return invalid("bad arguments");
+  {
+    // (a scan still between its halves -- a caller that failed in between: its block is written before its staging
+    // buffer's turn comes round again)
+    const int rc0 = scan_assemble_now(ctx);
+    if (rc0) return rc0;
+  }
   if (weighting < 0 || weighting > 2) return invalid("unknown weighting kind");
   DeviceMap *m = get_map(ctx, map_id);
   if (bounded && !m) return invalid("unknown map id");
@@ -1514,9 +1569,9 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
   }
   // ... and the host's own copies of weights and factors (what the commit records; the device makes the same bits),
   // touched only once nothing can fail any more that would leave the scan before as the current one
+  // (those that nothing in front of the launch needs are made behind it, while the GPU runs: scan_record_finish)
   if (weighting == 0) {
     as.w_even = 1.0 / k;  // EvenSPW (:21-32)
-    ctx->h_weight.assign(k, as.w_even);
   } else if (weighting == 1) {
     ctx->h_weight.resize(k);
     for (int q = 0; q < k; ++q) ctx->h_weight[q] = sp.viny_f[kept[q]] * std::sqrt(r_[q]);
@@ -1530,16 +1585,12 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
     if (rc) return rc;
     double *w_ = st + 3 * c;
     std::memcpy(w_, sp.w.data(), sizeof(double) * k);
-    ctx->h_weight.assign(w_, w_ + k);
     as.h_weight = w_;
   }
   if (factor) {
     double *f_ = st + 2 * c;
     for (int q = 0; q < k; ++q) f_[q] = factor[kept[q]];
-    ctx->h_factor.assign(f_, f_ + k);
     as.h_factor = f_;
-  } else {
-    ctx->h_factor.assign(k, 1.0);
   }
   as.tab_cos = ctx->d_scan_tab;
   as.tab_sin = ctx->d_scan_tab + (size_t)ctx->scan_tab_cap;
@@ -1547,17 +1598,27 @@ int slamhip_scan_filter_upload(slamhip_ctx *ctx, int map_id, int n, const double
   as.stride = c;
   as.n = k;
   int turn = 0;
-  const double tot_w = weighting == 0 ? scan_total_weight_even(k, as.w_even) : scan_total_weight(ctx->h_weight.data(), k);
+  const double tot_w = weighting == 0   ? scan_total_weight_even(k, as.w_even)
+                       : weighting == 1 ? scan_total_weight(ctx->h_weight.data(), k)
+                                        : scan_total_weight(as.h_weight, k);
   const unsigned seq = scan_stage_turnover(ctx, k, c, tot_w, &turn);
-  SLAMHIP_CHECK(launch_scan_assemble(as, ctx->d_scan_pull_count, ctx->h_scan_pulled + turn, seq, ctx->stream));
-  rc = scan_stage_fork(ctx, turn);
-  if (rc) return rc;
   // the kept points' angles, for SLAMHIP_POSE_TRIG_RAW_EXACT: sp.angle[sp.kept[q]], written out when an exact call asks
   // (scan_angles_materialise); slamhip_scan_set_angles replaces them
   sp.kept.swap(kept);
   ctx->scan_angle_lazy = true;
+  slamhip_ctx::ScanPending &pend = ctx->scan_pending;
+  pend.as = as;
+  pend.turn = turn;
+  pend.seq = seq;
+  pend.weighting = weighting;
+  pend.record_due = true;
+  pend.active = true;
   return SLAMHIP_OK;
 }
+
+}  // namespace slamhip
+
+extern "C" {
 
 int slamhip_scan_set_angles(slamhip_ctx *ctx, int n, const double *angle) {
   if (!ctx || !angle) return invalid("bad arguments");

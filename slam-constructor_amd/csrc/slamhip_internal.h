@@ -359,6 +359,17 @@ struct slamhip_ctx {
   int scan_tab_cap = 0;
   long long scan_tab_uploads = 0;
   std::vector<double> h_weight, h_factor;  // host copies for GMapping carry-in fix-ups
+  // The raw scan between its two halves (slamhip::scan_filter_stage / scan_assemble_now).  `active`: the current scan
+  // is staged in pinned memory and recorded as the current one, but the scan block in HBM has not been written yet --
+  // whoever reads the block launches nothing before scan_assemble_now; a lone co-resident hill-climbing chain takes
+  // `as` into its own launch instead (HcChainArgs::raw) and ends the turn with scan_fused_done.  `record_due`: the host
+  // copies of weights / factors are still to be made (scan_record_finish: behind the launch, while the GPU runs).
+  struct ScanPending {
+    bool active = false, record_due = false;
+    slamhip::ScanAssembleArgs as{};
+    int turn = 0, weighting = 0;
+    unsigned seq = 0;
+  } scan_pending;
   // the libm-exact modes (exact_kernels.hip): the beam ANGLES of the current scan (slamhip_scan_set_angles, or the kept
   // angles of slamhip_scan_filter_upload) -- on the host until an exact scoring call needs them in HBM --, the
   // per-pose trig tables, the reference's one GMapping cache object on the device
@@ -412,6 +423,8 @@ struct slamhip_ctx {
   // slamhip_ctx_set_option: equivalent execution paths (defaults = what is measured)
   bool filter_chains = true, k6_batch_fast = true, k6_batch_key64 = false, resident_chains = true, tbm_plane = true;
   int inert_tail = 2;  // SLAMHIP_OPT_INERT_TAIL
+  bool raw_prologue = true;  // SLAMHIP_OPT_RAW_PROLOGUE
+  long long raw_prologue_matches = 0;  // SLAMHIP_OPT_RAW_PROLOGUE_MATCHES
   int k6_path = 0;
   // profiling: event pairs recorded around scoring launches, resolved lazily in profile_read
   bool profile = false;
@@ -431,6 +444,19 @@ inline bool scan_angles_known(const slamhip_ctx *ctx) {
 }
 // ... and has them in h_scan_angle (slamhip_api.cpp)
 void scan_angles_materialise(slamhip_ctx *ctx);
+// The raw scan's upload in two halves (slamhip_api.cpp; slamhip_scan_filter_upload is the two in a row).
+// scan_filter_stage: filter, weights, the staging buffer filled, the new scan recorded as the current one --
+// ctx->scan_pending.active unless the filter kept nothing.  scan_assemble_now: k_scan_assemble on the context's stream
+// and the second lane's wait, if the scan is still pending (else nothing): THE way the scan block gets written when no
+// chain does it -- the plain path and every fail-over call this one function.  scan_fused_done: a chain launched with
+// HcChainArgs::raw has reported its result -- every workgroup has read the staging buffer, the bookkeeping one has
+// written the block.  scan_record_finish: the host's copies of the scan's weights / factors, made behind the launch.
+int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, const double *angle, const int *is_occ,
+                      const double *factor, int trig_mode, double a_min, double a_max, double a_inc, const double pose[3],
+                      unsigned skip_rate, double max_range, int bounded, int weighting, int *kept_n, int *kept_idx);
+int scan_assemble_now(slamhip_ctx *ctx);
+int scan_fused_done(slamhip_ctx *ctx);
+void scan_record_finish(slamhip_ctx *ctx);
 // scoring target made of per-slot copy-on-write maps (tile_pool.h) instead of a bound dense window;
 // pose p reads the map of slot ctx->h_pose_slot[p]
 struct TiledTarget {
