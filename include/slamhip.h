@@ -278,7 +278,8 @@ int slamhip_scan_generate_host(int cell_model, int occ_kind, int variant, int wi
  * The two data-parallel parts of the many-to-many multi-resolution matcher (BF_M3RSM, Olson 2015):
  * M3RSMRescalableGridMap (src/core/scan_matchers/m3rsm_engine.h:17-131 over RescalableCachingGridMap,
  * src/core/maps/rescalable_caching_grid_map.h) and Match::prob_upper_bound (m3rsm_engine.h:156-180).  The best-first
- * engine (M3RSMEngine, :238-382) is not here.
+ * engine (M3RSMEngine, :238-382) runs on the host over them: slamhip_matcher_create_m3rsm below ("matchers"), which
+ * refines a whole layer of matches per launch with slamhip_pyramid_expand_matches (csrc/m3rsm.hip).
  *
  * LEVELS.  Over a bound dense map of model OCC, TBM or CREDIBILIST (the "fine" map, level 0) the pyramid keeps levels
  * 1 .. K, each an ORDINARY bound map with its own map id (first_level_map_id + k - 1), the fine map's cell model and
@@ -352,6 +353,33 @@ int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *pyr, const 
 int slamhip_pyramid_score_matches_device(slamhip_ctx *ctx, slamhip_pyramid *pyr, const slamhip_spe_cfg *cfg,
                                          const double base_pose[3], int n, const double *d_rotation, const double *d_rect,
                                          double *d_score_out, int *d_level_out);
+/* EXPAND.  The children of n parent matches (rotation[i], rect[i]) made on the device by the reference's refinement rule
+ * and bounded as above, in ONE launch (csrc/m3rsm.hip).  The children of a rectangle under `translation_step`
+ * (M3RSMEngine::next_best_match / branch, m3rsm_engine.h:318-357, and the matcher's five points,
+ * bf_multi_res_scan_matcher.h:55-64), with hb = less(step, right - left), vb = less(step, top - bot),
+ * less(a, b) = a < b + DBL_EPSILON (so a side equal to the step still branches) and
+ * c = (left + (right - left) / 2, bot + (top - bot) / 2):
+ *   hb and vb   4: (bot, c.y, left, c.x), (c.y, top, left, c.x), (bot, c.y, c.x, right), (c.y, top, c.x, right)
+ *   hb only     2: (bot, top, left, c.x), (bot, top, c.x, right)          vb only  2: (bot, c.y, ..), (c.y, top, ..)
+ *   neither, and not a point (right - left + top - bot > 0)
+ *               5: the points (y, y, x, x) at (left, bot), (left, top), (right, bot), (right, top) and c
+ *   a point, or a reversed rectangle: none.
+ * SLOT LAYOUT.  Every node has 5 child slots, so parent i owns S = 5 (depth 1), 30 (depth 2) or 155 (depth 3) slots,
+ * breadth first: slots [0, 5) are its children; slots [5, 30) its grandchildren, slot 5 + 5 a + b being child b of child
+ * a; slots [30, 155) the third generation, slot 30 + 25 a + 5 b + c being child c of child b of child a.  Slot s of parent
+ * i is entry i * S + s of the outputs: rect_out (4 doubles), score_out, level_out.  A slot without a node (its path
+ * meets a node with fewer children) holds a NaN rectangle, a NaN score and level -1.  Every child carries its parent's
+ * rotation.  score_out / level_out of a slot with a node are BIT-EQUAL to slamhip_pyramid_score_matches on
+ * (rotation[i], rect_out): both kernels run one scoring function.  Both sum orders; pose_trig DEVICE, or HOST with one
+ * sincos per parent.  SLAMHIP_ERR_INVALID: depth outside 1..3, a step that is not positive, values that are not finite.
+ * _device: everything in HBM, asynchronous on the context's stream, pose_trig DEVICE only. */
+int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *pyr, const slamhip_spe_cfg *cfg,
+                                   const double base_pose[3], int n, const double *rotation, const double *rect,
+                                   double translation_step, int depth, double *rect_out, double *score_out, int *level_out);
+int slamhip_pyramid_expand_matches_device(slamhip_ctx *ctx, slamhip_pyramid *pyr, const slamhip_spe_cfg *cfg,
+                                          const double base_pose[3], int n, const double *d_rotation, const double *d_rect,
+                                          double translation_step, int depth, double *d_rect_out, double *d_score_out,
+                                          int *d_level_out);
 
 /* ---------------------------------------------------------------- map update (kernel K6)
  * Replaces GridMapScanAdder::append_scan (src/core/maps/grid_map_scan_adders.h:54-75) with
@@ -541,6 +569,34 @@ int slamhip_matcher_create_hc(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg,
                               double rotation_delta, slamhip_matcher **out);
 int slamhip_matcher_create_bf(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const double range9[9],
                               slamhip_matcher **out);
+/* BruteForceMultiResolutionScanMatcher (bf_multi_res_scan_matcher.h, BF_M3RSM) over M3RSMEngine (m3rsm_engine.h:252-365):
+ * best-first branch and bound over the levels of `pyramid`.  The engine's loop -- std::priority_queue under
+ * Match::operator<, add_match's cut, the root layer, next_best_match, the five points of a box that no longer branches,
+ * the end at a top that is a point -- runs on the host (csrc/m3rsm_engine.cpp) and takes every score from a memo keyed by
+ * (rotation, rectangle).  A child the memo lacks starts a SUPER-STEP: the popped match and the next width - 1 unexpanded
+ * entries of the queue are expanded to `depth` generations by one slamhip_pyramid_expand_matches launch.  Scores are
+ * pure functions of their node, so the committed calls are the reference's for every width and depth.
+ *   cfg: a window OOPE (max / mean / overlap), the pyramid's OIE, pose_trig DEVICE or HOST.  With
+ *   SLAMHIP_SUM_SEQUENTIAL and HOST trig the match is the compiled reference's bit for bit -- delta, probability and
+ *   every call -- for scans under the cached trig provider; the default mode's scores differ by the sum order (~1e-13).
+ *   process_scan / process_raw_scan: map_id must be the pyramid's fine map; delta = (centre x, centre y, rotation) of
+ *   the winning point, prob = its bound; on_matching_end is the only observer event (the reference's matcher emits no
+ *   on_scan_test).  slamhip_matcher_stats: scorer_calls = the calls the reference would have made, poses_evaluated =
+ *   candidates scored on the GPU, launches = super-steps + the root launch.
+ * SLAMHIP_ERR_INVALID: a 1-cell or GMapping OOPE, an OIE that is not the pyramid's, a pyramid of another context, steps
+ * that are not positive; SLAMHIP_ERR_STATE from a match: the pyramid is stale (slamhip_pyramid_rebuild);
+ * SLAMHIP_ERR_UNSUPPORTED from a match: the bound on super-steps (2^20) was reached.  The pyramid must outlive the matcher. */
+int slamhip_matcher_create_m3rsm(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, slamhip_pyramid *pyramid,
+                                 double max_x_error, double max_y_error, double max_th_error, double angle_step,
+                                 double translation_step, slamhip_matcher **out);
+/* parents per expand launch (>= 1) and generations per parent (1..3); default 32, 3 -- the
+ * fastest point of the grid tools/m3rsm_ms.py measures.  (0, 0): no expand launches at
+ * all -- every popped match's children are split on the host and bounded by one slamhip_pyramid_score_matches launch, a
+ * round trip per pop: the route the speculation is measured against (tools/m3rsm_ms.py).  Same trace either way. */
+int slamhip_matcher_set_m3rsm_speculation(slamhip_matcher *m, int width, int depth);
+/* The committed scorer calls of the last match in the reference's order: row k of rows (room for cap rows of 7
+ * doubles) = rotation, bot, top, left, right, score, level; *n = how many there were (may exceed cap). */
+int slamhip_matcher_m3rsm_trace(slamhip_matcher *m, int cap, double *rows, int *n);
 int slamhip_matcher_destroy(slamhip_matcher *m);
 /* GridScanMatcher::reset_state (grid_scan_matcher.h:158) */
 int slamhip_matcher_reset_state(slamhip_matcher *m);

@@ -63,6 +63,8 @@ slamhip_map_render slamhip_gmapping_particle_map_render slamhip_render_cells
 slamhip_scan_gen_angles slamhip_scan_gen_libm_variant slamhip_map_generate_scans slamhip_scan_generate_host
 slamhip_pyramid_create slamhip_pyramid_destroy slamhip_pyramid_info slamhip_pyramid_rebuild slamhip_pyramid_refresh
 slamhip_pyramid_build_host slamhip_pyramid_score_matches slamhip_pyramid_score_matches_device
+slamhip_pyramid_expand_matches slamhip_pyramid_expand_matches_device slamhip_matcher_create_m3rsm
+slamhip_matcher_set_m3rsm_speculation slamhip_matcher_m3rsm_trace
 slamhip_scan_table_uploads slamhip_scan_download""".split()
 
 SHARD_ID_BYTES = 128
@@ -285,6 +287,11 @@ def load(testing=False):
                                              C.POINTER(C.c_size_t)]
     L.slamhip_pyramid_score_matches.argtypes = [vp, vp, C.POINTER(SpeCfg), _dp, i, _dp, _dp, _dp, _ip]
     L.slamhip_pyramid_score_matches_device.argtypes = [vp, vp, C.POINTER(SpeCfg), _dp, i, vp, vp, vp, vp]
+    L.slamhip_pyramid_expand_matches.argtypes = [vp, vp, C.POINTER(SpeCfg), _dp, i, _dp, _dp, d, i, _dp, _dp, _ip]
+    L.slamhip_pyramid_expand_matches_device.argtypes = [vp, vp, C.POINTER(SpeCfg), _dp, i, vp, vp, d, i, vp, vp, vp]
+    L.slamhip_matcher_create_m3rsm.argtypes = [vp, C.POINTER(SpeCfg), vp, d, d, d, d, d, C.POINTER(vp)]
+    L.slamhip_matcher_set_m3rsm_speculation.argtypes = [vp, i, i]
+    L.slamhip_matcher_m3rsm_trace.argtypes = [vp, i, _dp, _ip]
     _libs[testing] = L
     return L
 
@@ -903,6 +910,11 @@ class Matcher:
         elif kind == "BF":
             p = _f64(params)
             _check(self.L.slamhip_matcher_create_bf(ctx.h, C.byref(cfg), _d(p), C.byref(h)))
+        elif kind == "BF_M3RSM":
+            # params: (pyramid, max_x_error, max_y_error, max_th_error, angle_step, translation_step)
+            self.pyramid = params[0]  # (kept alive: the matcher reads it at every match)
+            _check(self.L.slamhip_matcher_create_m3rsm(ctx.h, C.byref(cfg), self.pyramid.h, *[float(v) for v in params[1:6]],
+                                                       C.byref(h)))
         else:
             raise ValueError(kind)
         self.h = h
@@ -1087,6 +1099,19 @@ class Matcher:
                     kernels_launched=kl.value, steps_rescored=rs.value, build_us=t[0].value, stage_us=t[1].value, score_us=t[2].value,
                     replay_us=t[3].value, calls_closed_form=tc.value)
 
+    def set_m3rsm_speculation(self, width, depth):
+        """BF_M3RSM: parents per expand launch and generations per parent (slamhip_matcher_set_m3rsm_speculation)."""
+        _check(self.L.slamhip_matcher_set_m3rsm_speculation(self.h, int(width), int(depth)))
+
+    def m3rsm_trace(self):
+        """BF_M3RSM: the committed scorer calls of the last match in the reference's order, [n, 7] = rotation, bot, top,
+        left, right, score, level."""
+        n = C.c_int(0)
+        _check(self.L.slamhip_matcher_m3rsm_trace(self.h, 0, None, C.byref(n)))
+        rows = np.zeros((n.value, 7))
+        _check(self.L.slamhip_matcher_m3rsm_trace(self.h, n.value, _d(rows), C.byref(n)))
+        return rows
+
     def resident_stats(self):
         """Matches launched in the co-resident form, and how many of them gave up and were redone by the kernel chain."""
         a, b = C.c_longlong(), C.c_longlong()
@@ -1222,6 +1247,23 @@ class Pyramid:
         _check(self.L.slamhip_pyramid_score_matches(self.ctx.h, self.h, C.byref(cfg), _d(base), rotation.size, _d(rotation),
                                                     _d(rect), _d(scores), levels.ctypes.data_as(_ip)))
         return scores, levels
+
+    def expand_matches(self, cfg, base_pose, rotation, rect, translation_step, depth=1):
+        """The children of every parent (rotation[i], rect[i]) to `depth` generations, made and bounded in one launch
+        (slamhip_pyramid_expand_matches): (rects[n, S, 4], scores[n, S], levels[n, S]) with S = 5, 30 or 155 slots per
+        parent, breadth first; a slot without a node holds NaN / NaN / -1."""
+        rotation = _f64(rotation).ravel()
+        rect = _f64(rect).reshape(-1, 4)
+        if rect.shape[0] != rotation.size:
+            raise ValueError("one rectangle per rotation")
+        slots = {1: 5, 2: 30, 3: 155}.get(int(depth), 1)  # (a bad depth is the library's to refuse)
+        base = _f64(base_pose).ravel()
+        n = rotation.size
+        rects, scores, levels = np.zeros((n, slots, 4)), np.zeros((n, slots)), np.zeros((n, slots), np.int32)
+        _check(self.L.slamhip_pyramid_expand_matches(self.ctx.h, self.h, C.byref(cfg), _d(base), n, _d(rotation), _d(rect),
+                                                     float(translation_step), int(depth), _d(rects), _d(scores),
+                                                     levels.ctypes.data_as(_ip)))
+        return rects, scores, levels
 
     def score_matches_device(self, cfg, base_pose, n, d_rotation_ptr, d_rect_ptr, d_scores_ptr, d_levels_ptr):
         base = _f64(base_pose).ravel()

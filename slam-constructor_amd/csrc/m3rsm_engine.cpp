@@ -1,0 +1,244 @@
+// m3rsm_engine.cpp -- see m3rsm_engine.h.  No HIP in here: compiles with any C++17 compiler (-ffp-contract=off).
+#include "m3rsm_engine.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <queue>
+#include <unordered_map>
+
+namespace slamhip {
+namespace m3rsm {
+namespace {
+
+// are_equal / less_or_equal of math_utils.h:15-39
+bool are_equal(double a, double b) {
+  const double eps_scale = std::max(1.0, std::max(std::abs(a), std::abs(b)));
+  return std::abs(a - b) <= 1e-7 * eps_scale;
+}
+bool less_or_equal(double a, double b) { return are_equal(a, b) || less(a, b); }
+
+struct Match {
+  double prob, rotation;
+  Rect rect;
+  double abs_rotation, drift_amount;
+  bool finest() const { return drift_amount <= 0; }
+  // true if this match is LESS preferable (Match::operator<)
+  bool operator<(const Match &that) const {
+    if (!are_equal(prob, that.prob)) return less(prob, that.prob);
+    if (!are_equal(drift_amount, that.drift_amount)) return drift_amount > that.drift_amount;
+    return abs_rotation > that.abs_rotation;
+  }
+};
+
+Match make_match(double rotation, const Rect &r, double prob) {
+  return Match{prob, rotation, r, std::abs(rotation), (r.right - r.left) + (r.top - r.bot)};
+}
+
+struct Key {
+  uint64_t w[5];
+  bool operator==(const Key &o) const { return std::memcmp(w, o.w, sizeof(w)) == 0; }
+};
+struct KeyHash {
+  size_t operator()(const Key &k) const {
+    uint64_t h = 0x9e3779b97f4a7c15ull;
+    for (uint64_t v : k.w) {
+      h ^= v + 0x9e3779b97f4a7c15ull + (h << 6) + (h >> 2);
+      h *= 0xff51afd7ed558ccdull;
+      h ^= h >> 32;
+    }
+    return (size_t)h;
+  }
+};
+Key key_of(double rotation, const Rect &r) {
+  const double v[5] = {rotation, r.bot, r.top, r.left, r.right};
+  Key k;
+  std::memcpy(k.w, v, sizeof(v));
+  return k;
+}
+struct Bound {
+  double score;
+  int level;
+};
+
+// std::priority_queue, plus a look at the heap it keeps (the speculation reads ahead in it without popping)
+struct Queue : std::priority_queue<Match> {
+  const std::vector<Match> &heap() const { return c; }
+};
+
+struct Engine {
+  const Config &cfg;
+  const ExpandFn &expand;
+  Result *res;
+  std::vector<Call> *trace;
+  Queue matches;
+  double best_finest = 0.0;
+  std::unordered_map<Key, Bound, KeyHash> memo;
+  std::vector<double> p_rot, p_rect, s_rect, s_score;
+  std::vector<int> s_level;
+  std::vector<size_t> front;
+
+  // M3RSMEngine::add_match with max_finest_prob_diff = 0, after the call has been committed to the trace
+  void commit(double rotation, const Rect &r, const Bound &b) {
+    ++res->scorer_calls;
+    if (trace) trace->push_back(Call{rotation, r, b.score, b.level});
+    Match m = make_match(rotation, r, b.score);
+    if (m.prob < best_finest) return;
+    if (m.finest()) best_finest = std::max(best_finest, m.prob - 0.0);
+    matches.push(std::move(m));
+  }
+
+  bool expanded(const Match &m) const {
+    Rect kids[kMaxChildren];
+    const int n = children(m.rect, cfg.translation_step, kids);
+    return n == 0 || memo.count(key_of(m.rotation, kids[0])) != 0;
+  }
+
+  // one expand call: `first` and the next width - 1 entries of the queue that have children nobody has scored yet
+  int super_step(const Match &first) {
+    if (res->super_steps >= cfg.max_super_steps) return kErrSuperSteps;
+    p_rot.clear();
+    p_rect.clear();
+    auto add = [&](const Match &m) {
+      p_rot.push_back(m.rotation);
+      p_rect.insert(p_rect.end(), {m.rect.bot, m.rect.top, m.rect.left, m.rect.right});
+    };
+    add(first);
+    if (cfg.width > 1 && !matches.empty()) {
+      // the queue's entries from the top down, without popping: a best-first walk over the binary heap (an entry is not
+      // better than its parent), through a small heap of positions.  Which entries ride along changes no result.
+      const std::vector<Match> &heap = matches.heap();
+      const auto worse = [&heap](size_t a, size_t b) { return heap[a] < heap[b]; };
+      front.assign(1, 0);
+      long long looked = 0;
+      const long long look_limit = 4ll * cfg.width + 64;  // (points and expanded entries are passed over, not for ever)
+      while ((int)p_rot.size() < cfg.width && !front.empty() && looked < look_limit) {
+        std::pop_heap(front.begin(), front.end(), worse);
+        const size_t i = front.back();
+        front.pop_back();
+        const Match &m = heap[i];
+        if (!m.finest() && !expanded(m)) add(m);
+        for (size_t c = 2 * i + 1; c <= 2 * i + 2 && c < heap.size(); ++c) {
+          front.push_back(c);
+          std::push_heap(front.begin(), front.end(), worse);
+        }
+        ++looked;
+      }
+    }
+    const int n = (int)p_rot.size(), slots = slots_of(cfg.depth);
+    const size_t n_out = (size_t)n * slots;
+    s_rect.resize(4 * n_out);
+    s_score.resize(n_out);
+    s_level.resize(n_out);
+    const int rc = expand(n, p_rot.data(), p_rect.data(), cfg.depth, s_rect.data(), s_score.data(), s_level.data());
+    ++res->super_steps;
+    ++res->launches;
+    if (rc) {
+      res->callback_rc = rc;
+      return kErrCallback;
+    }
+    for (int i = 0; i < n; ++i)
+      for (int s = 0; s < slots; ++s) {
+        const size_t g = (size_t)i * slots + s;
+        if (std::isnan(s_rect[4 * g])) continue;  // no node in this slot
+        ++res->scored;
+        const Rect r{s_rect[4 * g], s_rect[4 * g + 1], s_rect[4 * g + 2], s_rect[4 * g + 3]};
+        memo[key_of(p_rot[i], r)] = Bound{s_score[g], s_level[g]};
+      }
+    return kOk;
+  }
+
+  // the children of the popped match, committed in the reference's order
+  int branch(const Match &m) {
+    Rect kids[kMaxChildren];
+    const int n = children(m.rect, cfg.translation_step, kids);
+    for (int c = 0; c < n; ++c) {
+      auto it = memo.find(key_of(m.rotation, kids[c]));
+      if (it == memo.end()) {
+        const int rc = super_step(m);
+        if (rc) return rc;
+        it = memo.find(key_of(m.rotation, kids[c]));
+        if (it == memo.end()) return kErrScorer;
+      }
+      commit(m.rotation, kids[c], it->second);
+    }
+    return kOk;
+  }
+};
+
+}  // namespace
+
+void root_candidates(const Config &cfg, std::vector<double> *rotation, std::vector<Rect> *rect) {
+  rotation->clear();
+  rect->clear();
+  const Rect empty{0, 0, 0, 0}, entire{-cfg.max_y_error, cfg.max_y_error, -cfg.max_x_error, cfg.max_x_error};
+  const double sector = 2 * cfg.max_th_error;
+  double drift = 0;
+  while (less_or_equal(2 * drift, sector)) {
+    // std::set<double>{drift, -drift}: ascending, and -0 is 0 (the first of the two stays)
+    const double rots[2] = {-drift, drift};
+    for (int k = (drift == 0 ? 1 : 0); k < 2; ++k) {
+      rotation->push_back(rots[k]);
+      rect->push_back(empty);
+      rotation->push_back(rots[k]);
+      rect->push_back(entire);
+    }
+    drift += cfg.angle_step;
+  }
+}
+
+int run(const Config &cfg, const ScoreFn &score_roots, const ExpandFn &expand, Result *result, std::vector<Call> *trace) {
+  *result = Result{};
+  if (trace) trace->clear();
+  if (!(cfg.angle_step > 0) || !(cfg.translation_step > 0) || !(cfg.max_x_error >= 0) || !(cfg.max_y_error >= 0) ||
+      !(cfg.max_th_error >= 0) || !std::isfinite(cfg.max_x_error) || !std::isfinite(cfg.max_y_error) ||
+      !std::isfinite(cfg.max_th_error) || !std::isfinite(cfg.angle_step) || !std::isfinite(cfg.translation_step) ||
+      cfg.width < 1 || cfg.depth < 1 || cfg.depth > kMaxDepth || cfg.max_super_steps < 1)
+    return kErrInvalid;
+  Engine e{cfg, expand, result, trace};
+  e.memo.reserve(1 << 16);
+  {
+    std::vector<double> rot;
+    std::vector<Rect> rect;
+    root_candidates(cfg, &rot, &rect);
+    const int n = (int)rot.size();
+    std::vector<double> flat(4 * (size_t)n), score(n);
+    std::vector<int> level(n);
+    for (int i = 0; i < n; ++i) {
+      flat[4 * i] = rect[i].bot;
+      flat[4 * i + 1] = rect[i].top;
+      flat[4 * i + 2] = rect[i].left;
+      flat[4 * i + 3] = rect[i].right;
+    }
+    const int rc = score_roots(n, rot.data(), flat.data(), score.data(), level.data());
+    ++result->launches;
+    result->scored += n;
+    if (rc) {
+      result->callback_rc = rc;
+      return kErrCallback;
+    }
+    for (int i = 0; i < n; ++i) e.commit(rot[i], rect[i], Bound{score[i], level[i]});
+  }
+  // BruteForceMultiResolutionScanMatcher::process_scan's loop around M3RSMEngine::next_best_match
+  for (;;) {
+    if (e.matches.empty()) return kErrNoMatch;
+    const Match best = e.matches.top();
+    e.matches.pop();
+    if (best.finest()) {
+      const double hside = best.rect.right - best.rect.left, vside = best.rect.top - best.rect.bot;
+      result->delta[0] = best.rect.left + hside / 2;
+      result->delta[1] = best.rect.bot + vside / 2;
+      result->delta[2] = best.rotation;
+      result->prob = best.prob;
+      return kOk;
+    }
+    // (children() is next_best_match's branching decision and, for a box that no longer branches, the five points)
+    ++result->branching_pops;
+    const int rc = e.branch(best);
+    if (rc) return rc;
+  }
+}
+
+}  // namespace m3rsm
+}  // namespace slamhip

@@ -23,31 +23,10 @@
 
 #include "kernel_pick.h"
 #include "map_pyramid_device.h"
+#include "map_pyramid_score.h"
 #include "score_device.h"
 
-struct slamhip_pyramid {
-  slamhip_ctx *ctx = nullptr;  // null once the context has gone
-  int fine_id = -1, first_id = -1, oie = 0;
-  int cell_model = 0;
-  // the fine map the levels were planned for: a re-bound (grown) fine map needs slamhip_pyramid_rebuild
-  int fine_w = 0, fine_h = 0, fine_ox = 0, fine_oy = 0;
-  const double *fine_payload = nullptr;
-  slamhip::pyr::Plan plan{};
-  std::vector<int *> d_coord;               // per level: the fine coordinate of every cell's winner (x, y)
-  std::vector<const double *> lv_payload;   // per level: the payload the table below points at
-  slamhip::MapView *d_views = nullptr;      // plan.n + 1 views, the fine map first
-  // slamhip_pyramid_score_matches' staging in HBM: rotation | rect | sin, cos per candidate; scores; levels; terms
-  double *d_in = nullptr, *d_scores = nullptr, *d_terms = nullptr;
-  int *d_levels = nullptr;
-  int in_cap = 0;
-  size_t terms_cap = 0;
-};
-
 namespace slamhip {
-namespace {
-
-constexpr int kPyrThreads = 256;
-constexpr int kMaxGridY = 65535;
 
 int pyr_invalid(const char *msg) {
   set_error(msg);
@@ -57,6 +36,10 @@ int pyr_state(const char *msg) {
   set_error(msg);
   return SLAMHIP_ERR_STATE;
 }
+
+namespace {
+
+constexpr int kMaxGridY = 65535;
 
 DeviceMap *bound_map(slamhip_ctx *ctx, int map_id) {
   if (!ctx || map_id < 0 || map_id >= (int)ctx->maps.size() || !ctx->maps[map_id].bound) return nullptr;
@@ -213,77 +196,12 @@ int check_fresh(const slamhip_pyramid *p) {
 }
 
 // ---- score ---------------------------------------------------------------------------------------
-struct MatchArgs {
-  const MapView *levels;  // n_levels views, the fine map first
-  int n_levels;
-  ScanView scan;
-  const double *rotation;  // n
-  const double *rect;      // n x (bot, top, left, right)
-  const double *pose_sc;   // optional n x (sin, cos) of rotation + heading from the host; null = device sincos
-  double base[3];
-  double *scores;
-  int *level_out;
-  double *terms;  // beam-order sum only: n x scan.n
-  int n, oie, oope;
-};
-
 template <int MODEL>
 __global__ __launch_bounds__(kPyrThreads) void k_pyr_score(MatchArgs a) {
   __shared__ double s_trig[2];
   __shared__ double s_part[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int i = blockIdx.x;
-  const int n = a.scan.n;
-  const double bot = a.rect[4 * i], top = a.rect[4 * i + 1], left = a.rect[4 * i + 2], right = a.rect[4 * i + 3];
-  const double vside = top - bot, hside = right - left;
-  // (a rectangle that is no rectangle -- NaN, infinite or reversed -- has no level and no window: NaN, level -1)
-  if (!(vside >= 0.0 && hside >= 0.0 && vside < __builtin_inf() && hside < __builtin_inf())) {
-    if (t == 0) {
-      a.scores[i] = __builtin_nan("");
-      a.level_out[i] = -1;
-    }
-    return;
-  }
-  // RescalableCachingGridMap::rescale(std::max(vside, hside)): the first level whose scale holds the target
-  const double target = vside < hside ? hside : vside;
-  int lv = 0;
-  while (lv < a.n_levels - 1 && !(target <= a.levels[lv].scale)) ++lv;
-  const MapView map = a.levels[lv];
-  // LightWeightRectangle::center() added to the pose
-  const double x = a.base[0] + (left + hside / 2), y = a.base[1] + (bot + vside / 2);
-  if (t == 0) {
-    double sn, cs;
-    if (a.pose_sc) {
-      sn = a.pose_sc[2 * i];
-      cs = a.pose_sc[2 * i + 1];
-    } else {
-      sincos(a.rotation[i] + a.base[2], &sn, &cs);
-    }
-    s_trig[0] = sn;
-    s_trig[1] = cs;
-  }
-  __syncthreads();
-  const double sn = s_trig[0], cs = s_trig[1];
-  const double half_v = (top - bot) / 2, half_h = (right - left) / 2;
-  double acc = 0.0;
-  for (int b = t; b < n; b += kPyrThreads) {
-    const double ca = a.scan.cos_a[b], sa = a.scan.sin_a[b], r = a.scan.range[b];
-    const double c = cs * ca - sn * sa;
-    const double s = sn * ca + cs * sa;
-    const double ox = x + r * c, oy = y + r * s;
-    const double pr = window_probability<MODEL>(map, a.oie, a.oope, half_v, half_h, ox, oy);
-    const double term = pr * a.scan.weight[b] * a.scan.factor[b];
-    if (a.terms) a.terms[(size_t)i * n + b] = term;
-    acc = acc + term;
-  }
-  acc = wave_xor_sum(acc);
-  if (lane == 0) s_part[wave] = acc;
-  __syncthreads();
-  if (t == 0) {
-    const double total = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-    a.scores[i] = (a.scan.tot_w == 0.0) ? __builtin_nan("") : total / a.scan.tot_w;
-    a.level_out[i] = lv;
-  }
+  const size_t i = blockIdx.x;
+  pyr_score_one<MODEL>(a, i, i, a.rect[4 * i], a.rect[4 * i + 1], a.rect[4 * i + 2], a.rect[4 * i + 3], s_trig, s_part);
 }
 
 // the reference's beam-order sum over the terms (k_sum_sequential's loop), one lane per candidate that has a level
@@ -310,6 +228,43 @@ int check_score_cfg(const slamhip_pyramid *p, const slamhip_spe_cfg *cfg) {
 int queue_score(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base[3], int n, const double *d_rotation,
                 const double *d_rect, const double *d_pose_sc, double *d_scores, int *d_levels) {
   slamhip_ctx *ctx = p->ctx;
+  MatchArgs a;
+  int rc = pyr_fill_args(p, cfg, base, (size_t)n, &a);
+  if (rc) return rc;
+  a.rotation = d_rotation;
+  a.rect = d_rect;
+  a.pose_sc = d_pose_sc;
+  a.scores = d_scores;
+  a.level_out = d_levels;
+  a.n = n;
+  ProfilePairGuard prof;
+  rc = prof.open(ctx, ctx->stream, 0);
+  if (rc) return rc;
+  typedef void (*Kernel)(MatchArgs);
+  const Kernel kernel = pick_cell_model(p->cell_model, [](auto m) -> Kernel { return k_pyr_score<decltype(m)::value>; });
+  SLAMHIP_CHECK(launch_kernel(kernel, dim3(n), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
+  if (a.terms) {
+    rc = pyr_launch_sum_sequential(a, (size_t)n, ctx->stream);
+    if (rc) return rc;
+  }
+  rc = prof.close();
+  if (rc) return rc;
+  if (ctx->profile) {
+    ctx->prof_launches += 1;
+    ctx->prof_units += (long long)n * a.scan.n;
+  }
+  return SLAMHIP_OK;
+}
+
+}  // namespace
+
+int pyr_check_fresh(const slamhip_pyramid *p) { return check_fresh(p); }
+int pyr_check_score_cfg(const slamhip_pyramid *p, const slamhip_spe_cfg *cfg) { return check_score_cfg(p, cfg); }
+
+// what every bound-scoring launch shares: the level table, the context's current scan, the base pose, the OOPE / OIE and,
+// for the beam-order sum, room for n_out x scan.n terms
+int pyr_fill_args(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base[3], size_t n_out, MatchArgs *out) {
+  slamhip_ctx *ctx = p->ctx;
   if (ctx->scan_n <= 0) return pyr_state("no scan uploaded");
   MatchArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -323,18 +278,11 @@ int queue_score(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double bas
   a.scan.factor = ctx->scan_ptr + 4 * c;
   a.scan.n = ctx->scan_n;
   a.scan.tot_w = ctx->scan_tot_w;
-  a.rotation = d_rotation;
-  a.rect = d_rect;
-  a.pose_sc = d_pose_sc;
   for (int k = 0; k < 3; ++k) a.base[k] = base[k];
-  a.scores = d_scores;
-  a.level_out = d_levels;
-  a.n = n;
   a.oie = cfg->oie;
   a.oope = cfg->oope;
-  const bool seq = cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL;
-  if (seq) {
-    const size_t need = (size_t)n * ctx->scan_n;
+  if (cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL) {
+    const size_t need = n_out * (size_t)ctx->scan_n;
     if (need > p->terms_cap) {
       SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
       if (p->d_terms) (void)hipFree(p->d_terms);
@@ -345,36 +293,35 @@ int queue_score(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double bas
     }
     a.terms = p->d_terms;
   }
-  ProfilePairGuard prof;
-  int rc = prof.open(ctx, ctx->stream, 0);
-  if (rc) return rc;
-  typedef void (*Kernel)(MatchArgs);
-  const Kernel kernel = pick_cell_model(p->cell_model, [](auto m) -> Kernel { return k_pyr_score<decltype(m)::value>; });
-  SLAMHIP_CHECK(launch_kernel(kernel, dim3(n), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
-  if (seq)
-    SLAMHIP_CHECK(launch_kernel(k_pyr_sum_sequential, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, nullptr, nullptr,
-                                (const double *)a.terms, (const int *)d_levels, n, a.scan.n, a.scan.tot_w, d_scores));
-  rc = prof.close();
-  if (rc) return rc;
-  if (ctx->profile) {
-    ctx->prof_launches += 1;
-    ctx->prof_units += (long long)n * a.scan.n;
-  }
+  *out = a;
   return SLAMHIP_OK;
 }
 
-}  // namespace
+int pyr_launch_sum_sequential(const MatchArgs &a, size_t n_out, hipStream_t stream) {
+  SLAMHIP_CHECK(launch_kernel(k_pyr_sum_sequential, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, stream, nullptr, nullptr,
+                              (const double *)a.terms, (const int *)a.level_out, (int)n_out, a.scan.n, a.scan.tot_w, a.scores));
+  return SLAMHIP_OK;
+}
+
+void pyr_free_staging(slamhip_pyramid *p) {
+  if (p->d_in) (void)hipFree(p->d_in);
+  if (p->d_scores) (void)hipFree(p->d_scores);
+  if (p->d_levels) (void)hipFree(p->d_levels);
+  if (p->d_terms) (void)hipFree(p->d_terms);
+  if (p->d_x_in) (void)hipFree(p->d_x_in);
+  if (p->d_x_out) (void)hipFree(p->d_x_out);
+  if (p->h_x) (void)hipHostFree(p->h_x);
+  p->d_in = p->d_scores = p->d_terms = p->d_x_in = p->d_x_out = p->h_x = nullptr;
+  p->d_levels = nullptr;
+  p->in_cap = p->x_parent_cap = 0;
+  p->terms_cap = p->x_slot_cap = 0;
+}
 
 void pyramids_release(slamhip_ctx *ctx) {
   for (void *v : ctx->pyramids) {
     slamhip_pyramid *p = static_cast<slamhip_pyramid *>(v);
     free_levels(p, false);  // (the context frees its maps itself)
-    if (p->d_in) (void)hipFree(p->d_in);
-    if (p->d_scores) (void)hipFree(p->d_scores);
-    if (p->d_levels) (void)hipFree(p->d_levels);
-    if (p->d_terms) (void)hipFree(p->d_terms);
-    p->d_in = p->d_scores = p->d_terms = nullptr;
-    p->d_levels = nullptr;
+    pyr_free_staging(p);
     p->ctx = nullptr;
   }
   ctx->pyramids.clear();
@@ -409,10 +356,7 @@ int slamhip_pyramid_destroy(slamhip_pyramid *p) {
   if (p->ctx) {
     slamhip_ctx *ctx = p->ctx;
     free_levels(p, true);
-    if (p->d_in) (void)hipFree(p->d_in);
-    if (p->d_scores) (void)hipFree(p->d_scores);
-    if (p->d_levels) (void)hipFree(p->d_levels);
-    if (p->d_terms) (void)hipFree(p->d_terms);
+    pyr_free_staging(p);
     ctx->pyramids.erase(std::remove(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)p), ctx->pyramids.end());
   }
   delete p;

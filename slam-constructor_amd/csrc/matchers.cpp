@@ -9,6 +9,8 @@
 #include "bf_device.h"
 #include "hc_chain_device.h"
 #include "hc_shape.h"
+#include "m3rsm_engine.h"
+#include "map_pyramid_score.h"
 #include "mc_chain_device.h"
 #include "matchers.h"
 #include "resident_policy.h"
@@ -230,6 +232,16 @@ struct slamhip_matcher {
     unsigned seq = 0;
     std::vector<double> scores_host;
   } bf;
+  // ---- the multi-resolution matcher (BF_M3RSM): the best-first engine of m3rsm_engine.h over a pyramid's expand launches
+  struct M3rsm {
+    slamhip_pyramid *pyr = nullptr;  // the caller's; must outlive the matcher's matches
+    slamhip::m3rsm::Config cfg;
+    slamhip::m3rsm::Result res;
+    std::vector<slamhip::m3rsm::Call> trace;  // the committed calls of the last match
+    bool per_pop = false;  // no expand launches: a slamhip_pyramid_score_matches launch per popped match
+  };
+  bool is_m3rsm = false;
+  std::unique_ptr<M3rsm> m3;
 };
 
 using namespace slamhip;
@@ -1644,9 +1656,147 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
   return lone_chain_report(m, h, launched, a.scan.n, t0, init_pose, out_delta, out_prob);
 }
 
+// ---- the multi-resolution matcher ------------------------------------------------------------------
+// BruteForceMultiResolutionScanMatcher::process_scan: the engine's loop on the host, its scores from the pyramid -- the
+// root layer in one slamhip_pyramid_score_matches launch, everything below it in expand launches (m3rsm.hip), one per
+// super-step.  on_matching_end is the one event the reference's matcher emits.
+int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3], double *out_prob) {
+  slamhip_matcher::M3rsm &s = *m->m3;
+  slamhip_ctx *ctx = m->ctx;
+  m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
+  s.trace.clear();
+  s.res = m3rsm::Result{};
+  if (std::find(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)s.pyr) == ctx->pyramids.end())
+    return invalid_arg("the matcher's pyramid has been destroyed");
+  int rc = pyr_check_fresh(s.pyr);
+  if (rc) return rc;
+  if (map_id != s.pyr->fine_id) return invalid_arg("map_id must be the pyramid's fine map");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(init_pose[k])) return invalid_arg("the initial pose is not finite");
+  rc = scan_assemble_now(ctx);  // (a raw scan whose block is still to be assembled)
+  if (rc) return rc;
+  const double t0 = MatchJob::now_us();
+  const m3rsm::ScoreFn roots = [&](int n, const double *rot, const double *rect, double *score, int *level) {
+    return slamhip_pyramid_score_matches(ctx, s.pyr, &m->cfg, init_pose, n, rot, rect, score, level);
+  };
+  const m3rsm::ExpandFn expand = [&](int n, const double *rot, const double *rect, int depth, double *slot_rect,
+                                     double *slot_score, int *slot_level) {
+    return slamhip_pyramid_expand_matches(ctx, s.pyr, &m->cfg, init_pose, n, rot, rect, s.cfg.translation_step, depth,
+                                          slot_rect, slot_score, slot_level);
+  };
+  // without the expand kernel (slamhip_matcher_set_m3rsm_speculation(m, 0, 0)): the popped match alone, its children
+  // split on the host and bounded by one slamhip_pyramid_score_matches launch -- a round trip per pop
+  const m3rsm::ExpandFn per_pop = [&](int n, const double *rot, const double *rect, int, double *slot_rect, double *slot_score,
+                                      int *slot_level) {
+    const m3rsm::Rect parent{rect[0], rect[1], rect[2], rect[3]};
+    m3rsm::Rect kids[m3rsm::kMaxChildren] = {};
+    const int nk = n == 1 ? m3rsm::children(parent, s.cfg.translation_step, kids) : 0;
+    double k_rot[m3rsm::kMaxChildren], k_rect[4 * m3rsm::kMaxChildren];
+    for (int c = 0; c < m3rsm::kMaxChildren; ++c) {
+      k_rot[c] = rot[0];
+      const m3rsm::Rect &r = kids[c < nk ? c : 0];
+      const double nan = std::numeric_limits<double>::quiet_NaN();
+      const double v[4] = {c < nk ? r.bot : nan, c < nk ? r.top : nan, c < nk ? r.left : nan, c < nk ? r.right : nan};
+      for (int q = 0; q < 4; ++q) k_rect[4 * c + q] = slot_rect[4 * c + q] = v[q];
+      slot_score[c] = nan;
+      slot_level[c] = -1;
+    }
+    return nk ? slamhip_pyramid_score_matches(ctx, s.pyr, &m->cfg, init_pose, nk, k_rot, k_rect, slot_score, slot_level) : 0;
+  };
+  m3rsm::Config run_cfg = s.cfg;
+  if (s.per_pop) run_cfg.width = run_cfg.depth = 1;
+  const int erc = m3rsm::run(run_cfg, roots, s.per_pop ? per_pop : expand, &s.res, &s.trace);
+  m->t_stage_us = 0;
+  m->t_score_us = MatchJob::now_us() - t0;
+  m->job.scorer_calls = s.res.scorer_calls;
+  m->job.poses_evaluated = s.res.scored;
+  m->job.launches = s.res.launches;
+  switch (erc) {
+    case m3rsm::kOk: break;
+    case m3rsm::kErrCallback: return s.res.callback_rc;
+    case m3rsm::kErrSuperSteps:
+      set_error("the multi-resolution match reached its bound on super-steps");
+      return SLAMHIP_ERR_UNSUPPORTED;
+    case m3rsm::kErrNoMatch:  // (no candidate left: nothing is accepted, as for a scan with no point)
+      out_delta[0] = out_delta[1] = out_delta[2] = 0.0;
+      *out_prob = std::numeric_limits<double>::quiet_NaN();
+      return SLAMHIP_OK;
+    default:
+      set_error("internal: the multi-resolution engine failed (an expand launch did not deliver a child)");
+      return SLAMHIP_ERR_STATE;
+  }
+  for (int k = 0; k < 3; ++k) out_delta[k] = s.res.delta[k];
+  *out_prob = s.res.prob;
+  if (m->has_obs && m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, out_delta, s.res.prob);
+  return SLAMHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int slamhip_matcher_create_m3rsm(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, slamhip_pyramid *pyramid, double max_x_error,
+                                 double max_y_error, double max_th_error, double angle_step, double translation_step,
+                                 slamhip_matcher **out) {
+  if (!ctx || !cfg || !pyramid || !out) return invalid_arg("null argument");
+  *out = nullptr;
+  if (pyramid->ctx != ctx) return invalid_arg("the pyramid belongs to another context");
+  // (a window OOPE -- not the 1-cell or the GMapping one --, the pyramid's OIE, a known sum order)
+  int rc = pyr_check_score_cfg(pyramid, cfg);
+  if (rc) return rc;
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
+    return invalid_arg("pose_trig: DEVICE or HOST (bounds know no per-beam raw trigonometry)");
+  if (!(angle_step > 0) || !(translation_step > 0) || !std::isfinite(angle_step) || !std::isfinite(translation_step))
+    return invalid_arg("the rotation and translation steps must be positive and finite");
+  if (!(max_x_error >= 0) || !(max_y_error >= 0) || !(max_th_error >= 0) || !std::isfinite(max_x_error) ||
+      !std::isfinite(max_y_error) || !std::isfinite(max_th_error))
+    return invalid_arg("the lookup limits must be finite and not negative");
+  rc = make_matcher(ctx, cfg, nullptr, 0, out);
+  if (rc) return rc;
+  slamhip_matcher *m = *out;
+  m->is_m3rsm = true;
+  m->m3 = std::make_unique<slamhip_matcher::M3rsm>();
+  m->m3->pyr = pyramid;
+  m3rsm::Config &c = m->m3->cfg;
+  c.max_x_error = max_x_error;
+  c.max_y_error = max_y_error;
+  c.max_th_error = max_th_error;
+  c.angle_step = angle_step;
+  c.translation_step = translation_step;
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_set_m3rsm_speculation(slamhip_matcher *m, int width, int depth) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (width == 0 && depth == 0) {  // the route without the expand kernel: what the speculation is measured against
+    m->m3->per_pop = true;
+    return SLAMHIP_OK;
+  }
+  if (width < 1 || width > 65536 || depth < 1 || depth > m3rsm::kMaxDepth)
+    return invalid_arg("speculation: width in [1, 65536], depth 1, 2 or 3 (or 0, 0)");
+  m->m3->per_pop = false;
+  m->m3->cfg.width = width;
+  m->m3->cfg.depth = depth;
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_m3rsm_trace(slamhip_matcher *m, int cap, double *rows, int *n) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (cap < 0 || (cap > 0 && !rows)) return invalid_arg("bad trace buffer");
+  const std::vector<m3rsm::Call> &t = m->m3->trace;
+  if (n) *n = (int)t.size();
+  for (size_t i = 0; i < std::min((size_t)cap, t.size()); ++i) {
+    double *r = rows + 7 * i;
+    r[0] = t[i].rotation;
+    r[1] = t[i].rect.bot;
+    r[2] = t[i].rect.top;
+    r[3] = t[i].rect.left;
+    r[4] = t[i].rect.right;
+    r[5] = t[i].score;
+    r[6] = (double)t[i].level;
+  }
+  return SLAMHIP_OK;
+}
 
 int slamhip_matcher_create_mc(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, unsigned seed,
                               double td, double rd, unsigned failed_limit, unsigned attempts_limit,
@@ -1701,7 +1851,7 @@ int slamhip_matcher_destroy(slamhip_matcher *m) {
 
 int slamhip_matcher_reset_state(slamhip_matcher *m) {
   if (!m) return invalid_arg("null matcher");
-  m->pe->reset();
+  if (m->pe) m->pe->reset();  // (the multi-resolution matcher keeps no state between matches)
   return SLAMHIP_OK;
 }
 
@@ -1757,6 +1907,7 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
                                        double *out_deltas, double *out_probs) {
   if (!m || n_jobs < 0 || (n_jobs > 0 && (!jobs || !out_deltas || !out_probs))) return invalid_arg("null argument");
   if (n_jobs == 0) return SLAMHIP_OK;
+  if (m->is_m3rsm) return invalid_arg("multi-resolution matches are not batched");
   slamhip_ctx *ctx = m->ctx;
   for (int c = 0; c < n_jobs; ++c) {
     const slamhip_match_job &j = jobs[c];
@@ -1892,6 +2043,7 @@ int slamhip_matcher_process_raw_scan(slamhip_matcher *m, int map_id, const slamh
   if (kept_n) *kept_n = kept;
   if (rc) return rc;
   if (kept == 0) {  // 0 / 0 for every candidate (weighted_mean_point_probability_spe.h:126-132): nothing is accepted
+    if (m->is_m3rsm) m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;  // (its stats are per match)
     out_delta[0] = out_delta[1] = out_delta[2] = 0.0;
     *out_prob = std::numeric_limits<double>::quiet_NaN();
     return SLAMHIP_OK;
@@ -1999,6 +2151,7 @@ int slamhip_matcher_process_scan(slamhip_matcher *m, int map_id, const double in
     return SLAMHIP_ERR_HIP;
   }
 #endif
+  if (m->is_m3rsm) return m3rsm_process_scan(m, map_id, init_pose, out_delta, out_prob);
   // (r06) the GMapping OOPE's checked default mode: a chain that met a comparison its sums cannot settle reports it
   // before anything has been shown to an observer; the match is then redone below in the exact mode
   bool force_exact = false;

@@ -13,13 +13,17 @@
 
 #include "utils/init_scan_matching.h"
 #include "slamhip_reference_adapter.h"
+#include "slamhip_m3rsm_map.h"
 
 // cell_model >= 0: the payload model of the map instead of the one "slam/mapping/grid/area/type" names (a world whose
-// cell class is fixed by its factory: slamhip_credibilist_slam.h), with the reader of its cells' belief masses
+// cell class is fixed by its factory: slamhip_credibilist_slam.h), with the reader of its cells' belief masses.
+// m3rsm_map: the resident map with its levels that "slam/scmtch/type" = BF_M3RSM matches against (the multi-resolution
+// matcher bounds its candidates on levels kept in HBM, so it needs the map to live there: slamhip_m3rsm_map.h)
 inline std::shared_ptr<GridScanMatcher> init_hip_scan_matcher(const PropertiesProvider &props,
                                                               slamhip_ctx *ctx = nullptr, int map_id = 0,
                                                               int cell_model = -1,
-                                                              HipMapMirror::BeliefReader belief_reader = nullptr) {
+                                                              HipMapMirror::BeliefReader belief_reader = nullptr,
+                                                              HipM3rsmMap *m3rsm_map = nullptr) {
   if (!ctx) slamhip_or_die(slamhip_ctx_create(props.get_int("slam/scmtch/hip/device", 0), &ctx), "ctx_create");
   // the reference's own SPE: still does filter_scan on the host and prints "Used OIE/OOPE/SWP"
   auto spe = init_spe(props);
@@ -61,8 +65,24 @@ inline std::shared_ptr<GridScanMatcher> init_hip_scan_matcher(const PropertiesPr
                          props.get_dbl(ns + "t/from", -deg2rad(5)), props.get_dbl(ns + "t/to", deg2rad(5)),
                          props.get_dbl(ns + "t/step", deg2rad(1))};
     slamhip_or_die(slamhip_matcher_create_bf(ctx, &cfg, r, &m), "create_bf");
+  } else if (is_m3rsm(type)) {
+    // init_bf_m3rsm (src/utils/init_scan_matching.h:171-183): the same keys, the same defaults
+    if (!m3rsm_map) {
+      std::cerr << "scan matcher type BF_M3RSM needs the resident map with its levels (HipM3rsmMap)" << std::endl;
+      std::exit(-1);
+    }
+    const std::string ns = Slam_SM_NS + "BF_M3RSM/";
+    // (strict: bounds are scored under the cached provider's angle addition only)
+    if (cfg.pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT) cfg.pose_trig = SLAMHIP_POSE_TRIG_HOST;
+    const auto ang_acc = props.get_dbl(ns + "accuracy/rotation", deg2rad(0.1));
+    const auto trl_acc = props.get_dbl(ns + "accuracy/translation", 0.05);
+    const auto max_x_err = props.get_dbl(ns + "limits/x_translation", 1);
+    const auto max_y_err = props.get_dbl(ns + "limits/y_translation", 1);
+    const auto max_rot_err = props.get_dbl(ns + "limits/rotation", deg2rad(5));
+    m = m3rsm_map->matcher(cfg, max_x_err, max_y_err, max_rot_err, ang_acc, trl_acc);
+    map_id = m3rsm_map->map_id();
   } else {
-    std::cerr << "scan matcher type " << type << " is outside the HIP path (MC / HC / BF)" << std::endl;
+    std::cerr << "scan matcher type " << type << " is outside the HIP path (MC / HC / BF / BF_M3RSM)" << std::endl;
     std::exit(-1);
   }
   const auto area = props.get_str("slam/mapping/grid/area/type", "<undefined>");
@@ -78,6 +98,7 @@ inline std::shared_ptr<GridScanMatcher> init_hip_scan_matcher(const PropertiesPr
   auto mirror = std::make_shared<HipMapMirror>(ctx, map_id, model, bounded);
   mirror->set_belief_reader(belief_reader);
   auto gsm = std::make_shared<HipGridScanMatcher>(spe, ctx, m, mirror, weighting);
+  if (is_m3rsm(type)) gsm->set_resident_map(true);  // (the map is matched where it lives: nothing to mirror)
   if (props.get_str(Slam_SM_NS + "spe/type", "<undefined>") == "wmpp")  // (init_spe's own parameters, :99-100)
     gsm->set_filter_params(props.get_uint(Slam_SM_NS + "spe/wmpp/sp_skip_rate", 0),
                            props.get_dbl(Slam_SM_NS + "spe/wmpp/sp_max_usable_range", -1), bounded);

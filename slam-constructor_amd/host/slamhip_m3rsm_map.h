@@ -4,8 +4,9 @@
 // The reference keeps the coarse levels up to date inside GridMap::update, cell by cell.  Here the fine map lives in
 // HBM (HipResidentMapView reads it back for the map's consumers), the levels are a slamhip_pyramid over it, and
 // append_scan refreshes the levels behind every scan it writes -- queued on the context's stream, so the caller does
-// not wait for either.  bounds() is Match::prob_upper_bound (:156-180) for a batch of candidates.
-// The best-first engine (M3RSMEngine) is not part of the device path yet: a caller drives the priority queue itself.
+// not wait for either.  bounds() is Match::prob_upper_bound (:156-180) for a batch of candidates; matcher() makes the
+// device counterpart of BruteForceMultiResolutionScanMatcher over these levels (slamhip_matcher_create_m3rsm: the
+// best-first engine, M3RSMEngine :252-365, replayed on the host over expand launches).
 // Compiled only with the reference headers on the include path; contains no reference code.
 #ifndef SLAMHIP_M3RSM_MAP_H
 #define SLAMHIP_M3RSM_MAP_H
@@ -33,6 +34,18 @@ public:
 
   const GridMap &map() const { return *_view; }
   slamhip_pyramid *pyramid() { return _pyr; }
+  int map_id() const { return _map_id; }
+
+  // BruteForceMultiResolutionScanMatcher over this map's levels, with init_bf_m3rsm's parameters
+  // (src/utils/init_scan_matching.h:171-183).  The caller owns the matcher and destroys it before this map.
+  slamhip_matcher *matcher(const slamhip_spe_cfg &cfg, double max_x_error = 1, double max_y_error = 1,
+                           double max_th_error = deg2rad(5), double angle_step = deg2rad(0.1),
+                           double translation_step = 0.05) {
+    slamhip_matcher *m = nullptr;
+    slamhip_or_die(slamhip_matcher_create_m3rsm(_ctx, &cfg, _pyr, max_x_error, max_y_error, max_th_error, angle_step,
+                                                translation_step, &m), "create_m3rsm");
+    return m;
+  }
 
   // GridMapScanAdder::append_scan on the fine map (slamhip_map_append_scan_q), then the levels over what it wrote:
   // the cells within the longest beam (plus the blur) of the pose -- or everything, when the window has grown
