@@ -380,6 +380,30 @@ int slamhip_pyramid_expand_matches_device(slamhip_ctx *ctx, slamhip_pyramid *pyr
                                           const double base_pose[3], int n, const double *d_rotation, const double *d_rect,
                                           double translation_step, int depth, double *d_rect_out, double *d_score_out,
                                           int *d_level_out);
+/* SEVERAL REQUESTS IN ONE LAUNCH.  M3RSMEngine::add_scan_matching_request (m3rsm_engine.h:291-316) may be called any
+ * number of times, each call with its own scan, pose and map, and every match of the one queue carries its request's.
+ * A request here: a pyramid, a scan kept in HBM by slamhip_scan_store and the pose its drifts are added to.  Candidate
+ * (or parent) i of a launch belongs to table[request[i]]; its workgroup takes levels, scan and base pose from that entry
+ * (csrc/map_pyramid.hip k_pyr_score_many, csrc/m3rsm.hip k_m3rsm_expand_many) and runs the scoring function of the
+ * single-request kernels, so score_out / level_out are BIT-EQUAL to slamhip_pyramid_score_matches /
+ * slamhip_pyramid_expand_matches on that request's pyramid, scan (slamhip_scan_select) and pose alone.  Outputs, slot
+ * layout, sum orders and pose_trig (HOST: one sincos per candidate / parent, on its own request's heading) as above.
+ * All pyramids of one call belong to `ctx` and share the cell model and the OIE (= cfg->oie).
+ * SLAMHIP_ERR_INVALID: n_requests < 1, a null pyramid or one that is not this context's, mixed cell models or OIEs, a
+ * scan slot that holds no scan, a pose that is not finite, a request index outside the table, values that are not
+ * finite; SLAMHIP_ERR_STATE: a stale pyramid. */
+typedef struct {
+  slamhip_pyramid *pyramid;
+  int scan_slot;
+  double init_pose[3];
+} slamhip_m3rsm_request;
+int slamhip_pyramid_score_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests,
+                                   const slamhip_m3rsm_request *table, int n, const int *request, const double *rotation,
+                                   const double *rect, double *score_out, int *level_out);
+int slamhip_pyramid_expand_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests,
+                                    const slamhip_m3rsm_request *table, int n, const int *request, const double *rotation,
+                                    const double *rect, double translation_step, int depth, double *rect_out,
+                                    double *score_out, int *level_out);
 
 /* ---------------------------------------------------------------- map update (kernel K6)
  * Replaces GridMapScanAdder::append_scan (src/core/maps/grid_map_scan_adders.h:54-75) with
@@ -597,6 +621,22 @@ int slamhip_matcher_set_m3rsm_speculation(slamhip_matcher *m, int width, int dep
 /* The committed scorer calls of the last match in the reference's order: row k of rows (room for cap rows of 7
  * doubles) = rotation, bot, top, left, right, score, level; *n = how many there were (may exceed cap). */
 int slamhip_matcher_m3rsm_trace(slamhip_matcher *m, int cap, double *rows, int *n);
+/* MANY-TO-MANY: several requests in ONE search, as the reference's engine takes them (add_scan_matching_request once per
+ * request, m3rsm_engine.h:291-316; then BruteForceMultiResolutionScanMatcher::process_scan's loop,
+ * bf_multi_res_scan_matcher.h:44-65).  The root layers are committed request by request in the order given -- all of
+ * them bounded in one slamhip_pyramid_score_requests launch --; there is one queue and one best finest probability, so
+ * a good point of one request prunes the others; a super-step's parents come from the shared queue whatever request
+ * they belong to (slamhip_pyramid_expand_requests).  The first popped match that is a point wins:
+ * *out_request = its request, out_delta = (centre x, centre y, rotation), *out_prob = its bound -- the request whose
+ * lone match has the largest probability, in fewer calls than the lone matches together.  The matcher's limits, steps,
+ * cfg and speculation apply to every request; the matcher's own pyramid takes no part.  Stats and observer
+ * (on_matching_end once) as for a lone match.  If every bound is NaN: *out_request = -1, delta 0, prob NaN.
+ * SLAMHIP_ERR_INVALID / _STATE as for slamhip_pyramid_score_requests. */
+int slamhip_matcher_m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req,
+                                     int *out_request, double out_delta[3], double *out_prob);
+/* The committed calls of the last slamhip_matcher_m3rsm_match_many: rows of 8 doubles = request, rotation, bot, top,
+ * left, right, score, level; cap and *n as for slamhip_matcher_m3rsm_trace. */
+int slamhip_matcher_m3rsm_trace_many(slamhip_matcher *m, int cap, double *rows, int *n);
 int slamhip_matcher_destroy(slamhip_matcher *m);
 /* GridScanMatcher::reset_state (grid_scan_matcher.h:158) */
 int slamhip_matcher_reset_state(slamhip_matcher *m);

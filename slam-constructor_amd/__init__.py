@@ -65,6 +65,8 @@ slamhip_pyramid_create slamhip_pyramid_destroy slamhip_pyramid_info slamhip_pyra
 slamhip_pyramid_build_host slamhip_pyramid_score_matches slamhip_pyramid_score_matches_device
 slamhip_pyramid_expand_matches slamhip_pyramid_expand_matches_device slamhip_matcher_create_m3rsm
 slamhip_matcher_set_m3rsm_speculation slamhip_matcher_m3rsm_trace
+slamhip_pyramid_score_requests slamhip_pyramid_expand_requests slamhip_matcher_m3rsm_match_many
+slamhip_matcher_m3rsm_trace_many
 slamhip_scan_table_uploads slamhip_scan_download""".split()
 
 SHARD_ID_BYTES = 128
@@ -292,6 +294,11 @@ def load(testing=False):
     L.slamhip_matcher_create_m3rsm.argtypes = [vp, C.POINTER(SpeCfg), vp, d, d, d, d, d, C.POINTER(vp)]
     L.slamhip_matcher_set_m3rsm_speculation.argtypes = [vp, i, i]
     L.slamhip_matcher_m3rsm_trace.argtypes = [vp, i, _dp, _ip]
+    rq = C.POINTER(M3rsmRequest)
+    L.slamhip_pyramid_score_requests.argtypes = [vp, C.POINTER(SpeCfg), i, rq, i, _ip, _dp, _dp, _dp, _ip]
+    L.slamhip_pyramid_expand_requests.argtypes = [vp, C.POINTER(SpeCfg), i, rq, i, _ip, _dp, _dp, d, i, _dp, _dp, _ip]
+    L.slamhip_matcher_m3rsm_match_many.argtypes = [vp, i, rq, _ip, _dp, _dp]
+    L.slamhip_matcher_m3rsm_trace_many.argtypes = [vp, i, _dp, _ip]
     _libs[testing] = L
     return L
 
@@ -1112,6 +1119,24 @@ class Matcher:
         _check(self.L.slamhip_matcher_m3rsm_trace(self.h, n.value, _d(rows), C.byref(n)))
         return rows
 
+    def m3rsm_match_many(self, requests):
+        """BF_M3RSM, many-to-many (slamhip_matcher_m3rsm_match_many): requests = a list of (pyramid, scan_slot, pose), scans
+        from Context.scan_store; ONE search over all of them.  Returns dict(request, delta[3], prob): the best match of any
+        request (request -1, prob NaN when no request had a valid bound)."""
+        table = m3rsm_request_table(requests)
+        which, d3, prob = C.c_int(-1), (C.c_double * 3)(), C.c_double()
+        _check(self.L.slamhip_matcher_m3rsm_match_many(self.h, len(table), table, C.byref(which), d3, C.byref(prob)))
+        return dict(request=which.value, delta=np.array(list(d3)), prob=prob.value)
+
+    def m3rsm_trace_many(self):
+        """The committed scorer calls of the last m3rsm_match_many, [n, 8] = request, rotation, bot, top, left, right,
+        score, level."""
+        n = C.c_int(0)
+        _check(self.L.slamhip_matcher_m3rsm_trace_many(self.h, 0, None, C.byref(n)))
+        rows = np.zeros((n.value, 8))
+        _check(self.L.slamhip_matcher_m3rsm_trace_many(self.h, n.value, _d(rows), C.byref(n)))
+        return rows
+
     def resident_stats(self):
         """Matches launched in the co-resident form, and how many of them gave up and were redone by the kernel chain."""
         a, b = C.c_longlong(), C.c_longlong()
@@ -1184,6 +1209,23 @@ def m3rsm_root_candidates(limits, ang_step):
                 rect.append(box)
         drift += step
     return np.asarray(rot, dtype=np.float64), np.asarray(rect, dtype=np.float64).reshape(-1, 4)
+
+
+class M3rsmRequest(C.Structure):
+    """slamhip_m3rsm_request (include/slamhip.h)"""
+    _fields_ = [("pyramid", C.c_void_p), ("scan_slot", C.c_int), ("init_pose", C.c_double * 3)]
+
+
+def m3rsm_request_table(requests):
+    """[(pyramid, scan_slot, pose), ...] as an array of slamhip_m3rsm_request (a pyramid may be None: the library refuses)"""
+    requests = list(requests)
+    table = (M3rsmRequest * max(len(requests), 1))()
+    for k, (pyr, slot, pose) in enumerate(requests):
+        table[k].pyramid = None if pyr is None else pyr.h
+        table[k].scan_slot = int(slot)
+        table[k].init_pose[:] = [float(v) for v in np.asarray(pose, dtype=np.float64).ravel()[:3]]
+    table._n = len(requests)
+    return table
 
 
 class Pyramid:
@@ -1263,6 +1305,39 @@ class Pyramid:
         _check(self.L.slamhip_pyramid_expand_matches(self.ctx.h, self.h, C.byref(cfg), _d(base), n, _d(rotation), _d(rect),
                                                      float(translation_step), int(depth), _d(rects), _d(scores),
                                                      levels.ctypes.data_as(_ip)))
+        return rects, scores, levels
+
+    @staticmethod
+    def score_requests(ctx, cfg, table, request, rotation, rect):
+        """Bounds of candidates of several requests in one launch (slamhip_pyramid_score_requests): table = a list of
+        (pyramid, scan_slot, base_pose), candidate i = (request[i], rotation[i], rect[i]); (scores[n], levels[n])."""
+        tab = m3rsm_request_table(table)
+        request = np.ascontiguousarray(request, dtype=np.int32).ravel()
+        rotation = _f64(rotation).ravel()
+        rect = _f64(rect).reshape(-1, 4)
+        if rect.shape[0] != rotation.size or request.size != rotation.size:
+            raise ValueError("one request and one rectangle per rotation")
+        scores, levels = np.zeros(rotation.size), np.zeros(rotation.size, np.int32)
+        _check(ctx.L.slamhip_pyramid_score_requests(ctx.h, C.byref(cfg), tab._n, tab, rotation.size, request.ctypes.data_as(_ip),
+                                                    _d(rotation), _d(rect), _d(scores), levels.ctypes.data_as(_ip)))
+        return scores, levels
+
+    @staticmethod
+    def expand_requests(ctx, cfg, table, request, rotation, rect, translation_step, depth=1):
+        """expand_matches for parents of several requests in one launch (slamhip_pyramid_expand_requests): parent i =
+        (request[i], rotation[i], rect[i]); (rects[n, S, 4], scores[n, S], levels[n, S])."""
+        tab = m3rsm_request_table(table)
+        request = np.ascontiguousarray(request, dtype=np.int32).ravel()
+        rotation = _f64(rotation).ravel()
+        rect = _f64(rect).reshape(-1, 4)
+        if rect.shape[0] != rotation.size or request.size != rotation.size:
+            raise ValueError("one request and one rectangle per rotation")
+        slots = {1: 5, 2: 30, 3: 155}.get(int(depth), 1)
+        n = rotation.size
+        rects, scores, levels = np.zeros((n, slots, 4)), np.zeros((n, slots)), np.zeros((n, slots), np.int32)
+        _check(ctx.L.slamhip_pyramid_expand_requests(ctx.h, C.byref(cfg), tab._n, tab, n, request.ctypes.data_as(_ip),
+                                                     _d(rotation), _d(rect), float(translation_step), int(depth), _d(rects),
+                                                     _d(scores), levels.ctypes.data_as(_ip)))
         return rects, scores, levels
 
     def score_matches_device(self, cfg, base_pose, n, d_rotation_ptr, d_rect_ptr, d_scores_ptr, d_levels_ptr):

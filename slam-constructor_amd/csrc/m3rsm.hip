@@ -14,6 +14,11 @@
 // whose path ends early writes level -1 / NaN and leaves, the whole workgroup at once; the others run pyr_score_one,
 // the body of k_pyr_score (map_pyramid_score.h), on the rectangle they arrived at.  Compute bound like k_pyr_score: a
 // beam costs a sincos-free rotation, a window of at most 3 x 3 cells and one multiply-add chain.
+//
+// k_m3rsm_expand_many is the same launch for parents of SEVERAL scan matching requests
+// (M3RSMEngine::add_scan_matching_request :291-316 called more than once: one queue, so a layer of its matches mixes
+// requests): scan, level table and base pose come per parent from a request table in HBM
+// (slamhip_pyramid_expand_requests), everything else is k_m3rsm_expand.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -30,6 +35,15 @@ struct ExpandArgs {
   double *rect_out;  // n x slots x (bot, top, left, right)
   double step;
   int slots;  // per parent: m3rsm::slots_of(depth)
+};
+
+// the multi-request form: the parents of one launch belong to different requests (the shared queue of
+// m3rsm::run_many), each with its own scan, level table and base pose in a table in HBM
+struct ExpandManyArgs {
+  ManyArgs q;  // q.m as ExpandArgs::m (its own levels / scan / base are not read); q.request: per PARENT
+  double *rect_out;
+  double step;
+  int slots;
 };
 
 template <int MODEL>
@@ -57,7 +71,43 @@ __global__ __launch_bounds__(kPyrThreads) void k_m3rsm_expand(ExpandArgs a) {
     a.rect_out[4 * g + 2] = node.left;
     a.rect_out[4 * g + 3] = node.right;
   }
-  pyr_score_one<MODEL>(a.m, parent, g, node.bot, node.top, node.left, node.right, s_trig, s_part);
+  pyr_score_one<MODEL>(a.m, a.m, parent, g, a.m.terms, g * (size_t)a.m.scan.n, node.bot, node.top, node.left, node.right, s_trig,
+                       s_part);
+}
+
+// One workgroup per slot, the same walk and the same outputs as above (the two kernels spell the slot's prologue out
+// each: handed to a shared function through a pointer to the node it cost k_m3rsm_expand 13 VGPRs).  The request's entry
+// of the table is uniform over the workgroup: it is read once, after the slot is known to hold a node, and everything
+// per beam comes from that copy.
+template <int MODEL>
+__global__ __launch_bounds__(kPyrThreads) void k_m3rsm_expand_many(ExpandManyArgs a) {
+  __shared__ double s_trig[2];
+  __shared__ double s_part[4];
+  const size_t g = blockIdx.x;
+  const size_t parent = g / (size_t)a.slots;
+  const int slot = (int)(g - parent * (size_t)a.slots);
+  const MatchArgs &m = a.q.m;
+  const m3rsm::Rect top{m.rect[4 * parent], m.rect[4 * parent + 1], m.rect[4 * parent + 2], m.rect[4 * parent + 3]};
+  m3rsm::Rect node;
+  const bool there = m3rsm::slot_node(top, a.step, slot, &node);  // (uniform, as above)
+  if (!there) {
+    if (threadIdx.x == 0) {
+      const double nan = __builtin_nan("");
+      m.scores[g] = nan;
+      m.level_out[g] = -1;
+      a.rect_out[4 * g] = a.rect_out[4 * g + 1] = a.rect_out[4 * g + 2] = a.rect_out[4 * g + 3] = nan;
+    }
+    return;
+  }
+  if (threadIdx.x == 0) {
+    a.rect_out[4 * g] = node.bot;
+    a.rect_out[4 * g + 1] = node.top;
+    a.rect_out[4 * g + 2] = node.left;
+    a.rect_out[4 * g + 3] = node.right;
+  }
+  const PyrSource q = a.q.table[a.q.request[parent]];
+  const size_t terms_at = a.q.m.terms ? (size_t)a.q.terms_off[parent] + (size_t)slot * (size_t)q.scan.n : 0;
+  pyr_score_one<MODEL>(q, a.q.m, parent, g, a.q.m.terms, terms_at, node.bot, node.top, node.left, node.right, s_trig, s_part);
 }
 
 int check_expand(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base_pose[3], int n,
@@ -193,4 +243,50 @@ int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const s
   std::memcpy(score_out, h_out + 4 * n_out, sizeof(double) * n_out);
   std::memcpy(level_out, h_out + 5 * n_out, sizeof(int) * n_out);
   return SLAMHIP_OK;
+}
+
+int slamhip_pyramid_expand_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests,
+                                    const slamhip_m3rsm_request *table, int n, const int *request, const double *rotation,
+                                    const double *rect, double translation_step, int depth, double *rect_out,
+                                    double *score_out, int *level_out) {
+  std::vector<PyrSource> src;
+  int rc = pyr_many_sources(ctx, cfg, n_requests, table, &src);
+  if (rc) return rc;
+  if (n < 0) return pyr_invalid("bad parent batch");
+  if (!(translation_step > 0.0) || !std::isfinite(translation_step))
+    return pyr_invalid("the translation step must be positive and finite");
+  if (depth < 1 || depth > m3rsm::kMaxDepth) return pyr_invalid("depth: 1, 2 or 3");
+  if ((long long)n * m3rsm::slots_of(depth) > 0x7fffffffll) return pyr_invalid("too many slots for one launch");
+  if (n == 0) return SLAMHIP_OK;
+  if (!rect_out || !score_out || !level_out) return pyr_invalid("null output arrays");
+  // (a reversed rectangle is let through: it has no children, every slot of it comes back empty)
+  rc = pyr_many_check_batch(n_requests, n, request, rotation, rect, true);
+  if (rc) return rc;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  const int slots = m3rsm::slots_of(depth);
+  const size_t n_out = (size_t)n * slots;
+  ExpandManyArgs a;
+  std::memset(&a, 0, sizeof(a));
+  rc = pyr_many_stage(ctx, cfg, src, n, request, rotation, rect, slots, &a.q, &a.rect_out);
+  if (rc) return rc;
+  a.step = translation_step;
+  a.slots = slots;
+  ProfilePairGuard prof;
+  rc = prof.open(ctx, ctx->stream, 0);
+  if (rc) return rc;
+  typedef void (*Kernel)(ExpandManyArgs);
+  const Kernel kernel =
+      pick_cell_model(table[0].pyramid->cell_model, [](auto m) -> Kernel { return k_m3rsm_expand_many<decltype(m)::value>; });
+  SLAMHIP_CHECK(launch_kernel(kernel, dim3((unsigned)n_out), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
+  if (a.q.m.terms) {
+    rc = pyr_launch_sum_sequential_many(a.q, n_out, slots, ctx->stream);
+    if (rc) return rc;
+  }
+  rc = prof.close();
+  if (rc) return rc;
+  if (ctx->profile) {
+    ctx->prof_launches += 1;
+    for (int i = 0; i < n; ++i) ctx->prof_units += (long long)slots * src[request[i]].scan.n;
+  }
+  return pyr_many_fetch(ctx, n_out, true, rect_out, score_out, level_out);
 }

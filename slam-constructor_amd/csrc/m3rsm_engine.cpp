@@ -23,6 +23,7 @@ struct Match {
   double prob, rotation;
   Rect rect;
   double abs_rotation, drift_amount;
+  int request;  // (Match::spe / filtered_scan / pose / map: whose they are; no part of the order)
   bool finest() const { return drift_amount <= 0; }
   // true if this match is LESS preferable (Match::operator<)
   bool operator<(const Match &that) const {
@@ -32,12 +33,12 @@ struct Match {
   }
 };
 
-Match make_match(double rotation, const Rect &r, double prob) {
-  return Match{prob, rotation, r, std::abs(rotation), (r.right - r.left) + (r.top - r.bot)};
+Match make_match(int request, double rotation, const Rect &r, double prob) {
+  return Match{prob, rotation, r, std::abs(rotation), (r.right - r.left) + (r.top - r.bot), request};
 }
 
 struct Key {
-  uint64_t w[5];
+  uint64_t w[6];
   bool operator==(const Key &o) const { return std::memcmp(w, o.w, sizeof(w)) == 0; }
 };
 struct KeyHash {
@@ -51,10 +52,11 @@ struct KeyHash {
     return (size_t)h;
   }
 };
-Key key_of(double rotation, const Rect &r) {
+Key key_of(int request, double rotation, const Rect &r) {
   const double v[5] = {rotation, r.bot, r.top, r.left, r.right};
   Key k;
   std::memcpy(k.w, v, sizeof(v));
+  k.w[5] = (uint64_t)request;
   return k;
 }
 struct Bound {
@@ -69,21 +71,21 @@ struct Queue : std::priority_queue<Match> {
 
 struct Engine {
   const Config &cfg;
-  const ExpandFn &expand;
+  const ExpandManyFn &expand;
   Result *res;
   std::vector<Call> *trace;
   Queue matches;
   double best_finest = 0.0;
   std::unordered_map<Key, Bound, KeyHash> memo;
   std::vector<double> p_rot, p_rect, s_rect, s_score;
-  std::vector<int> s_level;
+  std::vector<int> s_level, p_req;
   std::vector<size_t> front;
 
   // M3RSMEngine::add_match with max_finest_prob_diff = 0, after the call has been committed to the trace
-  void commit(double rotation, const Rect &r, const Bound &b) {
+  void commit(int request, double rotation, const Rect &r, const Bound &b) {
     ++res->scorer_calls;
-    if (trace) trace->push_back(Call{rotation, r, b.score, b.level});
-    Match m = make_match(rotation, r, b.score);
+    if (trace) trace->push_back(Call{rotation, r, b.score, b.level, request});
+    Match m = make_match(request, rotation, r, b.score);
     if (m.prob < best_finest) return;
     if (m.finest()) best_finest = std::max(best_finest, m.prob - 0.0);
     matches.push(std::move(m));
@@ -92,15 +94,17 @@ struct Engine {
   bool expanded(const Match &m) const {
     Rect kids[kMaxChildren];
     const int n = children(m.rect, cfg.translation_step, kids);
-    return n == 0 || memo.count(key_of(m.rotation, kids[0])) != 0;
+    return n == 0 || memo.count(key_of(m.request, m.rotation, kids[0])) != 0;
   }
 
   // one expand call: `first` and the next width - 1 entries of the queue that have children nobody has scored yet
   int super_step(const Match &first) {
     if (res->super_steps >= cfg.max_super_steps) return kErrSuperSteps;
+    p_req.clear();
     p_rot.clear();
     p_rect.clear();
     auto add = [&](const Match &m) {
+      p_req.push_back(m.request);
       p_rot.push_back(m.rotation);
       p_rect.insert(p_rect.end(), {m.rect.bot, m.rect.top, m.rect.left, m.rect.right});
     };
@@ -131,7 +135,7 @@ struct Engine {
     s_rect.resize(4 * n_out);
     s_score.resize(n_out);
     s_level.resize(n_out);
-    const int rc = expand(n, p_rot.data(), p_rect.data(), cfg.depth, s_rect.data(), s_score.data(), s_level.data());
+    const int rc = expand(n, p_req.data(), p_rot.data(), p_rect.data(), cfg.depth, s_rect.data(), s_score.data(), s_level.data());
     ++res->super_steps;
     ++res->launches;
     if (rc) {
@@ -144,7 +148,7 @@ struct Engine {
         if (std::isnan(s_rect[4 * g])) continue;  // no node in this slot
         ++res->scored;
         const Rect r{s_rect[4 * g], s_rect[4 * g + 1], s_rect[4 * g + 2], s_rect[4 * g + 3]};
-        memo[key_of(p_rot[i], r)] = Bound{s_score[g], s_level[g]};
+        memo[key_of(p_req[i], p_rot[i], r)] = Bound{s_score[g], s_level[g]};
       }
     return kOk;
   }
@@ -154,14 +158,14 @@ struct Engine {
     Rect kids[kMaxChildren];
     const int n = children(m.rect, cfg.translation_step, kids);
     for (int c = 0; c < n; ++c) {
-      auto it = memo.find(key_of(m.rotation, kids[c]));
+      auto it = memo.find(key_of(m.request, m.rotation, kids[c]));
       if (it == memo.end()) {
         const int rc = super_step(m);
         if (rc) return rc;
-        it = memo.find(key_of(m.rotation, kids[c]));
+        it = memo.find(key_of(m.request, m.rotation, kids[c]));
         if (it == memo.end()) return kErrScorer;
       }
-      commit(m.rotation, kids[c], it->second);
+      commit(m.request, m.rotation, kids[c], it->second);
     }
     return kOk;
   }
@@ -189,36 +193,55 @@ void root_candidates(const Config &cfg, std::vector<double> *rotation, std::vect
 }
 
 int run(const Config &cfg, const ScoreFn &score_roots, const ExpandFn &expand, Result *result, std::vector<Call> *trace) {
+  const ScoreManyFn roots = [&](int n, const int *, const double *rotation, const double *rect, double *score, int *level) {
+    return score_roots(n, rotation, rect, score, level);
+  };
+  const ExpandManyFn expand_many = [&](int n, const int *, const double *rotation, const double *rect, int depth,
+                                       double *slot_rect, double *slot_score, int *slot_level) {
+    return expand(n, rotation, rect, depth, slot_rect, slot_score, slot_level);
+  };
+  return run_many(cfg, 1, roots, expand_many, result, trace);
+}
+
+int run_many(const Config &cfg, int n_requests, const ScoreManyFn &score_roots, const ExpandManyFn &expand, Result *result,
+             std::vector<Call> *trace) {
   *result = Result{};
   if (trace) trace->clear();
   if (!(cfg.angle_step > 0) || !(cfg.translation_step > 0) || !(cfg.max_x_error >= 0) || !(cfg.max_y_error >= 0) ||
       !(cfg.max_th_error >= 0) || !std::isfinite(cfg.max_x_error) || !std::isfinite(cfg.max_y_error) ||
       !std::isfinite(cfg.max_th_error) || !std::isfinite(cfg.angle_step) || !std::isfinite(cfg.translation_step) ||
-      cfg.width < 1 || cfg.depth < 1 || cfg.depth > kMaxDepth || cfg.max_super_steps < 1)
+      cfg.width < 1 || cfg.depth < 1 || cfg.depth > kMaxDepth || cfg.max_super_steps < 1 || n_requests < 1)
     return kErrInvalid;
   Engine e{cfg, expand, result, trace};
-  e.memo.reserve(1 << 16);
+  // (room per request for what a lone match memoises -- 22 636 nodes on the benchmark scene --: a node-based map that
+  // outgrows its buckets is rehashed by a walk over every node, a cache miss each, several times on the way up)
+  e.memo.reserve((size_t)(1 << 16) * (size_t)std::min(n_requests, 64));
   {
+    // add_scan_matching_request once per request: every request's root layer is the same list, bounded in one call
     std::vector<double> rot;
     std::vector<Rect> rect;
     root_candidates(cfg, &rot, &rect);
-    const int n = (int)rot.size();
-    std::vector<double> flat(4 * (size_t)n), score(n);
-    std::vector<int> level(n);
-    for (int i = 0; i < n; ++i) {
-      flat[4 * i] = rect[i].bot;
-      flat[4 * i + 1] = rect[i].top;
-      flat[4 * i + 2] = rect[i].left;
-      flat[4 * i + 3] = rect[i].right;
+    const size_t per = rot.size(), n = per * (size_t)n_requests;
+    if (n > 0x7fffffffu) return kErrInvalid;
+    std::vector<double> all_rot(n), flat(4 * n), score(n);
+    std::vector<int> req(n), level(n);
+    for (size_t g = 0; g < n; ++g) {
+      const size_t i = g % per;
+      req[g] = (int)(g / per);
+      all_rot[g] = rot[i];
+      flat[4 * g] = rect[i].bot;
+      flat[4 * g + 1] = rect[i].top;
+      flat[4 * g + 2] = rect[i].left;
+      flat[4 * g + 3] = rect[i].right;
     }
-    const int rc = score_roots(n, rot.data(), flat.data(), score.data(), level.data());
+    const int rc = score_roots((int)n, req.data(), all_rot.data(), flat.data(), score.data(), level.data());
     ++result->launches;
-    result->scored += n;
+    result->scored += (long long)n;
     if (rc) {
       result->callback_rc = rc;
       return kErrCallback;
     }
-    for (int i = 0; i < n; ++i) e.commit(rot[i], rect[i], Bound{score[i], level[i]});
+    for (size_t g = 0; g < n; ++g) e.commit(req[g], all_rot[g], rect[g % per], Bound{score[g], level[g]});
   }
   // BruteForceMultiResolutionScanMatcher::process_scan's loop around M3RSMEngine::next_best_match
   for (;;) {
@@ -231,6 +254,7 @@ int run(const Config &cfg, const ScoreFn &score_roots, const ExpandFn &expand, R
       result->delta[1] = best.rect.bot + vside / 2;
       result->delta[2] = best.rotation;
       result->prob = best.prob;
+      result->request = best.request;
       return kOk;
     }
     // (children() is next_best_match's branching decision and, for a box that no longer branches, the five points)

@@ -11,7 +11,7 @@
 // The loop is the reference's, call for call: a std::priority_queue of matches (libstdc++'s heap, as there: the
 // comparator is no strict weak order, so WHICH heap it is matters), the `< best finest probability` cut of add_match,
 // the five crucial points of a box that no longer branches, the end at a top that is a point.  What differs is where a
-// score comes from: a memo keyed by (rotation, rectangle) bit patterns.  When the loop needs a child the memo does not
+// score comes from: a memo keyed by (request, rotation, rectangle) bit patterns.  When the loop needs a child the memo does not
 // hold, the engine takes the popped match and the next `width` - 1 unexpanded non-point entries of a copy of the queue
 // and has ONE expand call score all their descendants to `depth` generations (a "super-step").  A score is a pure
 // function of its node, so the sequence of committed calls -- the trace -- is the reference's whatever width and depth.
@@ -38,6 +38,7 @@ struct Call {
   Rect rect;
   double score;
   int level;
+  int request = 0;  // run_many: the request the call belongs to
 };
 
 // Scores n candidates (rotation[i], rect[4 i ..]) -> score[i], level[i]; returns 0 or an error code passed through.
@@ -47,9 +48,16 @@ using ScoreFn = std::function<int(int n, const double *rotation, const double *r
 using ExpandFn = std::function<int(int n, const double *rotation, const double *rect, int depth, double *slot_rect,
                                    double *slot_score, int *slot_level)>;
 
+// the same two calls for candidates of several requests (run_many): request[i] says whose scan, pose and map
+using ScoreManyFn =
+    std::function<int(int n, const int *request, const double *rotation, const double *rect, double *score, int *level)>;
+using ExpandManyFn = std::function<int(int n, const int *request, const double *rotation, const double *rect, int depth,
+                                       double *slot_rect, double *slot_score, int *slot_level)>;
+
 struct Result {
   double delta[3] = {0, 0, 0};  // centre x, centre y, rotation of the winning point
   double prob = 0;
+  int request = 0;              // run_many: the request the winning point belongs to
   long long scorer_calls = 0;   // committed calls: what the reference would have made
   long long scored = 0;         // candidates the two callbacks were asked to score (roots + non-empty slots)
   long long launches = 0;       // callback invocations: the root layer + the super-steps
@@ -72,6 +80,13 @@ void root_candidates(const Config &cfg, std::vector<double> *rotation, std::vect
 
 // One match; returns one of the codes above.  `trace` (may be null) receives every committed call.
 int run(const Config &cfg, const ScoreFn &score_roots, const ExpandFn &expand, Result *result, std::vector<Call> *trace);
+
+// Several requests in one search, as M3RSMEngine takes them: add_scan_matching_request once per request, in order -- the
+// root layers committed request by request, all of them bounded by ONE score_roots call --, then the matcher's loop over
+// the one queue under the one best finest probability.  A super-step's parents are whatever the queue holds on top, of
+// whichever request; the memo is keyed by (request, rotation, rectangle).  run() is run_many() with one request.
+int run_many(const Config &cfg, int n_requests, const ScoreManyFn &score_roots, const ExpandManyFn &expand, Result *result,
+             std::vector<Call> *trace);
 
 }  // namespace m3rsm
 }  // namespace slamhip

@@ -15,7 +15,9 @@
 // Score: one workgroup of 256 threads per candidate.  It picks the candidate's level from its rectangle, takes that
 // level's MapView from a table in HBM and runs k_score_window's body (score_kernels.hip) for one pose: thread t adds the
 // beams t, t + 256, ... in ascending order, the wave butterfly, (g0 + g1) + (g2 + g3) -- the canonical sum, hence the
-// bits slamhip_score_poses gives for that pose on that level's map with cfg.area = the rectangle.
+// bits slamhip_score_poses gives for that pose on that level's map with cfg.area = the rectangle.  k_pyr_score_many scores
+// candidates of several requests in one launch: level table, scan and base pose per candidate from a request table in HBM
+// (slamhip_pyramid_score_requests; the staging both multi-request launches share is in here too).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -201,7 +203,26 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyr_score(MatchArgs a) {
   __shared__ double s_trig[2];
   __shared__ double s_part[4];
   const size_t i = blockIdx.x;
-  pyr_score_one<MODEL>(a, i, i, a.rect[4 * i], a.rect[4 * i + 1], a.rect[4 * i + 2], a.rect[4 * i + 3], s_trig, s_part);
+  pyr_score_one<MODEL>(a, a, i, i, a.terms, i * (size_t)a.scan.n, a.rect[4 * i], a.rect[4 * i + 1], a.rect[4 * i + 2],
+                       a.rect[4 * i + 3], s_trig, s_part);
+}
+
+// the same for candidates of several requests: the workgroup's scan, levels and base pose are its request's entry of the
+// table (one read per workgroup, uniform: it goes through the scalar cache), the rest is k_pyr_score
+template <int MODEL>
+__global__ __launch_bounds__(kPyrThreads) void k_pyr_score_many(ManyArgs a) {
+  __shared__ double s_trig[2];
+  __shared__ double s_part[4];
+  const size_t i = blockIdx.x;
+  const PyrSource q = a.table[a.request[i]];
+  pyr_score_one<MODEL>(q, a.m, i, i, a.m.terms, a.m.terms ? (size_t)a.terms_off[i] : 0, a.m.rect[4 * i], a.m.rect[4 * i + 1],
+                       a.m.rect[4 * i + 2], a.m.rect[4 * i + 3], s_trig, s_part);
+}
+
+__device__ __forceinline__ double sum_sequential_row(const double *row, int n, double tot_w) {
+  double acc = 0.0;
+  for (int b = 0; b < n; ++b) acc = acc + row[b];
+  return (tot_w == 0.0) ? __builtin_nan("") : acc / tot_w;
 }
 
 // the reference's beam-order sum over the terms (k_sum_sequential's loop), one lane per candidate that has a level
@@ -209,10 +230,16 @@ __global__ __launch_bounds__(64) void k_pyr_sum_sequential(const double *terms, 
                                                            double *scores) {
   const int p = blockIdx.x * 64 + threadIdx.x;
   if (p >= n_cand || level[p] < 0) return;
-  const double *row = terms + (size_t)p * n;
-  double acc = 0.0;
-  for (int b = 0; b < n; ++b) acc = acc + row[b];
-  scores[p] = (tot_w == 0.0) ? __builtin_nan("") : acc / tot_w;
+  scores[p] = sum_sequential_row(terms + (size_t)p * n, n, tot_w);
+}
+
+// ... over the rows of a multi-request launch: output p is slot p % slots of parent p / slots
+__global__ __launch_bounds__(64) void k_pyr_sum_sequential_many(ManyArgs a, int n_out, int slots) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= n_out || a.m.level_out[p] < 0) return;
+  const int parent = p / slots;
+  const ScanView &scan = a.table[a.request[parent]].scan;
+  a.m.scores[p] = sum_sequential_row(a.m.terms + a.terms_off[parent] + (size_t)(p - parent * slots) * scan.n, scan.n, scan.tot_w);
 }
 
 int check_score_cfg(const slamhip_pyramid *p, const slamhip_spe_cfg *cfg) {
@@ -303,6 +330,169 @@ int pyr_launch_sum_sequential(const MatchArgs &a, size_t n_out, hipStream_t stre
   return SLAMHIP_OK;
 }
 
+int pyr_launch_sum_sequential_many(const ManyArgs &a, size_t n_out, int slots, hipStream_t stream) {
+  SLAMHIP_CHECK(launch_kernel(k_pyr_sum_sequential_many, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, stream, nullptr, nullptr,
+                              a, (int)n_out, slots));
+  return SLAMHIP_OK;
+}
+
+// ---- several requests in one launch ----------------------------------------------------------------
+void pyr_many_release(slamhip_ctx *ctx) {
+  PyrManyStage *st = static_cast<PyrManyStage *>(ctx->pyr_many);
+  if (!st) return;
+  if (st->h) (void)hipHostFree(st->h);
+  if (st->d) (void)hipFree(st->d);
+  if (st->d_terms) (void)hipFree(st->d_terms);
+  delete st;
+  ctx->pyr_many = nullptr;
+}
+
+int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests, const slamhip_m3rsm_request *req,
+                     std::vector<PyrSource> *out) {
+  if (!ctx) return pyr_invalid("null context");
+  if (n_requests < 1 || !req) return pyr_invalid("at least one request");
+  out->clear();
+  const slamhip_pyramid *first = nullptr;
+  for (int r = 0; r < n_requests; ++r) {
+    slamhip_pyramid *p = req[r].pyramid;
+    if (!p) return pyr_invalid("a request without a pyramid");
+    // (a pyramid of another context, or one that has been destroyed, is not in this context's list: it is not read)
+    if (std::find(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)p) == ctx->pyramids.end())
+      return pyr_invalid("a request's pyramid belongs to another context, or has been destroyed");
+    int rc = check_fresh(p);
+    if (rc) return rc;
+    if (!first) {
+      first = p;
+      rc = check_score_cfg(p, cfg);
+      if (rc) return rc;
+      if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
+        return pyr_invalid("pose_trig: DEVICE or HOST");
+    }
+    if (p->cell_model != first->cell_model || p->oie != first->oie)
+      return pyr_invalid("the pyramids of one call share the cell model and the OIE");
+    const int slot = req[r].scan_slot;
+    if (slot < 0 || slot >= (int)ctx->scan_slots.size() || !ctx->scan_slots[slot].d || ctx->scan_slots[slot].n <= 0)
+      return pyr_invalid("a request's scan slot holds no scan (slamhip_scan_store)");
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(req[r].init_pose[k])) return pyr_invalid("a request's pose is not finite");
+    const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[slot];
+    PyrSource q;
+    std::memset(&q, 0, sizeof(q));
+    q.levels = p->d_views;
+    q.n_levels = p->plan.n + 1;
+    const size_t c = (size_t)sl.cap;
+    q.scan.range = sl.d;
+    q.scan.cos_a = sl.d + c;
+    q.scan.sin_a = sl.d + 2 * c;
+    q.scan.weight = sl.d + 3 * c;
+    q.scan.factor = sl.d + 4 * c;
+    q.scan.n = sl.n;
+    q.scan.tot_w = sl.tot_w;
+    for (int k = 0; k < 3; ++k) q.base[k] = req[r].init_pose[k];
+    out->push_back(q);
+  }
+  return SLAMHIP_OK;
+}
+
+namespace {
+size_t up8(size_t v) { return (v + 7) & ~(size_t)7; }
+size_t many_in_bytes(size_t n_src, size_t n) {
+  return up8(sizeof(PyrSource) * n_src) + sizeof(long long) * n + sizeof(double) * 7 * n + up8(sizeof(int) * n);
+}
+size_t many_out_bytes(size_t n_out) { return sizeof(double) * 5 * n_out + up8(sizeof(int) * n_out); }
+}  // namespace
+
+int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int n, const int *request,
+                   const double *rotation, const double *rect, int slots, ManyArgs *out, double **d_rect_out) {
+  const size_t n_src = src.size(), n_out = (size_t)n * slots;
+  if (!ctx->pyr_many) ctx->pyr_many = new PyrManyStage;
+  PyrManyStage *st = static_cast<PyrManyStage *>(ctx->pyr_many);
+  const size_t in_bytes = many_in_bytes(n_src, n), need = in_bytes + many_out_bytes(n_out);
+  if (need > st->cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (st->h) (void)hipHostFree(st->h);
+    if (st->d) (void)hipFree(st->d);
+    st->h = st->d = nullptr;
+    st->cap = 0;
+    size_t cap = 1 << 16;
+    while (cap < need) cap *= 2;
+    SLAMHIP_CHECK(hipMalloc(&st->d, cap));
+    SLAMHIP_CHECK(hipHostMalloc(&st->h, cap, hipHostMallocDefault));
+    st->cap = cap;
+  }
+  const bool host_trig = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST, terms = cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL;
+  // table | terms offsets | rotation | rect | sin, cos | request: every part starts on 8 bytes
+  size_t at = 0;
+  const size_t table_at = at;
+  std::memcpy(st->h + at, src.data(), sizeof(PyrSource) * n_src);
+  at += up8(sizeof(PyrSource) * n_src);
+  const size_t off_at = at;
+  long long *h_off = reinterpret_cast<long long *>(st->h + at);
+  size_t total_terms = 0;
+  for (int i = 0; i < n; ++i) {
+    h_off[i] = (long long)total_terms;
+    if (terms) total_terms += (size_t)slots * (size_t)src[request[i]].scan.n;
+  }
+  at += sizeof(long long) * n;
+  const size_t rot_at = at;
+  std::memcpy(st->h + at, rotation, sizeof(double) * n);
+  at += sizeof(double) * n;
+  const size_t rect_at = at;
+  std::memcpy(st->h + at, rect, sizeof(double) * 4 * n);
+  at += sizeof(double) * 4 * n;
+  const size_t sc_at = at;
+  double *h_sc = reinterpret_cast<double *>(st->h + at);
+  if (host_trig)  // (one sincos call per candidate / parent, on its own request's heading)
+    for (int i = 0; i < n; ++i) ::sincos(rotation[i] + src[request[i]].base[2], &h_sc[2 * i], &h_sc[2 * i + 1]);
+  else
+    std::memset(h_sc, 0, sizeof(double) * 2 * n);
+  at += sizeof(double) * 2 * n;
+  const size_t req_at = at;
+  std::memcpy(st->h + at, request, sizeof(int) * n);
+  if (terms && total_terms > st->terms_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (st->d_terms) (void)hipFree(st->d_terms);
+    st->d_terms = nullptr;
+    st->terms_cap = 0;
+    SLAMHIP_CHECK(hipMalloc(&st->d_terms, sizeof(double) * total_terms));
+    st->terms_cap = total_terms;
+  }
+  SLAMHIP_CHECK(hipMemcpyAsync(st->d, st->h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  ManyArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.table = reinterpret_cast<const PyrSource *>(st->d + table_at);
+  a.terms_off = reinterpret_cast<const long long *>(st->d + off_at);
+  a.request = reinterpret_cast<const int *>(st->d + req_at);
+  a.m.rotation = reinterpret_cast<const double *>(st->d + rot_at);
+  a.m.rect = reinterpret_cast<const double *>(st->d + rect_at);
+  a.m.pose_sc = host_trig ? reinterpret_cast<const double *>(st->d + sc_at) : nullptr;
+  st->out_at = in_bytes;
+  double *d_out = reinterpret_cast<double *>(st->d + in_bytes);
+  *d_rect_out = d_out;
+  a.m.scores = d_out + 4 * n_out;
+  a.m.level_out = reinterpret_cast<int *>(d_out + 5 * n_out);
+  a.m.terms = terms ? st->d_terms : nullptr;
+  a.m.n = n;
+  a.m.oie = cfg->oie;
+  a.m.oope = cfg->oope;
+  *out = a;
+  return SLAMHIP_OK;
+}
+
+int pyr_many_fetch(slamhip_ctx *ctx, size_t n_out, bool with_rect, double *rect_out, double *score_out, int *level_out) {
+  PyrManyStage *st = static_cast<PyrManyStage *>(ctx->pyr_many);
+  // rect | score | level per output, as the kernels wrote them; the rectangles are skipped where nobody wrote them
+  const size_t skip = with_rect ? 0 : sizeof(double) * 4 * n_out;
+  SLAMHIP_CHECK(hipMemcpyAsync(st->h + st->out_at + skip, st->d + st->out_at + skip, many_out_bytes(n_out) - skip,
+                               hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  const double *h_out = reinterpret_cast<const double *>(st->h + st->out_at);
+  if (with_rect) std::memcpy(rect_out, h_out, sizeof(double) * 4 * n_out);
+  std::memcpy(score_out, h_out + 4 * n_out, sizeof(double) * n_out);
+  std::memcpy(level_out, h_out + 5 * n_out, sizeof(int) * n_out);
+  return SLAMHIP_OK;
+}
+
 void pyr_free_staging(slamhip_pyramid *p) {
   if (p->d_in) (void)hipFree(p->d_in);
   if (p->d_scores) (void)hipFree(p->d_scores);
@@ -325,6 +515,7 @@ void pyramids_release(slamhip_ctx *ctx) {
     p->ctx = nullptr;
   }
   ctx->pyramids.clear();
+  pyr_many_release(ctx);
 }
 
 }  // namespace slamhip
@@ -471,6 +662,57 @@ int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const sl
   SLAMHIP_CHECK(hipMemcpyAsync(level_out, p->d_levels, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return SLAMHIP_OK;
+}
+
+namespace slamhip {
+// what both multi-request entry points check of their candidates
+int pyr_many_check_batch(int n_requests, int n, const int *request, const double *rotation, const double *rect, bool reversed_ok) {
+  if (!request || !rotation || !rect) return pyr_invalid("null candidate arrays");
+  for (int i = 0; i < n; ++i) {
+    const double *r = rect + 4 * (size_t)i;
+    if (request[i] < 0 || request[i] >= n_requests) return pyr_invalid("a candidate's request is not in the table");
+    if (!std::isfinite(rotation[i]) || !std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]) || !std::isfinite(r[3]))
+      return pyr_invalid("a candidate's rotation or rectangle is not finite");
+    if (!reversed_ok && !(r[0] <= r[1] && r[2] <= r[3])) return pyr_invalid("a candidate's rectangle: not bot <= top and left <= right");
+  }
+  return SLAMHIP_OK;
+}
+}  // namespace slamhip
+
+int slamhip_pyramid_score_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests,
+                                   const slamhip_m3rsm_request *table, int n, const int *request, const double *rotation,
+                                   const double *rect, double *score_out, int *level_out) {
+  std::vector<PyrSource> src;
+  int rc = pyr_many_sources(ctx, cfg, n_requests, table, &src);
+  if (rc) return rc;
+  if (n < 0) return pyr_invalid("bad candidate batch");
+  if (n == 0) return SLAMHIP_OK;
+  if (!score_out || !level_out) return pyr_invalid("null output arrays");
+  rc = pyr_many_check_batch(n_requests, n, request, rotation, rect, false);
+  if (rc) return rc;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  ManyArgs a;
+  double *d_rect_out = nullptr;
+  rc = pyr_many_stage(ctx, cfg, src, n, request, rotation, rect, 1, &a, &d_rect_out);
+  if (rc) return rc;
+  ProfilePairGuard prof;
+  rc = prof.open(ctx, ctx->stream, 0);
+  if (rc) return rc;
+  typedef void (*Kernel)(ManyArgs);
+  const Kernel kernel =
+      pick_cell_model(table[0].pyramid->cell_model, [](auto m) -> Kernel { return k_pyr_score_many<decltype(m)::value>; });
+  SLAMHIP_CHECK(launch_kernel(kernel, dim3(n), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
+  if (a.m.terms) {
+    rc = pyr_launch_sum_sequential_many(a, (size_t)n, 1, ctx->stream);
+    if (rc) return rc;
+  }
+  rc = prof.close();
+  if (rc) return rc;
+  if (ctx->profile) {
+    ctx->prof_launches += 1;
+    for (int i = 0; i < n; ++i) ctx->prof_units += src[request[i]].scan.n;
+  }
+  return pyr_many_fetch(ctx, (size_t)n, false, nullptr, score_out, level_out);
 }
 
 int slamhip_pyramid_build_host(int cell_model, int oie, int width, int height, int origin_x, int origin_y, double scale,

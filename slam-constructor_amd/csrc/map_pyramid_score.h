@@ -34,18 +34,34 @@ namespace slamhip {
 
 constexpr int kPyrThreads = 256;
 
-struct MatchArgs {
+// What a candidate is scored against: a pyramid's level table, a scan and the pose the drifts are added to.  One per
+// launch in the single-request kernels (MatchArgs is one); one per REQUEST, in a table in HBM, in the multi-request ones.
+struct PyrSource {
   const MapView *levels;  // n_levels views, the fine map first
   int n_levels;
   ScanView scan;
+  double base[3];
+};
+
+struct MatchArgs : PyrSource {
   const double *rotation;  // n
   const double *rect;      // n x (bot, top, left, right)
   const double *pose_sc;   // optional n x (sin, cos) of rotation + heading from the host; null = device sincos
-  double base[3];
   double *scores;
   int *level_out;
-  double *terms;  // beam-order sum only: n x scan.n
+  double *terms;  // beam-order sum only: n x scan.n (multi-request: the rows lie where ManyArgs::terms_off says)
   int n, oie, oope;
+};
+
+// The multi-request launches (k_pyr_score_many, k_m3rsm_expand_many): candidate / parent i belongs to request[i], whose
+// scan, levels and base pose are table[request[i]].  m's own PyrSource part is not read.  The requests' beam counts differ,
+// so the per-beam terms of the beam-order sum have no common stride: parent i's rows start at terms + terms_off[i], one row
+// of table[request[i]].scan.n doubles per output of that parent.
+struct ManyArgs {
+  MatchArgs m;
+  const PyrSource *table;
+  const int *request;          // n
+  const long long *terms_off;  // n, beam-order sum only
 };
 
 // map_pyramid.hip
@@ -57,16 +73,42 @@ int pyr_fill_args(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double b
 void pyr_free_staging(slamhip_pyramid *p);
 // the reference's beam-order sum over the stored terms, for every output that has a level
 int pyr_launch_sum_sequential(const MatchArgs &a, size_t n_out, hipStream_t stream);
+// ... of a multi-request launch with `slots` outputs per parent (1: the bounds kernel)
+int pyr_launch_sum_sequential_many(const ManyArgs &a, size_t n_out, int slots, hipStream_t stream);
+
+// The staging of the multi-request launches (slamhip_pyramid_score_requests / _expand_requests), kept by the context:
+// one pinned block and one block in HBM, each the inputs (table | terms offsets | rotation | rect | sin, cos | request)
+// in front of the outputs (rect | score | level per slot), and the terms.
+struct PyrManyStage {
+  char *h = nullptr, *d = nullptr;
+  size_t cap = 0, out_at = 0;  // out_at: where the outputs of the launch staged last begin
+  double *d_terms = nullptr;
+  size_t terms_cap = 0;
+};
+void pyr_many_release(slamhip_ctx *ctx);
+// checks a request table against the context and cfg and fills the sources the kernels read
+int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests, const slamhip_m3rsm_request *req,
+                     std::vector<PyrSource> *out);
+// stages n candidates (request, rotation, rect) of the table, leaving room for n x slots outputs; fills a->m's inputs and
+// outputs, a->table, a->request, a->terms_off.  After the launch: pyr_many_fetch
+int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int n, const int *request,
+                   const double *rotation, const double *rect, int slots, ManyArgs *a, double **d_rect_out);
+// request indices inside the table, finite rotations and rectangles (reversed ones only where the caller lets them through)
+int pyr_many_check_batch(int n_requests, int n, const int *request, const double *rotation, const double *rect, bool reversed_ok);
+int pyr_many_fetch(slamhip_ctx *ctx, size_t n_out, bool with_rect, double *rect_out, double *score_out, int *level_out);
 
 #if defined(__HIPCC__)
-// Match::prob_upper_bound of ONE candidate by the whole workgroup (kPyrThreads threads): rotation index `src` (into
-// a.rotation / a.pose_sc), the rectangle in registers, the result at index `out` of a.scores / a.level_out / a.terms.
-// Every thread of the workgroup calls it with the same arguments.
+// Match::prob_upper_bound of ONE candidate by the whole workgroup (kPyrThreads threads): levels, scan and base pose
+// from `q` (the launch's own MatchArgs, or the candidate's entry of the request table, read once by its caller),
+// rotation index `src` (into a.rotation / a.pose_sc), the rectangle in registers, the result at index `out` of a.scores /
+// a.level_out, the per-beam terms (beam-order sum; else `terms` is null) from terms[terms_at] on.  Every thread of the
+// workgroup calls it with the same arguments.
 template <int MODEL>
-__device__ __forceinline__ void pyr_score_one(const MatchArgs &a, size_t src, size_t out, double bot, double top, double left,
-                                              double right, double *s_trig, double *s_part) {
+__device__ __forceinline__ void pyr_score_one(const PyrSource &q, const MatchArgs &a, size_t src, size_t out, double *terms,
+                                              size_t terms_at, double bot, double top, double left, double right, double *s_trig,
+                                              double *s_part) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int n = a.scan.n;
+  const int n = q.scan.n;
   const double vside = top - bot, hside = right - left;
   // (a rectangle that is no rectangle -- NaN, infinite or reversed -- has no level and no window: NaN, level -1)
   if (!(vside >= 0.0 && hside >= 0.0 && vside < __builtin_inf() && hside < __builtin_inf())) {
@@ -79,17 +121,17 @@ __device__ __forceinline__ void pyr_score_one(const MatchArgs &a, size_t src, si
   // RescalableCachingGridMap::rescale(std::max(vside, hside)): the first level whose scale holds the target
   const double target = vside < hside ? hside : vside;
   int lv = 0;
-  while (lv < a.n_levels - 1 && !(target <= a.levels[lv].scale)) ++lv;
-  const MapView map = a.levels[lv];
+  while (lv < q.n_levels - 1 && !(target <= q.levels[lv].scale)) ++lv;
+  const MapView map = q.levels[lv];
   // LightWeightRectangle::center() added to the pose
-  const double x = a.base[0] + (left + hside / 2), y = a.base[1] + (bot + vside / 2);
+  const double x = q.base[0] + (left + hside / 2), y = q.base[1] + (bot + vside / 2);
   if (t == 0) {
     double sn, cs;
     if (a.pose_sc) {
       sn = a.pose_sc[2 * src];
       cs = a.pose_sc[2 * src + 1];
     } else {
-      sincos(a.rotation[src] + a.base[2], &sn, &cs);
+      sincos(a.rotation[src] + q.base[2], &sn, &cs);
     }
     s_trig[0] = sn;
     s_trig[1] = cs;
@@ -99,13 +141,13 @@ __device__ __forceinline__ void pyr_score_one(const MatchArgs &a, size_t src, si
   const double half_v = (top - bot) / 2, half_h = (right - left) / 2;
   double acc = 0.0;
   for (int b = t; b < n; b += kPyrThreads) {
-    const double ca = a.scan.cos_a[b], sa = a.scan.sin_a[b], r = a.scan.range[b];
+    const double ca = q.scan.cos_a[b], sa = q.scan.sin_a[b], r = q.scan.range[b];
     const double c = cs * ca - sn * sa;
     const double s = sn * ca + cs * sa;
     const double ox = x + r * c, oy = y + r * s;
     const double pr = window_probability<MODEL>(map, a.oie, a.oope, half_v, half_h, ox, oy);
-    const double term = pr * a.scan.weight[b] * a.scan.factor[b];
-    if (a.terms) a.terms[out * n + b] = term;
+    const double term = pr * q.scan.weight[b] * q.scan.factor[b];
+    if (terms) terms[terms_at + b] = term;
     acc = acc + term;
   }
   acc = wave_xor_sum(acc);
@@ -113,7 +155,7 @@ __device__ __forceinline__ void pyr_score_one(const MatchArgs &a, size_t src, si
   __syncthreads();
   if (t == 0) {
     const double total = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-    a.scores[out] = (a.scan.tot_w == 0.0) ? __builtin_nan("") : total / a.scan.tot_w;
+    a.scores[out] = (q.scan.tot_w == 0.0) ? __builtin_nan("") : total / q.scan.tot_w;
     a.level_out[out] = lv;
   }
 }

@@ -1731,9 +1731,109 @@ int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
   return SLAMHIP_OK;
 }
 
+// Several requests in one search (m3rsm::run_many): the root layers of all requests in one
+// slamhip_pyramid_score_requests launch, every super-step one slamhip_pyramid_expand_requests launch over parents of
+// whichever requests the shared queue holds on top.
+int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req, int *out_request, double out_delta[3],
+                     double *out_prob) {
+  slamhip_matcher::M3rsm &s = *m->m3;
+  slamhip_ctx *ctx = m->ctx;
+  m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
+  s.trace.clear();
+  s.res = m3rsm::Result{};
+  {
+    std::vector<PyrSource> src;  // (checked before anything runs: the launches check again, they are entry points too)
+    const int rc = pyr_many_sources(ctx, &m->cfg, n_requests, req, &src);
+    if (rc) return rc;
+  }
+  const double t0 = MatchJob::now_us();
+  const m3rsm::ScoreManyFn roots = [&](int n, const int *rq, const double *rot, const double *rect, double *score, int *level) {
+    return slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, n, rq, rot, rect, score, level);
+  };
+  const m3rsm::ExpandManyFn expand = [&](int n, const int *rq, const double *rot, const double *rect, int depth,
+                                         double *slot_rect, double *slot_score, int *slot_level) {
+    return slamhip_pyramid_expand_requests(ctx, &m->cfg, n_requests, req, n, rq, rot, rect, s.cfg.translation_step, depth,
+                                           slot_rect, slot_score, slot_level);
+  };
+  // without the expand kernel (speculation 0, 0): as for the lone match, a bounds launch per popped match
+  const m3rsm::ExpandManyFn per_pop = [&](int n, const int *rq, const double *rot, const double *rect, int, double *slot_rect,
+                                          double *slot_score, int *slot_level) {
+    const m3rsm::Rect parent{rect[0], rect[1], rect[2], rect[3]};
+    m3rsm::Rect kids[m3rsm::kMaxChildren] = {};
+    const int nk = n == 1 ? m3rsm::children(parent, s.cfg.translation_step, kids) : 0;
+    int k_req[m3rsm::kMaxChildren];
+    double k_rot[m3rsm::kMaxChildren], k_rect[4 * m3rsm::kMaxChildren];
+    for (int c = 0; c < m3rsm::kMaxChildren; ++c) {
+      k_req[c] = rq[0];
+      k_rot[c] = rot[0];
+      const m3rsm::Rect &r = kids[c < nk ? c : 0];
+      const double nan = std::numeric_limits<double>::quiet_NaN();
+      const double v[4] = {c < nk ? r.bot : nan, c < nk ? r.top : nan, c < nk ? r.left : nan, c < nk ? r.right : nan};
+      for (int q = 0; q < 4; ++q) k_rect[4 * c + q] = slot_rect[4 * c + q] = v[q];
+      slot_score[c] = nan;
+      slot_level[c] = -1;
+    }
+    return nk ? slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, nk, k_req, k_rot, k_rect, slot_score, slot_level) : 0;
+  };
+  m3rsm::Config run_cfg = s.cfg;
+  if (s.per_pop) run_cfg.width = run_cfg.depth = 1;
+  const int erc = m3rsm::run_many(run_cfg, n_requests, roots, s.per_pop ? per_pop : expand, &s.res, &s.trace);
+  m->t_stage_us = 0;
+  m->t_score_us = MatchJob::now_us() - t0;
+  m->job.scorer_calls = s.res.scorer_calls;
+  m->job.poses_evaluated = s.res.scored;
+  m->job.launches = s.res.launches;
+  switch (erc) {
+    case m3rsm::kOk: break;
+    case m3rsm::kErrCallback: return s.res.callback_rc;
+    case m3rsm::kErrSuperSteps:
+      set_error("the multi-resolution match reached its bound on super-steps");
+      return SLAMHIP_ERR_UNSUPPORTED;
+    case m3rsm::kErrNoMatch:
+      *out_request = -1;
+      out_delta[0] = out_delta[1] = out_delta[2] = 0.0;
+      *out_prob = std::numeric_limits<double>::quiet_NaN();
+      return SLAMHIP_OK;
+    default:
+      set_error("internal: the multi-resolution engine failed (an expand launch did not deliver a child)");
+      return SLAMHIP_ERR_STATE;
+  }
+  *out_request = s.res.request;
+  for (int k = 0; k < 3; ++k) out_delta[k] = s.res.delta[k];
+  *out_prob = s.res.prob;
+  if (m->has_obs && m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, out_delta, s.res.prob);
+  return SLAMHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int slamhip_matcher_m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req, int *out_request,
+                                     double out_delta[3], double *out_prob) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (!out_request || !out_delta || !out_prob) return invalid_arg("null outputs");
+  return m3rsm_match_many(m, n_requests, req, out_request, out_delta, out_prob);
+}
+
+int slamhip_matcher_m3rsm_trace_many(slamhip_matcher *m, int cap, double *rows, int *n) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (cap < 0 || (cap > 0 && !rows)) return invalid_arg("bad trace buffer");
+  const std::vector<m3rsm::Call> &t = m->m3->trace;
+  if (n) *n = (int)t.size();
+  for (size_t i = 0; i < std::min((size_t)cap, t.size()); ++i) {
+    double *r = rows + 8 * i;
+    r[0] = (double)t[i].request;
+    r[1] = t[i].rotation;
+    r[2] = t[i].rect.bot;
+    r[3] = t[i].rect.top;
+    r[4] = t[i].rect.left;
+    r[5] = t[i].rect.right;
+    r[6] = t[i].score;
+    r[7] = (double)t[i].level;
+  }
+  return SLAMHIP_OK;
+}
 
 int slamhip_matcher_create_m3rsm(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, slamhip_pyramid *pyramid, double max_x_error,
                                  double max_y_error, double max_th_error, double angle_step, double translation_step,

@@ -418,6 +418,7 @@ struct slamhip_ctx {
   size_t scan_gen_cap = 0;
   std::vector<double> scan_gen_stage;  // ... and its host side: what goes up and what comes back, one copy each
   std::vector<void *> pyramids;  // the slamhip_pyramid objects made over this context's maps (map_pyramid.hip)
+  void *pyr_many = nullptr;      // PyrManyStage: the staging of the multi-request pyramid launches (map_pyramid.hip)
   bool low_latency = true;
   bool stage_poses = false;  // copy poses to HBM first instead of reading them over PCIe
   // slamhip_ctx_set_option: equivalent execution paths (defaults = what is measured)

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <memory>
 #include <vector>
 
@@ -101,6 +102,75 @@ private:
   int _map_id;
   slamhip_pyramid *_pyr = nullptr;
   std::shared_ptr<HipResidentMapView> _view;
+};
+
+// The request surface of M3RSMEngine (add_scan_matching_request :291-316, then the matcher's loop around
+// next_best_match, bf_multi_res_scan_matcher.h:44-65) over HipM3rsmMaps: any number of (pose, scan, map) requests, one
+// search over all of them (slamhip_matcher_m3rsm_match_many), the best match of any request as the answer.  `matcher`
+// (made by HipM3rsmMap::matcher: its limits, steps and cfg hold for every request) and the maps outlive the engine; the
+// maps share one context.  Request k keeps its filtered scan in scan slot first_scan_slot + k.
+class HipM3rsmEngine {
+public:
+  struct BestMatch {
+    int request = -1;  // -1: no request had a valid match
+    RobotPoseDelta pose_delta{0, 0, 0};
+    double prob_upper_bound = std::numeric_limits<double>::quiet_NaN();
+    bool is_valid() const { return request >= 0; }
+  };
+
+  HipM3rsmEngine(slamhip_ctx *ctx, slamhip_matcher *matcher, std::shared_ptr<ScanProbabilityEstimator> spe,
+                 int weighting = 0, const HipScanTrig &trig = HipScanTrig{}, int first_scan_slot = 0)
+      : _ctx{ctx}, _matcher{matcher}, _spe{spe}, _weighting{weighting}, _trig{trig}, _first_slot{first_scan_slot} {}
+
+  void reset_engine_state() { _requests.clear(); }
+
+  // the scan is filtered by the estimator against the map's fine level, as add_scan_matching_request does, and stored
+  void add_scan_matching_request(const RobotPose &pose, const LaserScan2D &raw_scan, HipM3rsmMap &map) {
+    const LaserScan2D scan = _spe->filter_scan(raw_scan, pose, map.map());
+    const auto &pts = scan.points();
+    const int n = int(pts.size());
+    std::vector<double> r(n), a(n), f(n), w(n), c(n), s(n);
+    for (int i = 0; i < n; ++i) {
+      r[i] = pts[i].range();
+      a[i] = pts[i].angle();
+      f[i] = pts[i].factor();
+    }
+    slamhip_or_die(slamhip_scan_weights(_weighting, n, r.data(), a.data(), w.data()), "scan_weights");
+    if (_trig.mode == SLAMHIP_TRIG_CACHED)
+      slamhip_or_die(slamhip_beam_trig_cached(n, a.data(), _trig.a_min, _trig.a_max, _trig.a_inc, c.data(), s.data()),
+                     "beam_trig_cached");
+    else
+      slamhip_or_die(slamhip_beam_trig_raw(n, a.data(), c.data(), s.data()), "beam_trig_raw");
+    slamhip_m3rsm_request q;
+    q.pyramid = map.pyramid();
+    q.scan_slot = _first_slot + int(_requests.size());
+    q.init_pose[0] = pose.x;
+    q.init_pose[1] = pose.y;
+    q.init_pose[2] = pose.theta;
+    slamhip_or_die(slamhip_scan_store(_ctx, q.scan_slot, n, r.data(), c.data(), s.data(), w.data(), f.data()), "scan_store");
+    _requests.push_back(q);
+  }
+
+  size_t requests_nm() const { return _requests.size(); }
+
+  // BruteForceMultiResolutionScanMatcher::process_scan's loop over every request added since the last reset
+  BestMatch best_match() {
+    BestMatch best;
+    double delta[3] = {0, 0, 0};
+    slamhip_or_die(slamhip_matcher_m3rsm_match_many(_matcher, int(_requests.size()), _requests.data(), &best.request, delta,
+                                                    &best.prob_upper_bound), "m3rsm_match_many");
+    best.pose_delta = RobotPoseDelta{delta[0], delta[1], delta[2]};
+    return best;
+  }
+
+private:
+  slamhip_ctx *_ctx;
+  slamhip_matcher *_matcher;
+  std::shared_ptr<ScanProbabilityEstimator> _spe;
+  int _weighting;
+  HipScanTrig _trig;
+  int _first_slot;
+  std::vector<slamhip_m3rsm_request> _requests;
 };
 
 #endif  // SLAMHIP_M3RSM_MAP_H
