@@ -421,6 +421,7 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
         // ---- the chain is over: the last workgroup reports (every lane's trace stores first, then the result, then
         // the flag the host spins on)
         const HcState &w = s_st;  // (the bookkeeping half: this thread's own stores of the replay)
+        const long long t_over = SLAMHIP_STAMPS_ON(ap->stamps != nullptr) ? (long long)wall_clock64() : 0ll;
         __threadfence_system();
         HcHostOut *h = host;
         h->pose[0] = e.x;
@@ -436,6 +437,12 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
         h->gm_cy = -1;
         h->gm_prob = -1.0;
         __hip_atomic_store(&h->done_seq, ap->epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (SLAMHIP_STAMPS_ON(ap->stamps != nullptr) && blockIdx.y == 0) {
+          // (testing builds, spare stamp 6 of super-steps 1 and 2: the chain seen to be over, and the flag arrived)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          ap->stamps[8 + 6] = t_over;
+          ap->stamps[16 + 6] = wall_clock64();
+        }
         if (ap->n_done) {
           // a batch: the last chain to end tells the host.  This chain's result is on its way to the host BEFORE
           // it counts itself, so whoever sees the full count may announce everybody's

@@ -186,6 +186,7 @@ struct slamhip_matcher {
   int debug_resident_mute = 0;  // testing (slamhip_matcher_debug_resident_mute)
   int debug_trace_cap = 0;      // testing (slamhip_matcher_debug_trace_cap): pretend the trace buffer is this small
   int debug_fail_next = 0;      // testing (slamhip_matcher_debug_fail_next): injected failures left
+  double debug_ends[5] = {0, 0, 0, 0, 0};  // testing: the host's clock at the ends of a lone match (SLAMHIP_MATCH_END)
   // ---- hill climbing kept on the device (hc_chain.h): parameters of the enumerator, device / pinned blocks
   struct HcChain {
     unsigned max_failed = 0;
@@ -605,6 +606,16 @@ int chain_prepare(slamhip_matcher *m) {
   return SLAMHIP_OK;
 }
 
+// testing builds: the host's clock at the ends of a lone hill-climbing match behind slamhip_matcher_process_raw_scan --
+// 0 entry, 1 filter and staging done, 2 the co-resident launch called, 3 the launch call returned, 4 the result seen.
+// slamhip_matcher_timing of such a match without an observer then reports build_us = 0 -> 1, stage_us = 1 -> 2 and
+// replay_us = 3 -> 4 (tools/match_ends.py); the shipped library reads no clock for them
+#ifdef SLAMHIP_TESTING
+#define SLAMHIP_MATCH_END(m, i) ((m)->debug_ends[i] = slamhip::MatchJob::now_us())
+#else
+#define SLAMHIP_MATCH_END(m, i) ((void)0)
+#endif
+
 int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
                        double *out_prob, bool resident) {
   slamhip_ctx *ctx = m->ctx;
@@ -713,8 +724,10 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
         return SLAMHIP_OK;
       },
       [&](hipEvent_t e0, hipEvent_t e1) {
+        SLAMHIP_MATCH_END(m, 2);
         const hipError_t e = gm ? launch_hc_chain_resident_gm(a, m->chain_nt, ctx->stream, e0, e1)
                                 : launch_hc_chain_resident(a, cell_model, m->chain_nt, ctx->stream, e0, e1);
+        SLAMHIP_MATCH_END(m, 3);
         scan_record_finish(ctx);  // (the host's copies of the raw scan's weights / factors: while the GPU runs)
         return e;
       },
@@ -741,6 +754,7 @@ int chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
       },
       LoneChainText{"internal: the co-resident chain ended without publishing a result", "co-resident hill-climbing chain",
                     "hill-climbing chain did not end", "hill-climbing chain kernel"});
+  SLAMHIP_MATCH_END(m, 4);
   if (ctx->scan_pending.active) {
     // the RAW launch has reported: every workgroup read its beams before its first granule, the result needed every
     // granule, and the bookkeeping workgroup wrote the block behind the first super-step -- the staging buffer's turn is
@@ -2134,12 +2148,14 @@ int slamhip_matcher_process_raw_scan(slamhip_matcher *m, int map_id, const slamh
                                      double out_delta[3], double *out_prob, int *kept_n) {
   if (!m || !scan || !init_pose || !out_delta || !out_prob) return invalid_arg("null argument");
   int kept = 0;
+  SLAMHIP_MATCH_END(m, 0);
   // the first half of slamhip_scan_filter_upload: filter and staging.  Who writes the scan block is decided where the
   // match is launched: the lone co-resident hill-climbing chain does it itself (chain_process_scan), every other path
   // goes through scan_assemble_now before its first kernel.
   int rc = scan_filter_stage(m->ctx, map_id, scan->n, scan->range, scan->angle, scan->is_occ, scan->factor, scan->trig_mode,
                              scan->a_min, scan->a_max, scan->a_inc, init_pose, scan->skip_rate, scan->max_range,
                              scan->bounded, scan->weighting, &kept, nullptr);
+  SLAMHIP_MATCH_END(m, 1);
   if (kept_n) *kept_n = kept;
   if (rc) return rc;
   if (kept == 0) {  // 0 / 0 for every candidate (weighted_mean_point_probability_spe.h:126-132): nothing is accepted
@@ -2149,6 +2165,13 @@ int slamhip_matcher_process_raw_scan(slamhip_matcher *m, int map_id, const slamh
     return SLAMHIP_OK;
   }
   rc = slamhip_matcher_process_scan(m, map_id, init_pose, out_delta, out_prob);
+#ifdef SLAMHIP_TESTING
+  if (!rc && m->is_hc && !m->has_obs && m->debug_ends[2] > m->debug_ends[1]) {
+    m->job.t_build_us = m->debug_ends[1] - m->debug_ends[0];
+    m->t_stage_us = m->debug_ends[2] - m->debug_ends[1];
+    m->job.t_replay_us = m->debug_ends[4] - m->debug_ends[3];
+  }
+#endif
   // (a match that failed before it launched anything: the scan is the current one all the same, its block gets written)
   const int arc = scan_assemble_now(m->ctx);
   return rc ? rc : arc;

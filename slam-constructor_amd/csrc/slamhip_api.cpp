@@ -14,6 +14,7 @@
 
 #include "slamhip_internal.h"
 #include "libm_exact.h"
+#include "scan_filter.h"
 
 namespace slamhip {
 
@@ -1515,31 +1516,32 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
   }
   // ---- filter_scan: keeps point i iff (skip_rate == 0 or i % skip_rate == 0), occupied, its end point's cell in the
   // map, and not beyond the usable range (Q8 - Q10)
-  constexpr double eps = std::numeric_limits<double>::epsilon();
   std::vector<int> &kept = sp.kept_next;  // (sp.kept stays the current scan's until this one has taken its place)
-  kept.clear();
-  const bool cut = 0.0 < max_range + eps;  // (a usable range is set at all)
-  double sb = 0, cb = 1;
-  if (bounded) ::sincos(pose[2], &sb, &cb);
-  for (int i = 0; i < n; ++i) {
-    if (skip_rate && (unsigned(i) % skip_rate)) continue;
-    if (is_occ && !is_occ[i]) continue;
-    const bool too_far = cut && (max_range < range[i] + eps);
-    if (too_far) continue;
-    if (bounded) {
-      double c, s;
-      if (trig_mode == SLAMHIP_TRIG_CACHED) {
-        c = cb * sp.cos_a[i] - sb * sp.sin_a[i];
-        s = sb * sp.cos_a[i] + cb * sp.sin_a[i];
-      } else {
-        ::sincos(pose[2] + angle[i], &s, &c);
-      }
-      const double wx = pose[0] + range[i] * c, wy = pose[1] + range[i] * s;
-      const int ix = (int)std::floor(wx / m->scale) + m->origin_x, iy = (int)std::floor(wy / m->scale) + m->origin_y;
-      if (!(0 <= ix && ix < m->width && 0 <= iy && iy < m->height)) continue;
-    }
-    kept.push_back(i);
+  // (scan_filter.cpp: a branch-free pass that writes one byte per point, then the bytes compacted into the index list)
+  ScanFilterArgs fa{};
+  fa.n = n;
+  fa.range = range;
+  fa.angle = angle;
+  fa.is_occ = is_occ;
+  fa.skip_rate = skip_rate;
+  fa.max_range = max_range;
+  fa.bounded = bounded ? 1 : 0;
+  if (bounded) {
+    fa.trig_raw = trig_mode == SLAMHIP_TRIG_CACHED ? 0 : 1;
+    fa.cos_a = sp.cos_a.data();
+    fa.sin_a = sp.sin_a.data();
+    for (int q = 0; q < 3; ++q) fa.pose[q] = pose[q];
+    fa.scale = m->scale;
+    fa.origin_x = m->origin_x;
+    fa.origin_y = m->origin_y;
+    fa.width = m->width;
+    fa.height = m->height;
+    if (fa.trig_raw) sp.filter_trig.resize(2 * (size_t)n);
   }
+  sp.filter_mask.resize(n);
+  kept.resize(n);
+  scan_filter_mask(fa, sp.filter_mask.data(), sp.filter_trig.data());
+  kept.resize(scan_filter_compact(sp.filter_mask.data(), n, kept.data()));
   const int k = (int)kept.size();
   if (kept_n) *kept_n = k;
   if (kept_idx) std::memcpy(kept_idx, kept.data(), sizeof(int) * k);
@@ -1559,22 +1561,28 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
   ScanAssembleArgs as{};
   double *r_ = st;
   as.h_range = r_;
+  // (the rows that are gathered through the kept list -- ranges, factors, the viny weights -- in ONE sweep over it:
+  // scan_filter_fill)
+  double *f_ = factor ? st + 2 * c : nullptr, *w_viny = nullptr;
+  if (weighting == 1) {
+    ctx->h_weight.resize(k);
+    w_viny = ctx->h_weight.data();
+  }
   if (k == n) {
     std::memcpy(r_, range, sizeof(double) * k);
   } else {
     int *k_ = reinterpret_cast<int *>(st + c);
-    for (int q = 0; q < k; ++q) r_[q] = range[kept[q]];
     std::memcpy(k_, kept.data(), sizeof(int) * k);
     as.h_kept = k_;
   }
+  const double tot_viny =
+      scan_filter_fill(k, kept.data(), range, factor, sp.viny_f.data(), k == n ? nullptr : r_, f_, w_viny);
   // ... and the host's own copies of weights and factors (what the commit records; the device makes the same bits),
   // touched only once nothing can fail any more that would leave the scan before as the current one
   // (those that nothing in front of the launch needs are made behind it, while the GPU runs: scan_record_finish)
   if (weighting == 0) {
     as.w_even = 1.0 / k;  // EvenSPW (:21-32)
   } else if (weighting == 1) {
-    ctx->h_weight.resize(k);
-    for (int q = 0; q < k; ++q) ctx->h_weight[q] = sp.viny_f[kept[q]] * std::sqrt(r_[q]);
     as.tab_viny = ctx->d_scan_tab + 2 * (size_t)ctx->scan_tab_cap;
   } else {
     sp.a.resize(k);
@@ -1587,11 +1595,7 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
     std::memcpy(w_, sp.w.data(), sizeof(double) * k);
     as.h_weight = w_;
   }
-  if (factor) {
-    double *f_ = st + 2 * c;
-    for (int q = 0; q < k; ++q) f_[q] = factor[kept[q]];
-    as.h_factor = f_;
-  }
+  as.h_factor = f_;
   as.tab_cos = ctx->d_scan_tab;
   as.tab_sin = ctx->d_scan_tab + (size_t)ctx->scan_tab_cap;
   as.dst = ctx->d_scan;
@@ -1599,7 +1603,7 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
   as.n = k;
   int turn = 0;
   const double tot_w = weighting == 0   ? scan_total_weight_even(k, as.w_even)
-                       : weighting == 1 ? scan_total_weight(ctx->h_weight.data(), k)
+                       : weighting == 1 ? tot_viny  // (the same additions in the same order)
                                         : scan_total_weight(as.h_weight, k);
   const unsigned seq = scan_stage_turnover(ctx, k, c, tot_w, &turn);
   // the kept points' angles, for SLAMHIP_POSE_TRIG_RAW_EXACT: sp.angle[sp.kept[q]], written out when an exact call asks

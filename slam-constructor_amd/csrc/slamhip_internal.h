@@ -352,6 +352,8 @@ struct slamhip_ctx {
     std::vector<double> r, a, c, s, w, f;
     std::vector<int> kept;       // raw indices of the CURRENT scan's points (of the last call that uploaded one)
     std::vector<int> kept_next;  // ... of the call under way: becomes `kept` once its scan is the current one
+    std::vector<unsigned char> filter_mask;  // scan_filter.cpp: one byte per raw point ...
+    std::vector<double> filter_trig;         // ... and the per-beam cosines | sines of SLAMHIP_TRIG_RAW on a bounded map
   } scan_prep;
   // ... and the same three per-beam arrays resident in HBM (cos | sin | viny_f, scan_tab_cap doubles each), where
   // k_scan_assemble gathers them: uploaded when scan_prep recomputes, never by a context that is not given raw scans
