@@ -733,6 +733,40 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
  * chain's super-steps); on_device_chain: 1 when the match ran in the shared launches */
 int slamhip_matcher_batch_stats(slamhip_matcher *m, int job, long long *scorer_calls, long long *poses_evaluated,
                                 long long *super_steps, int *on_device_chain);
+/* K RAW scans in, K matches in the shared launches: slamhip_matcher_process_raw_scan for K robots / replicas.  Per job
+ * the host runs the lone call's filter against the job's map window and initial pose and makes the ahr weights; what
+ * is new with each scan (kept ranges, kept indices where a beam was dropped, factors where given, ahr weights) goes
+ * into ONE pinned arena, one kernel launch assembles all the scan blocks in HBM from it and from per-beam tables kept
+ * resident per distinct scanner (n, angles, trig_mode, a_min / a_max / a_inc: jobs with equal scanners share a table, a
+ * later call with the same scanners uploads none -- slamhip_scan_table_uploads counts these uploads too), and the
+ * chains of slamhip_matcher_process_scan_batch run behind it.
+ *  - Per-job results: job k gets the delta, probability, kept count (kept_n[k]; kept_n may be NULL), observer event
+ *    sequence and slamhip_matcher_batch_stats counters of a lone slamhip_matcher_process_raw_scan on the same inputs,
+ *    bit for bit.  Observer sequences run job 0 first, each closed by on_matching_end.
+ *  - A job whose filter keeps no point is what the lone call makes of it: probability NaN, delta 0, no observer call.
+ *    It takes no part in the launches; the other jobs are unaffected.
+ *  - Jobs the chains do not cover run one after another through the lone raw call, in job order (a Monte-Carlo
+ *    matcher's engine stream is that of the sequence of lone calls): a matcher that is not hill climbing, a window or
+ *    GMapping OOPE, the beam-order sum, a job with more than 4096 kept points, n_jobs == 1 (or one non-empty job).
+ *  - Errors are those of slamhip_matcher_process_scan_batch and of the lone raw call -- unknown map, maps of different
+ *    cell models (or GMAPPING cells) in the shared launches, a trig_mode that is neither provider, an angle outside
+ *    the cached provider's table, n <= 0, null arrays, an unknown weighting --, found before anything is launched; the
+ *    matcher's last-batch state (slamhip_matcher_batch_stats) stays that of the batch before.
+ *  - Stored scan slots are never touched.  The context's selected or uploaded scan is not touched by the shared
+ *    launches; where a job went through the lone call, a selected slot is selected again afterwards and an uploaded
+ *    scan is invalidated (its buffer has been overwritten), as slamhip_matcher_process_scan_batch leaves them.
+ *  - A BF_M3RSM matcher is refused (SLAMHIP_ERR_INVALID), as by slamhip_matcher_process_scan_batch. */
+typedef struct {
+  int map_id;
+  slamhip_raw_scan scan;   /* as for slamhip_matcher_process_raw_scan */
+  double init_pose[3];
+} slamhip_raw_match_job;
+int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const slamhip_raw_match_job *jobs,
+                                           double *out_deltas, double *out_probs, int *kept_n);
+/* job's scan block of the last raw batch, as slamhip_scan_download gives the current scan: *n = its kept count, out5
+ * five rows of cap doubles (cap 0: only *n).  A job that went through the lone call has no block in the batch's arena:
+ * *n is set, asking for the rows is an error. */
+int slamhip_matcher_batch_scan_download(slamhip_matcher *m, int job, int cap, double *out5, int *n);
 /* counters of the last process_scan: scorer calls the reference would have made
  * (= on_scan_test events), poses actually evaluated on the GPU, launches */
 int slamhip_matcher_stats(slamhip_matcher *m, long long *scorer_calls, long long *poses_evaluated,

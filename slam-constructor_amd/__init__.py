@@ -67,7 +67,8 @@ slamhip_pyramid_expand_matches slamhip_pyramid_expand_matches_device slamhip_mat
 slamhip_matcher_set_m3rsm_speculation slamhip_matcher_m3rsm_trace
 slamhip_pyramid_score_requests slamhip_pyramid_expand_requests slamhip_matcher_m3rsm_match_many
 slamhip_matcher_m3rsm_trace_many
-slamhip_scan_table_uploads slamhip_scan_download""".split()
+slamhip_scan_table_uploads slamhip_scan_download
+slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -1352,6 +1353,96 @@ class RawScan(C.Structure):
     _fields_ = [("n", C.c_int), ("range", _dp), ("angle", _dp), ("is_occ", _ip), ("factor", _dp), ("trig_mode", C.c_int),
                 ("a_min", C.c_double), ("a_max", C.c_double), ("a_inc", C.c_double), ("skip_rate", C.c_uint),
                 ("max_range", C.c_double), ("bounded", C.c_int), ("weighting", C.c_int)]
+
+
+class RawMatchJob(C.Structure):
+    """slamhip_raw_match_job: one match of slamhip_matcher_process_raw_scan_batch."""
+    _fields_ = [("map_id", C.c_int), ("scan", RawScan), ("init_pose", C.c_double * 3)]
+
+
+def _make_raw_batch(self, jobs):
+    """Argument block of process_raw_scan_batch, made once for a list of jobs = dicts(map_id, range, angle, init_pose[,
+    is_occ, factor, trig_mode, a_min, a_max, a_inc, skip_rate, max_range, bounded, weighting]) -- the keywords of
+    make_raw_process_scan: the arrays are kept alive by the returned object."""
+    arr = (RawMatchJob * max(len(jobs), 1))()
+    keep = []
+    for k, j in enumerate(jobs):
+        rng, ang = _f64(j["range"]), _f64(j["angle"])
+        assert rng.size == ang.size
+        occ = np.ascontiguousarray(j["is_occ"], dtype=np.int32) if j.get("is_occ") is not None else None
+        fac = _f64(j["factor"]) if j.get("factor") is not None else None
+        keep += [rng, ang, occ, fac]
+        arr[k].map_id = int(j["map_id"])
+        for q in range(3):
+            arr[k].init_pose[q] = float(j["init_pose"][q])
+        arr[k].scan = RawScan(rng.size, _d(rng), _d(ang), occ.ctypes.data_as(_ip) if occ is not None else None,
+                              _d(fac) if fac is not None else None, int(j.get("trig_mode", TRIG_RAW)),
+                              float(j.get("a_min", 0.0)), float(j.get("a_max", 0.0)), float(j.get("a_inc", 1.0)),
+                              int(j.get("skip_rate", 0)), float(j.get("max_range", -1.0)), int(bool(j.get("bounded", False))),
+                              {"even": 0, "viny": 1, "ahr": 2}[j.get("weighting", "even")])
+    n = len(jobs)
+    return dict(raw_arr=arr, keep=keep, n=n, deltas=np.zeros((n, 3)), probs=np.zeros(n), kept=np.zeros(max(n, 1), np.int32))
+
+
+def _process_raw_scan_batch(self, jobs, trace=False):
+    """K raw scans, K matches in shared launches (slamhip_matcher_process_raw_scan_batch).  jobs: a list of dicts (see
+    make_raw_batch) or a block make_raw_batch returned.  Returns a list of dicts like process_scan_batch's plus `kept`,
+    the points the job's filter kept."""
+    blk = jobs if isinstance(jobs, dict) and "raw_arr" in jobs else self.make_raw_batch(jobs)
+    recs = None
+    if trace:
+        recs = [dict(poses=[], scores=[], accepted=[])]
+
+        def on_test(_u, p, s):
+            recs[-1]["poses"].append((p[0], p[1], p[2]))
+            recs[-1]["scores"].append(s)
+            recs[-1]["accepted"].append(0)
+
+        def on_update(_u, p, s):
+            recs[-1]["accepted"][-1] = 1
+
+        def on_end(_u, d, s):
+            recs.append(dict(poses=[], scores=[], accepted=[]))
+
+        self._obs = Observer(None, OBS_FN(on_test), OBS_FN(on_update), OBS_FN(on_end))
+        _check(self.L.slamhip_matcher_set_observer(self.h, C.byref(self._obs)))
+        self._obs_cleared = False
+    elif not self._obs_cleared:
+        _check(self.L.slamhip_matcher_set_observer(self.h, None))
+        self._obs_cleared = True
+    fn = self.L.slamhip_matcher_process_raw_scan_batch
+    fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(RawMatchJob), _dp, _dp, _ip]
+    rc = fn(self.h, blk["n"], blk["raw_arr"], _d(blk["deltas"]), _d(blk["probs"]), blk["kept"].ctypes.data_as(_ip))
+    if rc:
+        _check(rc)
+    out, at = [], 0
+    for k in range(blk["n"]):
+        o = dict(prob=float(blk["probs"][k]), delta=blk["deltas"][k].copy(), kept=int(blk["kept"][k]))
+        if recs is not None:
+            # (a job that kept nothing shows the observer nothing, not even an end: it has no record of its own)
+            r = recs[at] if o["kept"] > 0 else dict(poses=[], scores=[], accepted=[])
+            at += 1 if o["kept"] > 0 else 0
+            o.update(poses=np.array(r["poses"]).reshape(-1, 3), scores=np.array(r["scores"]),
+                     accepted=np.array(r["accepted"], dtype=np.int32), n_calls=len(r["scores"]))
+        out.append(o)
+    return out
+
+
+def _batch_scan_download(self, job):
+    """Job's scan block of the last raw batch as five rows [5, kept] (range, cos, sin, weight, factor), back from HBM."""
+    fn = self.L.slamhip_matcher_batch_scan_download
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _ip]
+    n = C.c_int(-1)
+    _check(fn(self.h, int(job), 0, None, C.byref(n)))
+    out = np.full((5, max(n.value, 1)), np.nan)
+    if n.value > 0:
+        _check(fn(self.h, int(job), out.shape[1], _d(out), C.byref(n)))
+    return out[:, :max(n.value, 0)]
+
+
+Matcher.make_raw_batch = _make_raw_batch
+Matcher.process_raw_scan_batch = _process_raw_scan_batch
+Matcher.batch_scan_download = _batch_scan_download
 
 
 class GmappingFilter:

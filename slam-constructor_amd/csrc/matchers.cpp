@@ -140,6 +140,25 @@ struct HcBatch : slamhip::ChainSet<slamhip::HcResidentCtl, slamhip::HcJobView> {
   int trace_per = 0, trace_chains = 0;
   long long kernels = 0;
   std::vector<BatchJobResult> res;
+  // slamhip_matcher_process_raw_scan_batch: the host half (filter, rows, the scanners' tables: scan_filter.h), the ONE
+  // pinned arena k_scan_assemble_batch reads, the arena in HBM it writes the scan blocks into, the tables in HBM (one
+  // block of cos | sin | viny_f per slot of raw.slots), and where each job's block of the last raw batch lies
+  slamhip::RawBatchStage raw;
+  slamhip::PinnedBuf<unsigned char> h_raw;
+  slamhip::DeviceBuf<double> d_raw;
+  size_t h_raw_cap = 0, d_raw_cap = 0;
+  struct RawTab {
+    slamhip::DeviceBuf<double> d;
+    int cap = 0;
+  };
+  std::vector<RawTab> raw_tabs;
+  struct RawBlock {
+    const double *d = nullptr;  // null: none in the arena (nothing kept, or the job went through the lone call)
+    size_t stride = 0;
+    int n = 0;
+    bool lone = false;
+  };
+  std::vector<RawBlock> raw_blocks;
 };
 
 struct slamhip_matcher {
@@ -999,7 +1018,83 @@ bool batch_chain_eligible(slamhip_matcher *m) {
 constexpr int kBatchWgs = 1024;
 constexpr int kBatchTracePer = 1 << 14;  // trace entries per chain (a longer match is redone by the single path)
 
-int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
+// the maps of the shared launches: bound, 1-cell, of one cell model (asked before anything is staged or launched)
+template <class Job>
+int batch_maps_check(slamhip_ctx *ctx, int n, const Job *jobs, int *cell_model_out) {
+  int cell_model = -1;
+  for (int c = 0; c < n; ++c) {
+    const int id = jobs[c].map_id;
+    const DeviceMap *dm = (id >= 0 && id < (int)ctx->maps.size() && ctx->maps[id].bound) ? &ctx->maps[id] : nullptr;
+    if (!dm) return invalid_arg("unknown map id in a match job");
+    if (dm->cell_model == SLAMHIP_CELL_GMAPPING) return invalid_arg("the batch form covers the 1-cell OOPE (OCC / TBM cells)");
+    if (cell_model >= 0 && dm->cell_model != cell_model) return invalid_arg("the maps of one batch must share a cell model");
+    cell_model = dm->cell_model;
+  }
+  *cell_model_out = cell_model;
+  return SLAMHIP_OK;
+}
+
+// a match's scan where it lies in HBM: five rows of `stride` doubles
+struct BatchScanBlock {
+  const double *d = nullptr;
+  size_t stride = 0;
+  int n = 0;
+  double tot_w = 0;
+};
+
+// The batch's scans: stored scans are read where they lie; scans handed over as host arrays go into one arena with one
+// copy (the staging buffers are free: the previous batch returned after its chains had ended, i.e. long after its
+// copies).  blocks: n entries out.
+int hc_batch_stage_scans(slamhip_matcher *m, int n, const slamhip_match_job *jobs, BatchScanBlock *blocks) {
+  slamhip_ctx *ctx = m->ctx;
+  HcBatch *b = m->batch.get();
+  size_t doubles = 0;
+  for (int c = 0; c < n; ++c)
+    if (jobs[c].scan_slot < 0) doubles += 5 * (size_t)((jobs[c].n + 7) & ~7);
+  if (doubles > b->scan_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    size_t cap = 1 << 14;
+    while (cap < doubles) cap *= 2;
+    SLAMHIP_CHECK(b->h_scan.alloc(cap, hipHostMallocDefault));
+    SLAMHIP_CHECK(b->d_scan.alloc(cap));
+    b->scan_cap = cap;
+  }
+  size_t at = 0;
+  for (int c = 0; c < n; ++c) {
+    const slamhip_match_job &j = jobs[c];
+    BatchScanBlock &k = blocks[c];
+    if (j.scan_slot >= 0) {
+      const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[j.scan_slot];
+      k.d = sl.d;
+      k.stride = (size_t)sl.cap;
+      k.n = sl.n;
+      k.tot_w = sl.tot_w;
+    } else {
+      const size_t stride = (size_t)((j.n + 7) & ~7);
+      double *hs = b->h_scan.get() + at;
+      const size_t bytes = sizeof(double) * (size_t)j.n;
+      std::memcpy(hs, j.range, bytes);
+      std::memcpy(hs + stride, j.cos_a, bytes);
+      std::memcpy(hs + 2 * stride, j.sin_a, bytes);
+      std::memcpy(hs + 3 * stride, j.weight, bytes);
+      if (j.factor) std::memcpy(hs + 4 * stride, j.factor, bytes);
+      else for (int i = 0; i < j.n; ++i) hs[4 * stride + i] = 1.0;
+      double tot_w = 0;  // in beam order, pose independent (weighted_mean_point_probability_spe.h:125)
+      for (int i = 0; i < j.n; ++i) tot_w += j.weight[i];
+      k.d = b->d_scan.get() + at;
+      k.stride = stride;
+      k.n = j.n;
+      k.tot_w = tot_w;
+      at += 5 * stride;
+    }
+  }
+  if (at) SLAMHIP_CHECK(hipMemcpyAsync(b->d_scan.get(), b->h_scan.get(), sizeof(double) * at, hipMemcpyHostToDevice, ctx->stream));
+  return SLAMHIP_OK;
+}
+
+// The shared launches over n matches whose scans lie in HBM (blocks); a job gives its map and its initial pose.
+template <class Job>
+int hc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBlock *blocks) {
   slamhip_ctx *ctx = m->ctx;
   HcBatch *b = m->batch.get();
   if (!b->d_shapes) {
@@ -1034,33 +1129,16 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
     SLAMHIP_CHECK(b->h_trace.alloc((size_t)b->trace_per * b->cap, kPinnedCoherent));
     b->trace_chains = b->cap;
   }
-  // ---- the batch's scans: stored scans are read where they lie; scans handed over as host arrays go into one
-  // arena with one copy (the staging buffers are free: the previous batch returned after its chains had ended,
-  // i.e. long after its copies)
-  size_t doubles = 0;
   int max_n = 0;
-  auto beams_of = [&](const slamhip_match_job &j) { return j.scan_slot >= 0 ? ctx->scan_slots[j.scan_slot].n : j.n; };
-  for (int c = 0; c < n; ++c) {
-    if (jobs[c].scan_slot < 0) doubles += 5 * (size_t)((jobs[c].n + 7) & ~7);
-    max_n = std::max(max_n, beams_of(jobs[c]));
-  }
-  if (doubles > b->scan_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    size_t cap = 1 << 14;
-    while (cap < doubles) cap *= 2;
-    SLAMHIP_CHECK(b->h_scan.alloc(cap, hipHostMallocDefault));
-    SLAMHIP_CHECK(b->d_scan.alloc(cap));
-    b->scan_cap = cap;
-  }
+  for (int c = 0; c < n; ++c) max_n = std::max(max_n, blocks[c].n);
   int cell_model = -1;
-  size_t at = 0;
+  {
+    const int rc = batch_maps_check(ctx, n, jobs, &cell_model);
+    if (rc) return rc;
+  }
   for (int c = 0; c < n; ++c) {
-    const slamhip_match_job &j = jobs[c];
-    DeviceMap *dm = (j.map_id >= 0 && j.map_id < (int)ctx->maps.size() && ctx->maps[j.map_id].bound) ? &ctx->maps[j.map_id] : nullptr;
-    if (!dm) return invalid_arg("unknown map id in a match job");
-    if (dm->cell_model == SLAMHIP_CELL_GMAPPING) return invalid_arg("the batch form covers the 1-cell OOPE (OCC / TBM cells)");
-    if (cell_model >= 0 && dm->cell_model != cell_model) return invalid_arg("the maps of one batch must share a cell model");
-    cell_model = dm->cell_model;
+    const Job &j = jobs[c];
+    const DeviceMap *dm = &ctx->maps[j.map_id];
     HcJobView &v = b->stage.h_table()[c];
     v.map.payload = dm->d_payload;
     v.map.width = dm->width;
@@ -1071,31 +1149,10 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
     v.map.scale = dm->scale;
     v.map.inv_scale = 1.0 / dm->scale;
     for (int q = 0; q < 4; ++q) v.map.unknown[q] = dm->unknown[q];
-    const double *ds;
-    size_t stride;
-    if (j.scan_slot >= 0) {
-      const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[j.scan_slot];
-      ds = sl.d;
-      stride = (size_t)sl.cap;
-      v.scan.n = sl.n;
-      v.scan.tot_w = sl.tot_w;
-    } else {
-      stride = (size_t)((j.n + 7) & ~7);
-      double *hs = b->h_scan.get() + at;
-      const size_t bytes = sizeof(double) * (size_t)j.n;
-      std::memcpy(hs, j.range, bytes);
-      std::memcpy(hs + stride, j.cos_a, bytes);
-      std::memcpy(hs + 2 * stride, j.sin_a, bytes);
-      std::memcpy(hs + 3 * stride, j.weight, bytes);
-      if (j.factor) std::memcpy(hs + 4 * stride, j.factor, bytes);
-      else for (int i = 0; i < j.n; ++i) hs[4 * stride + i] = 1.0;
-      double tot_w = 0;  // in beam order, pose independent (weighted_mean_point_probability_spe.h:125)
-      for (int i = 0; i < j.n; ++i) tot_w += j.weight[i];
-      ds = b->d_scan.get() + at;
-      v.scan.n = j.n;
-      v.scan.tot_w = tot_w;
-      at += 5 * stride;
-    }
+    const double *ds = blocks[c].d;
+    const size_t stride = blocks[c].stride;
+    v.scan.n = blocks[c].n;
+    v.scan.tot_w = blocks[c].tot_w;
     v.scan.range = ds;
     v.scan.cos_a = ds + stride;
     v.scan.sin_a = ds + 2 * stride;
@@ -1104,7 +1161,6 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
     for (int q = 0; q < 3; ++q) b->stage.h_inits()[3 * c + q] = j.init_pose[q];
   }
   hipStream_t st = ctx->stream;
-  if (at) SLAMHIP_CHECK(hipMemcpyAsync(b->d_scan.get(), b->h_scan.get(), sizeof(double) * at, hipMemcpyHostToDevice, st));
   // (counter = 0, initial poses, job table: one pull of the pinned block)
   SLAMHIP_CHECK(launch_block_pull(b->stage.h.get(), b->stage.d.get(), b->stage.bytes_upto_table(n), st));
   HcChainArgs a;
@@ -1159,7 +1215,7 @@ int hc_batch_run(slamhip_matcher *m, int n, const slamhip_match_job *jobs) {
         r.rescored = h->rescored;
         r.steps = h->steps;
         m->tail_calls += h->tail_calls;
-        units += h->evaluated * (long long)beams_of(jobs[c]);
+        units += h->evaluated * (long long)blocks[c].n;
       },
       ManyChainsText{"co-resident hill-climbing chains", "the batch's hill-climbing chains did not end"});
   if (rc) return rc;
@@ -2041,7 +2097,13 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
   for (int c = 0; c < n_jobs && chains; ++c)
     chains = (jobs[c].scan_slot >= 0 ? ctx->scan_slots[jobs[c].scan_slot].n : jobs[c].n) <= 4096;
   if (chains) {
-    const int rc = hc_batch_run(m, n_jobs, jobs);
+    int cell_model = -1;
+    int rc = batch_maps_check(ctx, n_jobs, jobs, &cell_model);
+    if (rc) return rc;
+    std::vector<BatchScanBlock> blocks(n_jobs);
+    rc = hc_batch_stage_scans(m, n_jobs, jobs, blocks.data());
+    if (rc) return rc;
+    rc = hc_batch_run(m, n_jobs, jobs, blocks.data());
     if (rc) return rc;
   }
   // results in job order; a match the chains did not settle (a configuration they do not cover, a trace longer
@@ -2175,6 +2237,274 @@ int slamhip_matcher_process_raw_scan(slamhip_matcher *m, int map_id, const slamh
   // (a match that failed before it launched anything: the scan is the current one all the same, its block gets written)
   const int arc = scan_assemble_now(m->ctx);
   return rc ? rc : arc;
+}
+
+// K raw scans, K matches in the shared launches.  The host half per job is the lone call's (scan_filter.h); the scans
+// reach HBM through ONE launch of k_scan_assemble_batch in front of the chains' launch, which reads the call's pinned
+// arena: kept ranges, kept indices, factors, ahr weights and the table of per-job ScanAssembleArgs.  The arena is
+// refilled by the next call only: this one returns after its chains have reported their results, the chains were
+// launched on the same stream behind the assembly kernel, so the kernel has read the arena by then -- no flag.
+int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const slamhip_raw_match_job *jobs,
+                                           double *out_deltas, double *out_probs, int *kept_n) {
+  if (!m || n_jobs < 0 || (n_jobs > 0 && (!jobs || !out_deltas || !out_probs))) return invalid_arg("null argument");
+  if (n_jobs == 0) return SLAMHIP_OK;
+  if (m->is_m3rsm) return invalid_arg("multi-resolution matches are not batched");
+  slamhip_ctx *ctx = m->ctx;
+  // ---- every check in front of the first launch: the arguments, the maps, the scanners' tables (prepare)
+  for (int c = 0; c < n_jobs; ++c) {
+    const slamhip_raw_match_job &j = jobs[c];
+    if (j.scan.n <= 0 || !j.scan.range || !j.scan.angle) return invalid_arg("bad scan in a raw match job");
+    if (j.scan.trig_mode != SLAMHIP_TRIG_RAW && j.scan.trig_mode != SLAMHIP_TRIG_CACHED)
+      return invalid_arg("unknown trig mode in a raw match job");
+    if (j.scan.weighting < 0 || j.scan.weighting > 2) return invalid_arg("unknown weighting kind");
+    if (j.map_id < 0 || j.map_id >= (int)ctx->maps.size() || !ctx->maps[j.map_id].bound)
+      return invalid_arg("unknown map id in a match job");
+  }
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  if (!m->batch) m->batch = std::make_unique<HcBatch>();
+  HcBatch *b = m->batch.get();
+  RawBatchStage &raw = b->raw;
+  const bool planned = n_jobs > 1;  // (a batch of one is the lone call, which checks for itself)
+  bool on_chains = false;
+  if (planned) {
+    std::vector<RawBatchJob> in(n_jobs);
+    for (int c = 0; c < n_jobs; ++c) {
+      const slamhip_raw_scan &s = jobs[c].scan;
+      const DeviceMap &dm = ctx->maps[jobs[c].map_id];
+      RawBatchJob &r = in[c];
+      r.n = s.n;
+      r.range = s.range;
+      r.angle = s.angle;
+      r.is_occ = s.is_occ;
+      r.factor = s.factor;
+      r.trig_mode = s.trig_mode;
+      r.a_min = s.a_min;
+      r.a_max = s.a_max;
+      r.a_inc = s.a_inc;
+      r.skip_rate = s.skip_rate;
+      r.max_range = s.max_range;
+      r.bounded = s.bounded ? 1 : 0;
+      r.weighting = s.weighting;
+      for (int q = 0; q < 3; ++q) r.pose[q] = jobs[c].init_pose[q];
+      r.win = ScanWindow{dm.scale, dm.origin_x, dm.origin_y, dm.width, dm.height};
+    }
+    int rc = raw.prepare(n_jobs, in.data(), sizeof(ScanAssembleArgs));
+    if (rc) return invalid_arg(scan_error_text(rc));
+    // the jobs that kept something, and whether the shared launches take them
+    struct LiveJob {
+      int map_id;
+      double init_pose[3];
+    };
+    std::vector<LiveJob> live(raw.n_live);
+    for (int c = 0; c < n_jobs; ++c) {
+      if (raw.plan[c].live < 0) continue;
+      LiveJob &l = live[raw.plan[c].live];
+      l.map_id = jobs[c].map_id;
+      for (int q = 0; q < 3; ++q) l.init_pose[q] = jobs[c].init_pose[q];
+    }
+    const bool chains = raw.n_live > 1 && raw.n_live <= 65535 && raw.max_k <= 4096 && batch_chain_eligible(m);
+    if (chains) {
+      int cell_model = -1;
+      rc = batch_maps_check(ctx, raw.n_live, live.data(), &cell_model);
+      if (rc) return rc;
+      // ---- the arenas (the stream is idle: the batch before returned after its chains had ended): the pinned one, its
+      // rows filled; then the one in HBM
+      if (raw.arena_bytes > b->h_raw_cap) {
+        SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+        size_t cap = 1 << 16;
+        while (cap < raw.arena_bytes) cap *= 2;
+        b->h_raw_cap = 0;
+        SLAMHIP_CHECK(b->h_raw.alloc(cap, hipHostMallocMapped));
+        b->h_raw_cap = cap;
+      }
+      rc = raw.fill(in.data(), b->h_raw.get());
+      if (rc) return invalid_arg(scan_error_text(rc));
+      // (the last check of the arguments lies behind: from here on the last batch's blocks may go)
+      if (raw.dst_doubles > b->d_raw_cap) {
+        SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+        size_t cap = 1 << 14;
+        while (cap < raw.dst_doubles) cap *= 2;
+        b->d_raw_cap = 0;
+        b->raw_blocks.clear();  // (they pointed into the block that goes away)
+        SLAMHIP_CHECK(b->d_raw.alloc(cap));
+        b->d_raw_cap = cap;
+      }
+      // ---- the tables of the scanners this call has met for the first time: to HBM, as the lone call sends its one
+      // (the call waits for the copies instead of keeping the sources alive; a later call with these scanners sends none)
+      if (b->raw_tabs.size() < raw.slots.size()) b->raw_tabs.resize(raw.slots.size());
+      bool sent = false;
+      for (size_t q = 0; q < raw.slots.size(); ++q) {
+        RawBatchStage::Slot &sl = raw.slots[q];
+        if (!sl.fresh || sl.used != raw.call) continue;
+        HcBatch::RawTab &tab = b->raw_tabs[q];
+        const int n = (int)sl.t.cos_a.size();
+        if (n > tab.cap) {
+          SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+          int cap = 2048;
+          while (cap < n) cap *= 2;
+          tab.cap = 0;
+          SLAMHIP_CHECK(tab.d.alloc(3 * (size_t)cap));
+          tab.cap = cap;
+        }
+        const size_t bytes = sizeof(double) * n;
+        SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get(), sl.t.cos_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + tab.cap, sl.t.sin_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + 2 * (size_t)tab.cap, sl.t.viny_f.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        sl.fresh = false;
+        sent = true;
+        ++ctx->scan_tab_uploads;
+      }
+      if (sent) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+      // ---- the args table, the blocks, the launch
+      ScanAssembleArgs *table = reinterpret_cast<ScanAssembleArgs *>(b->h_raw.get());
+      std::vector<BatchScanBlock> blocks(raw.n_live);
+      b->raw_blocks.assign(n_jobs, HcBatch::RawBlock{});
+      for (int c = 0; c < n_jobs; ++c) {
+        const RawBatchPlan &p = raw.plan[c];
+        if (p.live < 0) continue;
+        const unsigned char *h = b->h_raw.get();
+        const HcBatch::RawTab &tab = b->raw_tabs[p.table];
+        ScanAssembleArgs as{};
+        as.h_range = reinterpret_cast<const double *>(h + p.off_range);
+        if (p.off_kept != kNoRow) as.h_kept = reinterpret_cast<const int *>(h + p.off_kept);
+        if (p.off_factor != kNoRow) as.h_factor = reinterpret_cast<const double *>(h + p.off_factor);
+        if (p.off_weight != kNoRow) as.h_weight = reinterpret_cast<const double *>(h + p.off_weight);
+        as.tab_cos = tab.d.get();
+        as.tab_sin = tab.d.get() + tab.cap;
+        if (jobs[c].scan.weighting == 1) as.tab_viny = tab.d.get() + 2 * (size_t)tab.cap;
+        as.dst = b->d_raw.get() + p.dst_at;
+        as.stride = p.stride;
+        as.n = p.k;
+        as.w_even = p.w_even;
+        table[p.live] = as;
+        blocks[p.live] = BatchScanBlock{as.dst, p.stride, p.k, p.tot_w};
+        b->raw_blocks[c] = HcBatch::RawBlock{as.dst, p.stride, p.k, false};
+      }
+      {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        rc = profile_event_pair(ctx, &e0, &e1);
+        if (rc) return rc;
+        if (e0) SLAMHIP_CHECK(hipEventRecord(e0, ctx->stream));
+        SLAMHIP_CHECK(launch_scan_assemble_batch(table, raw.n_live, raw.max_stride, ctx->stream));
+        if (e1) SLAMHIP_CHECK(hipEventRecord(e1, ctx->stream));
+        if (ctx->profile) ++ctx->prof_launches;
+      }
+      b->res.assign(n_jobs, BatchJobResult{});
+      b->kernels = 0;
+      rc = hc_batch_run(m, raw.n_live, live.data(), blocks.data());
+      if (rc) return rc;
+      // (the chains' results by live place -> by job)
+      std::vector<BatchJobResult> by_live(b->res.begin(), b->res.begin() + raw.n_live);
+      b->res.assign(n_jobs, BatchJobResult{});
+      for (int c = 0; c < n_jobs; ++c)
+        if (raw.plan[c].live >= 0) b->res[c] = by_live[raw.plan[c].live];
+      on_chains = true;
+    }
+  }
+  if (!on_chains) {  // (every job that kept something goes through the lone call below)
+    b->res.assign(n_jobs, BatchJobResult{});
+    b->kernels = 0;
+    b->raw_blocks.assign(n_jobs, HcBatch::RawBlock{});
+  }
+  // ---- results in job order.  A job the chains did not take or did not settle goes through the lone raw call, which
+  // works on the context's CURRENT scan: the caller's own selection is put back afterwards, or invalidated when it was
+  // the upload buffer the lone calls have overwritten (as slamhip_matcher_process_scan_batch leaves it)
+  long long calls = 0, evaluated = 0, steps = 0;
+  const double *saved_ptr = ctx->scan_ptr;
+  const size_t saved_stride = ctx->scan_stride;
+  const int saved_n = ctx->scan_n;
+  const double saved_tot_w = ctx->scan_tot_w;
+  // (asked now: a lone call may replace the upload buffer by a larger one)
+  const bool saved_is_upload = !saved_ptr || saved_ptr == ctx->d_scan;
+  std::vector<double> saved_w, saved_f;
+  bool fell_back = false;
+  auto restore = [&]() {
+    if (!fell_back) return;
+    if (saved_is_upload) {
+      ctx->scan_n = 0;  // (its contents are gone: "no scan uploaded" from here on)
+    } else {
+      ctx->scan_ptr = saved_ptr;
+      ctx->scan_stride = saved_stride;
+      ctx->scan_n = saved_n;
+      ctx->scan_tot_w = saved_tot_w;
+      ctx->h_weight.swap(saved_w);
+      ctx->h_factor.swap(saved_f);
+      ctx->h_scan_angle.clear();  // (a stored scan has none, as slamhip_scan_select leaves it)
+      ctx->scan_angle_on_device = false;
+    }
+    ctx->scan_angle_lazy = false;
+  };
+  for (int c = 0; c < n_jobs; ++c) {
+    BatchJobResult &r = b->res[c];
+    const slamhip_raw_match_job &j = jobs[c];
+    double *dl = out_deltas + 3 * c;
+    int kept = planned ? raw.plan[c].k : 0;
+    if (r.on_chain) {
+      for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
+      out_probs[c] = r.prob;
+      if (m->has_obs) {
+        replay_trace(m->obs, b->h_trace.get() + (size_t)raw.plan[c].live * b->trace_per, r.calls);
+        if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
+      }
+    } else if (planned && kept == 0) {
+      // 0 / 0 for every candidate: nothing is accepted, no launch, no observer call (the lone call's answer)
+      dl[0] = dl[1] = dl[2] = 0.0;
+      out_probs[c] = std::numeric_limits<double>::quiet_NaN();
+      r = BatchJobResult{};
+      for (int q = 0; q < 3; ++q) r.pose[q] = j.init_pose[q];
+      r.prob = out_probs[c];
+    } else {
+      if (!fell_back) {
+        saved_w = ctx->h_weight;
+        saved_f = ctx->h_factor;
+        fell_back = true;
+      }
+      const int rc = slamhip_matcher_process_raw_scan(m, j.map_id, &j.scan, j.init_pose, dl, &out_probs[c], &kept);
+      if (rc) {
+        restore();
+        return rc;
+      }
+      b->raw_blocks[c] = HcBatch::RawBlock{nullptr, 0, kept, true};
+      r = BatchJobResult{};
+      if (kept > 0) {
+        r.calls = m->job.scorer_calls;
+        r.evaluated = m->job.poses_evaluated;
+        r.steps = (int)m->job.launches;
+        r.rescored = m->chain_rescored;
+      }
+      for (int q = 0; q < 3; ++q) r.pose[q] = j.init_pose[q] + dl[q];
+      r.prob = out_probs[c];
+    }
+    if (kept_n) kept_n[c] = kept;
+    calls += r.calls;
+    evaluated += r.evaluated;
+    steps = std::max<long long>(steps, r.steps);
+  }
+  restore();
+  m->job.scorer_calls = calls;
+  m->job.poses_evaluated = evaluated;
+  m->job.launches = steps;
+  m->chain_launched = b->kernels;
+  long long resc = 0;
+  for (const BatchJobResult &r : b->res) resc += r.rescored;
+  m->chain_rescored = resc;
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_batch_scan_download(slamhip_matcher *m, int job, int cap, double *out5, int *n) {
+  if (!m || !n || cap < 0 || (cap > 0 && !out5)) return invalid_arg("bad arguments");
+  if (!m->batch || job < 0 || job >= (int)m->batch->raw_blocks.size()) return invalid_arg("no such job in the last raw batch");
+  const HcBatch::RawBlock &k = m->batch->raw_blocks[job];
+  *n = k.n;
+  if (cap == 0 || k.n <= 0) return SLAMHIP_OK;
+  if (k.lone || !k.d) return invalid_arg("that job went through the lone call: its scan is not in the batch's arena");
+  if (cap < k.n) return invalid_arg("slamhip_matcher_batch_scan_download: room for fewer points than the job's scan has");
+  slamhip_ctx *ctx = m->ctx;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  SLAMHIP_CHECK(hipMemcpy2DAsync(out5, sizeof(double) * cap, k.d, sizeof(double) * k.stride, sizeof(double) * k.n, 5,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return SLAMHIP_OK;
 }
 
 int slamhip_matcher_tail_stats(slamhip_matcher *m, long long *calls_closed_form) {

@@ -196,4 +196,311 @@ double scan_filter_fill(int k, const int *kept, const double *range, const doubl
                            : fill_generic(k, kept, range, factor, viny_f, r_out, f_out, w_out);
 }
 
+const char *scan_error_text(int code) {
+  switch (code) {
+    case kScanOk: return "ok";
+    case kScanAngleOutsideTable: return "scan angle outside the trig table";
+    case kScanAhrBin: return "angle histogram bin out of range (reference asserts here)";
+    case kScanBadWeighting: return "unknown weighting kind";
+    default: return "bad arguments";
+  }
+}
+
+int beam_trig_raw(int n, const double *angle, double *cos_out, double *sin_out) {
+  if (n < 0 || !angle || !cos_out || !sin_out) return kScanBadArgs;
+  for (int i = 0; i < n; ++i) ::sincos(angle[i], &sin_out[i], &cos_out[i]);
+  return kScanOk;
+}
+
+int beam_trig_cached(int n, const double *angle, double a_min, double a_max, double a_inc, double *cos_out, double *sin_out) {
+  if (n < 0 || !angle || !cos_out || !sin_out || !(a_inc > 0)) return kScanBadArgs;
+  // the table of the last (a_min, a_max, a_inc) is kept: a world loop asks for the same one twice per scan, and
+  // building it is a libm sincos per entry
+  struct Table {
+    double a_min = 0, a_max = 0, a_inc = 0;
+    std::vector<double> ts, tc;
+  };
+  static thread_local Table tab;
+  if (tab.ts.empty() || tab.a_min != a_min || tab.a_max != a_max || tab.a_inc != a_inc) {
+    tab.ts.clear();
+    tab.tc.clear();
+    for (double a = a_min; a < a_max; a += a_inc) {  // accumulating loop, as the provider builds it
+      double sv, cv;
+      ::sincos(a, &sv, &cv);  // fused pair, as in the reference build (see score_staged)
+      tab.ts.push_back(sv);
+      tab.tc.push_back(cv);
+    }
+    tab.a_min = a_min;
+    tab.a_max = a_max;
+    tab.a_inc = a_inc;
+  }
+  const std::vector<double> &ts = tab.ts, &tc = tab.tc;
+  for (int i = 0; i < n; ++i) {
+    const int idx = (int)std::round((angle[i] - a_min) / a_inc);
+    if (idx < 0 || idx >= (int)ts.size()) return kScanAngleOutsideTable;
+    cos_out[i] = tc[idx];
+    sin_out[i] = ts[idx];
+  }
+  return kScanOk;
+}
+
+// VinySlamSPW's angular factor (weighted_mean_point_probability_spe.h:47-60): the weight is this times sqrt(range)
+static inline double viny_factor(double angle) {
+  double sv, cv;
+  ::sincos(angle, &sv, &cv);
+  const double ac = std::abs(cv);
+  double w = std::abs(sv) + ac;
+  if (0.9 < ac) w = 3;
+  else if (0.8 < ac) w = 2;
+  return w;
+}
+
+int scan_weights(int kind, int n, const double *range, const double *angle, double *out) {
+  if (n < 0 || !range || !angle || !out) return kScanBadArgs;
+  if (kind == 0) {
+    const double w = 1.0 / n;
+    for (int i = 0; i < n; ++i) out[i] = w;
+    return kScanOk;
+  }
+  if (kind == 1) {
+    for (int i = 0; i < n; ++i) out[i] = viny_factor(angle[i]) * std::sqrt(range[i]);
+    return kScanOk;
+  }
+  if (kind == 2) {
+    constexpr int NB = 20;
+    unsigned hist[NB] = {0};
+    std::vector<double> dirs(n > 0 ? n : 1, 0.0);
+    const double step = (180 * M_PI / 180) / NB;
+    for (int i = 1; i < n; ++i) {
+      double s1, c1, s0, c0;
+      ::sincos(angle[i], &s1, &c1);
+      ::sincos(angle[i - 1], &s0, &c0);
+      const double d_x = range[i] * c1 - range[i - 1] * c0;
+      const double d_y = range[i] * s1 - range[i - 1] * s0;
+      double a = 0;
+      if (d_y != 0) {
+        a = std::acos(d_x / std::sqrt(d_x * d_x + d_y * d_y));
+        if (d_y < 0 && d_x != 0) a = M_PI - a;
+      }
+      const size_t bin = (size_t)std::floor(a / step);
+      if (bin >= NB) return kScanAhrBin;
+      hist[bin]++;
+      dirs[i] = a;
+    }
+    for (int i = 0; i < n; ++i) {
+      const unsigned v = i == 0 ? (unsigned)n : hist[(size_t)std::floor(dirs[i] / step)];
+      out[i] = 1.0 / v;
+    }
+    return kScanOk;
+  }
+  return kScanBadWeighting;
+}
+
+// total_weight accumulates in beam order and does not depend on the pose
+// (weighted_mean_point_probability_spe.h:125)
+double scan_total_weight(const double *weight, int n) {
+  double tot_w = 0;
+  for (int i = 0; i < n; ++i) tot_w += weight[i];
+  return tot_w;
+}
+
+// ... of EvenSPW's k weights 1.0 / k: the same k additions in the same order, made once per k -- the value depends on
+// nothing else, and the chain of k dependent additions was the longest single item of the raw scan's host half (about
+// 1.3 us at 1080 beams by the additions' latency).  Per thread, as beam_trig_cached keeps its table.
+double scan_total_weight_even(int k, double w) {
+  static thread_local std::vector<double> memo;  // [k] = the sum, 0.0 = not made yet (a sum of positive weights is not 0)
+  if ((int)memo.size() <= k) memo.resize((size_t)k + 1, 0.0);
+  if (memo[k] == 0.0) {
+    double tot_w = 0;
+    for (int i = 0; i < k; ++i) tot_w += w;
+    memo[k] = tot_w;
+  }
+  return memo[k];
+}
+
+bool ScanTables::same(int n, const double *angle_, int trig_mode_, double a_min_, double a_max_, double a_inc_) const {
+  return (int)angle.size() == n && trig_mode == trig_mode_ && a_min == a_min_ && a_max == a_max_ && a_inc == a_inc_ &&
+         std::memcmp(angle.data(), angle_, sizeof(double) * n) == 0;
+}
+
+int scan_tables_build(ScanTables &t, int n, const double *angle, int trig_mode, double a_min, double a_max, double a_inc) {
+  t.angle.assign(angle, angle + n);
+  t.trig_mode = trig_mode;
+  t.a_min = a_min;
+  t.a_max = a_max;
+  t.a_inc = a_inc;
+  t.cos_a.resize(n);
+  t.sin_a.resize(n);
+  // (trig_mode 1 is SLAMHIP_TRIG_CACHED; everything else the raw provider, as the lone call has always read it)
+  const int rc = trig_mode == 1 ? beam_trig_cached(n, angle, a_min, a_max, a_inc, t.cos_a.data(), t.sin_a.data())
+                                : beam_trig_raw(n, angle, t.cos_a.data(), t.sin_a.data());
+  if (rc) {
+    t.angle.clear();
+    return rc;
+  }
+  t.viny_f.resize(n);
+  for (int i = 0; i < n; ++i) t.viny_f[i] = viny_factor(angle[i]);
+  return kScanOk;
+}
+
+// ---- filter_scan: keeps point i iff (skip_rate == 0 or i % skip_rate == 0), occupied, its end point's cell in the
+// map, and not beyond the usable range (Q8 - Q10)
+int scan_filter_kept(const ScanTables &t, int n, const double *range, const double *angle, const int *is_occ,
+                     unsigned skip_rate, double max_range, const ScanWindow *win, const double pose[3],
+                     ScanFilterScratch &s, int *kept) {
+  // (a branch-free pass that writes one byte per point, then the bytes compacted into the index list)
+  ScanFilterArgs fa{};
+  fa.n = n;
+  fa.range = range;
+  fa.angle = angle;
+  fa.is_occ = is_occ;
+  fa.skip_rate = skip_rate;
+  fa.max_range = max_range;
+  fa.bounded = win ? 1 : 0;
+  if (win) {
+    fa.trig_raw = t.trig_mode == 1 ? 0 : 1;
+    fa.cos_a = t.cos_a.data();
+    fa.sin_a = t.sin_a.data();
+    for (int q = 0; q < 3; ++q) fa.pose[q] = pose[q];
+    fa.scale = win->scale;
+    fa.origin_x = win->origin_x;
+    fa.origin_y = win->origin_y;
+    fa.width = win->width;
+    fa.height = win->height;
+    if (fa.trig_raw) s.trig.resize(2 * (size_t)n);
+  }
+  s.mask.resize(n);
+  scan_filter_mask(fa, s.mask.data(), s.trig.data());
+  return scan_filter_compact(s.mask.data(), n, kept);
+}
+
+int scan_stage_rows(const ScanTables &t, int n, const double *range, const double *angle, const double *factor,
+                    int weighting, int k, const int *kept, const ScanStageRows &rows, double *w_viny,
+                    ScanStageScratch &s, double *w_even, double *tot_w) {
+  // (the rows that are gathered through the kept list -- ranges, factors, the viny weights -- in ONE sweep over it:
+  // scan_filter_fill)
+  if (k == n) std::memcpy(rows.range, range, sizeof(double) * k);
+  else std::memcpy(rows.kept, kept, sizeof(int) * k);
+  const double tot_viny = scan_filter_fill(k, kept, range, factor, t.viny_f.data(), k == n ? nullptr : rows.range,
+                                           factor ? rows.factor : nullptr, weighting == 1 ? w_viny : nullptr);
+  *w_even = 0.0;
+  if (weighting == 0) {
+    *w_even = 1.0 / k;  // EvenSPW (:21-32)
+    *tot_w = scan_total_weight_even(k, *w_even);
+  } else if (weighting == 1) {
+    *tot_w = tot_viny;  // (the same additions in the same order)
+  } else {
+    s.a.resize(k);
+    s.r.resize(k);
+    s.w.resize(k);
+    for (int q = 0; q < k; ++q) {
+      s.a[q] = angle[kept[q]];
+      s.r[q] = range[kept[q]];
+    }
+    const int rc = scan_weights(2, k, s.r.data(), s.a.data(), s.w.data());
+    if (rc) return rc;
+    std::memcpy(rows.weight, s.w.data(), sizeof(double) * k);
+    *tot_w = scan_total_weight(s.w.data(), k);
+  }
+  return kScanOk;
+}
+
+int RawBatchStage::prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entry_bytes) {
+  for (int c = 0; c < n_jobs; ++c) {
+    const RawBatchJob &j = jobs[c];
+    if (j.n <= 0 || !j.range || !j.angle) return kScanBadArgs;
+    if (j.weighting < 0 || j.weighting > 2) return kScanBadWeighting;
+  }
+  ++call;
+  plan.assign(n_jobs, RawBatchPlan{});
+  kept.clear();
+  n_live = max_stride = max_k = 0;
+  dst_doubles = 0;
+  size_t total_n = 0;
+  for (int c = 0; c < n_jobs; ++c) total_n += (size_t)jobs[c].n;
+  kept.resize(total_n);
+  size_t kept_at = 0;
+  for (int c = 0; c < n_jobs; ++c) {
+    const RawBatchJob &j = jobs[c];
+    RawBatchPlan &p = plan[c];
+    // the job's scanner: one that is known (jobs of one call with equal scanners share it, a later call finds it), else
+    // built in the place of the one that has gone unused longest once kSlotsKept are held
+    int at = -1;
+    for (int q = 0; q < (int)slots.size() && at < 0; ++q)
+      if (slots[q].t.same(j.n, j.angle, j.trig_mode, j.a_min, j.a_max, j.a_inc)) at = q;
+    if (at < 0) {
+      if ((int)slots.size() >= kSlotsKept) {
+        for (int q = 0; q < (int)slots.size(); ++q)
+          if (slots[q].used < call && (at < 0 || slots[q].used < slots[at].used)) at = q;
+      }
+      const bool added = at < 0;
+      if (added) {
+        slots.emplace_back();
+        at = (int)slots.size() - 1;
+      }
+      slots[at].fresh = true;
+      const int rc = scan_tables_build(slots[at].t, j.n, j.angle, j.trig_mode, j.a_min, j.a_max, j.a_inc);
+      if (rc) {
+        if (added) slots.pop_back();  // (a taken-over slot stays, empty: it matches no scanner)
+        return rc;
+      }
+    }
+    slots[at].used = call;
+    p.table = at;
+    p.kept_at = kept_at;
+    p.k = scan_filter_kept(slots[at].t, j.n, j.range, j.angle, j.is_occ, j.skip_rate, j.max_range,
+                           j.bounded ? &j.win : nullptr, j.pose, fs, kept.data() + kept_at);
+    kept_at += (size_t)p.k;
+    if (p.k > 0) p.live = n_live++;
+    max_k = p.k > max_k ? p.k : max_k;
+  }
+  // the arena: the args table, then per live job its rows -- only what is new with each scan
+  auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  size_t at = align16(args_entry_bytes * (size_t)n_live);
+  for (int c = 0; c < n_jobs; ++c) {
+    const RawBatchJob &j = jobs[c];
+    RawBatchPlan &p = plan[c];
+    if (p.k == 0) continue;
+    const size_t k = (size_t)p.k;
+    p.off_range = at;
+    at = align16(at + sizeof(double) * k);
+    if (p.k < j.n) {
+      p.off_kept = at;
+      at = align16(at + sizeof(int) * k);
+    }
+    if (j.factor) {
+      p.off_factor = at;
+      at = align16(at + sizeof(double) * k);
+    }
+    if (j.weighting == 2) {
+      p.off_weight = at;
+      at = align16(at + sizeof(double) * k);
+    }
+    p.stride = (k + 7) & ~(size_t)7;
+    p.dst_at = dst_doubles;
+    dst_doubles += 5 * p.stride;
+    max_stride = (int)p.stride > max_stride ? (int)p.stride : max_stride;
+  }
+  arena_bytes = at;
+  return kScanOk;
+}
+
+int RawBatchStage::fill(const RawBatchJob *jobs, unsigned char *arena) {
+  for (int c = 0; c < (int)plan.size(); ++c) {
+    const RawBatchJob &j = jobs[c];
+    RawBatchPlan &p = plan[c];
+    if (p.k == 0) continue;
+    ScanStageRows rows{};
+    rows.range = reinterpret_cast<double *>(arena + p.off_range);
+    if (p.off_kept != kNoRow) rows.kept = reinterpret_cast<int *>(arena + p.off_kept);
+    if (p.off_factor != kNoRow) rows.factor = reinterpret_cast<double *>(arena + p.off_factor);
+    if (p.off_weight != kNoRow) rows.weight = reinterpret_cast<double *>(arena + p.off_weight);
+    if (j.weighting == 1) w_viny.resize(p.k);
+    const int rc = scan_stage_rows(slots[p.table].t, j.n, j.range, j.angle, j.factor, j.weighting, p.k,
+                                   kept.data() + p.kept_at, rows, w_viny.data(), ss, &p.w_even, &p.tot_w);
+    if (rc) return rc;
+  }
+  return kScanOk;
+}
+
 }  // namespace slamhip

@@ -134,6 +134,31 @@ hipError_t launch_scan_assemble(const ScanAssembleArgs &a, unsigned *counter, un
   return hipGetLastError();
 }
 
+// K raw scans of one call (slamhip_matcher_process_raw_scan_batch): grid.y = job, grid.x over the widest job's block
+// stride.  `table` lies in the call's pinned arena next to the rows it points at: every thread reads its job's entry (a
+// uniform address: scalar loads) and does what k_scan_assemble does for a lone scan -- scan_assemble_point is the one
+// statement of the arithmetic, the pads of the five rows come out zero.  Plain loads and stores, 8 bytes per thread
+// and row as in k_scan_assemble; nobody is told that the arena has been read: the host refills it only after the
+// chains launched behind this kernel have reported their results.
+__global__ __launch_bounds__(256) void k_scan_assemble_batch(const ScanAssembleArgs *__restrict__ table) {
+  const ScanAssembleArgs a = table[blockIdx.y];
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= (int)a.stride) return;
+  ScanPoint p{0.0, 0.0, 0.0, 0.0, 0.0};
+  if (q < a.n) p = scan_assemble_point(a, q);
+  a.dst[q] = p.range;
+  a.dst[a.stride + q] = p.cos_a;
+  a.dst[2 * a.stride + q] = p.sin_a;
+  a.dst[3 * a.stride + q] = p.weight;
+  a.dst[4 * a.stride + q] = p.factor;
+}
+
+hipError_t launch_scan_assemble_batch(const ScanAssembleArgs *table, int n_jobs, int max_stride, hipStream_t stream) {
+  if (n_jobs <= 0 || max_stride <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_scan_assemble_batch, dim3((max_stride + 255) / 256, n_jobs), dim3(256), 0, stream, table);
+  return hipGetLastError();
+}
+
 // The same for a launch's small argument blocks (job tables, initial poses, a zeroed counter): ONE pull of the pinned
 // block in front of the launch instead of several hipMemcpyAsync / hipMemsetAsync calls (each ~6 us of host time and
 // ~10 us of stream time, see above).  The host rewrites the block only after the launch that follows has reported its

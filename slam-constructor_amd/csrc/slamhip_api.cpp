@@ -1117,27 +1117,7 @@ static int scan_stage_acquire(slamhip_ctx *ctx, int n_max, double **st, size_t *
   return SLAMHIP_OK;
 }
 
-// total_weight accumulates in beam order and does not depend on the pose
-// (weighted_mean_point_probability_spe.h:125)
-static double scan_total_weight(const double *weight, int n) {
-  double tot_w = 0;
-  for (int i = 0; i < n; ++i) tot_w += weight[i];
-  return tot_w;
-}
-
-// ... of EvenSPW's k weights 1.0 / k: the same k additions in the same order, made once per k -- the value depends on
-// nothing else, and the chain of k dependent additions was the longest single item of the raw scan's host half (about
-// 1.3 us at 1080 beams by the additions' latency).  Per thread, as slamhip_beam_trig_cached keeps its table.
-static double scan_total_weight_even(int k, double w) {
-  static thread_local std::vector<double> memo;  // [k] = the sum, 0.0 = not made yet (a sum of positive weights is not 0)
-  if ((int)memo.size() <= k) memo.resize((size_t)k + 1, 0.0);
-  if (memo[k] == 0.0) {
-    double tot_w = 0;
-    for (int i = 0; i < k; ++i) tot_w += w;
-    memo[k] = tot_w;
-  }
-  return memo[k];
-}
+// (scan_total_weight / scan_total_weight_even: scan_filter.cpp)
 
 // commit in three steps, shared by the packed upload and the raw scan's assembly.  (1) the host's record of the new
 // current scan -- n points whose weights / factors are in ctx->h_weight / h_factor already -- and the staging buffer's
@@ -1260,42 +1240,14 @@ int slamhip_scan_select(slamhip_ctx *ctx, int slot) {
 }
 
 int slamhip_beam_trig_raw(int n, const double *angle, double *cos_out, double *sin_out) {
-  if (n < 0 || !angle || !cos_out || !sin_out) return invalid("bad arguments");
-  for (int i = 0; i < n; ++i) ::sincos(angle[i], &sin_out[i], &cos_out[i]);
-  return SLAMHIP_OK;
+  const int rc = slamhip::beam_trig_raw(n, angle, cos_out, sin_out);
+  return rc ? invalid(slamhip::scan_error_text(rc)) : SLAMHIP_OK;
 }
 
 int slamhip_beam_trig_cached(int n, const double *angle, double a_min, double a_max, double a_inc,
                              double *cos_out, double *sin_out) {
-  if (n < 0 || !angle || !cos_out || !sin_out || !(a_inc > 0)) return invalid("bad arguments");
-  // the table of the last (a_min, a_max, a_inc) is kept: a world loop asks for the same one twice per scan, and
-  // building it is a libm sincos per entry
-  struct Table {
-    double a_min = 0, a_max = 0, a_inc = 0;
-    std::vector<double> ts, tc;
-  };
-  static thread_local Table tab;
-  if (tab.ts.empty() || tab.a_min != a_min || tab.a_max != a_max || tab.a_inc != a_inc) {
-    tab.ts.clear();
-    tab.tc.clear();
-    for (double a = a_min; a < a_max; a += a_inc) {  // accumulating loop, as the provider builds it
-      double sv, cv;
-      ::sincos(a, &sv, &cv);  // fused pair, as in the reference build (see score_staged)
-      tab.ts.push_back(sv);
-      tab.tc.push_back(cv);
-    }
-    tab.a_min = a_min;
-    tab.a_max = a_max;
-    tab.a_inc = a_inc;
-  }
-  const std::vector<double> &ts = tab.ts, &tc = tab.tc;
-  for (int i = 0; i < n; ++i) {
-    const int idx = (int)std::round((angle[i] - a_min) / a_inc);
-    if (idx < 0 || idx >= (int)ts.size()) return invalid("scan angle outside the trig table");
-    cos_out[i] = tc[idx];
-    sin_out[i] = ts[idx];
-  }
-  return SLAMHIP_OK;
+  const int rc = slamhip::beam_trig_cached(n, angle, a_min, a_max, a_inc, cos_out, sin_out);
+  return rc ? invalid(slamhip::scan_error_text(rc)) : SLAMHIP_OK;
 }
 
 int slamhip_filter_scan(int n, const double *range, const double *angle, const int *is_occ,
@@ -1337,52 +1289,8 @@ int slamhip_filter_scan(int n, const double *range, const double *angle, const i
 }
 
 int slamhip_scan_weights(int kind, int n, const double *range, const double *angle, double *out) {
-  if (n < 0 || !range || !angle || !out) return invalid("bad arguments");
-  if (kind == 0) {
-    const double w = 1.0 / n;
-    for (int i = 0; i < n; ++i) out[i] = w;
-    return SLAMHIP_OK;
-  }
-  if (kind == 1) {
-    for (int i = 0; i < n; ++i) {
-      double sv, cv;
-      ::sincos(angle[i], &sv, &cv);
-      const double ac = std::abs(cv);
-      double w = std::abs(sv) + ac;
-      if (0.9 < ac) w = 3;
-      else if (0.8 < ac) w = 2;
-      out[i] = w * std::sqrt(range[i]);
-    }
-    return SLAMHIP_OK;
-  }
-  if (kind == 2) {
-    constexpr int NB = 20;
-    unsigned hist[NB] = {0};
-    std::vector<double> dirs(n > 0 ? n : 1, 0.0);
-    const double step = (180 * M_PI / 180) / NB;
-    for (int i = 1; i < n; ++i) {
-      double s1, c1, s0, c0;
-      ::sincos(angle[i], &s1, &c1);
-      ::sincos(angle[i - 1], &s0, &c0);
-      const double d_x = range[i] * c1 - range[i - 1] * c0;
-      const double d_y = range[i] * s1 - range[i - 1] * s0;
-      double a = 0;
-      if (d_y != 0) {
-        a = std::acos(d_x / std::sqrt(d_x * d_x + d_y * d_y));
-        if (d_y < 0 && d_x != 0) a = M_PI - a;
-      }
-      const size_t bin = (size_t)std::floor(a / step);
-      if (bin >= NB) return invalid("angle histogram bin out of range (reference asserts here)");
-      hist[bin]++;
-      dirs[i] = a;
-    }
-    for (int i = 0; i < n; ++i) {
-      const unsigned v = i == 0 ? (unsigned)n : hist[(size_t)std::floor(dirs[i] / step)];
-      out[i] = 1.0 / v;
-    }
-    return SLAMHIP_OK;
-  }
-  return invalid("unknown weighting kind");
+  const int rc = slamhip::scan_weights(kind, n, range, angle, out);
+  return rc ? invalid(slamhip::scan_error_text(rc)) : SLAMHIP_OK;
 }
 
 // scan_prep's per-beam arrays (cos, sin, viny_f) to the context's block in HBM, where k_scan_assemble gathers them: on
@@ -1479,69 +1387,23 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
   DeviceMap *m = get_map(ctx, map_id);
   if (bounded && !m) return invalid("unknown map id");
   slamhip_ctx::ScanPrep &sp = ctx->scan_prep;
-  const bool same = (int)sp.angle.size() == n && sp.trig_mode == trig_mode && sp.a_min == a_min && sp.a_max == a_max &&
-                    sp.a_inc == a_inc && std::memcmp(sp.angle.data(), angle, sizeof(double) * n) == 0;
-  if (!same) {
+  if (!sp.same(n, angle, trig_mode, a_min, a_max, a_inc)) {
     scan_angles_materialise(ctx);  // (the current scan's angles are entries of the array that goes away here)
-    sp.angle.assign(angle, angle + n);
-    sp.trig_mode = trig_mode;
-    sp.a_min = a_min;
-    sp.a_max = a_max;
-    sp.a_inc = a_inc;
-    sp.cos_a.resize(n);
-    sp.sin_a.resize(n);
-    int rc = trig_mode == SLAMHIP_TRIG_CACHED
-                 ? slamhip_beam_trig_cached(n, angle, a_min, a_max, a_inc, sp.cos_a.data(), sp.sin_a.data())
-                 : slamhip_beam_trig_raw(n, angle, sp.cos_a.data(), sp.sin_a.data());
-    if (rc) {
-      sp.angle.clear();
-      return rc;
-    }
-    // VinySlamSPW's angular factor (weighted_mean_point_probability_spe.h:47-60): the weight is this times sqrt(range)
-    sp.viny_f.resize(n);
-    for (int i = 0; i < n; ++i) {
-      double sv, cv;
-      ::sincos(angle[i], &sv, &cv);
-      const double ac = std::abs(cv);
-      double w = std::abs(sv) + ac;
-      if (0.9 < ac) w = 3;
-      else if (0.8 < ac) w = 2;
-      sp.viny_f[i] = w;
-    }
+    int rc = scan_tables_build(sp, n, angle, trig_mode, a_min, a_max, a_inc);  // (scan_filter.cpp)
+    if (rc) return invalid(scan_error_text(rc));
     rc = scan_tables_upload(ctx);
     if (rc) {
       sp.angle.clear();
       return rc;
     }
   }
-  // ---- filter_scan: keeps point i iff (skip_rate == 0 or i % skip_rate == 0), occupied, its end point's cell in the
-  // map, and not beyond the usable range (Q8 - Q10)
+  // ---- filter_scan (scan_filter_kept, scan_filter.cpp: the statement a batch of raw scans runs per job as well)
   std::vector<int> &kept = sp.kept_next;  // (sp.kept stays the current scan's until this one has taken its place)
-  // (scan_filter.cpp: a branch-free pass that writes one byte per point, then the bytes compacted into the index list)
-  ScanFilterArgs fa{};
-  fa.n = n;
-  fa.range = range;
-  fa.angle = angle;
-  fa.is_occ = is_occ;
-  fa.skip_rate = skip_rate;
-  fa.max_range = max_range;
-  fa.bounded = bounded ? 1 : 0;
-  if (bounded) {
-    fa.trig_raw = trig_mode == SLAMHIP_TRIG_CACHED ? 0 : 1;
-    fa.cos_a = sp.cos_a.data();
-    fa.sin_a = sp.sin_a.data();
-    for (int q = 0; q < 3; ++q) fa.pose[q] = pose[q];
-    fa.scale = m->scale;
-    fa.origin_x = m->origin_x;
-    fa.origin_y = m->origin_y;
-    fa.width = m->width;
-    fa.height = m->height;
-    if (fa.trig_raw) sp.filter_trig.resize(2 * (size_t)n);
-  }
-  sp.filter_mask.resize(n);
+  ScanWindow win{};
+  if (bounded) win = ScanWindow{m->scale, m->origin_x, m->origin_y, m->width, m->height};
   kept.resize(n);
-  scan_filter_mask(fa, sp.filter_mask.data(), sp.filter_trig.data());
-  kept.resize(scan_filter_compact(sp.filter_mask.data(), n, kept.data()));
+  kept.resize(scan_filter_kept(sp, n, range, angle, is_occ, skip_rate, max_range, bounded ? &win : nullptr, pose, sp.filter,
+                               kept.data()));
   const int k = (int)kept.size();
   if (kept_n) *kept_n = k;
   if (kept_idx) std::memcpy(kept_idx, kept.data(), sizeof(int) * k);
@@ -1559,52 +1421,28 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
   int rc = scan_stage_acquire(ctx, k, &st, &c);
   if (rc) return rc;
   ScanAssembleArgs as{};
-  double *r_ = st;
-  as.h_range = r_;
-  // (the rows that are gathered through the kept list -- ranges, factors, the viny weights -- in ONE sweep over it:
-  // scan_filter_fill)
-  double *f_ = factor ? st + 2 * c : nullptr, *w_viny = nullptr;
-  if (weighting == 1) {
-    ctx->h_weight.resize(k);
-    w_viny = ctx->h_weight.data();
-  }
-  if (k == n) {
-    std::memcpy(r_, range, sizeof(double) * k);
-  } else {
-    int *k_ = reinterpret_cast<int *>(st + c);
-    std::memcpy(k_, kept.data(), sizeof(int) * k);
-    as.h_kept = k_;
-  }
-  const double tot_viny =
-      scan_filter_fill(k, kept.data(), range, factor, sp.viny_f.data(), k == n ? nullptr : r_, f_, w_viny);
+  // (scan_stage_rows, scan_filter.cpp: the rows that are gathered through the kept list in ONE sweep over it, the ahr
+  // weights, the total weight -- shared with the batch of raw scans)
+  const ScanStageRows rows{st, reinterpret_cast<int *>(st + c), st + 2 * c, st + 3 * c};
   // ... and the host's own copies of weights and factors (what the commit records; the device makes the same bits),
   // touched only once nothing can fail any more that would leave the scan before as the current one
   // (those that nothing in front of the launch needs are made behind it, while the GPU runs: scan_record_finish)
-  if (weighting == 0) {
-    as.w_even = 1.0 / k;  // EvenSPW (:21-32)
-  } else if (weighting == 1) {
-    as.tab_viny = ctx->d_scan_tab + 2 * (size_t)ctx->scan_tab_cap;
-  } else {
-    sp.a.resize(k);
-    sp.r.assign(r_, r_ + k);
-    sp.w.resize(k);
-    for (int q = 0; q < k; ++q) sp.a[q] = angle[kept[q]];
-    rc = slamhip_scan_weights(2, k, sp.r.data(), sp.a.data(), sp.w.data());
-    if (rc) return rc;
-    double *w_ = st + 3 * c;
-    std::memcpy(w_, sp.w.data(), sizeof(double) * k);
-    as.h_weight = w_;
-  }
-  as.h_factor = f_;
+  if (weighting == 1) ctx->h_weight.resize(k);
+  double tot_w = 0;
+  rc = scan_stage_rows(sp, n, range, angle, factor, weighting, k, kept.data(), rows, ctx->h_weight.data(), sp.stage,
+                       &as.w_even, &tot_w);
+  if (rc) return invalid(scan_error_text(rc));
+  as.h_range = rows.range;
+  as.h_kept = k == n ? nullptr : rows.kept;
+  as.h_factor = factor ? rows.factor : nullptr;
+  as.h_weight = weighting == 2 ? rows.weight : nullptr;
+  if (weighting == 1) as.tab_viny = ctx->d_scan_tab + 2 * (size_t)ctx->scan_tab_cap;
   as.tab_cos = ctx->d_scan_tab;
   as.tab_sin = ctx->d_scan_tab + (size_t)ctx->scan_tab_cap;
   as.dst = ctx->d_scan;
   as.stride = c;
   as.n = k;
   int turn = 0;
-  const double tot_w = weighting == 0   ? scan_total_weight_even(k, as.w_even)
-                       : weighting == 1 ? tot_viny  // (the same additions in the same order)
-                                        : scan_total_weight(as.h_weight, k);
   const unsigned seq = scan_stage_turnover(ctx, k, c, tot_w, &turn);
   // the kept points' angles, for SLAMHIP_POSE_TRIG_RAW_EXACT: sp.angle[sp.kept[q]], written out when an exact call asks
   // (scan_angles_materialise); slamhip_scan_set_angles replaces them

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "scan_filter.h"
 #include "slamhip.h"
 
 namespace slamhip {
@@ -238,6 +239,9 @@ struct ScanAssembleArgs {
 };
 hipError_t launch_scan_assemble(const ScanAssembleArgs &a, unsigned *counter, unsigned *h_flag, unsigned seq,
                                 hipStream_t stream);
+// k_scan_assemble_batch: n_jobs scan blocks in one launch, job c from table[c] (a table in pinned memory; grid.y = job,
+// max_stride = the widest block's stride)
+hipError_t launch_scan_assemble_batch(const ScanAssembleArgs *table, int n_jobs, int max_stride, hipStream_t stream);
 // (both uploads write the host's stride_host doubles of a cell and leave the rest of it alone -- a GMAPPING cell's pad)
 hipError_t launch_scatter_cells(double *payload, int pitch, int cell_dbl, int stride_host, int n,
                                 const int *d_coords, const double *d_vals, hipStream_t stream);
@@ -345,15 +349,13 @@ struct slamhip_ctx {
   // slamhip_scan_filter_upload: what depends on the scanner's beam ANGLES only (cos / sin per raw beam as the scan's
   // trig provider tabulates them, the viny weighting's angular factor) is kept between scans -- a scanner's angles do
   // not change -- next to the buffers the filtered scan is assembled in
-  struct ScanPrep {
-    std::vector<double> angle, cos_a, sin_a, viny_f;
-    int trig_mode = -1;
-    double a_min = 0, a_max = 0, a_inc = 0;
+  struct ScanPrep : slamhip::ScanTables {  // (angle, cos_a, sin_a, viny_f and the scanner's settings: scan_filter.h)
     std::vector<double> r, a, c, s, w, f;
     std::vector<int> kept;       // raw indices of the CURRENT scan's points (of the last call that uploaded one)
     std::vector<int> kept_next;  // ... of the call under way: becomes `kept` once its scan is the current one
-    std::vector<unsigned char> filter_mask;  // scan_filter.cpp: one byte per raw point ...
-    std::vector<double> filter_trig;         // ... and the per-beam cosines | sines of SLAMHIP_TRIG_RAW on a bounded map
+    slamhip::ScanFilterScratch filter;  // scan_filter.cpp: one byte per raw point and the per-beam cosines | sines of
+                                        // SLAMHIP_TRIG_RAW on a bounded map
+    slamhip::ScanStageScratch stage;    // ... the filtered scan's angles / ranges / weights where the weighting asks
   } scan_prep;
   // ... and the same three per-beam arrays resident in HBM (cos | sin | viny_f, scan_tab_cap doubles each), where
   // k_scan_assemble gathers them: uploaded when scan_prep recomputes, never by a context that is not given raw scans

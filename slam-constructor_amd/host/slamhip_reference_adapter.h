@@ -16,6 +16,8 @@
 //                          use / growth, dirty log afterwards)
 //   HipGridScanMatcher     GridScanMatcher whose process_scan runs the MC / HC / BF accept chain
 //                          through slamhip_matcher_process_scan; observers are fed from the replay
+//   hip_process_raw_scans  K robots' raw scans through ONE slamhip_matcher_process_raw_scan_batch call: what
+//                          HipGridScanMatcher::process_raw_scan does for one scan, for K of them
 //   HipScanProbabilityEstimator  ScanProbabilityEstimator whose estimate_scan_probability is one
 //                          slamhip_score_poses call (used by code that scores single poses)
 //
@@ -24,6 +26,7 @@
 #ifndef SLAMHIP_REFERENCE_ADAPTER_H
 #define SLAMHIP_REFERENCE_ADAPTER_H
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -351,7 +354,23 @@ inline void hip_upload_filtered_scan(slamhip_ctx *ctx, const LaserScan2D &scan, 
 }
 
 // ------------------------------------------------------------------------------------------------
+class HipGridScanMatcher;
+// One of K raw scans matched in one library call (hip_process_raw_scans below): `owner` is the robot's own matcher --
+// its map mirror, filter parameters, trig provider and weighting describe the job's map and scanner --, the rest is
+// what its process_scan would have been given.  pose_delta / prob: the results.
+struct HipRawScanJob {
+  HipGridScanMatcher *owner;
+  const TransformedLaserScan *raw_scan;
+  const RobotPose *init_pose;
+  const GridMap *map;
+  RobotPoseDelta pose_delta;
+  double prob;
+};
+inline void hip_process_raw_scans(HipGridScanMatcher &matcher, std::vector<HipRawScanJob> &jobs);
+
 class HipGridScanMatcher : public GridScanMatcher {
+  friend void hip_process_raw_scans(HipGridScanMatcher &matcher, std::vector<HipRawScanJob> &jobs);
+
 public:
   // `spe` is the reference estimator the SLAM was configured with: it still does filter_scan on
   // the host (once per scan); scoring goes to the GPU.  `matcher` was created with
@@ -491,6 +510,86 @@ private:
   std::vector<double> _r, _a, _f;
   std::vector<int> _occ;
 };
+
+// K robots / replicas, one library call: what HipGridScanMatcher::process_raw_scan does for one scan, for K of them --
+// every job's map mirror synced, its raw points as three arrays (kept between calls in the job's owner), then
+// slamhip_matcher_process_raw_scan_batch on `matcher`'s library matcher: the scans are filtered per job against its own
+// map and initial pose, assembled on the device by one launch and matched in the shared launches.  Every job gets the
+// result of its owner's process_raw_scan, bit for bit.  All owners live on `matcher`'s context and have been given
+// their filter parameters (set_filter_params); nobody listens (observers are not called).  A run-time failure is
+// handled as process_scan handles it: once more on the chain of kernels, then every job reports "unknown".
+inline void hip_process_raw_scans(HipGridScanMatcher &matcher, std::vector<HipRawScanJob> &jobs) {
+  const int K = (int)jobs.size();
+  if (K == 0) return;
+  std::vector<slamhip_raw_match_job> lib(K);
+  for (int k = 0; k < K; ++k) {
+    HipRawScanJob &j = jobs[k];
+    HipGridScanMatcher &o = *j.owner;
+    if (o._ctx != matcher._ctx || !o._own_filter) {
+      std::cerr << "[slamhip] hip_process_raw_scans: job " << k << " has another context or no filter parameters" << std::endl;
+      std::exit(-1);
+    }
+    const auto &pts = j.raw_scan->scan.points();
+    const int n = (int)pts.size();
+    o._mirror->sync(*j.map, o._dirty_source);
+    o._scan = LaserScan2D{};
+    o._r.resize(n);
+    o._a.resize(n);
+    o._f.resize(n);
+    o._occ.resize(n);
+    for (int i = 0; i < n; ++i) {
+      o._r[i] = pts[i].range();
+      o._a[i] = pts[i].angle();
+      o._f[i] = pts[i].factor();
+      o._occ[i] = pts[i].is_occupied() ? 1 : 0;
+    }
+    slamhip_raw_match_job &l = lib[k];
+    l.map_id = o._mirror->id();
+    l.scan = slamhip_raw_scan{n, o._r.data(), o._a.data(), o._occ.data(), o._f.data(), o._trig.mode, o._trig.a_min,
+                              o._trig.a_max, o._trig.a_inc, o._skip_rate, o._max_range, o._bounded ? 1 : 0, o._weighting};
+    l.init_pose[0] = j.init_pose->x;
+    l.init_pose[1] = j.init_pose->y;
+    l.init_pose[2] = j.init_pose->theta;
+  }
+  // (a scan without points: the library asks for n > 0; the reference's answer for it is the empty scan's)
+  std::vector<int> live;
+  std::vector<slamhip_raw_match_job> packed;
+  for (int k = 0; k < K; ++k)
+    if (lib[k].scan.n > 0) {
+      live.push_back(k);
+      packed.push_back(lib[k]);
+    }
+  std::vector<double> d(3 * packed.size() + 3, 0.0), prob(packed.size() + 1, std::numeric_limits<double>::quiet_NaN());
+  if (!packed.empty()) {
+    slamhip_or_die(slamhip_matcher_set_observer(matcher._m, nullptr), "set_observer");
+    int rc = slamhip_matcher_process_raw_scan_batch(matcher._m, (int)packed.size(), packed.data(), d.data(), prob.data(), nullptr);
+    if (rc == SLAMHIP_ERR_INVALID || rc == SLAMHIP_ERR_UNSUPPORTED || rc == SLAMHIP_ERR_NO_DEVICE)
+      slamhip_or_die(rc, "process_raw_scan_batch");
+    if (rc != SLAMHIP_OK) {
+      ++matcher._n_failures;
+      std::cerr << "[slamhip] process_raw_scan_batch failed (" << slamhip_last_error() << "): once more on the chain of kernels"
+                << std::endl;
+      slamhip_matcher_set_device_chain(matcher._m, 1, 0);
+      rc = slamhip_matcher_process_raw_scan_batch(matcher._m, (int)packed.size(), packed.data(), d.data(), prob.data(), nullptr);
+      slamhip_matcher_set_device_chain(matcher._m, 2, 0);
+      if (rc != SLAMHIP_OK) {
+        ++matcher._n_failures;
+        std::cerr << "[slamhip] process_raw_scan_batch failed again (" << slamhip_last_error()
+                  << "): these scans' matches are reported as unknown (NaN, no pose correction)" << std::endl;
+        std::fill(d.begin(), d.end(), 0.0);
+        std::fill(prob.begin(), prob.end(), std::numeric_limits<double>::quiet_NaN());
+      }
+    }
+  }
+  for (int k = 0; k < K; ++k) {
+    jobs[k].pose_delta = RobotPoseDelta{0, 0, 0};
+    jobs[k].prob = std::numeric_limits<double>::quiet_NaN();
+  }
+  for (size_t q = 0; q < live.size(); ++q) {
+    jobs[live[q]].pose_delta = RobotPoseDelta{d[3 * q], d[3 * q + 1], d[3 * q + 2]};
+    jobs[live[q]].prob = prob[q];
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 class HipScanProbabilityEstimator : public ScanProbabilityEstimator {
