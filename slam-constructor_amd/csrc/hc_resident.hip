@@ -99,9 +99,10 @@ constexpr int kSelStop = -3;     // leave: the replay found no terminal round (a
 // again beside the table (K = 8).
 // RAW (a lone chain in the default sum order, straight behind the raw scan's filter: slamhip_matcher_process_raw_scan):
 // nobody has assembled the scan block yet.  Every workgroup makes its beams' constants itself, the way k_scan_assemble
-// makes them (scan_assemble_point: the staged ranges / indices / factors / weights from pinned memory -- one PCIe read
+// makes them (scan_assemble_device.h: the staged ranges / indices / factors / weights from pinned memory -- one PCIe read
 // per XCD, the other workgroups' loads hit its L2: tools/probes/host_read_probe.hip --, cosine / sine / the viny factor
-// from the resident tables), keeps ALL FIVE constants of the beams behind a thread's first one in LDS, and reads
+// from the resident tables; issued at the top of the prologue, waited for ONCE at its end: see "RAW" in the prologue),
+// keeps ALL FIVE constants of the beams behind a thread's first one in LDS, and reads
 // nothing of the scan block; the bookkeeping workgroup, idle behind the first super-step, writes the block for
 // whoever comes after this launch.  The assembly kernel and the kernel boundary behind it leave the match's critical
 // path; no workgroup waits for another one's scan data.
@@ -174,38 +175,55 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
   }
   // RAW: this thread's beams, assembled from the staged scan and the resident tables.  The staged arrays come over
   // PCIe (~2 us more than HBM, tools/probes/host_read_probe.hip) and nothing in the prologue needs them: they are asked
-  // for HERE and first touched at the barrier that ends the prologue, with the exchange block's set-up and the serial
-  // derivation of the first pose in between.  A wave's loads return in the order they were issued, so whatever the
-  // prologue does wait for -- the word read at entry, this workgroup's round instances -- is asked for in FRONT of them.
+  // for HERE (scan_assemble_issue: loads the compiler's wait counts do not see), the thread's first beam and its first
+  // further one together, and waited for ONCE, in front of the barrier that ends the prologue, with the exchange
+  // block's set-up, the first barrier and the serial derivation of the first pose in between.  A wave's loads return in
+  // the order they were issued, and a wait the compiler places counts only the loads it sees: so in that window the
+  // prologue consumes no vector load at all --
+  //   this workgroup's round instances are asked for in FRONT of the staged loads, stay in eight named registers
+  //     (an indexed private array went through scratch) and go to LDS behind the one wait -- the loop reads them, the
+  //     prologue does not:
+  //   the first pose is derived from the ONE instance it needs, read by scalar loads (first_in, below);
+  //   the word read at entry is looked at behind the one wait, and acted on behind the barrier that follows it.
   // The first further beam's constants wait in registers (1080 beams on 1024 threads: those threads are the very wave
-  // that derives the pose); where a thread has more than one further beam, the others follow behind the pose.
+  // that derives the pose); where a thread has more than one further beam, the others follow behind the pose, two at
+  // a time in the same issue / wait / finish shape.
+  // (threads without a beam ask for the scan's last one: no lane-divergent branch around the loads, and a line that is
+  // read anyway; a WAVE without a further beam skips the second issue)
   const bool mine_here = lwave == 1 && (t & 63) < kHcShapes && !init_slot && exists;
   constexpr int kMineQ = (int)(sizeof(HcInst) / 16);
-  uint4 mine_regs[kMineQ];
-  ScanPoint raw_more{0.0, 0.0, 0.0, 0.0, 0.0};
+  static_assert(!RAW || kMineQ == 8, "RAW: the instance record in eight named registers");
+  u32x4 mine0, mine1, mine2, mine3, mine4, mine5, mine6, mine7;
+  ScanInFlight raw_first{0.0, 0.0, 0.0, 0.0, 1.0, 0}, raw_more{0.0, 0.0, 0.0, 0.0, 1.0, 0};
+  HcInst first_in = {};  // RAW: this workgroup's round instance of the first tree's shape (uniform: scalar registers)
+  const int n_last = n > 0 ? n - 1 : 0;
+  const bool raw_more_wave = RAW && __builtin_amdgcn_readfirstlane(NTH + (t & ~63)) < n;
   if constexpr (RAW) {
     if (mine_here) {
-      const uint4 *src = reinterpret_cast<const uint4 *>(&a.shapes[t & 63].inst[inst_of_slot]);
-#pragma unroll
-      for (int q = 0; q < kMineQ; ++q) mine_regs[q] = src[q];
+      const u32x4 *src = reinterpret_cast<const u32x4 *>(&a.shapes[t & 63].inst[inst_of_slot]);
+      mine0 = src[0];
+      mine1 = src[1];
+      mine2 = src[2];
+      mine3 = src[3];
+      mine4 = src[4];
+      mine5 = src[5];
+      mine6 = src[6];
+      mine7 = src[7];
     }
     asm volatile("" ::: "memory");  // (issue order: the instances' loads, then the beams')
-    if (tl < n) {
-      const ScanPoint p = scan_assemble_point(a.raw, tl);
-      br = p.range;
-      bc = p.cos_a;
-      bs = p.sin_a;
-      bw = p.weight;
-      bf = p.factor;
+    scan_assemble_issue(a.raw, tl < n ? tl : n_last, raw_first);
+    if (raw_more_wave) scan_assemble_issue(a.raw, NTH + t < n ? NTH + t : n_last, raw_more);
+    {
+      const __attribute__((address_space(4))) HcInst *ip = (const __attribute__((address_space(4))) HcInst *)(
+          unsigned long long)&a.shapes[a.shape0].inst[init_slot ? 0 : inst_of_slot];
+#pragma unroll
+      for (int q = 0; q < 14; ++q) first_in.w[q] = ip->w[q];
     }
-    if (NTH + t < n) raw_more = scan_assemble_point(a.raw, NTH + t);
-    asm volatile("" ::: "memory");
-  }
-  if (mine_here) {
+  } else if (mine_here) {
     const uint4 *src = reinterpret_cast<const uint4 *>(&a.shapes[t & 63].inst[inst_of_slot]);
     uint4 *dst = reinterpret_cast<uint4 *>(&s_mine[half][t & 63]);
 #pragma unroll
-    for (int q = 0; q < kMineQ; ++q) dst[q] = RAW ? mine_regs[q] : src[q];
+    for (int q = 0; q < kMineQ; ++q) dst[q] = src[q];
   }
   // A thread scores up to five beams, and 1080 beams on 1024 threads give the first 56 threads a second one.  What
   // the cell ADDRESS of those further beams depends on -- range, cosine, sine -- is kept in LDS for the whole match
@@ -230,7 +248,8 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
   HcNextEntry *const s_tab = reinterpret_cast<HcNextEntry *>(s_term + a.tab_offset);
   // (ONE thread's reading decides for the workgroup, behind the barrier below: every thread for itself could let some
   // waves of a workgroup leave and others stay -- ADVICE r4)
-  if (t == 0) s_stop = fail_epoch_at_entry == a.epoch ? 1 : 0;
+  // (RAW: behind the staged scan's wait, below -- looking at a loaded word here would wait for the staged loads too)
+  if (!RAW && t == 0) s_stop = fail_epoch_at_entry == a.epoch ? 1 : 0;
   if (tl < 4 && exists) {  // this slot's granules of both parities start the match empty (see hc_tag)
     HcGranule *g0 = (tl & 2) ? &rc->seq[tl & 1][slot] : &rc->gran[tl & 1][slot];
     gran_store(g0, 0.0, 0ull, 0u);
@@ -244,9 +263,11 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
 
   if (t == 0) {
     HcState st{};
-    st.x = a.inits ? a.inits[3 * blockIdx.y] : a.init[0];
-    st.y = a.inits ? a.inits[3 * blockIdx.y + 1] : a.init[1];
-    st.theta = a.inits ? a.inits[3 * blockIdx.y + 2] : a.init[2];
+    // (RAW: a lone chain, `init` -- the launcher refuses anything else; a load here would wait for the staged scan)
+    const double *const inits = RAW ? nullptr : a.inits;
+    st.x = inits ? inits[3 * blockIdx.y] : a.init[0];
+    st.y = inits ? inits[3 * blockIdx.y + 1] : a.init[1];
+    st.theta = inits ? inits[3 * blockIdx.y + 2] : a.init[2];
     st.dt = a.dt0;
     st.dr = a.dr0;
     st.shape = a.shape0;
@@ -257,8 +278,8 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
     s_sel = kSelFirst;
     s_cert_end = 0;
   }
-  __syncthreads();  // s_mine, s_stop, s_st
-  if (s_stop) return;  // started after the others gave up (uniform)
+  __syncthreads();  // s_mine, s_stop, s_st (RAW: s_st; the other two at the next barrier)
+  if (!RAW && s_stop) return;  // started after the others gave up (uniform)
   // ---- the first super-step's pose: the initial pose (bookkeeping workgroup), or this workgroup's candidate of the
   // first tree -- the one pose of a match that is derived serially
   if (lwave == 0) {
@@ -268,7 +289,7 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
     if (!init_slot && exists) {
       HcInst in;
 #pragma unroll
-      for (int q = 0; q < 14; ++q) in.w[q] = s_mine[half][st.shape].w[q];
+      for (int q = 0; q < 14; ++q) in.w[q] = RAW ? first_in.w[q] : s_mine[half][st.shape].w[q];  // (st.shape == a.shape0)
       go = inst_of_slot < (int)((a.n_inst >> (8 * st.shape)) & 0xffull) &&
            (hc_is_root(in) || st.failed + hc_nfail_parent(in) < a.max_failed);  // else: behind the end of the chain
       if (go) {
@@ -288,16 +309,58 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
     }
   }
   if constexpr (RAW) {
-    for (int b = NTH + t; b < n; b += NT) {
-      const ScanPoint p = b == NTH + t ? raw_more : scan_assemble_point(a.raw, b);
+    const auto keep = [&](int b, const ScanPoint &p) __attribute__((always_inline)) {
       s_r[b] = p.range;
       s_ca[b] = p.cos_a;
       s_sa[b] = p.sin_a;
       s_w[b] = p.weight;
       s_f[b] = p.factor;
+    };
+    // ---- the ONE wait for the staged scan (and for everything this wave asked for in front of it)
+    scan_assemble_wait(raw_first, raw_more);
+    // (the instance records and the word read at entry count as arrived in the compiler's books on EVERY path from here
+    // on -- left pending on the paths that do not use them, their wait would land in the loop below, behind its issue)
+    asm volatile("" ::"v"(mine0), "v"(mine1), "v"(mine2), "v"(mine3), "v"(mine4), "v"(mine5), "v"(mine6), "v"(mine7),
+                 "v"(fail_epoch_at_entry));
+    {
+      ScanPoint p, pm;
+      scan_assemble_finish(a.raw, raw_first, raw_more, p, pm);
+      if (tl < n) {
+        br = p.range;
+        bc = p.cos_a;
+        bs = p.sin_a;
+        bw = p.weight;
+        bf = p.factor;
+      }
+      if (NTH + t < n) keep(NTH + t, pm);
+    }
+    if (mine_here) {
+      u32x4 *dst = reinterpret_cast<u32x4 *>(&s_mine[half][t & 63]);
+      dst[0] = mine0;
+      dst[1] = mine1;
+      dst[2] = mine2;
+      dst[3] = mine3;
+      dst[4] = mine4;
+      dst[5] = mine5;
+      dst[6] = mine6;
+      dst[7] = mine7;
+    }
+    if (t == 0) s_stop = fail_epoch_at_entry == a.epoch ? 1 : 0;
+    // further beams of a narrow workgroup (256 threads: up to three more, 512: one), two at a time; the bound is the
+    // wave's, so that every lane of a wave that issues has a load to wait for
+    for (int b = NTH + NT + t; b - (t & 63) < n; b += 2 * NT) {
+      ScanInFlight f0{0.0, 0.0, 0.0, 0.0, 1.0, 0}, f1{0.0, 0.0, 0.0, 0.0, 1.0, 0};
+      scan_assemble_issue(a.raw, b < n ? b : n_last, f0);
+      scan_assemble_issue(a.raw, b + NT < n ? b + NT : n_last, f1);
+      scan_assemble_wait(f0, f1);
+      ScanPoint p0, p1;
+      scan_assemble_finish(a.raw, f0, f1, p0, p1);
+      if (b < n) keep(b, p0);
+      if (b + NT < n) keep(b + NT, p1);
     }
   }
-  __syncthreads();
+  __syncthreads();  // (RAW: s_mine and s_stop as well)
+  if (RAW && s_stop) return;  // started after the others gave up (uniform)
 
   // RAW ---- the scan block for whoever comes after this launch (the map update, a download, a later match on the
   // resident scan), as k_scan_assemble leaves it, pads zeroed: by the bookkeeping workgroup, which scores nothing behind
@@ -1022,7 +1085,7 @@ hipError_t launch_hc_chain_resident(const HcChainArgs &a_in, int cell_model, int
   const bool pair = key.batch && key.pair;
   // (the window form keeps no beam constants in LDS; the RAW form all five of them)
   const int ldsc = key.window ? 0 : (key.raw ? 2 : (a.lds_consts != 0 ? 1 : 0));
-  if (key.raw && a.raw.n != a.scan.n) return hipErrorInvalidValue;
+  if (key.raw && (a.raw.n != a.scan.n || a.inits || n_chains != 1)) return hipErrorInvalidValue;
   const int grid = pair ? 3 * a.max_inst + 1 : 6 * a.max_inst + 1;  // (a pair: two scoring slots per workgroup + the bookkeeping one)
   a.tab_offset = (int)hc_resident_tab_offset(nt, a.scan.n, ldsc, pair);
   return launch_kernel(hc_resident_kernel(cell_model, key), dim3(grid, n_chains), dim3(hc_nt_of(nt)),
