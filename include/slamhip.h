@@ -637,6 +637,41 @@ int slamhip_matcher_m3rsm_match_many(slamhip_matcher *m, int n_requests, const s
 /* The committed calls of the last slamhip_matcher_m3rsm_match_many: rows of 8 doubles = request, rotation, bot, top,
  * left, right, score, level; cap and *n as for slamhip_matcher_m3rsm_trace. */
 int slamhip_matcher_m3rsm_trace_many(slamhip_matcher *m, int cap, double *rows, int *n);
+/* K INDEPENDENT matches in one call -- K robots or replicas --: request k = (pyramid, stored scan slot, pose), K answers.
+ * Every request has its own search (queue, best finest probability, memo); the searches advance in LOCK-STEP and share
+ * nothing but the launches: all root layers in one slamhip_pyramid_score_requests launch, then rounds -- every search
+ * that needs children the memo lacks hands over its popped match and its own width - 1 ride-alongs, the parents of all
+ * of them go, in request order, into ONE slamhip_pyramid_expand_requests launch, every search takes its slice and runs
+ * on; a search that has ended takes no further part.  1 + (the longest search's super-steps) launches instead of the sum
+ * over requests; between two launches the searches run on worker threads (slamhip_matcher_set_m3rsm_threads).
+ *   out_deltas[3 k ..], out_probs[k]: what a lone slamhip_matcher_process_scan gives -- a matcher with this cfg, these
+ *   limits, steps and speculation over req[k].pyramid, slot req[k].scan_slot selected, at req[k].init_pose --, bit for
+ *   bit in both sum orders: delta, probability, committed calls and counters.  A request whose search finds nothing gets
+ *   what the lone call makes of that (delta 0, prob NaN, no observer call); the other requests are not affected.
+ *   The matcher's limits, steps, cfg and speculation apply to every request; its own pyramid takes no part.  The same
+ *   slot or pyramid may appear in several requests.  Observer: on_matching_end once per request that has a match, in
+ *   request order, after the searches.  slamhip_matcher_stats: scorer_calls and poses_evaluated summed over the requests,
+ *   launches = the launches made.  With SLAMHIP_SUM_SEQUENTIAL a launch stages slots x beams doubles of terms per
+ *   candidate; a round whose terms would exceed 256 MiB goes as consecutive launches in request order (same results).
+ *   slamhip_matcher_m3rsm_trace / _trace_many are NOT defined after this call: use slamhip_matcher_m3rsm_trace_each.
+ * SLAMHIP_ERR_INVALID / _STATE as for slamhip_matcher_m3rsm_match_many, found before anything is launched; also
+ * SLAMHIP_ERR_INVALID: not a BF_M3RSM matcher; speculation (0, 0) (the per-pop measuring route has no batched form).
+ * SLAMHIP_ERR_UNSUPPORTED: a request reached the bound on super-steps (no outputs then).
+ * slamhip_matcher_process_scan_batch / _process_raw_scan_batch keep refusing a BF_M3RSM matcher. */
+int slamhip_matcher_m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req,
+                                     double *out_deltas /* 3 per request */, double *out_probs);
+/* Request `request` of the last slamhip_matcher_m3rsm_match_each: its committed calls (rows as for
+ * slamhip_matcher_m3rsm_trace) and its counters -- scorer_calls, poses_evaluated as slamhip_matcher_stats reports them
+ * after the lone match, the super-steps it took part in and its branching pops.  Null outputs are skipped. */
+int slamhip_matcher_m3rsm_trace_each(slamhip_matcher *m, int request, int cap, double *rows /* 7 per row */, int *n);
+int slamhip_matcher_m3rsm_each_stats(slamhip_matcher *m, int request, long long *scorer_calls,
+                                     long long *poses_evaluated, long long *super_steps, long long *branching_pops);
+/* worker threads of slamhip_matcher_m3rsm_match_each's host half: 1 .. 16 (1: the calling thread alone), 0 = the default,
+ * min(requests, 8).  Results do not depend on it. */
+int slamhip_matcher_set_m3rsm_threads(slamhip_matcher *m, int threads);
+/* Bytes the launches of the last BF_M3RSM match -- lone, many-to-many or each -- wrote back to the host: 12 per root
+ * candidate (score, level), 44 per slot of every parent (rectangle, score, level), slots without a node included. */
+int slamhip_matcher_m3rsm_copied_back(slamhip_matcher *m, long long *bytes);
 int slamhip_matcher_destroy(slamhip_matcher *m);
 /* GridScanMatcher::reset_state (grid_scan_matcher.h:158) */
 int slamhip_matcher_reset_state(slamhip_matcher *m);

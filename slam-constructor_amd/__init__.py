@@ -67,6 +67,8 @@ slamhip_pyramid_expand_matches slamhip_pyramid_expand_matches_device slamhip_mat
 slamhip_matcher_set_m3rsm_speculation slamhip_matcher_m3rsm_trace
 slamhip_pyramid_score_requests slamhip_pyramid_expand_requests slamhip_matcher_m3rsm_match_many
 slamhip_matcher_m3rsm_trace_many
+slamhip_matcher_m3rsm_match_each slamhip_matcher_m3rsm_trace_each slamhip_matcher_m3rsm_each_stats
+slamhip_matcher_set_m3rsm_threads slamhip_matcher_m3rsm_copied_back
 slamhip_scan_table_uploads slamhip_scan_download
 slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download""".split()
 
@@ -300,6 +302,11 @@ def load(testing=False):
     L.slamhip_pyramid_expand_requests.argtypes = [vp, C.POINTER(SpeCfg), i, rq, i, _ip, _dp, _dp, d, i, _dp, _dp, _ip]
     L.slamhip_matcher_m3rsm_match_many.argtypes = [vp, i, rq, _ip, _dp, _dp]
     L.slamhip_matcher_m3rsm_trace_many.argtypes = [vp, i, _dp, _ip]
+    L.slamhip_matcher_m3rsm_match_each.argtypes = [vp, i, rq, _dp, _dp]
+    L.slamhip_matcher_m3rsm_trace_each.argtypes = [vp, i, i, _dp, _ip]
+    L.slamhip_matcher_m3rsm_each_stats.argtypes = [vp, i] + [C.POINTER(C.c_longlong)] * 4
+    L.slamhip_matcher_set_m3rsm_threads.argtypes = [vp, i]
+    L.slamhip_matcher_m3rsm_copied_back.argtypes = [vp, C.POINTER(C.c_longlong)]
     _libs[testing] = L
     return L
 
@@ -1137,6 +1144,41 @@ class Matcher:
         rows = np.zeros((n.value, 8))
         _check(self.L.slamhip_matcher_m3rsm_trace_many(self.h, n.value, _d(rows), C.byref(n)))
         return rows
+
+    def m3rsm_match_each(self, requests):
+        """BF_M3RSM, K independent matches in one call (slamhip_matcher_m3rsm_match_each): requests = a list of (pyramid,
+        scan_slot, pose), scans from Context.scan_store; every request has its own search, the searches share the
+        launches.  Returns a list of dict(delta[3], prob), request k's being the lone process_scan's on its inputs (delta
+        0, prob NaN where the search found nothing)."""
+        table = m3rsm_request_table(requests)
+        deltas, probs = np.zeros((len(table), 3)), np.zeros(len(table))
+        _check(self.L.slamhip_matcher_m3rsm_match_each(self.h, len(table), table, _d(deltas), _d(probs)))
+        return [dict(delta=deltas[k].copy(), prob=float(probs[k])) for k in range(len(table))]
+
+    def m3rsm_trace_each(self, k):
+        """The committed scorer calls of request k of the last m3rsm_match_each, [n, 7] as m3rsm_trace."""
+        n = C.c_int(0)
+        _check(self.L.slamhip_matcher_m3rsm_trace_each(self.h, int(k), 0, None, C.byref(n)))
+        rows = np.zeros((n.value, 7))
+        _check(self.L.slamhip_matcher_m3rsm_trace_each(self.h, int(k), n.value, _d(rows), C.byref(n)))
+        return rows
+
+    def m3rsm_each_stats(self, k):
+        """Request k of the last m3rsm_match_each: scorer_calls and poses_evaluated as stats() has them after the lone
+        match, the super-steps it took part in and its branching pops."""
+        v = [C.c_longlong() for _ in range(4)]
+        _check(self.L.slamhip_matcher_m3rsm_each_stats(self.h, int(k), *[C.byref(x) for x in v]))
+        return dict(scorer_calls=v[0].value, poses_evaluated=v[1].value, super_steps=v[2].value, branching_pops=v[3].value)
+
+    def set_m3rsm_threads(self, n):
+        """Worker threads of m3rsm_match_each's host half: 1 .. 16, 0 = the default (slamhip_matcher_set_m3rsm_threads)."""
+        _check(self.L.slamhip_matcher_set_m3rsm_threads(self.h, int(n)))
+
+    def m3rsm_copied_back(self):
+        """Bytes the launches of the last BF_M3RSM match wrote back to the host (slamhip_matcher_m3rsm_copied_back)."""
+        v = C.c_longlong()
+        _check(self.L.slamhip_matcher_m3rsm_copied_back(self.h, C.byref(v)))
+        return v.value
 
     def resident_stats(self):
         """Matches launched in the co-resident form, and how many of them gave up and were redone by the kernel chain."""

@@ -70,13 +70,48 @@ constexpr int kOk = 0;
 constexpr int kErrInvalid = 1;     // bad configuration
 constexpr int kErrSuperSteps = 2;  // max_super_steps reached
 constexpr int kErrScorer = 3;      // an expand call did not deliver a child the rule says exists
-constexpr int kErrNoMatch = 4;     // the queue ran empty (every bound NaN)
+constexpr int kErrNoMatch = 4;     // the queue ran empty (every bound under the cut)
 constexpr int kErrCallback = 5;    // a callback failed: its code is in Result::callback_rc
+constexpr int kPending = -1;       // Search::advance: parents wait for an expand call; run_each: the call ended first
 
 // The root layer of M3RSMEngine::add_scan_matching_request: rotation_drift = 0, step, 2 step, ... (accumulated) while
 // 2 drift <= 2 max_th_error under less_or_equal; per drift the rotations of std::set{drift, -drift}; per rotation the
 // empty rectangle, then the entire one.
 void root_candidates(const Config &cfg, std::vector<double> *rotation, std::vector<Rect> *rect);
+
+// The search as a RESUMABLE object: the loop stops where it needs an expand call and goes on once the caller has made it.
+// run_many drives one Search to its end; run_each (m3rsm_each.h) drives several, one expand call per round for all of
+// them.  The loop stops at the first child of a popped match that the memo lacks -- usually child 0, but a point may be
+// there already as the corner of a neighbouring box -- with the children before it committed, and resumes at that child:
+// the queue the ride-alongs are read from is the one a mid-branch super-step has always seen.
+//   Search s(cfg, n_requests, &result, &trace);   // cfg, result and trace outlive s; Search::check(cfg, n) said kOk
+//   s.commit_roots(n, request, rotation, rect, score, level);       // add_scan_matching_request, request by request
+//   while ((rc = s.advance()) == kPending) { <expand s.parent_*() to cfg.depth>; s.absorb(slot_rect, slot_score, slot_level); }
+class Search {
+ public:
+  static int check(const Config &cfg, int n_requests);  // kOk or kErrInvalid
+  Search(const Config &cfg, int n_requests, Result *result, std::vector<Call> *trace);
+  ~Search();
+  Search(const Search &) = delete;
+  Search &operator=(const Search &) = delete;
+  // the root layer: candidates in the order they are to be committed, with their bounds
+  void commit_roots(size_t n, const int *request, const double *rotation, const double *rect, const double *score,
+                    const int *level);
+  // Runs the matcher's loop until it ends (kOk, kErrNoMatch, kErrSuperSteps, kErrScorer: the result is complete) or
+  // needs a child the memo lacks: kPending, with the popped match and the next width - 1 unexpanded non-point entries of
+  // the queue as parents.
+  int advance();
+  int n_parents() const;
+  const int *parent_request() const;
+  const double *parent_rotation() const;
+  const double *parent_rect() const;  // 4 per parent
+  // the expand call's answer for the parents at hand: slots_of(cfg.depth) slots per parent (counts the super-step)
+  void absorb(const double *slot_rect, const double *slot_score, const int *slot_level);
+
+ private:
+  struct Impl;
+  Impl *impl_;
+};
 
 // One match; returns one of the codes above.  `trace` (may be null) receives every committed call.
 int run(const Config &cfg, const ScoreFn &score_roots, const ExpandFn &expand, Result *result, std::vector<Call> *trace);

@@ -9,6 +9,7 @@
 #include "bf_device.h"
 #include "hc_chain_device.h"
 #include "hc_shape.h"
+#include "m3rsm_each.h"
 #include "m3rsm_engine.h"
 #include "map_pyramid_score.h"
 #include "mc_chain_device.h"
@@ -259,6 +260,13 @@ struct slamhip_matcher {
     slamhip::m3rsm::Result res;
     std::vector<slamhip::m3rsm::Call> trace;  // the committed calls of the last match
     bool per_pop = false;  // no expand launches: a slamhip_pyramid_score_matches launch per popped match
+    // the last slamhip_matcher_m3rsm_match_each: per request its result, the engine's code and its committed calls
+    std::vector<slamhip::m3rsm::Result> each_res;
+    std::vector<int> each_code;
+    std::vector<std::vector<slamhip::m3rsm::Call>> each_trace;
+    int each_threads = 0;  // workers of the host half of a round (0: min(requests, 8))
+    std::unique_ptr<slamhip::m3rsm::Pool> each_pool;  // ... kept from call to call, made anew when the count changes
+    long long copied_back = 0;  // bytes the launches of the last match wrote back to the host (scores, levels, rectangles)
   };
   bool is_m3rsm = false;
   std::unique_ptr<M3rsm> m3;
@@ -1730,12 +1738,16 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
 // BruteForceMultiResolutionScanMatcher::process_scan: the engine's loop on the host, its scores from the pyramid -- the
 // root layer in one slamhip_pyramid_score_matches launch, everything below it in expand launches (m3rsm.hip), one per
 // super-step.  on_matching_end is the one event the reference's matcher emits.
+// what a launch writes back per candidate (score, level) and per slot (rectangle, score, level)
+constexpr long long kScoreBack = sizeof(double) + sizeof(int), kSlotBack = 5 * sizeof(double) + sizeof(int);
+
 int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3], double *out_prob) {
   slamhip_matcher::M3rsm &s = *m->m3;
   slamhip_ctx *ctx = m->ctx;
   m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
   s.trace.clear();
   s.res = m3rsm::Result{};
+  s.copied_back = 0;
   if (std::find(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)s.pyr) == ctx->pyramids.end())
     return invalid_arg("the matcher's pyramid has been destroyed");
   int rc = pyr_check_fresh(s.pyr);
@@ -1747,10 +1759,12 @@ int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
   if (rc) return rc;
   const double t0 = MatchJob::now_us();
   const m3rsm::ScoreFn roots = [&](int n, const double *rot, const double *rect, double *score, int *level) {
+    s.copied_back += kScoreBack * n;
     return slamhip_pyramid_score_matches(ctx, s.pyr, &m->cfg, init_pose, n, rot, rect, score, level);
   };
   const m3rsm::ExpandFn expand = [&](int n, const double *rot, const double *rect, int depth, double *slot_rect,
                                      double *slot_score, int *slot_level) {
+    s.copied_back += kSlotBack * n * m3rsm::slots_of(depth);
     return slamhip_pyramid_expand_matches(ctx, s.pyr, &m->cfg, init_pose, n, rot, rect, s.cfg.translation_step, depth,
                                           slot_rect, slot_score, slot_level);
   };
@@ -1771,6 +1785,7 @@ int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
       slot_score[c] = nan;
       slot_level[c] = -1;
     }
+    s.copied_back += kScoreBack * nk;
     return nk ? slamhip_pyramid_score_matches(ctx, s.pyr, &m->cfg, init_pose, nk, k_rot, k_rect, slot_score, slot_level) : 0;
   };
   m3rsm::Config run_cfg = s.cfg;
@@ -1811,6 +1826,7 @@ int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
   m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
   s.trace.clear();
   s.res = m3rsm::Result{};
+  s.copied_back = 0;
   {
     std::vector<PyrSource> src;  // (checked before anything runs: the launches check again, they are entry points too)
     const int rc = pyr_many_sources(ctx, &m->cfg, n_requests, req, &src);
@@ -1818,10 +1834,12 @@ int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
   }
   const double t0 = MatchJob::now_us();
   const m3rsm::ScoreManyFn roots = [&](int n, const int *rq, const double *rot, const double *rect, double *score, int *level) {
+    s.copied_back += kScoreBack * n;
     return slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, n, rq, rot, rect, score, level);
   };
   const m3rsm::ExpandManyFn expand = [&](int n, const int *rq, const double *rot, const double *rect, int depth,
                                          double *slot_rect, double *slot_score, int *slot_level) {
+    s.copied_back += kSlotBack * n * m3rsm::slots_of(depth);
     return slamhip_pyramid_expand_requests(ctx, &m->cfg, n_requests, req, n, rq, rot, rect, s.cfg.translation_step, depth,
                                            slot_rect, slot_score, slot_level);
   };
@@ -1843,6 +1861,7 @@ int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
       slot_score[c] = nan;
       slot_level[c] = -1;
     }
+    s.copied_back += kScoreBack * nk;
     return nk ? slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, nk, k_req, k_rot, k_rect, slot_score, slot_level) : 0;
   };
   m3rsm::Config run_cfg = s.cfg;
@@ -1875,9 +1894,170 @@ int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
   return SLAMHIP_OK;
 }
 
+// K INDEPENDENT matches advancing in lock-step (m3rsm::run_each): all root layers in one slamhip_pyramid_score_requests
+// launch, then per round one slamhip_pyramid_expand_requests launch over the parents of every search that waits for
+// one, request = job.  Each search is the lone match's, so request k gets what m3rsm_process_scan gives on its inputs.
+constexpr size_t kEachStageLimit = (size_t)256 << 20;  // a launch's strict-mode terms beyond this: consecutive launches
+
+int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req, double *out_deltas, double *out_probs) {
+  slamhip_matcher::M3rsm &s = *m->m3;
+  slamhip_ctx *ctx = m->ctx;
+  m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
+  s.trace.clear();
+  s.res = m3rsm::Result{};
+  s.copied_back = 0;
+  s.each_res.clear();
+  s.each_code.clear();
+  s.each_trace.clear();
+  if (s.per_pop) return invalid_arg("speculation (0, 0), the per-pop measuring route, has no batched form");
+  std::vector<PyrSource> src;  // (checked before anything runs: the launches check again, they are entry points too)
+  {
+    const int rc = pyr_many_sources(ctx, &m->cfg, n_requests, req, &src);
+    if (rc) return rc;
+  }
+  const double t0 = MatchJob::now_us();
+  const bool strict = m->cfg.sum_order == SLAMHIP_SUM_SEQUENTIAL;
+  long long launches = 0;
+  std::vector<size_t> bytes;
+  std::vector<int> first;
+  // entries [first[c], first[c + 1]) per launch: one launch, unless strict mode's terms (slots x beams doubles per
+  // entry) would outgrow the limit
+  const auto cut = [&](int n, const int *rq, size_t slots) {
+    if (!strict) {
+      first.assign({0, n});
+      return;
+    }
+    bytes.resize(n);
+    for (int i = 0; i < n; ++i) bytes[i] = sizeof(double) * slots * (size_t)src[rq[i]].scan.n;
+    m3rsm::split_by_bytes(bytes.data(), n, kEachStageLimit, &first);
+  };
+  const m3rsm::ScoreManyFn roots = [&](int n, const int *rq, const double *rot, const double *rect, double *score, int *level) {
+    cut(n, rq, 1);
+    s.copied_back += kScoreBack * n;
+    for (size_t c = 0; c + 1 < first.size(); ++c) {
+      const int at = first[c];
+      const int rc = slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, first[c + 1] - at, rq + at, rot + at,
+                                                    rect + 4 * (size_t)at, score + at, level + at);
+      ++launches;
+      if (rc) return rc;
+    }
+    return 0;
+  };
+  const m3rsm::ExpandManyFn expand = [&](int n, const int *rq, const double *rot, const double *rect, int depth,
+                                         double *slot_rect, double *slot_score, int *slot_level) {
+    const size_t slots = (size_t)m3rsm::slots_of(depth);
+    cut(n, rq, slots);
+    s.copied_back += kSlotBack * n * (long long)slots;
+    for (size_t c = 0; c + 1 < first.size(); ++c) {
+      const size_t at = (size_t)first[c];
+      const int rc = slamhip_pyramid_expand_requests(ctx, &m->cfg, n_requests, req, first[c + 1] - first[c], rq + at, rot + at,
+                                                     rect + 4 * at, s.cfg.translation_step, depth, slot_rect + 4 * at * slots,
+                                                     slot_score + at * slots, slot_level + at * slots);
+      ++launches;
+      if (rc) return rc;
+    }
+    return 0;
+  };
+  const std::vector<m3rsm::Config> cfgs((size_t)n_requests, s.cfg);
+  s.each_res.resize(n_requests);
+  s.each_code.assign(n_requests, m3rsm::kPending);
+  s.each_trace.resize(n_requests);
+  const int threads = std::min(s.each_threads ? s.each_threads : m3rsm::each_default_threads(n_requests), n_requests);
+  if (!s.each_pool || s.each_pool->threads() != threads) s.each_pool = std::make_unique<m3rsm::Pool>(threads);
+  const int erc = m3rsm::run_each(cfgs.data(), n_requests, roots, expand, s.each_res.data(), s.each_code.data(),
+                                  s.each_trace.data(), s.each_pool.get());
+  m->t_stage_us = 0;
+  m->t_score_us = MatchJob::now_us() - t0;
+  for (const m3rsm::Result &r : s.each_res) {
+    m->job.scorer_calls += r.scorer_calls;
+    m->job.poses_evaluated += r.scored;
+  }
+  m->job.launches = launches;
+  switch (erc) {
+    case m3rsm::kOk: break;
+    case m3rsm::kErrCallback:
+      for (const m3rsm::Result &r : s.each_res)
+        if (r.callback_rc) return r.callback_rc;
+      set_error("internal: the multi-resolution engine lost a launch's error");
+      return SLAMHIP_ERR_STATE;
+    case m3rsm::kErrSuperSteps:
+      set_error("a multi-resolution match reached its bound on super-steps");
+      return SLAMHIP_ERR_UNSUPPORTED;
+    case m3rsm::kErrInvalid: return invalid_arg("more candidates than one launch takes");
+    default:
+      set_error("internal: the multi-resolution engine failed (an expand launch did not deliver a child)");
+      return SLAMHIP_ERR_STATE;
+  }
+  for (int k = 0; k < n_requests; ++k) {
+    double *d = out_deltas + 3 * (size_t)k;
+    if (s.each_code[k] != m3rsm::kOk) {  // (no candidate left: nothing is accepted, as the lone match has it)
+      d[0] = d[1] = d[2] = 0.0;
+      out_probs[k] = std::numeric_limits<double>::quiet_NaN();
+      continue;
+    }
+    for (int q = 0; q < 3; ++q) d[q] = s.each_res[k].delta[q];
+    out_probs[k] = s.each_res[k].prob;
+  }
+  if (m->has_obs && m->obs.on_matching_end)
+    for (int k = 0; k < n_requests; ++k)
+      if (s.each_code[k] == m3rsm::kOk) m->obs.on_matching_end(m->obs.user, out_deltas + 3 * (size_t)k, s.each_res[k].prob);
+  return SLAMHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int slamhip_matcher_m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req, double *out_deltas,
+                                     double *out_probs) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (!out_deltas || !out_probs) return invalid_arg("null outputs");
+  return m3rsm_match_each(m, n_requests, req, out_deltas, out_probs);
+}
+
+int slamhip_matcher_m3rsm_trace_each(slamhip_matcher *m, int request, int cap, double *rows, int *n) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (request < 0 || request >= (int)m->m3->each_trace.size()) return invalid_arg("no such request in the last match_each");
+  if (cap < 0 || (cap > 0 && !rows)) return invalid_arg("bad trace buffer");
+  const std::vector<m3rsm::Call> &t = m->m3->each_trace[request];
+  if (n) *n = (int)t.size();
+  for (size_t i = 0; i < std::min((size_t)cap, t.size()); ++i) {
+    double *r = rows + 7 * i;
+    r[0] = t[i].rotation;
+    r[1] = t[i].rect.bot;
+    r[2] = t[i].rect.top;
+    r[3] = t[i].rect.left;
+    r[4] = t[i].rect.right;
+    r[5] = t[i].score;
+    r[6] = (double)t[i].level;
+  }
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_m3rsm_each_stats(slamhip_matcher *m, int request, long long *scorer_calls, long long *poses_evaluated,
+                                     long long *super_steps, long long *branching_pops) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (request < 0 || request >= (int)m->m3->each_res.size()) return invalid_arg("no such request in the last match_each");
+  const m3rsm::Result &r = m->m3->each_res[request];
+  if (scorer_calls) *scorer_calls = r.scorer_calls;
+  if (poses_evaluated) *poses_evaluated = r.scored;
+  if (super_steps) *super_steps = r.super_steps;
+  if (branching_pops) *branching_pops = r.branching_pops;
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_m3rsm_copied_back(slamhip_matcher *m, long long *bytes) {
+  if (!m || !m->is_m3rsm || !bytes) return invalid_arg("not a multi-resolution matcher");
+  *bytes = m->m3->copied_back;
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_set_m3rsm_threads(slamhip_matcher *m, int threads) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (threads < 0 || threads > m3rsm::kEachMaxThreads) return invalid_arg("threads: 1 .. 16, or 0 for the default");
+  m->m3->each_threads = threads;
+  return SLAMHIP_OK;
+}
 
 int slamhip_matcher_m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req, int *out_request,
                                      double out_delta[3], double *out_prob) {

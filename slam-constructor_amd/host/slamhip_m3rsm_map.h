@@ -163,6 +163,23 @@ public:
     return best;
   }
 
+  // K INDEPENDENT matches: every request added since the last reset searched on its own, as K matchers' process_scan
+  // would, in lock-step over shared launches (slamhip_matcher_m3rsm_match_each).  One match per request, in the order
+  // added; request k's is_valid() is false where its search found nothing.
+  std::vector<BestMatch> match_each() {
+    const size_t n = _requests.size();
+    std::vector<double> deltas(3 * n, 0.0), probs(n, 0.0);
+    slamhip_or_die(slamhip_matcher_m3rsm_match_each(_matcher, int(n), _requests.data(), deltas.data(), probs.data()),
+                   "m3rsm_match_each");
+    std::vector<BestMatch> out(n);
+    for (size_t k = 0; k < n; ++k) {
+      out[k].request = probs[k] == probs[k] ? int(k) : -1;  // (NaN: no match)
+      out[k].pose_delta = RobotPoseDelta{deltas[3 * k], deltas[3 * k + 1], deltas[3 * k + 2]};
+      out[k].prob_upper_bound = probs[k];
+    }
+    return out;
+  }
+
 private:
   slamhip_ctx *_ctx;
   slamhip_matcher *_matcher;
