@@ -342,11 +342,20 @@ int slamhip_pyramid_build_host(int cell_model, int oie, int width, int height, i
  *                  level, with sp_analysis_area = rect[i].
  * cfg->oope must be a window OOPE (max / mean / overlap), cfg->oie the pyramid's; cfg->area is ignored (the rule of
  * cfg->area, at most 10^4 cells per beam, holds by construction: a rectangle is at most one cell of its level wide).
- * Both sum orders; pose_trig DEVICE or HOST.  The value is BIT-EQUAL to slamhip_score_poses on level_out[i]'s map id
- * with cfg.area = rect[i] and that pose: the same per-beam functions, the same canonical sums.
+ * Both sum orders; pose_trig DEVICE, HOST or RAW_EXACT.  The value is BIT-EQUAL to slamhip_score_poses on level_out[i]'s
+ * map id with cfg.area = rect[i], the same pose_trig and that pose: the same per-beam functions, the same canonical sums.
+ *   SLAMHIP_POSE_TRIG_RAW_EXACT is the reference's DEFAULT provider (RawTrigonometryProvider under
+ *   LaserScan2D::to_cartesian(rot + pose.theta), m3rsm_engine.h:300-314): a beam's direction is glibc's
+ *   cos / sin((rotation[i] + theta) + angle[b]), the sum in the brackets formed first.  It depends on the rotation and the
+ *   beam alone, so ONE launch in front of the scoring one tabulates it for the distinct rotations (bit patterns) of the
+ *   call and the scoring launch reads its candidate's row; still one scoring launch per call.  Needs the angles of the
+ *   current scan's points (slamhip_scan_set_angles / slamhip_scan_filter_upload, or slamhip_scan_select of a slot that
+ *   has some): SLAMHIP_ERR_STATE without them, SLAMHIP_ERR_UNSUPPORTED where slamhip_libm_variant is -1 -- both before
+ *   anything is launched.
  * SLAMHIP_ERR_INVALID: a rotation, rectangle or base pose that is not finite, bot > top or left > right.
- * _device: rotation, rect, score_out, level_out in HBM, asynchronous on the context's stream, pose_trig DEVICE only;
- * a candidate whose rectangle is not finite or is reversed gets NaN and level -1 there. */
+ * _device: rotation, rect, score_out, level_out in HBM, asynchronous on the context's stream, pose_trig DEVICE or
+ * RAW_EXACT (a table row per candidate: the host does not see the rotations); a candidate whose rectangle is not finite
+ * or is reversed gets NaN and level -1 there. */
 int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *pyr, const slamhip_spe_cfg *cfg,
                                   const double base_pose[3], int n, const double *rotation, const double *rect,
                                   double *score_out, int *level_out);
@@ -370,9 +379,11 @@ int slamhip_pyramid_score_matches_device(slamhip_ctx *ctx, slamhip_pyramid *pyr,
  * i is entry i * S + s of the outputs: rect_out (4 doubles), score_out, level_out.  A slot without a node (its path
  * meets a node with fewer children) holds a NaN rectangle, a NaN score and level -1.  Every child carries its parent's
  * rotation.  score_out / level_out of a slot with a node are BIT-EQUAL to slamhip_pyramid_score_matches on
- * (rotation[i], rect_out): both kernels run one scoring function.  Both sum orders; pose_trig DEVICE, or HOST with one
- * sincos per parent.  SLAMHIP_ERR_INVALID: depth outside 1..3, a step that is not positive, values that are not finite.
- * _device: everything in HBM, asynchronous on the context's stream, pose_trig DEVICE only. */
+ * (rotation[i], rect_out): both kernels run one scoring function.  Both sum orders; pose_trig DEVICE, HOST with one
+ * sincos per parent, or RAW_EXACT with one table row per distinct parent rotation (children inherit the rotation; the
+ * table, its one launch and its errors as under BOUNDS).  SLAMHIP_ERR_INVALID: depth outside 1..3, a step that is not
+ * positive, values that are not finite.
+ * _device: everything in HBM, asynchronous on the context's stream, pose_trig DEVICE or RAW_EXACT. */
 int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *pyr, const slamhip_spe_cfg *cfg,
                                    const double base_pose[3], int n, const double *rotation, const double *rect,
                                    double translation_step, int depth, double *rect_out, double *score_out, int *level_out);
@@ -387,7 +398,10 @@ int slamhip_pyramid_expand_matches_device(slamhip_ctx *ctx, slamhip_pyramid *pyr
  * (csrc/map_pyramid.hip k_pyr_score_many, csrc/m3rsm.hip k_m3rsm_expand_many) and runs the scoring function of the
  * single-request kernels, so score_out / level_out are BIT-EQUAL to slamhip_pyramid_score_matches /
  * slamhip_pyramid_expand_matches on that request's pyramid, scan (slamhip_scan_select) and pose alone.  Outputs, slot
- * layout, sum orders and pose_trig (HOST: one sincos per candidate / parent, on its own request's heading) as above.
+ * layout, sum orders and pose_trig (HOST: one sincos per candidate / parent, on its own request's heading; RAW_EXACT:
+ * one table row per distinct (request, rotation), each over its own request's angles and beam count, filled by one
+ * launch in front of the scoring one) as above.  RAW_EXACT needs the angles of every request's slot
+ * (slamhip_scan_store_angles): SLAMHIP_ERR_STATE without them, before anything is launched.
  * All pyramids of one call belong to `ctx` and share the cell model and the OIE (= cfg->oie).
  * SLAMHIP_ERR_INVALID: n_requests < 1, a null pyramid or one that is not this context's, mixed cell models or OIEs, a
  * scan slot that holds no scan, a pose that is not finite, a request index outside the table, values that are not
@@ -488,6 +502,12 @@ int slamhip_scan_upload(slamhip_ctx *ctx, int n, const double *range, const doub
 int slamhip_scan_store(slamhip_ctx *ctx, int slot, int n, const double *range, const double *cos_a,
                        const double *sin_a, const double *weight, const double *factor);
 int slamhip_scan_select(slamhip_ctx *ctx, int slot);
+/* The angles of a STORED scan's points, n = the slot's point count (else SLAMHIP_ERR_INVALID): what
+ * SLAMHIP_POSE_TRIG_RAW_EXACT needs of the requests of slamhip_pyramid_score_requests / _expand_requests and of the
+ * matches over them.  Kept on the host and in HBM with the slot; a later slamhip_scan_store into the slot drops them;
+ * slamhip_scan_select of a slot that has angles makes them the current scan's angles (a slot without angles selects as
+ * before: the current scan then has none). */
+int slamhip_scan_store_angles(slamhip_ctx *ctx, int slot, int n, const double *angle);
 /* The angles of the CURRENT scan's points (ScanPoint2D::angle, sensor_data.h:60-70), n = its point count: what
  * SLAMHIP_POSE_TRIG_RAW_EXACT adds the pose heading to.  Dropped by the next upload / select; slamhip_scan_filter_upload
  * sets them itself. */
@@ -600,15 +620,21 @@ int slamhip_matcher_create_bf(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, cons
  * (rotation, rectangle).  A child the memo lacks starts a SUPER-STEP: the popped match and the next width - 1 unexpanded
  * entries of the queue are expanded to `depth` generations by one slamhip_pyramid_expand_matches launch.  Scores are
  * pure functions of their node, so the committed calls are the reference's for every width and depth.
- *   cfg: a window OOPE (max / mean / overlap), the pyramid's OIE, pose_trig DEVICE or HOST.  With
- *   SLAMHIP_SUM_SEQUENTIAL and HOST trig the match is the compiled reference's bit for bit -- delta, probability and
- *   every call -- for scans under the cached trig provider; the default mode's scores differ by the sum order (~1e-13).
+ *   cfg: a window OOPE (max / mean / overlap), the pyramid's OIE, pose_trig DEVICE, HOST or RAW_EXACT.  With
+ *   SLAMHIP_SUM_SEQUENTIAL the match is the compiled reference's bit for bit -- delta, probability and every call --
+ *   under HOST trig for scans under the cached trig provider, and under RAW_EXACT for scans under the reference's
+ *   default provider (RawTrigonometryProvider, use_trig_cache = false; the scan's cos_a / sin_a are then not read, its
+ *   angles are: slamhip_scan_set_angles, slamhip_scan_filter_upload or a raw scan).  The default mode's scores differ by
+ *   the sum order (~1e-13).  RAW_EXACT adds one small tabulation launch in front of every root and expand launch (the
+ *   exact directions of the launch's distinct rotations) and nothing else; the many-to-many and each forms below take
+ *   it too, given slamhip_scan_store_angles for every request's slot.
  *   process_scan / process_raw_scan: map_id must be the pyramid's fine map; delta = (centre x, centre y, rotation) of
  *   the winning point, prob = its bound; on_matching_end is the only observer event (the reference's matcher emits no
  *   on_scan_test).  slamhip_matcher_stats: scorer_calls = the calls the reference would have made, poses_evaluated =
  *   candidates scored on the GPU, launches = super-steps + the root launch.
  * SLAMHIP_ERR_INVALID: a 1-cell or GMapping OOPE, an OIE that is not the pyramid's, a pyramid of another context, steps
- * that are not positive; SLAMHIP_ERR_STATE from a match: the pyramid is stale (slamhip_pyramid_rebuild);
+ * that are not positive; SLAMHIP_ERR_STATE from a match: the pyramid is stale (slamhip_pyramid_rebuild), or RAW_EXACT
+ * without the scan's angles (nothing is launched, the stats of the match before stay);
  * SLAMHIP_ERR_UNSUPPORTED from a match: the bound on super-steps (2^20) was reached.  The pyramid must outlive the matcher. */
 int slamhip_matcher_create_m3rsm(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, slamhip_pyramid *pyramid,
                                  double max_x_error, double max_y_error, double max_th_error, double angle_step,

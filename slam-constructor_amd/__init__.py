@@ -55,7 +55,7 @@ slamhip_gmapping_particle_map_export slamhip_gmapping_import_maps slamhip_gmappi
 slamhip_shard_unique_id slamhip_shard_init slamhip_shard_destroy slamhip_shard_info slamhip_shard_allgather
 slamhip_shard_stats slamhip_gmapping_set_shard_chain slamhip_gmapping_match_begin slamhip_gmapping_carry_record
 slamhip_gmapping_carry_fix slamhip_gmapping_carry_commit slamhip_gmapping_match_finish
-slamhip_gmapping_step_sharded slamhip_matcher_process_scan_batch slamhip_matcher_batch_stats slamhip_scan_store slamhip_scan_select
+slamhip_gmapping_step_sharded slamhip_matcher_process_scan_batch slamhip_matcher_batch_stats slamhip_scan_store slamhip_scan_select slamhip_scan_store_angles
 slamhip_shard_attach slamhip_shard_exchange slamhip_shard_p2p_stats slamhip_shard_set_timeout slamhip_gmapping_match_abort
 slamhip_gmapping_migration_stats slamhip_map_append_scan_q slamhip_omqe_quality slamhip_scan_filter_upload
 slamhip_scan_set_angles slamhip_libm_variant slamhip_libm_eval slamhip_map_append_scan_raw
@@ -795,6 +795,13 @@ class Context:
         rng, cos_a, sin_a, weight = _f64(rng), _f64(cos_a), _f64(sin_a), _f64(weight)
         fac = _f64(factor) if factor is not None else np.ones(rng.size)
         _check(self.L.slamhip_scan_store(self.h, int(slot), rng.size, _d(rng), _d(cos_a), _d(sin_a), _d(weight), _d(fac)))
+
+    def scan_store_angles(self, slot, angle):
+        """the angles of a stored scan's points (slamhip_scan_store_angles): what POSE_TRIG_RAW_EXACT needs of the requests
+        of the multi-request BF_M3RSM calls; scan_select of the slot makes them the current scan's angles"""
+        angle = _f64(angle)
+        self.L.slamhip_scan_store_angles.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        _check(self.L.slamhip_scan_store_angles(self.h, int(slot), angle.size, _d(angle)))
 
     def scan_select(self, slot):
         rc = self.L.slamhip_scan_select(self.h, int(slot))

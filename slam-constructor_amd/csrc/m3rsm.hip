@@ -46,7 +46,7 @@ struct ExpandManyArgs {
   int slots;
 };
 
-template <int MODEL>
+template <int MODEL, bool RAW>
 __global__ __launch_bounds__(kPyrThreads) void k_m3rsm_expand(ExpandArgs a) {
   __shared__ double s_trig[2];
   __shared__ double s_part[4];
@@ -71,15 +71,15 @@ __global__ __launch_bounds__(kPyrThreads) void k_m3rsm_expand(ExpandArgs a) {
     a.rect_out[4 * g + 2] = node.left;
     a.rect_out[4 * g + 3] = node.right;
   }
-  pyr_score_one<MODEL>(a.m, a.m, parent, g, a.m.terms, g * (size_t)a.m.scan.n, node.bot, node.top, node.left, node.right, s_trig,
-                       s_part);
+  pyr_score_one<MODEL, RAW>(a.m, a.m, parent, g, a.m.terms, g * (size_t)a.m.scan.n, node.bot, node.top, node.left, node.right,
+                            s_trig, s_part);
 }
 
 // One workgroup per slot, the same walk and the same outputs as above (the two kernels spell the slot's prologue out
 // each: handed to a shared function through a pointer to the node it cost k_m3rsm_expand 13 VGPRs).  The request's entry
 // of the table is uniform over the workgroup: it is read once, after the slot is known to hold a node, and everything
 // per beam comes from that copy.
-template <int MODEL>
+template <int MODEL, bool RAW>
 __global__ __launch_bounds__(kPyrThreads) void k_m3rsm_expand_many(ExpandManyArgs a) {
   __shared__ double s_trig[2];
   __shared__ double s_part[4];
@@ -107,7 +107,8 @@ __global__ __launch_bounds__(kPyrThreads) void k_m3rsm_expand_many(ExpandManyArg
   }
   const PyrSource q = a.q.table[a.q.request[parent]];
   const size_t terms_at = a.q.m.terms ? (size_t)a.q.terms_off[parent] + (size_t)slot * (size_t)q.scan.n : 0;
-  pyr_score_one<MODEL>(q, a.q.m, parent, g, a.q.m.terms, terms_at, node.bot, node.top, node.left, node.right, s_trig, s_part);
+  pyr_score_one<MODEL, RAW>(q, a.q.m, parent, g, a.q.m.terms, terms_at, node.bot, node.top, node.left, node.right, s_trig,
+                            s_part);
 }
 
 int check_expand(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base_pose[3], int n,
@@ -126,10 +127,11 @@ int check_expand(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cf
   return SLAMHIP_OK;
 }
 
-// queues the expansion of n parents whose arrays are in HBM (pose_sc may be null)
+// queues the expansion of n parents whose arrays are in HBM (pose_sc may be null; raw: the table of beam directions
+// queued in front of this launch -- a row per parent, its children inherit the rotation --, or null)
 int queue_expand(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base[3], int n, const double *d_rotation,
-                 const double *d_rect, const double *d_pose_sc, double step, int depth, double *d_rect_out, double *d_scores,
-                 int *d_levels) {
+                 const double *d_rect, const double *d_pose_sc, const RawTrig *raw, double step, int depth, double *d_rect_out,
+                 double *d_scores, int *d_levels) {
   slamhip_ctx *ctx = p->ctx;
   const int slots = m3rsm::slots_of(depth);
   const size_t n_out = (size_t)n * slots;
@@ -143,6 +145,7 @@ int queue_expand(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double ba
   a.m.scores = d_scores;
   a.m.level_out = d_levels;
   a.m.n = n;
+  if (raw) a.m.raw = *raw;
   a.rect_out = d_rect_out;
   a.step = step;
   a.slots = slots;
@@ -150,7 +153,9 @@ int queue_expand(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double ba
   rc = prof.open(ctx, ctx->stream, 0);
   if (rc) return rc;
   typedef void (*Kernel)(ExpandArgs);
-  const Kernel kernel = pick_cell_model(p->cell_model, [](auto m) -> Kernel { return k_m3rsm_expand<decltype(m)::value>; });
+  const Kernel kernel = pick_cell_model(p->cell_model, [raw](auto m) -> Kernel {
+    return raw ? k_m3rsm_expand<decltype(m)::value, true> : k_m3rsm_expand<decltype(m)::value, false>;
+  });
   SLAMHIP_CHECK(launch_kernel(kernel, dim3((unsigned)n_out), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
   if (a.m.terms) {
     rc = pyr_launch_sum_sequential(a.m, n_out, ctx->stream);
@@ -178,11 +183,23 @@ int slamhip_pyramid_expand_matches_device(slamhip_ctx *ctx, slamhip_pyramid *p, 
   if (rc) return rc;
   if (n == 0) return SLAMHIP_OK;
   if (!d_rotation || !d_rect || !d_rect_out || !d_score_out || !d_level_out) return pyr_invalid("null device buffers");
-  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE)
-    return pyr_invalid("device-resident parents use device sincos (pose_trig = DEVICE): the host-trig mode takes host arrays");
+  const bool raw = cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && !raw)
+    return pyr_invalid("device-resident parents use device sincos (pose_trig = DEVICE) or RAW_EXACT: the host-trig mode takes "
+                       "host arrays");
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  return queue_expand(p, cfg, base_pose, n, d_rotation, d_rect, nullptr, translation_step, depth, d_rect_out, d_score_out,
-                      d_level_out);
+  RawTrig rt{};
+  if (raw) {
+    // (the host does not see the rotations: every parent is a row of its own, row i for parent i)
+    bool fma = false;
+    const double *d_angle = nullptr;
+    rc = pyr_raw_prepare(ctx, &fma, &d_angle);
+    if (rc) return rc;
+    rc = pyr_raw_queue_table(p, fma, d_rotation, n, base_pose[2], d_angle, ctx->scan_n, &rt);
+    if (rc) return rc;
+  }
+  return queue_expand(p, cfg, base_pose, n, d_rotation, d_rect, nullptr, raw ? &rt : nullptr, translation_step, depth, d_rect_out,
+                      d_score_out, d_level_out);
 }
 
 int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base_pose[3],
@@ -192,8 +209,9 @@ int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const s
   if (rc) return rc;
   if (n == 0) return SLAMHIP_OK;
   if (!rotation || !rect || !rect_out || !score_out || !level_out) return pyr_invalid("null parent or output arrays");
-  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
-    return pyr_invalid("pose_trig: DEVICE or HOST");
+  const bool raw = cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST && !raw)
+    return pyr_invalid("pose_trig: DEVICE, HOST or RAW_EXACT");
   for (int i = 0; i < n; ++i) {
     const double *r = rect + 4 * (size_t)i;
     // (a reversed rectangle is let through: it has no children, every slot of it comes back empty)
@@ -202,6 +220,12 @@ int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const s
       return pyr_invalid("a parent's rotation or rectangle is not finite");
   }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  bool fma = false;
+  const double *d_angle = nullptr;
+  if (raw) {  // (before anything is queued)
+    rc = pyr_raw_prepare(ctx, &fma, &d_angle);
+    if (rc) return rc;
+  }
   const int slots = m3rsm::slots_of(depth);
   const size_t n_out = (size_t)n * slots;
   if (n > p->x_parent_cap || n_out > p->x_slot_cap) {
@@ -231,11 +255,24 @@ int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const s
   if (host_trig)  // (one sincos call per parent: its children share the heading)
     for (int i = 0; i < n; ++i)
       ::sincos(rotation[i] + base_pose[2], &stage[5 * (size_t)n + 2 * i], &stage[5 * (size_t)n + 2 * i + 1]);
-  SLAMHIP_CHECK(hipMemcpyAsync(p->d_x_in, stage, sizeof(double) * (host_trig ? 7 : 5) * n, hipMemcpyHostToDevice, ctx->stream));
+  // RAW_EXACT: the (sin, cos) part holds the rows' rotations (at most n doubles) and, behind them, a row per parent
+  std::vector<double> rot_rows;
+  if (raw) {
+    pyr_raw_rows(n, rotation, reinterpret_cast<int *>(stage + 6 * (size_t)n), &rot_rows);
+    std::memcpy(stage + 5 * (size_t)n, rot_rows.data(), sizeof(double) * rot_rows.size());
+  }
+  SLAMHIP_CHECK(hipMemcpyAsync(p->d_x_in, stage, sizeof(double) * (host_trig || raw ? 7 : 5) * n, hipMemcpyHostToDevice,
+                               ctx->stream));
+  RawTrig rt{};
+  if (raw) {
+    rc = pyr_raw_queue_table(p, fma, p->d_x_in + 5 * (size_t)n, (int)rot_rows.size(), base_pose[2], d_angle, ctx->scan_n, &rt);
+    if (rc) return rc;
+    rt.row = reinterpret_cast<const int *>(p->d_x_in + 6 * (size_t)n);
+  }
   double *d_rect_out = p->d_x_out, *d_scores = p->d_x_out + 4 * n_out;
   int *d_levels = reinterpret_cast<int *>(p->d_x_out + 5 * n_out);
   rc = queue_expand(p, cfg, base_pose, n, p->d_x_in, p->d_x_in + n, host_trig ? p->d_x_in + 5 * (size_t)n : nullptr,
-                    translation_step, depth, d_rect_out, d_scores, d_levels);
+                    raw ? &rt : nullptr, translation_step, depth, d_rect_out, d_scores, d_levels);
   if (rc) return rc;
   SLAMHIP_CHECK(hipMemcpyAsync(h_out, p->d_x_out, (sizeof(double) * 5 + sizeof(int)) * n_out, hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -275,8 +312,10 @@ int slamhip_pyramid_expand_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg
   rc = prof.open(ctx, ctx->stream, 0);
   if (rc) return rc;
   typedef void (*Kernel)(ExpandManyArgs);
-  const Kernel kernel =
-      pick_cell_model(table[0].pyramid->cell_model, [](auto m) -> Kernel { return k_m3rsm_expand_many<decltype(m)::value>; });
+  const bool raw = a.q.m.raw.cos != nullptr;
+  const Kernel kernel = pick_cell_model(table[0].pyramid->cell_model, [raw](auto m) -> Kernel {
+    return raw ? k_m3rsm_expand_many<decltype(m)::value, true> : k_m3rsm_expand_many<decltype(m)::value, false>;
+  });
   SLAMHIP_CHECK(launch_kernel(kernel, dim3((unsigned)n_out), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
   if (a.q.m.terms) {
     rc = pyr_launch_sum_sequential_many(a.q, n_out, slots, ctx->stream);

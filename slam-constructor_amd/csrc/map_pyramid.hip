@@ -18,12 +18,16 @@
 // bits slamhip_score_poses gives for that pose on that level's map with cfg.area = the rectangle.  k_pyr_score_many scores
 // candidates of several requests in one launch: level table, scan and base pose per candidate from a request table in HBM
 // (slamhip_pyramid_score_requests; the staging both multi-request launches share is in here too).
+// SLAMHIP_POSE_TRIG_RAW_EXACT (the reference's default trig provider, bit for bit): k_pyr_raw_table(_many) tabulate
+// glibc's cos / sin((rotation + heading) + angle) for the distinct rotations of a call in one launch in front of the
+// scoring one, whose RAW instantiation reads its candidate's row (RawTrig, map_pyramid_score.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "kernel_pick.h"
+#include "libm_exact.h"
 #include "map_pyramid_device.h"
 #include "map_pyramid_score.h"
 #include "score_device.h"
@@ -198,26 +202,77 @@ int check_fresh(const slamhip_pyramid *p) {
 }
 
 // ---- score ---------------------------------------------------------------------------------------
-template <int MODEL>
+template <int MODEL, bool RAW>
 __global__ __launch_bounds__(kPyrThreads) void k_pyr_score(MatchArgs a) {
   __shared__ double s_trig[2];
   __shared__ double s_part[4];
   const size_t i = blockIdx.x;
-  pyr_score_one<MODEL>(a, a, i, i, a.terms, i * (size_t)a.scan.n, a.rect[4 * i], a.rect[4 * i + 1], a.rect[4 * i + 2],
-                       a.rect[4 * i + 3], s_trig, s_part);
+  pyr_score_one<MODEL, RAW>(a, a, i, i, a.terms, i * (size_t)a.scan.n, a.rect[4 * i], a.rect[4 * i + 1], a.rect[4 * i + 2],
+                            a.rect[4 * i + 3], s_trig, s_part);
 }
 
 // the same for candidates of several requests: the workgroup's scan, levels and base pose are its request's entry of the
 // table (one read per workgroup, uniform: it goes through the scalar cache), the rest is k_pyr_score
-template <int MODEL>
+template <int MODEL, bool RAW>
 __global__ __launch_bounds__(kPyrThreads) void k_pyr_score_many(ManyArgs a) {
   __shared__ double s_trig[2];
   __shared__ double s_part[4];
   const size_t i = blockIdx.x;
   const PyrSource q = a.table[a.request[i]];
-  pyr_score_one<MODEL>(q, a.m, i, i, a.m.terms, a.m.terms ? (size_t)a.terms_off[i] : 0, a.m.rect[4 * i], a.m.rect[4 * i + 1],
-                       a.m.rect[4 * i + 2], a.m.rect[4 * i + 3], s_trig, s_part);
+  pyr_score_one<MODEL, RAW>(q, a.m, i, i, a.m.terms, a.m.terms ? (size_t)a.terms_off[i] : 0, a.m.rect[4 * i],
+                            a.m.rect[4 * i + 1], a.m.rect[4 * i + 2], a.m.rect[4 * i + 3], s_trig, s_part);
 }
+
+// ---- SLAMHIP_POSE_TRIG_RAW_EXACT: the table of beam directions (RawTrig, map_pyramid_score.h) ------------------------
+// Row r of a launch: glibc's cos / sin(t_r + angle[b]) for the row's scan, t_r = rotation + base heading formed as ONE
+// double first (fscan->to_cartesian(rot + pose.theta), then RawTrigonometryProvider's _base_angle + angle_rad).  One
+// thread per (row, beam); rows beyond the grid's y extent are walked.  Compute bound and tiny: a few dozen rows of a
+// scan's beams per match.  Writes stay inside [r * stride, r * stride + n) with n <= stride, r < n_rows.
+template <bool FMA>
+__device__ __forceinline__ void raw_row_fill(double t, const double *__restrict__ angle, int n, double *__restrict__ out_cos,
+                                             double *__restrict__ out_sin) {
+  for (int b = (int)(blockIdx.x * 256 + threadIdx.x); b < n; b += (int)(gridDim.x * 256)) {
+    const double x = t + angle[b];
+    out_cos[b] = libm_exact::cos_<FMA>(x);
+    out_sin[b] = libm_exact::sin_<FMA>(x);
+  }
+}
+
+template <bool FMA>
+__global__ __launch_bounds__(256) void k_pyr_raw_table(const double *__restrict__ rot_rows, int n_rows, double base_theta,
+                                                      const double *__restrict__ angle, int n, size_t stride,
+                                                      double *__restrict__ out_cos, double *__restrict__ out_sin) {
+  for (int r = (int)blockIdx.y; r < n_rows; r += (int)gridDim.y)
+    raw_row_fill<FMA>(rot_rows[r] + base_theta, angle, n, out_cos + (size_t)r * stride, out_sin + (size_t)r * stride);
+}
+
+// ... for rows of several requests: row r belongs to request row_request[r], whose angles, beam count and heading come
+// from the request table (beam counts differ: a row fills its own request's n of the common stride)
+template <bool FMA>
+__global__ __launch_bounds__(256) void k_pyr_raw_table_many(const double *__restrict__ rot_rows, const int *__restrict__ row_request,
+                                                           int n_rows, const PyrSource *__restrict__ table, size_t stride,
+                                                           double *__restrict__ out_cos, double *__restrict__ out_sin) {
+  for (int r = (int)blockIdx.y; r < n_rows; r += (int)gridDim.y) {
+    const PyrSource &q = table[row_request[r]];
+    raw_row_fill<FMA>(rot_rows[r] + q.base[2], q.angle, q.scan.n, out_cos + (size_t)r * stride, out_sin + (size_t)r * stride);
+  }
+}
+
+// grows a table of beam directions to `need` doubles: synchronise, free, allocate
+int raw_table_room(slamhip_ctx *ctx, double **d_raw, size_t *cap, size_t need) {
+  if (need <= *cap) return SLAMHIP_OK;
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (*d_raw) (void)hipFree(*d_raw);
+  *d_raw = nullptr;
+  *cap = 0;
+  size_t c = 1 << 14;
+  while (c < need) c *= 2;
+  SLAMHIP_CHECK(hipMalloc(d_raw, sizeof(double) * c));
+  *cap = c;
+  return SLAMHIP_OK;
+}
+
+dim3 raw_table_grid(int max_beams, int n_rows) { return dim3((max_beams + 255) / 256, std::min(n_rows, kMaxGridY)); }
 
 __device__ __forceinline__ double sum_sequential_row(const double *row, int n, double tot_w) {
   double acc = 0.0;
@@ -251,9 +306,10 @@ int check_score_cfg(const slamhip_pyramid *p, const slamhip_spe_cfg *cfg) {
   return SLAMHIP_OK;
 }
 
-// queues the scoring of n candidates whose arrays are in HBM (pose_sc may be null)
+// queues the scoring of n candidates whose arrays are in HBM (pose_sc may be null; raw: the table of beam directions
+// queued in front of this launch, or null)
 int queue_score(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base[3], int n, const double *d_rotation,
-                const double *d_rect, const double *d_pose_sc, double *d_scores, int *d_levels) {
+                const double *d_rect, const double *d_pose_sc, const RawTrig *raw, double *d_scores, int *d_levels) {
   slamhip_ctx *ctx = p->ctx;
   MatchArgs a;
   int rc = pyr_fill_args(p, cfg, base, (size_t)n, &a);
@@ -264,11 +320,14 @@ int queue_score(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double bas
   a.scores = d_scores;
   a.level_out = d_levels;
   a.n = n;
+  if (raw) a.raw = *raw;
   ProfilePairGuard prof;
   rc = prof.open(ctx, ctx->stream, 0);
   if (rc) return rc;
   typedef void (*Kernel)(MatchArgs);
-  const Kernel kernel = pick_cell_model(p->cell_model, [](auto m) -> Kernel { return k_pyr_score<decltype(m)::value>; });
+  const Kernel kernel = pick_cell_model(p->cell_model, [raw](auto m) -> Kernel {
+    return raw ? k_pyr_score<decltype(m)::value, true> : k_pyr_score<decltype(m)::value, false>;
+  });
   SLAMHIP_CHECK(launch_kernel(kernel, dim3(n), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
   if (a.terms) {
     rc = pyr_launch_sum_sequential(a, (size_t)n, ctx->stream);
@@ -287,6 +346,55 @@ int queue_score(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double bas
 
 int pyr_check_fresh(const slamhip_pyramid *p) { return check_fresh(p); }
 int pyr_check_score_cfg(const slamhip_pyramid *p, const slamhip_spe_cfg *cfg) { return check_score_cfg(p, cfg); }
+
+static int raw_libm_build(bool *fma) {
+  const int variant = libm_variant();
+  if (variant < 0) {
+    set_error("this host's libm matches neither build of glibc's sin / cos restated in csrc/libm_exact.h: "
+              "SLAMHIP_POSE_TRIG_RAW_EXACT is not available here");
+    return SLAMHIP_ERR_UNSUPPORTED;
+  }
+  *fma = variant == 1;
+  return SLAMHIP_OK;
+}
+
+int pyr_raw_prepare(slamhip_ctx *ctx, bool *fma, const double **d_angle) {
+  const int rc = raw_libm_build(fma);
+  if (rc) return rc;
+  if (ctx->scan_n <= 0) return pyr_state("no scan uploaded");
+  return scan_exact_angles(ctx, d_angle);
+}
+
+void pyr_raw_rows(int n, const double *rotation, int *row_out, std::vector<double> *rot_rows) {
+  rot_rows->clear();
+  for (int i = 0; i < n; ++i) {
+    // (a layer of matches holds few rotations, and neighbours mostly share one: the row before is tried first)
+    int r = i ? row_out[i - 1] : 0;
+    if (!i || std::memcmp(&(*rot_rows)[r], &rotation[i], sizeof(double)) != 0) {
+      for (r = 0; r < (int)rot_rows->size(); ++r)
+        if (std::memcmp(&(*rot_rows)[r], &rotation[i], sizeof(double)) == 0) break;
+      if (r == (int)rot_rows->size()) rot_rows->push_back(rotation[i]);
+    }
+    row_out[i] = r;
+  }
+}
+
+int pyr_raw_queue_table(slamhip_pyramid *p, bool fma, const double *d_rot_rows, int n_rows, double base_theta,
+                        const double *d_angle, int n_beams, RawTrig *out) {
+  slamhip_ctx *ctx = p->ctx;
+  const size_t stride = (size_t)((n_beams + 7) & ~7);
+  const int rc = raw_table_room(ctx, &p->d_raw, &p->raw_cap, 2 * stride * (size_t)n_rows);
+  if (rc) return rc;
+  double *d_cos = p->d_raw, *d_sin = p->d_raw + stride * (size_t)n_rows;
+  const auto kernel = fma ? k_pyr_raw_table<true> : k_pyr_raw_table<false>;
+  SLAMHIP_CHECK(launch_kernel(kernel, raw_table_grid(n_beams, n_rows), dim3(256), 0, ctx->stream, nullptr, nullptr, d_rot_rows,
+                              n_rows, base_theta, d_angle, n_beams, stride, d_cos, d_sin));
+  out->cos = d_cos;
+  out->sin = d_sin;
+  out->row = nullptr;
+  out->stride = stride;
+  return SLAMHIP_OK;
+}
 
 // what every bound-scoring launch shares: the level table, the context's current scan, the base pose, the OOPE / OIE and,
 // for the beam-order sum, room for n_out x scan.n terms
@@ -343,6 +451,7 @@ void pyr_many_release(slamhip_ctx *ctx) {
   if (st->h) (void)hipHostFree(st->h);
   if (st->d) (void)hipFree(st->d);
   if (st->d_terms) (void)hipFree(st->d_terms);
+  if (st->d_raw) (void)hipFree(st->d_raw);
   delete st;
   ctx->pyr_many = nullptr;
 }
@@ -365,8 +474,14 @@ int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_request
       first = p;
       rc = check_score_cfg(p, cfg);
       if (rc) return rc;
-      if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
-        return pyr_invalid("pose_trig: DEVICE or HOST");
+      if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST &&
+          cfg->pose_trig != SLAMHIP_POSE_TRIG_RAW_EXACT)
+        return pyr_invalid("pose_trig: DEVICE, HOST or RAW_EXACT");
+      if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT) {
+        bool fma = false;
+        rc = raw_libm_build(&fma);
+        if (rc) return rc;
+      }
     }
     if (p->cell_model != first->cell_model || p->oie != first->oie)
       return pyr_invalid("the pyramids of one call share the cell model and the OIE");
@@ -376,6 +491,9 @@ int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_request
     for (int k = 0; k < 3; ++k)
       if (!std::isfinite(req[r].init_pose[k])) return pyr_invalid("a request's pose is not finite");
     const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[slot];
+    if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT && ((int)sl.angle.size() != sl.n || !sl.d_angle))
+      return pyr_state("SLAMHIP_POSE_TRIG_RAW_EXACT needs the angles of every request's stored scan: "
+                       "slamhip_scan_store_angles after slamhip_scan_store");
     PyrSource q;
     std::memset(&q, 0, sizeof(q));
     q.levels = p->d_views;
@@ -389,6 +507,7 @@ int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_request
     q.scan.n = sl.n;
     q.scan.tot_w = sl.tot_w;
     for (int k = 0; k < 3; ++k) q.base[k] = req[r].init_pose[k];
+    if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT) q.angle = sl.d_angle;
     out->push_back(q);
   }
   return SLAMHIP_OK;
@@ -404,6 +523,12 @@ size_t many_out_bytes(size_t n_out) { return sizeof(double) * 5 * n_out + up8(si
 
 int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int n, const int *request,
                    const double *rotation, const double *rect, int slots, ManyArgs *out, double **d_rect_out) {
+  const bool raw = cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
+  bool fma = false;
+  if (raw) {
+    const int rc = raw_libm_build(&fma);
+    if (rc) return rc;
+  }
   const size_t n_src = src.size(), n_out = (size_t)n * slots;
   if (!ctx->pyr_many) ctx->pyr_many = new PyrManyStage;
   PyrManyStage *st = static_cast<PyrManyStage *>(ctx->pyr_many);
@@ -442,10 +567,30 @@ int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vect
   at += sizeof(double) * 4 * n;
   const size_t sc_at = at;
   double *h_sc = reinterpret_cast<double *>(st->h + at);
-  if (host_trig)  // (one sincos call per candidate / parent, on its own request's heading)
+  // RAW_EXACT: the part holds the rows instead -- the distinct (request, rotation bits) pairs in order of first
+  // appearance: rotation per row (at most n doubles) | request per row | row per candidate (n ints each)
+  int n_rows = 0, max_beams = 0;
+  if (host_trig) {  // (one sincos call per candidate / parent, on its own request's heading)
     for (int i = 0; i < n; ++i) ::sincos(rotation[i] + src[request[i]].base[2], &h_sc[2 * i], &h_sc[2 * i + 1]);
-  else
+  } else if (raw) {
+    int *h_row_req = reinterpret_cast<int *>(h_sc + n), *h_row = h_row_req + n;
+    for (int i = 0; i < n; ++i) {
+      int r = i ? h_row[i - 1] : 0;  // (neighbours mostly share request and rotation: the row before is tried first)
+      if (!i || h_row_req[r] != request[i] || std::memcmp(&h_sc[r], &rotation[i], sizeof(double)) != 0) {
+        for (r = 0; r < n_rows; ++r)
+          if (h_row_req[r] == request[i] && std::memcmp(&h_sc[r], &rotation[i], sizeof(double)) == 0) break;
+        if (r == n_rows) {
+          h_sc[r] = rotation[i];
+          h_row_req[r] = request[i];
+          ++n_rows;
+        }
+      }
+      h_row[i] = r;
+    }
+    for (const PyrSource &q : src) max_beams = std::max(max_beams, q.scan.n);
+  } else {
     std::memset(h_sc, 0, sizeof(double) * 2 * n);
+  }
   at += sizeof(double) * 2 * n;
   const size_t req_at = at;
   std::memcpy(st->h + at, request, sizeof(int) * n);
@@ -457,10 +602,27 @@ int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vect
     SLAMHIP_CHECK(hipMalloc(&st->d_terms, sizeof(double) * total_terms));
     st->terms_cap = total_terms;
   }
+  const size_t raw_stride = (size_t)((max_beams + 7) & ~7);
+  if (raw) {
+    const int rc = raw_table_room(ctx, &st->d_raw, &st->raw_cap, 2 * raw_stride * (size_t)n_rows);
+    if (rc) return rc;
+  }
   SLAMHIP_CHECK(hipMemcpyAsync(st->d, st->h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   ManyArgs a;
   std::memset(&a, 0, sizeof(a));
   a.table = reinterpret_cast<const PyrSource *>(st->d + table_at);
+  if (raw) {
+    const double *d_rot_rows = reinterpret_cast<const double *>(st->d + sc_at);
+    const int *d_row_req = reinterpret_cast<const int *>(d_rot_rows + n);
+    double *d_cos = st->d_raw, *d_sin = st->d_raw + raw_stride * (size_t)n_rows;
+    const auto kernel = fma ? k_pyr_raw_table_many<true> : k_pyr_raw_table_many<false>;
+    SLAMHIP_CHECK(launch_kernel(kernel, raw_table_grid(max_beams, n_rows), dim3(256), 0, ctx->stream, nullptr, nullptr, d_rot_rows,
+                                d_row_req, n_rows, a.table, raw_stride, d_cos, d_sin));
+    a.m.raw.cos = d_cos;
+    a.m.raw.sin = d_sin;
+    a.m.raw.row = d_row_req + n;
+    a.m.raw.stride = raw_stride;
+  }
   a.terms_off = reinterpret_cast<const long long *>(st->d + off_at);
   a.request = reinterpret_cast<const int *>(st->d + req_at);
   a.m.rotation = reinterpret_cast<const double *>(st->d + rot_at);
@@ -501,10 +663,11 @@ void pyr_free_staging(slamhip_pyramid *p) {
   if (p->d_x_in) (void)hipFree(p->d_x_in);
   if (p->d_x_out) (void)hipFree(p->d_x_out);
   if (p->h_x) (void)hipHostFree(p->h_x);
-  p->d_in = p->d_scores = p->d_terms = p->d_x_in = p->d_x_out = p->h_x = nullptr;
+  if (p->d_raw) (void)hipFree(p->d_raw);
+  p->d_in = p->d_scores = p->d_terms = p->d_x_in = p->d_x_out = p->h_x = p->d_raw = nullptr;
   p->d_levels = nullptr;
   p->in_cap = p->x_parent_cap = 0;
-  p->terms_cap = p->x_slot_cap = 0;
+  p->terms_cap = p->x_slot_cap = p->raw_cap = 0;
 }
 
 void pyramids_release(slamhip_ctx *ctx) {
@@ -602,12 +765,24 @@ int slamhip_pyramid_score_matches_device(slamhip_ctx *ctx, slamhip_pyramid *p, c
   if (n < 0 || !base_pose) return pyr_invalid("bad candidate batch");
   if (n == 0) return SLAMHIP_OK;
   if (!d_rotation || !d_rect || !d_score_out || !d_level_out) return pyr_invalid("null device buffers");
-  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE)
-    return pyr_invalid("device-resident candidates use device sincos (pose_trig = DEVICE): the host-trig mode takes host arrays");
+  const bool raw = cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && !raw)
+    return pyr_invalid("device-resident candidates use device sincos (pose_trig = DEVICE) or RAW_EXACT: the host-trig mode "
+                       "takes host arrays");
   for (int k = 0; k < 3; ++k)
     if (!std::isfinite(base_pose[k])) return pyr_invalid("the base pose is not finite");
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  return queue_score(p, cfg, base_pose, n, d_rotation, d_rect, nullptr, d_score_out, d_level_out);
+  RawTrig rt{};
+  if (raw) {
+    // (the host does not see the rotations: every candidate is a row of its own, row i for candidate i)
+    bool fma = false;
+    const double *d_angle = nullptr;
+    rc = pyr_raw_prepare(ctx, &fma, &d_angle);
+    if (rc) return rc;
+    rc = pyr_raw_queue_table(p, fma, d_rotation, n, base_pose[2], d_angle, ctx->scan_n, &rt);
+    if (rc) return rc;
+  }
+  return queue_score(p, cfg, base_pose, n, d_rotation, d_rect, nullptr, raw ? &rt : nullptr, d_score_out, d_level_out);
 }
 
 int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double base_pose[3],
@@ -620,8 +795,9 @@ int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const sl
   if (n < 0 || !base_pose) return pyr_invalid("bad candidate batch");
   if (n == 0) return SLAMHIP_OK;
   if (!rotation || !rect || !score_out || !level_out) return pyr_invalid("null candidate arrays");
-  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
-    return pyr_invalid("pose_trig: DEVICE or HOST");
+  const bool raw = cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST && !raw)
+    return pyr_invalid("pose_trig: DEVICE, HOST or RAW_EXACT");
   for (int k = 0; k < 3; ++k)
     if (!std::isfinite(base_pose[k])) return pyr_invalid("the base pose is not finite");
   for (int i = 0; i < n; ++i) {
@@ -633,6 +809,12 @@ int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const sl
     // cell of its level wide, so a beam's window is at most 3 x 3 cells)
   }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  bool fma = false;
+  const double *d_angle = nullptr;
+  if (raw) {  // (before anything is queued)
+    rc = pyr_raw_prepare(ctx, &fma, &d_angle);
+    if (rc) return rc;
+  }
   if (n > p->in_cap) {
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (p->d_in) (void)hipFree(p->d_in);
@@ -654,9 +836,22 @@ int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const sl
   std::memcpy(stage.data() + n, rect, sizeof(double) * 4 * n);
   if (host_trig)  // (one sincos call per pose, as slamhip_score_poses' host mode makes it)
     for (int i = 0; i < n; ++i) ::sincos(rotation[i] + base_pose[2], &stage[5 * (size_t)n + 2 * i], &stage[5 * (size_t)n + 2 * i + 1]);
-  SLAMHIP_CHECK(hipMemcpyAsync(p->d_in, stage.data(), sizeof(double) * (host_trig ? 7 : 5) * n, hipMemcpyHostToDevice, ctx->stream));
-  rc = queue_score(p, cfg, base_pose, n, p->d_in, p->d_in + n, host_trig ? p->d_in + 5 * (size_t)n : nullptr, p->d_scores,
-                   p->d_levels);
+  // RAW_EXACT: the (sin, cos) part holds the rows' rotations (at most n doubles) and, behind them, a row per candidate
+  std::vector<double> rot_rows;
+  if (raw) {
+    pyr_raw_rows(n, rotation, reinterpret_cast<int *>(stage.data() + 6 * (size_t)n), &rot_rows);
+    std::memcpy(stage.data() + 5 * (size_t)n, rot_rows.data(), sizeof(double) * rot_rows.size());
+  }
+  SLAMHIP_CHECK(hipMemcpyAsync(p->d_in, stage.data(), sizeof(double) * (host_trig || raw ? 7 : 5) * n, hipMemcpyHostToDevice,
+                               ctx->stream));
+  RawTrig rt{};
+  if (raw) {
+    rc = pyr_raw_queue_table(p, fma, p->d_in + 5 * (size_t)n, (int)rot_rows.size(), base_pose[2], d_angle, ctx->scan_n, &rt);
+    if (rc) return rc;
+    rt.row = reinterpret_cast<const int *>(p->d_in + 6 * (size_t)n);
+  }
+  rc = queue_score(p, cfg, base_pose, n, p->d_in, p->d_in + n, host_trig ? p->d_in + 5 * (size_t)n : nullptr,
+                   raw ? &rt : nullptr, p->d_scores, p->d_levels);
   if (rc) return rc;
   SLAMHIP_CHECK(hipMemcpyAsync(score_out, p->d_scores, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipMemcpyAsync(level_out, p->d_levels, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -699,8 +894,10 @@ int slamhip_pyramid_score_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg,
   rc = prof.open(ctx, ctx->stream, 0);
   if (rc) return rc;
   typedef void (*Kernel)(ManyArgs);
-  const Kernel kernel =
-      pick_cell_model(table[0].pyramid->cell_model, [](auto m) -> Kernel { return k_pyr_score_many<decltype(m)::value>; });
+  const bool raw = a.m.raw.cos != nullptr;
+  const Kernel kernel = pick_cell_model(table[0].pyramid->cell_model, [raw](auto m) -> Kernel {
+    return raw ? k_pyr_score_many<decltype(m)::value, true> : k_pyr_score_many<decltype(m)::value, false>;
+  });
   SLAMHIP_CHECK(launch_kernel(kernel, dim3(n), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));
   if (a.m.terms) {
     rc = pyr_launch_sum_sequential_many(a, (size_t)n, 1, ctx->stream);

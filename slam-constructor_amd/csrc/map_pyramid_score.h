@@ -28,6 +28,10 @@ struct slamhip_pyramid {
   double *d_x_in = nullptr, *d_x_out = nullptr, *h_x = nullptr;
   int x_parent_cap = 0;
   size_t x_slot_cap = 0;
+  // SLAMHIP_POSE_TRIG_RAW_EXACT: the table of exact beam directions of the launch under way (RawTrig), cos rows in front
+  // of the sin rows
+  double *d_raw = nullptr;
+  size_t raw_cap = 0;
 };
 
 namespace slamhip {
@@ -41,6 +45,19 @@ struct PyrSource {
   int n_levels;
   ScanView scan;
   double base[3];
+  const double *angle;  // the scan's point angles in HBM: SLAMHIP_POSE_TRIG_RAW_EXACT's tabulation reads them, else null
+};
+
+// SLAMHIP_POSE_TRIG_RAW_EXACT, the reference's default provider (RawTrigonometryProvider under
+// LaserScan2D::to_cartesian(rot + pose.theta), m3rsm_engine.h:300-314): a beam's direction is libm's
+// cos / sin((rotation + base heading) + angle[b]) -- a function of (request, rotation, beam) alone, whatever the
+// rectangle.  The distinct (request, rotation) pairs of a call are the ROWS of a table filled by one launch in front of
+// the scoring one (k_pyr_raw_table, map_pyramid.hip); candidate / parent i takes its beams' directions from row row[i]
+// (null: row i) as they stand.  Null cos: the launch is not a RAW one.
+struct RawTrig {
+  const double *cos, *sin;  // n_rows x stride each
+  const int *row;           // per candidate / parent
+  size_t stride;
 };
 
 struct MatchArgs : PyrSource {
@@ -51,6 +68,7 @@ struct MatchArgs : PyrSource {
   int *level_out;
   double *terms;  // beam-order sum only: n x scan.n (multi-request: the rows lie where ManyArgs::terms_off says)
   int n, oie, oope;
+  RawTrig raw;  // read by the RAW instantiations only
 };
 
 // The multi-request launches (k_pyr_score_many, k_m3rsm_expand_many): candidate / parent i belongs to request[i], whose
@@ -76,6 +94,18 @@ int pyr_launch_sum_sequential(const MatchArgs &a, size_t n_out, hipStream_t stre
 // ... of a multi-request launch with `slots` outputs per parent (1: the bounds kernel)
 int pyr_launch_sum_sequential_many(const ManyArgs &a, size_t n_out, int slots, hipStream_t stream);
 
+// ---- SLAMHIP_POSE_TRIG_RAW_EXACT (map_pyramid.hip) ----
+// which libm build the tables restate (SLAMHIP_ERR_UNSUPPORTED where neither matches) and the current scan's angles in
+// HBM (SLAMHIP_ERR_STATE where the context has none); launches nothing
+int pyr_raw_prepare(slamhip_ctx *ctx, bool *fma, const double **d_angle);
+// the distinct rotations (bit patterns) of n candidates / parents of one request, in order of first appearance:
+// row_out[i] = the row of candidate i, rot_rows = the rows' rotations
+void pyr_raw_rows(int n, const double *rotation, int *row_out, std::vector<double> *rot_rows);
+// queues the tabulation of n_rows rows -- row r = cos / sin((d_rot_rows[r] + base_theta) + d_angle[b]), b < n_beams -- into
+// the pyramid's table (grown on demand) and fills *out but for `row`
+int pyr_raw_queue_table(slamhip_pyramid *p, bool fma, const double *d_rot_rows, int n_rows, double base_theta,
+                        const double *d_angle, int n_beams, RawTrig *out);
+
 // The staging of the multi-request launches (slamhip_pyramid_score_requests / _expand_requests), kept by the context:
 // one pinned block and one block in HBM, each the inputs (table | terms offsets | rotation | rect | sin, cos | request)
 // in front of the outputs (rect | score | level per slot), and the terms.
@@ -84,13 +114,17 @@ struct PyrManyStage {
   size_t cap = 0, out_at = 0;  // out_at: where the outputs of the launch staged last begin
   double *d_terms = nullptr;
   size_t terms_cap = 0;
+  double *d_raw = nullptr;  // SLAMHIP_POSE_TRIG_RAW_EXACT: the launch's table of beam directions (RawTrig)
+  size_t raw_cap = 0;
 };
 void pyr_many_release(slamhip_ctx *ctx);
 // checks a request table against the context and cfg and fills the sources the kernels read
+// (under SLAMHIP_POSE_TRIG_RAW_EXACT also that every request's slot has angles and the host's libm is a known build)
 int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests, const slamhip_m3rsm_request *req,
                      std::vector<PyrSource> *out);
 // stages n candidates (request, rotation, rect) of the table, leaving room for n x slots outputs; fills a->m's inputs and
-// outputs, a->table, a->request, a->terms_off.  After the launch: pyr_many_fetch
+// outputs, a->table, a->request, a->terms_off.  After the launch: pyr_many_fetch.  Under SLAMHIP_POSE_TRIG_RAW_EXACT it
+// also stages the rows of the distinct (request, rotation) pairs, queues their tabulation and fills a->m.raw
 int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int n, const int *request,
                    const double *rotation, const double *rect, int slots, ManyArgs *a, double **d_rect_out);
 // request indices inside the table, finite rotations and rectangles (reversed ones only where the caller lets them through)
@@ -102,8 +136,10 @@ int pyr_many_fetch(slamhip_ctx *ctx, size_t n_out, bool with_rect, double *rect_
 // from `q` (the launch's own MatchArgs, or the candidate's entry of the request table, read once by its caller),
 // rotation index `src` (into a.rotation / a.pose_sc), the rectangle in registers, the result at index `out` of a.scores /
 // a.level_out, the per-beam terms (beam-order sum; else `terms` is null) from terms[terms_at] on.  Every thread of the
-// workgroup calls it with the same arguments.
-template <int MODEL>
+// workgroup calls it with the same arguments.  RAW: a beam's direction is read from row a.raw.row[src] of the table of
+// exact cos / sin((rotation + heading) + angle) -- no pose rotation, no sincos, no barrier for it; everything behind the
+// direction is the other modes' code.
+template <int MODEL, bool RAW = false>
 __device__ __forceinline__ void pyr_score_one(const PyrSource &q, const MatchArgs &a, size_t src, size_t out, double *terms,
                                               size_t terms_at, double bot, double top, double left, double right, double *s_trig,
                                               double *s_part) {
@@ -125,25 +161,33 @@ __device__ __forceinline__ void pyr_score_one(const PyrSource &q, const MatchArg
   const MapView map = q.levels[lv];
   // LightWeightRectangle::center() added to the pose
   const double x = q.base[0] + (left + hside / 2), y = q.base[1] + (bot + vside / 2);
-  if (t == 0) {
-    double sn, cs;
-    if (a.pose_sc) {
-      sn = a.pose_sc[2 * src];
-      cs = a.pose_sc[2 * src + 1];
-    } else {
-      sincos(a.rotation[src] + q.base[2], &sn, &cs);
+  double sn = 0.0, cs = 1.0;
+  const double *cos_a = q.scan.cos_a, *sin_a = q.scan.sin_a;
+  if (RAW) {
+    const size_t at = (size_t)(a.raw.row ? a.raw.row[src] : (int)src) * a.raw.stride;
+    cos_a = a.raw.cos + at;
+    sin_a = a.raw.sin + at;
+  } else {
+    if (t == 0) {
+      if (a.pose_sc) {
+        sn = a.pose_sc[2 * src];
+        cs = a.pose_sc[2 * src + 1];
+      } else {
+        sincos(a.rotation[src] + q.base[2], &sn, &cs);
+      }
+      s_trig[0] = sn;
+      s_trig[1] = cs;
     }
-    s_trig[0] = sn;
-    s_trig[1] = cs;
+    __syncthreads();
+    sn = s_trig[0];
+    cs = s_trig[1];
   }
-  __syncthreads();
-  const double sn = s_trig[0], cs = s_trig[1];
   const double half_v = (top - bot) / 2, half_h = (right - left) / 2;
   double acc = 0.0;
   for (int b = t; b < n; b += kPyrThreads) {
-    const double ca = q.scan.cos_a[b], sa = q.scan.sin_a[b], r = q.scan.range[b];
-    const double c = cs * ca - sn * sa;
-    const double s = sn * ca + cs * sa;
+    const double ca = cos_a[b], sa = sin_a[b], r = q.scan.range[b];
+    const double c = RAW ? ca : cs * ca - sn * sa;
+    const double s = RAW ? sa : sn * ca + cs * sa;
     const double ox = x + r * c, oy = y + r * s;
     const double pr = window_probability<MODEL>(map, a.oie, a.oope, half_v, half_h, ox, oy);
     const double term = pr * q.scan.weight[b] * q.scan.factor[b];

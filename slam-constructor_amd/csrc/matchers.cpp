@@ -1744,6 +1744,12 @@ constexpr long long kScoreBack = sizeof(double) + sizeof(int), kSlotBack = 5 * s
 int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3], double *out_prob) {
   slamhip_matcher::M3rsm &s = *m->m3;
   slamhip_ctx *ctx = m->ctx;
+  // (found before anything is launched or counted: the raw provider's bounds need the scan's angles)
+  if (m->cfg.pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT && ctx->scan_n > 0 && !scan_angles_known(ctx)) {
+    set_error("SLAMHIP_POSE_TRIG_RAW_EXACT needs the angles of the current scan's points: slamhip_scan_set_angles (or "
+              "slamhip_scan_filter_upload) after the scan upload");
+    return SLAMHIP_ERR_STATE;
+  }
   m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
   s.trace.clear();
   s.res = m3rsm::Result{};
@@ -2094,8 +2100,9 @@ int slamhip_matcher_create_m3rsm(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, s
   // (a window OOPE -- not the 1-cell or the GMapping one --, the pyramid's OIE, a known sum order)
   int rc = pyr_check_score_cfg(pyramid, cfg);
   if (rc) return rc;
-  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
-    return invalid_arg("pose_trig: DEVICE or HOST (bounds know no per-beam raw trigonometry)");
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST &&
+      cfg->pose_trig != SLAMHIP_POSE_TRIG_RAW_EXACT)
+    return invalid_arg("pose_trig: DEVICE, HOST or RAW_EXACT");
   if (!(angle_step > 0) || !(translation_step > 0) || !std::isfinite(angle_step) || !std::isfinite(translation_step))
     return invalid_arg("the rotation and translation steps must be positive and finite");
   if (!(max_x_error >= 0) || !(max_y_error >= 0) || !(max_th_error >= 0) || !std::isfinite(max_x_error) ||
@@ -2609,7 +2616,9 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       ctx->scan_tot_w = saved_tot_w;
       ctx->h_weight.swap(saved_w);
       ctx->h_factor.swap(saved_f);
-      ctx->h_scan_angle.clear();  // (a stored scan has none, as slamhip_scan_select leaves it)
+      ctx->h_scan_angle.clear();  // (a stored scan has its slot's, if any, as slamhip_scan_select leaves it)
+      for (const slamhip_ctx::ScanSlot &sl : ctx->scan_slots)
+        if (sl.d == saved_ptr) ctx->h_scan_angle = sl.angle;
       ctx->scan_angle_on_device = false;
     }
     ctx->scan_angle_lazy = false;

@@ -479,7 +479,7 @@ void scan_angles_materialise(slamhip_ctx *ctx) {
 }
 
 // the beam angles of the current scan in HBM (uploaded on first use)
-static int exact_angles(slamhip_ctx *ctx, const double **d_angle) {
+int scan_exact_angles(slamhip_ctx *ctx, const double **d_angle) {
   const int n = ctx->scan_n;
   scan_angles_materialise(ctx);
   if ((int)ctx->h_scan_angle.size() != n) {
@@ -523,7 +523,7 @@ static int score_exact(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cf
   const bool gm = cfg->oope == SLAMHIP_OOPE_GMAPPING;
   const double *d_angle = nullptr;
   if (raw) {
-    const int rc = exact_angles(ctx, &d_angle);
+    const int rc = scan_exact_angles(ctx, &d_angle);
     if (rc) return rc;
   }
   const double *poses_src = ctx->h_poses + 3 * (size_t)off;
@@ -806,6 +806,8 @@ int slamhip_ctx_destroy(slamhip_ctx *ctx) {
   if (ctx->d_scan_angle) hipFree(ctx->d_scan_angle);
   if (ctx->d_exact_trig) hipFree(ctx->d_exact_trig);
   if (ctx->d_gm_exact_cache) hipFree(ctx->d_gm_exact_cache);
+  for (auto &sl : ctx->scan_slots)
+    if (sl.d_angle) hipFree(sl.d_angle);
   for (auto &sl : ctx->scan_slots)
     if (sl.d) hipFree(sl.d);
   for (int k = 0; k < 2; ++k) {
@@ -1200,6 +1202,7 @@ int slamhip_scan_store(slamhip_ctx *ctx, int slot, int n, const double *range, c
     if (selected) ctx->scan_ptr = sl.d;
   }
   sl.n = n;
+  sl.angle.clear();  // (the angles of the scan before: slamhip_scan_store_angles)
   sl.w.assign(weight, weight + n);
   if (factor) sl.f.assign(factor, factor + n);
   else sl.f.assign(n, 1.0);
@@ -1213,6 +1216,9 @@ int slamhip_scan_store(slamhip_ctx *ctx, int slot, int n, const double *range, c
   SLAMHIP_CHECK(hipMemcpy(sl.d + 3 * c, weight, bytes, hipMemcpyHostToDevice));
   SLAMHIP_CHECK(hipMemcpy(sl.d + 4 * c, sl.f.data(), bytes, hipMemcpyHostToDevice));
   if (ctx->scan_ptr == sl.d) {  // the selected scan was rewritten in place
+    ctx->h_scan_angle.clear();
+    ctx->scan_angle_lazy = false;
+    ctx->scan_angle_on_device = false;
     ctx->scan_n = n;
     ctx->scan_tot_w = tot_w;
     ctx->scan_stride = c;
@@ -1230,12 +1236,39 @@ int slamhip_scan_select(slamhip_ctx *ctx, int slot) {
   ctx->scan_ptr = sl.d;
   ctx->scan_stride = (size_t)sl.cap;
   ctx->scan_n = sl.n;
-  ctx->h_scan_angle.clear();
+  ctx->h_scan_angle = sl.angle;  // (none unless slamhip_scan_store_angles gave the slot some)
   ctx->scan_angle_lazy = false;
   ctx->scan_angle_on_device = false;
   ctx->scan_tot_w = sl.tot_w;
   ctx->h_weight.assign(sl.w.begin(), sl.w.end());
   ctx->h_factor.assign(sl.f.begin(), sl.f.end());
+  return SLAMHIP_OK;
+}
+
+int slamhip_scan_store_angles(slamhip_ctx *ctx, int slot, int n, const double *angle) {
+  if (!ctx || !angle) return invalid("bad arguments");
+  if (slot < 0 || slot >= (int)ctx->scan_slots.size() || !ctx->scan_slots[slot].d || ctx->scan_slots[slot].n <= 0)
+    return invalid("no scan stored in that slot");
+  slamhip_ctx::ScanSlot &sl = ctx->scan_slots[slot];
+  if (n != sl.n) return invalid("slamhip_scan_store_angles: n is not the stored scan's point count");
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  // work queued on the context may still read the slot's angles
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (n > sl.angle_cap) {
+    if (sl.d_angle) hipFree(sl.d_angle);
+    sl.d_angle = nullptr;
+    sl.angle_cap = 0;
+    const int cap = (n + 7) & ~7;
+    SLAMHIP_CHECK(hipMalloc(&sl.d_angle, sizeof(double) * cap));
+    sl.angle_cap = cap;
+  }
+  SLAMHIP_CHECK(hipMemcpy(sl.d_angle, angle, sizeof(double) * n, hipMemcpyHostToDevice));
+  sl.angle.assign(angle, angle + n);
+  if (ctx->scan_ptr == sl.d) {  // the slot is the current scan
+    ctx->h_scan_angle = sl.angle;
+    ctx->scan_angle_lazy = false;
+    ctx->scan_angle_on_device = false;
+  }
   return SLAMHIP_OK;
 }
 

@@ -344,6 +344,11 @@ struct slamhip_ctx {
     int cap = 0, n = 0;
     double tot_w = 0.0;
     std::vector<double> w, f;
+    // slamhip_scan_store_angles: the points' angles (SLAMHIP_POSE_TRIG_RAW_EXACT), on the host and in HBM; empty after
+    // a slamhip_scan_store into the slot
+    std::vector<double> angle;
+    double *d_angle = nullptr;
+    int angle_cap = 0;
   };
   std::vector<ScanSlot> scan_slots;
   // slamhip_scan_filter_upload: what depends on the scanner's beam ANGLES only (cos / sin per raw beam as the scan's
@@ -449,6 +454,8 @@ inline bool scan_angles_known(const slamhip_ctx *ctx) {
 }
 // ... and has them in h_scan_angle (slamhip_api.cpp)
 void scan_angles_materialise(slamhip_ctx *ctx);
+// ... and in HBM (uploaded on first use); SLAMHIP_ERR_STATE where it does not know them
+int scan_exact_angles(slamhip_ctx *ctx, const double **d_angle);
 // The raw scan's upload in two halves (slamhip_api.cpp; slamhip_scan_filter_upload is the two in a row).
 // scan_filter_stage: filter, weights, the staging buffer filled, the new scan recorded as the current one --
 // ctx->scan_pending.active unless the filter kept nothing.  scan_assemble_now: k_scan_assemble on the context's stream

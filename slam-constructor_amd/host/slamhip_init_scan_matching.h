@@ -72,8 +72,8 @@ inline std::shared_ptr<GridScanMatcher> init_hip_scan_matcher(const PropertiesPr
       std::exit(-1);
     }
     const std::string ns = Slam_SM_NS + "BF_M3RSM/";
-    // (strict: bounds are scored under the cached provider's angle addition only)
-    if (cfg.pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT) cfg.pose_trig = SLAMHIP_POSE_TRIG_HOST;
+    // (strict: the bounds take the scan's provider as the other matchers do -- RAW_EXACT under the raw provider, whose
+    // kept angles HipGridScanMatcher hands over with every scan, HOST with "hip/trig_cache")
     const auto ang_acc = props.get_dbl(ns + "accuracy/rotation", deg2rad(0.1));
     const auto trl_acc = props.get_dbl(ns + "accuracy/translation", 0.05);
     const auto max_x_err = props.get_dbl(ns + "limits/x_translation", 1);

@@ -148,6 +148,10 @@ public:
     q.init_pose[1] = pose.y;
     q.init_pose[2] = pose.theta;
     slamhip_or_die(slamhip_scan_store(_ctx, q.scan_slot, n, r.data(), c.data(), s.data(), w.data(), f.data()), "scan_store");
+    // a scan under the reference's default provider: the kept points' angles go with the slot, for a matcher made with
+    // SLAMHIP_POSE_TRIG_RAW_EXACT (the other modes do not read them)
+    if (_trig.mode != SLAMHIP_TRIG_CACHED)
+      slamhip_or_die(slamhip_scan_store_angles(_ctx, q.scan_slot, n, a.data()), "scan_store_angles");
     _requests.push_back(q);
   }
 

@@ -2,6 +2,7 @@
 """Time the multi-resolution matcher (BF_M3RSM) on the GPU against the route the pyramid API alone offers.
 
     python tools/m3rsm_ms.py [--reps 20] [--grid-reps 20] [--size 2000] [--beams 1080] [--out FILE.json]
+                             [--pose-trig device|host|raw_exact] [--strict] [--no-grid]
 
 Scene: a size x size OCC map with walls at 0.05 m (tests/synth.make_scene, the benchmark's scene), a scan of --beams
 beams, the `max` OOPE, the default mode (canonical tree sum, device sincos) and the documented default limits of
@@ -13,7 +14,9 @@ All routes run in one process and alternate match by match, after a check that t
 trace.  Per route: wall time per match (host clock around process_scan, which waits for its last download) as median /
 min / max over the matches; launches, super-steps, branching pops per super-step, candidates scored per committed call;
 kernel time per match from the library's HIP event pairs (slamhip_profile_enable), measured in a pass of its own.
-`ratio_b_over_a` is median (b) over median (a) at the default.  Needs a GPU; prints one JSON object."""
+`ratio_b_over_a` is median (b) over median (a) at the default.  --pose-trig and --strict (the beam-order sum) select the
+scoring mode of every route -- raw_exact: the reference's default trig provider bit for bit, one tabulation launch in
+front of every scoring launch --, --no-grid leaves the grid out.  Needs a GPU; prints one JSON object."""
 import argparse
 import json
 import os
@@ -58,6 +61,9 @@ def main():
     ap.add_argument("--size", type=int, default=2000)
     ap.add_argument("--beams", type=int, default=1080)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pose-trig", choices=("device", "host", "raw_exact"), default="device")
+    ap.add_argument("--strict", action="store_true")
+    ap.add_argument("--no-grid", action="store_true")
     a = ap.parse_args()
     import pyoracle as po
     from synth import make_scene
@@ -68,8 +74,11 @@ def main():
     scan = sc["scan"]
     cos_a, sin_a = pkg.beam_trig(scan.angle)
     ctx.scan_upload(scan.range, cos_a, sin_a, scan.weight, scan.factor)
+    ctx.scan_set_angles(scan.angle)  # (read by raw_exact only)
     pyr = pkg.Pyramid(ctx, FINE, pkg.OIE_DISCREPANCY, FIRST)
-    cfg = pkg.spe_cfg(oope=pkg.OOPE_MAX, oie=pkg.OIE_DISCREPANCY)
+    pose_trig = {"device": pkg.POSE_TRIG_DEVICE, "host": pkg.POSE_TRIG_HOST, "raw_exact": pkg.POSE_TRIG_RAW_EXACT}[a.pose_trig]
+    cfg = pkg.spe_cfg(oope=pkg.OOPE_MAX, oie=pkg.OIE_DISCREPANCY, pose_trig=pose_trig,
+                      sum_order=pkg.SUM_SEQUENTIAL if a.strict else pkg.SUM_TREE256)
     pose = sc["init_pose"]
 
     def matcher(width, depth):
@@ -79,7 +88,7 @@ def main():
         return m
 
     routes = {"default": matcher(None, None), "per_pop": matcher(0, 0)}
-    for w, d in GRID:
+    for w, d in ([] if a.no_grid else GRID):
         routes["W%d_D%d" % (w, d)] = matcher(w, d)
     # every route returns the same match, call for call
     ref, info = None, {}
@@ -117,8 +126,8 @@ def main():
         ctx.profile_enable(False)
         info[name]["match_ms"] = spread(times[name])
         info[name]["matches"] = len(times[name])
-    best = min((n for n in routes if n.startswith("W")), key=lambda n: info[n]["match_ms"]["median"])
-    out = dict(scene="OCC %d x %d at 0.05, %d beams, limits +-1 m, +-1 m, +-5 deg at 0.1 deg, step 0.05" % (a.size, a.size, a.beams),
+    best = min((n for n in routes if n.startswith("W")), key=lambda n: info[n]["match_ms"]["median"], default=None)
+    out = dict(pose_trig=a.pose_trig, sum_order="sequential" if a.strict else "tree256", scene="OCC %d x %d at 0.05, %d beams, limits +-1 m, +-1 m, +-5 deg at 0.1 deg, step 0.05" % (a.size, a.size, a.beams),
                roots=int(n_roots), branching_pops=int(pops), result=dict(delta=ref[0]["delta"].tolist(), prob=ref[0]["prob"]),
                routes=info, fastest_grid_point=best,
                ratio_b_over_a=info["per_pop"]["match_ms"]["median"] / info["default"]["match_ms"]["median"])
