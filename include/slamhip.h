@@ -695,6 +695,20 @@ int slamhip_matcher_m3rsm_each_stats(slamhip_matcher *m, int request, long long 
 /* worker threads of slamhip_matcher_m3rsm_match_each's host half: 1 .. 16 (1: the calling thread alone), 0 = the default,
  * min(requests, 8).  Results do not depend on it. */
 int slamhip_matcher_set_m3rsm_threads(slamhip_matcher *m, int threads);
+/* Scan point weights that turn with the candidate's ROTATION.  The reference's matcher hands its estimator PREROTATED scans
+ * (prerotate_scan = true, bf_multi_res_scan_matcher.h:42-43): Cartesian points in the world's orientation, and a weighting
+ * that reads a point's angle() -- VinySlamSPW, weighted_mean_point_probability_spe.h:47-60 -- weighs it by beam angle +
+ * rotation + heading.  `even` weights do not depend on the point and need none of this.
+ *   slamhip_matcher_m3rsm_rotations: the distinct rotations of the root layer in its order (0, -s, +s, -2 s, ...;
+ *   *n = how many, may exceed cap).
+ *   slamhip_matcher_set_m3rsm_rotation_slots(m, 1): from now on a request's scan_slot is the FIRST of *n consecutive slots,
+ *   slot scan_slot + j holding the scan -- the same points -- with the weights under rotation j of that list (and its angles,
+ *   for RAW_EXACT); a candidate reads the slot of its rotation.  The search, its calls and its counters are otherwise those
+ *   of slamhip_matcher_m3rsm_match_many / _match_each; a missing slot is SLAMHIP_ERR_INVALID before anything is launched.
+ *   While on, slamhip_matcher_process_scan / _process_raw_scan are refused (SLAMHIP_ERR_INVALID): the current scan has one
+ *   set of weights.  A lone match is match_many over one request. */
+int slamhip_matcher_m3rsm_rotations(slamhip_matcher *m, int cap, double *rotation, int *n);
+int slamhip_matcher_set_m3rsm_rotation_slots(slamhip_matcher *m, int on);
 /* Bytes the launches of the last BF_M3RSM match -- lone, many-to-many or each -- wrote back to the host: 12 per root
  * candidate (score, level), 44 per slot of every parent (rectangle, score, level), slots without a node included. */
 int slamhip_matcher_m3rsm_copied_back(slamhip_matcher *m, long long *bytes);

@@ -69,6 +69,7 @@ slamhip_pyramid_score_requests slamhip_pyramid_expand_requests slamhip_matcher_m
 slamhip_matcher_m3rsm_trace_many
 slamhip_matcher_m3rsm_match_each slamhip_matcher_m3rsm_trace_each slamhip_matcher_m3rsm_each_stats
 slamhip_matcher_set_m3rsm_threads slamhip_matcher_m3rsm_copied_back
+slamhip_matcher_m3rsm_rotations slamhip_matcher_set_m3rsm_rotation_slots
 slamhip_scan_table_uploads slamhip_scan_download
 slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download""".split()
 
@@ -306,6 +307,8 @@ def load(testing=False):
     L.slamhip_matcher_m3rsm_trace_each.argtypes = [vp, i, i, _dp, _ip]
     L.slamhip_matcher_m3rsm_each_stats.argtypes = [vp, i] + [C.POINTER(C.c_longlong)] * 4
     L.slamhip_matcher_set_m3rsm_threads.argtypes = [vp, i]
+    L.slamhip_matcher_m3rsm_rotations.argtypes = [vp, i, _dp, _ip]
+    L.slamhip_matcher_set_m3rsm_rotation_slots.argtypes = [vp, i]
     L.slamhip_matcher_m3rsm_copied_back.argtypes = [vp, C.POINTER(C.c_longlong)]
     _libs[testing] = L
     return L
@@ -1180,6 +1183,19 @@ class Matcher:
     def set_m3rsm_threads(self, n):
         """Worker threads of m3rsm_match_each's host half: 1 .. 16, 0 = the default (slamhip_matcher_set_m3rsm_threads)."""
         _check(self.L.slamhip_matcher_set_m3rsm_threads(self.h, int(n)))
+
+    def m3rsm_rotations(self):
+        """The distinct rotations of the root layer, in its order (slamhip_matcher_m3rsm_rotations)."""
+        n = C.c_int()
+        _check(self.L.slamhip_matcher_m3rsm_rotations(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value)
+        _check(self.L.slamhip_matcher_m3rsm_rotations(self.h, n.value, out.ctypes.data_as(_dp), C.byref(n)))
+        return out
+
+    def set_m3rsm_rotation_slots(self, on):
+        """A request's scan_slot is the first of one slot per root rotation, each with that rotation's weights
+        (slamhip_matcher_set_m3rsm_rotation_slots)."""
+        _check(self.L.slamhip_matcher_set_m3rsm_rotation_slots(self.h, int(bool(on))))
 
     def m3rsm_copied_back(self):
         """Bytes the launches of the last BF_M3RSM match wrote back to the host (slamhip_matcher_m3rsm_copied_back)."""

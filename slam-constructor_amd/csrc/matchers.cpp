@@ -260,6 +260,8 @@ struct slamhip_matcher {
     slamhip::m3rsm::Result res;
     std::vector<slamhip::m3rsm::Call> trace;  // the committed calls of the last match
     bool per_pop = false;  // no expand launches: a slamhip_pyramid_score_matches launch per popped match
+    // slamhip_matcher_set_m3rsm_rotation_slots: a request's scan_slot is the FIRST of one slot per root rotation
+    bool rot_slots = false;
     // the last slamhip_matcher_m3rsm_match_each: per request its result, the engine's code and its committed calls
     std::vector<slamhip::m3rsm::Result> each_res;
     std::vector<int> each_code;
@@ -1742,6 +1744,9 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
 constexpr long long kScoreBack = sizeof(double) + sizeof(int), kSlotBack = 5 * sizeof(double) + sizeof(int);
 
 int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3], double *out_prob) {
+  if (m->m3->rot_slots)
+    return invalid_arg("rotation slots are set (slamhip_matcher_set_m3rsm_rotation_slots): the scan comes from a request's slots, "
+                       "slamhip_matcher_m3rsm_match_many / _match_each");
   slamhip_matcher::M3rsm &s = *m->m3;
   slamhip_ctx *ctx = m->ctx;
   // (found before anything is launched or counted: the raw provider's bounds need the scan's angles)
@@ -1822,6 +1827,51 @@ int m3rsm_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3]
   return SLAMHIP_OK;
 }
 
+// slamhip_matcher_set_m3rsm_rotation_slots: scan point weights that depend on the candidate's ROTATION (the reference's
+// matcher hands its estimator prerotated scans, and VinySlamSPW weighs a point by its direction in the world).  The
+// engine keeps its requests; at the launch boundary candidate (request k, rotation j-th of the root layer) reads entry
+// k * n_rot + j of an expanded table, whose scan slot is req[k].scan_slot + j -- the same points, that rotation's weights.
+// The kernels see one more request per rotation and nothing else.
+struct RotationSlots {
+  bool on = false;
+  int n_rot = 1;
+  std::vector<double> rots;  // the root layer's distinct rotations, in its order
+  std::vector<slamhip_m3rsm_request> table;
+  std::vector<int> mapped;
+  void init(bool enabled, const m3rsm::Config &cfg, int n_requests, const slamhip_m3rsm_request *req) {
+    on = enabled;
+    if (!on) return;
+    std::vector<double> rot;
+    std::vector<m3rsm::Rect> rect;
+    m3rsm::root_candidates(cfg, &rot, &rect);
+    rots.clear();
+    for (double r : rot)
+      if (index_of(r) < 0) rots.push_back(r);
+    n_rot = (int)rots.size();
+    table.clear();
+    for (int k = 0; k < n_requests; ++k)
+      for (int j = 0; j < n_rot; ++j) {
+        slamhip_m3rsm_request q = req[k];
+        q.scan_slot = req[k].scan_slot + j;
+        table.push_back(q);
+      }
+  }
+  int index_of(double r) const {
+    for (size_t j = 0; j < rots.size(); ++j)
+      if (std::memcmp(&rots[j], &r, sizeof(double)) == 0) return (int)j;
+    return -1;
+  }
+  int n_table(int n_requests) const { return on ? (int)table.size() : n_requests; }
+  const slamhip_m3rsm_request *tab(const slamhip_m3rsm_request *req) const { return on ? table.data() : req; }
+  // (children carry their parent's rotation bit for bit: every rotation of a launch is one of the root layer's)
+  const int *map(int n, const int *rq, const double *rot) {
+    if (!on) return rq;
+    mapped.resize(n);
+    for (int i = 0; i < n; ++i) mapped[i] = rq[i] * n_rot + std::max(0, index_of(rot[i]));
+    return mapped.data();
+  }
+};
+
 // Several requests in one search (m3rsm::run_many): the root layers of all requests in one
 // slamhip_pyramid_score_requests launch, every super-step one slamhip_pyramid_expand_requests launch over parents of
 // whichever requests the shared queue holds on top.
@@ -1833,21 +1883,25 @@ int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
   s.trace.clear();
   s.res = m3rsm::Result{};
   s.copied_back = 0;
+  RotationSlots rs;
+  rs.init(s.rot_slots, s.cfg, n_requests, req);
+  const int n_tab = rs.n_table(n_requests);
+  const slamhip_m3rsm_request *tab = rs.tab(req);
   {
     std::vector<PyrSource> src;  // (checked before anything runs: the launches check again, they are entry points too)
-    const int rc = pyr_many_sources(ctx, &m->cfg, n_requests, req, &src);
+    const int rc = pyr_many_sources(ctx, &m->cfg, n_tab, tab, &src);
     if (rc) return rc;
   }
   const double t0 = MatchJob::now_us();
   const m3rsm::ScoreManyFn roots = [&](int n, const int *rq, const double *rot, const double *rect, double *score, int *level) {
     s.copied_back += kScoreBack * n;
-    return slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, n, rq, rot, rect, score, level);
+    return slamhip_pyramid_score_requests(ctx, &m->cfg, n_tab, tab, n, rs.map(n, rq, rot), rot, rect, score, level);
   };
   const m3rsm::ExpandManyFn expand = [&](int n, const int *rq, const double *rot, const double *rect, int depth,
                                          double *slot_rect, double *slot_score, int *slot_level) {
     s.copied_back += kSlotBack * n * m3rsm::slots_of(depth);
-    return slamhip_pyramid_expand_requests(ctx, &m->cfg, n_requests, req, n, rq, rot, rect, s.cfg.translation_step, depth,
-                                           slot_rect, slot_score, slot_level);
+    return slamhip_pyramid_expand_requests(ctx, &m->cfg, n_tab, tab, n, rs.map(n, rq, rot), rot, rect, s.cfg.translation_step,
+                                           depth, slot_rect, slot_score, slot_level);
   };
   // without the expand kernel (speculation 0, 0): as for the lone match, a bounds launch per popped match
   const m3rsm::ExpandManyFn per_pop = [&](int n, const int *rq, const double *rot, const double *rect, int, double *slot_rect,
@@ -1868,7 +1922,9 @@ int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
       slot_level[c] = -1;
     }
     s.copied_back += kScoreBack * nk;
-    return nk ? slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, nk, k_req, k_rot, k_rect, slot_score, slot_level) : 0;
+    return nk ? slamhip_pyramid_score_requests(ctx, &m->cfg, n_tab, tab, nk, rs.map(nk, k_req, k_rot), k_rot, k_rect, slot_score,
+                                               slot_level)
+              : 0;
   };
   m3rsm::Config run_cfg = s.cfg;
   if (s.per_pop) run_cfg.width = run_cfg.depth = 1;
@@ -1916,9 +1972,13 @@ int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
   s.each_code.clear();
   s.each_trace.clear();
   if (s.per_pop) return invalid_arg("speculation (0, 0), the per-pop measuring route, has no batched form");
+  RotationSlots rs;
+  rs.init(s.rot_slots, s.cfg, n_requests, req);
+  const int n_tab = rs.n_table(n_requests);
+  const slamhip_m3rsm_request *tab = rs.tab(req);
   std::vector<PyrSource> src;  // (checked before anything runs: the launches check again, they are entry points too)
   {
-    const int rc = pyr_many_sources(ctx, &m->cfg, n_requests, req, &src);
+    const int rc = pyr_many_sources(ctx, &m->cfg, n_tab, tab, &src);
     if (rc) return rc;
   }
   const double t0 = MatchJob::now_us();
@@ -1934,15 +1994,16 @@ int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
       return;
     }
     bytes.resize(n);
-    for (int i = 0; i < n; ++i) bytes[i] = sizeof(double) * slots * (size_t)src[rq[i]].scan.n;
+    for (int i = 0; i < n; ++i) bytes[i] = sizeof(double) * slots * (size_t)src[(size_t)rq[i] * rs.n_rot].scan.n;
     m3rsm::split_by_bytes(bytes.data(), n, kEachStageLimit, &first);
   };
   const m3rsm::ScoreManyFn roots = [&](int n, const int *rq, const double *rot, const double *rect, double *score, int *level) {
     cut(n, rq, 1);
     s.copied_back += kScoreBack * n;
+    const int *mq = rs.map(n, rq, rot);
     for (size_t c = 0; c + 1 < first.size(); ++c) {
       const int at = first[c];
-      const int rc = slamhip_pyramid_score_requests(ctx, &m->cfg, n_requests, req, first[c + 1] - at, rq + at, rot + at,
+      const int rc = slamhip_pyramid_score_requests(ctx, &m->cfg, n_tab, tab, first[c + 1] - at, mq + at, rot + at,
                                                     rect + 4 * (size_t)at, score + at, level + at);
       ++launches;
       if (rc) return rc;
@@ -1954,9 +2015,10 @@ int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
     const size_t slots = (size_t)m3rsm::slots_of(depth);
     cut(n, rq, slots);
     s.copied_back += kSlotBack * n * (long long)slots;
+    const int *mq = rs.map(n, rq, rot);
     for (size_t c = 0; c + 1 < first.size(); ++c) {
       const size_t at = (size_t)first[c];
-      const int rc = slamhip_pyramid_expand_requests(ctx, &m->cfg, n_requests, req, first[c + 1] - first[c], rq + at, rot + at,
+      const int rc = slamhip_pyramid_expand_requests(ctx, &m->cfg, n_tab, tab, first[c + 1] - first[c], mq + at, rot + at,
                                                      rect + 4 * at, s.cfg.translation_step, depth, slot_rect + 4 * at * slots,
                                                      slot_score + at * slots, slot_level + at * slots);
       ++launches;
@@ -2055,6 +2117,22 @@ int slamhip_matcher_m3rsm_each_stats(slamhip_matcher *m, int request, long long 
 int slamhip_matcher_m3rsm_copied_back(slamhip_matcher *m, long long *bytes) {
   if (!m || !m->is_m3rsm || !bytes) return invalid_arg("not a multi-resolution matcher");
   *bytes = m->m3->copied_back;
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_set_m3rsm_rotation_slots(slamhip_matcher *m, int on) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  m->m3->rot_slots = on != 0;
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_m3rsm_rotations(slamhip_matcher *m, int cap, double *rotation, int *n) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (cap < 0 || !n || (cap > 0 && !rotation)) return invalid_arg("null outputs");
+  RotationSlots rs;
+  rs.init(true, m->m3->cfg, 0, nullptr);
+  *n = rs.n_rot;
+  for (int j = 0; j < std::min(cap, rs.n_rot); ++j) rotation[j] = rs.rots[j];
   return SLAMHIP_OK;
 }
 

@@ -98,7 +98,16 @@ inline std::shared_ptr<GridScanMatcher> init_hip_scan_matcher(const PropertiesPr
   auto mirror = std::make_shared<HipMapMirror>(ctx, map_id, model, bounded);
   mirror->set_belief_reader(belief_reader);
   auto gsm = std::make_shared<HipGridScanMatcher>(spe, ctx, m, mirror, weighting);
-  if (is_m3rsm(type)) gsm->set_resident_map(true);  // (the map is matched where it lives: nothing to mirror)
+  if (is_m3rsm(type)) {
+    gsm->set_resident_map(true);  // (the map is matched where it lives: nothing to mirror)
+    // the reference's matcher weighs PREROTATED points: any weighting but `even` turns with the candidate's rotation
+    if (weighting == 1)
+      gsm->set_m3rsm_rotation_weights(std::make_shared<VinySlamSPW>(), m3rsm_map->pyramid(),
+                                      props.get_int(Slam_SM_NS + "hip/m3rsm_first_scan_slot", 0));
+    else if (weighting == 2)
+      gsm->set_m3rsm_rotation_weights(std::make_shared<AngleHistogramReciprocalSPW>(), m3rsm_map->pyramid(),
+                                      props.get_int(Slam_SM_NS + "hip/m3rsm_first_scan_slot", 0));
+  }
   if (props.get_str(Slam_SM_NS + "spe/type", "<undefined>") == "wmpp")  // (init_spe's own parameters, :99-100)
     gsm->set_filter_params(props.get_uint(Slam_SM_NS + "spe/wmpp/sp_skip_rate", 0),
                            props.get_dbl(Slam_SM_NS + "spe/wmpp/sp_max_usable_range", -1), bounded);

@@ -49,34 +49,31 @@ public:
   }
 
   // GridMapScanAdder::append_scan on the fine map (slamhip_map_append_scan_q), then the levels over what it wrote:
-  // the cells within the longest beam (plus the blur) of the pose -- or everything, when the window has grown
+  // the cells within the longest beam (plus the blur) of the pose -- or everything, when the window has grown.
+  // cos_a / sin_a: the scan's provider table (slamhip_beam_trig_cached / _raw); the heading is added by the cached
+  // provider's formulas -- the reference's bits for a scan under CachedTrigonometryProvider
   void append_scan(const slamhip_scan_adder_cfg &adder, const RobotPose &pose, int n, const double *range,
                    const double *cos_a, const double *sin_a, const int *is_occ, const double *quality = nullptr) {
-    int w0 = 0, h0 = 0, ox0 = 0, oy0 = 0;
-    slamhip_or_die(slamhip_map_info(_ctx, _map_id, nullptr, &w0, &h0, &ox0, &oy0, nullptr, nullptr), "map_info");
+    const Window before = window();
     const double p3[3] = {pose.x, pose.y, pose.theta};
     long long nu = 0;
     slamhip_or_die(slamhip_map_append_scan_q(_ctx, _map_id, &adder, p3, n, range, cos_a, sin_a, is_occ, quality, &nu),
                    "map_append_scan");
-    _view->invalidate();
-    int w = 0, h = 0, ox = 0, oy = 0;
-    double scale = 1.0;
-    slamhip_or_die(slamhip_map_info(_ctx, _map_id, nullptr, &w, &h, &ox, &oy, &scale, nullptr), "map_info");
-    if (w != w0 || h != h0 || ox != ox0 || oy != oy0) {
-      slamhip_or_die(slamhip_pyramid_rebuild(_pyr), "pyramid_rebuild");
-      return;
-    }
-    double reach = 0.0;
-    for (int i = 0; i < n; ++i) reach = std::max(reach, std::isfinite(range[i]) ? range[i] : 0.0);
-    if (std::isfinite(adder.max_range)) reach = std::min(reach, adder.max_range);
-    reach += std::fabs(adder.blur) + 2 * scale;  // (a dynamic blur is a fraction of the beam: inside twice the reach)
-    if (adder.blur < 0) reach *= 2;
-    const int x0 = std::max(0, (int)std::floor((pose.x - reach) / scale) + ox);
-    const int y0 = std::max(0, (int)std::floor((pose.y - reach) / scale) + oy);
-    const int x1 = std::min(w - 1, (int)std::floor((pose.x + reach) / scale) + ox);
-    const int y1 = std::min(h - 1, (int)std::floor((pose.y + reach) / scale) + oy);
-    if (x1 < x0 || y1 < y0) return;
-    slamhip_or_die(slamhip_pyramid_refresh(_pyr, x0, y0, x1 - x0 + 1, y1 - y0 + 1), "pyramid_refresh");
+    levels_behind_scan(before, adder, pose, n, range);
+  }
+
+  // The same for a scan under the reference's DEFAULT provider (RawTrigonometryProvider: cos / sin(heading + angle) per
+  // point by the host's libm, slamhip_map_append_scan_raw): the reference's bits where a cell's value depends on the end
+  // point continuously -- a dynamic blur scales the written occupancy by the beam's length, the area estimator by the
+  // beam's chords --, which the table form reaches only to the last ulp
+  void append_scan_raw(const slamhip_scan_adder_cfg &adder, const RobotPose &pose, int n, const double *range,
+                       const double *angle, const int *is_occ, const double *quality = nullptr) {
+    const Window before = window();
+    const double p3[3] = {pose.x, pose.y, pose.theta};
+    long long nu = 0;
+    slamhip_or_die(slamhip_map_append_scan_raw(_ctx, _map_id, &adder, p3, n, range, angle, is_occ, quality, &nu),
+                   "map_append_scan_raw");
+    levels_behind_scan(before, adder, pose, n, range);
   }
 
   // Match::prob_upper_bound of n candidates (rotation, translation rectangle) around `pose` on the context's scan
@@ -98,6 +95,39 @@ public:
   }
 
 private:
+  struct Window {
+    int w = 0, h = 0, ox = 0, oy = 0;
+    double scale = 1.0;
+    bool operator!=(const Window &o) const { return w != o.w || h != o.h || ox != o.ox || oy != o.oy; }
+  };
+  Window window() const {
+    Window g;
+    slamhip_or_die(slamhip_map_info(_ctx, _map_id, nullptr, &g.w, &g.h, &g.ox, &g.oy, &g.scale, nullptr), "map_info");
+    return g;
+  }
+  void levels_behind_scan(const Window &before, const slamhip_scan_adder_cfg &adder, const RobotPose &pose, int n,
+                          const double *range) {
+    _view->invalidate();
+    const Window g = window();
+    if (g != before) {
+      slamhip_or_die(slamhip_pyramid_rebuild(_pyr), "pyramid_rebuild");
+      return;
+    }
+    const double scale = g.scale;
+    const int w = g.w, h = g.h, ox = g.ox, oy = g.oy;
+    double reach = 0.0;
+    for (int i = 0; i < n; ++i) reach = std::max(reach, std::isfinite(range[i]) ? range[i] : 0.0);
+    if (std::isfinite(adder.max_range)) reach = std::min(reach, adder.max_range);
+    reach += std::fabs(adder.blur) + 2 * scale;  // (a dynamic blur is a fraction of the beam: inside twice the reach)
+    if (adder.blur < 0) reach *= 2;
+    const int x0 = std::max(0, (int)std::floor((pose.x - reach) / scale) + ox);
+    const int y0 = std::max(0, (int)std::floor((pose.y - reach) / scale) + oy);
+    const int x1 = std::min(w - 1, (int)std::floor((pose.x + reach) / scale) + ox);
+    const int y1 = std::min(h - 1, (int)std::floor((pose.y + reach) / scale) + oy);
+    if (x1 < x0 || y1 < y0) return;
+    slamhip_or_die(slamhip_pyramid_refresh(_pyr, x0, y0, x1 - x0 + 1, y1 - y0 + 1), "pyramid_refresh");
+  }
+
   slamhip_ctx *_ctx;
   int _map_id;
   slamhip_pyramid *_pyr = nullptr;
@@ -118,15 +148,34 @@ public:
     bool is_valid() const { return request >= 0; }
   };
 
+  // rotation_spw: the estimator's weighting where it is not `even` (VinySlamSPW, AngleHistogramReciprocalSPW) -- the
+  // reference weighs prerotated points, so every request keeps one scan per rotation of the matcher's root layer
+  // (hip_store_rotation_scans; request k takes the slots first_scan_slot + k * rotations ...)
   HipM3rsmEngine(slamhip_ctx *ctx, slamhip_matcher *matcher, std::shared_ptr<ScanProbabilityEstimator> spe,
-                 int weighting = 0, const HipScanTrig &trig = HipScanTrig{}, int first_scan_slot = 0)
-      : _ctx{ctx}, _matcher{matcher}, _spe{spe}, _weighting{weighting}, _trig{trig}, _first_slot{first_scan_slot} {}
+                 int weighting = 0, const HipScanTrig &trig = HipScanTrig{}, int first_scan_slot = 0,
+                 std::shared_ptr<ScanPointWeighting> rotation_spw = nullptr)
+      : _ctx{ctx}, _matcher{matcher}, _spe{spe}, _weighting{weighting}, _trig{trig}, _first_slot{first_scan_slot},
+        _rot_spw{rotation_spw} {
+    slamhip_or_die(slamhip_matcher_set_m3rsm_rotation_slots(matcher, rotation_spw ? 1 : 0), "set_m3rsm_rotation_slots");
+    if (rotation_spw) slamhip_or_die(slamhip_matcher_m3rsm_rotations(matcher, 0, nullptr, &_slots_per_request), "m3rsm_rotations");
+  }
 
   void reset_engine_state() { _requests.clear(); }
 
   // the scan is filtered by the estimator against the map's fine level, as add_scan_matching_request does, and stored
   void add_scan_matching_request(const RobotPose &pose, const LaserScan2D &raw_scan, HipM3rsmMap &map) {
     const LaserScan2D scan = _spe->filter_scan(raw_scan, pose, map.map());
+    if (_rot_spw) {
+      slamhip_m3rsm_request q;
+      q.pyramid = map.pyramid();
+      q.scan_slot = _first_slot + int(_requests.size()) * _slots_per_request;
+      q.init_pose[0] = pose.x;
+      q.init_pose[1] = pose.y;
+      q.init_pose[2] = pose.theta;
+      hip_store_rotation_scans(_ctx, _matcher, scan, pose.theta, *_rot_spw, _trig, q.scan_slot);
+      _requests.push_back(q);
+      return;
+    }
     const auto &pts = scan.points();
     const int n = int(pts.size());
     std::vector<double> r(n), a(n), f(n), w(n), c(n), s(n);
@@ -191,6 +240,8 @@ private:
   int _weighting;
   HipScanTrig _trig;
   int _first_slot;
+  std::shared_ptr<ScanPointWeighting> _rot_spw;
+  int _slots_per_request = 1;
   std::vector<slamhip_m3rsm_request> _requests;
 };
 

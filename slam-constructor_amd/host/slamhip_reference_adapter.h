@@ -353,6 +353,42 @@ inline void hip_upload_filtered_scan(slamhip_ctx *ctx, const LaserScan2D &scan, 
   slamhip_or_die(slamhip_scan_set_angles(ctx, n, a.data()), "scan_set_angles");
 }
 
+// BF_M3RSM under a weighting that reads a point's direction (VinySlamSPW, AngleHistogramReciprocalSPW).  The reference's
+// matcher hands its estimator PREROTATED scans -- fscan->to_cartesian(rot + pose.theta), m3rsm_engine.h:305-308 -- so
+// ScanPointWeighting::weight sees a Cartesian point in the world's orientation and the weights turn with the candidate's
+// rotation.  For every rotation of the matcher's root layer (slamhip_matcher_m3rsm_rotations) the filtered scan is turned
+// by the reference's own to_cartesian under the scan's own trig provider, weighed by the reference's own weighting, and
+// stored -- the same points, that rotation's weights, the points' angles -- in slot first_slot + j
+// (slamhip_matcher_set_m3rsm_rotation_slots).  Returns the number of slots written (0: the scan has no point).
+inline int hip_store_rotation_scans(slamhip_ctx *ctx, slamhip_matcher *m, const LaserScan2D &scan, double heading,
+                                    ScanPointWeighting &spw, const HipScanTrig &trig, int first_slot) {
+  const auto &pts = scan.points();
+  const int n = int(pts.size());
+  if (n == 0) return 0;
+  std::vector<double> r(n), a(n), f(n), w(n), c(n), s(n);
+  for (int i = 0; i < n; ++i) {
+    r[i] = pts[i].range();
+    a[i] = pts[i].angle();
+    f[i] = pts[i].factor();
+  }
+  if (trig.mode == SLAMHIP_TRIG_CACHED)
+    slamhip_or_die(slamhip_beam_trig_cached(n, a.data(), trig.a_min, trig.a_max, trig.a_inc, c.data(), s.data()), "beam_trig_cached");
+  else
+    slamhip_or_die(slamhip_beam_trig_raw(n, a.data(), c.data(), s.data()), "beam_trig_raw");
+  int n_rot = 0;
+  slamhip_or_die(slamhip_matcher_m3rsm_rotations(m, 0, nullptr, &n_rot), "m3rsm_rotations");
+  std::vector<double> rot(n_rot);
+  slamhip_or_die(slamhip_matcher_m3rsm_rotations(m, n_rot, rot.data(), &n_rot), "m3rsm_rotations");
+  spw.reset(scan);  // (filter_scan resets the estimator's weighting on the filtered scan, before any rotation)
+  for (int j = 0; j < n_rot; ++j) {
+    const LaserScan2D turned = scan.to_cartesian(rot[j] + heading);
+    for (int i = 0; i < n; ++i) w[i] = spw.weight(turned.points(), i);
+    slamhip_or_die(slamhip_scan_store(ctx, first_slot + j, n, r.data(), c.data(), s.data(), w.data(), f.data()), "scan_store");
+    slamhip_or_die(slamhip_scan_store_angles(ctx, first_slot + j, n, a.data()), "scan_store_angles");
+  }
+  return n_rot;
+}
+
 // ------------------------------------------------------------------------------------------------
 class HipGridScanMatcher;
 // One of K raw scans matched in one library call (hip_process_raw_scans below): `owner` is the robot's own matcher --
@@ -397,8 +433,18 @@ public:
     _own_filter = true;
   }
 
+  // BF_M3RSM with a weighting other than `even`: weights per candidate rotation (hip_store_rotation_scans), the match a
+  // one-request slamhip_matcher_m3rsm_match_many over `pyramid`; the scans take the slots first_slot ...
+  void set_m3rsm_rotation_weights(std::shared_ptr<ScanPointWeighting> spw, slamhip_pyramid *pyramid, int first_slot) {
+    _rot_spw = spw;
+    _rot_pyr = pyramid;
+    _rot_first_slot = first_slot;
+    slamhip_or_die(slamhip_matcher_set_m3rsm_rotation_slots(_m, spw ? 1 : 0), "set_m3rsm_rotation_slots");
+  }
+
   double process_scan(const TransformedLaserScan &raw_scan, const RobotPose &init_pose,
                       const GridMap &map, RobotPoseDelta &pose_delta) override {
+    if (_rot_spw) return process_scan_rotation_weights(raw_scan, init_pose, map, pose_delta);
     int n_obs = 0;
     do_for_each_observer([&](ObsPtr) { ++n_obs; });
     // (the fast path restates WeightedMeanPointProbabilitySPE's filter_scan / should_skip_point inside the library: it is
@@ -448,6 +494,31 @@ private:
     *prob = std::numeric_limits<double>::quiet_NaN();
   }
   long _n_failures = 0;
+
+  double process_scan_rotation_weights(const TransformedLaserScan &raw_scan, const RobotPose &init_pose, const GridMap &map,
+                                       RobotPoseDelta &pose_delta) {
+    do_for_each_observer([&](ObsPtr obs) { obs->on_matching_start(init_pose, raw_scan, map); });
+    _scan = filter_scan(raw_scan.scan, init_pose, map);
+    _mirror->sync(map, _dirty_source);
+    pose_delta = RobotPoseDelta{0, 0, 0};
+    // (no usable point: the reference's estimate is NaN for every candidate, nothing is found)
+    if (!hip_store_rotation_scans(_ctx, _m, _scan, init_pose.theta, *_rot_spw, _trig, _rot_first_slot))
+      return std::numeric_limits<double>::quiet_NaN();
+    slamhip_observer o{this, &on_test, &on_update, nullptr};
+    slamhip_or_die(slamhip_matcher_set_observer(_m, &o), "set_observer");
+    slamhip_m3rsm_request q;
+    q.pyramid = _rot_pyr;
+    q.scan_slot = _rot_first_slot;
+    q.init_pose[0] = init_pose.x;
+    q.init_pose[1] = init_pose.y;
+    q.init_pose[2] = init_pose.theta;
+    int which = -1;
+    double d[3] = {0, 0, 0}, prob = 0;
+    slamhip_or_die(slamhip_matcher_m3rsm_match_many(_m, 1, &q, &which, d, &prob), "m3rsm_match_many");
+    pose_delta = RobotPoseDelta{d[0], d[1], d[2]};
+    if (which >= 0) do_for_each_observer([&](ObsPtr obs) { obs->on_matching_end(pose_delta, _scan, prob); });
+    return prob;
+  }
 
   bool spe_is_plain_wmpp() const {
     const auto spe = scan_probability_estimator();
@@ -503,6 +574,9 @@ private:
   int _weighting;
   HipScanTrig _trig;
   const HipMirroredGridMap *_dirty_source = nullptr;
+  std::shared_ptr<ScanPointWeighting> _rot_spw;
+  slamhip_pyramid *_rot_pyr = nullptr;
+  int _rot_first_slot = 0;
   LaserScan2D _scan;
   bool _own_filter = false, _bounded = false;
   unsigned _skip_rate = 0;
