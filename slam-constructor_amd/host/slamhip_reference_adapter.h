@@ -592,6 +592,10 @@ private:
 // result of its owner's process_raw_scan, bit for bit.  All owners live on `matcher`'s context and have been given
 // their filter parameters (set_filter_params); nobody listens (observers are not called).  A run-time failure is
 // handled as process_scan handles it: once more on the chain of kernels, then every job reports "unknown".
+// Preconditions the library checks before anything is launched, and which end the process here like any configuration
+// error: the maps of one call share ONE cell model (mean_probability and affine_quality_merge maps go together, a TBM
+// map does not join them), and every job is scored under `matcher`'s estimator configuration (OOPE, OIE, strict) -- an
+// owner contributes its map, filter parameters, trig provider and weighting, not its own matcher's.
 inline void hip_process_raw_scans(HipGridScanMatcher &matcher, std::vector<HipRawScanJob> &jobs) {
   const int K = (int)jobs.size();
   if (K == 0) return;
