@@ -821,7 +821,8 @@ int slamhip_matcher_batch_stats(slamhip_matcher *m, int job, long long *scorer_c
  *  - A job whose filter keeps no point is what the lone call makes of it: probability NaN, delta 0, no observer call.
  *    It takes no part in the launches; the other jobs are unaffected.
  *  - Jobs the chains do not cover run one after another through the lone raw call, in job order (a Monte-Carlo
- *    matcher's engine stream is that of the sequence of lone calls): a matcher that is not hill climbing, a window or
+ *    matcher's engine stream is that of the sequence of lone calls, unless it has engine streams of its own:
+ *    slamhip_matcher_set_mc_streams below): a matcher that is neither hill climbing nor Monte Carlo with streams, a window or
  *    GMapping OOPE, the beam-order sum, a job with more than 4096 kept points, n_jobs == 1 (or one non-empty job).
  *  - Errors are those of slamhip_matcher_process_scan_batch and of the lone raw call -- unknown map, maps of different
  *    cell models (or GMAPPING cells) in the shared launches, a trig_mode that is neither provider, an angle outside
@@ -842,6 +843,40 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
  * five rows of cap doubles (cap 0: only *n).  A job that went through the lone call has no block in the batch's arena:
  * *n is set, asking for the rows is an error. */
 int slamhip_matcher_batch_scan_download(slamhip_matcher *m, int job, int cap, double *out5, int *n);
+/* K robots' engines on ONE Monte-Carlo matcher.  In the reference every robot owns its matcher and with it an engine of
+ * its own seed (init_scan_matching.h:118-135); a matcher has one std::mt19937, never reseeded, so the batch calls above
+ * run a Monte-Carlo matcher's jobs one after another on that one engine.  With streams set, the two batch calls run job
+ * j on ITS stream -- in shared launches (grid.y = job, one kernel = one super-step of every chain still alive), at most
+ * S = min(511, failed limit, attempts limit, 2048 / K - 1) candidates per job and super-step (a speed knob: results do
+ * not depend on it) -- and job j gets the result, the observer sequence and the counters of a lone matcher created with
+ * seeds[stream] and fed that stream's jobs in order, bit for bit.
+ *  - Stream k is what slamhip_matcher_create_mc(..., seeds[k], ...) with this matcher's dispersions and limits would
+ *    own: GaussianPoseEnumerator{mt19937(seed)} (monte_carlo_scan_matcher.h:14-37).  It is never reseeded and carries on
+ *    from batch call to batch call.  n_streams = 0 removes the streams; setting them anew restarts all of them and drops
+ *    the job mapping.  A matcher that is not Monte Carlo: SLAMHIP_ERR_INVALID.
+ *  - slamhip_matcher_reset_state resets every stream's enumerator as it resets the matcher's own; the engines stay
+ *    where they are.
+ *  - A matcher without streams behaves in every entry point as it did before these calls existed; a matcher with
+ *    streams changes only the two batch calls: lone slamhip_matcher_process_scan / _process_raw_scan keep using the
+ *    matcher's own engine.
+ *  - The shared launches cover what the lone Monte-Carlo chain covers (1-cell OOPE, device pose trigonometry, maps of one
+ *    cell model) in the default sum order.  Jobs they do not cover run the lone path ON THEIR OWN STREAM, in job order:
+ *    the beam-order sum, more than 4096 kept points, an observer trace that outgrows its buffer, n_jobs == 1 (or one
+ *    non-empty job).  A job's result never depends on the route; slamhip_matcher_batch_stats says which it took.
+ *  - A raw job whose filter keeps nothing does not advance its stream (NaN, zero delta, no observer call).
+ *  - Errors found before anything is launched -- unknown map, maps of different cell models, a bad stream mapping, null
+ *    arrays -- leave every stream and the last-batch state untouched.  After a HIP failure in flight the streams'
+ *    positions are unspecified. */
+int slamhip_matcher_set_mc_streams(slamhip_matcher *m, int n_streams, const unsigned *seeds);
+/* which stream job j of the NEXT batch calls uses.  NULL or n = 0: identity (job j on stream j).  Two jobs on one stream,
+ * a stream out of range, more jobs than streams: SLAMHIP_ERR_INVALID, here (the mapping stays what it was) and again in a
+ * batch call with more jobs than the mapping names -- before anything is staged or launched, no stream touched. */
+int slamhip_matcher_set_mc_job_streams(slamhip_matcher *m, int n, const int *stream_of_job);
+/* a stream's engine and enumerator: absolute position on its pair tape (Marsaglia pairs drawn since the seed), matches
+ * run on it, and state5 = (failed, poses, translation dispersion, rotation dispersion, has_saved) -- may be NULL.
+ * stream = -1: the matcher's own enumerator, the one the lone calls use. */
+int slamhip_matcher_mc_stream_info(slamhip_matcher *m, int stream, unsigned long long *pairs_consumed,
+                                   long long *matches, double *state5);
 /* counters of the last process_scan: scorer calls the reference would have made
  * (= on_scan_test events), poses actually evaluated on the GPU, launches */
 int slamhip_matcher_stats(slamhip_matcher *m, long long *scorer_calls, long long *poses_evaluated,

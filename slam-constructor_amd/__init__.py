@@ -71,7 +71,8 @@ slamhip_matcher_m3rsm_match_each slamhip_matcher_m3rsm_trace_each slamhip_matche
 slamhip_matcher_set_m3rsm_threads slamhip_matcher_m3rsm_copied_back
 slamhip_matcher_m3rsm_rotations slamhip_matcher_set_m3rsm_rotation_slots
 slamhip_scan_table_uploads slamhip_scan_download
-slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download""".split()
+slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download
+slamhip_matcher_set_mc_streams slamhip_matcher_set_mc_job_streams slamhip_matcher_mc_stream_info""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -310,6 +311,9 @@ def load(testing=False):
     L.slamhip_matcher_m3rsm_rotations.argtypes = [vp, i, _dp, _ip]
     L.slamhip_matcher_set_m3rsm_rotation_slots.argtypes = [vp, i]
     L.slamhip_matcher_m3rsm_copied_back.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.slamhip_matcher_set_mc_streams.argtypes = [vp, i, up]
+    L.slamhip_matcher_set_mc_job_streams.argtypes = [vp, i, _ip]
+    L.slamhip_matcher_mc_stream_info.argtypes = [vp, i, C.POINTER(C.c_ulonglong), ll, _dp]
     _libs[testing] = L
     return L
 
@@ -1106,6 +1110,34 @@ class Matcher:
                          accepted=np.array(r["accepted"], dtype=np.int32), n_calls=len(r["scores"]))
             out.append(o)
         return out
+
+    def set_mc_streams(self, seeds):
+        """K robots' engines on this Monte-Carlo matcher (slamhip_matcher_set_mc_streams): stream k is the enumerator a
+        matcher created with seeds[k] would own; the batch calls then run job j on its stream.  An empty list removes
+        the streams."""
+        arr = (C.c_uint * max(1, len(seeds)))(*[int(v) for v in seeds])
+        _check(self.L.slamhip_matcher_set_mc_streams(self.h, len(seeds), arr))
+
+    def set_mc_job_streams(self, streams=None):
+        """Which stream job j of the next batch calls uses (None: job j on stream j)."""
+        if not streams:
+            _check(self.L.slamhip_matcher_set_mc_job_streams(self.h, 0, None))
+            return
+        arr = (C.c_int * len(streams))(*[int(v) for v in streams])
+        _check(self.L.slamhip_matcher_set_mc_job_streams(self.h, len(streams), arr))
+
+    def mc_stream_info(self, stream=-1):
+        """Engine position (pairs of the tape consumed since the seed), matches run and the enumerator's state of a
+        stream; -1: the matcher's own engine, the one the lone calls use."""
+        pairs, matches, st = C.c_ulonglong(), C.c_longlong(), (C.c_double * 5)()
+        _check(self.L.slamhip_matcher_mc_stream_info(self.h, int(stream), C.byref(pairs), C.byref(matches), st))
+        return dict(pairs_consumed=pairs.value, matches=matches.value, failed=int(st[0]), poses=int(st[1]), td=st[2],
+                    rd=st[3], has_saved=bool(st[4]))
+
+    def chain_stats(self):
+        kl, rs = C.c_longlong(), C.c_longlong()
+        _check(self.L.slamhip_matcher_chain_stats(self.h, C.byref(kl), C.byref(rs)))
+        return dict(kernels_launched=kl.value, steps_rescored=rs.value)
 
     def batch_stats(self, job):
         a, b, c, d = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_int()

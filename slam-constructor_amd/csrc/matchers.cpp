@@ -162,6 +162,25 @@ struct HcBatch : slamhip::ChainSet<slamhip::HcResidentCtl, slamhip::HcJobView> {
   std::vector<RawBlock> raw_blocks;
 };
 
+// K Monte-Carlo matches per call (mc_batch_run): per-chain control / result blocks, the staged job table, the ONE arena
+// the jobs' tape windows go through, the observer's trace slices
+struct McBatch {
+  int cap = 0;  // chains the blocks hold
+  slamhip::DeviceBuf<slamhip::McChainCtl> d_ctl;
+  slamhip::PinnedBuf<slamhip::McHostOut> h_out;
+  slamhip::StageBlock<slamhip::McJobView> stage;
+  slamhip::PinnedBuf<unsigned> h_done_count;
+  slamhip::DeviceBuf<slamhip::McPair> d_tape;
+  slamhip::PinnedBuf<double> h_tape;
+  size_t tape_cap = 0;  // pairs
+  slamhip::PinnedBuf<slamhip::McTraceEntry> h_trace;  // trace_chains x trace_per entries (observer attached only)
+  size_t trace_per = 0;
+  int trace_chains = 0;
+  unsigned epoch = 0;
+  double kernels_avg = 6.0;  // kernels the longest chain of a call needed, smoothed: sizes the first burst
+  int slots = 0;             // candidates per job and super-step of the last call
+};
+
 struct slamhip_matcher {
   // ---- what every kind of matcher has
   slamhip_ctx *ctx = nullptr;
@@ -233,12 +252,24 @@ struct slamhip_matcher {
     size_t tape_filled = 0;             // pairs of the window already in HBM (or on their way, see tape_ready)
     hipStream_t tape_stream = nullptr;  // uploads the next match's pairs while this match's chain runs
     hipEvent_t tape_ready = nullptr;
+    const void *tape_owner = nullptr;   // the enumerator whose tape the window holds (an engine stream may be swapped in)
     int slots = 0;
     ~McChain() {
       if (tape_stream) hipStreamDestroy(tape_stream);
       if (tape_ready) hipEventDestroy(tape_ready);
     }
   } mc;
+  // ---- K robots' engines on one Monte-Carlo matcher (slamhip_matcher_set_mc_streams): stream k is the enumerator a
+  // matcher created with seeds[k] would own, never reseeded, carried on from batch call to batch call
+  struct McStream {
+    std::unique_ptr<slamhip::PoseEnumerator> pe;  // a GaussianPoseEnumerator
+    long long matches = 0;
+  };
+  std::vector<McStream> mc_streams;
+  std::vector<int> mc_job_streams;  // stream of job j of the next batch calls (empty: job j uses stream j)
+  long long mc_matches = 0;         // matches run on the matcher's own engine
+  std::unique_ptr<McBatch> mc_batch;
+  int debug_mc_batch_slots = 0;  // testing (slamhip_matcher_testing_mc_batch_slots): candidates per job and super-step
   // ---- brute force as one flat sweep + a device arg-max (bf_device.hip)
   struct BfSweep {
     double r[9] = {0};
@@ -1606,8 +1637,10 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
     mc.tape_filled += cnt;
     return SLAMHIP_OK;
   };
-  if (!mc.d_tape || pos < mc.tape_base || pos + need > mc.tape_base + mc.tape_cap) {
-    // (re)start the window at the current position
+  if (!mc.d_tape || mc.tape_owner != pe || pos < mc.tape_base || pos + need > mc.tape_base + mc.tape_cap) {
+    // (re)start the window at the current position (of THIS enumerator's tape: a batch call's fall-back runs a job on
+    // its engine stream, swapped in for the call)
+    mc.tape_owner = pe;
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
     SLAMHIP_CHECK(hipStreamSynchronize(mc.tape_stream));
     const size_t cap = std::max<size_t>(64 * need, 1 << 16);
@@ -1735,6 +1768,257 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
   m->tail_calls = 0;
   return lone_chain_report(m, h, launched, a.scan.n, t0, init_pose, out_delta, out_prob);
 }
+
+// ---- K independent Monte-Carlo matches in shared launches -----------------------------------------
+// MonteCarloScanMatcher::process_scan once per robot, every robot on ITS engine (init_scan_matching.h:118-135: each
+// matcher object owns a GaussianPoseEnumerator{mt19937(seed)}): match c = (scan c, initial pose c, map c, stream c).
+// A lone match at the reference's preset (20 failed / 100 poses) can speculate on at most 20 candidates per super-step,
+// so K chains advancing together -- one kernel = one super-step of every chain still alive, grid.y = chain -- are what
+// fills the device.  The driver is run_many_chains' burst pattern: kernels queued in bursts, each closed by the marker,
+// the next burst queued before the wait.
+
+// the matcher-level conditions of the shared Monte-Carlo launches: mc_chain_eligible's (without the context's current
+// scan, which a batch does not use) and the canonical sum -- the beam-order sum stays with the lone route
+bool mc_batch_eligible(slamhip_matcher *m) {
+  if (!m->is_mc || m->mc_streams.empty()) return false;
+  if (m->cfg.oope != SLAMHIP_OOPE_OBSTACLE || m->cfg.pose_trig != SLAMHIP_POSE_TRIG_DEVICE) return false;
+  if (m->cfg.sum_order != SLAMHIP_SUM_TREE256) return false;
+  if (!m->ctx->low_latency || m->ctx->stage_poses) return false;
+  if (m->max_batch < 64) return false;
+  if (m->chain_mode < 0) m->chain_mode = kChainDefaultMode;
+  return m->chain_mode >= 1;
+}
+
+// Workgroups per launch over all chains: the element-wise rule of thumb (about 2048 blocks keep every CU of an MI355X
+// busy with several workgroups without a long tail).  Candidates per job and super-step:
+//   S = min(kMcSlots, max_failed, max_poses, kMcBatchWgs / K - 1)
+// -- slots beyond max_failed (or max_poses) can never hold a candidate (mc_available), and K x (S + 1) workgroups stay
+// within the budget.  A speed knob only: the replay consumes min(available, S) candidates whatever S is.
+constexpr int kMcBatchWgs = 2048;
+
+int mc_batch_slots(const slamhip_matcher *m, int n, unsigned max_failed, unsigned max_poses) {
+  if (m->debug_mc_batch_slots > 0) return std::min(kMcSlots, m->debug_mc_batch_slots);
+  long long s = std::min<long long>(kMcSlots, std::min<long long>(max_failed, max_poses));
+  s = std::min<long long>(s, kMcBatchWgs / n - 1);
+  return (int)std::max<long long>(1, s);
+}
+
+// pairs of the tape one match can consume (mc_chain_process_scan: three pairs per two candidates, every reset_shift may
+// drop a triple's second half)
+size_t mc_tape_need(const GaussianPoseEnumerator *pe) {
+  const size_t max_poses = pe->max_poses();
+  const size_t resets = max_poses / (pe->max_failed() / 3 + 1) + 2;
+  return 3 * (max_poses / 2 + 2 + resets) + 8;
+}
+
+// The shared launches over n matches whose scans lie in HBM (blocks); job c gives its map and initial pose and runs on
+// engine stream streams[c].  Results go to m->batch->res[c]; a chain whose trace outgrew its slice is left to the lone
+// route (on_chain false, its stream as it was).
+template <class Job>
+int mc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBlock *blocks, const int *streams,
+                 int cell_model) {
+  slamhip_ctx *ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  if (!m->mc_batch) m->mc_batch = std::make_unique<McBatch>();
+  McBatch *s = m->mc_batch.get();
+  auto stream_pe = [&](int c) { return static_cast<GaussianPoseEnumerator *>(m->mc_streams[streams[c]].pe.get()); };
+  const GaussianPoseEnumerator *pe0 = stream_pe(0);
+  const unsigned max_failed = pe0->max_failed(), max_poses = pe0->max_poses();
+  const size_t need = mc_tape_need(pe0);
+  if (!s->h_done_count) SLAMHIP_CHECK(s->h_done_count.alloc(1, kPinnedCoherent));
+  if (n > s->cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+    int cap = 8;
+    while (cap < n) cap *= 2;
+    s->cap = 0;
+    SLAMHIP_CHECK(s->d_ctl.alloc(cap));
+    SLAMHIP_CHECK(hipMemsetAsync(s->d_ctl.get(), 0, sizeof(McChainCtl) * cap, st));
+    SLAMHIP_CHECK(s->h_out.alloc(cap, kPinnedCoherent));
+    std::memset(s->h_out.get(), 0, sizeof(McHostOut) * cap);
+    const int rc = s->stage.alloc(cap, st);
+    if (rc) return rc;
+    s->cap = cap;
+  }
+  if ((size_t)n * need > s->tape_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+    size_t cap = 1 << 14;
+    while (cap < (size_t)n * need) cap *= 2;
+    s->tape_cap = 0;
+    static_assert(sizeof(McPair) == 2 * sizeof(double), "the pinned staging holds pairs as two doubles");
+    SLAMHIP_CHECK(s->d_tape.alloc(cap));
+    SLAMHIP_CHECK(s->h_tape.alloc(2 * cap, hipHostMallocDefault));
+    s->tape_cap = cap;
+  }
+  const size_t trace_need = (size_t)max_poses + 2;
+  if (m->has_obs && (s->trace_chains < s->cap || s->trace_per < trace_need)) {
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+    s->trace_chains = 0;
+    SLAMHIP_CHECK(s->h_trace.alloc(trace_need * (size_t)s->cap, kPinnedCoherent));
+    s->trace_per = trace_need;
+    s->trace_chains = s->cap;
+  }
+  // every job's enumerator starts its match (pose_enumeration_scan_matcher.h:47); the windows of the K tapes in ONE
+  // arena, one copy (the arena is free: the call before returned after its chains had ended)
+  int max_n = 0;
+  for (int c = 0; c < n; ++c) {
+    GaussianPoseEnumerator *pe = stream_pe(c);
+    pe->reset();
+    pe->copy_tape_abs(pe->tape_pos(), need, s->h_tape.get() + 2 * need * (size_t)c);
+    max_n = std::max(max_n, blocks[c].n);
+  }
+  SLAMHIP_CHECK(hipMemcpyAsync(s->d_tape.get(), s->h_tape.get(), sizeof(McPair) * need * (size_t)n, hipMemcpyHostToDevice, st));
+  for (int c = 0; c < n; ++c) {
+    const Job &j = jobs[c];
+    const DeviceMap *dm = &ctx->maps[j.map_id];
+    McJobView &v = s->stage.h_table()[c];
+    v.map.payload = dm->d_payload;
+    v.map.width = dm->width;
+    v.map.height = dm->height;
+    v.map.pitch = dm->pitch;
+    v.map.origin_x = dm->origin_x;
+    v.map.origin_y = dm->origin_y;
+    v.map.scale = dm->scale;
+    v.map.inv_scale = 1.0 / dm->scale;
+    for (int q = 0; q < 4; ++q) v.map.unknown[q] = dm->unknown[q];
+    const double *ds = blocks[c].d;
+    const size_t stride = blocks[c].stride;
+    v.scan.n = blocks[c].n;
+    v.scan.tot_w = blocks[c].tot_w;
+    v.scan.range = ds;
+    v.scan.cos_a = ds + stride;
+    v.scan.sin_a = ds + 2 * stride;
+    v.scan.weight = ds + 3 * stride;
+    v.scan.factor = ds + 4 * stride;
+    v.tape = s->d_tape.get() + need * (size_t)c;
+    for (int q = 0; q < 3; ++q) v.init[q] = j.init_pose[q];
+    v.trace = m->has_obs ? s->h_trace.get() + s->trace_per * (size_t)c : nullptr;
+  }
+  // (counter = 0, job table with the initial poses: one pull of the pinned block)
+  SLAMHIP_CHECK(launch_block_pull(s->stage.h.get(), s->stage.d.get(), s->stage.bytes_upto_table(n), st));
+  McChainArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.jobs = s->stage.d_table();
+  a.n_done = s->stage.d_n_done();
+  a.scan.n = max_n;  // (the launch's LDS size)
+  a.oie = m->cfg.oie;
+  a.verify = tie_check_default(m) ? 1 : 0;
+  a.ctl = s->d_ctl.get();
+  a.n_slots = s->slots = mc_batch_slots(m, n, max_failed, max_poses);
+  a.td0 = pe0->base_td();
+  a.rd0 = pe0->base_rd();
+  a.max_failed = max_failed;
+  a.max_poses = max_poses;
+  a.epoch = next_epoch(s->epoch);
+  a.host = s->h_out.get();
+  a.trace_cap = m->has_obs ? (int)s->trace_per : 0;
+  if (m->has_obs && m->debug_trace_cap > 0) a.trace_cap = std::min(a.trace_cap, m->debug_trace_cap);
+  volatile McHostOut *h_out = s->h_out.get();
+  for (int c = 0; c < n; ++c) {
+    h_out[c].error = 0;
+    h_out[c].progress = 0;
+  }
+  int launched = 0;
+  auto burst = [&](int count, unsigned *seq_out) -> int {
+    for (int i = 0; i < count; ++i) {
+      hipEvent_t e0, e1;
+      const int r = profile_event_pair(ctx, &e0, &e1);
+      if (r) return r;
+      SLAMHIP_CHECK(launch_mc_chain_step(a, cell_model, launched, m->chain_nt, st, e0, e1, n));
+      ++launched;
+    }
+    const unsigned seq = next_epoch(ctx->seq);
+    SLAMHIP_CHECK(launch_chain_marker(s->stage.d_n_done(), s->h_done_count.get(), ctx->h_done_flag, seq, st));
+    *seq_out = seq;
+    return SLAMHIP_OK;
+  };
+  unsigned seq_prev = 0, seq_next = 0;
+  int rc = burst(std::max(2, (int)(s->kernels_avg * 0.9)), &seq_prev);
+  if (rc) return rc;
+  for (;;) {
+    rc = burst(2, &seq_next);  // queued before the wait: the GPU never runs dry
+    if (rc) return rc;
+    rc = score_wait(ctx, seq_prev);
+    if (rc) return rc;
+    if (*(volatile unsigned *)s->h_done_count.get() >= (unsigned)n) break;
+    if (launched >= (1 << 16)) {
+      set_error("the batch's Monte-Carlo chains did not end");
+      return SLAMHIP_ERR_STATE;
+    }
+    seq_prev = seq_next;
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  HcBatch *b = m->batch.get();
+  long long units = 0;
+  int max_steps = 0;
+  for (int c = 0; c < n; ++c) {
+    const volatile McHostOut *h = &h_out[c];
+    if (h->done_seq != a.epoch) {
+      set_error("internal: a Monte-Carlo chain was counted as finished without publishing its result");
+      return SLAMHIP_ERR_STATE;
+    }
+    max_steps = std::max(max_steps, (int)h->steps);
+    BatchJobResult &r = b->res[c];
+    r.error = h->error;
+    r.on_chain = h->error == 0;
+    units += h->evaluated * (long long)blocks[c].n;
+    if (!r.on_chain) continue;  // (2: the trace outgrew its slice -- nothing reported, the stream not advanced)
+    if ((size_t)h->tape_pos + 3 > need) {
+      set_error("internal: a Monte-Carlo chain ran past the uploaded window of its pair tape");
+      return SLAMHIP_ERR_STATE;
+    }
+    const double saved[3] = {h->saved[0], h->saved[1], h->saved[2]};
+    GaussianPoseEnumerator *pe = stream_pe(c);
+    pe->set_chain_result((size_t)h->tape_pos, h->failed, h->poses, h->td, h->rd, h->has_saved != 0, saved);
+    pe->trim();
+    ++m->mc_streams[streams[c]].matches;
+    for (int q = 0; q < 3; ++q) r.pose[q] = h->pose[q];
+    r.prob = h->best_prob;
+    r.calls = h->calls;
+    r.evaluated = h->evaluated;
+    r.rescored = h->rescored;
+    r.steps = h->steps;
+  }
+  s->kernels_avg = 0.75 * s->kernels_avg + 0.25 * (double)(max_steps + 1);
+  b->kernels = launched;
+  if (ctx->profile) {
+    ctx->prof_launches += launched;
+    ctx->prof_units += units;
+  }
+  return SLAMHIP_OK;
+}
+
+// the engine stream of every job of a batch call (slamhip_matcher_set_mc_job_streams; none set: job j on stream j),
+// checked before anything is staged or launched
+int mc_job_streams_of(const slamhip_matcher *m, int n_jobs, std::vector<int> *out) {
+  const int ns = (int)m->mc_streams.size();
+  if (n_jobs > ns) return invalid_arg("more jobs than engine streams (slamhip_matcher_set_mc_streams)");
+  if (!m->mc_job_streams.empty() && n_jobs > (int)m->mc_job_streams.size())
+    return invalid_arg("more jobs than slamhip_matcher_set_mc_job_streams named streams for");
+  out->resize(n_jobs);
+  std::vector<char> used(ns, 0);
+  for (int c = 0; c < n_jobs; ++c) {
+    const int k = m->mc_job_streams.empty() ? c : m->mc_job_streams[c];
+    if (k < 0 || k >= ns) return invalid_arg("a job's engine stream is out of range");
+    if (used[k]) return invalid_arg("two jobs of one batch on the same engine stream");
+    used[k] = 1;
+    (*out)[c] = k;
+  }
+  return SLAMHIP_OK;
+}
+
+// a batch call's fall-back: the lone path on the job's OWN stream -- its enumerator (and match count) in the matcher's
+// place for the call
+struct McStreamSwap {
+  slamhip_matcher *m;
+  int k;
+  McStreamSwap(slamhip_matcher *m_, int k_) : m(m_), k(k_) { swap(); }
+  ~McStreamSwap() { swap(); }
+  void swap() {
+    if (k < 0) return;
+    std::swap(m->pe, m->mc_streams[k].pe);
+    std::swap(m->mc_matches, m->mc_streams[k].matches);
+  }
+};
 
 // ---- the multi-resolution matcher ------------------------------------------------------------------
 // BruteForceMultiResolutionScanMatcher::process_scan: the engine's loop on the host, its scores from the pyramid -- the
@@ -2287,6 +2571,7 @@ int slamhip_matcher_destroy(slamhip_matcher *m) {
 int slamhip_matcher_reset_state(slamhip_matcher *m) {
   if (!m) return invalid_arg("null matcher");
   if (m->pe) m->pe->reset();  // (the multi-resolution matcher keeps no state between matches)
+  for (slamhip_matcher::McStream &k : m->mc_streams) k.pe->reset();  // (the engines' positions stay)
   return SLAMHIP_OK;
 }
 
@@ -2353,23 +2638,45 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
       return invalid_arg("bad scan in a match job");
     }
   }
+  // a Monte-Carlo matcher with engine streams: job c runs on ITS stream, in the shared launches or through the lone
+  // path.  Everything that can be refused is refused here, before a stream or the last-batch state is touched.
+  const bool mc_streams = m->is_mc && !m->mc_streams.empty();
+  std::vector<int> sid;
+  bool chains = n_jobs > 1 && (mc_streams ? mc_batch_eligible(m) : batch_chain_eligible(m));
+  for (int c = 0; c < n_jobs && chains; ++c)
+    chains = (jobs[c].scan_slot >= 0 ? ctx->scan_slots[jobs[c].scan_slot].n : jobs[c].n) <= 4096;
+  int cell_model = -1;
+  if (mc_streams) {
+    int rc = mc_job_streams_of(m, n_jobs, &sid);
+    if (rc) return rc;
+    for (int c = 0; c < n_jobs; ++c)
+      if (jobs[c].map_id < 0 || jobs[c].map_id >= (int)ctx->maps.size() || !ctx->maps[jobs[c].map_id].bound)
+        return invalid_arg("unknown map id in a match job");
+    if (chains) {
+      rc = batch_maps_check(ctx, n_jobs, jobs, &cell_model);
+      if (rc) return rc;
+    }
+  }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
   if (!m->batch) m->batch = std::make_unique<HcBatch>();
   HcBatch *b = m->batch.get();
   b->res.assign(n_jobs, BatchJobResult{});
   b->kernels = 0;
-  bool chains = n_jobs > 1 && batch_chain_eligible(m);
-  for (int c = 0; c < n_jobs && chains; ++c)
-    chains = (jobs[c].scan_slot >= 0 ? ctx->scan_slots[jobs[c].scan_slot].n : jobs[c].n) <= 4096;
   if (chains) {
-    int cell_model = -1;
-    int rc = batch_maps_check(ctx, n_jobs, jobs, &cell_model);
+    int rc = mc_streams ? SLAMHIP_OK : batch_maps_check(ctx, n_jobs, jobs, &cell_model);
     if (rc) return rc;
     std::vector<BatchScanBlock> blocks(n_jobs);
     rc = hc_batch_stage_scans(m, n_jobs, jobs, blocks.data());
     if (rc) return rc;
-    rc = hc_batch_run(m, n_jobs, jobs, blocks.data());
+    rc = mc_streams ? mc_batch_run(m, n_jobs, jobs, blocks.data(), sid.data(), cell_model)
+                    : hc_batch_run(m, n_jobs, jobs, blocks.data());
     if (rc) return rc;
+  }
+  const HcTraceEntry *chain_trace = b->h_trace.get();
+  size_t chain_trace_per = (size_t)b->trace_per;
+  if (mc_streams && m->mc_batch) {
+    chain_trace = reinterpret_cast<const HcTraceEntry *>(m->mc_batch->h_trace.get());
+    chain_trace_per = m->mc_batch->trace_per;
   }
   // results in job order; a match the chains did not settle (a configuration they do not cover, a trace longer
   // than a chain's buffer) goes through the single-match path: upload its scan, process_scan
@@ -2392,7 +2699,7 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
       for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
       out_probs[c] = r.prob;
       if (m->has_obs) {
-        replay_trace(m->obs, b->h_trace.get() + (size_t)c * b->trace_per, r.calls);
+        replay_trace(m->obs, chain_trace + (size_t)c * chain_trace_per, r.calls);
         if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
       }
     } else {
@@ -2405,7 +2712,10 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
       int rc = j.scan_slot >= 0 ? slamhip_scan_select(ctx, j.scan_slot)
                                 : slamhip_scan_upload(ctx, j.n, j.range, j.cos_a, j.sin_a, j.weight, j.factor);
       if (rc) return rc;
-      rc = slamhip_matcher_process_scan(m, j.map_id, j.init_pose, dl, &out_probs[c]);
+      {
+        McStreamSwap own(m, mc_streams ? sid[c] : -1);  // (the job's engine for the call)
+        rc = slamhip_matcher_process_scan(m, j.map_id, j.init_pose, dl, &out_probs[c]);
+      }
       if (rc) return rc;
       r.calls = m->job.scorer_calls;
       r.evaluated = m->job.poses_evaluated;
@@ -2451,7 +2761,60 @@ int slamhip_matcher_batch_stats(slamhip_matcher *m, int job, long long *scorer_c
   return SLAMHIP_OK;
 }
 
+int slamhip_matcher_set_mc_streams(slamhip_matcher *m, int n_streams, const unsigned *seeds) {
+  if (!m || n_streams < 0 || (n_streams > 0 && !seeds)) return invalid_arg("bad engine streams");
+  if (!m->is_mc) return invalid_arg("engine streams belong to a Monte-Carlo matcher");
+  const auto *own = static_cast<const GaussianPoseEnumerator *>(m->pe.get());
+  std::vector<slamhip_matcher::McStream> streams(n_streams);
+  for (int k = 0; k < n_streams; ++k)
+    streams[k].pe = std::make_unique<GaussianPoseEnumerator>(seeds[k], own->base_td(), own->base_rd(), own->max_failed(),
+                                                             own->max_poses());
+  m->mc_streams.swap(streams);
+  m->mc_job_streams.clear();
+  m->mc.tape_owner = nullptr;  // (the lone chain's tape window may hold a stream's pairs that is gone now)
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_set_mc_job_streams(slamhip_matcher *m, int n, const int *stream_of_job) {
+  if (!m || n < 0) return invalid_arg("bad stream mapping");
+  if (!m->is_mc) return invalid_arg("engine streams belong to a Monte-Carlo matcher");
+  if (!stream_of_job || n == 0) {
+    m->mc_job_streams.clear();
+    return SLAMHIP_OK;
+  }
+  const int ns = (int)m->mc_streams.size();
+  if (n > ns) return invalid_arg("more jobs than engine streams (slamhip_matcher_set_mc_streams)");
+  std::vector<char> used(ns, 0);
+  for (int c = 0; c < n; ++c) {
+    const int k = stream_of_job[c];
+    if (k < 0 || k >= ns) return invalid_arg("a job's engine stream is out of range");
+    if (used[k]) return invalid_arg("two jobs of one batch on the same engine stream");
+    used[k] = 1;
+  }
+  m->mc_job_streams.assign(stream_of_job, stream_of_job + n);
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_mc_stream_info(slamhip_matcher *m, int stream, unsigned long long *pairs_consumed, long long *matches,
+                                   double *state5) {
+  if (!m || !m->is_mc) return invalid_arg("engine streams belong to a Monte-Carlo matcher");
+  if (stream < -1 || stream >= (int)m->mc_streams.size()) return invalid_arg("no such engine stream");
+  const auto *pe = static_cast<const GaussianPoseEnumerator *>(stream < 0 ? m->pe.get() : m->mc_streams[stream].pe.get());
+  if (pairs_consumed) *pairs_consumed = (unsigned long long)pe->tape_pos();
+  if (matches) *matches = stream < 0 ? m->mc_matches : m->mc_streams[stream].matches;
+  if (state5) pe->state5(state5);
+  return SLAMHIP_OK;
+}
+
 #ifdef SLAMHIP_TESTING
+// testing aid, not part of include/slamhip.h: the shared Monte-Carlo launches speculate on `slots` candidates per job
+// and super-step instead of what mc_batch_slots picks (0: the rule again) -- the results must not depend on it
+// (named *_testing_*: the list of *debug* hooks of the testing library is pinned by tests/test_host_abi.py)
+int slamhip_matcher_testing_mc_batch_slots(slamhip_matcher *m, int slots) {
+  if (!m || slots < 0) return invalid_arg("bad slot count");
+  m->debug_mc_batch_slots = slots;
+  return SLAMHIP_OK;
+}
 // testing aid, not part of include/slamhip.h: the hill-climbing chain treats its observer trace buffer as `cap`
 // entries long (0 = its real size), so that the overflow path -- the match redone by the host-driven matcher --
 // can be exercised without a 65536-call match
@@ -2525,6 +2888,12 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
     if (j.map_id < 0 || j.map_id >= (int)ctx->maps.size() || !ctx->maps[j.map_id].bound)
       return invalid_arg("unknown map id in a match job");
   }
+  const bool mc_streams = m->is_mc && !m->mc_streams.empty();
+  std::vector<int> sid;
+  if (mc_streams) {  // (refused before a stream or the last-batch state is touched)
+    const int rc = mc_job_streams_of(m, n_jobs, &sid);
+    if (rc) return rc;
+  }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
   if (!m->batch) m->batch = std::make_unique<HcBatch>();
   HcBatch *b = m->batch.get();
@@ -2567,7 +2936,11 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       l.map_id = jobs[c].map_id;
       for (int q = 0; q < 3; ++q) l.init_pose[q] = jobs[c].init_pose[q];
     }
-    const bool chains = raw.n_live > 1 && raw.n_live <= 65535 && raw.max_k <= 4096 && batch_chain_eligible(m);
+    std::vector<int> live_sid(mc_streams ? raw.n_live : 0);
+    for (int c = 0; c < n_jobs && mc_streams; ++c)
+      if (raw.plan[c].live >= 0) live_sid[raw.plan[c].live] = sid[c];
+    const bool chains = raw.n_live > 1 && raw.n_live <= 65535 && raw.max_k <= 4096 &&
+                        (mc_streams ? mc_batch_eligible(m) : batch_chain_eligible(m));
     if (chains) {
       int cell_model = -1;
       rc = batch_maps_check(ctx, raw.n_live, live.data(), &cell_model);
@@ -2656,7 +3029,8 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       }
       b->res.assign(n_jobs, BatchJobResult{});
       b->kernels = 0;
-      rc = hc_batch_run(m, raw.n_live, live.data(), blocks.data());
+      rc = mc_streams ? mc_batch_run(m, raw.n_live, live.data(), blocks.data(), live_sid.data(), cell_model)
+                      : hc_batch_run(m, raw.n_live, live.data(), blocks.data());
       if (rc) return rc;
       // (the chains' results by live place -> by job)
       std::vector<BatchJobResult> by_live(b->res.begin(), b->res.begin() + raw.n_live);
@@ -2701,6 +3075,12 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
     }
     ctx->scan_angle_lazy = false;
   };
+  const HcTraceEntry *chain_trace = b->h_trace.get();
+  size_t chain_trace_per = (size_t)b->trace_per;
+  if (mc_streams && m->mc_batch) {
+    chain_trace = reinterpret_cast<const HcTraceEntry *>(m->mc_batch->h_trace.get());
+    chain_trace_per = m->mc_batch->trace_per;
+  }
   for (int c = 0; c < n_jobs; ++c) {
     BatchJobResult &r = b->res[c];
     const slamhip_raw_match_job &j = jobs[c];
@@ -2710,7 +3090,7 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
       out_probs[c] = r.prob;
       if (m->has_obs) {
-        replay_trace(m->obs, b->h_trace.get() + (size_t)raw.plan[c].live * b->trace_per, r.calls);
+        replay_trace(m->obs, chain_trace + (size_t)raw.plan[c].live * chain_trace_per, r.calls);
         if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
       }
     } else if (planned && kept == 0) {
@@ -2726,7 +3106,11 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
         saved_f = ctx->h_factor;
         fell_back = true;
       }
-      const int rc = slamhip_matcher_process_raw_scan(m, j.map_id, &j.scan, j.init_pose, dl, &out_probs[c], &kept);
+      int rc;
+      {
+        McStreamSwap own(m, mc_streams ? sid[c] : -1);  // (the job's engine for the call; not advanced when nothing is kept)
+        rc = slamhip_matcher_process_raw_scan(m, j.map_id, &j.scan, j.init_pose, dl, &out_probs[c], &kept);
+      }
       if (rc) {
         restore();
         return rc;
@@ -2859,9 +3243,19 @@ int slamhip_matcher_timing(slamhip_matcher *m, double *build_us, double *stage_u
   return SLAMHIP_OK;
 }
 
+static int process_scan_body(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
+                             double *out_prob);
+
 int slamhip_matcher_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3],
                                  double out_delta[3], double *out_prob) {
   if (!m || !init_pose || !out_delta || !out_prob) return invalid_arg("null argument");
+  const int rc = process_scan_body(m, map_id, init_pose, out_delta, out_prob);
+  if (!rc && m->is_mc) ++m->mc_matches;  // (slamhip_matcher_mc_stream_info)
+  return rc;
+}
+
+static int process_scan_body(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
+                             double *out_prob) {
   slamhip_ctx *ctx = m->ctx;
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
 #ifdef SLAMHIP_TESTING

@@ -245,6 +245,14 @@ public:
   double base_td() const { return base_td_; }
   double base_rd() const { return base_rd_; }
   size_t tape_pos() const { return pos_; }
+  // (failed, poses, td, rd, has_saved) -- slamhip_matcher_mc_stream_info; the three distributions alternate in phase
+  void state5(double out[5]) const {
+    out[0] = (double)failed_;
+    out[1] = (double)poses_;
+    out[2] = td_;
+    out[3] = rd_;
+    out[4] = rv_x_.has_saved ? 1.0 : 0.0;
+  }
   // host idle time while a chain runs on the GPU: pairs for the NEXT match
   void prefetch_ahead(size_t pairs_from_pos, int max_new) { tape_->prefetch(pos_ + pairs_from_pos, max_new); }
   // pairs [from, from + n) of the tape by absolute position (generated on demand; from >= the trimmed base)

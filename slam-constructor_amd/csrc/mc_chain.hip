@@ -10,6 +10,9 @@
 //   body              workgroup w scores candidate w of the new state (the last workgroup: the initial pose in the
 //                     first super-step, the best pose when a super-step is scored twice) with k_score_point's
 //                     arithmetic and canonical sum, so its bits equal the host-driven matcher's.
+// The BATCH instantiations run K such chains side by side, grid.y = chain: every chain on its own map, scan, tape window
+// (its own engine stream), initial pose and trace slice from a job table in HBM, control block and result block indexed
+// by the row.  One kernel is one super-step of every chain that has not ended; nothing waits inside a launch.
 #include <hip/hip_runtime.h>
 
 #include "mc_chain_device.h"
@@ -22,8 +25,11 @@ static constexpr int kSumLanes = 256;
 #define MC_PIN64(x) asm volatile("" ::"s"((unsigned long long)(x)))
 #define MC_PINF(x) asm volatile("" ::"s"(__double_as_longlong(x)))
 
-template <int MODEL, int NT, bool SEQ>
+// BATCH: grid.y independent matches, each with its own map, scan, tape window, initial pose and trace (McChainArgs::jobs);
+// one kernel = one super-step of every chain that has not ended, no workgroup waits for another inside a launch
+template <int MODEL, int NT, bool SEQ, bool BATCH>
 __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
+  static_assert(!(BATCH && SEQ), "the batch form sums in the canonical order only");
   extern __shared__ double s_term[];
   __shared__ double s_sc[kMcSlots + 8];
   __shared__ unsigned long long s_hash[kMcSlots + 8];
@@ -35,38 +41,64 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const bool init_slot = blockIdx.x + 1 == gridDim.x;  // the bookkeeping workgroup: slot kMcSlots
   const int slot = init_slot ? kMcSlots : (int)blockIdx.x;
-  McChainCtl *ctl = a.ctl;
+  McChainCtl *ctl = BATCH ? a.ctl + blockIdx.y : a.ctl;  // (one chain per grid row)
+  McHostOut *host = BATCH ? a.host + blockIdx.y : a.host;
+  // this chain's map, scan, tape, initial pose and trace: kernel arguments, or -- a batch of matches -- its entry of the
+  // job table (a uniform address read before any store of the kernel: scalar loads)
+  MapView map;
+  ScanView scan;
+  const McPair *tape;
+  McTraceEntry *trace;
+  double init0, init1, init2;
+  if (BATCH) {
+    const McJobView *__restrict__ jv = a.jobs + blockIdx.y;
+    map = jv->map;
+    scan = jv->scan;
+    tape = jv->tape;
+    trace = jv->trace;
+    init0 = jv->init[0];
+    init1 = jv->init[1];
+    init2 = jv->init[2];
+  } else {
+    map = a.map;
+    scan = a.scan;
+    tape = a.tape;
+    trace = a.trace;
+    init0 = a.init[0];
+    init1 = a.init[1];
+    init2 = a.init[2];
+  }
   const unsigned done_epoch = __hip_atomic_load(&ctl->done_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int n = a.scan.n;
+  const int n = scan.n;
   double br = 0.0, bc = 0.0, bs = 0.0, bw = 0.0, bf = 0.0;
   if (t < n) {
-    br = a.scan.range[t];
-    bc = a.scan.cos_a[t];
-    bs = a.scan.sin_a[t];
-    bw = a.scan.weight[t];
-    bf = a.scan.factor[t];
+    br = scan.range[t];
+    bc = scan.cos_a[t];
+    bs = scan.sin_a[t];
+    bw = scan.weight[t];
+    bf = scan.factor[t];
   }
   MC_PIN32(a.max_failed);
   MC_PIN32(a.max_poses);
   MC_PIN32(a.n_slots);
-  MC_PIN64(a.tape);
-  MC_PIN64(a.host);
-  MC_PIN64(a.trace);
+  MC_PIN64(tape);
+  MC_PIN64(host);
+  MC_PIN64(trace);
   MC_PIN32(a.trace_cap);
-  MC_PIN64(a.map.payload);
-  MC_PIN32(a.map.width);
-  MC_PIN32(a.map.height);
-  MC_PIN32(a.map.pitch);
-  MC_PIN32(a.map.origin_x);
-  MC_PIN32(a.map.origin_y);
-  MC_PINF(a.map.scale);
-  MC_PINF(a.map.inv_scale);
-  MC_PINF(a.map.unknown[0]);
-  MC_PINF(a.map.unknown[1]);
-  MC_PINF(a.map.unknown[2]);
-  MC_PINF(a.map.unknown[3]);
+  MC_PIN64(map.payload);
+  MC_PIN32(map.width);
+  MC_PIN32(map.height);
+  MC_PIN32(map.pitch);
+  MC_PIN32(map.origin_x);
+  MC_PIN32(map.origin_y);
+  MC_PINF(map.scale);
+  MC_PINF(map.inv_scale);
+  MC_PINF(map.unknown[0]);
+  MC_PINF(map.unknown[1]);
+  MC_PINF(map.unknown[2]);
+  MC_PINF(map.unknown[3]);
   MC_PIN32(a.oie);
-  MC_PINF(a.scan.tot_w);
+  MC_PINF(scan.tot_w);
   const int pb = (k - 1) & 1;
   if (k > 0) {
     const double *sc_prev = ctl->scores[pb];
@@ -85,15 +117,15 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
     McState st;
     if (k == 0) {
       st = McState{};
-      st.x = a.init[0];
-      st.y = a.init[1];
-      st.theta = a.init[2];
+      st.x = init0;
+      st.y = init1;
+      st.theta = init2;
       st.td = a.td0;
       st.rd = a.rd0;
       st.first = 1;
       if (init_slot && lane == 0) {
         ctl->state[0] = st;
-        __hip_atomic_store(&a.host->progress, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host->progress, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     } else {
       // ---- replay of the previous super-step: lane l looks at candidates 8 l .. 8 l + 7 (kMcPerLane)
@@ -139,7 +171,7 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
       McState next = sp;
       double ax = 0.0, ay = 0.0, ath = 0.0;
       if (!dirty) {
-        if (j_acc >= 0) mc_candidate(sp, a.tape, j_acc, &ax, &ay, &ath);
+        if (j_acc >= 0) mc_candidate(sp, tape, j_acc, &ax, &ay, &ath);
         const double aprob = j_acc >= 0 ? s_sc[j_acc] : 0.0;
         const unsigned long long ahash = (verify && j_acc >= 0) ? s_hash[j_acc] : 0ull;
         if (sp.first) {  // the initial pose was scored in the same super-step: call number one
@@ -147,7 +179,7 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
           next.best_hash = root_hash;
           next.calls = 1;
         }
-        mc_advance(next, a.tape, n_cand, j_acc, ax, ay, ath, aprob, ahash, a.max_failed, a.max_poses);
+        mc_advance(next, tape, n_cand, j_acc, ax, ay, ath, aprob, ahash, a.max_failed, a.max_poses);
         next.evaluated = sp.evaluated + n_cand + (sp.first ? 1 : 0);
         next.first = 0;
         next.mode = 0;
@@ -159,23 +191,23 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
       next.steps = sp.steps + 1;
       st = next;
       if (init_slot) {
-        if (a.trace && !dirty) {
+        if (trace && !dirty) {
           const long long base = sp.calls + (sp.first ? 1 : 0);
           if (sp.first && lane == 0 && a.trace_cap > 0) {
             McTraceEntry e{sp.x, sp.y, sp.theta, root, 1, 0};
-            a.trace[0] = e;
+            trace[0] = e;
           }
           for (int c = 0; c < kMcPerLane; ++c) {
             const int j = kMcPerLane * lane + c;
             if (j < used) {
               McTraceEntry e;
-              mc_candidate(sp, a.tape, j, &e.x, &e.y, &e.theta);
+              mc_candidate(sp, tape, j, &e.x, &e.y, &e.theta);
               e.score = s_sc[j];
               e.accepted = j == j_acc ? 1 : 0;
               e.pad = 0;
               const long long at = base + j;
-              if (at < a.trace_cap) a.trace[at] = e;
-              else a.host->error = 2;
+              if (at < a.trace_cap) trace[at] = e;
+              else host->error = 2;
             }
           }
         }
@@ -184,7 +216,7 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
           __threadfence_system();
           if (lane == 0) {
             ctl->done_epoch = a.epoch;
-            McHostOut *h = a.host;
+            McHostOut *h = host;
             h->pose[0] = next.x;
             h->pose[1] = next.y;
             h->pose[2] = next.theta;
@@ -202,10 +234,11 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
             h->saved[0] = next.saved[0];
             h->saved[1] = next.saved[1];
             h->saved[2] = next.saved[2];
+            if (BATCH) atomicAdd(a.n_done, 1u);  // (once per chain: done_epoch keeps later launches out)
             __hip_atomic_store(&h->done_seq, a.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
           }
         } else if (lane == 0) {
-          __hip_atomic_store(&a.host->progress, (unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(&host->progress, (unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       }
     }
@@ -217,7 +250,7 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
     } else if (go) {
       const int avail = (int)mc_available(st, a.max_failed, a.max_poses);
       go = slot < (avail < a.n_slots ? avail : a.n_slots);
-      if (go) mc_candidate(st, a.tape, slot, &px, &py, &pth);
+      if (go) mc_candidate(st, tape, slot, &px, &py, &pth);
     }
     if (go) {
       double sn, cs;
@@ -253,13 +286,13 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
       w_[j] = bw;
       f_[j] = bf;
       if (j > 0 || base != t) {
-        r_ = a.scan.range[bc_];
-        ca = a.scan.cos_a[bc_];
-        sa = a.scan.sin_a[bc_];
-        w_[j] = a.scan.weight[bc_];
-        f_[j] = a.scan.factor[bc_];
+        r_ = scan.range[bc_];
+        ca = scan.cos_a[bc_];
+        sa = scan.sin_a[bc_];
+        w_[j] = scan.weight[bc_];
+        f_[j] = scan.factor[bc_];
       }
-      cell[j] = beam_cell<MODEL>(a.map, px, py, sn, cs, r_, ca, sa);
+      cell[j] = beam_cell<MODEL>(map, px, py, sn, cs, r_, ca, sa);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -272,7 +305,7 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
     if (t == 0) {
       double acc = 0.0;
       for (int b = 0; b < n; ++b) acc = acc + s_term[b];
-      ctl->scores[k & 1][slot] = (a.scan.tot_w == 0.0) ? __builtin_nan("") : acc / a.scan.tot_w;
+      ctl->scores[k & 1][slot] = (scan.tot_w == 0.0) ? __builtin_nan("") : acc / scan.tot_w;
     }
     return;
   }
@@ -299,29 +332,33 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
   __syncthreads();
   if (t == 0) {
     const double total = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-    ctl->scores[k & 1][slot] = (a.scan.tot_w == 0.0) ? __builtin_nan("") : total / a.scan.tot_w;
+    ctl->scores[k & 1][slot] = (scan.tot_w == 0.0) ? __builtin_nan("") : total / scan.tot_w;
     if (verify) ctl->hashes[k & 1][slot] = s_hpart[0] + s_hpart[1] + s_hpart[2] + s_hpart[3];
   }
   if (verify && s_mode && t == 64) {
     double acc = 0.0;
     for (int b = 0; b < n; ++b) acc = acc + s_term[b];
-    ctl->scores_seq[k & 1][slot] = (a.scan.tot_w == 0.0) ? __builtin_nan("") : acc / a.scan.tot_w;
+    ctl->scores_seq[k & 1][slot] = (scan.tot_w == 0.0) ? __builtin_nan("") : acc / scan.tot_w;
   }
 }
 
 hipError_t launch_mc_chain_step(const McChainArgs &a, int cell_model, int k, int nt, hipStream_t stream,
-                                hipEvent_t e0, hipEvent_t e1) {
+                                hipEvent_t e0, hipEvent_t e1, int n_chains) {
   if (a.n_slots < 1 || a.n_slots > kMcSlots) return hipErrorInvalidValue;
   typedef void (*Kernel)(McChainArgs, int);
+  const bool batch = n_chains > 1;
+  if (batch && (a.seq || !a.jobs || !a.n_done || n_chains > 65535)) return hipErrorInvalidValue;
   const Kernel kernel = pick_cell_model(cell_model, [&](auto model) -> Kernel {
     return pick_mc_nt(nt, [&](auto nt_c) -> Kernel {
+      if (batch) return k_mc_chain_step<decltype(model)::value, decltype(nt_c)::value, false, true>;
       return pick_bool(a.seq != 0, [](auto seq_c) -> Kernel {
-        return k_mc_chain_step<decltype(model)::value, decltype(nt_c)::value, decltype(seq_c)::value>;
+        return k_mc_chain_step<decltype(model)::value, decltype(nt_c)::value, decltype(seq_c)::value, false>;
       });
     });
   });
-  return launch_kernel(kernel, dim3(a.n_slots + 1), dim3(mc_nt_of(nt)), sizeof(double) * (size_t)(a.scan.n > 0 ? a.scan.n : 1),
-                       stream, e0, e1, a, k);
+  // dynamic LDS: one double per beam (of the longest job), rounded up to a multiple of 16 bytes
+  const size_t lds = sizeof(double) * (size_t)(((a.scan.n > 0 ? a.scan.n : 1) + 1) & ~1);
+  return launch_kernel(kernel, dim3(a.n_slots + 1, batch ? n_chains : 1), dim3(mc_nt_of(nt)), lds, stream, e0, e1, a, k);
 }
 
 }  // namespace slamhip

@@ -49,6 +49,16 @@ struct McChainCtl {
   unsigned done_epoch;
 };
 
+// one match of a BATCH of independent Monte-Carlo matches (grid.y = match, k_mc_chain_step<..., BATCH>): its own map,
+// scan, window of ITS engine stream's pair tape, initial pose and slice of the observer trace
+struct McJobView {
+  MapView map;
+  ScanView scan;
+  const McPair *tape;
+  double init[3];
+  McTraceEntry *trace;  // null = no observer
+};
+
 struct McChainArgs {
   MapView map;
   ScanView scan;
@@ -72,6 +82,11 @@ struct McChainArgs {
   int lds_consts;  // range, cosine, sine of the beams behind a thread's first one are kept in LDS
   int debug_mute;  // testing: workgroup debug_mute - 1 leaves at once, as if it had never become resident
   long long *stamps;  // debugging (slamhip_matcher_debug_stamps): wall-clock stamps of workgroup 1, eight per super-step
+  // the batch form of the chain of kernels (launch_mc_chain_step with n_chains > 1): chain c = grid row c reads map,
+  // scan, tape, initial pose and trace from jobs[c] (scan.n above is then the longest job's beam count: the launch's LDS
+  // size), `ctl` and `host` are arrays, and every chain that ends bumps *n_done (k_chain_marker reports it)
+  const McJobView *jobs;
+  unsigned *n_done;
 };
 
 // the granule block of a co-resident Monte-Carlo chain (HcResidentCtl's layout with this chain's row length)
@@ -89,8 +104,8 @@ hipError_t launch_mc_chain_resident(const McChainArgs &a, int cell_model, int nt
                                     hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 hipError_t mc_resident_capacity(int cell_model, int nt, int n_beams, bool lds_consts, int *out_wgs, int *out_per_cu = nullptr);
 
-// threads per workgroup: 512 or 1024
+// threads per workgroup: 512 or 1024; n_chains > 1: the batch form (McChainArgs::jobs; the canonical sum only)
 hipError_t launch_mc_chain_step(const McChainArgs &a, int cell_model, int k, int nt, hipStream_t stream,
-                                hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                                hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int n_chains = 1);
 
 }  // namespace slamhip

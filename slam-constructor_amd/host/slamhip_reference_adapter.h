@@ -418,6 +418,14 @@ public:
   ~HipGridScanMatcher() override { slamhip_matcher_destroy(_m); }
 
   void reset_state() override { slamhip_or_die(slamhip_matcher_reset_state(_m), "reset_state"); }
+  // K robots on ONE Monte-Carlo matcher object: robot k's engine is what its own MonteCarloScanMatcher would own,
+  // GaussianPoseEnumerator{mt19937(seeds[k])} (init_scan_matching.h:118-135, slam/scmtch/MC/seed).  hip_process_raw_scans
+  // then runs job k on stream k, all jobs in shared launches (slamhip_matcher_set_mc_streams); process_scan of this
+  // object keeps using the matcher's own engine.  An empty vector removes the streams.
+  void set_mc_streams(const std::vector<unsigned> &seeds) {
+    slamhip_or_die(slamhip_matcher_set_mc_streams(_m, (int)seeds.size(), seeds.empty() ? nullptr : seeds.data()), "set_mc_streams");
+    _n_mc_streams = (int)seeds.size();
+  }
   // optional: a log kept somewhere else than in the map handed to process_scan (a map that IS a
   // HipMirroredGridMap is recognised by itself; any other map is compared cell by cell)
   void set_dirty_source(const HipMirroredGridMap *src) { _dirty_source = src; }
@@ -583,6 +591,7 @@ private:
   double _max_range = -1;
   std::vector<double> _r, _a, _f;
   std::vector<int> _occ;
+  int _n_mc_streams = 0;
 };
 
 // K robots / replicas, one library call: what HipGridScanMatcher::process_raw_scan does for one scan, for K of them --
@@ -640,6 +649,9 @@ inline void hip_process_raw_scans(HipGridScanMatcher &matcher, std::vector<HipRa
   std::vector<double> d(3 * packed.size() + 3, 0.0), prob(packed.size() + 1, std::numeric_limits<double>::quiet_NaN());
   if (!packed.empty()) {
     slamhip_or_die(slamhip_matcher_set_observer(matcher._m, nullptr), "set_observer");
+    // job k <-> engine stream k, whatever was packed out in front of it (a scan without points leaves its stream alone)
+    if (matcher._n_mc_streams > 0)
+      slamhip_or_die(slamhip_matcher_set_mc_job_streams(matcher._m, (int)live.size(), live.data()), "set_mc_job_streams");
     int rc = slamhip_matcher_process_raw_scan_batch(matcher._m, (int)packed.size(), packed.data(), d.data(), prob.data(), nullptr);
     if (rc == SLAMHIP_ERR_INVALID || rc == SLAMHIP_ERR_UNSUPPORTED || rc == SLAMHIP_ERR_NO_DEVICE)
       slamhip_or_die(rc, "process_raw_scan_batch");
