@@ -482,6 +482,44 @@ int slamhip_omqe_quality(int kind, int n, const double *range, const double *ang
  * same context drains what is queued into its own count. */
 int slamhip_map_set_deferred(slamhip_ctx *ctx, int on);
 int slamhip_map_drain(slamhip_ctx *ctx, long long *n_updates);
+/* K scans into K resident maps in ONE call: the second half of a K-robot step (the first is
+ * slamhip_matcher_process_scan_batch / _raw_scan_batch).  After the call every map holds bit for bit what it would
+ * hold after the same jobs went through slamhip_map_append_scan_q (angle == NULL) or slamhip_map_append_scan_raw
+ * (angle != NULL) one after another in job order; n_updates[k] is that call's count for job k.
+ * The jobs share launches: one k_mu_lines_batch and one k_mu_cells_batch per ROUND (the gather form of the update), a
+ * status kernel and one wait.  A round holds jobs on distinct maps; a job naming a map an earlier job of the round
+ * names opens the next round, so two robots on one map are applied in job order.  A job the shared launches do not
+ * cover -- n > 4096, a key window above 2^22 cells, beam directions that do not ascend within one turn,
+ * SLAMHIP_OPT_K6_PATH 1 or 2, a context that is not low-latency, n_jobs == 1 -- runs through the lone call at its
+ * place in the order of its map.  Jobs with n <= 0 or every beam range-gated report 0 updates.
+ * Maps that may grow (slamhip_map_set_auto_grow) grow by the lone rule, on the host, before their round is launched.
+ * cfg->rule must fit the cell model of EVERY job's map; that, null arrays, unknown maps and non-finite end points
+ * are found before anything is launched or changed.  A job whose beam leaves a window that may not grow gets
+ * status[k] = SLAMHIP_ERR_STATE (its cells inside the window are updated, every other job completes) and the call
+ * returns SLAMHIP_ERR_STATE.  The call is awaited, also while slamhip_map_set_deferred is on: it is ordered behind the
+ * queued lone updates on the context's stream and leaves them queued (slamhip_map_drain reports them alone). */
+typedef struct {
+  int map_id;
+  double pose[3];
+  double scan_quality;          /* replaces cfg->scan_quality for this job (a world sets it per scan) */
+  int n;
+  const double *range;
+  const double *cos_a, *sin_a;  /* as slamhip_map_append_scan_q ... */
+  const double *angle;          /* ... or non-NULL: the raw-provider form of slamhip_map_append_scan_raw (cos_a/sin_a ignored) */
+  const int *is_occ;            /* may be NULL */
+  const double *quality;        /* per point, may be NULL */
+  const slamhip_scan_adder_cfg *cfg; /* NULL: the call's cfg.  Else this job's own base probabilities, blur, max_range
+                                      * and shift amount (robots whose adders differ still share the launches); its
+                                      * rule and occupancy estimator must be the call's, its scan_quality is not read */
+} slamhip_map_update_job;
+int slamhip_map_append_scan_batch(slamhip_ctx *ctx, const slamhip_scan_adder_cfg *cfg, int n_jobs,
+                                  const slamhip_map_update_job *jobs, long long *n_updates /* K */, int *status /* K, may be NULL */);
+/* of the last slamhip_map_append_scan_batch: rounds launched, jobs they held, jobs that went through the lone call,
+ * kernel launches of the rounds (three per round: lines, cells, status) */
+int slamhip_map_update_batch_stats(slamhip_ctx *ctx, int *rounds, int *jobs_in_shared_launches, int *jobs_lone, int *launches);
+/* the direction tables the batch keeps per distinct scanner (at most 16, least recently used evicted): how many the
+ * context holds, and how many were uploaded since it was created -- a call with known scanners uploads none */
+int slamhip_map_update_batch_tables(slamhip_ctx *ctx, int *tables, long long *uploads);
 /* update counters of a window (MEAN: n; GMAPPING: hits, tries) -- tests / debugging */
 int slamhip_map_download_aux(slamhip_ctx *ctx, int map_id, int x0, int y0, int w, int h, double *out);
 

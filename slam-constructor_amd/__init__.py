@@ -72,7 +72,8 @@ slamhip_matcher_set_m3rsm_threads slamhip_matcher_m3rsm_copied_back
 slamhip_matcher_m3rsm_rotations slamhip_matcher_set_m3rsm_rotation_slots
 slamhip_scan_table_uploads slamhip_scan_download
 slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download
-slamhip_matcher_set_mc_streams slamhip_matcher_set_mc_job_streams slamhip_matcher_mc_stream_info""".split()
+slamhip_matcher_set_mc_streams slamhip_matcher_set_mc_job_streams slamhip_matcher_mc_stream_info
+slamhip_map_append_scan_batch slamhip_map_update_batch_stats slamhip_map_update_batch_tables""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -114,6 +115,12 @@ class ScanAdderCfg(C.Structure):
                 ("base_occupied_qual", C.c_double), ("base_empty_prob", C.c_double),
                 ("base_empty_qual", C.c_double), ("blur", C.c_double), ("max_range", C.c_double),
                 ("occupancy_estimator", C.c_int), ("area_shift_amount", C.c_double)]
+
+
+class MapUpdateJob(C.Structure):
+    """slamhip_map_update_job: one scan into one resident map (slamhip_map_append_scan_batch)."""
+    _fields_ = [("map_id", C.c_int), ("pose", C.c_double * 3), ("scan_quality", C.c_double), ("n", C.c_int),
+                ("range", _dp), ("cos_a", _dp), ("sin_a", _dp), ("angle", _dp), ("is_occ", _ip), ("quality", _dp), ("cfg", C.c_void_p)]
 
 
 class GmappingParams(C.Structure):
@@ -627,6 +634,73 @@ class Context:
                                                   occ.ctypes.data_as(_ip) if occ is not None else None,
                                                   _d(bq) if bq is not None else None, C.byref(nu)))
         return nu.value
+
+    def map_append_scan_batch(self, rule, jobs, base=(0.95, 1.0, 0.01, 1.0), blur=0.0, max_range=float("inf"),
+                              estimator=0, shift_amount=0.0):
+        """K scans into K resident maps through shared launches (slamhip_map_append_scan_batch).  jobs: dicts with
+        map_id, pose, range and either cos_a / sin_a or angle (the raw trig provider's form), optionally is_occ,
+        beam_quality (per point) and quality (the scan's, default 1.0); a job that names base, blur or max_range has its own
+        adder settings in place of the call's.  Returns (n_updates, status), one entry per job;
+        a failing call raises SlamHipError carrying both as attributes."""
+        cfg = ScanAdderCfg(rule, 1.0, base[0], base[1], base[2], base[3], blur, max_range, estimator, shift_amount)
+        K = len(jobs)
+        arr = (MapUpdateJob * max(K, 1))()
+        keep = []
+
+        def dbl(a):
+            a = _f64(a)
+            keep.append(a)
+            return _d(a)
+        for k, j in enumerate(jobs):
+            rng = _f64(j["range"])
+            keep.append(rng)
+            arr[k].map_id = int(j["map_id"])
+            arr[k].pose[:] = [float(v) for v in np.asarray(j["pose"], dtype=np.float64).ravel()[:3]]
+            arr[k].scan_quality = float(j.get("quality", 1.0))
+            arr[k].n = rng.size
+            arr[k].range = _d(rng)
+            if j.get("angle") is not None:
+                assert np.size(j["angle"]) == rng.size
+                arr[k].angle = dbl(j["angle"])
+            else:
+                assert np.size(j["cos_a"]) == rng.size and np.size(j["sin_a"]) == rng.size
+                arr[k].cos_a, arr[k].sin_a = dbl(j["cos_a"]), dbl(j["sin_a"])
+            if j.get("is_occ") is not None:
+                occ = np.ascontiguousarray(j["is_occ"], dtype=np.int32)
+                assert occ.size == rng.size
+                keep.append(occ)
+                arr[k].is_occ = occ.ctypes.data_as(_ip)
+            if j.get("beam_quality") is not None:
+                assert np.size(j["beam_quality"]) == rng.size
+                arr[k].quality = dbl(j["beam_quality"])
+            if any(key in j for key in ("base", "blur", "max_range", "shift_amount")):
+                b = j.get("base", base)
+                own = ScanAdderCfg(rule, 1.0, b[0], b[1], b[2], b[3], j.get("blur", blur), j.get("max_range", max_range),
+                                   estimator, j.get("shift_amount", shift_amount))
+                keep.append(own)
+                arr[k].cfg = C.addressof(own)
+        nu = np.zeros(max(K, 1), dtype=np.int64)
+        st = np.zeros(max(K, 1), dtype=np.int32)
+        self.L.slamhip_map_append_scan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = self.L.slamhip_map_append_scan_batch(self.h, C.byref(cfg), K, C.byref(arr), nu.ctypes.data, st.ctypes.data)
+        try:
+            _check(rc)
+        except SlamHipError as e:
+            e.n_updates, e.status = nu[:K].copy(), st[:K].copy()
+            raise
+        return nu[:K].copy(), st[:K].copy()
+
+    def map_update_batch_stats(self):
+        """of the last map_append_scan_batch: rounds, jobs in shared launches, jobs through the lone call, kernel launches
+        of the rounds; and the direction tables the context holds / has uploaded so far"""
+        v = [C.c_int() for _ in range(5)]
+        up = C.c_longlong()
+        self.L.slamhip_map_update_batch_stats.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        self.L.slamhip_map_update_batch_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(self.L.slamhip_map_update_batch_stats(self.h, *[C.byref(x) for x in v[:4]]))
+        _check(self.L.slamhip_map_update_batch_tables(self.h, C.byref(v[4]), C.byref(up)))
+        return dict(rounds=v[0].value, jobs_shared=v[1].value, jobs_lone=v[2].value, launches=v[3].value,
+                    tables=v[4].value, table_uploads=up.value)
 
     def map_download_aux(self, map_id, x0, y0, w, h, stride):
         out = np.zeros((h, w, stride))

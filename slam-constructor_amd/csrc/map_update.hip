@@ -36,8 +36,9 @@
 // HBM traffic: per (beam, cell) an 8-byte (key, beam) pair written, sorted and read, one 8-byte
 // observation written and read, plus one read-modify-write of the cell (8-48 bytes) per distinct cell; on the
 // batch's fast path a 4-byte key written and read, the cell's mean read and its try counter updated in place.
-// The kernels live in map_update_kernels.h; this file holds the two host drivers (one scan into a bound
-// dense map; one scan from many poses into the copy-on-write maps of a particle filter).
+// The kernels live in map_update_kernels.h; this file holds the host drivers (one scan into a bound dense map; K scans
+// into K bound dense maps through shared launches of the gather kernels, planned by map_update_batch_plan.h; one scan
+// from many poses into the copy-on-write maps of a particle filter).
 
 #include <string.h>  // rocprim's texture iterator calls ::memset without including it
 
@@ -64,6 +65,7 @@ struct MuJob {
 }  // namespace slamhip
 
 #include "map_update_kernels.h"
+#include "map_update_batch_plan.h"
 #include "map_update_gather.h"
 
 using namespace slamhip;
@@ -222,8 +224,53 @@ int mu_finish(slamhip_ctx *ctx, const int *d_error_flag, const unsigned long lon
 }  // namespace
 
 // The gather form needs the scan's beam directions in ascending order over less than a full turn (a laser scan's
-// are), and a table from direction to beam index.  Both depend on the scanner only: analysed when cos_a / sin_a differ
-// from the last call's (a 17 KB compare per update), not per scan.
+// are), and a table from direction to beam index.  Both depend on the scanner only.  The analysis: false = the
+// directions do not ascend within one turn; else the table, the angle of beam 0 and the radius of the near cells.
+static bool mu_analyse_directions(int n, const double *cos_a, const double *sin_a, std::vector<unsigned> &lut, double *a0_out,
+                                  int *near_r_out) {
+  std::vector<double> rel(n);
+  double prev = 0.0, a0 = 0.0;
+  for (int b = 0; b < n; ++b) {
+    double ang = std::atan2(sin_a[b], cos_a[b]);
+    if (!std::isfinite(ang)) return false;
+    if (b == 0) {
+      a0 = ang;
+      rel[0] = 0.0;
+      prev = ang;
+      continue;
+    }
+    while (ang < prev - 1e-12) ang += kTwoPi;  // unwrap: ascending
+    if (!(ang >= prev) || ang - a0 >= kTwoPi - 0.05) return false;  // not ascending within one turn
+    rel[b] = ang - a0;
+    prev = ang;
+  }
+  // the table over the PSEUDO-angle of a beam relative to beam 0 (mu_pseudo_angle: monotone in the angle)
+  auto pseudo = [](double ang) {
+    const double x = std::cos(ang), y = std::sin(ang);
+    const double t = std::fabs(y) / (std::fabs(x) + std::fabs(y));
+    return y >= 0.0 ? (x >= 0.0 ? t : 2.0 - t) : (x < 0.0 ? 2.0 + t : 4.0 - t);
+  };
+  lut.resize(kGatherLut + 1);
+  int b = 0;
+  for (int m = 0; m <= kGatherLut; ++m) {
+    const double edge = (double)m * (4.0 / kGatherLut);
+    // (rel ascends within one turn, so its pseudo-angle ascends too -- except that angles a hair below a full turn
+    // fold to ~4; they stay in front of `edge` only while rel itself is below the turn)
+    while (b < n && (rel[b] < 1e-12 ? 0.0 : pseudo(rel[b])) < edge) ++b;
+    lut[m] = (unsigned)b;
+  }
+  *a0_out = a0;
+  // cells closer to the robot than this take one wave each: beyond it a cell asks at most ~50 beams
+  const double span = n > 1 ? rel[n - 1] : 1.0;
+  const double density = n > 1 && span > 0 ? (double)(n - 1) / span : 1.0;  // beams per radian
+  // (measured, 1080 beams over 270 degrees, k_mu_cells in us by radius: 8 cells 49, 12 cells 35, 18 cells 19, 26 and
+  // 36 cells 19-20: a far cell's thread asks its candidates one after the other, a near cell's wave 64 at a time)
+  const double half_window = std::min(1.5, 10.0 / density);
+  *near_r_out = std::max(2, std::min(40, (int)std::ceil(0.75 / std::sin(half_window))));
+  return true;
+}
+
+// (the lone route: analysed when cos_a / sin_a differ from the last call's -- a 17 KB compare per update --, not per scan)
 int mu_scan_geometry(slamhip_ctx *ctx, MuScratch &sc, int n, const double *cos_a, const double *sin_a, bool *ok) {
   if ((int)sc.geo_cos.size() == n && std::memcmp(sc.geo_cos.data(), cos_a, sizeof(double) * n) == 0 &&
       std::memcmp(sc.geo_sin.data(), sin_a, sizeof(double) * n) == 0) {
@@ -234,52 +281,356 @@ int mu_scan_geometry(slamhip_ctx *ctx, MuScratch &sc, int n, const double *cos_a
   sc.geo_sin.assign(sin_a, sin_a + n);
   sc.geo_ok = false;
   *ok = false;
-  std::vector<double> rel(n);
-  double prev = 0.0, a0 = 0.0;
-  for (int b = 0; b < n; ++b) {
-    double ang = std::atan2(sin_a[b], cos_a[b]);
-    if (!std::isfinite(ang)) return SLAMHIP_OK;
-    if (b == 0) {
-      a0 = ang;
-      rel[0] = 0.0;
-      prev = ang;
-      continue;
-    }
-    while (ang < prev - 1e-12) ang += kTwoPi;  // unwrap: ascending
-    if (!(ang >= prev) || ang - a0 >= kTwoPi - 0.05) return SLAMHIP_OK;  // not ascending within one turn
-    rel[b] = ang - a0;
-    prev = ang;
-  }
-  // the table over the PSEUDO-angle of a beam relative to beam 0 (mu_pseudo_angle: monotone in the angle)
-  auto pseudo = [](double ang) {
-    const double x = std::cos(ang), y = std::sin(ang);
-    const double t = std::fabs(y) / (std::fabs(x) + std::fabs(y));
-    return y >= 0.0 ? (x >= 0.0 ? t : 2.0 - t) : (x < 0.0 ? 2.0 + t : 4.0 - t);
-  };
-  std::vector<unsigned> lut(kGatherLut + 1);
-  int b = 0;
-  for (int m = 0; m <= kGatherLut; ++m) {
-    const double edge = (double)m * (4.0 / kGatherLut);
-    // (rel ascends within one turn, so its pseudo-angle ascends too -- except that angles a hair below a full turn
-    // fold to ~4; they stay in front of `edge` only while rel itself is below the turn)
-    while (b < n && (rel[b] < 1e-12 ? 0.0 : pseudo(rel[b])) < edge) ++b;
-    lut[m] = (unsigned)b;
-  }
+  std::vector<unsigned> lut;
+  double a0 = 0.0;
+  int near_r = 8;
+  if (!mu_analyse_directions(n, cos_a, sin_a, lut, &a0, &near_r)) return SLAMHIP_OK;
   if (!sc.d_lut) SLAMHIP_CHECK(hipMalloc(&sc.d_lut, sizeof(unsigned) * (kGatherLut + 1)));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));  // (queued updates may still read the old table)
   SLAMHIP_CHECK(hipMemcpy(sc.d_lut, lut.data(), sizeof(unsigned) * (kGatherLut + 1), hipMemcpyHostToDevice));
   sc.geo_a0 = a0;
-  // cells closer to the robot than this take one wave each: beyond it a cell asks at most ~50 beams
-  const double span = n > 1 ? rel[n - 1] : 1.0;
-  const double density = n > 1 && span > 0 ? (double)(n - 1) / span : 1.0;  // beams per radian
-  // (measured, 1080 beams over 270 degrees, k_mu_cells in us by radius: 8 cells 49, 12 cells 35, 18 cells 19, 26 and
-  // 36 cells 19-20: a far cell's thread asks its candidates one after the other, a near cell's wave 64 at a time)
-  const double half_window = std::min(1.5, 10.0 / density);
-  sc.geo_near_r = std::max(2, std::min(40, (int)std::ceil(0.75 / std::sin(half_window))));
+  sc.geo_near_r = near_r;
   sc.geo_ok = true;
   *ok = true;
   return SLAMHIP_OK;
 }
+
+// ---- slamhip_map_append_scan_batch: K scans into K resident maps through shared launches of the gather kernels ------
+namespace {
+// what is known about one scanner's beam directions (mu_analyse_directions), kept on the device: jobs with equal
+// scanners share a table, and a later call with the same scanners uploads none.  The key is the bytes the caller
+// hands in: (cos_a | sin_a), or the angles of a raw-provider job -- its table is made from cos / sin(angle) and turned
+// by the pose's heading through rot_c / rot_s like any other (the directions of such a job are cos / sin(heading +
+// angle) by the host's libm: the same angles to an ulp, and the table only has to name a superset of a cell's beams).
+constexpr int kScannerTables = 16;
+struct MuScannerTable {
+  int n = 0;
+  bool from_angle = false;
+  std::vector<double> key;
+  bool ok = false;
+  double a0 = 0.0;
+  int near_r = 8;
+  unsigned *d_lut = nullptr;
+  unsigned long long used = 0, used_call = 0;  // least recently used goes first; never a table of the running call
+};
+struct MuFleetScratch {
+  unsigned char *arena = nullptr, *h_stage = nullptr, *d_table = nullptr, *h_table = nullptr;
+  size_t cap_arena = 0, cap_stage = 0, cap_table = 0, cap_htable = 0, cap_irr = 0, cap_status = 0;
+  unsigned *irr = nullptr;  // the marker words of all jobs' key windows: all zero between calls
+  unsigned long long *d_status = nullptr, *h_status = nullptr;  // per job (padding records, error flag)
+  std::vector<MuScannerTable> scanners;
+  unsigned long long tick = 0, call = 0;
+  long long table_uploads = 0;
+  int rounds = 0, jobs_shared = 0, jobs_lone = 0, launches = 0;  // of the last call
+};
+MuFleetScratch &fleet_of(slamhip_ctx *ctx) {
+  if (!ctx->mu_kscratch) ctx->mu_kscratch = new MuFleetScratch;
+  return *static_cast<MuFleetScratch *>(ctx->mu_kscratch);
+}
+
+// the table of a job's scanner: its index, -1 when the cache holds only tables of this call (the job goes lone)
+int mu_scanner_table(MuFleetScratch &fs, int n, bool from_angle, const double *k0, const double *k1, int *index) {
+  const size_t words = from_angle ? (size_t)n : 2 * (size_t)n;
+  *index = -1;
+  for (size_t i = 0; i < fs.scanners.size(); ++i) {
+    MuScannerTable &t = fs.scanners[i];
+    if (t.n != n || t.from_angle != from_angle || t.key.size() != words) continue;
+    if (std::memcmp(t.key.data(), k0, sizeof(double) * n) != 0) continue;
+    if (!from_angle && std::memcmp(t.key.data() + n, k1, sizeof(double) * n) != 0) continue;
+    t.used = ++fs.tick;
+    t.used_call = fs.call;
+    *index = (int)i;
+    return SLAMHIP_OK;
+  }
+  int slot = -1;
+  if ((int)fs.scanners.size() < kScannerTables) {
+    fs.scanners.emplace_back();
+    slot = (int)fs.scanners.size() - 1;
+  } else {
+    for (size_t i = 0; i < fs.scanners.size(); ++i)
+      if (fs.scanners[i].used_call != fs.call && (slot < 0 || fs.scanners[i].used < fs.scanners[slot].used)) slot = (int)i;
+    if (slot < 0) return SLAMHIP_OK;
+  }
+  MuScannerTable &t = fs.scanners[slot];
+  t.n = n;
+  t.from_angle = from_angle;
+  t.key.assign(k0, k0 + n);
+  if (!from_angle) t.key.insert(t.key.end(), k1, k1 + n);
+  t.used = ++fs.tick;
+  t.used_call = fs.call;
+  std::vector<unsigned> lut;
+  if (from_angle) {
+    std::vector<double> c(n), s_(n);
+    for (int b = 0; b < n; ++b) {
+      c[b] = std::cos(k0[b]);
+      s_[b] = std::sin(k0[b]);
+    }
+    t.ok = mu_analyse_directions(n, c.data(), s_.data(), lut, &t.a0, &t.near_r);
+  } else {
+    t.ok = mu_analyse_directions(n, k0, k1, lut, &t.a0, &t.near_r);
+  }
+  if (t.ok) {
+    // (no kernel of an earlier batch is in flight -- the call is awaited -- and lone updates read their own table)
+    if (!t.d_lut) SLAMHIP_CHECK(hipMalloc(&t.d_lut, sizeof(unsigned) * (kGatherLut + 1)));
+    SLAMHIP_CHECK(hipMemcpy(t.d_lut, lut.data(), sizeof(unsigned) * (kGatherLut + 1), hipMemcpyHostToDevice));
+    ++fs.table_uploads;
+  }
+  *index = slot;
+  return SLAMHIP_OK;
+}
+
+// one job of the batch after the host pass
+struct MuFleetJob {
+  bool empty = true, lone = false, grows = false;
+  std::vector<double> raw_cos, raw_sin;  // a raw-provider job: cos / sin(heading + angle), as the lone entry point makes them
+  const double *cos_a = nullptr, *sin_a = nullptr;
+  double pose[3] = {0, 0, 0};  // (heading 0 for a raw-provider job)
+  double heading = 0.0;
+  unsigned total = 0;
+  mu_plan::CellBox bb{0, 0, 0, 0};
+  mu_plan::Window win{0, 0, 0, 0};  // the map's window when the job runs (grown, if it grows)
+  mu_plan::KeyWindow kw{0, 0, 0, 0, 0};
+  std::vector<unsigned> h_off;
+  int scanner = -1;
+};
+
+template <typename T>
+int mu_fleet_reserve(T **p, size_t *cap, size_t need, size_t floor_, bool pinned) {
+  if (need <= *cap) return SLAMHIP_OK;
+  const size_t ncap = mu_plan::grow_capacity(*cap, need, floor_);
+  if (*p) {
+    if (pinned) hipHostFree(*p);
+    else hipFree(*p);
+  }
+  *p = nullptr;
+  *cap = 0;
+  if (pinned) SLAMHIP_CHECK(hipHostMalloc((void **)p, ncap, hipHostMallocDefault));
+  else SLAMHIP_CHECK(hipMalloc((void **)p, ncap));
+  *cap = ncap;
+  return SLAMHIP_OK;
+}
+
+const char *const kLeavesWindow =
+    "a beam leaves the bound map window: grow the map (slamhip_map_bind) before updating; cells inside the window were updated";
+
+// one round: jobs on distinct maps through one lines launch, one cells launch, one status kernel and one wait
+int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adder_cfg *cfg, const slamhip_map_update_job *jobs,
+                   std::vector<MuFleetJob> &prep, const std::vector<int> &round, long long *n_updates, int *status,
+                   bool *any_left) {
+  const int K = (int)round.size();
+  const int rule = cfg->rule;
+  const int aux_stride = rule == SLAMHIP_RULE_MEAN ? 1 : (rule == SLAMHIP_RULE_GMAPPING ? 2 : 0);
+  // growth and update counters, on the host, before anything of the round is queued
+  for (int k : round) {
+    const slamhip_map_update_job &jb = jobs[k];
+    MuFleetJob &pj = prep[k];
+    if (pj.grows) {
+      const DeviceMap &m = ctx->maps[jb.map_id];
+      const long grown = m.grown + 1;
+      const int model = m.cell_model;
+      const double scale = m.scale;
+      double unk[4];
+      for (int q = 0; q < 4; ++q) unk[q] = m.unknown[q];
+      const int rc = slamhip_map_bind(ctx, jb.map_id, model, pj.win.width, pj.win.height, pj.win.origin_x, pj.win.origin_y,
+                                      scale, unk);
+      if (rc) return rc;
+      ctx->maps[jb.map_id].grown = grown;
+    }
+    DeviceMap &m = ctx->maps[jb.map_id];
+    if (aux_stride && (m.aux_stride != aux_stride || !m.d_aux)) {
+      if (m.d_aux) hipFree(m.d_aux);
+      m.d_aux = nullptr;
+      const size_t bytes = (size_t)m.pitch * m.height * aux_stride * sizeof(double);
+      SLAMHIP_CHECK(hipMalloc(&m.d_aux, bytes));
+      SLAMHIP_CHECK(hipMemsetAsync(m.d_aux, 0, bytes, ctx->stream));
+      m.aux_stride = aux_stride;
+    }
+  }
+  // arena, grids
+  std::vector<mu_plan::JobShape> shapes;
+  std::vector<mu_plan::JobGrid> grids;
+  for (int k : round) {
+    const MuFleetJob &pj = prep[k];
+    shapes.push_back(mu_plan::JobShape{jobs[k].n, pj.total, pj.kw.n_bins});
+    grids.push_back(mu_plan::job_grid(jobs[k].n, pj.kw.w, pj.kw.h, fs.scanners[pj.scanner].near_r));
+  }
+  const mu_plan::ArenaLayout lay = mu_plan::plan_arena(shapes, sizeof(MuLine), sizeof(MuBeam));
+  const mu_plan::GridPlan gp = mu_plan::plan_grid(grids);
+  if (!gp.fits) return fail("the batch needs more than 2^31 workgroups in one launch: split it");
+  const size_t table_bytes = mu_plan::align_up(sizeof(MuBatchJob) * K) + 2 * sizeof(unsigned) * (K + 1);
+  {
+    int rc = mu_fleet_reserve(&fs.arena, &fs.cap_arena, lay.arena_bytes, (size_t)1 << 20, false);
+    if (!rc) rc = mu_fleet_reserve(&fs.h_stage, &fs.cap_stage, lay.upload_bytes, (size_t)1 << 18, true);
+    if (!rc) rc = mu_fleet_reserve(&fs.d_table, &fs.cap_table, table_bytes, (size_t)1 << 14, false);
+    if (!rc) rc = mu_fleet_reserve(&fs.h_table, &fs.cap_htable, table_bytes, (size_t)1 << 14, true);
+    if (rc) return rc;
+  }
+  if (lay.irr_words > fs.cap_irr) {
+    const size_t cap = mu_plan::grow_capacity(fs.cap_irr, lay.irr_words, (size_t)1 << 16);
+    if (fs.irr) hipFree(fs.irr);  // (all zero: nothing to carry over)
+    fs.irr = nullptr;
+    fs.cap_irr = 0;
+    SLAMHIP_CHECK(hipMalloc(&fs.irr, sizeof(unsigned) * cap));
+    SLAMHIP_CHECK(hipMemsetAsync(fs.irr, 0, sizeof(unsigned) * cap, ctx->stream));
+    fs.cap_irr = cap;
+  }
+  if ((size_t)K > fs.cap_status) {
+    const size_t cap = mu_plan::grow_capacity(fs.cap_status, (size_t)K, 64);
+    if (fs.d_status) hipFree(fs.d_status);
+    if (fs.h_status) hipHostFree(fs.h_status);
+    fs.d_status = fs.h_status = nullptr;
+    fs.cap_status = 0;
+    SLAMHIP_CHECK(hipMalloc(&fs.d_status, 2 * sizeof(unsigned long long) * cap));
+    SLAMHIP_CHECK(hipMemsetAsync(fs.d_status, 0, 2 * sizeof(unsigned long long) * cap, ctx->stream));
+    SLAMHIP_CHECK(hipHostMalloc(&fs.h_status, 2 * sizeof(unsigned long long) * cap, hipHostMallocDefault));
+    fs.cap_status = cap;
+  }
+  // staging: all scans of the round in one block, one copy
+  MuBatchJob *tj = reinterpret_cast<MuBatchJob *>(fs.h_table);
+  unsigned *t_line = reinterpret_cast<unsigned *>(fs.h_table + mu_plan::align_up(sizeof(MuBatchJob) * K));
+  unsigned *t_cell = t_line + (K + 1);
+  for (int i = 0; i < K; ++i) {
+    const int k = round[i];
+    const slamhip_map_update_job &jb = jobs[k];
+    const MuFleetJob &pj = prep[k];
+    const mu_plan::JobSlices &sl = lay.jobs[i];
+    const size_t n = (size_t)jb.n;
+    double *st = reinterpret_cast<double *>(fs.h_stage + sl.scan);
+    std::memcpy(st, jb.range, sizeof(double) * n);
+    std::memcpy(st + n, pj.cos_a, sizeof(double) * n);
+    std::memcpy(st + 2 * n, pj.sin_a, sizeof(double) * n);
+    if (jb.quality) std::memcpy(st + 3 * n, jb.quality, sizeof(double) * n);
+    if (jb.is_occ) std::memcpy(fs.h_stage + sl.occ, jb.is_occ, sizeof(int) * n);
+    std::memcpy(fs.h_stage + sl.host_offsets, pj.h_off.data(), sizeof(unsigned) * n);
+
+    const DeviceMap &m = ctx->maps[jb.map_id];
+    const MuScannerTable &tab = fs.scanners[pj.scanner];
+    const slamhip_scan_adder_cfg *jc = jb.cfg ? jb.cfg : cfg;  // (rule and estimator are the call's: checked)
+    MuArgs &a = tj[i].a;
+    std::memset(&tj[i], 0, sizeof(MuBatchJob));
+    a.n_jobs = 1;
+    a.payload = m.d_payload;
+    a.aux = aux_stride ? m.d_aux : nullptr;
+    a.width = m.width;
+    a.height = m.height;
+    a.pitch = m.pitch;
+    a.origin_x = m.origin_x;
+    a.origin_y = m.origin_y;
+    a.nbr_on = (m.nbr_ok && m.cell_model == SLAMHIP_CELL_GMAPPING) ? 1 : 0;
+    a.nbr_th = m.nbr_th;
+    a.prob = (m.prob_ok && cell_is_belief(m.cell_model)) ? m.d_prob : nullptr;
+    a.prob_model = m.cell_model;
+    a.cell_dbl = cell_doubles(m.cell_model);
+    a.aux_stride = aux_stride;
+    a.scale = m.scale;
+    const double *d_scan = reinterpret_cast<const double *>(fs.arena + sl.scan);
+    a.range = d_scan;
+    a.cos_a = d_scan + n;
+    a.sin_a = d_scan + 2 * n;
+    a.is_occ = jb.is_occ ? reinterpret_cast<const int *>(fs.arena + sl.occ) : nullptr;
+    a.beam_quality = jb.quality ? d_scan + 3 * n : nullptr;
+    a.n = jb.n;
+    a.px = pj.pose[0];
+    a.py = pj.pose[1];
+    ::sincos(pj.pose[2], &a.sn, &a.cs);
+    a.rule = rule;
+    a.est_kind = cfg->occupancy_estimator;
+    a.shift_amount = jc->area_shift_amount > 0 ? jc->area_shift_amount : 0.01 * m.scale;
+    a.quality = jb.scan_quality * 1.0;  // IdleOMQE
+    a.base_occ_prob = jc->base_occupied_prob;
+    a.base_occ_qual = jc->base_occupied_qual;
+    a.base_empty_prob = jc->base_empty_prob;
+    a.base_empty_qual = jc->base_empty_qual;
+    a.blur = jc->blur;
+    a.max_range_sq = jc->max_range * jc->max_range;
+    a.counts = reinterpret_cast<unsigned *>(fs.arena + sl.counts);
+    a.offsets = reinterpret_cast<unsigned *>(fs.arena + sl.offsets);
+    a.beam_end = reinterpret_cast<double *>(fs.arena + sl.beam_end);
+    a.beam_inv = reinterpret_cast<double *>(fs.arena + sl.beam_inv);
+    a.beam_info = reinterpret_cast<MuBeam *>(fs.arena + sl.beam_info);
+    a.n_padding = fs.d_status + 2 * i;
+    a.error_flag = reinterpret_cast<int *>(fs.d_status + 2 * i + 1);
+    a.host_offsets = reinterpret_cast<const unsigned *>(fs.arena + sl.host_offsets);
+    a.near_words = (jb.n + 63) / 64;
+    a.keys = fs.arena + sl.keys;
+    a.keys_cap = (unsigned long long)pj.total;
+    a.key_x0 = pj.kw.x0;
+    a.key_y0 = pj.kw.y0;
+    a.key_w = pj.kw.w;
+    a.key_h = pj.kw.h;
+    a.n_bins = (unsigned)pj.kw.n_bins;
+    a.near_r = tab.near_r;
+    a.robot_ix = (int)std::floor(a.px / a.scale) + m.origin_x;
+    a.robot_iy = (int)std::floor(a.py / a.scale) + m.origin_y;
+    a.lines = reinterpret_cast<MuLine *>(fs.arena + sl.lines);
+    a.lut = tab.d_lut;
+    a.lut_bins = kGatherLut;
+    ::sincos(pj.heading + tab.a0, &a.rot_s, &a.rot_c);
+    a.irr_bits = fs.irr + sl.irr;
+    a.bad = fs.arena + sl.bad;
+    tj[i].near_blocks = grids[i].near_blocks;
+    tj[i].far_blocks = grids[i].far_blocks;
+    t_line[i] = gp.line_off[i];
+    t_cell[i] = gp.cell_off[i];
+  }
+  t_line[K] = gp.line_off[K];
+  t_cell[K] = gp.cell_off[K];
+  SLAMHIP_CHECK(hipMemcpyAsync(fs.arena, fs.h_stage, lay.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(fs.d_table, fs.h_table, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+  MuBatchTable tb;
+  tb.jobs = reinterpret_cast<const MuBatchJob *>(fs.d_table);
+  tb.line_off = reinterpret_cast<const unsigned *>(fs.d_table + mu_plan::align_up(sizeof(MuBatchJob) * K));
+  tb.cell_off = tb.line_off + (K + 1);
+  tb.n_jobs = K;
+  const dim3 lgrid(gp.line_off[K]), cgrid(gp.cell_off[K]), block(256);
+  const int est = cfg->occupancy_estimator;
+  if (est == 1) hipLaunchKernelGGL(k_mu_lines_batch<1>, lgrid, block, 0, ctx->stream, tb);
+  else hipLaunchKernelGGL(k_mu_lines_batch<0>, lgrid, block, 0, ctx->stream, tb);
+#define SLAMHIP_MU_CELLS_BATCH(R)                                                             \
+  case R:                                                                                     \
+    if (est == 1) hipLaunchKernelGGL((k_mu_cells_batch<R, 1>), cgrid, block, 0, ctx->stream, tb); \
+    else hipLaunchKernelGGL((k_mu_cells_batch<R, 0>), cgrid, block, 0, ctx->stream, tb);      \
+    break;
+  switch (rule) {
+    SLAMHIP_MU_CELLS_BATCH(0)
+    SLAMHIP_MU_CELLS_BATCH(1)
+    SLAMHIP_MU_CELLS_BATCH(2)
+    SLAMHIP_MU_CELLS_BATCH(3)
+    default:
+      SLAMHIP_MU_CELLS_BATCH(4)
+  }
+#undef SLAMHIP_MU_CELLS_BATCH
+  unsigned seq = ++ctx->seq;
+  if (seq == 0) seq = ++ctx->seq;
+  hipLaunchKernelGGL(k_mu_finish_batch, dim3(1), block, 0, ctx->stream, fs.d_status, 2 * K, fs.h_status, ctx->h_done_flag, seq);
+  SLAMHIP_CHECK(hipGetLastError());
+  fs.launches += 3;
+  fs.rounds += 1;
+  fs.jobs_shared += K;
+  const int wrc = score_wait(ctx, seq);
+  if (wrc) {
+    // (what the kernels left behind is unknown: the marker words and status pairs start from zero again)
+    hipStreamSynchronize(ctx->stream);
+    hipMemset(fs.irr, 0, sizeof(unsigned) * fs.cap_irr);
+    hipMemset(fs.d_status, 0, 2 * sizeof(unsigned long long) * fs.cap_status);
+    return wrc;
+  }
+  bool internal = false;
+  for (int i = 0; i < K; ++i) {
+    const int k = round[i];
+    const unsigned long long pad = ((volatile unsigned long long *)fs.h_status)[2 * i];
+    const int err = (int)((volatile unsigned long long *)fs.h_status)[2 * i + 1];
+    n_updates[k] = (long long)((unsigned long long)prep[k].total - pad);
+    if (err == 2) internal = true;
+    else if (err) {
+      if (status) status[k] = SLAMHIP_ERR_STATE;
+      *any_left = true;
+    }
+  }
+  if (internal) return fail("internal: the device counted more cell updates than the host sized the buffers for", SLAMHIP_ERR_STATE);
+  return SLAMHIP_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -806,6 +1157,170 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   return SLAMHIP_OK;
 }
 
+int slamhip_map_append_scan_batch(slamhip_ctx *ctx, const slamhip_scan_adder_cfg *cfg, int n_jobs,
+                                  const slamhip_map_update_job *jobs, long long *n_updates, int *status) {
+  if (!ctx || !cfg || n_jobs < 0 || (n_jobs > 0 && (!jobs || !n_updates))) return fail("null argument");
+  const int rule = cfg->rule;
+  if (rule < SLAMHIP_RULE_LAST || rule > SLAMHIP_RULE_GMAPPING) return fail("unknown cell update rule");
+  if (cfg->occupancy_estimator != 0 && cfg->occupancy_estimator != 1) return fail("unknown occupancy estimator");
+  for (int k = 0; k < n_jobs; ++k) {
+    n_updates[k] = 0;
+    if (status) status[k] = SLAMHIP_OK;
+  }
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  MuFleetScratch &fs = fleet_of(ctx);
+  fs.rounds = fs.jobs_shared = fs.jobs_lone = fs.launches = 0;
+  ++fs.call;
+  // ---- everything the host can know, before a launch and before a map is touched: arguments, the rule against every
+  // map's cells, end points, the windows after growth, which jobs the shared launches cover
+  std::vector<MuFleetJob> prep(n_jobs);
+  std::vector<mu_plan::JobKind> kinds(n_jobs);
+  std::vector<std::pair<int, mu_plan::Window>> windows;  // of the maps the batch names, as the jobs in front leave them
+  const bool shared_ok = n_jobs > 1 && ctx->low_latency && ctx->k6_path == 0;
+  for (int k = 0; k < n_jobs; ++k) {
+    const slamhip_map_update_job &jb = jobs[k];
+    MuFleetJob &pj = prep[k];
+    if (!jb.range || (!jb.angle && (!jb.cos_a || !jb.sin_a))) return fail("null argument");
+    if (jb.map_id < 0 || jb.map_id >= (int)ctx->maps.size() || !ctx->maps[jb.map_id].bound) return fail("unknown map id");
+    if (jb.n > 8192 * 1024) return fail("too many scan points");
+    const slamhip_scan_adder_cfg *jc = jb.cfg ? jb.cfg : cfg;
+    if (jc->rule != rule || jc->occupancy_estimator != cfg->occupancy_estimator)
+      return fail("a job's own adder settings must name the rule and the occupancy estimator of the call");
+    const DeviceMap &m = ctx->maps[jb.map_id];
+    const bool ok_model = (rule == SLAMHIP_RULE_TBM && cell_is_belief(m.cell_model)) ||
+                          (rule == SLAMHIP_RULE_GMAPPING && m.cell_model == SLAMHIP_CELL_GMAPPING) ||
+                          (rule <= SLAMHIP_RULE_MEAN && m.cell_model == SLAMHIP_CELL_OCC);
+    if (!ok_model) return fail("cell update rule does not fit the map's payload model");
+    kinds[k] = mu_plan::JobKind{jb.map_id, false, true};
+    if (jb.n <= 0) continue;
+    const int n = jb.n;
+    pj.heading = jb.pose[2];
+    pj.pose[0] = jb.pose[0];
+    pj.pose[1] = jb.pose[1];
+    if (jb.angle) {  // slamhip_map_append_scan_raw's directions, from the heading-free pose
+      double (*volatile p_sin)(double) = ::sin;
+      double (*volatile p_cos)(double) = ::cos;
+      pj.raw_cos.resize(n);
+      pj.raw_sin.resize(n);
+      for (int b = 0; b < n; ++b) {
+        const double x = jb.pose[2] + jb.angle[b];
+        pj.raw_cos[b] = p_cos(x);
+        pj.raw_sin[b] = p_sin(x);
+      }
+      pj.cos_a = pj.raw_cos.data();
+      pj.sin_a = pj.raw_sin.data();
+      pj.pose[2] = 0.0;
+    } else {
+      pj.cos_a = jb.cos_a;
+      pj.sin_a = jb.sin_a;
+      pj.pose[2] = jb.pose[2];
+    }
+    // the host pass of the lone call: the same IEEE operations as the device's give every beam's first key slot
+    double sn, cs;
+    ::sincos(pj.pose[2], &sn, &cs);
+    const double px = pj.pose[0], py = pj.pose[1], scale = m.scale, max_range_sq = jc->max_range * jc->max_range;
+    const int rcx = (int)std::floor(px / scale), rcy = (int)std::floor(py / scale);
+    pj.bb = mu_plan::CellBox{rcx, rcy, rcx, rcy};
+    pj.h_off.resize(n);
+    unsigned total = 0;
+    for (int b = 0; b < n; ++b) {
+      pj.h_off[b] = total;
+      const double c = cs * pj.cos_a[b] - sn * pj.sin_a[b];
+      const double s = sn * pj.cos_a[b] + cs * pj.sin_a[b];
+      const double wx = px + jb.range[b] * c, wy = py + jb.range[b] * s;
+      const double ddx = wx - px, ddy = wy - py;
+      if (max_range_sq < ddx * ddx + ddy * ddy) continue;
+      if (!(std::fabs(wx / scale) < 1073741824.0) || !(std::fabs(wy / scale) < 1073741824.0))
+        return fail("a scan point that is not range-gated has a non-finite or absurdly far end point "
+                    "(no-return beams need a finite range or slam/mapping/max_range)");
+      const int ocx = (int)std::floor(wx / scale), ocy = (int)std::floor(wy / scale);
+      total += (unsigned)(std::abs(ocx - rcx) + std::abs(ocy - rcy) + 1);
+      pj.bb.lo_x = std::min(pj.bb.lo_x, ocx);
+      pj.bb.hi_x = std::max(pj.bb.hi_x, ocx);
+      pj.bb.lo_y = std::min(pj.bb.lo_y, ocy);
+      pj.bb.hi_y = std::max(pj.bb.hi_y, ocy);
+    }
+    pj.total = total;
+    if (total == 0) continue;
+    pj.empty = false;
+    kinds[k].empty = false;
+    // the window the job finds: the map's, as the jobs in front of it on the same map leave it
+    size_t wi = 0;
+    while (wi < windows.size() && windows[wi].first != jb.map_id) ++wi;
+    if (wi == windows.size()) windows.push_back({jb.map_id, mu_plan::Window{m.width, m.height, m.origin_x, m.origin_y}});
+    mu_plan::Window &win = windows[wi].second;
+    if (m.auto_grow) {
+      const int g = mu_plan::grow_window(&win, pj.bb);
+      if (g < 0)
+        return fail("an unbounded map would grow beyond 2^31 cells: a scan point far outside the site?", SLAMHIP_ERR_STATE);
+      pj.grows = g > 0;
+    }
+    pj.win = win;
+    pj.kw = mu_plan::key_window(win, pj.bb);
+    bool shared = shared_ok && n <= 4096 && pj.kw.n_bins > 0 && pj.kw.n_bins <= (1ll << 22);
+    if (shared) {
+      const int trc = jb.angle ? mu_scanner_table(fs, n, true, jb.angle, nullptr, &pj.scanner)
+                               : mu_scanner_table(fs, n, false, jb.cos_a, jb.sin_a, &pj.scanner);
+      if (trc) return trc;
+      shared = pj.scanner >= 0 && fs.scanners[pj.scanner].ok;
+    }
+    pj.lone = !shared;
+    kinds[k].lone = pj.lone;
+  }
+  // ---- the steps, in order
+  bool any_left = false;
+  for (const mu_plan::Step &st : mu_plan::plan_steps(kinds)) {
+    if (!st.lone) {
+      const int rc = mu_fleet_round(ctx, fs, cfg, jobs, prep, st.jobs, n_updates, status, &any_left);
+      if (rc) return rc;
+      continue;
+    }
+    const int k = st.jobs[0];
+    const slamhip_map_update_job &jb = jobs[k];
+    MuScratch &sc = scratch_of(ctx);
+    const bool was_deferred = sc.deferred;
+    // (the call is awaited; an awaited lone update re-uses the staging slot of the first queued one)
+    if (was_deferred && sc.pending) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    sc.deferred = false;
+    slamhip_scan_adder_cfg one = jb.cfg ? *jb.cfg : *cfg;
+    one.scan_quality = jb.scan_quality;
+    long long nu = 0;
+    const int rc = jb.angle ? slamhip_map_append_scan_raw(ctx, jb.map_id, &one, jb.pose, jb.n, jb.range, jb.angle, jb.is_occ,
+                                                          jb.quality, &nu)
+                            : slamhip_map_append_scan_q(ctx, jb.map_id, &one, jb.pose, jb.n, jb.range, jb.cos_a, jb.sin_a,
+                                                        jb.is_occ, jb.quality, &nu);
+    sc.deferred = was_deferred;
+    fs.jobs_lone += 1;
+    n_updates[k] = nu;
+    if (rc == SLAMHIP_ERR_STATE) {
+      if (status) status[k] = rc;
+      any_left = true;
+    } else if (rc) {
+      return rc;
+    }
+  }
+  if (any_left) return fail(kLeavesWindow, SLAMHIP_ERR_STATE);
+  return SLAMHIP_OK;
+}
+
+int slamhip_map_update_batch_stats(slamhip_ctx *ctx, int *rounds, int *jobs_in_shared_launches, int *jobs_lone, int *launches) {
+  if (!ctx) return fail("null argument");
+  const MuFleetScratch &fs = fleet_of(ctx);
+  if (rounds) *rounds = fs.rounds;
+  if (jobs_in_shared_launches) *jobs_in_shared_launches = fs.jobs_shared;
+  if (jobs_lone) *jobs_lone = fs.jobs_lone;
+  if (launches) *launches = fs.launches;
+  return SLAMHIP_OK;
+}
+
+int slamhip_map_update_batch_tables(slamhip_ctx *ctx, int *tables, long long *uploads) {
+  if (!ctx) return fail("null argument");
+  const MuFleetScratch &fs = fleet_of(ctx);
+  if (tables) *tables = (int)fs.scanners.size();
+  if (uploads) *uploads = fs.table_uploads;
+  return SLAMHIP_OK;
+}
+
 int slamhip_map_download_aux(slamhip_ctx *ctx, int map_id, int x0, int y0, int w, int h, double *out) {
   if (!ctx || !out) return fail("null argument");
   if (map_id < 0 || map_id >= (int)ctx->maps.size() || !ctx->maps[map_id].bound) return fail("unknown map id");
@@ -1244,6 +1759,17 @@ void mu_release(slamhip_ctx *ctx) {
     if (s.h_occ_stage) hipHostFree(s.h_occ_stage);
     delete &s;
     ctx->mu_scratch = nullptr;
+  }
+  if (ctx->mu_kscratch) {
+    MuFleetScratch &s = *static_cast<MuFleetScratch *>(ctx->mu_kscratch);
+    for (void *p : {(void *)s.arena, (void *)s.d_table, (void *)s.irr, (void *)s.d_status})
+      if (p) hipFree(p);
+    for (void *p : {(void *)s.h_stage, (void *)s.h_table, (void *)s.h_status})
+      if (p) hipHostFree(p);
+    for (MuScannerTable &t : s.scanners)
+      if (t.d_lut) hipFree(t.d_lut);
+    delete &s;
+    ctx->mu_kscratch = nullptr;
   }
   if (ctx->mu_bscratch) {
     MuBatchScratch &s = *static_cast<MuBatchScratch *>(ctx->mu_bscratch);

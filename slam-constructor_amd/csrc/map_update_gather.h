@@ -34,12 +34,14 @@ constexpr int kGatherLut = 4096;  // bins of the angle table over [0, 2 pi)
 constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 // ---- k_mu_lines -------------------------------------------------------------------------------------------------
+// the work of ONE workgroup on beam b of the update `a` (the lone kernel hands in its by-value argument block, the batch
+// kernel its job's block in the job table)
 template <int EST>
-__global__ __launch_bounds__(256) void k_mu_lines(MuArgs a) {
+__device__ __forceinline__ void mu_lines_body(const MuArgs &a, const int b) {
   __shared__ int s_ok[4];
   __shared__ double s_c[8];   // e0, A, B, q0, absA, inv_W, absB of the beam (made by wave 0 alone)
   __shared__ int s_i[8];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   MuLine line{0.0, 0.0, 0.0, 0u, 0u, 0, 0, 0.0, 0.0, 0.0};  // (thread 0 keeps it and writes it once, at the end)
   if (wave == 0) {
     const MuJob j = mu_job(a, b);
@@ -223,6 +225,32 @@ __global__ __launch_bounds__(256) void k_mu_lines(MuArgs a) {
   if (pad) atomicAdd(a.n_padding, (unsigned long long)pad);
 }
 
+template <int EST>
+__global__ __launch_bounds__(256) void k_mu_lines(MuArgs a) {
+  mu_lines_body<EST>(a, (int)blockIdx.x);
+}
+
+// K updates in ONE launch (slamhip_map_append_scan_batch): a job table in HBM -- every job's argument block and the
+// workgroups of its cells -- and the first workgroup of every job in the two flat grids (map_update_batch_plan.h).
+// All of it is indexed by blockIdx alone: workgroup-uniform addresses, which the compiler reads through the scalar
+// unit wherever no store of the kernel stands in front of the load.
+struct MuBatchJob {
+  MuArgs a;
+  unsigned near_blocks, far_blocks;
+  unsigned pad[2];
+};
+struct MuBatchTable {
+  const MuBatchJob *jobs;
+  const unsigned *line_off, *cell_off;  // n_jobs + 1 entries each
+  int n_jobs;
+};
+
+template <int EST>
+__global__ __launch_bounds__(256) void k_mu_lines_batch(MuBatchTable tb) {
+  const int job = mu_plan::find_job(tb.line_off, tb.n_jobs, blockIdx.x);
+  mu_lines_body<EST>(tb.jobs[job].a, (int)(blockIdx.x - tb.line_off[job]));
+}
+
 // ---- k_mu_cells -------------------------------------------------------------------------------------------------
 // does beam b (closed form L) stand on the cell (dxc, dyc) away from the robot's at step k = |dxc| + |dyc| ?
 __device__ __forceinline__ bool mu_line_visits(const MuLine &L, int dxc, int dyc, unsigned k) {
@@ -356,8 +384,9 @@ __device__ __forceinline__ void mu_block_min_max(int *s_red, int t, int lo, int 
 // cell, (2 near_r + 1)^2 of them): one wave each, four per workgroup, behind the far workgroups.  Either way the
 // workgroup stages the closed forms of the beams its cells may ask -- the union of their candidate ranges, 512 at a
 // time -- in LDS: a thread's candidates are then an LDS read apart, not an L2 round trip.
+// The work of workgroup `wg` of the update `a`, which has near_blocks near workgroups in front of its far ones.
 template <int RULE, int EST>
-__global__ __launch_bounds__(256) void k_mu_cells(MuArgs a, unsigned far_blocks) {
+__device__ __forceinline__ void mu_cells_body(const MuArgs &a, const unsigned wg, const unsigned near_blocks) {
   __shared__ MuLine s_line[kGatherChunk];
   __shared__ double s_buf[4][5][64];
   __shared__ int s_red[8];
@@ -366,9 +395,8 @@ __global__ __launch_bounds__(256) void k_mu_cells(MuArgs a, unsigned far_blocks)
   const int rcx = rbx - a.origin_x, rcy = rby - a.origin_y;  // ... external
   const int side = 2 * a.near_r + 1;
   // (the near workgroups come FIRST: behind 700 far ones they started when those were through, 21 us late)
-  const unsigned near_blocks = gridDim.x - far_blocks;
-  const bool far_wg = blockIdx.x >= near_blocks;
-  const unsigned far_id = blockIdx.x - near_blocks;
+  const bool far_wg = wg >= near_blocks;
+  const unsigned far_id = wg - near_blocks;
   // ---- this thread's (far) or this wave's (near) cell
   int ix, iy;
   bool inside, mine;  // inside the window; a cell this thread / wave works on
@@ -379,7 +407,7 @@ __global__ __launch_bounds__(256) void k_mu_cells(MuArgs a, unsigned far_blocks)
     inside = ix < a.key_x0 + a.key_w && iy < a.key_y0 + a.key_h;
     mine = inside && !(abs(ix - rbx) <= a.near_r && abs(iy - rby) <= a.near_r);
   } else {
-    const unsigned cell_id = blockIdx.x * 4u + (unsigned)wave;
+    const unsigned cell_id = wg * 4u + (unsigned)wave;
     const bool exists = cell_id < (unsigned)(side * side);
     ix = rbx + (exists ? (int)(cell_id % (unsigned)side) - a.near_r : 0);
     iy = rby + (exists ? (int)(cell_id / (unsigned)side) - a.near_r : 0);
@@ -534,6 +562,31 @@ __global__ __launch_bounds__(256) void k_mu_cells(MuArgs a, unsigned far_blocks)
     if (loaded) mu_cell_store<RULE>(a, at, c, was);
     if (irregular) a.irr_bits[key] = 0u;
   }
+}
+
+template <int RULE, int EST>
+__global__ __launch_bounds__(256) void k_mu_cells(MuArgs a, unsigned far_blocks) {
+  mu_cells_body<RULE, EST>(a, blockIdx.x, gridDim.x - far_blocks);
+}
+
+// (every workgroup of the flat grid has a job and every job's workgroups have cells: nobody leaves early)
+template <int RULE, int EST>
+__global__ __launch_bounds__(256) void k_mu_cells_batch(MuBatchTable tb) {
+  const int job = mu_plan::find_job(tb.cell_off, tb.n_jobs, blockIdx.x);
+  const MuBatchJob &j = tb.jobs[job];
+  mu_cells_body<RULE, EST>(j.a, blockIdx.x - tb.cell_off[job], j.near_blocks);
+}
+
+// the status pairs of a round's jobs (padding records, error flag) handed to the host at once, the words back to zero
+__global__ __launch_bounds__(256) void k_mu_finish_batch(unsigned long long *status, int n_words,
+                                                         unsigned long long *h_status, unsigned *flag, unsigned seq) {
+  for (int k = threadIdx.x; k < n_words; k += 256) {
+    h_status[k] = status[k];
+    status[k] = 0ull;
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace slamhip

@@ -421,6 +421,7 @@ struct slamhip_ctx {
   hipEvent_t ev_fork = nullptr;
   void *shard = nullptr;  // RCCL group of the context (shard.cpp), or null
   void *mu_scratch = nullptr, *mu_bscratch = nullptr;  // K6 work buffers (map_update.hip), owned by the context
+  void *mu_kscratch = nullptr;  // ... of slamhip_map_append_scan_batch: the per-job arena, staging, direction tables
   unsigned char *d_render = nullptr;  // the render kernels' output (map_render.hip): grows on demand, freed with the context
   size_t render_cap = 0;
   void *d_scan_gen = nullptr;  // slamhip_map_generate_scans' block in HBM (scan_generate.hip): grows on demand, freed with the context

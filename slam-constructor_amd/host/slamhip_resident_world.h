@@ -64,16 +64,48 @@ public:
   }
 
   void handle_observation(TransformedLaserScan &tr_scan) override {
+    match_scan(tr_scan);
+    if (!prepare_update(tr_scan)) return;
+    slamhip_scan_adder_cfg adder = _cfg.adder;
+    adder.scan_quality = tr_scan.quality;
+    const RobotPose p = pose();
+    const double p3[3] = {p.x, p.y, p.theta};
+    const int n = (int)_r.size();
+    long long nu = 0;
+    // strict with the raw provider (the reference's default): the scan adder's end points are cos / sin(theta + a) by the
+    // host's libm, the reference's bits -- what the area estimator's occupancies and TBM / GMapping payloads depend on
+    // continuously (slamhip_map_append_scan_raw); else the provider's table and the cached provider's angle addition
+    if (update_is_raw())
+      slamhip_or_die(slamhip_map_append_scan_raw(_ctx, _cfg.map_id, &adder, p3, n, _r.data(), _a.data(), _occ.data(),
+                                                 _cfg.omqe ? _q.data() : nullptr, &nu), "map_append_scan_raw");
+    else
+      slamhip_or_die(slamhip_map_append_scan_q(_ctx, _cfg.map_id, &adder, p3, n, _r.data(), _c.data(), _s.data(), _occ.data(),
+                                               _cfg.omqe ? _q.data() : nullptr, &nu), "map_append_scan");
+    if (nu > 0) _cell_updates += nu;  // (-1: queued, counted by cell_updates())
+    _view->invalidate();
+  }
+
+  // K worlds, one scan each: every world's match as in handle_observation, then ONE slamhip_map_append_scan_batch per
+  // group of worlds that share a context and the adder's rule and estimator (slamhip_resident_world.h, below)
+  friend inline void hip_handle_observations(std::vector<HipResidentWorld *> &worlds,
+                                             std::vector<TransformedLaserScan *> &scans);
+
+private:
+  // the first half of handle_observation: the match, the pose, the scan's quality
+  void match_scan(TransformedLaserScan &tr_scan) {
     _gsm->reset_state();
     auto pose_delta = RobotPoseDelta{};
     _gsm->process_scan(tr_scan, pose(), map(), pose_delta);  // the mirror is resident: nothing is uploaded
     update_robot_pose(pose_delta);
     tr_scan.quality = pose_delta ? _cfg.localized_scan_quality : _cfg.raw_scan_quality;
-
+  }
+  bool update_is_raw() const { return _cfg.raw_exact && _cfg.trig.mode != SLAMHIP_TRIG_CACHED; }
+  // the scan as GridMapScanAdder::append_scan takes it, left in _r / _a / _occ / _q / _c / _s; false: no points
+  bool prepare_update(const TransformedLaserScan &tr_scan) {
     // GridMapScanAdder::append_scan (grid_map_scan_adders.h:54-75): the points [margin, n - margin - 1]; the
     // observation quality estimator is reset on the WHOLE scan and asked per point index (:63-71)
     const auto &pts = tr_scan.scan.points();
-    if (pts.empty()) return;
+    if (pts.empty()) return false;
     const size_t first = _cfg.scan_margin, last = pts.size() - _cfg.scan_margin - 1;
     std::vector<double> &r = _r, &a = _a, &q = _q;
     std::vector<int> &occ = _occ;
@@ -110,25 +142,9 @@ public:
         slamhip_or_die(slamhip_beam_trig_raw(n, a.data(), c.data(), s.data()), "beam_trig_raw");
       _trig_a = a;
     }
-    slamhip_scan_adder_cfg adder = _cfg.adder;
-    adder.scan_quality = tr_scan.quality;
-    const RobotPose p = pose();
-    const double p3[3] = {p.x, p.y, p.theta};
-    long long nu = 0;
-    // strict with the raw provider (the reference's default): the scan adder's end points are cos / sin(theta + a) by the
-    // host's libm, the reference's bits -- what the area estimator's occupancies and TBM / GMapping payloads depend on
-    // continuously (slamhip_map_append_scan_raw); else the provider's table and the cached provider's angle addition
-    if (_cfg.raw_exact && _cfg.trig.mode != SLAMHIP_TRIG_CACHED)
-      slamhip_or_die(slamhip_map_append_scan_raw(_ctx, _cfg.map_id, &adder, p3, n, r.data(), a.data(), occ.data(),
-                                                 _cfg.omqe ? q.data() : nullptr, &nu), "map_append_scan_raw");
-    else
-      slamhip_or_die(slamhip_map_append_scan_q(_ctx, _cfg.map_id, &adder, p3, n, r.data(), c.data(), s.data(), occ.data(),
-                                               _cfg.omqe ? q.data() : nullptr, &nu), "map_append_scan");
-    if (nu > 0) _cell_updates += nu;  // (-1: queued, counted by cell_updates())
-    _view->invalidate();
+    return true;
   }
 
-private:
   slamhip_ctx *_ctx;
   std::shared_ptr<HipGridScanMatcher> _gsm;
   Config _cfg;
@@ -137,6 +153,65 @@ private:
   std::vector<double> _r, _a, _q, _c, _s, _all_r, _all_a, _all_q, _trig_a;  // per-scan buffers, kept between scans
   std::vector<int> _occ;
 };
+
+// K robots, one scan each: the matches one after the other as in handle_observation (K matches in one call are
+// hip_process_raw_scans', slamhip_reference_adapter.h), then the map updates of all worlds that share a context, a
+// cell rule and an occupancy estimator in ONE slamhip_map_append_scan_batch -- every job carries its world's own
+// adder settings.  Each world stands once in the list.  The call is awaited; updates the worlds queued before stay
+// queued (cell_updates() drains them).
+inline void hip_handle_observations(std::vector<HipResidentWorld *> &worlds, std::vector<TransformedLaserScan *> &scans) {
+  const size_t K = worlds.size() < scans.size() ? worlds.size() : scans.size();
+  std::vector<char> ready(K, 0), done(K, 0);
+  for (size_t k = 0; k < K; ++k)
+    for (size_t i = 0; i < k; ++i)
+      if (worlds[i] == worlds[k]) {  // (its scan buffers hold one scan, and its second match needs the first update)
+        std::cerr << "hip_handle_observations: a world is listed twice" << std::endl;
+        std::exit(-1);
+      }
+  for (size_t k = 0; k < K; ++k) {
+    worlds[k]->match_scan(*scans[k]);
+    ready[k] = worlds[k]->prepare_update(*scans[k]) ? 1 : 0;
+  }
+  for (size_t k0 = 0; k0 < K; ++k0) {
+    if (!ready[k0] || done[k0]) continue;
+    HipResidentWorld &lead = *worlds[k0];
+    std::vector<size_t> group;
+    for (size_t k = k0; k < K; ++k) {
+      HipResidentWorld &w = *worlds[k];
+      if (!ready[k] || done[k] || w._ctx != lead._ctx || w._cfg.adder.rule != lead._cfg.adder.rule ||
+          w._cfg.adder.occupancy_estimator != lead._cfg.adder.occupancy_estimator)
+        continue;
+      group.push_back(k);
+      done[k] = 1;
+    }
+    std::vector<slamhip_map_update_job> jobs(group.size());
+    std::vector<long long> nu(group.size(), 0);
+    for (size_t i = 0; i < group.size(); ++i) {
+      HipResidentWorld &w = *worlds[group[i]];
+      const RobotPose p = w.pose();
+      slamhip_map_update_job &j = jobs[i];
+      j.map_id = w._cfg.map_id;
+      j.pose[0] = p.x;
+      j.pose[1] = p.y;
+      j.pose[2] = p.theta;
+      j.scan_quality = scans[group[i]]->quality;
+      j.n = (int)w._r.size();
+      j.range = w._r.data();
+      j.cos_a = w._c.data();
+      j.sin_a = w._s.data();
+      j.angle = w.update_is_raw() ? w._a.data() : nullptr;
+      j.is_occ = w._occ.data();
+      j.quality = w._cfg.omqe ? w._q.data() : nullptr;
+      j.cfg = &w._cfg.adder;
+    }
+    slamhip_or_die(slamhip_map_append_scan_batch(lead._ctx, &lead._cfg.adder, (int)jobs.size(), jobs.data(), nu.data(), nullptr),
+                   "map_append_scan_batch");
+    for (size_t i = 0; i < group.size(); ++i) {
+      worlds[group[i]]->_cell_updates += nu[i];
+      worlds[group[i]]->_view->invalidate();
+    }
+  }
+}
 
 // the scan adder's half of a resident world's configuration: init_occ_estimator / init_omqe / init_scan_adder
 // (init_occupancy_mapping.h:38-92) and whether the strict mode takes the raw provider's end points
