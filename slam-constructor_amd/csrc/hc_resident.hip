@@ -81,6 +81,17 @@ __device__ __forceinline__ void wave_min2(double &a, double &b) {
   HCR_MIN_STEP(32) HCR_MIN_STEP(16) HCR_MIN_STEP(8) HCR_MIN_STEP(4) HCR_MIN_STEP(2) HCR_MIN_STEP(1)
 #undef HCR_MIN_STEP
 }
+// sum mod 2^64 over a wave (every lane ends with it): the fingerprint partial of a wave that does not sum terms
+__device__ __forceinline__ unsigned long long wave_xor_sum_u64(unsigned long long h) {
+#define HCR_ADD_STEP(OFF)                                                                            \
+  {                                                                                                  \
+    const unsigned ol = lane_xor_u32<OFF>((unsigned)h), oh = lane_xor_u32<OFF>((unsigned)(h >> 32)); \
+    h += ((unsigned long long)oh << 32) | ol;                                                        \
+  }
+  HCR_ADD_STEP(32) HCR_ADD_STEP(16) HCR_ADD_STEP(8) HCR_ADD_STEP(4) HCR_ADD_STEP(2) HCR_ADD_STEP(1)
+#undef HCR_ADD_STEP
+  return h;
+}
 
 // s_sel: what the pose of the next super-step is read from
 constexpr int kSelRescore = -1;  // the same tree once more (an unsettled comparison): the poses just scored
@@ -126,6 +137,12 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
   __shared__ HcState s_st;              // root state of the super-step being scored
   __shared__ double s_part[H][4];
   __shared__ unsigned long long s_hpart[H][4];
+  // Workgroups of more than four waves per pose (512 and 1024 threads, not a pair): between barriers (B) and (C) the
+  // four summing waves used to do the float partials AND the fingerprint while the others watched.  The fingerprint
+  // is a sum mod 2^64 -- any order, any split gives the same value --, so the watching waves make it, each over a
+  // contiguous share of the beams, and hand one partial per wave to thread 0 in s_hidle
+  constexpr int kFpWaves = NTH / 64 > 4 ? NTH / 64 - 4 : 0;
+  __shared__ unsigned long long s_hidle[kFpWaves > 0 ? kFpWaves : 1];
   __shared__ double s_cert[2][16];  // the bookkeeping workgroup's certificate: per-wave minima (see "certificate" below)
   __shared__ int s_cert_end;        // the replay's verdict: the chain ends on a certified root
   // (testing builds: the kernel's first instruction on the wall clock -- spare stamp 6 of super-step 0: what the prologue costs)
@@ -256,6 +273,7 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
   }
   const bool verify = a.verify != 0;
   const bool stamp = SLAMHIP_STAMPS_ON(a.stamps && slot == 1 && tl == 0 && blockIdx.y == 0);
+  [[maybe_unused]] const bool stamp_wave = SLAMHIP_STAMPS_ON(a.stamps && slot == 1 && tl < 64 && blockIdx.y == 0);  // (its whole wave)
   if (stamp) a.stamps[6] = t_kernel_begin;
   HcGranule *const gran = &rc->gran[0][0];
   HcGranule *const gseq = &rc->seq[0][0];
@@ -647,6 +665,17 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
       cert_r = tr;
     }
     if (stamp && k < 64) ap->stamps[8 * k + 4] = wall_clock64();
+#ifdef SLAMHIP_TESTING
+    // testing: a LATE workgroup (debug_mute < 0: -(workgroup + 1 + 65536 (every + 16 phase)); workgroup + 1 == 0xffff: the
+    // bookkeeping one) spends ~2 us here, in front of its granule's store, in the super-steps k with k % every == phase
+    // -- everybody's sweep of those super-steps then needs a re-poll.  Bounded (five short sleeps): a delay, nobody
+    // gives up.
+    if (ap->debug_mute < 0) {
+      const int dm = -ap->debug_mute, every = (dm >> 16) & 15, phase = (dm >> 20) & 15, who = dm & 0xffff;
+      if ((who == 0xffff ? init_slot : (int)blockIdx.x + 1 == who) && every > 0 && k % every == phase)
+        for (int q = 0; q < 5; ++q) __builtin_amdgcn_s_sleep(16);
+    }
+#endif
     if (go) {
       if (SEQ) {
         // the reference's own order: one running sum over the beams (weighted_mean_point_probability_spe.h:108-124)
@@ -675,17 +704,29 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
         for (int b = tl; b < n; b += kSumLanes) {
           const double term = my_term[b];
           acc = acc + term;
-          if (verify) {
+          if (kFpWaves == 0 && verify) {
             h += term_fingerprint(term, k_lo, k_hi);
             k_lo += 2u * kSumLanes * 0x9E3779B1u;
             k_hi += 2u * kSumLanes * 0x85EBCA6Bu;
           }
         }
-        wave_xor_sum_with(acc, h);
+        if (kFpWaves == 0) wave_xor_sum_with(acc, h);
+        else acc = wave_xor_sum(acc);  // (the same butterfly without the fingerprint's exchanges: the same bits)
         if (lane == 0) {
           s_part[half][lwave] = acc;
-          s_hpart[half][lwave] = h;
+          if (kFpWaves == 0) s_hpart[half][lwave] = h;
         }
+      } else if (kFpWaves > 0 && verify) {
+        // a wave that does not sum: the fingerprint of beams [w per, (w + 1) per), multipliers (2b + 1) C as above
+        // (a share may be empty -- few beams -- : its partial is 0)
+        const int w = lwave - kSumLanes / 64;
+        const int per = (n + kFpWaves - 1) / kFpWaves;
+        const int b_end = (w + 1) * per < n ? (w + 1) * per : n;
+        unsigned long long h = 0ull;
+        for (int b = w * per + lane; b < b_end; b += 64)
+          h += term_fingerprint(my_term[b], (2u * (unsigned)b + 1u) * 0x9E3779B1u, (2u * (unsigned)b + 1u) * 0x85EBCA6Bu);
+        h = wave_xor_sum_u64(h);
+        if (lane == 0) s_hidle[w] = h;
       }
     }
     __syncthreads();  // (C) (the terms are rewritten by the next super-step)
@@ -693,8 +734,14 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
       if (!SEQ) {
         if (tl == 0) {
           const double total = (s_part[half][0] + s_part[half][1]) + (s_part[half][2] + s_part[half][3]);
-          const unsigned long long fp =
-              verify ? fold_fingerprint48(s_hpart[half][0] + s_hpart[half][1] + s_hpart[half][2] + s_hpart[half][3]) : 0ull;
+          unsigned long long fp = 0ull;
+          if (verify) {
+            unsigned long long h = 0ull;
+            if (kFpWaves == 0) h = s_hpart[half][0] + s_hpart[half][1] + s_hpart[half][2] + s_hpart[half][3];
+#pragma unroll
+            for (int w = 0; w < kFpWaves; ++w) h += s_hidle[w];
+            fp = fold_fingerprint48(h);
+          }
           gran_store(&gran[pk * kGranRow + slot], (scan.tot_w == 0.0) ? __builtin_nan("") : total / scan.tot_w, fp, tag);
         }
         if (verify && mode && tl == 64) {
@@ -805,6 +852,8 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
       const int n_grid = 6 * ap->max_inst;  // scoring slots (+ the bookkeeping workgroup's)
       const bool rescored = !SEQ && verify && sp.mode == 1;
       bool failed = false;
+      unsigned sweep_polls = 0u;  // (testing builds: what the stamped workgroup's sweep took, spare stamp 6)
+      int missing_first = 0;
       {
         const HcGranule *g0 = gran + pk * kGranRow;
         unsigned spins = 0;
@@ -828,6 +877,8 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
               s_sc[j] = gran_score(g[q]);
               s_hash[j] = gran_hash(g[q]);
             }
+            // (testing builds: granules still missing behind the first poll, over the wave)
+            if (SLAMHIP_STAMPS_ON(stamp_wave) && spins == 0u) missing_first += __popcll(__ballot(!here && i <= n_grid));
           }
           if (__all(ok)) break;
           ++spins;
@@ -842,6 +893,7 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
             }
           }
         }
+        sweep_polls = spins + 1u;
       }
       if (stamp && k < 64) ap->stamps[8 * k + 1] = wall_clock64();
       if (failed || k + 1 >= kHcResidentMaxSteps) {
@@ -991,6 +1043,10 @@ __global__ __launch_bounds__(NT, 4) void k_hc_chain_resident(HcChainArgs a) {
           }
         }
         if (stamp && k < 64) ap->stamps[8 * k + 2] = wall_clock64();
+        // (testing builds, spare stamp 6 of the super-steps from the fourth on -- the first three hold the prologue's and
+        // the chain's ends --: polls this sweep took | granules still missing behind its first poll << 32; written here,
+        // behind the last stamp of the super-step, so that it lengthens none of the stamped phases)
+        if (stamp && k >= 3 && k < 64) ap->stamps[8 * k + 6] = (long long)sweep_polls | ((long long)missing_first << 32);
         if (lane == 0) {
           s_cert_end = cert_end ? 1 : 0;
           // the bookkeeping half of the next root state (`sp` above is this very object: the trace was written from

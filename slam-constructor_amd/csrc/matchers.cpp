@@ -2608,7 +2608,8 @@ int slamhip_matcher_set_tie_check(slamhip_matcher *m, int on) {
 #ifdef SLAMHIP_TESTING
 // debugging aid, not part of include/slamhip.h: wall-clock stamps (100 MHz) of workgroup 1 inside the
 // first 64 super-steps of the following process_scan calls: kernel entry, staged, replayed, pose ready,
-// terms ready, score stored, two spare
+// terms ready, score stored, two spare (the co-resident 1-cell chain, spare stamp 6 of the super-steps from the fourth
+// on: polls the stamped workgroup's sweep took | granules still missing behind its first poll << 32)
 int slamhip_matcher_debug_stamps(slamhip_matcher *m, long long *out512) {
   if (!m) return invalid_arg("null matcher");
   if (!m->d_stamps) {
@@ -3181,7 +3182,10 @@ int slamhip_matcher_debug_fail_next(slamhip_matcher *m, int n) {
   return SLAMHIP_OK;
 }
 // testing aid, not part of include/slamhip.h: workgroup `slot_plus_1 - 1` of the following co-resident launches leaves
-// at once (0 = none) -- what a workgroup that never became resident looks like to the others
+// at once (0 = none) -- what a workgroup that never became resident looks like to the others.
+// A NEGATIVE argument delays instead (the lone and batched 1-cell / window chains, hc_resident.hip):
+// -(workgroup + 1 + 65536 (every + 16 phase)), workgroup + 1 == 0xffff for the bookkeeping one: that workgroup is
+// ~2 us late with its granule in the super-steps k with k % every == phase; nothing gives up
 int slamhip_matcher_debug_resident_mute(slamhip_matcher *m, int slot_plus_1) {
   if (!m) return invalid_arg("null matcher");
   m->debug_resident_mute = slot_plus_1;

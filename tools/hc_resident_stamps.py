@@ -60,3 +60,22 @@ for threads, check in [(1024, 1), (1024, 0), (512, 1), (256, 1), (1024, -1), (51
     nxt = (st[1:, 0] - st[:-1, 2]) / 100.0
     print("  replay end -> next super-step's start %.2f; super-step to super-step %.2f us" %
           (nxt.mean(), (np.diff(st[:, 0]) / 100.0).mean()))
+    if not (mc or gm):
+        # spare stamp 6 of the super-steps from the fourth on: polls workgroup 1's sweep took | granules still missing
+        # behind its first poll << 32 -- over 24 matches from jittered initial poses
+        polls, missing = [], []
+        rs = np.random.RandomState(7)
+        for _ in range(24):
+            L.slamhip_matcher_debug_stamps(m.h, None)
+            m.process_scan(0, sc["init_pose"] + rs.randn(3) * [0.05, 0.05, 0.02])
+            L.slamhip_matcher_debug_stamps(m.h, buf)
+            w = np.array(list(buf)).reshape(64, 8)[3:min(m.stats()["launches"], 64), 6]
+            w = w[w > 0]
+            polls += list(w & 0xffffffff)
+            missing += list(w >> 32)
+        if polls:
+            polls, missing = np.array(polls), np.array(missing)
+            print("  polls per sweep over %d sweeps: %s; a second poll in %.0f %% of them" %
+                  (polls.size, {int(p): int(c) for p, c in zip(*np.unique(polls, return_counts=True))}, 100.0 * (polls > 1).mean()))
+            print("  granules missing behind the first poll, sweeps of more than one poll: median %d, quartiles %d / %d, max %d"
+                  % tuple(np.percentile(missing[polls > 1], [50, 25, 75, 100]).astype(int)) if (polls > 1).any() else "  (no re-polls)")
