@@ -126,21 +126,6 @@ void free_levels(slamhip_pyramid *p, bool release_maps) {
   p->plan.n = 0;
 }
 
-MapView view_of(const DeviceMap &m) {
-  MapView v;
-  std::memset(&v, 0, sizeof(v));
-  v.payload = m.d_payload;
-  v.width = m.width;
-  v.height = m.height;
-  v.pitch = m.pitch;
-  v.origin_x = m.origin_x;
-  v.origin_y = m.origin_y;
-  v.scale = m.scale;
-  v.inv_scale = 1.0 / m.scale;
-  for (int k = 0; k < 4; ++k) v.unknown[k] = m.unknown[k];
-  return v;
-}
-
 // plans the levels over the fine map as it is bound now, binds them and queues the whole build
 int make_levels(slamhip_pyramid *p) {
   slamhip_ctx *ctx = p->ctx;

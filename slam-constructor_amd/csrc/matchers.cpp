@@ -60,6 +60,23 @@ template <class T>
 using PinnedBuf = HipBlock<T, true>;
 constexpr unsigned kPinnedCoherent = hipHostMallocMapped | hipHostMallocCoherent;
 
+// A block that holds `cap` units of `per` elements and has to hold `need`: nothing, or the stream waited for (what runs
+// on it may read the block that goes away) and `floor` doubled up to `need` units allocated in its place.  alloc frees
+// first and a failed one leaves the owner empty, so the stored capacity is zero from the free to the success: an error
+// return never leaves an old capacity over a null block.
+template <class T, bool kPinned, class Cap>
+int grow_block(hipStream_t stream, HipBlock<T, kPinned> &block, Cap &cap, size_t need, size_t floor, size_t per = 1,
+               unsigned pinned_flags = 0) {
+  if (need <= (size_t)cap) return SLAMHIP_OK;
+  SLAMHIP_CHECK(hipStreamSynchronize(stream));
+  size_t grown = floor;
+  while (grown < need) grown *= 2;
+  cap = 0;
+  SLAMHIP_CHECK(block.alloc(per * grown, pinned_flags));
+  cap = (Cap)grown;
+  return SLAMHIP_OK;
+}
+
 // {chains-done counter (0), initial poses, a table with one Entry per chain}: one block per side that ONE pull kernel
 // moves in front of a launch (launch_block_pull)
 template <class Entry>
@@ -134,7 +151,7 @@ struct HcBatch : slamhip::ChainSet<slamhip::HcResidentCtl, slamhip::HcJobView> {
   bool resident_call = false;  // hc_resident_asked() of the call in flight, asked once
   slamhip::PinnedBuf<double> h_scan;  // the batch's scans: per match five arrays of its beam count
   slamhip::DeviceBuf<double> d_scan;
-  size_t scan_cap = 0;  // doubles
+  size_t scan_cap = 0, h_scan_cap = 0;  // doubles d_scan / h_scan hold (they grow together)
   bool pair = false;    // the co-resident launch's workgroups (512 threads) score two poses per super-step
   int cus = 0;          // CUs of the device (sizes the pair form's trees)
   slamhip::PinnedBuf<slamhip::HcTraceEntry> h_trace;  // cap x trace_per entries (observer attached only)
@@ -172,7 +189,7 @@ struct McBatch {
   slamhip::PinnedBuf<unsigned> h_done_count;
   slamhip::DeviceBuf<slamhip::McPair> d_tape;
   slamhip::PinnedBuf<double> h_tape;
-  size_t tape_cap = 0;  // pairs
+  size_t tape_cap = 0, h_tape_cap = 0;  // pairs d_tape / h_tape hold (they grow together)
   slamhip::PinnedBuf<slamhip::McTraceEntry> h_trace;  // trace_chains x trace_per entries (observer attached only)
   size_t trace_per = 0;
   int trace_chains = 0;
@@ -866,12 +883,13 @@ int many_chains_prepare(slamhip_ctx *ctx, Set &s, int n, int want, double reach,
   }
   const int total = n * (6 * s.shapes.max_inst + 1);
   s.nt = total <= 256 ? 1024 : (total <= 512 ? 512 : 256);
-  if (n > s.cap) {
+  if (n > s.cap) {  // (three blocks and what clears them: not grow_block's one)
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
     s.d_rctl.reset();
     s.rctl_grid = s.rctl_chains = 0;
     int cap = cap0;
     while (cap < n) cap *= 2;
+    s.cap = 0;
     SLAMHIP_CHECK(s.d_ctl.alloc(cap));
     SLAMHIP_CHECK(hipMemsetAsync(s.d_ctl.get(), 0, sizeof(HcChainCtl) * cap, ctx->stream));
     SLAMHIP_CHECK(s.h_out.alloc(cap, kPinnedCoherent));
@@ -1059,7 +1077,8 @@ bool batch_chain_eligible(slamhip_matcher *m) {
 constexpr int kBatchWgs = 1024;
 constexpr int kBatchTracePer = 1 << 14;  // trace entries per chain (a longer match is redone by the single path)
 
-// the maps of the shared launches: bound, 1-cell, of one cell model (asked before anything is staged or launched)
+// the maps of a batch's jobs, asked ONCE per call, before anything is staged or launched: bound -- and, for the shared
+// launches (cell_model_out given), 1-cell and of one cell model
 template <class Job>
 int batch_maps_check(slamhip_ctx *ctx, int n, const Job *jobs, int *cell_model_out) {
   int cell_model = -1;
@@ -1067,11 +1086,12 @@ int batch_maps_check(slamhip_ctx *ctx, int n, const Job *jobs, int *cell_model_o
     const int id = jobs[c].map_id;
     const DeviceMap *dm = (id >= 0 && id < (int)ctx->maps.size() && ctx->maps[id].bound) ? &ctx->maps[id] : nullptr;
     if (!dm) return invalid_arg("unknown map id in a match job");
+    if (!cell_model_out) continue;
     if (dm->cell_model == SLAMHIP_CELL_GMAPPING) return invalid_arg("the batch form covers the 1-cell OOPE (OCC / TBM cells)");
     if (cell_model >= 0 && dm->cell_model != cell_model) return invalid_arg("the maps of one batch must share a cell model");
     cell_model = dm->cell_model;
   }
-  *cell_model_out = cell_model;
+  if (cell_model_out) *cell_model_out = cell_model;
   return SLAMHIP_OK;
 }
 
@@ -1082,6 +1102,12 @@ struct BatchScanBlock {
   int n = 0;
   double tot_w = 0;
 };
+// a job's map and scan in its entry of a staged job table (HcJobView, McJobView)
+template <class JobView>
+void fill_job_view(JobView &v, const DeviceMap &dm, const BatchScanBlock &k) {
+  v.map = view_of(dm);
+  v.scan = scan_view_of(k.d, k.stride, k.n, k.tot_w);
+}
 
 // The batch's scans: stored scans are read where they lie; scans handed over as host arrays go into one arena with one
 // copy (the staging buffers are free: the previous batch returned after its chains had ended, i.e. long after its
@@ -1092,14 +1118,9 @@ int hc_batch_stage_scans(slamhip_matcher *m, int n, const slamhip_match_job *job
   size_t doubles = 0;
   for (int c = 0; c < n; ++c)
     if (jobs[c].scan_slot < 0) doubles += 5 * (size_t)((jobs[c].n + 7) & ~7);
-  if (doubles > b->scan_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    size_t cap = 1 << 14;
-    while (cap < doubles) cap *= 2;
-    SLAMHIP_CHECK(b->h_scan.alloc(cap, hipHostMallocDefault));
-    SLAMHIP_CHECK(b->d_scan.alloc(cap));
-    b->scan_cap = cap;
-  }
+  int rc = grow_block(ctx->stream, b->h_scan, b->h_scan_cap, doubles, 1 << 14, 1, hipHostMallocDefault);
+  if (!rc) rc = grow_block(ctx->stream, b->d_scan, b->scan_cap, doubles, 1 << 14);
+  if (rc) return rc;
   size_t at = 0;
   for (int c = 0; c < n; ++c) {
     const slamhip_match_job &j = jobs[c];
@@ -1133,9 +1154,10 @@ int hc_batch_stage_scans(slamhip_matcher *m, int n, const slamhip_match_job *job
   return SLAMHIP_OK;
 }
 
-// The shared launches over n matches whose scans lie in HBM (blocks); a job gives its map and its initial pose.
+// The shared launches over n matches whose scans lie in HBM (blocks); a job gives its map and its initial pose
+// (cell_model: batch_maps_check's answer, asked by the entry point).
 template <class Job>
-int hc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBlock *blocks) {
+int hc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBlock *blocks, int cell_model) {
   slamhip_ctx *ctx = m->ctx;
   HcBatch *b = m->batch.get();
   if (!b->d_shapes) {
@@ -1164,42 +1186,16 @@ int hc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
     const int rc = many_chains_prepare(ctx, *b, n, want, 0.002, 8);
     if (rc) return rc;
   }
-  if (m->has_obs && b->trace_chains < b->cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (m->has_obs) {  // (one slice of kBatchTracePer entries per chain the blocks hold)
     b->trace_per = kBatchTracePer;
-    SLAMHIP_CHECK(b->h_trace.alloc((size_t)b->trace_per * b->cap, kPinnedCoherent));
-    b->trace_chains = b->cap;
-  }
-  int max_n = 0;
-  for (int c = 0; c < n; ++c) max_n = std::max(max_n, blocks[c].n);
-  int cell_model = -1;
-  {
-    const int rc = batch_maps_check(ctx, n, jobs, &cell_model);
+    const int rc = grow_block(ctx->stream, b->h_trace, b->trace_chains, b->cap, b->cap, kBatchTracePer, kPinnedCoherent);
     if (rc) return rc;
   }
+  int max_n = 0;
   for (int c = 0; c < n; ++c) {
-    const Job &j = jobs[c];
-    const DeviceMap *dm = &ctx->maps[j.map_id];
-    HcJobView &v = b->stage.h_table()[c];
-    v.map.payload = dm->d_payload;
-    v.map.width = dm->width;
-    v.map.height = dm->height;
-    v.map.pitch = dm->pitch;
-    v.map.origin_x = dm->origin_x;
-    v.map.origin_y = dm->origin_y;
-    v.map.scale = dm->scale;
-    v.map.inv_scale = 1.0 / dm->scale;
-    for (int q = 0; q < 4; ++q) v.map.unknown[q] = dm->unknown[q];
-    const double *ds = blocks[c].d;
-    const size_t stride = blocks[c].stride;
-    v.scan.n = blocks[c].n;
-    v.scan.tot_w = blocks[c].tot_w;
-    v.scan.range = ds;
-    v.scan.cos_a = ds + stride;
-    v.scan.sin_a = ds + 2 * stride;
-    v.scan.weight = ds + 3 * stride;
-    v.scan.factor = ds + 4 * stride;
-    for (int q = 0; q < 3; ++q) b->stage.h_inits()[3 * c + q] = j.init_pose[q];
+    max_n = std::max(max_n, blocks[c].n);
+    fill_job_view(b->stage.h_table()[c], ctx->maps[jobs[c].map_id], blocks[c]);
+    for (int q = 0; q < 3; ++q) b->stage.h_inits()[3 * c + q] = jobs[c].init_pose[q];
   }
   hipStream_t st = ctx->stream;
   // (counter = 0, initial poses, job table: one pull of the pinned block)
@@ -1588,6 +1584,14 @@ bool mc_chain_eligible(slamhip_matcher *m) {
   return m->chain_mode >= 1;
 }
 
+// pairs of the tape one match can consume: three pairs per two candidates, and every reset_shift (at most one per
+// max_failed / 3 + 1 candidates) may drop a triple's second half
+size_t mc_tape_need(const GaussianPoseEnumerator *pe) {
+  const size_t max_poses = pe->max_poses();
+  const size_t resets = max_poses / (pe->max_failed() / 3 + 1) + 2;
+  return 3 * (max_poses / 2 + 2 + resets) + 8;
+}
+
 int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
                           double *out_prob) {
   slamhip_ctx *ctx = m->ctx;
@@ -1610,12 +1614,10 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
   int rc = score_views(ctx, map_id, &m->cfg, &a.map, &a.scan, &cell_model, nullptr, &oie_eff);  // (TBM: through the plane)
   if (rc) return rc;
   // the enumerator is reset when a match starts (pose_enumeration_scan_matcher.h:47): what carries over from
-  // match to match is the engine, i.e. the position on the pair tape.  A match draws three pairs per two
-  // candidates; every reset_shift (at most one per max_failed / 3 + 1 candidates) may drop a triple's second half.
+  // match to match is the engine, i.e. the position on the pair tape.
   pe->reset();
   const size_t max_poses = pe->max_poses();
-  const size_t resets = max_poses / (pe->max_failed() / 3 + 1) + 2;
-  const size_t need = 3 * (max_poses / 2 + 2 + resets) + 8;
+  const size_t need = mc_tape_need(pe);
   // The pairs live in HBM as a window [tape_base, tape_base + tape_filled) of the tape, filled AHEAD: while a
   // chain runs, the host (spinning anyway) generates the pairs of the next match and a side stream uploads them,
   // so a match in steady state starts without touching the tape.  The window is restarted when it runs out.
@@ -1803,14 +1805,6 @@ int mc_batch_slots(const slamhip_matcher *m, int n, unsigned max_failed, unsigne
   return (int)std::max<long long>(1, s);
 }
 
-// pairs of the tape one match can consume (mc_chain_process_scan: three pairs per two candidates, every reset_shift may
-// drop a triple's second half)
-size_t mc_tape_need(const GaussianPoseEnumerator *pe) {
-  const size_t max_poses = pe->max_poses();
-  const size_t resets = max_poses / (pe->max_failed() / 3 + 1) + 2;
-  return 3 * (max_poses / 2 + 2 + resets) + 8;
-}
-
 // The shared launches over n matches whose scans lie in HBM (blocks); job c gives its map and initial pose and runs on
 // engine stream streams[c].  Results go to m->batch->res[c]; a chain whose trace outgrew its slice is left to the lone
 // route (on_chain false, its stream as it was).
@@ -1826,7 +1820,7 @@ int mc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
   const unsigned max_failed = pe0->max_failed(), max_poses = pe0->max_poses();
   const size_t need = mc_tape_need(pe0);
   if (!s->h_done_count) SLAMHIP_CHECK(s->h_done_count.alloc(1, kPinnedCoherent));
-  if (n > s->cap) {
+  if (n > s->cap) {  // (three blocks and what clears them: not grow_block's one)
     SLAMHIP_CHECK(hipStreamSynchronize(st));
     int cap = 8;
     while (cap < n) cap *= 2;
@@ -1839,23 +1833,18 @@ int mc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
     if (rc) return rc;
     s->cap = cap;
   }
-  if ((size_t)n * need > s->tape_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    size_t cap = 1 << 14;
-    while (cap < (size_t)n * need) cap *= 2;
-    s->tape_cap = 0;
-    static_assert(sizeof(McPair) == 2 * sizeof(double), "the pinned staging holds pairs as two doubles");
-    SLAMHIP_CHECK(s->d_tape.alloc(cap));
-    SLAMHIP_CHECK(s->h_tape.alloc(2 * cap, hipHostMallocDefault));
-    s->tape_cap = cap;
-  }
+  static_assert(sizeof(McPair) == 2 * sizeof(double), "the pinned staging holds pairs as two doubles");
+  int grc = grow_block(st, s->d_tape, s->tape_cap, (size_t)n * need, 1 << 14);
+  if (!grc) grc = grow_block(st, s->h_tape, s->h_tape_cap, (size_t)n * need, 1 << 14, 2, hipHostMallocDefault);
+  if (grc) return grc;
   const size_t trace_need = (size_t)max_poses + 2;
-  if (m->has_obs && (s->trace_chains < s->cap || s->trace_per < trace_need)) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    s->trace_chains = 0;
-    SLAMHIP_CHECK(s->h_trace.alloc(trace_need * (size_t)s->cap, kPinnedCoherent));
-    s->trace_per = trace_need;
-    s->trace_chains = s->cap;
+  if (m->has_obs) {  // (one slice of trace_per entries per chain the blocks hold)
+    if (s->trace_per < trace_need) {  // (slices too short for these matches: all of them anew)
+      s->trace_chains = 0;
+      s->trace_per = trace_need;
+    }
+    grc = grow_block(st, s->h_trace, s->trace_chains, s->cap, s->cap, s->trace_per, kPinnedCoherent);
+    if (grc) return grc;
   }
   // every job's enumerator starts its match (pose_enumeration_scan_matcher.h:47); the windows of the K tapes in ONE
   // arena, one copy (the arena is free: the call before returned after its chains had ended)
@@ -1869,26 +1858,8 @@ int mc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
   SLAMHIP_CHECK(hipMemcpyAsync(s->d_tape.get(), s->h_tape.get(), sizeof(McPair) * need * (size_t)n, hipMemcpyHostToDevice, st));
   for (int c = 0; c < n; ++c) {
     const Job &j = jobs[c];
-    const DeviceMap *dm = &ctx->maps[j.map_id];
     McJobView &v = s->stage.h_table()[c];
-    v.map.payload = dm->d_payload;
-    v.map.width = dm->width;
-    v.map.height = dm->height;
-    v.map.pitch = dm->pitch;
-    v.map.origin_x = dm->origin_x;
-    v.map.origin_y = dm->origin_y;
-    v.map.scale = dm->scale;
-    v.map.inv_scale = 1.0 / dm->scale;
-    for (int q = 0; q < 4; ++q) v.map.unknown[q] = dm->unknown[q];
-    const double *ds = blocks[c].d;
-    const size_t stride = blocks[c].stride;
-    v.scan.n = blocks[c].n;
-    v.scan.tot_w = blocks[c].tot_w;
-    v.scan.range = ds;
-    v.scan.cos_a = ds + stride;
-    v.scan.sin_a = ds + 2 * stride;
-    v.scan.weight = ds + 3 * stride;
-    v.scan.factor = ds + 4 * stride;
+    fill_job_view(v, ctx->maps[j.map_id], blocks[c]);
     v.tape = s->d_tape.get() + need * (size_t)c;
     for (int q = 0; q < 3; ++q) v.init[q] = j.init_pose[q];
     v.trace = m->has_obs ? s->h_trace.get() + s->trace_per * (size_t)c : nullptr;
@@ -2019,6 +1990,126 @@ struct McStreamSwap {
     std::swap(m->mc_matches, m->mc_streams[k].matches);
   }
 };
+
+// A batch call's fall-backs work on the context's CURRENT scan: each selects, uploads or filters its job's scan into that
+// place.  The keeper records the caller's own selection in front of the first of them (arm) and puts it back when the
+// call ends, error returns included -- or, where that selection was the upload buffer and a fall-back has overwritten
+// it, invalidates it, so that a later process_scan fails loudly instead of scoring another robot's scan.
+struct ScanKeeper {
+  slamhip_ctx *ctx;
+  bool armed = false, saved_is_upload = false;
+  bool upload_overwritten = false;  // set by the call: a fall-back's scan went through the context's upload buffer
+  const double *saved_ptr = nullptr;
+  size_t saved_stride = 0;
+  int saved_n = 0;
+  double saved_tot_w = 0;
+  std::vector<double> saved_w, saved_f;
+  explicit ScanKeeper(slamhip_ctx *ctx_) : ctx(ctx_) {}
+  ScanKeeper(const ScanKeeper &) = delete;
+  ScanKeeper &operator=(const ScanKeeper &) = delete;
+  void arm() {
+    if (armed) return;
+    armed = true;
+    saved_ptr = ctx->scan_ptr;
+    saved_stride = ctx->scan_stride;
+    saved_n = ctx->scan_n;
+    saved_tot_w = ctx->scan_tot_w;
+    // (asked now: a lone call may replace the upload buffer by a larger one)
+    saved_is_upload = !saved_ptr || saved_ptr == ctx->d_scan;
+    saved_w = ctx->h_weight;
+    saved_f = ctx->h_factor;
+  }
+  ~ScanKeeper() {
+    if (!armed) return;
+    if (saved_is_upload && upload_overwritten) {
+      ctx->scan_n = 0;  // (its contents are gone: "no scan uploaded" from here on)
+    } else {
+      ctx->scan_ptr = saved_ptr;
+      ctx->scan_stride = saved_stride;
+      ctx->scan_n = saved_n;
+      ctx->scan_tot_w = saved_tot_w;
+      ctx->h_weight.swap(saved_w);
+      ctx->h_factor.swap(saved_f);
+      ctx->h_scan_angle.clear();  // (a stored scan has its slot's, if any, as slamhip_scan_select leaves it)
+      for (const slamhip_ctx::ScanSlot &sl : ctx->scan_slots)
+        if (sl.d == saved_ptr) ctx->h_scan_angle = sl.angle;
+      ctx->scan_angle_on_device = false;
+    }
+    ctx->scan_angle_lazy = false;
+  }
+};
+
+// THE hand-over of both batch calls, behind their chains: results in job order, the observer's events, the totals.
+//   live_of(c)   job c's place among the chains' jobs (its slice of their trace); negative: its scan kept nothing -- no
+//                launch, no observer call, its engine not advanced: 0 / 0 for every candidate, the lone call's answer
+//   lone(j, keep, delta, prob, &kept)   the lone call for a job the chains did not take or did not settle (a
+//                configuration they do not cover, a trace longer than a chain's slice), run on the job's engine stream
+//                and under the keeper; kept: the points of its scan
+// sid: the jobs' engine streams (empty: the matcher's own enumerator).  kept_n (optional): the points each job kept.
+template <class Job, class LiveOf, class Lone>
+int batch_hand_over(slamhip_matcher *m, int n_jobs, const Job *jobs, const std::vector<int> &sid, LiveOf &&live_of,
+                    double *out_deltas, double *out_probs, int *kept_n, Lone &&lone) {
+  constexpr bool kRaw = std::is_same<Job, slamhip_raw_match_job>::value;  // (its jobs' blocks are on record: raw_blocks)
+  HcBatch *b = m->batch.get();
+  const HcTraceEntry *chain_trace = b->h_trace.get();
+  size_t chain_trace_per = (size_t)b->trace_per;
+  if (!sid.empty() && m->mc_batch) {
+    chain_trace = reinterpret_cast<const HcTraceEntry *>(m->mc_batch->h_trace.get());
+    chain_trace_per = m->mc_batch->trace_per;
+  }
+  ScanKeeper keep(m->ctx);
+  long long calls = 0, evaluated = 0, steps = 0, rescored = 0;
+  for (int c = 0; c < n_jobs; ++c) {
+    BatchJobResult &r = b->res[c];
+    const Job &j = jobs[c];
+    double *dl = out_deltas + 3 * c;
+    const int live = live_of(c);
+    int kept = 0;
+    if (r.on_chain) {
+      if constexpr (kRaw) kept = b->raw_blocks[c].n;
+      for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
+      out_probs[c] = r.prob;
+      if (m->has_obs) {
+        replay_trace(m->obs, chain_trace + (size_t)live * chain_trace_per, r.calls);
+        if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
+      }
+    } else {
+      r = BatchJobResult{};
+      if (live < 0) {
+        dl[0] = dl[1] = dl[2] = 0.0;
+        out_probs[c] = std::numeric_limits<double>::quiet_NaN();
+      } else {
+        keep.arm();
+        int rc;
+        {
+          McStreamSwap own(m, sid.empty() ? -1 : sid[c]);  // (the job's engine for the call)
+          rc = lone(j, keep, dl, &out_probs[c], &kept);
+        }
+        if (rc) return rc;
+        if constexpr (kRaw) b->raw_blocks[c] = HcBatch::RawBlock{nullptr, 0, kept, true};
+        if (kept > 0) {
+          r.calls = m->job.scorer_calls;
+          r.evaluated = m->job.poses_evaluated;
+          r.steps = (int)m->job.launches;
+          r.rescored = m->chain_rescored;
+        }
+      }
+      for (int q = 0; q < 3; ++q) r.pose[q] = j.init_pose[q] + dl[q];
+      r.prob = out_probs[c];
+    }
+    if (kept_n) kept_n[c] = kept;
+    calls += r.calls;
+    evaluated += r.evaluated;
+    steps = std::max<long long>(steps, r.steps);
+    rescored += r.rescored;
+  }
+  m->job.scorer_calls = calls;
+  m->job.poses_evaluated = evaluated;
+  m->job.launches = steps;
+  m->chain_launched = b->kernels;
+  m->chain_rescored = rescored;
+  return SLAMHIP_OK;
+}
 
 // ---- the multi-resolution matcher ------------------------------------------------------------------
 // BruteForceMultiResolutionScanMatcher::process_scan: the engine's loop on the host, its scores from the pyramid -- the
@@ -2648,15 +2739,12 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
     chains = (jobs[c].scan_slot >= 0 ? ctx->scan_slots[jobs[c].scan_slot].n : jobs[c].n) <= 4096;
   int cell_model = -1;
   if (mc_streams) {
-    int rc = mc_job_streams_of(m, n_jobs, &sid);
+    const int rc = mc_job_streams_of(m, n_jobs, &sid);
     if (rc) return rc;
-    for (int c = 0; c < n_jobs; ++c)
-      if (jobs[c].map_id < 0 || jobs[c].map_id >= (int)ctx->maps.size() || !ctx->maps[jobs[c].map_id].bound)
-        return invalid_arg("unknown map id in a match job");
-    if (chains) {
-      rc = batch_maps_check(ctx, n_jobs, jobs, &cell_model);
-      if (rc) return rc;
-    }
+  }
+  if (chains || mc_streams) {  // (the lone route of a hill-climbing or brute-force job checks its map for itself)
+    const int rc = batch_maps_check(ctx, n_jobs, jobs, chains ? &cell_model : nullptr);
+    if (rc) return rc;
   }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
   if (!m->batch) m->batch = std::make_unique<HcBatch>();
@@ -2664,91 +2752,24 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
   b->res.assign(n_jobs, BatchJobResult{});
   b->kernels = 0;
   if (chains) {
-    int rc = mc_streams ? SLAMHIP_OK : batch_maps_check(ctx, n_jobs, jobs, &cell_model);
-    if (rc) return rc;
     std::vector<BatchScanBlock> blocks(n_jobs);
-    rc = hc_batch_stage_scans(m, n_jobs, jobs, blocks.data());
+    int rc = hc_batch_stage_scans(m, n_jobs, jobs, blocks.data());
     if (rc) return rc;
     rc = mc_streams ? mc_batch_run(m, n_jobs, jobs, blocks.data(), sid.data(), cell_model)
-                    : hc_batch_run(m, n_jobs, jobs, blocks.data());
+                    : hc_batch_run(m, n_jobs, jobs, blocks.data(), cell_model);
     if (rc) return rc;
   }
-  const HcTraceEntry *chain_trace = b->h_trace.get();
-  size_t chain_trace_per = (size_t)b->trace_per;
-  if (mc_streams && m->mc_batch) {
-    chain_trace = reinterpret_cast<const HcTraceEntry *>(m->mc_batch->h_trace.get());
-    chain_trace_per = m->mc_batch->trace_per;
-  }
-  // results in job order; a match the chains did not settle (a configuration they do not cover, a trace longer
-  // than a chain's buffer) goes through the single-match path: upload its scan, process_scan
-  long long calls = 0, evaluated = 0, steps = 0;
-  // The single-match path works on the context's CURRENT scan: a fallback selects or uploads the job's scan.  The
-  // caller's own selection is put back afterwards -- or, when a fallback upload has overwritten the very buffer it
-  // pointed at, invalidated, so that a later process_scan fails loudly instead of scoring another robot's scan
-  // 
-  const double *saved_ptr = ctx->scan_ptr;
-  const size_t saved_stride = ctx->scan_stride;
-  const int saved_n = ctx->scan_n;
-  const double saved_tot_w = ctx->scan_tot_w;
-  std::vector<double> saved_w, saved_f;
-  bool fell_back = false, uploaded = false;
-  for (int c = 0; c < n_jobs; ++c) {
-    BatchJobResult &r = b->res[c];
-    const slamhip_match_job &j = jobs[c];
-    double *dl = out_deltas + 3 * c;
-    if (r.on_chain) {
-      for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
-      out_probs[c] = r.prob;
-      if (m->has_obs) {
-        replay_trace(m->obs, chain_trace + (size_t)c * chain_trace_per, r.calls);
-        if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
-      }
-    } else {
-      if (!fell_back) {
-        saved_w = ctx->h_weight;
-        saved_f = ctx->h_factor;
-        fell_back = true;
-      }
-      uploaded = uploaded || j.scan_slot < 0;
-      int rc = j.scan_slot >= 0 ? slamhip_scan_select(ctx, j.scan_slot)
-                                : slamhip_scan_upload(ctx, j.n, j.range, j.cos_a, j.sin_a, j.weight, j.factor);
-      if (rc) return rc;
-      {
-        McStreamSwap own(m, mc_streams ? sid[c] : -1);  // (the job's engine for the call)
-        rc = slamhip_matcher_process_scan(m, j.map_id, j.init_pose, dl, &out_probs[c]);
-      }
-      if (rc) return rc;
-      r.calls = m->job.scorer_calls;
-      r.evaluated = m->job.poses_evaluated;
-      r.steps = (int)m->job.launches;
-      r.rescored = m->chain_rescored;
-      for (int q = 0; q < 3; ++q) r.pose[q] = j.init_pose[q] + dl[q];
-      r.prob = out_probs[c];
-    }
-    calls += r.calls;
-    evaluated += r.evaluated;
-    steps = std::max<long long>(steps, r.steps);
-  }
-  if (fell_back) {
-    if (uploaded && saved_ptr == ctx->d_scan) {
-      ctx->scan_n = 0;  // (its contents are gone: "no scan uploaded" from here on)
-    } else {
-      ctx->scan_ptr = saved_ptr;
-      ctx->scan_stride = saved_stride;
-      ctx->scan_n = saved_n;
-      ctx->scan_tot_w = saved_tot_w;
-      ctx->h_weight.swap(saved_w);
-      ctx->h_factor.swap(saved_f);
-    }
-  }
-  m->job.scorer_calls = calls;
-  m->job.poses_evaluated = evaluated;
-  m->job.launches = steps;
-  m->chain_launched = b->kernels;
-  long long resc = 0;
-  for (const BatchJobResult &r : b->res) resc += r.rescored;
-  m->chain_rescored = resc;
-  return SLAMHIP_OK;
+  // a job the chains did not take or did not settle: its scan selected or uploaded as the current one, process_scan
+  return batch_hand_over(
+      m, n_jobs, jobs, sid, [](int c) { return c; }, out_deltas, out_probs, nullptr,
+      [&](const slamhip_match_job &j, ScanKeeper &keep, double *delta, double *prob, int *kept) -> int {
+        keep.upload_overwritten = keep.upload_overwritten || j.scan_slot < 0;
+        const int rc = j.scan_slot >= 0 ? slamhip_scan_select(ctx, j.scan_slot)
+                                        : slamhip_scan_upload(ctx, j.n, j.range, j.cos_a, j.sin_a, j.weight, j.factor);
+        if (rc) return rc;
+        *kept = ctx->scan_n;
+        return slamhip_matcher_process_scan(m, j.map_id, j.init_pose, delta, prob);
+      });
 }
 
 int slamhip_matcher_batch_stats(slamhip_matcher *m, int job, long long *scorer_calls, long long *poses_evaluated,
@@ -2948,26 +2969,14 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       if (rc) return rc;
       // ---- the arenas (the stream is idle: the batch before returned after its chains had ended): the pinned one, its
       // rows filled; then the one in HBM
-      if (raw.arena_bytes > b->h_raw_cap) {
-        SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-        size_t cap = 1 << 16;
-        while (cap < raw.arena_bytes) cap *= 2;
-        b->h_raw_cap = 0;
-        SLAMHIP_CHECK(b->h_raw.alloc(cap, hipHostMallocMapped));
-        b->h_raw_cap = cap;
-      }
+      rc = grow_block(ctx->stream, b->h_raw, b->h_raw_cap, raw.arena_bytes, 1 << 16, 1, hipHostMallocMapped);
+      if (rc) return rc;
       rc = raw.fill(in.data(), b->h_raw.get());
       if (rc) return invalid_arg(scan_error_text(rc));
       // (the last check of the arguments lies behind: from here on the last batch's blocks may go)
-      if (raw.dst_doubles > b->d_raw_cap) {
-        SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-        size_t cap = 1 << 14;
-        while (cap < raw.dst_doubles) cap *= 2;
-        b->d_raw_cap = 0;
-        b->raw_blocks.clear();  // (they pointed into the block that goes away)
-        SLAMHIP_CHECK(b->d_raw.alloc(cap));
-        b->d_raw_cap = cap;
-      }
+      if (raw.dst_doubles > b->d_raw_cap) b->raw_blocks.clear();  // (they point into the block that goes away)
+      rc = grow_block(ctx->stream, b->d_raw, b->d_raw_cap, raw.dst_doubles, 1 << 14);
+      if (rc) return rc;
       // ---- the tables of the scanners this call has met for the first time: to HBM, as the lone call sends its one
       // (the call waits for the copies instead of keeping the sources alive; a later call with these scanners sends none)
       if (b->raw_tabs.size() < raw.slots.size()) b->raw_tabs.resize(raw.slots.size());
@@ -2977,14 +2986,8 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
         if (!sl.fresh || sl.used != raw.call) continue;
         HcBatch::RawTab &tab = b->raw_tabs[q];
         const int n = (int)sl.t.cos_a.size();
-        if (n > tab.cap) {
-          SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-          int cap = 2048;
-          while (cap < n) cap *= 2;
-          tab.cap = 0;
-          SLAMHIP_CHECK(tab.d.alloc(3 * (size_t)cap));
-          tab.cap = cap;
-        }
+        rc = grow_block(ctx->stream, tab.d, tab.cap, n, 2048, 3);  // (cos | sin | viny_f)
+        if (rc) return rc;
         const size_t bytes = sizeof(double) * n;
         SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get(), sl.t.cos_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
         SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + tab.cap, sl.t.sin_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -3031,7 +3034,7 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       b->res.assign(n_jobs, BatchJobResult{});
       b->kernels = 0;
       rc = mc_streams ? mc_batch_run(m, raw.n_live, live.data(), blocks.data(), live_sid.data(), cell_model)
-                      : hc_batch_run(m, raw.n_live, live.data(), blocks.data());
+                      : hc_batch_run(m, raw.n_live, live.data(), blocks.data(), cell_model);
       if (rc) return rc;
       // (the chains' results by live place -> by job)
       std::vector<BatchJobResult> by_live(b->res.begin(), b->res.begin() + raw.n_live);
@@ -3046,101 +3049,13 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
     b->kernels = 0;
     b->raw_blocks.assign(n_jobs, HcBatch::RawBlock{});
   }
-  // ---- results in job order.  A job the chains did not take or did not settle goes through the lone raw call, which
-  // works on the context's CURRENT scan: the caller's own selection is put back afterwards, or invalidated when it was
-  // the upload buffer the lone calls have overwritten (as slamhip_matcher_process_scan_batch leaves it)
-  long long calls = 0, evaluated = 0, steps = 0;
-  const double *saved_ptr = ctx->scan_ptr;
-  const size_t saved_stride = ctx->scan_stride;
-  const int saved_n = ctx->scan_n;
-  const double saved_tot_w = ctx->scan_tot_w;
-  // (asked now: a lone call may replace the upload buffer by a larger one)
-  const bool saved_is_upload = !saved_ptr || saved_ptr == ctx->d_scan;
-  std::vector<double> saved_w, saved_f;
-  bool fell_back = false;
-  auto restore = [&]() {
-    if (!fell_back) return;
-    if (saved_is_upload) {
-      ctx->scan_n = 0;  // (its contents are gone: "no scan uploaded" from here on)
-    } else {
-      ctx->scan_ptr = saved_ptr;
-      ctx->scan_stride = saved_stride;
-      ctx->scan_n = saved_n;
-      ctx->scan_tot_w = saved_tot_w;
-      ctx->h_weight.swap(saved_w);
-      ctx->h_factor.swap(saved_f);
-      ctx->h_scan_angle.clear();  // (a stored scan has its slot's, if any, as slamhip_scan_select leaves it)
-      for (const slamhip_ctx::ScanSlot &sl : ctx->scan_slots)
-        if (sl.d == saved_ptr) ctx->h_scan_angle = sl.angle;
-      ctx->scan_angle_on_device = false;
-    }
-    ctx->scan_angle_lazy = false;
-  };
-  const HcTraceEntry *chain_trace = b->h_trace.get();
-  size_t chain_trace_per = (size_t)b->trace_per;
-  if (mc_streams && m->mc_batch) {
-    chain_trace = reinterpret_cast<const HcTraceEntry *>(m->mc_batch->h_trace.get());
-    chain_trace_per = m->mc_batch->trace_per;
-  }
-  for (int c = 0; c < n_jobs; ++c) {
-    BatchJobResult &r = b->res[c];
-    const slamhip_raw_match_job &j = jobs[c];
-    double *dl = out_deltas + 3 * c;
-    int kept = planned ? raw.plan[c].k : 0;
-    if (r.on_chain) {
-      for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
-      out_probs[c] = r.prob;
-      if (m->has_obs) {
-        replay_trace(m->obs, chain_trace + (size_t)raw.plan[c].live * chain_trace_per, r.calls);
-        if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
-      }
-    } else if (planned && kept == 0) {
-      // 0 / 0 for every candidate: nothing is accepted, no launch, no observer call (the lone call's answer)
-      dl[0] = dl[1] = dl[2] = 0.0;
-      out_probs[c] = std::numeric_limits<double>::quiet_NaN();
-      r = BatchJobResult{};
-      for (int q = 0; q < 3; ++q) r.pose[q] = j.init_pose[q];
-      r.prob = out_probs[c];
-    } else {
-      if (!fell_back) {
-        saved_w = ctx->h_weight;
-        saved_f = ctx->h_factor;
-        fell_back = true;
-      }
-      int rc;
-      {
-        McStreamSwap own(m, mc_streams ? sid[c] : -1);  // (the job's engine for the call; not advanced when nothing is kept)
-        rc = slamhip_matcher_process_raw_scan(m, j.map_id, &j.scan, j.init_pose, dl, &out_probs[c], &kept);
-      }
-      if (rc) {
-        restore();
-        return rc;
-      }
-      b->raw_blocks[c] = HcBatch::RawBlock{nullptr, 0, kept, true};
-      r = BatchJobResult{};
-      if (kept > 0) {
-        r.calls = m->job.scorer_calls;
-        r.evaluated = m->job.poses_evaluated;
-        r.steps = (int)m->job.launches;
-        r.rescored = m->chain_rescored;
-      }
-      for (int q = 0; q < 3; ++q) r.pose[q] = j.init_pose[q] + dl[q];
-      r.prob = out_probs[c];
-    }
-    if (kept_n) kept_n[c] = kept;
-    calls += r.calls;
-    evaluated += r.evaluated;
-    steps = std::max<long long>(steps, r.steps);
-  }
-  restore();
-  m->job.scorer_calls = calls;
-  m->job.poses_evaluated = evaluated;
-  m->job.launches = steps;
-  m->chain_launched = b->kernels;
-  long long resc = 0;
-  for (const BatchJobResult &r : b->res) resc += r.rescored;
-  m->chain_rescored = resc;
-  return SLAMHIP_OK;
+  // a job the chains did not take or did not settle: the lone raw call, which filters its scan into the upload buffer
+  return batch_hand_over(
+      m, n_jobs, jobs, sid, [&](int c) { return planned ? raw.plan[c].live : 0; }, out_deltas, out_probs, kept_n,
+      [&](const slamhip_raw_match_job &j, ScanKeeper &keep, double *delta, double *prob, int *kept) -> int {
+        keep.upload_overwritten = true;
+        return slamhip_matcher_process_raw_scan(m, j.map_id, &j.scan, j.init_pose, delta, prob, kept);
+      });
 }
 
 int slamhip_matcher_batch_scan_download(slamhip_matcher *m, int job, int cap, double *out5, int *n) {

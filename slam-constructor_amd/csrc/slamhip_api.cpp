@@ -163,15 +163,7 @@ static int fill_args(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cfg,
     return SLAMHIP_ERR_STATE;
   }
   std::memset(a, 0, sizeof(*a));
-  a->map.payload = m.d_payload;
-  a->map.width = m.width;
-  a->map.height = m.height;
-  a->map.pitch = m.pitch;
-  a->map.origin_x = m.origin_x;
-  a->map.origin_y = m.origin_y;
-  a->map.scale = m.scale;
-  a->map.inv_scale = 1.0 / m.scale;
-  for (int k = 0; k < 4; ++k) a->map.unknown[k] = m.unknown[k];
+  a->map = view_of(m);
   if (cfg->oope == SLAMHIP_OOPE_GMAPPING && m.cell_model == SLAMHIP_CELL_GMAPPING && m.bytes > 0 && cfg->gm_window == 1 &&
       m.width >= 3 && m.height >= 3) {  // (bytes: a dense window -- the view of a tile pool has none)
     // (the window holds the masks of ONE threshold.  A second scorer configuration with another threshold
@@ -189,14 +181,7 @@ static int fill_args(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cfg,
              m.nbr_ok && m.nbr_th == cfg->gm_fullness_th) {
     a->map.nbr_ok = 1;  // a tile pool whose owner derived the masks (tile_pool_nbr_masks)
   }
-  const size_t c = ctx->scan_stride;
-  a->scan.range = ctx->scan_ptr;
-  a->scan.cos_a = ctx->scan_ptr + c;
-  a->scan.sin_a = ctx->scan_ptr + 2 * c;
-  a->scan.weight = ctx->scan_ptr + 3 * c;
-  a->scan.factor = ctx->scan_ptr + 4 * c;
-  a->scan.n = ctx->scan_n;
-  a->scan.tot_w = ctx->scan_tot_w;
+  a->scan = scan_view_of(ctx->scan_ptr, ctx->scan_stride, ctx->scan_n, ctx->scan_tot_w);
   a->poses = d_poses;
   a->pose_sc = d_pose_sc;
   a->scores = d_scores;

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -279,6 +280,34 @@ struct DeviceMap {
   double *d_prob = nullptr;
   bool prob_ok = false;
 };
+// the views the kernels take, every byte of them defined: a bound map's own window (no masks: nbr_ok = 0, the caller
+// that has derived them says so), and a scan block of five rows of `stride` doubles at `d`
+inline MapView view_of(const DeviceMap &m) {
+  MapView v;
+  std::memset(&v, 0, sizeof(v));
+  v.payload = m.d_payload;
+  v.width = m.width;
+  v.height = m.height;
+  v.pitch = m.pitch;
+  v.origin_x = m.origin_x;
+  v.origin_y = m.origin_y;
+  v.scale = m.scale;
+  v.inv_scale = 1.0 / m.scale;
+  for (int k = 0; k < 4; ++k) v.unknown[k] = m.unknown[k];
+  return v;
+}
+inline ScanView scan_view_of(const double *d, size_t stride, int n, double tot_w) {
+  ScanView v;
+  std::memset(&v, 0, sizeof(v));
+  v.range = d;
+  v.cos_a = d + stride;
+  v.sin_a = d + 2 * stride;
+  v.weight = d + 3 * stride;
+  v.factor = d + 4 * stride;
+  v.n = n;
+  v.tot_w = tot_w;
+  return v;
+}
 // (re)derives the plane over [x0, x0 + w) x [y0, y0 + h) (clipped) / over n listed cells (d_coords: x, y pairs);
 // model: SLAMHIP_CELL_TBM / _CREDIBILIST = which of the two functions the map's plane holds (anything else is an error)
 hipError_t launch_prob_build(int model, const double *payload, double *prob, int width, int height, int pitch, int x0, int y0, int w, int h,

@@ -182,6 +182,46 @@ def test_stored_scans_equal_uploaded_scans(pkg, ctx):
         mb.process_scan_batch([dict(map_id=0, scan_slot=998, init_pose=[0, 0, 0])])
 
 
+@pytest.mark.parametrize("carried", [False, True])
+def test_fallbacks_leave_the_callers_scan_and_its_angles(pkg, ctx, carried):
+    """The lone fall-backs of a batch make their jobs' scans the context's current one; when the call returns the
+    caller's own selection is back, WITH its points' angles: stored scan A (slot 20) selected, two fall-back jobs on
+    scan B of as many points and other angles -- naming its slot 21, or `carried` as arrays, which go through the upload
+    buffer -- and a SLAMHIP_POSE_TRIG_RAW_EXACT scoring call on A gives the bits it gave before the batch.
+    (cast_scan's angles are relative to the scanner, the same for every pose: B's scanner is mounted 0.3 rad off, so its
+    points' angles differ from A's in every entry.)"""
+    sc = make_scene(size=200, n_beams=90)
+    ctx.upload_map(0, sc["map"])
+    a = sc["scan"]
+    mount = 0.3
+    pose_b = sc["true_pose"] + np.array([0.1, -0.1, mount])
+    rng_b, ang_b = cast_scan(sc["gt"], 0.05, pose_b, 90, seed=43)
+    ang_b = ang_b + mount
+    assert a.range.size == rng_b.size == 90 and np.all(a.angle != ang_b)
+    w_b = np.full(rng_b.size, 1.0 / rng_b.size)
+    scans = {20: (a.range, a.angle, a.weight), 21: (rng_b, ang_b, w_b)}
+    for slot, (rng, ang, w) in scans.items():
+        cos_a, sin_a = pkg.beam_trig(ang)
+        ctx.scan_store(slot, rng, cos_a, sin_a, w)
+        ctx.scan_store_angles(slot, ang)
+    ctx.scan_select(20)
+    cfg = pkg.spe_cfg(pose_trig=pkg.POSE_TRIG_RAW_EXACT)
+    poses = sc["true_pose"] + np.random.RandomState(7).randn(8, 3) * [0.1, 0.1, 0.05]
+    want = ctx.score_poses(0, cfg, poses)
+    init_b = pose_b - [0.0, 0.0, mount] + [0.07, -0.04, 0.03]
+    if carried:
+        cos_b, sin_b = pkg.beam_trig(ang_b)
+        job = dict(map_id=0, range=rng_b, cos_a=cos_b, sin_a=sin_b, weight=w_b, factor=None, init_pose=init_b)
+    else:
+        job = dict(map_id=0, scan_slot=21, init_pose=init_b)
+    mb = pkg.Matcher(ctx, "HC", pkg.spe_cfg(sum_order=1, pose_trig=1), [12, 0.1, 0.1])  # strict: every job falls back
+    for trace in (False, True):  # (with an observer: the fall-back's trace through the hand-over)
+        got = mb.process_scan_batch([job, job], trace=trace)
+        assert len(got) == 2 and not any(mb.batch_stats(j)["on_device_chain"] for j in range(2))
+        assert np.array_equal(ctx.score_poses(0, cfg, poses), want)  # bit for bit
+    assert got[0]["n_calls"] > 0 and got[0]["n_calls"] == mb.batch_stats(0)["scorer_calls"]
+
+
 def test_resident_batch_gives_up_when_a_workgroup_is_missing(pkg, tctx):
     """The co-resident batch launch (csrc/hc_resident.hip) with one workgroup of every chain leaving at once (testing
     hook): the chains must give up within the bound, and the kernel chains redo the whole batch with the lone
