@@ -458,8 +458,12 @@ __global__ __launch_bounds__(NT) void k_hc_chain_step(HcChainArgs a, int k) {
               h->first_info = ctl->first_info;
               h->first_raw = ctl->first_raw;
             }
-            if (a.n_done) atomicAdd(a.n_done, 1u);
             __hip_atomic_store(&h->done_seq, a.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (a.n_done) {
+              // the count LAST, behind a fence: who reads count >= n finds every done_seq (as hc_resident_gm.hip)
+              __threadfence_system();
+              atomicAdd(a.n_done, 1u);
+            }
           }
         } else if (lane == 0) {
           __hip_atomic_store(&host->progress, (unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -614,7 +618,8 @@ __global__ __launch_bounds__(NT) void k_hc_chain_step(HcChainArgs a, int k) {
 }
 
 __global__ void k_chain_marker(const unsigned *n_done, unsigned *h_done_count, unsigned *flag, unsigned seq) {
-  *h_done_count = *n_done;
+  // acquire: a count of n here means every chain's done_seq store, fenced before its bump, is out
+  *h_done_count = __hip_atomic_load(n_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 

@@ -234,8 +234,13 @@ __global__ __launch_bounds__(NT) void k_mc_chain_step(McChainArgs a, int k) {
             h->saved[0] = next.saved[0];
             h->saved[1] = next.saved[1];
             h->saved[2] = next.saved[2];
-            if (BATCH) atomicAdd(a.n_done, 1u);  // (once per chain: done_epoch keeps later launches out)
             __hip_atomic_store(&h->done_seq, a.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (BATCH) {
+              // the count LAST, behind a fence: who reads count >= n finds every done_seq (as hc_resident_gm.hip).
+              // Once per chain: done_epoch keeps later launches out
+              __threadfence_system();
+              atomicAdd(a.n_done, 1u);
+            }
           }
         } else if (lane == 0) {
           __hip_atomic_store(&host->progress, (unsigned)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
