@@ -673,6 +673,29 @@ class RefMapHandle(RefHandle):
         self.ref.lib.ref_map_export_aux(self.h, _d(out))
         return out
 
+    def window(self, x0, y0, w, h):
+        """Flat mirror of the external cells [x0, x0 + w) x [y0, y0 + h) alone (ref_map_export): the way to look at a
+        map that has grown across kilometres.  The result's origin is (-x0, -y0): outside it unless the box holds (0, 0)."""
+        model = REF_TO_MODEL[self.cell]
+        st = STRIDE[model]
+        out = np.zeros((h, w, st))
+        self.ref.lib.ref_map_export(self.h, int(x0), int(y0), int(w), int(h), _d(out))
+        unk = np.zeros(4)
+        self.ref.lib.ref_map_unknown_payload(self.h, _d(unk))
+        bounded = self.map_type in (MAP_PLAIN, MAP_LAZY_TILED)
+        return GridMapData(model, out, (-int(x0), -int(y0)), self.geometry()["scale"], unk[:st], bounded)
+
+    def aux_window(self, x0, y0, w, h):
+        """aux() of the same box of external cells."""
+        st = {REF_CELL_MEAN: 1, REF_CELL_GMAPPING: 2}.get(self.cell, 0)
+        if not st:
+            return None
+        fn = self.ref.lib.ref_map_export_aux_window
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
+        out = np.zeros((h, w, st))
+        fn(self.h, int(x0), int(y0), int(w), int(h), _d(out))
+        return out
+
     def to_data(self):
         """Flat mirror of the whole map window (what the adapter uploads)."""
         g = self.geometry()

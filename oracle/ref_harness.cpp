@@ -285,15 +285,15 @@ void ref_map_export_all(void *h, double *out) {
 
 // per-cell update state that is not part of the scoring payload: MeanProbabilityCell::_n
 // (naive_grid_cells.h:43) -> 1 double; GmappingBaseCell::_hits/_tries (gmapping_grid_cell.h:41) -> 2
-int ref_map_export_aux(void *h, double *out) {
+// ... of the external cells [x0, x0 + w) x [y0, y0 + hh): a map that has grown across kilometres is never exported whole
+int ref_map_export_aux_window(void *h, int x0, int y0, int w, int hh, double *out) {
   auto *rm = static_cast<RefMap *>(h);
   auto &m = *rm->map;
-  const int w = m.width(), hh = m.height(), ox = m.origin().x, oy = m.origin().y;
   if (rm->cell_model != CELL_MEAN && rm->cell_model != CELL_GMAPPING) return 0;
   const int st = rm->cell_model == CELL_MEAN ? 1 : 2;
   for (int y = 0; y < hh; ++y)
     for (int x = 0; x < w; ++x) {
-      const GridCell &c = m[{x - ox, y - oy}];
+      const GridCell &c = m[{x0 + x, y0 + y}];
       double *o = out + (size_t(y) * w + x) * st;
       if (rm->cell_model == CELL_MEAN) {
         o[0] = static_cast<const MeanProbabilityCell &>(c)._n;
@@ -303,6 +303,12 @@ int ref_map_export_aux(void *h, double *out) {
       }
     }
   return st;
+}
+
+// whole internal window
+int ref_map_export_aux(void *h, double *out) {
+  auto &m = *static_cast<RefMap *>(h)->map;
+  return ref_map_export_aux_window(h, -m.origin().x, -m.origin().y, m.width(), m.height(), out);
 }
 
 // bulk GridMap::update of n external cells with {occupied, {prob, 1}, (0,0), quality 1}.  On an
