@@ -191,15 +191,16 @@ def root_candidates(limits):
     return ge.load_package().m3rsm_root_candidates((limits[0], limits[1], 2 * limits[2]), limits[3])
 
 
-def main():
-    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "bf_multi_res_scan_matcher.h")):
-        sys.exit("reference tree not found at %s" % REFERENCE)
-    exe = build()
-    scenes, inp, maps = [], [], {}
-    for k, (name, cls, (w, h, origin), scale, n_beams, limits) in enumerate(SCENES):
+def make_scenes(specs, shift=(0, 0)):
+    """the scenes of `specs` -- (index into SCENES, which seeds the draws; the SCENES entry) -- with the whole scene moved by
+    `shift` cells (make_golden_placed_pyramid.py: a station): the room, the pose and the scan's origin follow the map's
+    origin, the draws are the same numbers as without the shift"""
+    scenes, maps = [], {}
+    for k, (name, cls, (w, h, origin), scale, n_beams, limits) in specs:
         rs = np.random.RandomState(SEED + k)
         cid, model, stride = CLASSES[cls]
         o = origin or (w // 2, h // 2)
+        o = (o[0] - shift[0], o[1] - shift[1])
         mk = (cls, w, h, o, scale)
         if mk not in maps:  # the occ scenes on the 33x33 map share it
             maps[mk] = observations(np.random.RandomState(SEED + 100 + k), cid, w, h, o)
@@ -211,11 +212,17 @@ def main():
         ranges, angles, a_min, a_max, a_inc = cast_scan(rs, n_beams, true_pose, w, h, o, scale)
         scenes.append(dict(name=name, cls=cls, cid=cid, model=model, stride=stride, oie=0, w=w, h=h, origin=o, scale=scale,
                            obs=maps[mk], pose=pose, ranges=ranges, angles=angles, trig=(a_min, a_max, a_inc), limits=limits))
-    inp.append(len(scenes))
+    return scenes
+
+
+def run(exe, scenes, tag="m3rsm"):
+    """the harness over `scenes`: every assertion of this generator per scene, then the fixture's arrays and the counters
+    (one-sided splits, five-point expansions, the set of levels called on)"""
+    inp = [len(scenes)]
     for m in scenes:
         inp += [m["cid"], m["oie"], m["w"], m["h"], m["scale"], m["origin"][0], m["origin"][1], len(m["obs"]), *m["obs"].ravel(),
                 *m["pose"], len(m["ranges"]), *m["ranges"], *m["angles"], *m["trig"], *m["limits"]]
-    f_in, f_out = os.path.join(OUT_DIR, "m3rsm_in.bin"), os.path.join(OUT_DIR, "m3rsm_out.bin")
+    f_in, f_out = os.path.join(OUT_DIR, tag + "_in.bin"), os.path.join(OUT_DIR, tag + "_out.bin")
     np.asarray(inp, dtype=np.float64).tofile(f_in)
     subprocess.check_call([exe, f_in, f_out])
     o = np.fromfile(f_out, dtype=np.float64)
@@ -304,6 +311,17 @@ def main():
         print("%-12s %5d calls, delta (%+.4f, %+.4f, %+.5f), prob %.6f, levels %s"
               % (m["name"], n_calls, res_a[0], res_a[1], res_a[2], res_a[3], sorted(set(rec_a[:, 8].astype(int).tolist()))))
     assert pos[0] == o.size
+    if tag != "m3rsm":  # (a run for another fixture: the dense levels written out whole are large)
+        os.remove(f_in), os.remove(f_out)
+    return out, n_one_sided, n_five, all_levels
+
+
+def main():
+    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "bf_multi_res_scan_matcher.h")):
+        sys.exit("reference tree not found at %s" % REFERENCE)
+    exe = build()
+    scenes = make_scenes(list(enumerate(SCENES)))
+    out, n_one_sided, n_five, all_levels = run(exe, scenes)
     assert n_one_sided >= 10, "hardly a one-sided split among the calls (%d)" % n_one_sided
     assert n_five >= 50, "hardly a five-point expansion among the calls (%d)" % n_five
     assert len(all_levels) >= 4, "calls on fewer than four levels"

@@ -77,16 +77,17 @@ def build():
     return exe
 
 
-def main():
-    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "bf_multi_res_scan_matcher.h")):
-        sys.exit("reference tree not found at %s" % REFERENCE)
-    exe = build()
-    scenes, inp = [], []
-    for k, (name, cls, map_specs, limits, req_specs) in enumerate(SCENES):
+def make_scenes(specs):
+    """the scenes of `specs` (entries like SCENES'; a map spec may carry a fifth element, a shift in cells by which the
+    whole map -- and with its room the poses and scans of its requests -- is moved: make_golden_placed_pyramid.py)"""
+    scenes = []
+    for k, (name, cls, map_specs, limits, req_specs) in enumerate(specs):
         cid, model, stride = CLASSES[cls]
         maps = []
-        for j, (w, h, origin, scale) in enumerate(map_specs):
+        for j, (w, h, origin, scale, *shift) in enumerate(map_specs):
             o = origin or (w // 2, h // 2)
+            if shift:
+                o = (o[0] - shift[0][0], o[1] - shift[0][1])
             maps.append(dict(w=w, h=h, origin=o, scale=scale, stride=stride,
                              obs=observations(np.random.RandomState(SEED + 1000 + 10 * k + j), cid, w, h, o)))
         reqs = []
@@ -102,7 +103,13 @@ def main():
             ranges = ranges + noise * m["scale"] * rs.randn(n_beams)
             reqs.append(dict(map=mi, pose=pose, ranges=ranges, angles=angles, trig=(a_min, a_max, a_inc)))
         scenes.append(dict(name=name, cls=cls, cid=cid, model=model, stride=stride, oie=0, maps=maps, reqs=reqs, limits=limits))
-    inp.append(len(scenes))
+    return scenes
+
+
+def run(exe, scenes, tag="m3rsm_many"):
+    """the harness over `scenes`: every assertion of this generator per scene, then the fixture's arrays and the counters
+    (scenes request 0 does not win, scenes in which the shared cut saves calls)"""
+    inp = [len(scenes)]
     for s in scenes:
         inp += [s["cid"], s["oie"], len(s["maps"])]
         for m in s["maps"]:
@@ -113,7 +120,7 @@ def main():
         inp += [*s["limits"], len(s["reqs"])]
         for j, r in enumerate(s["reqs"]):
             inp += [r["map"], j, *r["pose"]]
-    f_in, f_out = os.path.join(OUT_DIR, "m3rsm_many_in.bin"), os.path.join(OUT_DIR, "m3rsm_many_out.bin")
+    f_in, f_out = os.path.join(OUT_DIR, tag + "_in.bin"), os.path.join(OUT_DIR, tag + "_out.bin")
     np.asarray(inp, dtype=np.float64).tofile(f_in)
     subprocess.check_call([exe, f_in, f_out])
     o = np.fromfile(f_out, dtype=np.float64)
@@ -227,6 +234,17 @@ def main():
               % (s["name"], n_calls, lone[:, 4].astype(int).tolist(), winner, res_m[1], res_m[2], res_m[3], res_m[4],
                  ["%.6f" % v for v in lone[:, 3]], runs))
     assert pos[0] == o.size
+    if tag != "m3rsm_many":  # (a run for another fixture: the dense levels written out whole are large)
+        os.remove(f_in), os.remove(f_out)
+    return out, not_first, cut_bites
+
+
+def main():
+    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "bf_multi_res_scan_matcher.h")):
+        sys.exit("reference tree not found at %s" % REFERENCE)
+    exe = build()
+    scenes = make_scenes(SCENES)
+    out, not_first, cut_bites = run(exe, scenes)
     assert not_first >= 1, "request 0 wins every scene"
     assert cut_bites >= 1, "the shared cut saves no call in any scene"
     path = os.path.join(GOLDEN_DIR, "m3rsm_many.npz")

@@ -116,17 +116,15 @@ def n_bitwise_different(trace, other):
     return int(np.sum(trace[:k, 5].view(np.int64) != other[:k, 5].view(np.int64)))
 
 
-def main():
-    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "bf_multi_res_scan_matcher.h")):
-        sys.exit("reference tree not found at %s" % REFERENCE)
-    variant = libm_variant()
-    assert variant in (0, 1), "this host's libm is neither build of glibc's sin / cos"
-    exe = build()
+def make_scenes(small=SMALL, edge=EDGE, shift=(0, 0)):
+    """the scenes named in `small` and the edge scenes `edge`, the whole scene moved by `shift` cells
+    (make_golden_placed_pyramid.py: a station; an edge scene stays one: a shift of whole 0.125 m cells is an exact double)"""
     scenes = []
-    for k, (name, cls, (w, h, origin), scale, n_beams, limits) in enumerate(s for s in base.SCENES if s[0] in SMALL):
+    for k, (name, cls, (w, h, origin), scale, n_beams, limits) in enumerate(s for s in base.SCENES if s[0] in small):
         rs = np.random.RandomState(SEED + k)
         cid, model, stride = base.CLASSES[cls]
         o = origin or (w // 2, h // 2)
+        o = (o[0] - shift[0], o[1] - shift[1])
         obs = base.observations(np.random.RandomState(SEED + 100 + k), cid, w, h, o)
         x0, x1, y0, y1 = base.room(w, h, o)
         mid = np.array([(x0 + x1 + 1) / 2 * scale, (y0 + y1 + 1) / 2 * scale])
@@ -135,23 +133,29 @@ def main():
         ranges, angles, a_min, a_max, a_inc = base.cast_scan(rs, n_beams, true_pose, w, h, o, scale)
         scenes.append(dict(name=name, cls=cls, cid=cid, model=model, stride=stride, oie=0, w=w, h=h, origin=o, scale=scale, obs=obs,
                            pose=pose, ranges=ranges, angles=angles, trig=(a_min, a_max, a_inc), limits=limits, edge=0))
-    for k, (name, cls, pose, off, a_min, n_beams, limits) in enumerate(EDGE):
+    for k, (name, cls, pose, off, a_min, n_beams, limits) in enumerate(edge):
         rs = np.random.RandomState(SEED + 50 + k)
         cid, model, stride = base.CLASSES[cls]
-        w, h, o, scale = 33, 33, (16, 16), 0.125
+        w, h, o, scale = 33, 33, (16 - shift[0], 16 - shift[1]), 0.125
         obs = base.observations(np.random.RandomState(SEED + 150 + k), cid, w, h, o)
-        pose = np.array(pose, dtype=np.float64)
+        pose = np.array(pose, dtype=np.float64) + [shift[0] * scale, shift[1] * scale, 0.0]
         assert np.all(np.round(pose[:2] * 16) == pose[:2] * 16) and np.all(np.round(pose[:2] * 16) % 2 == 1), "not a cell centre"
         ranges, angles, a_min, a_max, a_inc = edge_scan(rs, n_beams, a_min, pose + np.array(off), w, h, o, scale)
         t = pose[2] + np.arange(-8, 9) / 64
         assert np.any((t[:, None] + angles[None, :]) == 0.0), "no beam along the x axis at any rotation"
         scenes.append(dict(name=name, cls=cls, cid=cid, model=model, stride=stride, oie=0, w=w, h=h, origin=o, scale=scale, obs=obs,
                            pose=pose, ranges=ranges, angles=angles, trig=(a_min, a_max, a_inc), limits=limits, edge=1))
+    return scenes
+
+
+def run(exe, scenes, variant, tag="m3rsm_rawtrig"):
+    """the harness over `scenes`: every per-scene assertion of this generator, then the fixture's arrays, the number of
+    scores that differ bitwise between the providers and the scenes in which the provider moves the match"""
     inp = [len(scenes)]
     for m in scenes:
         inp += [m["cid"], m["oie"], m["w"], m["h"], m["scale"], m["origin"][0], m["origin"][1], len(m["obs"]), *m["obs"].ravel(),
                 *m["pose"], len(m["ranges"]), *m["ranges"], *m["angles"], *m["trig"], *m["limits"]]
-    f_in, f_out = os.path.join(OUT_DIR, "m3rsm_rawtrig_in.bin"), os.path.join(OUT_DIR, "m3rsm_rawtrig_out.bin")
+    f_in, f_out = os.path.join(OUT_DIR, tag + "_in.bin"), os.path.join(OUT_DIR, tag + "_out.bin")
     np.asarray(inp, dtype=np.float64).tofile(f_in)
     subprocess.check_call([exe, f_in, f_out])
     o = np.fromfile(f_out, dtype=np.float64)
@@ -240,6 +244,19 @@ def main():
         print("%-12s %5d calls (cached %5d), %4d scores differ bitwise, delta (%+.4f, %+.4f, %+.5f) (cached (%+.4f, %+.4f, %+.5f)), "
               "prob %.6f" % (m["name"], n_calls, len(rec_d), n_diff, *res_a[:3], *res_d[:3], res_a[3]))
     assert pos[0] == o.size
+    if tag != "m3rsm_rawtrig":  # (a run for another fixture: the dense levels written out whole are large)
+        os.remove(f_in), os.remove(f_out)
+    return out, n_diff_all, moved
+
+
+def main():
+    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "bf_multi_res_scan_matcher.h")):
+        sys.exit("reference tree not found at %s" % REFERENCE)
+    variant = libm_variant()
+    assert variant in (0, 1), "this host's libm is neither build of glibc's sin / cos"
+    exe = build()
+    scenes = make_scenes()
+    out, n_diff_all, moved = run(exe, scenes, variant)
     assert n_diff_all >= 10, "hardly a call that tells the providers apart (%d)" % n_diff_all
     assert moved, "no scene in which the provider changes the number of calls or the delta"
     path = os.path.join(GOLDEN_DIR, "m3rsm_rawtrig.npz")

@@ -115,25 +115,43 @@ def scans(rs, scale, w, h):
     return out
 
 
-def main():
-    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "m3rsm_engine.h")):
-        sys.exit("reference tree not found at %s" % REFERENCE)
-    exe = build()
-    rs = np.random.RandomState(20261018)
-    maps, inp = [], []
-    for w, h, origin in SHAPES:
+def make_maps(rs, shapes, shift=(0, 0), match_shapes=None):
+    """the maps of the fixture: shapes x SCALES x classes (GridCell under both OIEs), with their match sets.  shift: the
+    whole map, observations and poses moved by that many cells (make_golden_placed_pyramid.py: a station) -- the draws
+    are the same numbers as without it."""
+    maps = []
+    for w, h, origin in shapes:
         o = origin or (w // 2, h // 2)
+        o = (o[0] - shift[0], o[1] - shift[1])
         for scale in SCALES:
             for name, cid, model, stride in CLASSES:
                 for oie in ((0, 1) if cid == 0 else (0,)):
                     obs = observations(rs, cid, w, h, o)
                     sets = []
-                    if (w, h, origin) in MATCH_SHAPES:
+                    if (w, h, origin) in (MATCH_SHAPES if match_shapes is None else match_shapes):
                         pose = np.array([(0.3 + 0.4 * rs.rand()) * scale, (-0.2 + 0.4 * rs.rand()) * scale, 0.3 * rs.randn()])
+                        pose = pose + [shift[0] * scale, shift[1] * scale, 0.0]
                         for ranges, angles, a_min, a_max, a_inc in scans(rs, scale, w, h):
                             sets.append(dict(pose=pose, ranges=ranges, angles=angles, trig=(a_min, a_max, a_inc)))
                     maps.append(dict(cls=name, cid=cid, model=model, stride=stride, oie=oie, w=w, h=h, origin=o, scale=scale, obs=obs,
                                      sets=sets))
+    return maps
+
+
+def crop_level(payload, origin, proto):
+    """the window of a level cut down to the box of the cells that are not the prototype (a dense level of a map far from
+    (0, 0) spans back to the origin: nearly all of it never written); origin moved along"""
+    known = ~np.all(payload.view(np.int64) == proto.view(np.int64), axis=-1)
+    if not known.any():
+        return payload[:1, :1].copy(), origin
+    ys, xs = np.nonzero(known)
+    return payload[ys.min():ys.max() + 1, xs.min():xs.max() + 1].copy(), (origin[0] - int(xs.min()), origin[1] - int(ys.min()))
+
+
+def run(exe, maps, crop=False, tag="pyramid"):
+    """the harness over `maps`: every assertion of this generator, then the fixture's arrays and the counters
+    (sets, candidates, maps with a level added during the fill, one-sided splits, sets that reached the fine map)"""
+    inp = []
     inp.append(len(maps))
     for m in maps:
         inp += [m["cid"], m["oie"], m["w"], m["h"], m["scale"], m["origin"][0], m["origin"][1], len(m["obs"]), *m["obs"].ravel(),
@@ -142,7 +160,7 @@ def main():
             inp += [*s["pose"], len(s["ranges"]), *s["ranges"], *s["angles"], *s["trig"], *LIMITS[2:], len(RUNS)]
             for run in RUNS:
                 inp += list(run)
-    f_in, f_out = os.path.join(OUT_DIR, "pyramid_in.bin"), os.path.join(OUT_DIR, "pyramid_out.bin")
+    f_in, f_out = os.path.join(OUT_DIR, tag + "_in.bin"), os.path.join(OUT_DIR, tag + "_out.bin")
     np.asarray(inp, dtype=np.float64).tofile(f_in)
     subprocess.check_call([exe, f_in, f_out])
     o = np.fromfile(f_out, dtype=np.float64)
@@ -211,8 +229,9 @@ def main():
                     pre + "scale": np.array(m["scale"]), pre + "origin": np.array(m["origin"]), pre + "unknown": proto,
                     pre + "payload": fine["payload"], pre + "n_levels": np.array(n_scales - 1)})
         for k in range(1, n_scales):
-            out.update({pre + "L%d_origin" % k: np.array(levels[k]["origin"]), pre + "L%d_scale" % k: np.array(levels[k]["scale"]),
-                        pre + "L%d_payload" % k: levels[k]["payload"]})
+            pay, org = crop_level(levels[k]["payload"], levels[k]["origin"], proto) if crop else (levels[k]["payload"], levels[k]["origin"])
+            out.update({pre + "L%d_origin" % k: np.array(org), pre + "L%d_scale" % k: np.array(levels[k]["scale"]),
+                        pre + "L%d_payload" % k: pay})
         for s in m["sets"]:
             sp = "s%d_" % n_sets
             assert int(take(1)[0]) == len(RUNS)
@@ -270,10 +289,20 @@ def main():
             n_sets += 1
             n_cands += nc
     assert pos[0] == o.size
+    out["n_sets"] = np.array(n_sets)
+    return out, dict(sets=n_sets, cands=n_cands, extended=extended, one_sided=n_one_sided, reached_fine=reached_fine)
+
+
+def main():
+    if not os.path.isfile(os.path.join(REFERENCE, "src", "core", "scan_matchers", "m3rsm_engine.h")):
+        sys.exit("reference tree not found at %s" % REFERENCE)
+    exe = build()
+    maps = make_maps(np.random.RandomState(20261018), SHAPES)
+    out, c = run(exe, maps)
+    n_sets, n_cands, extended, n_one_sided, reached_fine = c["sets"], c["cands"], c["extended"], c["one_sided"], c["reached_fine"]
     assert extended > 0, "no map made the reference add a level while it was filled"
     assert reached_fine >= 8, "hardly a branch that reached the fine map on a map finer than the rectangle"
     assert n_one_sided >= 10, "hardly a one-sided split (split_horz / split_vert) among the branches"
-    out["n_sets"] = np.array(n_sets)
     path = os.path.join(GOLDEN_DIR, "pyramid.npz")
     np.savez_compressed(path, **out)
     print("wrote pyramid.npz: %d maps (%d with a level added during the fill), %d match sets, %d candidates, %d KiB"

@@ -10,6 +10,7 @@
 //   * refreshing the cells pyr::level_window names after changing fine cells equals building anew.
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 //       -I<repo>/include -I<repo>/slam-constructor_amd/csrc pyramid_test.cpp
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -46,9 +47,16 @@ static void reduce_window(const pyr::Level &src, const pyr::Level &dst, bool top
 }
 
 template <int CD>
-static long run_case(std::mt19937 &rng, int model, int oie) {
+static long run_case(std::mt19937 &rng, int model, int oie, bool far = false) {
   std::uniform_int_distribution<int> dim(1, 41), off(-9, 50), val(0, 5), coin(0, 3);
-  const int w = dim(rng), h = dim(rng), ox = off(rng), oy = off(rng);
+  // far: the window stands 10^4 ... 2^21 cells from external (0, 0), in any quadrant, now and then exactly a power of two
+  // out (the window then starts, or ends, on the border of the last finite level's block)
+  std::uniform_int_distribution<int> far_off(10000, 1 << 21), pow2(14, 21);
+  auto far_origin = [&]() {
+    const int d = coin(rng) == 0 ? (1 << pow2(rng)) + coin(rng) - 1 : far_off(rng);
+    return (rng() & 1) ? d : -d;
+  };
+  const int w = dim(rng), h = dim(rng), ox = far ? far_origin() : off(rng), oy = far ? far_origin() : off(rng);
   double unknown[4] = {0.5, 0, 0, 0};
   if (CD == 4) unknown[0] = 1.0, unknown[1] = unknown[2] = unknown[3] = 0.0;
   auto fill_cell = [&](double *p) {
@@ -73,6 +81,14 @@ static long run_case(std::mt19937 &rng, int model, int oie) {
   pyr::Plan pl;
   CHECK(pyr::plan_levels(w, h, ox, oy, 0.05, &pl));
   CHECK(pl.n >= 1 && pl.n < pyr::kMaxLevels);
+  if (far) {
+    // one level per doubling: ceil(log2(extent)) + 1, and the fine window's origin far outside every finite level
+    long long extent = std::max(std::max((long long)ox, (long long)w - ox), std::max((long long)oy, (long long)h - oy));
+    int want = 1;
+    while ((1ll << (want - 1)) < extent) ++want;
+    CHECK(pl.n == want && pl.n >= 15 && pl.n <= 23);
+    CHECK(pl.origin_x[0] < 0 || pl.origin_x[0] >= pl.width[0]);
+  }
   CHECK(pl.width[pl.n - 1] == 1 && pl.height[pl.n - 1] == 1 && std::isinf(pl.scale[pl.n - 1]));
   if (pl.n >= 2) CHECK(pl.width[pl.n - 2] <= 2 && pl.height[pl.n - 2] <= 2);
   else CHECK(w <= 2 && h <= 2);
@@ -150,6 +166,12 @@ int main() {
     cells += run_case<4>(rng, SLAMHIP_CELL_TBM, SLAMHIP_OIE_DISCREPANCY);
     cells += run_case<4>(rng, SLAMHIP_CELL_CREDIBILIST, SLAMHIP_OIE_DISCREPANCY);
   }
+  for (int i = 0; i < 100; ++i) {  // the same checks, window origins out to +-2^21 cells
+    cells += run_case<1>(rng, SLAMHIP_CELL_OCC, SLAMHIP_OIE_DISCREPANCY, true);
+    cells += run_case<1>(rng, SLAMHIP_CELL_OCC, SLAMHIP_OIE_OCCUPANCY, true);
+    cells += run_case<4>(rng, SLAMHIP_CELL_TBM, SLAMHIP_OIE_DISCREPANCY, true);
+    cells += run_case<4>(rng, SLAMHIP_CELL_CREDIBILIST, SLAMHIP_OIE_DISCREPANCY, true);
+  }
   // the order of impacts: numbers, -0 below +0
   CHECK(pyr::key(-0.0) < pyr::key(0.0) && pyr::key(-1.0) < pyr::key(-0.5) && pyr::key(0.5) < pyr::key(1.0) &&
         pyr::key(-1e-300) < pyr::key(0.0));
@@ -157,6 +179,6 @@ int main() {
   pyr::Plan pl;
   CHECK(!pyr::plan_levels(0, 3, 0, 0, 1.0, &pl) && !pyr::plan_levels(4, 4, (1 << 30) + 1, 0, 1.0, &pl) && !pyr::plan_levels(4, 4, -(1 << 30), 0, 1.0, &pl));
   if (fails) return 1;
-  std::printf("ok %ld cells in 1200 maps\n", cells);
+  std::printf("ok %ld cells in 1600 maps (400 of them 10^4 ... 2^21 cells from the origin)\n", cells);
   return 0;
 }

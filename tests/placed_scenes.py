@@ -35,16 +35,33 @@ F_STATIONS = ["F1", "F2"]
 SEEDS = {"O": 3, "Q1": 15, "Q2": 12, "Q3": 13, "Q4": 19, "F1": 21, "F2": 22}
 INIT_OFFSET = np.array([0.07, -0.04, 0.03])  # synth.make_scene's perturbation of the true pose
 
+# A second table, apart from STATIONS (whose parametrised tests do not change): the N stations, 500 ... 1500 cells out,
+# which the compiled reference reaches with a DENSE pyramid (M3RSMRescalableGridMap<UnboundedPlainGridMap>: every level
+# grows from (0, 0) to the data, so its cost is the square of the distance).  Both shifts odd -- no block corner of any
+# level falls on the window's -- one station per sign pattern that is not (+, +).
+N_TABLE = {
+    "N1": ((-1021, 517), 2.2),
+    "N2": ((1303, -771), -0.8),
+    "N3": ((-643, -1459), -2.4),
+}
+N_STATIONS = list(N_TABLE)
+N_SEEDS = {"N1": 31, "N2": 32, "N3": 33}
+
+
+def station_entry(name):
+    """((kx, ky), heading) of a station of either table"""
+    return STATIONS[name] if name in STATIONS else N_TABLE[name]
+
 
 def shift_m(station, scale):
     """The station's shift in metres, as the doubles every moved quantity is built from."""
-    (kx, ky), _ = STATIONS[station]
+    (kx, ky), _ = station_entry(station)
     return np.array([kx * scale, ky * scale, 0.0])
 
 
 def move_map(m, station):
     """The map of a scene built next to (0, 0), moved to the station (a new MapData; GMapping means moved too)."""
-    (kx, ky), _ = STATIONS[station]
+    (kx, ky), _ = station_entry(station)
     s = shift_m(station, m.scale)
     pay = m.payload.copy()
     if m.cell_model == synth.CELL_GMAPPING:
@@ -59,8 +76,8 @@ def place(station, cell_model=synth.CELL_OCC, size=240, scale=0.1, n_beams=360, 
     """One scene at `station`: dict(map, scan, init_pose, true_pose, gt, shift, local[, raw]) like synth.make_scene's.
     raw: also the scan as the scanner hands it over, (ranges, angles, is_occupied) of every beam (cast_scan's raw form;
     ranges[is_occupied] are scan.range)."""
-    _, h = STATIONS[station]
-    seed = SEEDS[station] if seed is None else seed
+    _, h = station_entry(station)
+    seed = {**SEEDS, **N_SEEDS}[station] if seed is None else seed
     gt = synth.make_world(size, scale, seed)
     local = np.array([scale / 2, scale / 2, h])
     rng, ang = synth.cast_scan(gt, scale, local, n_beams, max_dist=max_dist)

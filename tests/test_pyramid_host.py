@@ -9,7 +9,10 @@ import types
 
 import numpy as np
 import pytest
-from pyramid_cases import N_MAPS, N_SETS, assert_levels_are, assert_same_level, bits, brute_levels, golden_map, golden_set
+from pyramid_cases import (FAR_MAPS, FAR_STATIONS, N_MAPS, N_SETS, ORACLE_MAPS, assert_levels_are, assert_same_level, belief_impact,
+                           bits, bound_probe_rows, brute_levels, expected_level_count, far_brute_levels, golden_map, golden_set,
+                           moved_golden, moved_set, placed_counts, placed_golden_map)
+from placed_scenes import N_STATIONS
 
 import __graft_entry__ as ge
 
@@ -140,19 +143,68 @@ def test_the_infinite_level_holds_the_argmax_of_the_map(pkg, i):
     np.testing.assert_array_equal(bits(levels[-1]["payload"][0, 0]), bits(want[-1][(0, 0)]))
 
 
-def belief_impact(pkg, model, p):
-    """the scorer's per-beam probability of a belief cell, restated (csrc/slamhip_internal.h)"""
-    u, e, o, c = (float(v) for v in p)
-    if model == pkg.CELL_CREDIBILIST:
-        t0, t2 = u + e, o + c
-        tot = ((t0 + 0.0) + t2) + 0.0
-        return 1.0 - (1.0 - (0.0 if tot == 0.0 else t2 / tot))
-    d_occ = abs(1.0 - o)
-    t2, t3 = u + o, e + c
-    tot = t2 + t3
-    conflict = 0.0 if tot == 0.0 else t3 / tot
-    unknown = u / 2.0
-    return 1.0 - (unknown / 2 + (1 - unknown) * (conflict + d_occ) / 2.0)
+# ---- far from the world origin: the golden maps 64 / 66 / 67 (37 x 29, origin (11, 20): GridCell, TBM, Credibilist) moved
+# to every station of tests/placed_scenes.py.  A map 20 000 cells out has 16 levels, one 2 x 10^6 cells out 23; most are
+# 1 x 1 or 1 x 2 windows whose origin lies far outside them.
+@pytest.mark.parametrize("st", FAR_STATIONS)
+@pytest.mark.parametrize("i", FAR_MAPS)
+def test_host_levels_equal_the_definition_far_from_the_origin(pkg, i, st):
+    m = moved_golden(i, st)
+    levels = pkg.pyramid_build_host(m, m.oie)
+    assert_levels_are(levels, far_brute_levels(pkg, i, st), m.unknown)
+    assert len(levels) == expected_level_count(m)
+    assert np.isinf(levels[-1]["scale"]) and levels[-1]["payload"].shape[:2] == (1, 1) and levels[-1]["origin"] == (0, 0)
+    scale = m.scale
+    for k, lv in enumerate(levels[:-1], 1):
+        scale = scale * 2
+        assert lv["scale"] == scale
+        # the window of a level is the fine window's, floored: external cells floor(-ox / 2^k) ... floor((w - 1 - ox) / 2^k)
+        lo = (-m.origin[0]) >> k, (-m.origin[1]) >> k
+        hi = (m.width - 1 - m.origin[0]) >> k, (m.height - 1 - m.origin[1]) >> k
+        assert lv["origin"] == (-lo[0], -lo[1]) and (lv["width"], lv["height"]) == (hi[0] - lo[0] + 1, hi[1] - lo[1] + 1)
+    if st != "O":
+        assert not (0 <= levels[0]["origin"][0] < levels[0]["width"]) and levels[-2]["width"] * levels[-2]["height"] <= 2
+    # the moved pyramid is the pyramid of the map where it was built ONLY at the top: the blocks fall elsewhere
+    np.testing.assert_array_equal(bits(levels[-1]["payload"]), bits(pkg.pyramid_build_host(golden_map(i), m.oie)[-1]["payload"]))
+
+
+@pytest.mark.parametrize("st", FAR_STATIONS)
+@pytest.mark.parametrize("i", ORACLE_MAPS)
+def test_the_oracle_alone_leaves_few_bound_candidates_ill_conditioned(pkg, oracle, i, st):
+    """what tests/test_gpu_placed_pyramid.py's default-mode comparison relies on: of the 170 candidates of the set, scored
+    by the oracle on their levels, at most MAX_LEFT_OUT change their score when x / y move by one ulp"""
+    import placed_cases as pc
+    import pyoracle as po
+    rows = bound_probe_rows(pkg, po, oracle, i, st)
+    assert rows.shape == (9, 170) and np.all(np.isfinite(rows))
+    ill = pc.ill_conditioned(rows)
+    print("%s map %d: %d of %d candidates ill-conditioned" % (st, i, ill.sum(), ill.size))
+    assert ill.mean() <= pc.MAX_LEFT_OUT
+    if st == "O":  # the control: the golden's own bounds
+        np.testing.assert_array_equal(rows[0], moved_set(i, st)[1].cand[:, 6])
+
+
+@pytest.mark.parametrize("st", N_STATIONS)
+def test_host_levels_equal_the_references_at_the_n_stations(pkg, st):
+    """tests/golden/placed_pyramid.npz: the compiled reference's dense pyramid 500 ... 1500 cells from the origin -- GridCell
+    under both OIEs, TBM and Credibilist, 37 x 29 off centre and 33 x 33, scales 0.05 / 0.1 / 1.0"""
+    seen, n_maps = set(), placed_counts()[0]
+    for i in range(n_maps):
+        m = placed_golden_map(st, i)
+        assert not (0 <= m.origin[0] < m.width) and not (0 <= m.origin[1] < m.height)
+        levels = pkg.pyramid_build_host(m, m.oie)
+        assert len(levels) == len(m.levels) == expected_level_count(m) == 12
+        for k, (got, want) in enumerate(zip(levels, m.levels), 1):
+            assert got["scale"] == want["scale"]
+            assert_same_level(got["payload"], got["origin"], want["payload"], want["origin"], m.unknown, "%s map %d level %d" % (st, i, k))
+        seen.add((m.width, m.height, m.scale, m.cell_model, m.oie))
+    assert len(seen) == n_maps == 24
+
+
+def test_level_counts_far_from_the_origin(pkg):
+    want = {"O": 6, "Q1": 16, "Q2": 16, "Q3": 16, "Q4": 16, "F1": 23, "F2": 23, "N1": 12, "N2": 12, "N3": 12}
+    got = {st: len(pkg.pyramid_build_host(moved_golden(64, st), 0)) for st in FAR_STATIONS}
+    assert got == want
 
 
 def test_invalid_arguments(pkg):

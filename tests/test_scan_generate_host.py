@@ -71,6 +71,58 @@ def test_the_golden_holds_the_cases(pkg):
     assert {float(G[c + "_scale"]) for c in CALLS} == {0.1, 0.05}
 
 
+# ---- far from the world origin: tests/golden/placed_generate.npz (make_golden_placed_generate.py), the reference's scans on
+# windows 1000 ... 2000 m out, one station per quadrant
+P = np.load(os.path.join(ROOT, "tests", "golden", "placed_generate.npz"))
+P_CALLS = [str(c) for c in P["calls"]]
+P_VARIANT = int(P["sincos_variant"])
+
+
+def placed_map(name):
+    return types.SimpleNamespace(cell_model=int(P[name + "_cell_model"]), payload=P[name + "_payload"],
+                                 origin=tuple(int(v) for v in P[name + "_origin"]), scale=float(P[name + "_scale"]),
+                                 unknown=P[name + "_unknown"], width=P[name + "_payload"].shape[1], height=P[name + "_payload"].shape[0])
+
+
+def placed_call(pkg, c):
+    max_dist, fov, pts = P[c + "_lsp"]
+    _, inc, hs = pkg.to_lsp(max_dist, fov, int(pts))
+    return placed_map(str(P[c + "_map"])), P[c + "_poses"], pkg.scan_gen_angles(hs, inc), float(max_dist), float(P[c + "_threshold"])
+
+
+@pytest.mark.parametrize("c", P_CALLS)
+def test_host_scans_equal_the_references_far_from_the_origin(pkg, c):
+    m, poses, angles, max_dist, thr = placed_call(pkg, c)
+    assert 37 <= angles.size <= 90
+    rng, status = pkg.generate_scans_host(m, poses, angles, max_dist, thr, int(P[c + "_occ_kind"]), P_VARIANT)
+    np.testing.assert_array_equal(status, P[c + "_status"])
+    np.testing.assert_array_equal(rng, P[c + "_range"])
+
+
+def test_the_far_golden_holds_the_cases(pkg):
+    import placed_scenes as ps
+    keys = [str(k) for k in P["stat_keys"]]
+    for st in ps.Q_STATIONS:
+        (kx, ky), _ = ps.STATIONS[st]
+        s = dict(zip(keys, P[st + "_stats"]))
+        for k in ("robot_outside", "tie", "astray", "touch", "leaves_window", "hit_early", "hit_late", "no_hit", "short_walks"):
+            assert s[k] > 0, (st, k)
+        assert s["max_cells"] > 1000
+        models = set()
+        for name in ("cecum", "mean", "tbm", "gmapping"):
+            m = placed_map("%s_%s" % (st, name))
+            models.add(m.cell_model)
+            assert not (0 <= m.origin[0] < m.width) and not (0 <= m.origin[1] < m.height)  # (0, 0) is no cell of the window
+            assert (m.width // 2 - m.origin[0], m.height // 2 - m.origin[1]) == (kx, ky)
+        assert models == {pkg.CELL_OCC, pkg.CELL_TBM, pkg.CELL_GMAPPING}
+        steps = np.concatenate([P[c + "_hit_step"].ravel() for c in P_CALLS if c.startswith(st)])
+        assert np.any(steps == -1) and np.any((steps >= 0) & (steps < 64)) and np.any(steps >= 64)
+    # the scenes are one scene moved by whole cells, and still no two stations' ranges are the same doubles
+    a, b = P["Q1_cecum_long_range"], P["Q3_cecum_long_range"]
+    assert np.array_equal(a != 0, b != 0) and not np.array_equal(a, b)
+    np.testing.assert_allclose(a, b, rtol=0, atol=1e-3)
+
+
 def test_robot_on_a_cell_boundary_is_invalid(pkg):
     m, poses, angles, max_dist, thr = golden_call(pkg, "cecum_short")
     for bad in ([0.2, 0.123, 0.0], [0.123, -0.2, 0.0], [0.2 + 1e-9, 0.123, 0.0]):  # (floor(x / scale) * scale is x)
