@@ -915,6 +915,44 @@ int slamhip_matcher_set_mc_job_streams(slamhip_matcher *m, int n, const int *str
  * stream = -1: the matcher's own enumerator, the one the lone calls use. */
 int slamhip_matcher_mc_stream_info(slamhip_matcher *m, int stream, unsigned long long *pairs_consumed,
                                    long long *matches, double *state5);
+/* K robots' enumerators on ONE brute-force matcher.  In the reference every robot owns its matcher, and a
+ * BruteForcePoseEnumerator latches the pose it is given at the FIRST next() of its life as its base and never clears it
+ * (brute_force_scan_matcher.h:27-40).  With one matcher every job of a batch therefore enumerates around the first job's
+ * first initial pose: right for a sequence of lone calls on one matcher, not what K robots with K matchers compute.
+ * With streams set, the two batch calls run job j on ITS stream, all jobs in three shared launches for any K (score,
+ * scan, decide, grid.y = job; the raw form's assembly launch in front makes four), and job j gets the delta, the
+ * probability, the observer sequence, the counters (scorer calls = 1 + nx ny nt) and, for raw jobs, the kept count of a
+ * lone brute-force matcher with the same configuration and range9, fed that stream's jobs in order, bit for bit.
+ *  - Stream k is what slamhip_matcher_create_bf with this matcher's range9 would own: the same offsets and an UNLATCHED
+ *    base.  n_streams = 0 removes the streams; setting them anew forgets every base and drops the job mapping.  A matcher
+ *    that is not brute force: SLAMHIP_ERR_INVALID.
+ *  - slamhip_matcher_reset_state rewinds every stream as it rewinds the matcher's own enumerator; latched bases stay, as
+ *    the reference's reset() leaves them.
+ *  - A matcher without streams behaves in every entry point as it did before these calls existed (its batch jobs run
+ *    job after job through the lone call, slamhip_matcher_batch_stats reports on_device_chain = 0); a matcher with
+ *    streams changes only the two batch calls: lone slamhip_matcher_process_scan / _process_raw_scan keep using the
+ *    matcher's own enumerator.
+ *  - The shared launches cover what the lone sweep covers over the 1-cell OOPE: the default sum order, device pose
+ *    trigonometry, a low-latency context, the device chain not switched off, maps of one cell model (TBM and
+ *    CREDIBILIST maps through their probability plane wherever the lone call goes through it).  What they do not cover
+ *    runs the lone call ON THE JOB'S OWN STREAM, in job order: window OOPEs, the GMapping OOPE, the beam-order sum, host
+ *    pose trigonometry, n_jobs == 1 (or one non-empty raw job), a job above 4096 beams (that job alone in the array
+ *    form; every job of a raw batch), and a call whose K x (1 + nx ny nt) poses exceed the scratch budget of 2^24 poses
+ *    (the launches keep a score, a fingerprint and a prefix index, 24 bytes, per pose: 384 MiB at the budget; a sweep
+ *    itself holds at most 2^26 poses).  A job whose walk meets a comparison the tree sums cannot settle (the checked
+ *    default mode) is redone alone by the host-driven route on its stream; the other jobs keep their results.  A job's
+ *    result never depends on the route; slamhip_matcher_batch_stats says which it took.
+ *  - A raw job whose filter keeps nothing is NaN, zero delta, no observer call, and does NOT latch its stream's base.
+ *  - Errors found before anything is launched -- unknown map, maps of different cell models, GMAPPING cells, a bad
+ *    stream mapping, null arrays -- leave every stream's base and the last-batch state untouched. */
+int slamhip_matcher_set_bf_streams(slamhip_matcher *m, int n_streams);
+/* which stream job j of the NEXT batch calls uses.  NULL or n = 0: identity (job j on stream j).  Two jobs on one stream,
+ * a stream out of range, more jobs than streams: SLAMHIP_ERR_INVALID, here (the mapping stays what it was) and again in a
+ * batch call -- before anything is staged, launched or latched. */
+int slamhip_matcher_set_bf_job_streams(slamhip_matcher *m, int n, const int *stream_of_job);
+/* a stream's enumerator: whether its base is latched, the base (zeros while it is not), the matches run on it.  Outputs
+ * may be NULL.  stream = -1: the matcher's own enumerator, the one the lone calls use. */
+int slamhip_matcher_bf_stream_info(slamhip_matcher *m, int stream, int *base_set, double base[3], long long *matches);
 /* counters of the last process_scan: scorer calls the reference would have made
  * (= on_scan_test events), poses actually evaluated on the GPU, launches */
 int slamhip_matcher_stats(slamhip_matcher *m, long long *scorer_calls, long long *poses_evaluated,

@@ -73,6 +73,7 @@ slamhip_matcher_m3rsm_rotations slamhip_matcher_set_m3rsm_rotation_slots
 slamhip_scan_table_uploads slamhip_scan_download
 slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download
 slamhip_matcher_set_mc_streams slamhip_matcher_set_mc_job_streams slamhip_matcher_mc_stream_info
+slamhip_matcher_set_bf_streams slamhip_matcher_set_bf_job_streams slamhip_matcher_bf_stream_info
 slamhip_map_append_scan_batch slamhip_map_update_batch_stats slamhip_map_update_batch_tables""".split()
 
 SHARD_ID_BYTES = 128
@@ -321,6 +322,9 @@ def load(testing=False):
     L.slamhip_matcher_set_mc_streams.argtypes = [vp, i, up]
     L.slamhip_matcher_set_mc_job_streams.argtypes = [vp, i, _ip]
     L.slamhip_matcher_mc_stream_info.argtypes = [vp, i, C.POINTER(C.c_ulonglong), ll, _dp]
+    L.slamhip_matcher_set_bf_streams.argtypes = [vp, i]
+    L.slamhip_matcher_set_bf_job_streams.argtypes = [vp, i, _ip]
+    L.slamhip_matcher_bf_stream_info.argtypes = [vp, i, _ip, _dp, ll]
     _libs[testing] = L
     return L
 
@@ -1207,6 +1211,27 @@ class Matcher:
         _check(self.L.slamhip_matcher_mc_stream_info(self.h, int(stream), C.byref(pairs), C.byref(matches), st))
         return dict(pairs_consumed=pairs.value, matches=matches.value, failed=int(st[0]), poses=int(st[1]), td=st[2],
                     rd=st[3], has_saved=bool(st[4]))
+
+    def set_bf_streams(self, n):
+        """K robots' enumerators on this brute-force matcher (slamhip_matcher_set_bf_streams): stream k is what a matcher
+        of its own with the same ranges would hold, its base unlatched; the batch calls then run job j on its stream,
+        all jobs in three shared launches.  0 removes the streams."""
+        _check(self.L.slamhip_matcher_set_bf_streams(self.h, int(n)))
+
+    def set_bf_job_streams(self, streams=None):
+        """Which stream job j of the next batch calls uses (None: job j on stream j)."""
+        if not streams:
+            _check(self.L.slamhip_matcher_set_bf_job_streams(self.h, 0, None))
+            return
+        arr = (C.c_int * len(streams))(*[int(v) for v in streams])
+        _check(self.L.slamhip_matcher_set_bf_job_streams(self.h, len(streams), arr))
+
+    def bf_stream_info(self, stream=-1):
+        """Whether a stream's base is latched, the base and the matches run on it; -1: the matcher's own enumerator,
+        the one the lone calls use."""
+        bs, base, matches = C.c_int(), (C.c_double * 3)(), C.c_longlong()
+        _check(self.L.slamhip_matcher_bf_stream_info(self.h, int(stream), C.byref(bs), base, C.byref(matches)))
+        return dict(base_set=bool(bs.value), base=np.array(list(base)), matches=matches.value)
 
     def chain_stats(self):
         kl, rs = C.c_longlong(), C.c_longlong()

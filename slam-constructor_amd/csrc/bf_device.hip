@@ -15,6 +15,7 @@
 // match on the host-driven path, which settles such comparisons from beam-order sums.
 #include <hip/hip_runtime.h>
 
+#include "bf_argmax_device.h"
 #include "bf_device.h"
 
 namespace slamhip {
@@ -22,131 +23,21 @@ namespace slamhip {
 __global__ __launch_bounds__(256) void k_bf_poses(BfPoseArgs a) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
-  double x = a.init[0], y = a.init[1], th = a.init[2];
-  if (i > 0) {  // pose 0 is the initial pose itself (scored first, pose_enumeration_scan_matcher.h:40-47)
-    const long long j = i - 1;
-    const int ix = (int)(j % a.nx);
-    const long long r = j / a.nx;
-    const int iy = (int)(r % a.ny), it = (int)(r / a.ny);
-    x = a.base[0] + a.off[ix];
-    y = a.base[1] + a.off[a.nx + iy];
-    th = a.base[2] + a.off[a.nx + a.ny + it];
-  }
+  double x, y, th;
+  bf_pose_of(i, a.init, a.base, a.off, a.nx, a.ny, &x, &y, &th);  // (bf_argmax_device.h: the batch makes its poses by it too)
   a.poses[3 * i] = x;
   a.poses[3 * i + 1] = y;
   a.poses[3 * i + 2] = th;
 }
 
-namespace {
-// (score, index) of the walk's best so far; a later element replaces it only when STRICTLY greater -- the
-// reference's `best < candidate` (ties and NaN are rejections), so the fold is associative and the first maximum wins
-struct BfBest {
-  double s;
-  long long i;
-};
-__device__ __forceinline__ BfBest bf_fold(const BfBest &earlier, const BfBest &later) {
-  return later.s > earlier.s ? later : earlier;
-}
-__device__ __forceinline__ BfBest bf_shfl_up(const BfBest &v, int d) {
-  BfBest o;
-  o.s = __shfl_up(v.s, d, 64);
-  o.i = __shfl_up(v.i, d, 64);
-  return o;
-}
-constexpr int kBfBlock = 1024;
-}  // namespace
-
-// Stage 1, one candidate per thread (coalesced): the inclusive scan of the walk inside a block of 1024 candidates.
-// Every candidate learns the best of the candidates in front of it in ITS block (pidx, -1 = none); the block's own
-// best goes to agg.
+// Stage 1 and stage 2 of the arg-max (bf_scan_body, bf_decide_body: bf_argmax_device.h, shared with the batch's
+// kernels).  The last block of the decide stage to finish publishes the result.
 __global__ __launch_bounds__(kBfBlock) void k_bf_scan(BfArgmaxArgs a) {
-  __shared__ double s_ws[16];
-  __shared__ long long s_wi[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const long long e = 1 + (long long)blockIdx.x * kBfBlock + t;
-  BfBest v{-__builtin_inf(), -1};
-  if (e < a.n) {
-    const double s = a.scores[e];
-    if (s == s) v = BfBest{s, e};  // (a NaN is never accepted: it takes part as -infinity)
-  }
-  BfBest inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const BfBest o = bf_shfl_up(inc, d);
-    if (lane >= d) inc = bf_fold(o, inc);
-  }
-  if (lane == 63) {
-    s_ws[wave] = inc.s;
-    s_wi[wave] = inc.i;
-  }
-  __syncthreads();
-  BfBest before{-__builtin_inf(), -1};  // the waves in front of this one
-  for (int w = 0; w < wave; ++w) before = bf_fold(before, BfBest{s_ws[w], s_wi[w]});
-  BfBest excl = bf_shfl_up(inc, 1);
-  if (lane == 0) excl = BfBest{-__builtin_inf(), -1};
-  excl = bf_fold(before, excl);
-  if (e < a.n) a.pidx[e] = excl.i;
-  if (t == kBfBlock - 1) {
-    const BfBest all = bf_fold(before, inc);
-    a.agg_s[blockIdx.x] = all.s;
-    a.agg_i[blockIdx.x] = all.i;
-  }
+  bf_scan_body(blockIdx.x, a.scores, a.n, a.pidx, a.agg_s, a.agg_i);
 }
 
-// Stage 2, same grid: a candidate meets the walk's state in front of it -- the initial pose folded with the blocks
-// before its own and with its block's prefix -- with the reference's exact rule and the checked mode's closeness
-// test.  The last block to finish publishes the result.
 __global__ __launch_bounds__(kBfBlock) void k_bf_decide(BfArgmaxArgs a) {
-  __shared__ double s_in_s;
-  __shared__ long long s_in_i;
-  __shared__ int s_last;
-  const int t = threadIdx.x, lane = t & 63;
-  const long long e = 1 + (long long)blockIdx.x * kBfBlock + t;
-  if (t == 0) {
-    BfBest b{a.scores[0], 0};
-    for (unsigned j = 0; j < blockIdx.x; ++j) b = bf_fold(b, BfBest{a.agg_s[j], a.agg_i[j]});
-    s_in_s = b.s;
-    s_in_i = b.i;
-  }
-  __syncthreads();
-  bool acc = false, amb = false;
-  if (e < a.n) {
-    BfBest prev{s_in_s, s_in_i};
-    const long long pi = a.pidx[e];
-    if (pi >= 0) prev = bf_fold(prev, BfBest{a.scores[pi], pi});
-    const double s = a.scores[e];
-    if (a.verify) {
-      const double diff = __builtin_fabs(s - prev.s);
-      const double as = __builtin_fabs(s), ab = __builtin_fabs(prev.s);
-      if (diff <= (as > ab ? as : ab) * 9.094947017729282e-13) {
-        // close: settled only when the two term vectors are identical (equal fingerprints AND equal sums)
-        amb = a.fprints[e] != a.fprints[prev.i] || __double_as_longlong(s) != __double_as_longlong(prev.s);
-      }
-    }
-    acc = prev.s < s;
-  }
-  const unsigned long long accs = __ballot(acc), ambs = __ballot(amb);
-  if (lane == 0) {
-    if (accs) atomicAdd(a.counters + 0, (unsigned)__popcll(accs));
-    if (ambs) atomicOr(a.counters + 1, 1u);
-  }
-  __syncthreads();
-  if (t == 0) {
-    __threadfence();
-    s_last = atomicAdd(a.counters + 2, 1u) + 1u == gridDim.x ? 1 : 0;
-  }
-  __syncthreads();
-  if (s_last && t == 0) {
-    __threadfence();
-    BfBest b{a.scores[0], 0};
-    for (unsigned j = 0; j < gridDim.x; ++j) b = bf_fold(b, BfBest{a.agg_s[j], a.agg_i[j]});
-    a.out->best_index = b.i;
-    a.out->best_score = b.s;
-    a.out->accepts = (long long)__hip_atomic_load(a.counters + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a.out->ambiguous = (int)__hip_atomic_load(a.counters + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(a.counters + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(a.counters + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(a.counters + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (bf_decide_body(blockIdx.x, gridDim.x, a.scores, a.fprints, a.n, a.verify, a.pidx, a.agg_s, a.agg_i, a.counters, a.out)) {
     __threadfence_system();
     __hip_atomic_store(&a.out->seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }

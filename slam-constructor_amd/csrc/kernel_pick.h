@@ -60,6 +60,16 @@ auto pick_mc_nt(int nt, F &&f) -> decltype(f(int_c<512>{})) {
   return mc_nt_of(nt) == 512 ? f(int_c<512>{}) : f(int_c<1024>{});
 }
 
+// poses per workgroup of the 1-cell scorers (k_score_point, k_bf_score_batch) for a launch of n_poses: enough workgroups
+// to fill 256 CUs several times over, while amortising the per-workgroup beam-constant loads (40 B/beam) over several
+// poses once there are plenty of poses.  Results do not depend on it.
+inline int pick_poses_per_block(long long n_poses) {
+  if (n_poses >= 8192) return 8;
+  if (n_poses >= 2048) return 4;
+  if (n_poses >= 1024) return 2;
+  return 1;
+}
+
 // ---- the one launch.  Scoring and chain launches go through hipExtLaunchKernel when an event is given, so that
 // slamhip_profile_* can attach its HIP events to the dispatch itself: the elapsed time is then the kernel's own
 // begin..end (what rocprofv3 --kernel-trace reports), not record-to-record on an idle stream which adds ~4 us of

@@ -6,6 +6,8 @@
 #include <limits>
 #include <mutex>
 
+#include "bf_batch.h"
+#include "bf_batch_plan.h"
 #include "bf_device.h"
 #include "hc_chain_device.h"
 #include "hc_shape.h"
@@ -198,6 +200,26 @@ struct McBatch {
   int slots = 0;             // candidates per job and super-step of the last call
 };
 
+// K brute-force sweeps per call (bf_batch_run): the staged job table, the jobs' slices of the flat score / fingerprint /
+// prefix arrays, per job its aggregates, three counter words and its entry of the pinned result array, the call's ONE
+// completion word, and what the hand-over needs to turn a best index into a pose
+struct BfBatch {
+  int job_cap = 0;
+  long long pose_cap = 0, blk_cap = 0;
+  slamhip::PinnedBuf<slamhip::BfJobView> h_jobs;
+  slamhip::DeviceBuf<slamhip::BfJobView> d_jobs;
+  slamhip::DeviceBuf<double> d_scores, d_agg_s;
+  slamhip::DeviceBuf<unsigned long long> d_fp;
+  slamhip::DeviceBuf<long long> d_pidx, d_agg_i;
+  slamhip::DeviceBuf<unsigned> d_counters;
+  slamhip::PinnedBuf<slamhip::BfHostOut> h_out;
+  slamhip::PinnedBuf<unsigned> h_done;
+  unsigned seq = 0;
+  long long n = 0;                // poses per job of the last call
+  std::vector<double> poses6;     // per job of the last call: its initial pose, its base
+  std::vector<double> scores_host;  // the last call's K x n scores (observer attached only)
+};
+
 struct slamhip_matcher {
   // ---- what every kind of matcher has
   slamhip_ctx *ctx = nullptr;
@@ -300,7 +322,12 @@ struct slamhip_matcher {
     long long cap = 0;
     unsigned seq = 0;
     std::vector<double> scores_host;
+    bool skip_device = false;  // the next lone match goes straight to the host-driven batches (a batch's ambiguous job)
   } bf;
+  // ---- K robots' enumerators on one brute-force matcher (slamhip_matcher_set_bf_streams; bf_batch_plan.h)
+  slamhip::BfStreams bf_streams;
+  long long bf_matches = 0;  // matches run on the matcher's own enumerator
+  std::unique_ptr<BfBatch> bf_batch;
   // ---- the multi-resolution matcher (BF_M3RSM): the best-first engine of m3rsm_engine.h over a pyramid's expand launches
   struct M3rsm {
     slamhip_pyramid *pyr = nullptr;  // the caller's; must outlive the matcher's matches
@@ -1399,8 +1426,8 @@ bool bf_device_eligible(slamhip_matcher *m) {
   return m->chain_mode >= 1;  // (slamhip_matcher_set_device_chain(0) keeps the host-driven batches)
 }
 
-int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
-                           double *out_prob) {
+// the enumerator's offsets on the host and in HBM, made once per matcher (kChainNeedsHost: an axis too long for a sweep)
+int bf_sweep_offsets(slamhip_matcher *m) {
   slamhip_ctx *ctx = m->ctx;
   slamhip_matcher::BfSweep &bf = m->bf;
   if (bf.off.empty()) {
@@ -1431,6 +1458,52 @@ int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pos
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
     SLAMHIP_CHECK(bf.h_out.alloc(1, kPinnedCoherent));
     std::memset(bf.h_out.get(), 0, sizeof(BfHostOut));
+  }
+  return SLAMHIP_OK;
+}
+
+// pose i of a sweep around `base` whose match started at `init` (k_bf_poses' additions)
+void bf_pose_of_host(const slamhip_matcher::BfSweep &bf, const double *init, const double *base, long long i, double p3[3]) {
+  p3[0] = init[0];
+  p3[1] = init[1];
+  p3[2] = init[2];
+  if (i > 0) {
+    const long long j = i - 1;
+    const int ix = (int)(j % bf.nx);
+    const long long r = j / bf.nx;
+    const int iy = (int)(r % bf.ny), it = (int)(r / bf.ny);
+    p3[0] = base[0] + bf.off[ix];
+    p3[1] = base[1] + bf.off[bf.nx + iy];
+    p3[2] = base[2] + bf.off[bf.nx + bf.ny + it];
+  }
+}
+
+// the observer's events of one sweep in the reference's order, from its score array (:43-46, :53-60); on_matching_end
+// is the caller's
+void bf_replay_scores(const slamhip_observer &obs, const slamhip_matcher::BfSweep &bf, const double *init, const double *base,
+                      const double *sc, long long n) {
+  double b = sc[0];
+  double p3[3];
+  bf_pose_of_host(bf, init, base, 0, p3);
+  if (obs.on_scan_test) obs.on_scan_test(obs.user, p3, sc[0]);
+  if (obs.on_pose_update) obs.on_pose_update(obs.user, p3, sc[0]);
+  for (long long i = 1; i < n; ++i) {
+    bf_pose_of_host(bf, init, base, i, p3);
+    if (obs.on_scan_test) obs.on_scan_test(obs.user, p3, sc[i]);
+    if (b < sc[i]) {
+      b = sc[i];
+      if (obs.on_pose_update) obs.on_pose_update(obs.user, p3, sc[i]);
+    }
+  }
+}
+
+int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pose[3], double out_delta[3],
+                           double *out_prob) {
+  slamhip_ctx *ctx = m->ctx;
+  slamhip_matcher::BfSweep &bf = m->bf;
+  {
+    const int prc = bf_sweep_offsets(m);
+    if (prc) return prc;
   }
   const long long n = 1 + (long long)bf.nx * bf.ny * bf.nt;
   if (n > (1ll << 26)) return kChainNeedsHost;
@@ -1521,22 +1594,8 @@ int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pos
     ctx->prof_units += n * (long long)a.scan.n;
   }
   if (h->ambiguous) return kChainNeedsHost;  // nothing reported yet: the host-driven batches settle it
-  auto pose_of = [&](long long i, double p3[3]) {
-    p3[0] = init_pose[0];
-    p3[1] = init_pose[1];
-    p3[2] = init_pose[2];
-    if (i > 0) {
-      const long long j = i - 1;
-      const int ix = (int)(j % bf.nx);
-      const long long r = j / bf.nx;
-      const int iy = (int)(r % bf.ny), it = (int)(r / bf.ny);
-      p3[0] = base3[0] + bf.off[ix];
-      p3[1] = base3[1] + bf.off[bf.nx + iy];
-      p3[2] = base3[2] + bf.off[bf.nx + bf.ny + it];
-    }
-  };
   double best[3];
-  pose_of(h->best_index, best);
+  bf_pose_of_host(bf, init_pose, base3, h->best_index, best);
   for (int k = 0; k < 3; ++k) out_delta[k] = best[k] - init_pose[k];
   *out_prob = h->best_score;
   MatchJob &job = m->job;
@@ -1552,20 +1611,7 @@ int bf_device_process_scan(slamhip_matcher *m, int map_id, const double init_pos
   if (m->has_obs) {
     // the observer's events in the reference's order, from the score array (:43-46, :53-60)
     const double t1 = MatchJob::now_us();
-    const double *sc = bf.scores_host.data();
-    double b = sc[0];
-    double p3[3];
-    pose_of(0, p3);
-    if (m->obs.on_scan_test) m->obs.on_scan_test(m->obs.user, p3, sc[0]);
-    if (m->obs.on_pose_update) m->obs.on_pose_update(m->obs.user, p3, sc[0]);
-    for (long long i = 1; i < n; ++i) {
-      pose_of(i, p3);
-      if (m->obs.on_scan_test) m->obs.on_scan_test(m->obs.user, p3, sc[i]);
-      if (b < sc[i]) {
-        b = sc[i];
-        if (m->obs.on_pose_update) m->obs.on_pose_update(m->obs.user, p3, sc[i]);
-      }
-    }
+    bf_replay_scores(m->obs, bf, init_pose, base3, bf.scores_host.data(), n);
     job.t_replay_us = MatchJob::now_us() - t1;
     if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, out_delta, *out_prob);
   }
@@ -1977,15 +2023,237 @@ int mc_job_streams_of(const slamhip_matcher *m, int n_jobs, std::vector<int> *ou
   return SLAMHIP_OK;
 }
 
+// ---- K brute-force sweeps in three shared launches (bf_batch.hip) ---------------------------------------------
+// BruteForceScanMatcher::process_scan once per robot: job c = (scan c, initial pose c, map c) on enumerator stream
+// streams[c] (slamhip_matcher_set_bf_streams).  A brute-force enumerator hands out the same poses whatever the scorer
+// says, so nothing is speculated: the K sweeps are one grid (grid.y = job) through score, scan and decide, and ONE
+// completion word tells the host that all K results lie in the pinned array.
+
+// the matcher-level conditions of the shared sweeps: the lone sweep's (bf_device_eligible) over the 1-cell OOPE, with
+// enumerator streams set
+bool bf_batch_eligible(slamhip_matcher *m) {
+  if (!m->is_bf || !m->bf_streams.any()) return false;
+  if (m->cfg.oope != SLAMHIP_OOPE_OBSTACLE) return false;
+  return bf_device_eligible(m);
+}
+
+// whether the shared sweeps take n jobs of this matcher: its offsets made, K x n within the scratch budget
+int bf_batch_fits(slamhip_matcher *m, int n_jobs, bool *fits) {
+  *fits = false;
+  const int rc = bf_sweep_offsets(m);
+  if (rc == kChainNeedsHost) return SLAMHIP_OK;
+  if (rc) return rc;
+  const long long n = 1 + (long long)m->bf.nx * m->bf.ny * m->bf.nt;
+  *fits = n >= 2 && n <= (1ll << 26) && n_jobs <= 65535 && (long long)n_jobs * n <= kBfBatchMaxPoses;
+  return SLAMHIP_OK;
+}
+
+// The shared launches over n matches whose scans lie in HBM (blocks); job c gives its map and initial pose and runs on
+// enumerator stream streams[c].  Everything that can fail for the caller's arguments has been checked (the entry
+// points), the views and the blocks are made before a stream latches its base.  Results go to m->batch->res[c]; a job
+// whose walk met a comparison the tree sums cannot settle is left to the lone route (on_chain false, error 4).
+template <class Job>
+int bf_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBlock *blocks, const int *streams) {
+  slamhip_ctx *ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  slamhip_matcher::BfSweep &bf = m->bf;
+  if (!m->bf_batch) m->bf_batch = std::make_unique<BfBatch>();
+  BfBatch *s = m->bf_batch.get();
+  const long long np = 1 + (long long)bf.nx * bf.ny * bf.nt;
+  const long long per_blk = (np - 1 + 1023) / 1024;
+  if (n > s->job_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+    int cap = 8;
+    while (cap < n) cap *= 2;
+    s->job_cap = 0;
+    SLAMHIP_CHECK(s->h_jobs.alloc(cap, hipHostMallocDefault));
+    SLAMHIP_CHECK(s->d_jobs.alloc(cap));
+    SLAMHIP_CHECK(s->d_counters.alloc(3 * (size_t)cap + 1));
+    SLAMHIP_CHECK(hipMemsetAsync(s->d_counters.get(), 0, sizeof(unsigned) * (3 * (size_t)cap + 1), st));
+    SLAMHIP_CHECK(s->h_out.alloc(cap, kPinnedCoherent));
+    std::memset(s->h_out.get(), 0, sizeof(BfHostOut) * cap);
+    if (!s->h_done) {
+      SLAMHIP_CHECK(s->h_done.alloc(1, kPinnedCoherent));
+      *s->h_done.get() = 0;
+    }
+    s->job_cap = cap;
+  }
+  // (the jobs-done word lies behind the LAST job's counters of the call: zero, as every word of the block between calls)
+  if ((long long)n * np > s->pose_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+    s->pose_cap = 0;
+    long long cap = 1 << 14;
+    while (cap < (long long)n * np) cap *= 2;
+    SLAMHIP_CHECK(s->d_scores.alloc(cap));
+    SLAMHIP_CHECK(s->d_fp.alloc(cap));
+    SLAMHIP_CHECK(s->d_pidx.alloc(cap));
+    s->pose_cap = cap;
+  }
+  if ((long long)n * per_blk > s->blk_cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+    s->blk_cap = 0;
+    long long cap = 64;
+    while (cap < (long long)n * per_blk) cap *= 2;
+    SLAMHIP_CHECK(s->d_agg_s.alloc(cap));
+    SLAMHIP_CHECK(s->d_agg_i.alloc(cap));
+    s->blk_cap = cap;
+  }
+  // the views a lone sweep of each job would score through; one effective cell model and OIE for the launch
+  int cell_model = -1, oie_eff = m->cfg.oie, max_n = 0;
+  std::vector<double> inits(3 * (size_t)n);
+  for (int c = 0; c < n; ++c) {
+    BfJobView &v = s->h_jobs.get()[c];
+    std::memset(&v, 0, sizeof(v));
+    int model = 0, oie = 0;
+    const int rc = score_map_view(ctx, jobs[c].map_id, &m->cfg, &v.map, &model, &oie);
+    if (rc) return rc;
+    if (c > 0 && (model != cell_model || oie != oie_eff)) return invalid_arg("the maps of one batch must share a cell model");
+    cell_model = model;
+    oie_eff = oie;
+    v.scan = scan_view_of(blocks[c].d, blocks[c].stride, blocks[c].n, blocks[c].tot_w);
+    max_n = std::max(max_n, blocks[c].n);
+    for (int q = 0; q < 3; ++q) inits[3 * (size_t)c + q] = v.init[q] = jobs[c].init_pose[q];
+    v.at = (long long)c * np;
+    v.blk = (long long)c * per_blk;
+  }
+  (void)tie_check_default(m);
+  const bool verify = m->tie_check == 1;
+  // ---- validation lies behind: the streams latch, the jobs learn their bases
+  const BfBatchPlan plan = m->bf_streams.plan(n, streams, inits.data(), nullptr);
+  m->bf_streams.commit(plan);
+  s->poses6.resize(6 * (size_t)n);
+  for (int c = 0; c < n; ++c) {
+    BfJobView &v = s->h_jobs.get()[c];
+    for (int q = 0; q < 3; ++q) {
+      v.base[q] = plan.base[3 * (size_t)c + q];
+      s->poses6[6 * (size_t)c + q] = v.init[q];
+      s->poses6[6 * (size_t)c + 3 + q] = v.base[q];
+    }
+  }
+  s->n = np;
+  const double t0 = MatchJob::now_us();
+  SLAMHIP_CHECK(hipMemcpyAsync(s->d_jobs.get(), s->h_jobs.get(), sizeof(BfJobView) * (size_t)n, hipMemcpyHostToDevice, st));
+  BfBatchArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.jobs = s->d_jobs.get();
+  a.off = bf.d_off.get();
+  a.nx = bf.nx;
+  a.ny = bf.ny;
+  a.nt = bf.nt;
+  a.n = (int)np;
+  a.n_jobs = n;
+  a.oie = oie_eff;
+  a.poses_per_block = 0;  // (launch_bf_batch: pick_poses_per_block(K n))
+  a.verify = verify ? 1 : 0;
+  a.scores = s->d_scores.get();
+  a.fprints = s->d_fp.get();
+  a.pidx = s->d_pidx.get();
+  a.agg_s = s->d_agg_s.get();
+  a.agg_i = s->d_agg_i.get();
+  a.counters = s->d_counters.get();
+  a.out = s->h_out.get();
+  a.done = s->h_done.get();
+  const unsigned seq = a.seq = next_epoch(s->seq);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  {
+    const int rc = profile_event_pair(ctx, &e0, &e1);
+    if (rc) return rc;
+  }
+  if (e0) SLAMHIP_CHECK(hipEventRecord(e0, st));
+  SLAMHIP_CHECK(launch_bf_batch(a, cell_model, max_n, st));
+  if (e1) SLAMHIP_CHECK(hipEventRecord(e1, st));
+  if (m->has_obs) {  // (the K x n scores in one copy)
+    s->scores_host.resize((size_t)n * (size_t)np);
+    SLAMHIP_CHECK(hipMemcpyAsync(s->scores_host.data(), s->d_scores.get(), sizeof(double) * (size_t)n * (size_t)np,
+                                 hipMemcpyDeviceToHost, st));
+  }
+  volatile unsigned *done = s->h_done.get();
+  unsigned long long spins = 0;
+  while (*done != seq) {
+    __builtin_ia32_pause();
+    if ((++spins & 0xfffffull) == 0) {
+      hipError_t qe = hipStreamQuery(st);
+      if (qe != hipSuccess && qe != hipErrorNotReady) return hip_fail(qe, "batched brute-force sweeps");
+    }
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  if (m->has_obs) SLAMHIP_CHECK(hipStreamSynchronize(st));
+  HcBatch *b = m->batch.get();
+  long long units = 0;
+  for (int c = 0; c < n; ++c) {
+    const volatile BfHostOut *h = &s->h_out.get()[c];
+    BatchJobResult &r = b->res[c];
+    units += np * (long long)blocks[c].n;
+    if (h->ambiguous) {  // nothing reported yet: the host-driven batches settle it, on the job's stream
+      r.error = 4;
+      r.on_chain = false;
+      continue;
+    }
+    r.error = 0;
+    r.on_chain = true;
+    bf_pose_of_host(bf, &s->poses6[6 * (size_t)c], &s->poses6[6 * (size_t)c + 3], h->best_index, r.pose);
+    r.prob = h->best_score;
+    r.calls = r.evaluated = np;
+    r.rescored = 0;
+    r.steps = 1;
+    ++m->bf_streams.s[(size_t)streams[c]].matches;
+  }
+  b->kernels = 3;  // score, scan, decide
+  m->tail_calls = 0;
+  m->t_stage_us = 0;
+  m->t_score_us = MatchJob::now_us() - t0;
+  if (ctx->profile) {
+    ctx->prof_launches += 1;
+    ctx->prof_units += units;
+  }
+  return SLAMHIP_OK;
+}
+
+// the enumerator stream of every job of a batch call (slamhip_matcher_set_bf_job_streams; none set: job j on stream
+// j), checked before anything is staged, launched or latched
+int bf_job_streams_of(const slamhip_matcher *m, int n_jobs, std::vector<int> *out) {
+  if (const char *why = m->bf_streams.streams_of(n_jobs, out)) return invalid_arg(why);
+  return SLAMHIP_OK;
+}
+
 // a batch call's fall-back: the lone path on the job's OWN stream -- its enumerator (and match count) in the matcher's
-// place for the call
-struct McStreamSwap {
+// place for the call.  A Monte-Carlo stream IS an enumerator object; a brute-force stream's is made for the call from
+// the stream's record (its base, if latched) and the record follows what the call did to it.
+struct JobStreamSwap {
   slamhip_matcher *m;
   int k;
-  McStreamSwap(slamhip_matcher *m_, int k_) : m(m_), k(k_) { swap(); }
-  ~McStreamSwap() { swap(); }
-  void swap() {
+  std::unique_ptr<slamhip::PoseEnumerator> own;  // (brute force: the matcher's own enumerator while the stream's is in)
+  JobStreamSwap(slamhip_matcher *m_, int k_) : m(m_), k(k_) {
     if (k < 0) return;
+    if (m->is_bf) {
+      BfStream &rec = m->bf_streams.s[(size_t)k];
+      auto pe = std::make_unique<BruteForcePoseEnumerator>(m->bf.r);
+      if (rec.base_set) pe->latch_base(Pose{rec.base[0], rec.base[1], rec.base[2]});
+      own = std::move(m->pe);
+      m->pe = std::move(pe);
+      std::swap(m->bf_matches, rec.matches);
+    } else {
+      swap_mc();
+    }
+  }
+  ~JobStreamSwap() {
+    if (k < 0) return;
+    if (m->is_bf) {
+      BfStream &rec = m->bf_streams.s[(size_t)k];
+      const auto *pe = static_cast<const BruteForcePoseEnumerator *>(m->pe.get());
+      rec.base_set = pe->base_set();
+      if (rec.base_set) {
+        rec.base[0] = pe->base().x;
+        rec.base[1] = pe->base().y;
+        rec.base[2] = pe->base().theta;
+      }
+      m->pe = std::move(own);
+      std::swap(m->bf_matches, rec.matches);
+    } else {
+      swap_mc();
+    }
+  }
+  void swap_mc() {
     std::swap(m->pe, m->mc_streams[k].pe);
     std::swap(m->mc_matches, m->mc_streams[k].matches);
   }
@@ -2070,10 +2338,17 @@ int batch_hand_over(slamhip_matcher *m, int n_jobs, const Job *jobs, const std::
       for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
       out_probs[c] = r.prob;
       if (m->has_obs) {
-        replay_trace(m->obs, chain_trace + (size_t)live * chain_trace_per, r.calls);
+        if (m->is_bf) {  // (a sweep has no trace: its events from its slice of the call's score array)
+          const BfBatch *s = m->bf_batch.get();
+          bf_replay_scores(m->obs, m->bf, &s->poses6[6 * (size_t)live], &s->poses6[6 * (size_t)live + 3],
+                           s->scores_host.data() + (size_t)live * (size_t)s->n, s->n);
+        } else {
+          replay_trace(m->obs, chain_trace + (size_t)live * chain_trace_per, r.calls);
+        }
         if (m->obs.on_matching_end) m->obs.on_matching_end(m->obs.user, dl, r.prob);
       }
     } else {
+      const bool bf_unsettled = m->is_bf && r.error == 4;  // (the shared sweeps met a comparison they cannot settle)
       r = BatchJobResult{};
       if (live < 0) {
         dl[0] = dl[1] = dl[2] = 0.0;
@@ -2082,8 +2357,10 @@ int batch_hand_over(slamhip_matcher *m, int n_jobs, const Job *jobs, const std::
         keep.arm();
         int rc;
         {
-          McStreamSwap own(m, sid.empty() ? -1 : sid[c]);  // (the job's engine for the call)
+          JobStreamSwap own(m, sid.empty() ? -1 : sid[c]);  // (the job's engine / enumerator for the call)
+          m->bf.skip_device = bf_unsettled;
           rc = lone(j, keep, dl, &out_probs[c], &kept);
+          m->bf.skip_device = false;
         }
         if (rc) return rc;
         if constexpr (kRaw) b->raw_blocks[c] = HcBatch::RawBlock{nullptr, 0, kept, true};
@@ -2648,7 +2925,7 @@ int slamhip_matcher_create_bf(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, cons
 
 int slamhip_matcher_destroy(slamhip_matcher *m) {
   if (m) {
-    if (m->hc.d_chain || m->batch || m->bf.d_poses) {
+    if (m->hc.d_chain || m->batch || m->bf.d_poses || m->bf_batch) {
       // run-ahead kernels of the last chain may still read the blocks; the context may already be gone
       // (destroying it synchronised its stream), so wait on the device, not on the context's stream
       hipSetDevice(m->device);
@@ -2663,6 +2940,7 @@ int slamhip_matcher_reset_state(slamhip_matcher *m) {
   if (!m) return invalid_arg("null matcher");
   if (m->pe) m->pe->reset();  // (the multi-resolution matcher keeps no state between matches)
   for (slamhip_matcher::McStream &k : m->mc_streams) k.pe->reset();  // (the engines' positions stay)
+  m->bf_streams.reset();  // (the latched bases stay, as the reference's reset() leaves them)
   return SLAMHIP_OK;
 }
 
@@ -2732,25 +3010,73 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
   }
   // a Monte-Carlo matcher with engine streams: job c runs on ITS stream, in the shared launches or through the lone
   // path.  Everything that can be refused is refused here, before a stream or the last-batch state is touched.
+  // A brute-force matcher with enumerator streams (slamhip_matcher_set_bf_streams) likewise: job c enumerates around ITS
+  // stream's base, in the shared sweeps or through the lone path; without streams its jobs run job after job through
+  // the lone call on the matcher's own enumerator, as ever.
   const bool mc_streams = m->is_mc && !m->mc_streams.empty();
+  const bool bf_streams = m->is_bf && m->bf_streams.any();
   std::vector<int> sid;
-  bool chains = n_jobs > 1 && (mc_streams ? mc_batch_eligible(m) : batch_chain_eligible(m));
-  for (int c = 0; c < n_jobs && chains; ++c)
+  bool chains = n_jobs > 1 && (mc_streams ? mc_batch_eligible(m) : (bf_streams ? bf_batch_eligible(m) : batch_chain_eligible(m)));
+  if (m->is_bf && !bf_streams) chains = false;
+  // the jobs the shared launches take.  The chains take all or none; of a brute-force batch a job above 4096 beams
+  // leaves alone (dev_of[c] < 0: the lone call on its stream) and the others stay.
+  std::vector<int> dev_of;
+  int n_dev = n_jobs;
+  if (chains && bf_streams) {
+    dev_of.assign(n_jobs, -1);
+    n_dev = 0;
+    for (int c = 0; c < n_jobs; ++c)
+      if ((jobs[c].scan_slot >= 0 ? ctx->scan_slots[jobs[c].scan_slot].n : jobs[c].n) <= kBfBatchMaxBeams) dev_of[c] = n_dev++;
+    chains = n_dev > 1;
+  }
+  for (int c = 0; c < n_jobs && chains && !bf_streams; ++c)
     chains = (jobs[c].scan_slot >= 0 ? ctx->scan_slots[jobs[c].scan_slot].n : jobs[c].n) <= 4096;
   int cell_model = -1;
   if (mc_streams) {
     const int rc = mc_job_streams_of(m, n_jobs, &sid);
     if (rc) return rc;
   }
-  if (chains || mc_streams) {  // (the lone route of a hill-climbing or brute-force job checks its map for itself)
+  if (bf_streams) {
+    const int rc = bf_job_streams_of(m, n_jobs, &sid);
+    if (rc) return rc;
+  }
+  if (chains || mc_streams || bf_streams) {  // (the lone route of a hill-climbing or brute-force job checks its map for itself)
     const int rc = batch_maps_check(ctx, n_jobs, jobs, chains ? &cell_model : nullptr);
     if (rc) return rc;
   }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  if (chains && bf_streams) {  // (the offsets made, K x n within the scratch budget: else every job alone)
+    const int rc = bf_batch_fits(m, n_dev, &chains);
+    if (rc) return rc;
+  }
   if (!m->batch) m->batch = std::make_unique<HcBatch>();
   HcBatch *b = m->batch.get();
-  b->res.assign(n_jobs, BatchJobResult{});
-  b->kernels = 0;
+  if (chains && bf_streams) {
+    std::vector<slamhip_match_job> dj(n_dev);
+    std::vector<int> dsid(n_dev);
+    for (int c = 0; c < n_jobs; ++c)
+      if (dev_of[c] >= 0) {
+        dj[dev_of[c]] = jobs[c];
+        dsid[dev_of[c]] = sid[c];
+      }
+    std::vector<BatchScanBlock> blocks(n_dev);
+    int rc = hc_batch_stage_scans(m, n_dev, dj.data(), blocks.data());
+    if (rc) return rc;
+    b->res.assign(n_jobs, BatchJobResult{});
+    b->kernels = 0;
+    rc = bf_batch_run(m, n_dev, dj.data(), blocks.data(), dsid.data());
+    if (rc) return rc;
+    // (the sweeps' results by their place in the launch -> by job)
+    std::vector<BatchJobResult> by_dev(b->res.begin(), b->res.begin() + n_dev);
+    b->res.assign(n_jobs, BatchJobResult{});
+    for (int c = 0; c < n_jobs; ++c)
+      if (dev_of[c] >= 0) b->res[c] = by_dev[dev_of[c]];
+    chains = false;  // (done)
+  } else {
+    dev_of.clear();
+    b->res.assign(n_jobs, BatchJobResult{});
+    b->kernels = 0;
+  }
   if (chains) {
     std::vector<BatchScanBlock> blocks(n_jobs);
     int rc = hc_batch_stage_scans(m, n_jobs, jobs, blocks.data());
@@ -2761,7 +3087,7 @@ int slamhip_matcher_process_scan_batch(slamhip_matcher *m, int n_jobs, const sla
   }
   // a job the chains did not take or did not settle: its scan selected or uploaded as the current one, process_scan
   return batch_hand_over(
-      m, n_jobs, jobs, sid, [](int c) { return c; }, out_deltas, out_probs, nullptr,
+      m, n_jobs, jobs, sid, [&](int c) { return dev_of.empty() ? c : std::max(dev_of[c], 0); }, out_deltas, out_probs, nullptr,
       [&](const slamhip_match_job &j, ScanKeeper &keep, double *delta, double *prob, int *kept) -> int {
         keep.upload_overwritten = keep.upload_overwritten || j.scan_slot < 0;
         const int rc = j.scan_slot >= 0 ? slamhip_scan_select(ctx, j.scan_slot)
@@ -2825,6 +3151,40 @@ int slamhip_matcher_mc_stream_info(slamhip_matcher *m, int stream, unsigned long
   if (pairs_consumed) *pairs_consumed = (unsigned long long)pe->tape_pos();
   if (matches) *matches = stream < 0 ? m->mc_matches : m->mc_streams[stream].matches;
   if (state5) pe->state5(state5);
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_set_bf_streams(slamhip_matcher *m, int n_streams) {
+  if (!m || n_streams < 0) return invalid_arg("bad enumerator streams");
+  if (!m->is_bf) return invalid_arg("enumerator streams belong to a brute-force matcher");
+  m->bf_streams.set(n_streams);  // (every base forgotten, the job mapping dropped)
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_set_bf_job_streams(slamhip_matcher *m, int n, const int *stream_of_job) {
+  if (!m || n < 0) return invalid_arg("bad stream mapping");
+  if (!m->is_bf) return invalid_arg("enumerator streams belong to a brute-force matcher");
+  if (const char *why = m->bf_streams.set_job_streams(n, stream_of_job)) return invalid_arg(why);
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_bf_stream_info(slamhip_matcher *m, int stream, int *base_set, double base[3], long long *matches) {
+  if (!m || !m->is_bf) return invalid_arg("enumerator streams belong to a brute-force matcher");
+  if (stream < -1 || stream >= (int)m->bf_streams.s.size()) return invalid_arg("no such enumerator stream");
+  BfStream own;  // (stream -1: the matcher's own enumerator, the one the lone calls use)
+  if (stream < 0) {
+    const auto *pe = static_cast<const BruteForcePoseEnumerator *>(m->pe.get());
+    own.base_set = pe->base_set();
+    own.base[0] = pe->base().x;
+    own.base[1] = pe->base().y;
+    own.base[2] = pe->base().theta;
+    own.matches = m->bf_matches;
+  }
+  const BfStream &k = stream < 0 ? own : m->bf_streams.s[(size_t)stream];
+  if (base_set) *base_set = k.base_set ? 1 : 0;
+  if (base)
+    for (int q = 0; q < 3; ++q) base[q] = k.base_set ? k.base[q] : 0.0;
+  if (matches) *matches = k.matches;
   return SLAMHIP_OK;
 }
 
@@ -2911,9 +3271,15 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       return invalid_arg("unknown map id in a match job");
   }
   const bool mc_streams = m->is_mc && !m->mc_streams.empty();
+  const bool bf_streams = m->is_bf && m->bf_streams.any();
+  const bool streams = mc_streams || bf_streams;
   std::vector<int> sid;
   if (mc_streams) {  // (refused before a stream or the last-batch state is touched)
     const int rc = mc_job_streams_of(m, n_jobs, &sid);
+    if (rc) return rc;
+  }
+  if (bf_streams) {
+    const int rc = bf_job_streams_of(m, n_jobs, &sid);
     if (rc) return rc;
   }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
@@ -2958,15 +3324,25 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       l.map_id = jobs[c].map_id;
       for (int q = 0; q < 3; ++q) l.init_pose[q] = jobs[c].init_pose[q];
     }
-    std::vector<int> live_sid(mc_streams ? raw.n_live : 0);
-    for (int c = 0; c < n_jobs && mc_streams; ++c)
+    std::vector<int> live_sid(streams ? raw.n_live : 0);
+    for (int c = 0; c < n_jobs && streams; ++c)
       if (raw.plan[c].live >= 0) live_sid[raw.plan[c].live] = sid[c];
-    const bool chains = raw.n_live > 1 && raw.n_live <= 65535 && raw.max_k <= 4096 &&
-                        (mc_streams ? mc_batch_eligible(m) : batch_chain_eligible(m));
+    // (a brute-force matcher without streams: job after job through the lone call.  With streams a raw batch goes
+    // through the shared sweeps whole or not at all: one job above 4096 kept beams sends every job to its lone call)
+    bool chains = raw.n_live > 1 && raw.n_live <= 65535 && raw.max_k <= 4096 && (!m->is_bf || bf_streams) &&
+                  (mc_streams ? mc_batch_eligible(m) : (bf_streams ? bf_batch_eligible(m) : batch_chain_eligible(m)));
     if (chains) {
       int cell_model = -1;
       rc = batch_maps_check(ctx, raw.n_live, live.data(), &cell_model);
       if (rc) return rc;
+      if (bf_streams) {
+        rc = bf_batch_fits(m, raw.n_live, &chains);
+        if (rc) return rc;
+      }
+    }
+    if (chains) {
+      int cell_model = -1;
+      (void)batch_maps_check(ctx, raw.n_live, live.data(), &cell_model);
       // ---- the arenas (the stream is idle: the batch before returned after its chains had ended): the pinned one, its
       // rows filled; then the one in HBM
       rc = grow_block(ctx->stream, b->h_raw, b->h_raw_cap, raw.arena_bytes, 1 << 16, 1, hipHostMallocMapped);
@@ -3034,8 +3410,10 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       b->res.assign(n_jobs, BatchJobResult{});
       b->kernels = 0;
       rc = mc_streams ? mc_batch_run(m, raw.n_live, live.data(), blocks.data(), live_sid.data(), cell_model)
-                      : hc_batch_run(m, raw.n_live, live.data(), blocks.data(), cell_model);
+                      : (bf_streams ? bf_batch_run(m, raw.n_live, live.data(), blocks.data(), live_sid.data())
+                                    : hc_batch_run(m, raw.n_live, live.data(), blocks.data(), cell_model));
       if (rc) return rc;
+      if (bf_streams) ++b->kernels;  // (k_scan_assemble_batch in front of the three)
       // (the chains' results by live place -> by job)
       std::vector<BatchJobResult> by_live(b->res.begin(), b->res.begin() + raw.n_live);
       b->res.assign(n_jobs, BatchJobResult{});
@@ -3170,6 +3548,7 @@ int slamhip_matcher_process_scan(slamhip_matcher *m, int map_id, const double in
   if (!m || !init_pose || !out_delta || !out_prob) return invalid_arg("null argument");
   const int rc = process_scan_body(m, map_id, init_pose, out_delta, out_prob);
   if (!rc && m->is_mc) ++m->mc_matches;  // (slamhip_matcher_mc_stream_info)
+  if (!rc && m->is_bf) ++m->bf_matches;  // (slamhip_matcher_bf_stream_info)
   return rc;
 }
 
@@ -3203,7 +3582,7 @@ static int process_scan_body(slamhip_matcher *m, int map_id, const double init_p
     const int crc = mc_chain_process_scan(m, map_id, init_pose, out_delta, out_prob);
     if (crc != kChainNeedsHost) return crc;
   }
-  if (!force_exact && bf_device_eligible(m)) {
+  if (!force_exact && !m->bf.skip_device && bf_device_eligible(m)) {
     const int crc = bf_device_process_scan(m, map_id, init_pose, out_delta, out_prob);
     if (crc != kChainNeedsHost) return crc;
   }

@@ -434,6 +434,8 @@ public:
     }
     return base_;
   }
+  bool base_set() const { return base_set_; }
+  const Pose &base() const { return base_; }
 
 private:
   double r_[9];

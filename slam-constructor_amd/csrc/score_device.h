@@ -243,4 +243,97 @@ __device__ __forceinline__ double beam_term(const MapView &m, int oie, double x,
   return pr * w * f;
 }
 
+// ---- K1's scoring body (k_score_point, score_kernels.hip; k_bf_score_batch, bf_batch.hip) -----------------------
+// 256 threads per workgroup, thread t owns beams t, t + 256, ...; at most 16 poses per workgroup.
+constexpr int kScoreBlock = 256;
+constexpr int kScoreMaxPosesPerBlock = 16;
+
+// the beam constants of thread t (KB > 0: n <= 256 KB, they live in VGPRs for every pose of the workgroup)
+template <int KB>
+__device__ __forceinline__ void score_point_load_beams(const ScanView &scan, int n, int t, double *br, double *bc, double *bs,
+                                                       double *bw, double *bf) {
+  if (KB > 0) {
+#pragma unroll
+    for (int k = 0; k < (KB > 0 ? KB : 1); ++k) {
+      const int b = t + kScoreBlock * k;
+      const bool ok = b < n;
+      br[k] = ok ? scan.range[b] : 0.0;
+      bc[k] = ok ? scan.cos_a[b] : 0.0;
+      bs[k] = ok ? scan.sin_a[b] : 0.0;
+      bw[k] = ok ? scan.weight[b] : 0.0;
+      bf[k] = ok ? scan.factor[b] : 0.0;
+    }
+  }
+}
+
+// The npb poses staged in s_pose (x, y, sin, cos), scored in the canonical order: thread t adds its beams' terms in
+// ascending order, a wave64 xor-butterfly, (g0 + g1) + (g2 + g3) across the four waves, total / tot_w (NaN where tot_w
+// is 0); FPRINT: the term vector's fingerprint beside it.  Pose p0 + j goes to scores[p0 + j].  The caller has put a
+// barrier behind its stores to s_pose.
+template <int MODEL, int KB, bool WRITE_TERMS, bool FPRINT>
+__device__ __forceinline__ void score_point_body(const MapView &map, const ScanView &scan, int oie, int n, int p0, int npb,
+                                                 const double (*s_pose)[4], double (*s_part)[4], unsigned long long (*s_hpart)[4],
+                                                 const double *br, const double *bc, const double *bs, const double *bw,
+                                                 const double *bf, double *terms, double *scores, unsigned long long *fprints) {
+  constexpr int kBlock = kScoreBlock;
+  constexpr int KR = KB > 0 ? KB : 1;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const double scale = map.scale, inv_scale = map.inv_scale;
+  // position-sensitive multilinear form of the terms' 32-bit halves, odd per-beam multipliers (hc_chain.hip's)
+  const unsigned fk_lo = (2u * (unsigned)t + 1u) * 0x9E3779B1u, fk_hi = (2u * (unsigned)t + 1u) * 0x85EBCA6Bu;
+  for (int j = 0; j < npb; ++j) {
+    const double x = s_pose[j][0], y = s_pose[j][1], sn = s_pose[j][2], cs = s_pose[j][3];
+    double acc = 0.0;
+    unsigned long long h = 0ull;
+    if (KB > 0) {
+#pragma unroll
+      for (int k = 0; k < KR; ++k) {
+        const int b = t + kBlock * k;
+        if (b < n) {
+          const double c = cs * bc[k] - sn * bs[k];
+          const double s = sn * bc[k] + cs * bs[k];
+          const double wx = x + br[k] * c;
+          const double wy = y + br[k] * s;
+          const double pr = point_probability<MODEL>(map, oie, to_cell(wx, scale, inv_scale), to_cell(wy, scale, inv_scale));
+          const double term = pr * bw[k] * bf[k];
+          if (WRITE_TERMS) terms[(size_t)(p0 + j) * n + b] = term;
+          acc = acc + term;
+          if (FPRINT) h += term_fingerprint(term, fk_lo + (unsigned)k * (2u * kBlock * 0x9E3779B1u),
+                                            fk_hi + (unsigned)k * (2u * kBlock * 0x85EBCA6Bu));
+        }
+      }
+    } else {
+      for (int b = t; b < n; b += kBlock) {
+        const double ca = scan.cos_a[b], sa = scan.sin_a[b], r = scan.range[b];
+        const double c = cs * ca - sn * sa;
+        const double s = sn * ca + cs * sa;
+        const double wx = x + r * c;
+        const double wy = y + r * s;
+        const double pr = point_probability<MODEL>(map, oie, to_cell(wx, scale, inv_scale), to_cell(wy, scale, inv_scale));
+        const double term = pr * scan.weight[b] * scan.factor[b];
+        if (WRITE_TERMS) terms[(size_t)(p0 + j) * n + b] = term;
+        acc = acc + term;
+        if (FPRINT) {
+          const unsigned kq = (unsigned)(b / kBlock);
+          h += term_fingerprint(term, fk_lo + kq * (2u * kBlock * 0x9E3779B1u), fk_hi + kq * (2u * kBlock * 0x85EBCA6Bu));
+        }
+      }
+    }
+    if (FPRINT) {
+      wave_xor_sum_with(acc, h);
+      if (lane == 0) s_hpart[j][wave] = h;
+    } else {
+      acc = wave_xor_sum(acc);
+    }
+    if (lane == 0) s_part[j][wave] = acc;
+  }
+  __syncthreads();
+  if (t < npb) {
+    const double total = (s_part[t][0] + s_part[t][1]) + (s_part[t][2] + s_part[t][3]);
+    scores[p0 + t] = (scan.tot_w == 0.0) ? __builtin_nan("") : total / scan.tot_w;
+    if (FPRINT) fprints[p0 + t] = s_hpart[t][0] + s_hpart[t][1] + s_hpart[t][2] + s_hpart[t][3];
+  }
+}
+
 }  // namespace slamhip

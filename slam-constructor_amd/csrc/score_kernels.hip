@@ -45,8 +45,8 @@
 
 namespace slamhip {
 
-static constexpr int kBlock = 256;
-static constexpr int kMaxPosesPerBlock = 16;
+static constexpr int kBlock = kScoreBlock;  // (score_device.h)
+static constexpr int kMaxPosesPerBlock = kScoreMaxPosesPerBlock;
 
 // Completion signal for the low-latency host path: scoring kernels write their results straight
 // into pinned, coherent host memory with plain stores; this 1-thread kernel, queued right behind
@@ -187,7 +187,6 @@ __global__ __launch_bounds__(kBlock) void k_score_point(ScoreArgs a) {
   __shared__ double s_part[kMaxPosesPerBlock][4];
   __shared__ unsigned long long s_hpart[FPRINT ? kMaxPosesPerBlock : 1][4];
   const int t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
   const int n = a.scan.n;
   const int p0 = blockIdx.x * a.poses_per_block;
   const int npb = min(a.poses_per_block, a.n_poses - p0);
@@ -208,18 +207,7 @@ __global__ __launch_bounds__(kBlock) void k_score_point(ScoreArgs a) {
 
   constexpr int KR = KB > 0 ? KB : 1;
   double br[KR], bc[KR], bs[KR], bw[KR], bf[KR];
-  if (KB > 0) {
-#pragma unroll
-    for (int k = 0; k < KR; ++k) {
-      const int b = t + kBlock * k;
-      const bool ok = b < n;
-      br[k] = ok ? a.scan.range[b] : 0.0;
-      bc[k] = ok ? a.scan.cos_a[b] : 0.0;
-      bs[k] = ok ? a.scan.sin_a[b] : 0.0;
-      bw[k] = ok ? a.scan.weight[b] : 0.0;
-      bf[k] = ok ? a.scan.factor[b] : 0.0;
-    }
-  }
+  score_point_load_beams<KB>(a.scan, n, t, br, bc, bs, bw, bf);
   if (t < npb) {
     if (!a.pose_sc) sincos(pose_th, &pose_sn, &pose_cs);
     s_pose[t][0] = pose_x;
@@ -228,62 +216,9 @@ __global__ __launch_bounds__(kBlock) void k_score_point(ScoreArgs a) {
     s_pose[t][3] = pose_cs;
   }
   __syncthreads();
-
-  const double scale = a.map.scale, inv_scale = a.map.inv_scale;
-  // position-sensitive multilinear form of the terms' 32-bit halves, odd per-beam multipliers (hc_chain.hip's)
-  const unsigned fk_lo = (2u * (unsigned)t + 1u) * 0x9E3779B1u, fk_hi = (2u * (unsigned)t + 1u) * 0x85EBCA6Bu;
-  for (int j = 0; j < npb; ++j) {
-    const double x = s_pose[j][0], y = s_pose[j][1], sn = s_pose[j][2], cs = s_pose[j][3];
-    double acc = 0.0;
-    unsigned long long h = 0ull;
-    if (KB > 0) {
-#pragma unroll
-      for (int k = 0; k < KR; ++k) {
-        const int b = t + kBlock * k;
-        if (b < n) {
-          const double c = cs * bc[k] - sn * bs[k];
-          const double s = sn * bc[k] + cs * bs[k];
-          const double wx = x + br[k] * c;
-          const double wy = y + br[k] * s;
-          const double pr = point_probability<MODEL>(a.map, a.oie, to_cell(wx, scale, inv_scale), to_cell(wy, scale, inv_scale));
-          const double term = pr * bw[k] * bf[k];
-          if (WRITE_TERMS) a.terms[(size_t)(p0 + j) * n + b] = term;
-          acc = acc + term;
-          if (FPRINT) h += term_fingerprint(term, fk_lo + (unsigned)k * (2u * kBlock * 0x9E3779B1u),
-                                            fk_hi + (unsigned)k * (2u * kBlock * 0x85EBCA6Bu));
-        }
-      }
-    } else {
-      for (int b = t; b < n; b += kBlock) {
-        const double ca = a.scan.cos_a[b], sa = a.scan.sin_a[b], r = a.scan.range[b];
-        const double c = cs * ca - sn * sa;
-        const double s = sn * ca + cs * sa;
-        const double wx = x + r * c;
-        const double wy = y + r * s;
-        const double pr = point_probability<MODEL>(a.map, a.oie, to_cell(wx, scale, inv_scale), to_cell(wy, scale, inv_scale));
-        const double term = pr * a.scan.weight[b] * a.scan.factor[b];
-        if (WRITE_TERMS) a.terms[(size_t)(p0 + j) * n + b] = term;
-        acc = acc + term;
-        if (FPRINT) {
-          const unsigned kq = (unsigned)(b / kBlock);
-          h += term_fingerprint(term, fk_lo + kq * (2u * kBlock * 0x9E3779B1u), fk_hi + kq * (2u * kBlock * 0x85EBCA6Bu));
-        }
-      }
-    }
-    if (FPRINT) {
-      wave_xor_sum_with(acc, h);
-      if (lane == 0) s_hpart[j][wave] = h;
-    } else {
-      acc = wave_xor_sum(acc);
-    }
-    if (lane == 0) s_part[j][wave] = acc;
-  }
-  __syncthreads();
-  if (t < npb) {
-    const double total = (s_part[t][0] + s_part[t][1]) + (s_part[t][2] + s_part[t][3]);
-    a.scores[p0 + t] = (a.scan.tot_w == 0.0) ? __builtin_nan("") : total / a.scan.tot_w;
-    if (FPRINT) a.fprints[p0 + t] = s_hpart[t][0] + s_hpart[t][1] + s_hpart[t][2] + s_hpart[t][3];
-  }
+  // (the scoring body: score_device.h -- shared with the batched brute-force sweep, bf_batch.hip)
+  score_point_body<MODEL, KB, WRITE_TERMS, FPRINT>(a.map, a.scan, a.oie, n, p0, npb, s_pose, s_part, s_hpart, br, bc, bs, bw, bf,
+                                                   a.terms, a.scores, a.fprints);
 }
 
 // ---- K1s: the reference's sequential beam-order sum (bit-exact), one lane per pose -------------
@@ -595,14 +530,7 @@ static ScoreKernel point_kernel(int kb) {
   }
 }
 
-static int pick_poses_per_block(int n_poses) {
-  // enough workgroups to fill 256 CUs several times over, while amortising the per-workgroup
-  // beam-constant loads (40 B/beam) over several poses once there are plenty of poses.
-  if (n_poses >= 8192) return 8;
-  if (n_poses >= 2048) return 4;
-  if (n_poses >= 1024) return 2;
-  return 1;
-}
+// (pick_poses_per_block: kernel_pick.h)
 
 hipError_t launch_score(const ScoreArgs &args, int cell_model, int oope, int sum_order,
                         hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {

@@ -299,6 +299,28 @@ int score_views(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, MapVie
   return SLAMHIP_OK;
 }
 
+// score_views' map half for a job of a batch, whose scan is not the context's current one: the view, the cell model and
+// the OIE a lone call with this configuration scores the map through (fill_args: a TBM / CREDIBILIST map through its
+// probability plane wherever the lone call does)
+int score_map_view(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, MapView *map, int *cell_model, int *oie_eff) {
+  DeviceMap *m = get_map(ctx, map_id);
+  if (!m) return invalid("unknown map id");
+  const int rc = check_cfg(*m, cfg);
+  if (rc) return rc;
+  *map = view_of(*m);
+  *cell_model = m->cell_model;
+  *oie_eff = cfg->oie;
+  if (wants_prob_plane(ctx, *m, cfg)) {
+    const int prc = map_prob_plane(ctx, *m);
+    if (prc) return prc;
+    map->payload = m->d_prob;
+    map->unknown[0] = belief_probability(m->cell_model, m->unknown[0], m->unknown[1], m->unknown[2], m->unknown[3]);
+    *oie_eff = SLAMHIP_OIE_OCCUPANCY;
+    *cell_model = SLAMHIP_CELL_OCC;
+  }
+  return SLAMHIP_OK;
+}
+
 // an event pair of the profiling pool (resolved in slamhip_profile_read); null, null when profiling is off
 int profile_event_pair(slamhip_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1, int kind) {
   *e0 = *e1 = nullptr;

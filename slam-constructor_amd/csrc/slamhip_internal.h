@@ -525,6 +525,8 @@ int lane_fork(slamhip_ctx *ctx);
 // view is then an OCC one and *oie_eff the occupancy OIE, see DeviceMap::d_prob; without it the view is the map's own)
 int score_views(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, MapView *map, ScanView *scan,
                 int *cell_model, const TiledTarget *tiled = nullptr, int *oie_eff = nullptr);
+// the map half of score_views (plane included) for a job whose scan is not the context's current one
+int score_map_view(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, MapView *map, int *cell_model, int *oie_eff);
 int profile_event_pair(slamhip_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1, int kind = 0);
 // An event pair recorded AROUND a pipeline (the map update): every exit between the first record and the second --
 // an empty update, a failed grow, a HIP error -- would leave a pair whose end was never recorded (or holds a stale

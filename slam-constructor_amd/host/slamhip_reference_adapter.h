@@ -426,6 +426,15 @@ public:
     slamhip_or_die(slamhip_matcher_set_mc_streams(_m, (int)seeds.size(), seeds.empty() ? nullptr : seeds.data()), "set_mc_streams");
     _n_mc_streams = (int)seeds.size();
   }
+  // K robots on ONE brute-force matcher object: robot k's enumerator is what its own BruteForceScanMatcher would own -- the
+  // shared ranges and a base pose of its own, latched at the robot's first match that scores anything
+  // (brute_force_scan_matcher.h:27-40).  hip_process_raw_scans then runs job k on stream k, all jobs in three shared
+  // launches behind the assembly launch (slamhip_matcher_set_bf_streams); process_scan of this object keeps using the
+  // matcher's own enumerator.  0 removes the streams.
+  void set_bf_streams(int n_streams) {
+    slamhip_or_die(slamhip_matcher_set_bf_streams(_m, n_streams), "set_bf_streams");
+    _n_bf_streams = n_streams;
+  }
   // optional: a log kept somewhere else than in the map handed to process_scan (a map that IS a
   // HipMirroredGridMap is recognised by itself; any other map is compared cell by cell)
   void set_dirty_source(const HipMirroredGridMap *src) { _dirty_source = src; }
@@ -591,7 +600,7 @@ private:
   double _max_range = -1;
   std::vector<double> _r, _a, _f;
   std::vector<int> _occ;
-  int _n_mc_streams = 0;
+  int _n_mc_streams = 0, _n_bf_streams = 0;
 };
 
 // K robots / replicas, one library call: what HipGridScanMatcher::process_raw_scan does for one scan, for K of them --
@@ -652,6 +661,9 @@ inline void hip_process_raw_scans(HipGridScanMatcher &matcher, std::vector<HipRa
     // job k <-> engine stream k, whatever was packed out in front of it (a scan without points leaves its stream alone)
     if (matcher._n_mc_streams > 0)
       slamhip_or_die(slamhip_matcher_set_mc_job_streams(matcher._m, (int)live.size(), live.data()), "set_mc_job_streams");
+    // ... <-> enumerator stream k (a scan without points leaves its stream's base unlatched)
+    if (matcher._n_bf_streams > 0)
+      slamhip_or_die(slamhip_matcher_set_bf_job_streams(matcher._m, (int)live.size(), live.data()), "set_bf_job_streams");
     int rc = slamhip_matcher_process_raw_scan_batch(matcher._m, (int)packed.size(), packed.data(), d.data(), prob.data(), nullptr);
     if (rc == SLAMHIP_ERR_INVALID || rc == SLAMHIP_ERR_UNSUPPORTED || rc == SLAMHIP_ERR_NO_DEVICE)
       slamhip_or_die(rc, "process_raw_scan_batch");
