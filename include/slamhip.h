@@ -273,6 +273,16 @@ int slamhip_scan_generate_host(int cell_model, int occ_kind, int variant, int wi
                                double scale, const double *unknown_payload, const double *payload, int n_poses,
                                const double *poses_xyt, int n_angles, const double *angles, double max_dist,
                                double occ_threshold, double *range_out, unsigned char *status_out);
+/* Host only, no GPU: the same beams over ONE tile table in host memory, as slamhip_gmapping_particle_generate_scans
+ * (gmapping section) reads a particle's map -- pool[n_tiles][16384][4] GMAPPING cells in 128 x 128-cell tiles (row-major
+ * inside a tile, prob_occ first), table[tiles_y * tiles_x] tile ids, (origin_x, origin_y) = the virtual coordinates of
+ * external cell (0, 0); a cell outside [0, tiles_x * 128) x [0, tiles_y * 128) reads unknown_occ.  INVALID besides
+ * slamhip_scan_generate_host's refusals: a null pool or table, an empty or oversized (> 32768 tiles a side) extent, a
+ * table entry outside [0, n_tiles). */
+int slamhip_scan_generate_host_tiled(int variant, int tiles_x, int tiles_y, int origin_x, int origin_y, double scale,
+                                     double unknown_occ, const double *pool, int n_tiles, const int *table, int n_poses,
+                                     const double *poses_xyt, int n_angles, const double *angles, double max_dist,
+                                     double occ_threshold, double *range_out, unsigned char *status_out);
 
 /* ---------------------------------------------------------------- map pyramid (csrc/map_pyramid.hip)
  * The two data-parallel parts of the many-to-many multi-resolution matcher (BF_M3RSM, Olson 2015):
@@ -1070,6 +1080,21 @@ int slamhip_gmapping_particle_map_download(slamhip_gmapping *g, int particle, in
  * format, an empty window. */
 int slamhip_gmapping_particle_map_render(slamhip_gmapping *g, int particle, int format, int x0, int y0, int w, int h,
                                          void *out);
+/* Laser scans ray-cast from the particles' OWN maps ("scan generation" above: semantics, status bytes, `variant` and
+ * `flags` are slamhip_map_generate_scans'): job k = n_angles beams from pose poses_xyt[3k..3k+2] over the map of LOCAL
+ * particle particles[k] (indices as slamhip_gmapping_particle_map_download takes them; a particle may be named by
+ * several jobs), all jobs in ONE launch over the tile pool -- what a particle should see from its map, without the
+ * 40-byte-per-cell download and dense re-upload.  range_out[n_jobs][n_angles] doubles, status_out one byte per beam in
+ * the same order.  The cells are GMAPPING cells: double(map[cell]) is prob_occ; a cell outside the pool's extent reads
+ * as the never-observed cell (-1), so does the shared unknown tile.  Queued on the context's stream behind every queued
+ * pool operation (clones, table patches, appends); writes nothing to the pool; one copy up, one back.  While
+ * slamhip_profile_enable is on, the kernel's time is added to kernel_ms_total.  SLAMHIP_ERR_INVALID, before anything is
+ * queued: a filter without particle maps, a particle out of range, unknown flags, and everything
+ * slamhip_map_generate_scans refuses for a dense map of the pool's scale.  n_jobs == 0 or n_angles == 0: OK, nothing
+ * happens. */
+int slamhip_gmapping_particle_generate_scans(slamhip_gmapping *g, int variant, int flags, int n_jobs, const int *particles,
+                                             const double *poses_xyt, int n_angles, const double *angles, double max_dist,
+                                             double occ_threshold, double *range_out, unsigned char *status_out);
 /* The append half of GmappingWorld::handle_observation (gmapping_world.h:93-97) for a set of local
  * particles at once: the raw scan is appended to the map of particle particles[k] from poses3[3k..3k+2] --
  * ONE batched K6 over all (particle, beam) pairs, copy-on-write first.  The filter step does this itself for

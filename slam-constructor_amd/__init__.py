@@ -74,7 +74,8 @@ slamhip_scan_table_uploads slamhip_scan_download
 slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download
 slamhip_matcher_set_mc_streams slamhip_matcher_set_mc_job_streams slamhip_matcher_mc_stream_info
 slamhip_matcher_set_bf_streams slamhip_matcher_set_bf_job_streams slamhip_matcher_bf_stream_info
-slamhip_map_append_scan_batch slamhip_map_update_batch_stats slamhip_map_update_batch_tables""".split()
+slamhip_map_append_scan_batch slamhip_map_update_batch_stats slamhip_map_update_batch_tables
+slamhip_gmapping_particle_generate_scans slamhip_scan_generate_host_tiled""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -293,6 +294,8 @@ def load(testing=False):
     L.slamhip_scan_gen_libm_variant.argtypes = [_ip]
     L.slamhip_map_generate_scans.argtypes = [vp, i, i, i, i, i, _dp, i, _dp, d, d, _dp, vp]
     L.slamhip_scan_generate_host.argtypes = [i, i, i, i, i, i, i, d, _dp, _dp, i, _dp, i, _dp, d, d, _dp, vp]
+    L.slamhip_scan_generate_host_tiled.argtypes = [i, i, i, i, i, d, d, _dp, i, _ip, i, _dp, i, _dp, d, d, _dp, vp]
+    L.slamhip_gmapping_particle_generate_scans.argtypes = [vp, i, i, i, _ip, _dp, i, _dp, d, d, _dp, vp]
     L.slamhip_pyramid_create.argtypes = [vp, i, i, i, C.POINTER(vp)]
     L.slamhip_pyramid_destroy.argtypes = [vp]
     L.slamhip_pyramid_info.argtypes = [vp, _ip, i, _ip, _ip, _ip, _ip, _ip, _dp]
@@ -519,6 +522,29 @@ def generate_scans_host(m, poses, angles, max_dist, occ_threshold=1.0, occ_kind=
                                              int(m.origin[1]), float(m.scale), _d(unk), _d(payload), poses.shape[0],
                                              _d(poses), angles.size, _d(angles), float(max_dist), float(occ_threshold),
                                              _d(rng), status.ctypes.data))
+    return rng, status
+
+
+def generate_scans_host_tiled(pool, table, origin, scale, poses, angles, max_dist, occ_threshold=1.0, unknown_occ=-1.0,
+                              variant=None):
+    """slamhip_scan_generate_host_tiled, no GPU: the same routine over ONE tile table on the host, as
+    GmappingFilter.generate_particle_scans reads a particle's map.  pool[n_tiles, 16384, 4] GMAPPING cells in
+    128 x 128-cell tiles, table[tiles_y, tiles_x] tile ids, origin = the virtual cell of external cell (0, 0); cells
+    outside the extent read unknown_occ.  None for pool or table reaches the library as a null pointer.
+    Returns (range[K, B], status[K, B])."""
+    poses, angles, rng, status = _scan_gen_args(poses, angles)
+    variant = scan_gen_libm_variant() if variant is None else variant
+    n_tiles, tiles_y, tiles_x, p_pool, p_table = 0, 1, 1, None, None
+    if pool is not None:
+        pool = _f64(pool).reshape(-1, 128 * 128, 4)
+        n_tiles, p_pool = pool.shape[0], _d(pool)
+    if table is not None:
+        table = np.ascontiguousarray(table, dtype=np.int32)
+        (tiles_y, tiles_x), p_table = table.shape, table.ctypes.data_as(_ip)
+    _check(load().slamhip_scan_generate_host_tiled(int(variant), tiles_x, tiles_y, int(origin[0]), int(origin[1]),
+                                                   float(scale), float(unknown_occ), p_pool, n_tiles, p_table,
+                                                   poses.shape[0], _d(poses), angles.size, _d(angles), float(max_dist),
+                                                   float(occ_threshold), _d(rng), status.ctypes.data))
     return rng, status
 
 
@@ -1799,6 +1825,27 @@ class GmappingFilter:
         out = np.zeros((max(h, 0), max(w, 0)), dtype=_render_dtype(fmt))
         _check(self.L.slamhip_gmapping_particle_map_render(self.h, particle, int(fmt), x0, y0, w, h, out.ctypes.data))
         return out
+
+    def generate_particle_scans(self, particles, angles, max_dist, poses=None, occ_threshold=1.0, variant=None,
+                                sequential=False):
+        """Laser scans ray-cast from the listed local particles' OWN maps in one launch over the tile pool
+        (slamhip_gmapping_particle_generate_scans): job k = the beams `angles` from poses[k] over the map of
+        particles[k]; a particle may be named several times.  poses=None: the filter's current poses of the named
+        particles (state()).  Returns (range[K, B], status[K, B]) as Context.generate_scans does; compact_scans takes
+        them as they are.  variant None = this host's sincos (scan_gen_libm_variant())."""
+        pt = np.ascontiguousarray(particles, dtype=np.int32).ravel()
+        if poses is None:
+            # (an index the library is about to refuse still needs a pose to travel with)
+            poses = np.take(self.state()[0], pt, axis=0, mode="clip") if pt.size else np.zeros((0, 3))
+        poses, angles, rng, status = _scan_gen_args(poses, angles)
+        if poses.shape[0] != pt.size:
+            raise ValueError("generate_particle_scans: one pose per named particle")
+        variant = scan_gen_libm_variant() if variant is None else variant
+        _check(self.L.slamhip_gmapping_particle_generate_scans(self.h, int(variant), SCAN_GEN_SEQUENTIAL if sequential else 0,
+                                                               pt.size, pt.ctypes.data_as(_ip), _d(poses), angles.size,
+                                                               _d(angles), float(max_dist), float(occ_threshold), _d(rng),
+                                                               status.ctypes.data))
+        return rng, status
 
     def export_particle_map(self, particle):
         """The LOCAL particle's map as one uint8 array (tile positions + tiles) for another rank."""

@@ -922,6 +922,17 @@ int slamhip_gmapping_particle_map_render(slamhip_gmapping *g, int particle, int 
   return tile_pool_render(g->tp, particle, format, x0, y0, w, h, out);
 }
 
+int slamhip_gmapping_particle_generate_scans(slamhip_gmapping *g, int variant, int flags, int n_jobs, const int *particles,
+                                             const double *poses_xyt, int n_angles, const double *angles, double max_dist,
+                                             double occ_threshold, double *range_out, unsigned char *status_out) {
+  if (!g || !g->tp) return bad("per-particle maps are not enabled");
+  if (n_jobs > 0 && !particles) return bad("null particles");
+  for (int k = 0; k < n_jobs; ++k)
+    if (particles[k] < 0 || particles[k] >= g->count) return bad("particle index out of range");
+  return tile_pool_generate_scans(g->tp, variant, flags, n_jobs, particles, poses_xyt, n_angles, angles, max_dist,
+                                  occ_threshold, range_out, status_out);
+}
+
 int slamhip_gmapping_particle_maps_append(slamhip_gmapping *g, int n_jobs, const int *particles,
                                           const double *poses3, int n_raw, const double *range,
                                           const double *angle, const int *is_occ, long long *n_updates) {

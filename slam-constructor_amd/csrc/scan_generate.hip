@@ -17,12 +17,17 @@
 // sequential routine, hit included: nothing of an unproven walk is kept.
 // Sequential form (k_scan_generate_seq): one thread per beam runs sg_beam_sequential; SLAMHIP_SCAN_GEN_SEQUENTIAL
 // forces it for every beam.
+// Per-particle maps (k_scan_generate_tiled_wave / _seq, slamhip_gmapping_particle_generate_scans): the same two kernels
+// over the slots of a tile pool -- the per-beam routines take the map as a template parameter and read it through
+// sg_cell_occ alone, which for an SgTiledMap is the renderer's read (table entry, then the cell's prob_occ); job = (slot,
+// pose), all jobs in one launch.
 // No LDS, no atomics; results leave as one block (ranges, then status bytes) in one copy.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include "scan_generate_device.h"
+#include "tile_pool.h"
 
 namespace slamhip {
 namespace {
@@ -37,7 +42,8 @@ __device__ __forceinline__ double sg_readlane(double v, int lane) {
 }
 
 // false: nothing is decided, the caller runs the sequential routine
-__device__ bool sg_beam_wave(const SgMap &m, const SgBeam &b, double thr, int lane, int *status_out, double *range_out) {
+template <class Map>
+__device__ bool sg_beam_wave(const Map &m, const SgBeam &b, double thr, int lane, int *status_out, double *range_out) {
   const SgWalkLine L = sg_walk_line(b);
   const int steps_x = abs(b.ex - b.bx), steps_y = abs(b.ey - b.by);
   const unsigned cap = (unsigned)steps_x + (unsigned)steps_y + 1u;
@@ -128,6 +134,52 @@ __global__ __launch_bounds__(kSgThreads) void k_scan_generate_seq(SgMap m, const
   status_out[g] = (unsigned char)status;
 }
 
+// The same two kernels over the slots of a tile pool (tile_pool.h): job p = beam g / n_angles reads pose p through the
+// table of slot slots[p].  m.table is the pool's table block here, table_stride ints per slot.
+template <bool FMA>
+__global__ __launch_bounds__(kSgThreads) void k_scan_generate_tiled_wave(SgTiledMap m, int table_stride,
+                                                                         const int *__restrict__ slots,
+                                                                         const double *__restrict__ poses, int n_angles,
+                                                                         const double *__restrict__ angles, int n_beams,
+                                                                         double max_dist, double thr,
+                                                                         double *__restrict__ range_out,
+                                                                         unsigned char *__restrict__ status_out) {
+  const int g = blockIdx.x * (kSgThreads / 64) + (threadIdx.x >> 6);
+  if (g >= n_beams) return;  // (the same for the whole wave)
+  const int lane = threadIdx.x & 63;
+  const int p = g / n_angles, ai = g - p * n_angles;
+  m.table += (size_t)slots[p] * table_stride;
+  const SgBeam b = sg_beam_setup<FMA>(poses[3 * p], poses[3 * p + 1], poses[3 * p + 2], angles[ai], max_dist, m.scale);
+  int status = SG_NONE;
+  double range = 0.0;
+  if (!sg_beam_wave(m, b, thr, lane, &status, &range)) {
+    if (lane == 0) status = sg_beam_sequential(m, b, thr, &range);
+  }
+  if (lane == 0) {
+    range_out[g] = range;
+    status_out[g] = (unsigned char)status;
+  }
+}
+
+template <bool FMA>
+__global__ __launch_bounds__(kSgThreads) void k_scan_generate_tiled_seq(SgTiledMap m, int table_stride,
+                                                                        const int *__restrict__ slots,
+                                                                        const double *__restrict__ poses, int n_angles,
+                                                                        const double *__restrict__ angles, int n_beams,
+                                                                        double max_dist, double thr,
+                                                                        double *__restrict__ range_out,
+                                                                        unsigned char *__restrict__ status_out) {
+  const int g = blockIdx.x * kSgThreads + threadIdx.x;
+  if (g >= n_beams) return;
+  const int p = g / n_angles, ai = g - p * n_angles;
+  m.table += (size_t)slots[p] * table_stride;
+  const SgBeam b = sg_beam_setup<FMA>(poses[3 * p], poses[3 * p + 1], poses[3 * p + 2], angles[ai], max_dist, m.scale);
+  double range = 0.0;
+  const int status = sg_beam_sequential(m, b, thr, &range);
+  range_out[g] = range;
+  status_out[g] = (unsigned char)status;
+}
+
 int sg_invalid(const char *msg) {
   set_error(msg);
   return SLAMHIP_ERR_INVALID;
@@ -169,6 +221,85 @@ void scan_gen_release(slamhip_ctx *ctx) {
   if (ctx->d_scan_gen) hipFree(ctx->d_scan_gen);
   ctx->d_scan_gen = nullptr;
   ctx->scan_gen_cap = 0;
+}
+
+// n_jobs x n_angles beams, job k over slot slots[k] from pose k: slamhip_gmapping_particle_generate_scans behind its
+// particle checks.  Nothing is queued before every argument has passed.
+int tile_pool_generate_scans(TilePool *tp, int variant, int flags, int n_jobs, const int *slots, const double *poses_xyt,
+                             int n_angles, const double *angles, double max_dist, double occ_threshold, double *range_out,
+                             unsigned char *status_out) {
+  if (flags & ~SLAMHIP_SCAN_GEN_SEQUENTIAL) return sg_invalid("unknown flags");
+  const char *why = sg_check_call(SLAMHIP_CELL_GMAPPING, 0, variant, n_jobs, poses_xyt, n_angles, angles, range_out, status_out);
+  if (!why && n_jobs > 0 && !slots) why = "null particles";
+  if (!why) why = sg_check_beams(tp->scale, n_jobs, poses_xyt, n_angles, angles, max_dist);
+  if (why) return sg_invalid(why);
+  for (int k = 0; k < n_jobs; ++k)
+    if (slots[k] < 0 || slots[k] >= tp->n_slots) return sg_invalid("bad slot");
+  const int n_beams = n_jobs * n_angles;
+  if (n_beams == 0) return SLAMHIP_OK;
+  slamhip_ctx *ctx = tp->ctx;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  // one block: poses | angles | slots | ranges | status bytes; in and out are one copy each
+  const size_t in_doubles = 3 * (size_t)n_jobs + (size_t)n_angles + ((size_t)n_jobs + 1) / 2;
+  const size_t in_bytes = in_doubles * sizeof(double);
+  const size_t out_bytes = (size_t)n_beams * sizeof(double) + round8((size_t)n_beams);
+  int rc = sg_reserve(ctx, in_bytes + out_bytes);
+  if (rc) return rc;
+  // behind the queued copy-on-write clones and table patches; the tables are the current generation's from here on
+  rc = tile_pool_flush(tp);
+  if (rc) return rc;
+  std::vector<double> &stage = ctx->scan_gen_stage;
+  stage.resize(std::max(in_doubles, out_bytes / sizeof(double)));
+  std::memcpy(stage.data(), poses_xyt, sizeof(double) * 3 * (size_t)n_jobs);
+  std::memcpy(stage.data() + 3 * (size_t)n_jobs, angles, sizeof(double) * (size_t)n_angles);
+  stage[in_doubles - 1] = 0.0;  // (the pad behind an odd number of slots)
+  std::memcpy(stage.data() + 3 * (size_t)n_jobs + (size_t)n_angles, slots, sizeof(int) * (size_t)n_jobs);
+  double *d_in = static_cast<double *>(ctx->d_scan_gen);
+  double *d_range = d_in + in_doubles;
+  unsigned char *d_status = reinterpret_cast<unsigned char *>(d_range + n_beams);
+  SLAMHIP_CHECK(hipMemcpyAsync(d_in, stage.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  SgTiledMap m;
+  m.pool = tp->d_pool;
+  m.table = tp->d_table();
+  m.tiles_x = tp->tiles_x;
+  m.tiles_y = tp->tiles_y;
+  m.origin_x = tp->origin_x;
+  m.origin_y = tp->origin_y;
+  m.scale = tp->scale;
+  m.unknown_occ = tp->unknown[0];
+  const int stride = tp->table_stride();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  rc = profile_event_pair(ctx, &e0, &e1);
+  if (rc) return rc;
+  if (e0) SLAMHIP_CHECK(hipEventRecord(e0, ctx->stream));
+  const double *d_poses = d_in, *d_angles = d_in + 3 * (size_t)n_jobs;
+  const int *d_slots = reinterpret_cast<const int *>(d_angles + n_angles);
+  const bool fma = variant == 1;
+  if (flags & SLAMHIP_SCAN_GEN_SEQUENTIAL) {
+    const dim3 grid((n_beams + kSgThreads - 1) / kSgThreads);
+    if (fma)
+      hipLaunchKernelGGL(k_scan_generate_tiled_seq<true>, grid, dim3(kSgThreads), 0, ctx->stream, m, stride, d_slots, d_poses,
+                         n_angles, d_angles, n_beams, max_dist, occ_threshold, d_range, d_status);
+    else
+      hipLaunchKernelGGL(k_scan_generate_tiled_seq<false>, grid, dim3(kSgThreads), 0, ctx->stream, m, stride, d_slots, d_poses,
+                         n_angles, d_angles, n_beams, max_dist, occ_threshold, d_range, d_status);
+  } else {
+    constexpr int per_block = kSgThreads / 64;
+    const dim3 grid((n_beams + per_block - 1) / per_block);
+    if (fma)
+      hipLaunchKernelGGL(k_scan_generate_tiled_wave<true>, grid, dim3(kSgThreads), 0, ctx->stream, m, stride, d_slots, d_poses,
+                         n_angles, d_angles, n_beams, max_dist, occ_threshold, d_range, d_status);
+    else
+      hipLaunchKernelGGL(k_scan_generate_tiled_wave<false>, grid, dim3(kSgThreads), 0, ctx->stream, m, stride, d_slots, d_poses,
+                         n_angles, d_angles, n_beams, max_dist, occ_threshold, d_range, d_status);
+  }
+  SLAMHIP_CHECK(hipGetLastError());
+  if (e1) SLAMHIP_CHECK(hipEventRecord(e1, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(stage.data(), d_range, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  std::memcpy(range_out, stage.data(), sizeof(double) * (size_t)n_beams);
+  std::memcpy(status_out, stage.data() + n_beams, (size_t)n_beams);
+  return SLAMHIP_OK;
 }
 
 }  // namespace slamhip
@@ -309,6 +440,24 @@ int slamhip_scan_generate_host(int cell_model, int occ_kind, int variant, int wi
   m.scale = scale;
   m.unknown_occ = cell_occupancy(cell_model, occ_kind, unknown_payload[0], sh > 1 ? unknown_payload[1] : 0.0,
                                  sh > 2 ? unknown_payload[2] : 0.0);
+  if (variant == 1) sg_generate_host<true>(m, n_poses, poses_xyt, n_angles, angles, max_dist, occ_threshold, range_out, status_out);
+  else sg_generate_host<false>(m, n_poses, poses_xyt, n_angles, angles, max_dist, occ_threshold, range_out, status_out);
+  return SLAMHIP_OK;
+}
+
+int slamhip_scan_generate_host_tiled(int variant, int tiles_x, int tiles_y, int origin_x, int origin_y, double scale,
+                                     double unknown_occ, const double *pool, int n_tiles, const int *table, int n_poses,
+                                     const double *poses_xyt, int n_angles, const double *angles, double max_dist,
+                                     double occ_threshold, double *range_out, unsigned char *status_out) {
+  // (the extent's cell coordinates fit an int: the limit of the device pool is far below)
+  if (tiles_x <= 0 || tiles_y <= 0 || tiles_x > 32768 || tiles_y > 32768) return sg_invalid("bad extent");
+  if (!pool || n_tiles <= 0 || !table) return sg_invalid("null pool or table");
+  for (int i = 0; i < tiles_x * tiles_y; ++i)
+    if (table[i] < 0 || table[i] >= n_tiles) return sg_invalid("a table entry names no tile of the pool");
+  const char *why = sg_check_call(SLAMHIP_CELL_GMAPPING, 0, variant, n_poses, poses_xyt, n_angles, angles, range_out, status_out);
+  if (!why) why = sg_check_beams(scale, n_poses, poses_xyt, n_angles, angles, max_dist);
+  if (why) return sg_invalid(why);
+  const SgTiledMap m{pool, table, tiles_x, tiles_y, origin_x, origin_y, scale, unknown_occ};
   if (variant == 1) sg_generate_host<true>(m, n_poses, poses_xyt, n_angles, angles, max_dist, occ_threshold, range_out, status_out);
   else sg_generate_host<false>(m, n_poses, poses_xyt, n_angles, angles, max_dist, occ_threshold, range_out, status_out);
   return SLAMHIP_OK;

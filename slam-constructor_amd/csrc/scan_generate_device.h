@@ -64,6 +64,28 @@ SLAMHIP_SG_FN double sg_cell_occ(const SgMap &m, int cx, int cy) {
   return c[0];
 }
 
+// One slot of a tile pool (tile_pool.h): GMAPPING cells of 4 doubles in 128 x 128-cell tiles, `table` the slot's
+// tiles_y x tiles_x tile ids (0 = the shared unknown tile, whose cells hold the unknown payload).  double(map[cell]) is
+// prob_occ, the cell's first double.
+struct SgTiledMap {
+  const double *pool;
+  const int *table;
+  int tiles_x, tiles_y;
+  int origin_x, origin_y;  // virtual cell = external cell + origin
+  double scale;
+  double unknown_occ;  // what a cell outside the extent reads as
+};
+
+// the renderer's read (render_tiled_cell, map_render.hip); the bounds test in 64 bits: no cell coordinate the callers'
+// limits admit reaches the table from outside the extent
+SLAMHIP_SG_FN double sg_cell_occ(const SgTiledMap &m, int cx, int cy) {
+  const long long vx = (long long)cx + m.origin_x, vy = (long long)cy + m.origin_y;
+  if (vx < 0 || vx >= (long long)m.tiles_x * kTileSide || vy < 0 || vy >= (long long)m.tiles_y * kTileSide) return m.unknown_occ;
+  const int ix = (int)vx, iy = (int)vy;
+  const int tile = m.table[(iy >> kTileShift) * m.tiles_x + (ix >> kTileShift)];
+  return m.pool[((size_t)tile * kTileCells + ((size_t)(iy & kTileMask) << kTileShift) + (ix & kTileMask)) * 4];
+}
+
 template <bool FMA>
 SLAMHIP_SG_FN SgBeam sg_beam_setup(double x, double y, double theta, double a, double max_dist, double scale) {
   SgBeam b;
@@ -105,15 +127,17 @@ SLAMHIP_SG_FN int sg_test_cell(const SgBeam &b, int cx, int cy, double *range) {
   return SG_HIT;
 }
 
-// one cell of the list: SG_NONE = the scan of the list goes on
-SLAMHIP_SG_FN int sg_visit(const SgMap &m, const SgBeam &b, double thr, int cx, int cy, double *range) {
+// one cell of the list: SG_NONE = the scan of the list goes on.  Map: SgMap or SgTiledMap (sg_cell_occ is the one read)
+template <class Map>
+SLAMHIP_SG_FN int sg_visit(const Map &m, const SgBeam &b, double thr, int cx, int cy, double *range) {
   if (sg_cell_occ(m, cx, cy) < thr) return SG_NONE;
   const int r = sg_test_cell(b, cx, cy, range);
   return r == SG_TOUCH ? SG_NONE : r;
 }
 
 // The beam as the reference runs it, one cell after the other.  Returns the status, *range set on SG_HIT.
-SLAMHIP_SG_FN int sg_beam_sequential(const SgMap &m, const SgBeam &b, double thr, double *range) {
+template <class Map>
+SLAMHIP_SG_FN int sg_beam_sequential(const Map &m, const SgBeam &b, double thr, double *range) {
   const double scale = b.scale;
   const int inc_x = 0 < b.d_x ? 1 : -1, inc_y = 0 < b.d_y ? 1 : -1;
   int px = b.bx, py = b.by;
@@ -270,8 +294,8 @@ SLAMHIP_SG_FN bool sg_pose_ok(double x, double y, double scale) {
 }
 
 // The whole call on the host: n_poses x n_angles beams over a host payload.
-template <bool FMA>
-static inline void sg_generate_host(const SgMap &m, int n_poses, const double *poses_xyt, int n_angles, const double *angles,
+template <bool FMA, class Map>
+static inline void sg_generate_host(const Map &m, int n_poses, const double *poses_xyt, int n_angles, const double *angles,
                                     double max_dist, double thr, double *range_out, unsigned char *status_out) {
   for (int p = 0; p < n_poses; ++p)
     for (int i = 0; i < n_angles; ++i) {

@@ -107,6 +107,12 @@ int tile_pool_download(TilePool *tp, int slot, int x0, int y0, int w, int h, dou
 // the same external window as w * h bytes (map_render.hip; format: SLAMHIP_RENDER_*): reads prob_occ only, cells outside
 // the extent read as the unknown cell
 int tile_pool_render(TilePool *tp, int slot, int format, int x0, int y0, int w, int h, void *out);
+// laser scans ray-cast from the slots' maps (scan_generate.hip; slamhip_map_generate_scans' semantics over GMAPPING cells):
+// job k = n_angles beams from pose k over slot slots[k], one launch behind the queued pool operations; reads prob_occ
+// only, cells outside the extent read as the unknown cell; writes nothing to the pool
+int tile_pool_generate_scans(TilePool *tp, int variant, int flags, int n_jobs, const int *slots, const double *poses_xyt,
+                             int n_angles, const double *angles, double max_dist, double occ_threshold, double *range_out,
+                             unsigned char *status_out);
 // derives the masks of every tile in use for threshold th, unless they are there (waited for).  Leaves nbr_ok false
 // where the masks cannot be kept by the writers: th <= 0 or an unknown cell that counts as full.
 int tile_pool_nbr_masks(TilePool *tp, double th);

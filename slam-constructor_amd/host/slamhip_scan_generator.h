@@ -10,6 +10,8 @@
 // (an occupied cell the ray meets in neither one nor two points, a scan point outside its cell) this generator throws
 // std::logic_error; a robot on a cell boundary (the reference's opening assertion) is refused by the library, and
 // slamhip_or_die ends the process as the assertion would.
+// A second pair of calls takes a GMapping filter with per-particle maps and particle indices instead of a map: the
+// scans come from the particles' own tiled maps (slamhip_gmapping_particle_generate_scans).
 #ifndef SLAMHIP_SCAN_GENERATOR_H
 #define SLAMHIP_SCAN_GENERATOR_H
 
@@ -45,14 +47,48 @@ public:
   std::vector<LaserScan2D> laser_scans_2D(const HipResidentMapView &map, const std::vector<RobotPose> &poses,
                                           double occ_threshold = 1) const {
     const int k = (int)poses.size(), b = (int)_angles.size();
-    std::vector<double> xyt(3 * (size_t)k), range((size_t)k * b);
+    const std::vector<double> xyt = pack(poses);
+    std::vector<double> range((size_t)k * b);
     std::vector<unsigned char> status((size_t)k * b);
-    for (int p = 0; p < k; ++p) {
+    map.generate_scans(_variant, k, xyt.data(), b, _angles.data(), _max_dist, occ_threshold, range.data(), status.data());
+    return scans_of(k, range, status);
+  }
+
+  // The same from the particles' OWN maps of a GMapping filter with per-particle maps
+  // (slamhip_gmapping_enable_particle_maps): scan j is what LOCAL particle particles[j] sees from poses[j] over its
+  // tiled map, all of them in one launch over the tile pool (slamhip_gmapping_particle_generate_scans).  A particle may
+  // be named several times.
+  std::vector<LaserScan2D> laser_scans_2D(slamhip_gmapping *filter, const std::vector<int> &particles,
+                                          const std::vector<RobotPose> &poses, double occ_threshold = 1) const {
+    if (particles.size() != poses.size()) throw std::logic_error("HipLaserScanGenerator: one pose per named particle");
+    const int k = (int)poses.size(), b = (int)_angles.size();
+    const std::vector<double> xyt = pack(poses);
+    std::vector<double> range((size_t)k * b);
+    std::vector<unsigned char> status((size_t)k * b);
+    slamhip_or_die(slamhip_gmapping_particle_generate_scans(filter, _variant, 0, k, particles.data(), xyt.data(), b, _angles.data(),
+                                                            _max_dist, occ_threshold, range.data(), status.data()),
+                   "gmapping_particle_generate_scans");
+    return scans_of(k, range, status);
+  }
+
+  LaserScan2D laser_scan_2D(slamhip_gmapping *filter, int particle, const RobotPose &pose, double occ_threshold = 1) const {
+    return laser_scans_2D(filter, std::vector<int>{particle}, std::vector<RobotPose>{pose}, occ_threshold)[0];
+  }
+
+private:
+  static std::vector<double> pack(const std::vector<RobotPose> &poses) {
+    std::vector<double> xyt(3 * poses.size());
+    for (size_t p = 0; p < poses.size(); ++p) {
       xyt[3 * p] = poses[p].x;
       xyt[3 * p + 1] = poses[p].y;
       xyt[3 * p + 2] = poses[p].theta;
     }
-    map.generate_scans(_variant, k, xyt.data(), b, _angles.data(), _max_dist, occ_threshold, range.data(), status.data());
+    return xyt;
+  }
+
+  // the beams that hit, in beam order; status 2 throws
+  std::vector<LaserScan2D> scans_of(int k, const std::vector<double> &range, const std::vector<unsigned char> &status) const {
+    const int b = (int)_angles.size();
     std::vector<LaserScan2D> scans((size_t)k);
     for (int p = 0; p < k; ++p) {
       scans[p].trig_provider = std::make_shared<RawTrigonometryProvider>();
