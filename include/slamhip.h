@@ -334,6 +334,28 @@ int slamhip_pyramid_info(slamhip_pyramid *pyr, int *n_levels, int cap, int *map_
                          int *origin_x, int *origin_y, double *scale);
 int slamhip_pyramid_rebuild(slamhip_pyramid *pyr);
 int slamhip_pyramid_refresh(slamhip_pyramid *pyr, int x0, int y0, int w, int h);
+/* REFRESH OF SEVERAL PYRAMIDS in shared launches (after slamhip_map_append_scan_batch has written K maps).  After the
+ * call every level of every pyramid holds, BIT FOR BIT -- payload and winner coordinates -- what slamhip_pyramid_refresh
+ * leaves when the same jobs run one after another in job order (tests/test_gpu_pyramid_refresh_batch.py); like the lone
+ * call it is queued on the context's stream and does not wait.
+ *   A ROUND holds jobs on distinct pyramids (a job naming a pyramid the open round already holds starts the next one).
+ *   Per round: one launch per level for the jobs whose window at that level has more than 256 cells (k_pyr_reduce_batch:
+ *   a flat grid, the jobs side by side), then ONE launch in which a workgroup per job walks that job's remaining levels up
+ *   to the 1 x 1 one (k_pyr_reduce_tail) -- for windows of some hundred cells on 2000 x 2000 maps four or five launches
+ *   where K lone calls queue K x 11.  Cell models and OIEs may differ between the jobs.
+ *   A pyramid one of whose levels carries a probability plane (a TBM / CREDIBILIST level somebody has scored with the
+ *   1-cell OOPE) goes through the lone call at its place in the order (jobs_lone).
+ * n_jobs == 0: SLAMHIP_OK, nothing happens.  Refusals, all before anything is queued: SLAMHIP_ERR_INVALID for a null
+ * pyramid, one of another context, a window outside its fine map; SLAMHIP_ERR_STATE for a stale pyramid.
+ * _stats: the last call that was not refused -- rounds, the jobs that went through the shared launches and through the
+ * lone call, and the launches of the rounds (the lone calls' are not counted); any pointer may be NULL. */
+typedef struct {
+  slamhip_pyramid *pyramid;
+  int x0, y0, w, h; /* INTERNAL fine window, as slamhip_pyramid_refresh */
+} slamhip_pyramid_refresh_job;
+int slamhip_pyramid_refresh_batch(slamhip_ctx *ctx, int n_jobs, const slamhip_pyramid_refresh_job *jobs);
+int slamhip_pyramid_refresh_batch_stats(slamhip_ctx *ctx, int *rounds, int *jobs_in_shared_launches, int *jobs_lone,
+                                        int *launches);
 /* Host only, no GPU: the same levels over a map on the host (payload[height][width] cells of 1 (OCC) or 4 doubles,
  * (origin_x, origin_y) = the internal coordinates of external cell (0, 0)) by the definition the kernels share
  * (csrc/map_pyramid_device.h).  *n_levels = K; the geometry arrays (room for level_cap entries, any may be NULL) as in
@@ -891,6 +913,40 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
  * five rows of cap doubles (cap 0: only *n).  A job that went through the lone call has no block in the batch's arena:
  * *n is set, asking for the rows is an error. */
 int slamhip_matcher_batch_scan_download(slamhip_matcher *m, int job, int cap, double *out5, int *n);
+/* K RAW scans in, K MULTI-RESOLUTION matches: the raw-scan form of slamhip_matcher_m3rsm_match_each (a BF_M3RSM matcher
+ * only; the two batch calls above keep refusing one).  Per request the host runs the lone call's filter against the
+ * window of the request's pyramid's FINE map and the initial pose; what is new with each scan goes into ONE pinned arena
+ * of the matcher's own, ONE launch (k_scan_assemble_each) assembles every live request's block in HBM -- the five rows
+ * and, as a sixth, the kept points' angles (SLAMHIP_POSE_TRIG_RAW_EXACT reads them) -- from per-scanner tables kept
+ * resident between calls (slamhip_scan_table_uploads counts their uploads: a second call with the same scanners sends
+ * none), and the lock-step searches of slamhip_matcher_m3rsm_match_each run over those blocks.
+ *  - Request k gets what a lone slamhip_matcher_process_raw_scan gives it on a matcher with this cfg, these limits, these
+ *    steps and this speculation over req[k].pyramid, with map_id = that pyramid's fine map, the same slamhip_raw_scan and
+ *    the same pose: delta, probability, kept count (kept_n[k]; kept_n may be NULL), committed calls
+ *    (slamhip_matcher_m3rsm_trace_each) and counters (slamhip_matcher_m3rsm_each_stats), BIT FOR BIT, in both sum
+ *    orders, under pose_trig DEVICE, HOST and RAW_EXACT, for every weighting, both scan trig providers and every thread
+ *    count (tests/test_gpu_m3rsm_each_raw.py).
+ *  - A request whose filter keeps nothing: probability NaN, delta 0, kept 0, no observer call, zero counters, an empty
+ *    trace; it takes no part in the launches.  If every request is empty nothing is launched.  The observer gets
+ *    on_matching_end once per request that has a match, in request order.
+ *  - slamhip_matcher_stats: launches = slamhip_matcher_m3rsm_match_each's count + 1 (the assembly launch); 0 when
+ *    nothing was launched.
+ *  - Stored scan slots, the selected slot and an uploaded scan are not touched.  n_requests == 1 takes the same path.
+ *  - Refusals, all before anything is launched or the last call's state is replaced: SLAMHIP_ERR_INVALID for a matcher
+ *    that is not BF_M3RSM, speculation (0, 0), rotation slots on (rotation-slot scans are not made on the device: their
+ *    viny / ahr weights turn with the candidate), a null or foreign pyramid, pyramids of different cell models or OIEs,
+ *    and whatever the lone raw call and slamhip_matcher_process_raw_scan_batch refuse of a scan; SLAMHIP_ERR_STATE for
+ *    a stale pyramid; RAW_EXACT on a host whose libm is neither restated build: the code the stored form gives. */
+typedef struct {
+  slamhip_pyramid *pyramid; /* the scan is filtered against the fine map this pyramid stands over */
+  slamhip_raw_scan scan;    /* as for slamhip_matcher_process_raw_scan */
+  double init_pose[3];
+} slamhip_m3rsm_raw_request;
+int slamhip_matcher_m3rsm_match_each_raw(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_raw_request *req,
+                                         double *out_deltas /* 3 per request */, double *out_probs, int *kept_n);
+/* request's scan block of the last such call, as slamhip_matcher_batch_scan_download gives a job's; angle_out (may be
+ * NULL) the kept points' angles */
+int slamhip_matcher_m3rsm_each_scan_download(slamhip_matcher *m, int request, int cap, double *out5, double *angle_out, int *n);
 /* K robots' engines on ONE Monte-Carlo matcher.  In the reference every robot owns its matcher and with it an engine of
  * its own seed (init_scan_matching.h:118-135); a matcher has one std::mt19937, never reseeded, so the batch calls above
  * run a Monte-Carlo matcher's jobs one after another on that one engine.  With streams set, the two batch calls run job

@@ -75,7 +75,9 @@ slamhip_matcher_process_raw_scan_batch slamhip_matcher_batch_scan_download
 slamhip_matcher_set_mc_streams slamhip_matcher_set_mc_job_streams slamhip_matcher_mc_stream_info
 slamhip_matcher_set_bf_streams slamhip_matcher_set_bf_job_streams slamhip_matcher_bf_stream_info
 slamhip_map_append_scan_batch slamhip_map_update_batch_stats slamhip_map_update_batch_tables
-slamhip_gmapping_particle_generate_scans slamhip_scan_generate_host_tiled""".split()
+slamhip_gmapping_particle_generate_scans slamhip_scan_generate_host_tiled
+slamhip_pyramid_refresh_batch slamhip_pyramid_refresh_batch_stats
+slamhip_matcher_m3rsm_match_each_raw slamhip_matcher_m3rsm_each_scan_download""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -90,6 +92,11 @@ class SlamHipError(RuntimeError):
 class ShardMsg(C.Structure):
     """slamhip_shard_msg"""
     _fields_ = [("peer", C.c_int), ("buf", C.c_void_p), ("bytes", C.c_size_t)]
+
+
+class PyramidRefreshJob(C.Structure):
+    """slamhip_pyramid_refresh_job: one refresh of slamhip_pyramid_refresh_batch."""
+    _fields_ = [("pyramid", C.c_void_p), ("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
 
 
 class MatchJob(C.Structure):
@@ -301,6 +308,8 @@ def load(testing=False):
     L.slamhip_pyramid_info.argtypes = [vp, _ip, i, _ip, _ip, _ip, _ip, _ip, _dp]
     L.slamhip_pyramid_rebuild.argtypes = [vp]
     L.slamhip_pyramid_refresh.argtypes = [vp, i, i, i, i]
+    L.slamhip_pyramid_refresh_batch.argtypes = [vp, i, C.POINTER(PyramidRefreshJob)]
+    L.slamhip_pyramid_refresh_batch_stats.argtypes = [vp, _ip, _ip, _ip, _ip]
     L.slamhip_pyramid_build_host.argtypes = [i, i, i, i, i, i, d, _dp, _dp, i, _ip, _ip, _ip, _ip, _ip, _dp, C.c_size_t, _dp,
                                              C.POINTER(C.c_size_t)]
     L.slamhip_pyramid_score_matches.argtypes = [vp, vp, C.POINTER(SpeCfg), _dp, i, _dp, _dp, _dp, _ip]
@@ -731,6 +740,24 @@ class Context:
         _check(self.L.slamhip_map_update_batch_tables(self.h, C.byref(v[4]), C.byref(up)))
         return dict(rounds=v[0].value, jobs_shared=v[1].value, jobs_lone=v[2].value, launches=v[3].value,
                     tables=v[4].value, table_uploads=up.value)
+
+    def pyramid_refresh_batch(self, jobs):
+        """slamhip_pyramid_refresh_batch: jobs = [(pyramid, x0, y0, w, h), ...] (INTERNAL fine windows) refreshed in
+        shared launches; every level ends bit-equal to Pyramid.refresh of the same jobs in this order.  Queued on the
+        context's stream, no wait.  (A pyramid may be None: the library refuses.)"""
+        jobs = list(jobs)
+        table = (PyramidRefreshJob * max(len(jobs), 1))()
+        for k, (pyr, x0, y0, w, h) in enumerate(jobs):
+            table[k].pyramid = None if pyr is None else pyr.h
+            table[k].x0, table[k].y0, table[k].w, table[k].h = int(x0), int(y0), int(w), int(h)
+        _check(self.L.slamhip_pyramid_refresh_batch(self.h, len(jobs), table))
+
+    def pyramid_refresh_batch_stats(self):
+        """of the last pyramid_refresh_batch that was not refused: rounds, jobs in shared launches, jobs through the lone
+        call, kernel launches of the rounds"""
+        v = [C.c_int() for _ in range(4)]
+        _check(self.L.slamhip_pyramid_refresh_batch_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(rounds=v[0].value, jobs_shared=v[1].value, jobs_lone=v[2].value, launches=v[3].value)
 
     def map_download_aux(self, map_id, x0, y0, w, h, stride):
         out = np.zeros((h, w, stride))
@@ -1662,7 +1689,45 @@ def _batch_scan_download(self, job):
     return out[:, :max(n.value, 0)]
 
 
+class M3rsmRawRequest(C.Structure):
+    """slamhip_m3rsm_raw_request: one match of slamhip_matcher_m3rsm_match_each_raw."""
+    _fields_ = [("pyramid", C.c_void_p), ("scan", RawScan), ("init_pose", C.c_double * 3)]
+
+
+def _m3rsm_match_each_raw(self, requests):
+    """BF_M3RSM, K raw scans in, K independent matches (slamhip_matcher_m3rsm_match_each_raw).  requests: a list of dicts
+    like make_raw_batch's jobs with `pyramid` (a Pyramid; None: the library refuses) in place of map_id -- the scan is
+    filtered against the window of the pyramid's fine map.  Returns a list of dict(delta[3], prob, kept), request k's
+    being the lone process_raw_scan's on a matcher over its pyramid (delta 0, prob NaN, kept 0 where the filter kept
+    nothing)."""
+    requests = list(requests)
+    blk = self.make_raw_batch([dict(r, map_id=0) for r in requests])
+    arr = (M3rsmRawRequest * max(len(requests), 1))()
+    for k, r in enumerate(requests):
+        arr[k].pyramid = None if r["pyramid"] is None else r["pyramid"].h
+        arr[k].scan = blk["raw_arr"][k].scan
+        arr[k].init_pose = blk["raw_arr"][k].init_pose
+    fn = self.L.slamhip_matcher_m3rsm_match_each_raw
+    fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(M3rsmRawRequest), _dp, _dp, _ip]
+    _check(fn(self.h, len(requests), arr, _d(blk["deltas"]), _d(blk["probs"]), blk["kept"].ctypes.data_as(_ip)))
+    return [dict(delta=blk["deltas"][k].copy(), prob=float(blk["probs"][k]), kept=int(blk["kept"][k])) for k in range(len(requests))]
+
+
+def _m3rsm_each_scan_download(self, request):
+    """Request's scan block of the last m3rsm_match_each_raw: (rows [5, kept] as batch_scan_download, angles [kept])."""
+    fn = self.L.slamhip_matcher_m3rsm_each_scan_download
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip]
+    n = C.c_int(-1)
+    _check(fn(self.h, int(request), 0, None, None, C.byref(n)))
+    out, ang = np.full((5, max(n.value, 1)), np.nan), np.full(max(n.value, 1), np.nan)
+    if n.value > 0:
+        _check(fn(self.h, int(request), out.shape[1], _d(out), _d(ang), C.byref(n)))
+    return out[:, :max(n.value, 0)], ang[:max(n.value, 0)]
+
+
 Matcher.make_raw_batch = _make_raw_batch
+Matcher.m3rsm_match_each_raw = _m3rsm_match_each_raw
+Matcher.m3rsm_each_scan_download = _m3rsm_each_scan_download
 Matcher.process_raw_scan_batch = _process_raw_scan_batch
 Matcher.batch_scan_download = _batch_scan_download
 

@@ -287,8 +287,17 @@ int slamhip_pyramid_expand_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg
                                     const double *rect, double translation_step, int depth, double *rect_out,
                                     double *score_out, int *level_out) {
   std::vector<PyrSource> src;
-  int rc = pyr_many_sources(ctx, cfg, n_requests, table, &src);
+  const int rc = pyr_many_sources(ctx, cfg, n_requests, table, &src);
   if (rc) return rc;
+  return pyr_expand_sources(ctx, cfg, src, table[0].pyramid->cell_model, n, request, rotation, rect, translation_step, depth,
+                            rect_out, score_out, level_out);
+}
+
+int slamhip::pyr_expand_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int cell_model,
+                                int n, const int *request, const double *rotation, const double *rect, double translation_step,
+                                int depth, double *rect_out, double *score_out, int *level_out) {
+  const int n_requests = (int)src.size();
+  int rc = SLAMHIP_OK;
   if (n < 0) return pyr_invalid("bad parent batch");
   if (!(translation_step > 0.0) || !std::isfinite(translation_step))
     return pyr_invalid("the translation step must be positive and finite");
@@ -313,7 +322,7 @@ int slamhip_pyramid_expand_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg
   if (rc) return rc;
   typedef void (*Kernel)(ExpandManyArgs);
   const bool raw = a.q.m.raw.cos != nullptr;
-  const Kernel kernel = pick_cell_model(table[0].pyramid->cell_model, [raw](auto m) -> Kernel {
+  const Kernel kernel = pick_cell_model(cell_model, [raw](auto m) -> Kernel {
     return raw ? k_m3rsm_expand_many<decltype(m)::value, true> : k_m3rsm_expand_many<decltype(m)::value, false>;
   });
   SLAMHIP_CHECK(launch_kernel(kernel, dim3((unsigned)n_out), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));

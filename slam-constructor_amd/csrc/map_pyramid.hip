@@ -30,6 +30,7 @@
 #include "libm_exact.h"
 #include "map_pyramid_device.h"
 #include "map_pyramid_score.h"
+#include "pyr_refresh_batch_plan.h"
 #include "score_device.h"
 
 namespace slamhip {
@@ -63,6 +64,53 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyr_reduce(pyr::Level src, pyr:
   const double unknown[4] = {u0, u1, u2, u3};
   for (int y = (int)blockIdx.y; y < ch; y += (int)gridDim.y)
     pyr::reduce_cell<CD>(src, dst, bias_x, bias_y, model, oie, unknown, cx0 + x, cy0 + y);
+}
+
+// ---- refresh of several pyramids (slamhip_pyramid_refresh_batch; the planning: pyr_refresh_batch_plan.h) ----------
+// One (job, level) of a call, read from the job table in HBM: k_pyr_reduce's arguments.  Cells
+// [cx0, cx0 + cw) x [cy0, cy0 + ch) of dst lie inside dst's window (the plan clips), cd = doubles per cell (1 or 4).
+static_assert(pyr_plan::kThreads == kPyrThreads, "the plan sizes the grids for the kernels' workgroup");
+struct PyrReduceEntry {
+  pyr::Level src, dst;
+  int bias_x, bias_y;
+  int cx0, cy0, cw, ch;
+  int model, oie, cd, pad;
+  double unknown[4];
+};
+
+// cell c (row-major) of the entry's window; c < cw * ch
+__device__ __forceinline__ void reduce_entry_cell(const PyrReduceEntry &e, int c) {
+  const int y = c / e.cw, x = c - y * e.cw;
+  if (e.cd == 1) pyr::reduce_cell<1>(e.src, e.dst, e.bias_x, e.bias_y, e.model, e.oie, e.unknown, e.cx0 + x, e.cy0 + y);
+  else pyr::reduce_cell<4>(e.src, e.dst, e.bias_x, e.bias_y, e.model, e.oie, e.unknown, e.cx0 + x, e.cy0 + y);
+}
+
+// One level of every job of a round whose window at that level is large: a flat grid, job after job, a thread per cell;
+// workgroup b belongs to the job j with off[j] <= b < off[j + 1] (uniform per workgroup: entry and offsets go through
+// the scalar cache).  The jobs' pyramids differ, so no cell is written twice and no cell read is written by this launch.
+__global__ __launch_bounds__(kPyrThreads) void k_pyr_reduce_batch(const PyrReduceEntry *__restrict__ entries,
+                                                                  const unsigned *__restrict__ off, int n_jobs) {
+  const int j = pyr_plan::find_job(off, n_jobs, blockIdx.x);
+  const PyrReduceEntry &e = entries[j];
+  const long long c = (long long)(blockIdx.x - off[j]) * kPyrThreads + threadIdx.x;
+  if (c >= (long long)e.cw * e.ch) return;
+  reduce_entry_cell(e, (int)c);
+}
+
+// The upper levels of every job of a round: workgroup j walks the n entries of its run bottom-up, a workgroup barrier
+// between levels.  Level lv + 1 reads payload and coordinates this same workgroup has just written for level lv (its
+// other source cells were written by earlier kernels): the waves of a workgroup run on one CU and share its vector L1,
+// which its own stores go through, so __syncthreads() -- a workgroup-scope release (the stores' vmcnt wait), the
+// barrier, a workgroup-scope acquire -- is all the ordering this needs; nothing here is read by another workgroup.
+// The loop bounds come from the table and are uniform, and every thread reaches every barrier (no early return).
+__global__ __launch_bounds__(kPyrThreads) void k_pyr_reduce_tail(const PyrReduceEntry *entries, const int *__restrict__ runs) {
+  const int first = runs[2 * blockIdx.x], n = runs[2 * blockIdx.x + 1];
+  for (int k = 0; k < n; ++k) {
+    const PyrReduceEntry &e = entries[first + k];
+    const int cells = e.cw * e.ch;  // (at most kPyrThreads by the plan; walked all the same)
+    for (int c = (int)threadIdx.x; c < cells; c += kPyrThreads) reduce_entry_cell(e, c);
+    __syncthreads();
+  }
 }
 
 pyr::Level level_of(const DeviceMap &m, int *coord) {
@@ -441,6 +489,47 @@ void pyr_many_release(slamhip_ctx *ctx) {
   ctx->pyr_many = nullptr;
 }
 
+int pyr_source_begin(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, slamhip_pyramid *p, const slamhip_pyramid **first,
+                     PyrSource *q) {
+  if (!p) return pyr_invalid("a request without a pyramid");
+  // (a pyramid of another context, or one that has been destroyed, is not in this context's list: it is not read)
+  if (std::find(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)p) == ctx->pyramids.end())
+    return pyr_invalid("a request's pyramid belongs to another context, or has been destroyed");
+  int rc = check_fresh(p);
+  if (rc) return rc;
+  if (!*first) {
+    *first = p;
+    rc = check_score_cfg(p, cfg);
+    if (rc) return rc;
+    if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST &&
+        cfg->pose_trig != SLAMHIP_POSE_TRIG_RAW_EXACT)
+      return pyr_invalid("pose_trig: DEVICE, HOST or RAW_EXACT");
+    if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT) {
+      bool fma = false;
+      rc = raw_libm_build(&fma);
+      if (rc) return rc;
+    }
+  }
+  if (p->cell_model != (*first)->cell_model || p->oie != (*first)->oie)
+    return pyr_invalid("the pyramids of one call share the cell model and the OIE");
+  std::memset(q, 0, sizeof(*q));
+  q->levels = p->d_views;
+  q->n_levels = p->plan.n + 1;
+  return SLAMHIP_OK;
+}
+
+int pyr_source_pose(const double pose[3], PyrSource *q) {
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(pose[k])) return pyr_invalid("a request's pose is not finite");
+  for (int k = 0; k < 3; ++k) q->base[k] = pose[k];
+  return SLAMHIP_OK;
+}
+
+void pyr_source_block(const double *d, size_t stride, int n, double tot_w, const double *d_angle, PyrSource *q) {
+  q->scan = scan_view_of(d, stride, n, tot_w);
+  q->angle = d_angle;
+}
+
 int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests, const slamhip_m3rsm_request *req,
                      std::vector<PyrSource> *out) {
   if (!ctx) return pyr_invalid("null context");
@@ -448,51 +537,19 @@ int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_request
   out->clear();
   const slamhip_pyramid *first = nullptr;
   for (int r = 0; r < n_requests; ++r) {
-    slamhip_pyramid *p = req[r].pyramid;
-    if (!p) return pyr_invalid("a request without a pyramid");
-    // (a pyramid of another context, or one that has been destroyed, is not in this context's list: it is not read)
-    if (std::find(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)p) == ctx->pyramids.end())
-      return pyr_invalid("a request's pyramid belongs to another context, or has been destroyed");
-    int rc = check_fresh(p);
+    PyrSource q;
+    int rc = pyr_source_begin(ctx, cfg, req[r].pyramid, &first, &q);
     if (rc) return rc;
-    if (!first) {
-      first = p;
-      rc = check_score_cfg(p, cfg);
-      if (rc) return rc;
-      if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST &&
-          cfg->pose_trig != SLAMHIP_POSE_TRIG_RAW_EXACT)
-        return pyr_invalid("pose_trig: DEVICE, HOST or RAW_EXACT");
-      if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT) {
-        bool fma = false;
-        rc = raw_libm_build(&fma);
-        if (rc) return rc;
-      }
-    }
-    if (p->cell_model != first->cell_model || p->oie != first->oie)
-      return pyr_invalid("the pyramids of one call share the cell model and the OIE");
     const int slot = req[r].scan_slot;
     if (slot < 0 || slot >= (int)ctx->scan_slots.size() || !ctx->scan_slots[slot].d || ctx->scan_slots[slot].n <= 0)
       return pyr_invalid("a request's scan slot holds no scan (slamhip_scan_store)");
-    for (int k = 0; k < 3; ++k)
-      if (!std::isfinite(req[r].init_pose[k])) return pyr_invalid("a request's pose is not finite");
+    rc = pyr_source_pose(req[r].init_pose, &q);
+    if (rc) return rc;
     const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[slot];
     if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT && ((int)sl.angle.size() != sl.n || !sl.d_angle))
       return pyr_state("SLAMHIP_POSE_TRIG_RAW_EXACT needs the angles of every request's stored scan: "
                        "slamhip_scan_store_angles after slamhip_scan_store");
-    PyrSource q;
-    std::memset(&q, 0, sizeof(q));
-    q.levels = p->d_views;
-    q.n_levels = p->plan.n + 1;
-    const size_t c = (size_t)sl.cap;
-    q.scan.range = sl.d;
-    q.scan.cos_a = sl.d + c;
-    q.scan.sin_a = sl.d + 2 * c;
-    q.scan.weight = sl.d + 3 * c;
-    q.scan.factor = sl.d + 4 * c;
-    q.scan.n = sl.n;
-    q.scan.tot_w = sl.tot_w;
-    for (int k = 0; k < 3; ++k) q.base[k] = req[r].init_pose[k];
-    if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT) q.angle = sl.d_angle;
+    pyr_source_block(sl.d, (size_t)sl.cap, sl.n, sl.tot_w, cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT ? sl.d_angle : nullptr, &q);
     out->push_back(q);
   }
   return SLAMHIP_OK;
@@ -655,7 +712,43 @@ void pyr_free_staging(slamhip_pyramid *p) {
   p->terms_cap = p->x_slot_cap = p->raw_cap = 0;
 }
 
+// slamhip_pyramid_refresh_batch's job tables, kept by the context: one block in HBM and two pinned ones taking turns.
+// The call does not wait, so the copy of a table may still be pending when the next call fills one: a pinned block is
+// written only after the event behind its last copy has passed (the block in HBM is rewritten in stream order, behind
+// the kernels that read it).
+struct PyrRefreshStage {
+  char *h[2] = {nullptr, nullptr}, *d = nullptr;
+  hipEvent_t copied[2] = {nullptr, nullptr};
+  bool pending[2] = {false, false};
+  size_t cap = 0;
+  int turn = 0;
+  pyr_plan::Plan plan;  // of the last call that was not refused
+};
+
+static void pyr_refresh_free_blocks(PyrRefreshStage *st) {
+  for (int k = 0; k < 2; ++k) {
+    if (st->h[k]) (void)hipHostFree(st->h[k]);
+    st->h[k] = nullptr;
+    st->pending[k] = false;
+  }
+  if (st->d) (void)hipFree(st->d);
+  st->d = nullptr;
+  st->cap = 0;
+}
+
+static void pyr_refresh_release(slamhip_ctx *ctx) {
+  PyrRefreshStage *st = static_cast<PyrRefreshStage *>(ctx->pyr_refresh);
+  if (!st) return;
+  (void)hipStreamSynchronize(ctx->stream);
+  pyr_refresh_free_blocks(st);
+  for (int k = 0; k < 2; ++k)
+    if (st->copied[k]) (void)hipEventDestroy(st->copied[k]);
+  delete st;
+  ctx->pyr_refresh = nullptr;
+}
+
 void pyramids_release(slamhip_ctx *ctx) {
+  pyr_refresh_release(ctx);
   for (void *v : ctx->pyramids) {
     slamhip_pyramid *p = static_cast<slamhip_pyramid *>(v);
     free_levels(p, false);  // (the context frees its maps itself)
@@ -737,6 +830,149 @@ int slamhip_pyramid_refresh(slamhip_pyramid *p, int x0, int y0, int w, int h) {
     return pyr_invalid("window outside the fine map");
   SLAMHIP_CHECK(hipSetDevice(p->ctx->device));
   return queue_levels(p, x0, y0, w, h);
+}
+
+int slamhip_pyramid_refresh_batch(slamhip_ctx *ctx, int n_jobs, const slamhip_pyramid_refresh_job *jobs) {
+  if (!ctx) return pyr_invalid("null context");
+  if (n_jobs < 0) return pyr_invalid("negative job count");
+  if (n_jobs == 0) return SLAMHIP_OK;
+  if (!jobs) return pyr_invalid("null jobs");
+  // every refusal first: nothing is queued and the last call's plan stays
+  std::vector<pyr_plan::Job> pj(n_jobs);
+  std::vector<std::vector<pyr_plan::LevelGeom>> geom(n_jobs);
+  for (int k = 0; k < n_jobs; ++k) {
+    slamhip_pyramid *p = jobs[k].pyramid;
+    if (!p) return pyr_invalid("a job without a pyramid");
+    const auto at = std::find(ctx->pyramids.begin(), ctx->pyramids.end(), (void *)p);
+    if (at == ctx->pyramids.end()) return pyr_invalid("a job's pyramid belongs to another context, or has been destroyed");
+    const int rc = check_fresh(p);
+    if (rc) return rc;
+    pyr_plan::Job &j = pj[k];
+    j.pyramid = (int)(at - ctx->pyramids.begin());
+    j.n_levels = p->plan.n;
+    geom[k].resize(p->plan.n);
+    j.lone = false;
+    for (int lv = 1; lv <= p->plan.n; ++lv) {
+      geom[k][lv - 1] = pyr_plan::LevelGeom{p->plan.width[lv - 1], p->plan.height[lv - 1], p->plan.origin_x[lv - 1],
+                                            p->plan.origin_y[lv - 1]};
+      if (ctx->maps[p->first_id + lv - 1].prob_ok) j.lone = true;  // (its probability plane follows its cells: queue_levels)
+    }
+    j.levels = geom[k].data();
+    j.fine_w = p->fine_w;
+    j.fine_h = p->fine_h;
+    j.fine_ox = p->fine_ox;
+    j.fine_oy = p->fine_oy;
+    j.x0 = jobs[k].x0;
+    j.y0 = jobs[k].y0;
+    j.w = jobs[k].w;
+    j.h = jobs[k].h;
+    j.stale = false;
+  }
+  pyr_plan::Plan plan;
+  switch (pyr_plan::plan_call(pj, sizeof(PyrReduceEntry), &plan)) {
+    case pyr_plan::kOk: break;
+    case pyr_plan::kWindow: return pyr_invalid("a job's window is outside its fine map");
+    case pyr_plan::kTooLarge: return pyr_invalid("the batch needs more than 2^31 workgroups in one launch: split it");
+    default: return pyr_state("a job's pyramid is stale: slamhip_pyramid_rebuild");
+  }
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  if (!ctx->pyr_refresh) ctx->pyr_refresh = new PyrRefreshStage;
+  PyrRefreshStage *st = static_cast<PyrRefreshStage *>(ctx->pyr_refresh);
+  for (int k = 0; k < 2; ++k)
+    if (!st->copied[k]) SLAMHIP_CHECK(hipEventCreateWithFlags(&st->copied[k], hipEventDisableTiming));
+  if (plan.table_bytes > st->cap) {
+    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+    pyr_refresh_free_blocks(st);
+    size_t cap = 1 << 14;
+    while (cap < plan.table_bytes) cap *= 2;
+    SLAMHIP_CHECK(hipMalloc(&st->d, cap));
+    for (int k = 0; k < 2; ++k) SLAMHIP_CHECK(hipHostMalloc(&st->h[k], cap, hipHostMallocDefault));
+    st->cap = cap;
+  }
+  const PyrReduceEntry *d_entries = reinterpret_cast<const PyrReduceEntry *>(st->d);
+  const unsigned *d_off = reinterpret_cast<const unsigned *>(st->d + plan.off_bytes_at);
+  const int *d_runs = reinterpret_cast<const int *>(st->d + plan.run_bytes_at);
+  if (plan.table_bytes) {
+    const int turn = st->turn;
+    st->turn ^= 1;
+    if (st->pending[turn]) {
+      SLAMHIP_CHECK(hipEventSynchronize(st->copied[turn]));
+      st->pending[turn] = false;
+    }
+    char *h = st->h[turn];
+    std::memset(h, 0, plan.table_bytes);
+    PyrReduceEntry *h_entries = reinterpret_cast<PyrReduceEntry *>(h);
+    for (size_t i = 0; i < plan.entries.size(); ++i) {
+      const pyr_plan::EntryRef &r = plan.entries[i];
+      const slamhip_pyramid *p = jobs[r.job].pyramid;
+      const int lv = r.level;
+      const DeviceMap &src = ctx->maps[lv == 1 ? p->fine_id : p->first_id + lv - 2];
+      const DeviceMap &dst = ctx->maps[p->first_id + lv - 1];
+      const bool top = lv == p->plan.n;
+      PyrReduceEntry &e = h_entries[i];
+      e.src = level_of(src, lv == 1 ? nullptr : p->d_coord[lv - 2]);
+      e.dst = level_of(dst, p->d_coord[lv - 1]);
+      e.bias_x = top ? 0 : src.origin_x - 2 * dst.origin_x;
+      e.bias_y = top ? 0 : src.origin_y - 2 * dst.origin_y;
+      e.cx0 = r.win.cx0;
+      e.cy0 = r.win.cy0;
+      e.cw = r.win.cw;
+      e.ch = r.win.ch;
+      e.model = p->cell_model;
+      e.oie = p->oie;
+      e.cd = cell_doubles(p->cell_model) == 1 ? 1 : 4;
+      for (int k = 0; k < 4; ++k) e.unknown[k] = dst.unknown[k];
+    }
+    unsigned *h_off = reinterpret_cast<unsigned *>(h + plan.off_bytes_at);
+    int *h_runs = reinterpret_cast<int *>(h + plan.run_bytes_at);
+    for (const pyr_plan::Step &s : plan.steps) {
+      for (const pyr_plan::FlatLaunch &f : s.flat) std::copy(f.block_off.begin(), f.block_off.end(), h_off + f.off_at);
+      for (size_t k = 0; k < s.tail.size(); ++k) {
+        h_runs[2 * (s.run_at + k)] = (int)s.tail[k].entry_at;
+        h_runs[2 * (s.run_at + k) + 1] = s.tail[k].n_entries;
+      }
+    }
+    SLAMHIP_CHECK(hipMemcpyAsync(st->d, h, plan.table_bytes, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipEventRecord(st->copied[turn], ctx->stream));
+    st->pending[turn] = true;
+  }
+  st->plan = plan;
+  st->plan.stats.launches = 0;  // (counted as they are queued)
+  for (const pyr_plan::Step &s : plan.steps) {
+    if (s.lone) {
+      const slamhip_pyramid_refresh_job &jb = jobs[s.jobs[0]];
+      const int rc = queue_levels(jb.pyramid, jb.x0, jb.y0, jb.w, jb.h);
+      if (rc) return rc;
+      continue;
+    }
+    ProfilePairGuard prof;  // (while profiling is on: a round's kernels, first to last, in kernel_ms_total)
+    int rc = prof.open(ctx, ctx->stream, 0);
+    if (rc) return rc;
+    for (const pyr_plan::FlatLaunch &f : s.flat) {
+      SLAMHIP_CHECK(launch_kernel(k_pyr_reduce_batch, dim3(f.block_off.back()), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr,
+                                  d_entries + f.entry_at, d_off + f.off_at, (int)f.jobs.size()));
+      st->plan.stats.launches += 1;
+    }
+    SLAMHIP_CHECK(launch_kernel(k_pyr_reduce_tail, dim3((unsigned)s.tail.size()), dim3(kPyrThreads), 0, ctx->stream, nullptr,
+                                nullptr, d_entries, d_runs + 2 * s.run_at));
+    st->plan.stats.launches += 1;
+    rc = prof.close();
+    if (rc) return rc;
+    if (ctx->profile) ctx->prof_launches += 1;
+  }
+  return SLAMHIP_OK;
+}
+
+int slamhip_pyramid_refresh_batch_stats(slamhip_ctx *ctx, int *rounds, int *jobs_in_shared_launches, int *jobs_lone,
+                                        int *launches) {
+  if (!ctx) return pyr_invalid("null context");
+  const PyrRefreshStage *st = static_cast<const PyrRefreshStage *>(ctx->pyr_refresh);
+  const pyr_plan::Stats s = st ? st->plan.stats : pyr_plan::Stats{};
+  if (rounds) *rounds = s.rounds;
+  if (jobs_in_shared_launches) *jobs_in_shared_launches = s.jobs_shared;
+  if (jobs_lone) *jobs_lone = s.jobs_lone;
+  if (launches) *launches = s.launches;
+  return SLAMHIP_OK;
 }
 
 int slamhip_pyramid_score_matches_device(slamhip_ctx *ctx, slamhip_pyramid *p, const slamhip_spe_cfg *cfg,
@@ -863,8 +1099,16 @@ int slamhip_pyramid_score_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg,
                                    const slamhip_m3rsm_request *table, int n, const int *request, const double *rotation,
                                    const double *rect, double *score_out, int *level_out) {
   std::vector<PyrSource> src;
-  int rc = pyr_many_sources(ctx, cfg, n_requests, table, &src);
+  const int rc = pyr_many_sources(ctx, cfg, n_requests, table, &src);
   if (rc) return rc;
+  return pyr_score_sources(ctx, cfg, src, table[0].pyramid->cell_model, n, request, rotation, rect, score_out, level_out);
+}
+
+int slamhip::pyr_score_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int cell_model,
+                               int n, const int *request, const double *rotation, const double *rect, double *score_out,
+                               int *level_out) {
+  const int n_requests = (int)src.size();
+  int rc = SLAMHIP_OK;
   if (n < 0) return pyr_invalid("bad candidate batch");
   if (n == 0) return SLAMHIP_OK;
   if (!score_out || !level_out) return pyr_invalid("null output arrays");
@@ -880,7 +1124,7 @@ int slamhip_pyramid_score_requests(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg,
   if (rc) return rc;
   typedef void (*Kernel)(ManyArgs);
   const bool raw = a.m.raw.cos != nullptr;
-  const Kernel kernel = pick_cell_model(table[0].pyramid->cell_model, [raw](auto m) -> Kernel {
+  const Kernel kernel = pick_cell_model(cell_model, [raw](auto m) -> Kernel {
     return raw ? k_pyr_score_many<decltype(m)::value, true> : k_pyr_score_many<decltype(m)::value, false>;
   });
   SLAMHIP_CHECK(launch_kernel(kernel, dim3(n), dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, a));

@@ -122,6 +122,19 @@ void pyr_many_release(slamhip_ctx *ctx);
 // (under SLAMHIP_POSE_TRIG_RAW_EXACT also that every request's slot has angles and the host's libm is a known build)
 int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_requests, const slamhip_m3rsm_request *req,
                      std::vector<PyrSource> *out);
+// ... the parts of that, for a caller whose requests' scans are not in stored slots: the pyramid's checks (the first
+// request's also check cfg) and the level table; the pose; the scan as a block of five rows at `stride` with n points and
+// their total weight, and the row of the points' angles (SLAMHIP_POSE_TRIG_RAW_EXACT, else null)
+int pyr_source_begin(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, slamhip_pyramid *p, const slamhip_pyramid **first, PyrSource *q);
+int pyr_source_pose(const double pose[3], PyrSource *q);
+void pyr_source_block(const double *d, size_t stride, int n, double tot_w, const double *d_angle, PyrSource *q);
+// slamhip_pyramid_score_requests / slamhip_pyramid_expand_requests (m3rsm.hip) below the sources: the candidates' checks,
+// the staging, the launch, the fetch (cell_model: the pyramids')
+int pyr_score_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int cell_model, int n,
+                      const int *request, const double *rotation, const double *rect, double *score_out, int *level_out);
+int pyr_expand_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vector<PyrSource> &src, int cell_model, int n,
+                       const int *request, const double *rotation, const double *rect, double translation_step, int depth,
+                       double *rect_out, double *score_out, int *level_out);
 // stages n candidates (request, rotation, rect) of the table, leaving room for n x slots outputs; fills a->m's inputs and
 // outputs, a->table, a->request, a->terms_off.  After the launch: pyr_many_fetch.  Under SLAMHIP_POSE_TRIG_RAW_EXACT it
 // also stages the rows of the distinct (request, rotation) pairs, queues their tabulation and fills a->m.raw

@@ -200,6 +200,28 @@ struct McBatch {
   int slots = 0;             // candidates per job and super-step of the last call
 };
 
+// slamhip_matcher_m3rsm_match_each_raw: the multi-resolution matcher's own raw-scan state (the chains' HcBatch is not
+// touched) -- the host half (filter, rows, the scanners' tables: scan_filter.h), the ONE pinned arena
+// k_scan_assemble_each reads, the arena in HBM it writes the six-row blocks into, the tables in HBM (one block of
+// cos | sin | viny_f | angle per slot of stage.slots), and where each request's block of the last call lies
+struct M3rsmRaw {
+  slamhip::RawBatchStage stage;
+  slamhip::PinnedBuf<unsigned char> h_arena;
+  slamhip::DeviceBuf<double> d_blocks;
+  size_t h_cap = 0, d_cap = 0;
+  struct Tab {
+    slamhip::DeviceBuf<double> d;
+    int cap = 0;
+  };
+  std::vector<Tab> tabs;
+  struct Block {
+    const double *d = nullptr;  // null: the request kept nothing
+    size_t stride = 0;
+    int n = 0;
+  };
+  std::vector<Block> blocks;
+};
+
 // K brute-force sweeps per call (bf_batch_run): the staged job table, the jobs' slices of the flat score / fingerprint /
 // prefix arrays, per job its aggregates, three counter words and its entry of the pinned result array, the call's ONE
 // completion word, and what the hand-over needs to turn a best index into a pose
@@ -344,6 +366,7 @@ struct slamhip_matcher {
     int each_threads = 0;  // workers of the host half of a round (0: min(requests, 8))
     std::unique_ptr<slamhip::m3rsm::Pool> each_pool;  // ... kept from call to call, made anew when the count changes
     long long copied_back = 0;  // bytes the launches of the last match wrote back to the host (scores, levels, rectangles)
+    std::unique_ptr<M3rsmRaw> raw;  // slamhip_matcher_m3rsm_match_each_raw, made by its first call
   };
   bool is_m3rsm = false;
   std::unique_ptr<M3rsm> m3;
@@ -2613,6 +2636,9 @@ int m3rsm_match_many(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
 // one, request = job.  Each search is the lone match's, so request k gets what m3rsm_process_scan gives on its inputs.
 constexpr size_t kEachStageLimit = (size_t)256 << 20;  // a launch's strict-mode terms beyond this: consecutive launches
 
+int m3rsm_each_run(slamhip_matcher *m, int n_requests, const std::vector<PyrSource> &src, RotationSlots &rs, int cell_model,
+                   double *out_deltas, double *out_probs);
+
 int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_request *req, double *out_deltas, double *out_probs) {
   slamhip_matcher::M3rsm &s = *m->m3;
   slamhip_ctx *ctx = m->ctx;
@@ -2628,11 +2654,27 @@ int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
   rs.init(s.rot_slots, s.cfg, n_requests, req);
   const int n_tab = rs.n_table(n_requests);
   const slamhip_m3rsm_request *tab = rs.tab(req);
-  std::vector<PyrSource> src;  // (checked before anything runs: the launches check again, they are entry points too)
+  std::vector<PyrSource> src;  // (checked before anything runs)
   {
     const int rc = pyr_many_sources(ctx, &m->cfg, n_tab, tab, &src);
     if (rc) return rc;
   }
+  return m3rsm_each_run(m, n_requests, src, rs, tab[0].pyramid->cell_model, out_deltas, out_probs);
+}
+
+// ... below the sources: request k's scan, levels and base pose are src[k * rs.n_rot + rotation slot], wherever the scan
+// lies (a stored slot, or a block slamhip_matcher_m3rsm_match_each_raw has assembled).  Resets the last call's state.
+int m3rsm_each_run(slamhip_matcher *m, int n_requests, const std::vector<PyrSource> &src, RotationSlots &rs, int cell_model,
+                   double *out_deltas, double *out_probs) {
+  slamhip_matcher::M3rsm &s = *m->m3;
+  slamhip_ctx *ctx = m->ctx;
+  m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
+  s.trace.clear();
+  s.res = m3rsm::Result{};
+  s.copied_back = 0;
+  s.each_res.clear();
+  s.each_code.clear();
+  s.each_trace.clear();
   const double t0 = MatchJob::now_us();
   const bool strict = m->cfg.sum_order == SLAMHIP_SUM_SEQUENTIAL;
   long long launches = 0;
@@ -2655,8 +2697,8 @@ int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
     const int *mq = rs.map(n, rq, rot);
     for (size_t c = 0; c + 1 < first.size(); ++c) {
       const int at = first[c];
-      const int rc = slamhip_pyramid_score_requests(ctx, &m->cfg, n_tab, tab, first[c + 1] - at, mq + at, rot + at,
-                                                    rect + 4 * (size_t)at, score + at, level + at);
+      const int rc = pyr_score_sources(ctx, &m->cfg, src, cell_model, first[c + 1] - at, mq + at, rot + at,
+                                       rect + 4 * (size_t)at, score + at, level + at);
       ++launches;
       if (rc) return rc;
     }
@@ -2670,9 +2712,9 @@ int m3rsm_match_each(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_req
     const int *mq = rs.map(n, rq, rot);
     for (size_t c = 0; c + 1 < first.size(); ++c) {
       const size_t at = (size_t)first[c];
-      const int rc = slamhip_pyramid_expand_requests(ctx, &m->cfg, n_tab, tab, first[c + 1] - first[c], mq + at, rot + at,
-                                                     rect + 4 * at, s.cfg.translation_step, depth, slot_rect + 4 * at * slots,
-                                                     slot_score + at * slots, slot_level + at * slots);
+      const int rc = pyr_expand_sources(ctx, &m->cfg, src, cell_model, first[c + 1] - first[c], mq + at, rot + at,
+                                        rect + 4 * at, s.cfg.translation_step, depth, slot_rect + 4 * at * slots,
+                                        slot_score + at * slots, slot_level + at * slots);
       ++launches;
       if (rc) return rc;
     }
@@ -2733,6 +2775,198 @@ int slamhip_matcher_m3rsm_match_each(slamhip_matcher *m, int n_requests, const s
   if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
   if (!out_deltas || !out_probs) return invalid_arg("null outputs");
   return m3rsm_match_each(m, n_requests, req, out_deltas, out_probs);
+}
+
+// K raw scans in, K multi-resolution matches.  The host half per request is the lone raw call's (scan_filter.h, through
+// RawBatchStage as slamhip_matcher_process_raw_scan_batch drives it; the window is the request's pyramid's fine map);
+// ONE launch of k_scan_assemble_each writes every live request's block -- five rows and the kept angles -- into the
+// matcher's arena in HBM; the lock-step searches of m3rsm_match_each run over sources that point at the blocks.  The
+// pinned arena is refilled by the next call only: this one returns after the searches, launched on the same stream
+// behind the assembly kernel, have delivered their last results.  Every refusal comes before the first launch and
+// before the last call's state goes.
+int slamhip_matcher_m3rsm_match_each_raw(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_raw_request *req, double *out_deltas,
+                                         double *out_probs, int *kept_n) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (n_requests < 1 || !req || !out_deltas || !out_probs) return invalid_arg("at least one request, and room for the results");
+  slamhip_matcher::M3rsm &s = *m->m3;
+  slamhip_ctx *ctx = m->ctx;
+  if (s.per_pop) return invalid_arg("speculation (0, 0), the per-pop measuring route, has no batched form");
+  if (s.rot_slots)
+    return invalid_arg("rotation slots are set (slamhip_matcher_set_m3rsm_rotation_slots): rotation-slot scans are not made "
+                       "on the device, the scans come from a request's stored slots");
+  if (n_requests > 65535) return invalid_arg("more requests than one assembly launch takes");
+  std::vector<PyrSource> all(n_requests);
+  std::vector<RawBatchJob> in(n_requests);
+  const slamhip_pyramid *first = nullptr;
+  for (int k = 0; k < n_requests; ++k) {
+    const slamhip_raw_scan &sc = req[k].scan;
+    if (sc.n <= 0 || !sc.range || !sc.angle) return invalid_arg("bad scan in a raw request");
+    if (sc.trig_mode != SLAMHIP_TRIG_RAW && sc.trig_mode != SLAMHIP_TRIG_CACHED) return invalid_arg("unknown trig mode in a raw request");
+    if (sc.weighting < 0 || sc.weighting > 2) return invalid_arg("unknown weighting kind");
+    int rc = pyr_source_begin(ctx, &m->cfg, req[k].pyramid, &first, &all[k]);
+    if (rc) return rc;
+    rc = pyr_source_pose(req[k].init_pose, &all[k]);
+    if (rc) return rc;
+    const DeviceMap &dm = ctx->maps[req[k].pyramid->fine_id];  // (bound and the pyramid's: pyr_source_begin has checked)
+    RawBatchJob &r = in[k];
+    r.n = sc.n;
+    r.range = sc.range;
+    r.angle = sc.angle;
+    r.is_occ = sc.is_occ;
+    r.factor = sc.factor;
+    r.trig_mode = sc.trig_mode;
+    r.a_min = sc.a_min;
+    r.a_max = sc.a_max;
+    r.a_inc = sc.a_inc;
+    r.skip_rate = sc.skip_rate;
+    r.max_range = sc.max_range;
+    r.bounded = sc.bounded ? 1 : 0;
+    r.weighting = sc.weighting;
+    for (int q = 0; q < 3; ++q) r.pose[q] = req[k].init_pose[q];
+    r.win = ScanWindow{dm.scale, dm.origin_x, dm.origin_y, dm.width, dm.height};
+  }
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  if (!s.raw) s.raw = std::make_unique<M3rsmRaw>();
+  M3rsmRaw &w = *s.raw;
+  RawBatchStage &raw = w.stage;
+  int rc = raw.prepare(n_requests, in.data(), sizeof(ScanAssembleEachArgs), 6);
+  if (rc) return invalid_arg(scan_error_text(rc));
+  if (raw.n_live > 0) {
+    // (the stream is idle: the call before returned after its searches had ended)
+    rc = grow_block(ctx->stream, w.h_arena, w.h_cap, raw.arena_bytes, 1 << 16, 1, hipHostMallocMapped);
+    if (rc) return rc;
+    rc = raw.fill(in.data(), w.h_arena.get());
+    if (rc) return invalid_arg(scan_error_text(rc));
+  }
+  // ---- the last check lies behind: from here on the last call's state goes
+  if (kept_n)
+    for (int k = 0; k < n_requests; ++k) kept_n[k] = raw.plan[k].k;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int k = 0; k < n_requests; ++k) {
+    out_deltas[3 * (size_t)k] = out_deltas[3 * (size_t)k + 1] = out_deltas[3 * (size_t)k + 2] = 0.0;
+    out_probs[k] = nan;
+  }
+  w.blocks.assign(n_requests, M3rsmRaw::Block{});
+  const auto spread = [&](int n_live) {  // the searches' results by live place -> by request; an empty request: nothing ran
+    std::vector<m3rsm::Result> res(n_requests);
+    std::vector<int> code(n_requests, m3rsm::kErrNoMatch);
+    std::vector<std::vector<m3rsm::Call>> trace(n_requests);
+    for (int k = 0; k < n_requests && n_live > 0; ++k) {
+      const int l = raw.plan[k].live;
+      if (l < 0 || l >= (int)s.each_res.size()) continue;
+      res[k] = s.each_res[l];
+      code[k] = s.each_code[l];
+      trace[k] = std::move(s.each_trace[l]);
+    }
+    s.each_res = std::move(res);
+    s.each_code = std::move(code);
+    s.each_trace = std::move(trace);
+  };
+  if (raw.n_live == 0) {  // every filter kept nothing: no launch at all
+    m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
+    s.trace.clear();
+    s.res = m3rsm::Result{};
+    s.copied_back = 0;
+    s.each_res.clear();
+    s.each_code.clear();
+    s.each_trace.clear();
+    spread(0);
+    return SLAMHIP_OK;
+  }
+  rc = grow_block(ctx->stream, w.d_blocks, w.d_cap, raw.dst_doubles, 1 << 14);
+  if (rc) return rc;
+  // ---- the tables of the scanners this call has met for the first time: to HBM, the angle plane with them (the call
+  // waits for the copies instead of keeping the sources alive; a later call with these scanners sends none)
+  if (w.tabs.size() < raw.slots.size()) w.tabs.resize(raw.slots.size());
+  bool sent = false;
+  for (size_t q = 0; q < raw.slots.size(); ++q) {
+    RawBatchStage::Slot &sl = raw.slots[q];
+    if (!sl.fresh || sl.used != raw.call) continue;
+    M3rsmRaw::Tab &tab = w.tabs[q];
+    const int n = (int)sl.t.cos_a.size();
+    rc = grow_block(ctx->stream, tab.d, tab.cap, n, 2048, 4);  // (cos | sin | viny_f | angle)
+    if (rc) return rc;
+    const size_t bytes = sizeof(double) * n;
+    const size_t cap = (size_t)tab.cap;
+    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get(), sl.t.cos_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + cap, sl.t.sin_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + 2 * cap, sl.t.viny_f.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + 3 * cap, sl.t.angle.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    sl.fresh = false;
+    sent = true;
+    ++ctx->scan_tab_uploads;
+  }
+  if (sent) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  // ---- the args table, the sources, the launch
+  ScanAssembleEachArgs *table = reinterpret_cast<ScanAssembleEachArgs *>(w.h_arena.get());
+  std::vector<PyrSource> src(raw.n_live);
+  const bool exact = m->cfg.pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
+  for (int k = 0; k < n_requests; ++k) {
+    const RawBatchPlan &p = raw.plan[k];
+    if (p.live < 0) continue;
+    const unsigned char *h = w.h_arena.get();
+    const M3rsmRaw::Tab &tab = w.tabs[p.table];
+    const size_t cap = (size_t)tab.cap;
+    ScanAssembleEachArgs e{};
+    ScanAssembleArgs &as = e.a;
+    as.h_range = reinterpret_cast<const double *>(h + p.off_range);
+    if (p.off_kept != kNoRow) as.h_kept = reinterpret_cast<const int *>(h + p.off_kept);
+    if (p.off_factor != kNoRow) as.h_factor = reinterpret_cast<const double *>(h + p.off_factor);
+    if (p.off_weight != kNoRow) as.h_weight = reinterpret_cast<const double *>(h + p.off_weight);
+    as.tab_cos = tab.d.get();
+    as.tab_sin = tab.d.get() + cap;
+    if (req[k].scan.weighting == 1) as.tab_viny = tab.d.get() + 2 * cap;
+    e.tab_angle = tab.d.get() + 3 * cap;
+    as.dst = w.d_blocks.get() + p.dst_at;
+    as.stride = p.stride;
+    as.n = p.k;
+    as.w_even = p.w_even;
+    table[p.live] = e;
+    w.blocks[k] = M3rsmRaw::Block{as.dst, p.stride, p.k};
+    src[p.live] = all[k];
+    pyr_source_block(as.dst, p.stride, p.k, p.tot_w, exact ? as.dst + 5 * p.stride : nullptr, &src[p.live]);
+  }
+  {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    rc = profile_event_pair(ctx, &e0, &e1);
+    if (rc) return rc;
+    if (e0) SLAMHIP_CHECK(hipEventRecord(e0, ctx->stream));
+    SLAMHIP_CHECK(launch_scan_assemble_each(table, raw.n_live, raw.max_stride, ctx->stream));
+    if (e1) SLAMHIP_CHECK(hipEventRecord(e1, ctx->stream));
+    if (ctx->profile) ++ctx->prof_launches;
+  }
+  RotationSlots rs;  // (off)
+  std::vector<double> deltas(3 * (size_t)raw.n_live), probs(raw.n_live);
+  rc = m3rsm_each_run(m, raw.n_live, src, rs, first->cell_model, deltas.data(), probs.data());
+  m->job.launches += 1;  // (k_scan_assemble_each in front of the searches' launches)
+  spread(raw.n_live);
+  if (rc) return rc;
+  for (int k = 0; k < n_requests; ++k) {
+    const int l = raw.plan[k].live;
+    if (l < 0) continue;
+    for (int q = 0; q < 3; ++q) out_deltas[3 * (size_t)k + q] = deltas[3 * (size_t)l + q];
+    out_probs[k] = probs[l];
+  }
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_m3rsm_each_scan_download(slamhip_matcher *m, int request, int cap, double *out5, double *angle_out, int *n) {
+  if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
+  if (!n || cap < 0 || (cap > 0 && !out5)) return invalid_arg("bad arguments");
+  const M3rsmRaw *w = m->m3->raw.get();
+  if (!w || request < 0 || request >= (int)w->blocks.size()) return invalid_arg("no such request in the last match_each_raw");
+  const M3rsmRaw::Block &k = w->blocks[request];
+  *n = k.n;
+  if (cap == 0 || k.n <= 0) return SLAMHIP_OK;
+  if (cap < k.n) return invalid_arg("slamhip_matcher_m3rsm_each_scan_download: room for fewer points than the request's scan has");
+  slamhip_ctx *ctx = m->ctx;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  SLAMHIP_CHECK(hipMemcpy2DAsync(out5, sizeof(double) * cap, k.d, sizeof(double) * k.stride, sizeof(double) * k.n, 5,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  if (angle_out)
+    SLAMHIP_CHECK(hipMemcpyAsync(angle_out, k.d + 5 * k.stride, sizeof(double) * k.n, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return SLAMHIP_OK;
 }
 
 int slamhip_matcher_m3rsm_trace_each(slamhip_matcher *m, int request, int cap, double *rows, int *n) {

@@ -405,7 +405,7 @@ int scan_stage_rows(const ScanTables &t, int n, const double *range, const doubl
   return kScanOk;
 }
 
-int RawBatchStage::prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entry_bytes) {
+int RawBatchStage::prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entry_bytes, int dst_rows) {
   for (int c = 0; c < n_jobs; ++c) {
     const RawBatchJob &j = jobs[c];
     if (j.n <= 0 || !j.range || !j.angle) return kScanBadArgs;
@@ -478,7 +478,7 @@ int RawBatchStage::prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entr
     }
     p.stride = (k + 7) & ~(size_t)7;
     p.dst_at = dst_doubles;
-    dst_doubles += 5 * p.stride;
+    dst_doubles += (size_t)dst_rows * p.stride;
     max_stride = (int)p.stride > max_stride ? (int)p.stride : max_stride;
   }
   arena_bytes = at;

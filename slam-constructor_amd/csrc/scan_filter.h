@@ -117,7 +117,7 @@ struct RawBatchPlan {
   int live = -1;   // its place among the jobs that kept something (its entry of the args table)
   size_t kept_at = 0;                                                               // its kept list in RawBatchStage::kept
   size_t off_range = kNoRow, off_kept = kNoRow, off_factor = kNoRow, off_weight = kNoRow;  // bytes into the arena
-  size_t dst_at = 0, stride = 0;  // its five-row block, doubles into the batch's arena in HBM
+  size_t dst_at = 0, stride = 0;  // its block of dst_rows rows, doubles into the batch's arena in HBM
   double w_even = 0, tot_w = 0;
 };
 struct RawBatchStage {
@@ -137,8 +137,9 @@ struct RawBatchStage {
   ScanStageScratch ss;
   std::vector<double> w_viny;
   // Pass 1: arguments checked, scanners found or built, every job filtered, the arena laid out -- the args table of
-  // n_live entries of args_entry_bytes at offset 0, the rows behind it, every row 16-byte aligned.
-  int prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entry_bytes);
+  // n_live entries of args_entry_bytes at offset 0, the rows behind it, every row 16-byte aligned.  dst_rows: the rows
+  // of `stride` doubles a job's block in HBM has (five; six where the kept points' angles ride along as a sixth row).
+  int prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entry_bytes, int dst_rows = 5);
   // Pass 2: the rows of every live job written into `arena` (arena_bytes long), weights and their sums made.
   int fill(const RawBatchJob *jobs, unsigned char *arena);
 };

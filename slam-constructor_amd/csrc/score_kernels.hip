@@ -159,6 +159,35 @@ hipError_t launch_scan_assemble_batch(const ScanAssembleArgs *table, int n_jobs,
   return hipGetLastError();
 }
 
+// K raw scans of one slamhip_matcher_m3rsm_match_each_raw call: k_scan_assemble_batch's five rows by the same per-element
+// expressions (scan_assemble_point) and a SIXTH row, the kept points' angles -- angle[kept[q]] from the angle plane
+// kept with the scanner's table -- which SLAMHIP_POSE_TRIG_RAW_EXACT tabulates its beam directions from
+// (PyrSource::angle).  The pads of all six rows come out zero.  Writes stay inside [dst, dst + 6 * stride).
+__global__ __launch_bounds__(256) void k_scan_assemble_each(const ScanAssembleEachArgs *__restrict__ table) {
+  const ScanAssembleEachArgs e = table[blockIdx.y];
+  const ScanAssembleArgs &a = e.a;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= (int)a.stride) return;
+  ScanPoint p{0.0, 0.0, 0.0, 0.0, 0.0};
+  double angle = 0.0;
+  if (q < a.n) {
+    p = scan_assemble_point(a, q);
+    angle = e.tab_angle[a.h_kept ? a.h_kept[q] : q];
+  }
+  a.dst[q] = p.range;
+  a.dst[a.stride + q] = p.cos_a;
+  a.dst[2 * a.stride + q] = p.sin_a;
+  a.dst[3 * a.stride + q] = p.weight;
+  a.dst[4 * a.stride + q] = p.factor;
+  a.dst[5 * a.stride + q] = angle;
+}
+
+hipError_t launch_scan_assemble_each(const ScanAssembleEachArgs *table, int n_jobs, int max_stride, hipStream_t stream) {
+  if (n_jobs <= 0 || max_stride <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_scan_assemble_each, dim3((max_stride + 255) / 256, n_jobs), dim3(256), 0, stream, table);
+  return hipGetLastError();
+}
+
 // The same for a launch's small argument blocks (job tables, initial poses, a zeroed counter): ONE pull of the pinned
 // block in front of the launch instead of several hipMemcpyAsync / hipMemsetAsync calls (each ~6 us of host time and
 // ~10 us of stream time, see above).  The host rewrites the block only after the launch that follows has reported its

@@ -243,6 +243,13 @@ hipError_t launch_scan_assemble(const ScanAssembleArgs &a, unsigned *counter, un
 // k_scan_assemble_batch: n_jobs scan blocks in one launch, job c from table[c] (a table in pinned memory; grid.y = job,
 // max_stride = the widest block's stride)
 hipError_t launch_scan_assemble_batch(const ScanAssembleArgs *table, int n_jobs, int max_stride, hipStream_t stream);
+// k_scan_assemble_each: the same with a sixth row, angle[kept[q]] from the scanner's angle plane in HBM (six rows of
+// `stride` doubles at a.dst)
+struct ScanAssembleEachArgs {
+  ScanAssembleArgs a;
+  const double *tab_angle;
+};
+hipError_t launch_scan_assemble_each(const ScanAssembleEachArgs *table, int n_jobs, int max_stride, hipStream_t stream);
 // (both uploads write the host's stride_host doubles of a cell and leave the rest of it alone -- a GMAPPING cell's pad)
 hipError_t launch_scatter_cells(double *payload, int pitch, int cell_dbl, int stride_host, int n,
                                 const int *d_coords, const double *d_vals, hipStream_t stream);
@@ -458,6 +465,7 @@ struct slamhip_ctx {
   std::vector<double> scan_gen_stage;  // ... and its host side: what goes up and what comes back, one copy each
   std::vector<void *> pyramids;  // the slamhip_pyramid objects made over this context's maps (map_pyramid.hip)
   void *pyr_many = nullptr;      // PyrManyStage: the staging of the multi-request pyramid launches (map_pyramid.hip)
+  void *pyr_refresh = nullptr;   // PyrRefreshStage: slamhip_pyramid_refresh_batch's job tables and last plan (map_pyramid.hip)
   bool low_latency = true;
   bool stage_poses = false;  // copy poses to HBM first instead of reading them over PCIe
   // slamhip_ctx_set_option: equivalent execution paths (defaults = what is measured)

@@ -13,6 +13,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <iostream>
 #include <limits>
 #include <memory>
 #include <vector>
@@ -36,6 +38,7 @@ public:
   const GridMap &map() const { return *_view; }
   slamhip_pyramid *pyramid() { return _pyr; }
   int map_id() const { return _map_id; }
+  void invalidate_view() { _view->invalidate(); }  // the fine map has been written behind the view's back
 
   // BruteForceMultiResolutionScanMatcher over this map's levels, with init_bf_m3rsm's parameters
   // (src/utils/init_scan_matching.h:171-183).  The caller owns the matcher and destroys it before this map.
@@ -233,10 +236,78 @@ public:
     return out;
   }
 
+  // The filter parameters of the estimator (WeightedMeanPointProbabilitySPE: skip rate, usable range; bounded: the maps
+  // have a rim) that match_each_raw hands the library instead of running filter_scan on the host
+  void set_filter_params(unsigned skip_rate, double max_range, bool bounded) {
+    _skip_rate = skip_rate;
+    _max_range = max_range;
+    _bounded = bounded;
+    _own_filter = true;
+  }
+
+  // K INDEPENDENT matches from K RAW scans (slamhip_matcher_m3rsm_match_each_raw): request k = (poses[k], scans[k],
+  // maps[k]); the library filters every scan against its map's fine level, assembles all of them on the device in one
+  // launch and runs the searches of match_each -- no filter_scan, no scan_store per robot.  Needs set_filter_params, and
+  // an estimator whose weighting does not turn with the candidate (rotation_spw unset: rotation-slot scans are not made
+  // on the device).  The requests added with add_scan_matching_request are not touched.
+  std::vector<BestMatch> match_each_raw(const std::vector<RobotPose> &poses, const std::vector<const LaserScan2D *> &scans,
+                                        const std::vector<HipM3rsmMap *> &maps) {
+    const size_t n = poses.size();
+    if (scans.size() != n || maps.size() != n || !_own_filter || _rot_spw) {
+      std::cerr << "[slamhip] HipM3rsmEngine::match_each_raw: one scan and one map per pose, filter parameters set, no "
+                   "rotation weighting" << std::endl;
+      std::exit(-1);
+    }
+    std::vector<BestMatch> out(n);
+    // (a scan without points: the library asks for n > 0; the reference's answer for it is the empty scan's)
+    std::vector<size_t> live;
+    std::vector<slamhip_m3rsm_raw_request> req;
+    std::vector<std::vector<double>> r(n), a(n), f(n);
+    std::vector<std::vector<int>> occ(n);
+    for (size_t k = 0; k < n; ++k) {
+      const auto &pts = scans[k]->points();
+      const int m = int(pts.size());
+      if (m == 0) continue;
+      r[k].resize(m);
+      a[k].resize(m);
+      f[k].resize(m);
+      occ[k].resize(m);
+      for (int i = 0; i < m; ++i) {
+        r[k][i] = pts[i].range();
+        a[k][i] = pts[i].angle();
+        f[k][i] = pts[i].factor();
+        occ[k][i] = pts[i].is_occupied() ? 1 : 0;
+      }
+      slamhip_m3rsm_raw_request q;
+      q.pyramid = maps[k]->pyramid();
+      q.scan = slamhip_raw_scan{m, r[k].data(), a[k].data(), occ[k].data(), f[k].data(), _trig.mode, _trig.a_min, _trig.a_max,
+                                _trig.a_inc, _skip_rate, _max_range, _bounded ? 1 : 0, _weighting};
+      q.init_pose[0] = poses[k].x;
+      q.init_pose[1] = poses[k].y;
+      q.init_pose[2] = poses[k].theta;
+      req.push_back(q);
+      live.push_back(k);
+    }
+    if (req.empty()) return out;
+    std::vector<double> deltas(3 * req.size(), 0.0), probs(req.size(), 0.0);
+    slamhip_or_die(slamhip_matcher_m3rsm_match_each_raw(_matcher, int(req.size()), req.data(), deltas.data(), probs.data(), nullptr),
+                   "m3rsm_match_each_raw");
+    for (size_t l = 0; l < live.size(); ++l) {
+      BestMatch &b = out[live[l]];
+      b.request = probs[l] == probs[l] ? int(live[l]) : -1;  // (NaN: no match, or the filter kept nothing)
+      b.pose_delta = RobotPoseDelta{deltas[3 * l], deltas[3 * l + 1], deltas[3 * l + 2]};
+      b.prob_upper_bound = probs[l];
+    }
+    return out;
+  }
+
 private:
   slamhip_ctx *_ctx;
   slamhip_matcher *_matcher;
   std::shared_ptr<ScanProbabilityEstimator> _spe;
+  bool _own_filter = false, _bounded = false;
+  unsigned _skip_rate = 0;
+  double _max_range = -1;
   int _weighting;
   HipScanTrig _trig;
   int _first_slot;
@@ -244,5 +315,76 @@ private:
   int _slots_per_request = 1;
   std::vector<slamhip_m3rsm_request> _requests;
 };
+
+// K robots' map updates and the levels behind them in shared launches: ONE slamhip_map_append_scan_batch over the maps'
+// fine levels (scan k into maps[k] from poses[k]; cos_a / sin_a: the scans' provider tables, as for
+// HipM3rsmMap::append_scan) and ONE slamhip_pyramid_refresh_batch over the cells each scan can have reached -- the reach
+// rule of HipM3rsmMap::append_scan; a map whose window grew gets slamhip_pyramid_rebuild instead.  The maps share `ctx`
+// and are distinct.  HipM3rsmMap::append_scan stays what it is for one robot.
+struct HipM3rsmScan {
+  int n;
+  const double *range, *cos_a, *sin_a;
+  const int *is_occ;
+  const double *quality;  // may be null
+};
+inline void hip_m3rsm_append_scans(slamhip_ctx *ctx, const std::vector<HipM3rsmMap *> &maps, const slamhip_scan_adder_cfg &adder,
+                                   const std::vector<RobotPose> &poses, const std::vector<HipM3rsmScan> &scans) {
+  const size_t K = maps.size();
+  if (poses.size() != K || scans.size() != K) {
+    std::cerr << "[slamhip] hip_m3rsm_append_scans: one pose and one scan per map" << std::endl;
+    std::exit(-1);
+  }
+  if (K == 0) return;
+  struct Window {
+    int w = 0, h = 0, ox = 0, oy = 0;
+    double scale = 1.0;
+  };
+  const auto window_of = [&](int map_id) {
+    Window g;
+    slamhip_or_die(slamhip_map_info(ctx, map_id, nullptr, &g.w, &g.h, &g.ox, &g.oy, &g.scale, nullptr), "map_info");
+    return g;
+  };
+  std::vector<Window> before(K);
+  std::vector<slamhip_map_update_job> jobs(K);
+  for (size_t k = 0; k < K; ++k) {
+    before[k] = window_of(maps[k]->map_id());
+    slamhip_map_update_job &j = jobs[k];
+    j = slamhip_map_update_job{};
+    j.map_id = maps[k]->map_id();
+    j.pose[0] = poses[k].x;
+    j.pose[1] = poses[k].y;
+    j.pose[2] = poses[k].theta;
+    j.scan_quality = adder.scan_quality;
+    j.n = scans[k].n;
+    j.range = scans[k].range;
+    j.cos_a = scans[k].cos_a;
+    j.sin_a = scans[k].sin_a;
+    j.is_occ = scans[k].is_occ;
+    j.quality = scans[k].quality;
+  }
+  std::vector<long long> n_updates(K, 0);
+  slamhip_or_die(slamhip_map_append_scan_batch(ctx, &adder, int(K), jobs.data(), n_updates.data(), nullptr), "map_append_scan_batch");
+  std::vector<slamhip_pyramid_refresh_job> refresh;
+  for (size_t k = 0; k < K; ++k) {
+    maps[k]->invalidate_view();
+    const Window g = window_of(maps[k]->map_id());
+    if (g.w != before[k].w || g.h != before[k].h || g.ox != before[k].ox || g.oy != before[k].oy) {
+      slamhip_or_die(slamhip_pyramid_rebuild(maps[k]->pyramid()), "pyramid_rebuild");
+      continue;
+    }
+    double reach = 0.0;
+    for (int i = 0; i < scans[k].n; ++i) reach = std::max(reach, std::isfinite(scans[k].range[i]) ? scans[k].range[i] : 0.0);
+    if (std::isfinite(adder.max_range)) reach = std::min(reach, adder.max_range);
+    reach += std::fabs(adder.blur) + 2 * g.scale;  // (a dynamic blur is a fraction of the beam: inside twice the reach)
+    if (adder.blur < 0) reach *= 2;
+    const int x0 = std::max(0, (int)std::floor((poses[k].x - reach) / g.scale) + g.ox);
+    const int y0 = std::max(0, (int)std::floor((poses[k].y - reach) / g.scale) + g.oy);
+    const int x1 = std::min(g.w - 1, (int)std::floor((poses[k].x + reach) / g.scale) + g.ox);
+    const int y1 = std::min(g.h - 1, (int)std::floor((poses[k].y + reach) / g.scale) + g.oy);
+    if (x1 < x0 || y1 < y0) continue;
+    refresh.push_back(slamhip_pyramid_refresh_job{maps[k]->pyramid(), x0, y0, x1 - x0 + 1, y1 - y0 + 1});
+  }
+  slamhip_or_die(slamhip_pyramid_refresh_batch(ctx, int(refresh.size()), refresh.data()), "pyramid_refresh_batch");
+}
 
 #endif  // SLAMHIP_M3RSM_MAP_H
