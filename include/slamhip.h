@@ -916,7 +916,7 @@ int slamhip_matcher_batch_scan_download(slamhip_matcher *m, int job, int cap, do
 /* K RAW scans in, K MULTI-RESOLUTION matches: the raw-scan form of slamhip_matcher_m3rsm_match_each (a BF_M3RSM matcher
  * only; the two batch calls above keep refusing one).  Per request the host runs the lone call's filter against the
  * window of the request's pyramid's FINE map and the initial pose; what is new with each scan goes into ONE pinned arena
- * of the matcher's own, ONE launch (k_scan_assemble_each) assembles every live request's block in HBM -- the five rows
+ * of the matcher's own, ONE launch (k_scan_assemble_table) assembles every live request's block in HBM -- the five rows
  * and, as a sixth, the kept points' angles (SLAMHIP_POSE_TRIG_RAW_EXACT reads them) -- from per-scanner tables kept
  * resident between calls (slamhip_scan_table_uploads counts their uploads: a second call with the same scanners sends
  * none), and the lock-step searches of slamhip_matcher_m3rsm_match_each run over those blocks.

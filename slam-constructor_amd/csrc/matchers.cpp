@@ -16,68 +16,10 @@
 #include "map_pyramid_score.h"
 #include "mc_chain_device.h"
 #include "matchers.h"
+#include "raw_stage_device.h"
 #include "resident_policy.h"
 
 namespace slamhip {
-
-// A hipMalloc / hipHostMalloc block and its owner: freed when the owner goes, so that no error return between an
-// allocation and the store of its pointer can leak it.  Move-only; nothing else.
-template <class T, bool kPinned>
-class HipBlock {
-  T *p_ = nullptr;
-
- public:
-  HipBlock() = default;
-  HipBlock(const HipBlock &) = delete;
-  HipBlock &operator=(const HipBlock &) = delete;
-  HipBlock(HipBlock &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-  HipBlock &operator=(HipBlock &&o) noexcept {
-    if (this != &o) {
-      reset();
-      p_ = o.p_;
-      o.p_ = nullptr;
-    }
-    return *this;
-  }
-  ~HipBlock() { reset(); }
-  T *get() const { return p_; }
-  explicit operator bool() const { return p_ != nullptr; }
-  void reset() {
-    if (p_) {
-      if constexpr (kPinned) hipHostFree(p_);
-      else hipFree(p_);
-    }
-    p_ = nullptr;
-  }
-  // `count` elements in place of what was held (a failed allocation leaves the owner empty)
-  hipError_t alloc(size_t count, unsigned pinned_flags = 0) {
-    reset();
-    if constexpr (kPinned) return hipHostMalloc(&p_, sizeof(T) * count, pinned_flags);
-    else return hipMalloc(&p_, sizeof(T) * count);
-  }
-};
-template <class T>
-using DeviceBuf = HipBlock<T, false>;
-template <class T>
-using PinnedBuf = HipBlock<T, true>;
-constexpr unsigned kPinnedCoherent = hipHostMallocMapped | hipHostMallocCoherent;
-
-// A block that holds `cap` units of `per` elements and has to hold `need`: nothing, or the stream waited for (what runs
-// on it may read the block that goes away) and `floor` doubled up to `need` units allocated in its place.  alloc frees
-// first and a failed one leaves the owner empty, so the stored capacity is zero from the free to the success: an error
-// return never leaves an old capacity over a null block.
-template <class T, bool kPinned, class Cap>
-int grow_block(hipStream_t stream, HipBlock<T, kPinned> &block, Cap &cap, size_t need, size_t floor, size_t per = 1,
-               unsigned pinned_flags = 0) {
-  if (need <= (size_t)cap) return SLAMHIP_OK;
-  SLAMHIP_CHECK(hipStreamSynchronize(stream));
-  size_t grown = floor;
-  while (grown < need) grown *= 2;
-  cap = 0;
-  SLAMHIP_CHECK(block.alloc(per * grown, pinned_flags));
-  cap = (Cap)grown;
-  return SLAMHIP_OK;
-}
 
 // {chains-done counter (0), initial poses, a table with one Entry per chain}: one block per side that ONE pull kernel
 // moves in front of a launch (launch_block_pull)
@@ -160,25 +102,9 @@ struct HcBatch : slamhip::ChainSet<slamhip::HcResidentCtl, slamhip::HcJobView> {
   int trace_per = 0, trace_chains = 0;
   long long kernels = 0;
   std::vector<BatchJobResult> res;
-  // slamhip_matcher_process_raw_scan_batch: the host half (filter, rows, the scanners' tables: scan_filter.h), the ONE
-  // pinned arena k_scan_assemble_batch reads, the arena in HBM it writes the scan blocks into, the tables in HBM (one
-  // block of cos | sin | viny_f per slot of raw.slots), and where each job's block of the last raw batch lies
-  slamhip::RawBatchStage raw;
-  slamhip::PinnedBuf<unsigned char> h_raw;
-  slamhip::DeviceBuf<double> d_raw;
-  size_t h_raw_cap = 0, d_raw_cap = 0;
-  struct RawTab {
-    slamhip::DeviceBuf<double> d;
-    int cap = 0;
-  };
-  std::vector<RawTab> raw_tabs;
-  struct RawBlock {
-    const double *d = nullptr;  // null: none in the arena (nothing kept, or the job went through the lone call)
-    size_t stride = 0;
-    int n = 0;
-    bool lone = false;
-  };
-  std::vector<RawBlock> raw_blocks;
+  // slamhip_matcher_process_raw_scan_batch (the HC, MC and BF routes alike): the call's scans on their way into HBM,
+  // and where each job's block of the last raw batch lies
+  slamhip::RawDeviceStage raw;
 };
 
 // K Monte-Carlo matches per call (mc_batch_run): per-chain control / result blocks, the staged job table, the ONE arena
@@ -198,28 +124,6 @@ struct McBatch {
   unsigned epoch = 0;
   double kernels_avg = 6.0;  // kernels the longest chain of a call needed, smoothed: sizes the first burst
   int slots = 0;             // candidates per job and super-step of the last call
-};
-
-// slamhip_matcher_m3rsm_match_each_raw: the multi-resolution matcher's own raw-scan state (the chains' HcBatch is not
-// touched) -- the host half (filter, rows, the scanners' tables: scan_filter.h), the ONE pinned arena
-// k_scan_assemble_each reads, the arena in HBM it writes the six-row blocks into, the tables in HBM (one block of
-// cos | sin | viny_f | angle per slot of stage.slots), and where each request's block of the last call lies
-struct M3rsmRaw {
-  slamhip::RawBatchStage stage;
-  slamhip::PinnedBuf<unsigned char> h_arena;
-  slamhip::DeviceBuf<double> d_blocks;
-  size_t h_cap = 0, d_cap = 0;
-  struct Tab {
-    slamhip::DeviceBuf<double> d;
-    int cap = 0;
-  };
-  std::vector<Tab> tabs;
-  struct Block {
-    const double *d = nullptr;  // null: the request kept nothing
-    size_t stride = 0;
-    int n = 0;
-  };
-  std::vector<Block> blocks;
 };
 
 // K brute-force sweeps per call (bf_batch_run): the staged job table, the jobs' slices of the flat score / fingerprint /
@@ -366,7 +270,8 @@ struct slamhip_matcher {
     int each_threads = 0;  // workers of the host half of a round (0: min(requests, 8))
     std::unique_ptr<slamhip::m3rsm::Pool> each_pool;  // ... kept from call to call, made anew when the count changes
     long long copied_back = 0;  // bytes the launches of the last match wrote back to the host (scores, levels, rectangles)
-    std::unique_ptr<M3rsmRaw> raw;  // slamhip_matcher_m3rsm_match_each_raw, made by its first call
+    // slamhip_matcher_m3rsm_match_each_raw: its own raw-scan stage (the chains' HcBatch is not touched), made by its first call
+    std::unique_ptr<slamhip::RawDeviceStage> raw;
   };
   bool is_m3rsm = false;
   std::unique_ptr<M3rsm> m3;
@@ -2340,7 +2245,7 @@ struct ScanKeeper {
 template <class Job, class LiveOf, class Lone>
 int batch_hand_over(slamhip_matcher *m, int n_jobs, const Job *jobs, const std::vector<int> &sid, LiveOf &&live_of,
                     double *out_deltas, double *out_probs, int *kept_n, Lone &&lone) {
-  constexpr bool kRaw = std::is_same<Job, slamhip_raw_match_job>::value;  // (its jobs' blocks are on record: raw_blocks)
+  constexpr bool kRaw = std::is_same<Job, slamhip_raw_match_job>::value;  // (its jobs' blocks are on record: raw.blocks)
   HcBatch *b = m->batch.get();
   const HcTraceEntry *chain_trace = b->h_trace.get();
   size_t chain_trace_per = (size_t)b->trace_per;
@@ -2357,7 +2262,7 @@ int batch_hand_over(slamhip_matcher *m, int n_jobs, const Job *jobs, const std::
     const int live = live_of(c);
     int kept = 0;
     if (r.on_chain) {
-      if constexpr (kRaw) kept = b->raw_blocks[c].n;
+      if constexpr (kRaw) kept = b->raw.blocks[c].n;
       for (int q = 0; q < 3; ++q) dl[q] = r.pose[q] - j.init_pose[q];
       out_probs[c] = r.prob;
       if (m->has_obs) {
@@ -2386,7 +2291,7 @@ int batch_hand_over(slamhip_matcher *m, int n_jobs, const Job *jobs, const std::
           m->bf.skip_device = false;
         }
         if (rc) return rc;
-        if constexpr (kRaw) b->raw_blocks[c] = HcBatch::RawBlock{nullptr, 0, kept, true};
+        if constexpr (kRaw) b->raw.blocks[c] = RawDeviceStage::Block{nullptr, 0, kept, true};
         if (kept > 0) {
           r.calls = m->job.scorer_calls;
           r.evaluated = m->job.poses_evaluated;
@@ -2766,6 +2671,20 @@ int m3rsm_each_run(slamhip_matcher *m, int n_requests, const std::vector<PyrSour
   return SLAMHIP_OK;
 }
 
+// What the launches of a raw-scan call left per live place (plan[c].live) -> per job; `none` for a job that kept nothing.
+template <class T>
+void live_to_job(const std::vector<RawBatchPlan> &plan, std::vector<T> &v, const T &none) {
+  std::vector<T> by_job(plan.size(), none);
+  for (size_t c = 0; c < plan.size(); ++c) {
+    const int l = plan[c].live;
+    if (l >= 0 && l < (int)v.size()) by_job[c] = std::move(v[l]);
+  }
+  v = std::move(by_job);
+}
+// the texts of RawDeviceStage::check_scan's refusals, for a job of the chains' batch and for a fleet request
+const char *const kBadRawJob[] = {nullptr, "bad scan in a raw match job", "unknown trig mode in a raw match job", "unknown weighting kind"};
+const char *const kBadRawRequest[] = {nullptr, "bad scan in a raw request", "unknown trig mode in a raw request", "unknown weighting kind"};
+
 }  // namespace
 
 extern "C" {
@@ -2777,13 +2696,12 @@ int slamhip_matcher_m3rsm_match_each(slamhip_matcher *m, int n_requests, const s
   return m3rsm_match_each(m, n_requests, req, out_deltas, out_probs);
 }
 
-// K raw scans in, K multi-resolution matches.  The host half per request is the lone raw call's (scan_filter.h, through
-// RawBatchStage as slamhip_matcher_process_raw_scan_batch drives it; the window is the request's pyramid's fine map);
-// ONE launch of k_scan_assemble_each writes every live request's block -- five rows and the kept angles -- into the
-// matcher's arena in HBM; the lock-step searches of m3rsm_match_each run over sources that point at the blocks.  The
-// pinned arena is refilled by the next call only: this one returns after the searches, launched on the same stream
-// behind the assembly kernel, have delivered their last results.  Every refusal comes before the first launch and
-// before the last call's state goes.
+// K raw scans in, K multi-resolution matches.  The host half per request is the lone raw call's; RawDeviceStage (which
+// slamhip_matcher_process_raw_scan_batch drives too; the window is the request's pyramid's fine map) writes every live
+// request's block -- five rows and the kept angles -- into the matcher's arena in HBM with ONE launch; the lock-step
+// searches of m3rsm_match_each run over sources that point at the blocks.  The pinned arena is refilled by the next
+// call only: this one returns after the searches, launched on the same stream behind the assembly kernel, have
+// delivered their last results.  Every refusal comes before the first launch and before the last call's state goes.
 int slamhip_matcher_m3rsm_match_each_raw(slamhip_matcher *m, int n_requests, const slamhip_m3rsm_raw_request *req, double *out_deltas,
                                          double *out_probs, int *kept_n) {
   if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
@@ -2799,44 +2717,25 @@ int slamhip_matcher_m3rsm_match_each_raw(slamhip_matcher *m, int n_requests, con
   std::vector<RawBatchJob> in(n_requests);
   const slamhip_pyramid *first = nullptr;
   for (int k = 0; k < n_requests; ++k) {
-    const slamhip_raw_scan &sc = req[k].scan;
-    if (sc.n <= 0 || !sc.range || !sc.angle) return invalid_arg("bad scan in a raw request");
-    if (sc.trig_mode != SLAMHIP_TRIG_RAW && sc.trig_mode != SLAMHIP_TRIG_CACHED) return invalid_arg("unknown trig mode in a raw request");
-    if (sc.weighting < 0 || sc.weighting > 2) return invalid_arg("unknown weighting kind");
+    if (const int bad = RawDeviceStage::check_scan(req[k].scan)) return invalid_arg(kBadRawRequest[bad]);
     int rc = pyr_source_begin(ctx, &m->cfg, req[k].pyramid, &first, &all[k]);
     if (rc) return rc;
     rc = pyr_source_pose(req[k].init_pose, &all[k]);
     if (rc) return rc;
     const DeviceMap &dm = ctx->maps[req[k].pyramid->fine_id];  // (bound and the pyramid's: pyr_source_begin has checked)
-    RawBatchJob &r = in[k];
-    r.n = sc.n;
-    r.range = sc.range;
-    r.angle = sc.angle;
-    r.is_occ = sc.is_occ;
-    r.factor = sc.factor;
-    r.trig_mode = sc.trig_mode;
-    r.a_min = sc.a_min;
-    r.a_max = sc.a_max;
-    r.a_inc = sc.a_inc;
-    r.skip_rate = sc.skip_rate;
-    r.max_range = sc.max_range;
-    r.bounded = sc.bounded ? 1 : 0;
-    r.weighting = sc.weighting;
-    for (int q = 0; q < 3; ++q) r.pose[q] = req[k].init_pose[q];
-    r.win = ScanWindow{dm.scale, dm.origin_x, dm.origin_y, dm.width, dm.height};
+    in[k] = RawBatchStage::job_of(req[k].scan, req[k].init_pose, ScanWindow{dm.scale, dm.origin_x, dm.origin_y, dm.width, dm.height});
   }
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  if (!s.raw) s.raw = std::make_unique<M3rsmRaw>();
-  M3rsmRaw &w = *s.raw;
-  RawBatchStage &raw = w.stage;
-  int rc = raw.prepare(n_requests, in.data(), sizeof(ScanAssembleEachArgs), 6);
+  if (!s.raw) s.raw = std::make_unique<RawDeviceStage>();
+  RawDeviceStage &w = *s.raw;
+  const RawBatchStage &raw = w.host;
+  int rc = w.prepare(n_requests, in.data(), sizeof(ScanAssembleEachArgs), 6);
   if (rc) return invalid_arg(scan_error_text(rc));
   if (raw.n_live > 0) {
-    // (the stream is idle: the call before returned after its searches had ended)
-    rc = grow_block(ctx->stream, w.h_arena, w.h_cap, raw.arena_bytes, 1 << 16, 1, hipHostMallocMapped);
+    rc = w.assemble<ScanAssembleEachArgs>(ctx, in.data());
     if (rc) return rc;
-    rc = raw.fill(in.data(), w.h_arena.get());
-    if (rc) return invalid_arg(scan_error_text(rc));
+  } else {  // every filter kept nothing: no launch at all
+    w.blocks.assign(n_requests, RawDeviceStage::Block{});
   }
   // ---- the last check lies behind: from here on the last call's state goes
   if (kept_n)
@@ -2846,23 +2745,12 @@ int slamhip_matcher_m3rsm_match_each_raw(slamhip_matcher *m, int n_requests, con
     out_deltas[3 * (size_t)k] = out_deltas[3 * (size_t)k + 1] = out_deltas[3 * (size_t)k + 2] = 0.0;
     out_probs[k] = nan;
   }
-  w.blocks.assign(n_requests, M3rsmRaw::Block{});
-  const auto spread = [&](int n_live) {  // the searches' results by live place -> by request; an empty request: nothing ran
-    std::vector<m3rsm::Result> res(n_requests);
-    std::vector<int> code(n_requests, m3rsm::kErrNoMatch);
-    std::vector<std::vector<m3rsm::Call>> trace(n_requests);
-    for (int k = 0; k < n_requests && n_live > 0; ++k) {
-      const int l = raw.plan[k].live;
-      if (l < 0 || l >= (int)s.each_res.size()) continue;
-      res[k] = s.each_res[l];
-      code[k] = s.each_code[l];
-      trace[k] = std::move(s.each_trace[l]);
-    }
-    s.each_res = std::move(res);
-    s.each_code = std::move(code);
-    s.each_trace = std::move(trace);
+  const auto spread = [&] {  // the searches' results by live place -> by request; an empty request: nothing ran
+    live_to_job(raw.plan, s.each_res, m3rsm::Result{});
+    live_to_job(raw.plan, s.each_code, (int)m3rsm::kErrNoMatch);
+    live_to_job(raw.plan, s.each_trace, std::vector<m3rsm::Call>{});
   };
-  if (raw.n_live == 0) {  // every filter kept nothing: no launch at all
+  if (raw.n_live == 0) {
     m->job.scorer_calls = m->job.poses_evaluated = m->job.launches = 0;
     s.trace.clear();
     s.res = m3rsm::Result{};
@@ -2870,76 +2758,24 @@ int slamhip_matcher_m3rsm_match_each_raw(slamhip_matcher *m, int n_requests, con
     s.each_res.clear();
     s.each_code.clear();
     s.each_trace.clear();
-    spread(0);
+    spread();
     return SLAMHIP_OK;
   }
-  rc = grow_block(ctx->stream, w.d_blocks, w.d_cap, raw.dst_doubles, 1 << 14);
-  if (rc) return rc;
-  // ---- the tables of the scanners this call has met for the first time: to HBM, the angle plane with them (the call
-  // waits for the copies instead of keeping the sources alive; a later call with these scanners sends none)
-  if (w.tabs.size() < raw.slots.size()) w.tabs.resize(raw.slots.size());
-  bool sent = false;
-  for (size_t q = 0; q < raw.slots.size(); ++q) {
-    RawBatchStage::Slot &sl = raw.slots[q];
-    if (!sl.fresh || sl.used != raw.call) continue;
-    M3rsmRaw::Tab &tab = w.tabs[q];
-    const int n = (int)sl.t.cos_a.size();
-    rc = grow_block(ctx->stream, tab.d, tab.cap, n, 2048, 4);  // (cos | sin | viny_f | angle)
-    if (rc) return rc;
-    const size_t bytes = sizeof(double) * n;
-    const size_t cap = (size_t)tab.cap;
-    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get(), sl.t.cos_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + cap, sl.t.sin_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + 2 * cap, sl.t.viny_f.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + 3 * cap, sl.t.angle.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    sl.fresh = false;
-    sent = true;
-    ++ctx->scan_tab_uploads;
-  }
-  if (sent) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  // ---- the args table, the sources, the launch
-  ScanAssembleEachArgs *table = reinterpret_cast<ScanAssembleEachArgs *>(w.h_arena.get());
+  // ---- the sources: a live request's scan is its block
   std::vector<PyrSource> src(raw.n_live);
   const bool exact = m->cfg.pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
   for (int k = 0; k < n_requests; ++k) {
     const RawBatchPlan &p = raw.plan[k];
     if (p.live < 0) continue;
-    const unsigned char *h = w.h_arena.get();
-    const M3rsmRaw::Tab &tab = w.tabs[p.table];
-    const size_t cap = (size_t)tab.cap;
-    ScanAssembleEachArgs e{};
-    ScanAssembleArgs &as = e.a;
-    as.h_range = reinterpret_cast<const double *>(h + p.off_range);
-    if (p.off_kept != kNoRow) as.h_kept = reinterpret_cast<const int *>(h + p.off_kept);
-    if (p.off_factor != kNoRow) as.h_factor = reinterpret_cast<const double *>(h + p.off_factor);
-    if (p.off_weight != kNoRow) as.h_weight = reinterpret_cast<const double *>(h + p.off_weight);
-    as.tab_cos = tab.d.get();
-    as.tab_sin = tab.d.get() + cap;
-    if (req[k].scan.weighting == 1) as.tab_viny = tab.d.get() + 2 * cap;
-    e.tab_angle = tab.d.get() + 3 * cap;
-    as.dst = w.d_blocks.get() + p.dst_at;
-    as.stride = p.stride;
-    as.n = p.k;
-    as.w_even = p.w_even;
-    table[p.live] = e;
-    w.blocks[k] = M3rsmRaw::Block{as.dst, p.stride, p.k};
+    const double *d = w.blocks[k].d;
     src[p.live] = all[k];
-    pyr_source_block(as.dst, p.stride, p.k, p.tot_w, exact ? as.dst + 5 * p.stride : nullptr, &src[p.live]);
-  }
-  {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    rc = profile_event_pair(ctx, &e0, &e1);
-    if (rc) return rc;
-    if (e0) SLAMHIP_CHECK(hipEventRecord(e0, ctx->stream));
-    SLAMHIP_CHECK(launch_scan_assemble_each(table, raw.n_live, raw.max_stride, ctx->stream));
-    if (e1) SLAMHIP_CHECK(hipEventRecord(e1, ctx->stream));
-    if (ctx->profile) ++ctx->prof_launches;
+    pyr_source_block(d, p.stride, p.k, p.tot_w, exact ? d + 5 * p.stride : nullptr, &src[p.live]);
   }
   RotationSlots rs;  // (off)
   std::vector<double> deltas(3 * (size_t)raw.n_live), probs(raw.n_live);
   rc = m3rsm_each_run(m, raw.n_live, src, rs, first->cell_model, deltas.data(), probs.data());
-  m->job.launches += 1;  // (k_scan_assemble_each in front of the searches' launches)
-  spread(raw.n_live);
+  m->job.launches += 1;  // (k_scan_assemble_table in front of the searches' launches)
+  spread();
   if (rc) return rc;
   for (int k = 0; k < n_requests; ++k) {
     const int l = raw.plan[k].live;
@@ -2953,20 +2789,10 @@ int slamhip_matcher_m3rsm_match_each_raw(slamhip_matcher *m, int n_requests, con
 int slamhip_matcher_m3rsm_each_scan_download(slamhip_matcher *m, int request, int cap, double *out5, double *angle_out, int *n) {
   if (!m || !m->is_m3rsm) return invalid_arg("not a multi-resolution matcher");
   if (!n || cap < 0 || (cap > 0 && !out5)) return invalid_arg("bad arguments");
-  const M3rsmRaw *w = m->m3->raw.get();
+  const RawDeviceStage *w = m->m3->raw.get();
   if (!w || request < 0 || request >= (int)w->blocks.size()) return invalid_arg("no such request in the last match_each_raw");
-  const M3rsmRaw::Block &k = w->blocks[request];
-  *n = k.n;
-  if (cap == 0 || k.n <= 0) return SLAMHIP_OK;
-  if (cap < k.n) return invalid_arg("slamhip_matcher_m3rsm_each_scan_download: room for fewer points than the request's scan has");
-  slamhip_ctx *ctx = m->ctx;
-  SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  SLAMHIP_CHECK(hipMemcpy2DAsync(out5, sizeof(double) * cap, k.d, sizeof(double) * k.stride, sizeof(double) * k.n, 5,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-  if (angle_out)
-    SLAMHIP_CHECK(hipMemcpyAsync(angle_out, k.d + 5 * k.stride, sizeof(double) * k.n, hipMemcpyDeviceToHost, ctx->stream));
-  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return SLAMHIP_OK;
+  return w->download(m->ctx, request, cap, out5, angle_out, n,
+                     "slamhip_matcher_m3rsm_each_scan_download: room for fewer points than the request's scan has");
 }
 
 int slamhip_matcher_m3rsm_trace_each(slamhip_matcher *m, int request, int cap, double *rows, int *n) {
@@ -3484,7 +3310,7 @@ int slamhip_matcher_process_raw_scan(slamhip_matcher *m, int map_id, const slamh
 }
 
 // K raw scans, K matches in the shared launches.  The host half per job is the lone call's (scan_filter.h); the scans
-// reach HBM through ONE launch of k_scan_assemble_batch in front of the chains' launch, which reads the call's pinned
+// reach HBM through RawDeviceStage's ONE assembly launch in front of the chains' launch, which reads the call's pinned
 // arena: kept ranges, kept indices, factors, ahr weights and the table of per-job ScanAssembleArgs.  The arena is
 // refilled by the next call only: this one returns after its chains have reported their results, the chains were
 // launched on the same stream behind the assembly kernel, so the kernel has read the arena by then -- no flag.
@@ -3496,12 +3322,8 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
   slamhip_ctx *ctx = m->ctx;
   // ---- every check in front of the first launch: the arguments, the maps, the scanners' tables (prepare)
   for (int c = 0; c < n_jobs; ++c) {
-    const slamhip_raw_match_job &j = jobs[c];
-    if (j.scan.n <= 0 || !j.scan.range || !j.scan.angle) return invalid_arg("bad scan in a raw match job");
-    if (j.scan.trig_mode != SLAMHIP_TRIG_RAW && j.scan.trig_mode != SLAMHIP_TRIG_CACHED)
-      return invalid_arg("unknown trig mode in a raw match job");
-    if (j.scan.weighting < 0 || j.scan.weighting > 2) return invalid_arg("unknown weighting kind");
-    if (j.map_id < 0 || j.map_id >= (int)ctx->maps.size() || !ctx->maps[j.map_id].bound)
+    if (const int bad = RawDeviceStage::check_scan(jobs[c].scan)) return invalid_arg(kBadRawJob[bad]);
+    if (jobs[c].map_id < 0 || jobs[c].map_id >= (int)ctx->maps.size() || !ctx->maps[jobs[c].map_id].bound)
       return invalid_arg("unknown map id in a match job");
   }
   const bool mc_streams = m->is_mc && !m->mc_streams.empty();
@@ -3519,32 +3341,17 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
   if (!m->batch) m->batch = std::make_unique<HcBatch>();
   HcBatch *b = m->batch.get();
-  RawBatchStage &raw = b->raw;
+  RawDeviceStage &stage = b->raw;
+  const RawBatchStage &raw = stage.host;
   const bool planned = n_jobs > 1;  // (a batch of one is the lone call, which checks for itself)
   bool on_chains = false;
   if (planned) {
     std::vector<RawBatchJob> in(n_jobs);
     for (int c = 0; c < n_jobs; ++c) {
-      const slamhip_raw_scan &s = jobs[c].scan;
       const DeviceMap &dm = ctx->maps[jobs[c].map_id];
-      RawBatchJob &r = in[c];
-      r.n = s.n;
-      r.range = s.range;
-      r.angle = s.angle;
-      r.is_occ = s.is_occ;
-      r.factor = s.factor;
-      r.trig_mode = s.trig_mode;
-      r.a_min = s.a_min;
-      r.a_max = s.a_max;
-      r.a_inc = s.a_inc;
-      r.skip_rate = s.skip_rate;
-      r.max_range = s.max_range;
-      r.bounded = s.bounded ? 1 : 0;
-      r.weighting = s.weighting;
-      for (int q = 0; q < 3; ++q) r.pose[q] = jobs[c].init_pose[q];
-      r.win = ScanWindow{dm.scale, dm.origin_x, dm.origin_y, dm.width, dm.height};
+      in[c] = RawBatchStage::job_of(jobs[c].scan, jobs[c].init_pose, ScanWindow{dm.scale, dm.origin_x, dm.origin_y, dm.width, dm.height});
     }
-    int rc = raw.prepare(n_jobs, in.data(), sizeof(ScanAssembleArgs));
+    int rc = stage.prepare(n_jobs, in.data(), sizeof(ScanAssembleArgs), 5);
     if (rc) return invalid_arg(scan_error_text(rc));
     // the jobs that kept something, and whether the shared launches take them
     struct LiveJob {
@@ -3565,8 +3372,8 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
     // through the shared sweeps whole or not at all: one job above 4096 kept beams sends every job to its lone call)
     bool chains = raw.n_live > 1 && raw.n_live <= 65535 && raw.max_k <= 4096 && (!m->is_bf || bf_streams) &&
                   (mc_streams ? mc_batch_eligible(m) : (bf_streams ? bf_batch_eligible(m) : batch_chain_eligible(m)));
+    int cell_model = -1;
     if (chains) {
-      int cell_model = -1;
       rc = batch_maps_check(ctx, raw.n_live, live.data(), &cell_model);
       if (rc) return rc;
       if (bf_streams) {
@@ -3575,71 +3382,14 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
       }
     }
     if (chains) {
-      int cell_model = -1;
-      (void)batch_maps_check(ctx, raw.n_live, live.data(), &cell_model);
-      // ---- the arenas (the stream is idle: the batch before returned after its chains had ended): the pinned one, its
-      // rows filled; then the one in HBM
-      rc = grow_block(ctx->stream, b->h_raw, b->h_raw_cap, raw.arena_bytes, 1 << 16, 1, hipHostMallocMapped);
+      // (the arena is filled only now that the shared launches take the jobs; the stream is idle: the batch before
+      // returned after its chains had ended)
+      rc = stage.assemble<ScanAssembleArgs>(ctx, in.data());
       if (rc) return rc;
-      rc = raw.fill(in.data(), b->h_raw.get());
-      if (rc) return invalid_arg(scan_error_text(rc));
-      // (the last check of the arguments lies behind: from here on the last batch's blocks may go)
-      if (raw.dst_doubles > b->d_raw_cap) b->raw_blocks.clear();  // (they point into the block that goes away)
-      rc = grow_block(ctx->stream, b->d_raw, b->d_raw_cap, raw.dst_doubles, 1 << 14);
-      if (rc) return rc;
-      // ---- the tables of the scanners this call has met for the first time: to HBM, as the lone call sends its one
-      // (the call waits for the copies instead of keeping the sources alive; a later call with these scanners sends none)
-      if (b->raw_tabs.size() < raw.slots.size()) b->raw_tabs.resize(raw.slots.size());
-      bool sent = false;
-      for (size_t q = 0; q < raw.slots.size(); ++q) {
-        RawBatchStage::Slot &sl = raw.slots[q];
-        if (!sl.fresh || sl.used != raw.call) continue;
-        HcBatch::RawTab &tab = b->raw_tabs[q];
-        const int n = (int)sl.t.cos_a.size();
-        rc = grow_block(ctx->stream, tab.d, tab.cap, n, 2048, 3);  // (cos | sin | viny_f)
-        if (rc) return rc;
-        const size_t bytes = sizeof(double) * n;
-        SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get(), sl.t.cos_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + tab.cap, sl.t.sin_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        SLAMHIP_CHECK(hipMemcpyAsync(tab.d.get() + 2 * (size_t)tab.cap, sl.t.viny_f.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        sl.fresh = false;
-        sent = true;
-        ++ctx->scan_tab_uploads;
-      }
-      if (sent) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      // ---- the args table, the blocks, the launch
-      ScanAssembleArgs *table = reinterpret_cast<ScanAssembleArgs *>(b->h_raw.get());
       std::vector<BatchScanBlock> blocks(raw.n_live);
-      b->raw_blocks.assign(n_jobs, HcBatch::RawBlock{});
       for (int c = 0; c < n_jobs; ++c) {
         const RawBatchPlan &p = raw.plan[c];
-        if (p.live < 0) continue;
-        const unsigned char *h = b->h_raw.get();
-        const HcBatch::RawTab &tab = b->raw_tabs[p.table];
-        ScanAssembleArgs as{};
-        as.h_range = reinterpret_cast<const double *>(h + p.off_range);
-        if (p.off_kept != kNoRow) as.h_kept = reinterpret_cast<const int *>(h + p.off_kept);
-        if (p.off_factor != kNoRow) as.h_factor = reinterpret_cast<const double *>(h + p.off_factor);
-        if (p.off_weight != kNoRow) as.h_weight = reinterpret_cast<const double *>(h + p.off_weight);
-        as.tab_cos = tab.d.get();
-        as.tab_sin = tab.d.get() + tab.cap;
-        if (jobs[c].scan.weighting == 1) as.tab_viny = tab.d.get() + 2 * (size_t)tab.cap;
-        as.dst = b->d_raw.get() + p.dst_at;
-        as.stride = p.stride;
-        as.n = p.k;
-        as.w_even = p.w_even;
-        table[p.live] = as;
-        blocks[p.live] = BatchScanBlock{as.dst, p.stride, p.k, p.tot_w};
-        b->raw_blocks[c] = HcBatch::RawBlock{as.dst, p.stride, p.k, false};
-      }
-      {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        rc = profile_event_pair(ctx, &e0, &e1);
-        if (rc) return rc;
-        if (e0) SLAMHIP_CHECK(hipEventRecord(e0, ctx->stream));
-        SLAMHIP_CHECK(launch_scan_assemble_batch(table, raw.n_live, raw.max_stride, ctx->stream));
-        if (e1) SLAMHIP_CHECK(hipEventRecord(e1, ctx->stream));
-        if (ctx->profile) ++ctx->prof_launches;
+        if (p.live >= 0) blocks[p.live] = BatchScanBlock{stage.blocks[c].d, p.stride, p.k, p.tot_w};
       }
       b->res.assign(n_jobs, BatchJobResult{});
       b->kernels = 0;
@@ -3647,19 +3397,15 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
                       : (bf_streams ? bf_batch_run(m, raw.n_live, live.data(), blocks.data(), live_sid.data())
                                     : hc_batch_run(m, raw.n_live, live.data(), blocks.data(), cell_model));
       if (rc) return rc;
-      if (bf_streams) ++b->kernels;  // (k_scan_assemble_batch in front of the three)
-      // (the chains' results by live place -> by job)
-      std::vector<BatchJobResult> by_live(b->res.begin(), b->res.begin() + raw.n_live);
-      b->res.assign(n_jobs, BatchJobResult{});
-      for (int c = 0; c < n_jobs; ++c)
-        if (raw.plan[c].live >= 0) b->res[c] = by_live[raw.plan[c].live];
+      if (bf_streams) ++b->kernels;  // (k_scan_assemble_table in front of the three)
+      live_to_job(raw.plan, b->res, BatchJobResult{});  // (the chains' results by live place -> by job)
       on_chains = true;
     }
   }
   if (!on_chains) {  // (every job that kept something goes through the lone call below)
     b->res.assign(n_jobs, BatchJobResult{});
     b->kernels = 0;
-    b->raw_blocks.assign(n_jobs, HcBatch::RawBlock{});
+    stage.blocks.assign(n_jobs, RawDeviceStage::Block{});
   }
   // a job the chains did not take or did not settle: the lone raw call, which filters its scan into the upload buffer
   return batch_hand_over(
@@ -3672,18 +3418,9 @@ int slamhip_matcher_process_raw_scan_batch(slamhip_matcher *m, int n_jobs, const
 
 int slamhip_matcher_batch_scan_download(slamhip_matcher *m, int job, int cap, double *out5, int *n) {
   if (!m || !n || cap < 0 || (cap > 0 && !out5)) return invalid_arg("bad arguments");
-  if (!m->batch || job < 0 || job >= (int)m->batch->raw_blocks.size()) return invalid_arg("no such job in the last raw batch");
-  const HcBatch::RawBlock &k = m->batch->raw_blocks[job];
-  *n = k.n;
-  if (cap == 0 || k.n <= 0) return SLAMHIP_OK;
-  if (k.lone || !k.d) return invalid_arg("that job went through the lone call: its scan is not in the batch's arena");
-  if (cap < k.n) return invalid_arg("slamhip_matcher_batch_scan_download: room for fewer points than the job's scan has");
-  slamhip_ctx *ctx = m->ctx;
-  SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  SLAMHIP_CHECK(hipMemcpy2DAsync(out5, sizeof(double) * cap, k.d, sizeof(double) * k.stride, sizeof(double) * k.n, 5,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return SLAMHIP_OK;
+  if (!m->batch || job < 0 || job >= (int)m->batch->raw.blocks.size()) return invalid_arg("no such job in the last raw batch");
+  return m->batch->raw.download(m->ctx, job, cap, out5, nullptr, n,
+                                "slamhip_matcher_batch_scan_download: room for fewer points than the job's scan has");
 }
 
 int slamhip_matcher_tail_stats(slamhip_matcher *m, long long *calls_closed_form) {

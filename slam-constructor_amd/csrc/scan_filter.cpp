@@ -447,6 +447,7 @@ int RawBatchStage::prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entr
     }
     slots[at].used = call;
     p.table = at;
+    p.weighting = j.weighting;
     p.kept_at = kept_at;
     p.k = scan_filter_kept(slots[at].t, j.n, j.range, j.angle, j.is_occ, j.skip_rate, j.max_range,
                            j.bounded ? &j.win : nullptr, j.pose, fs, kept.data() + kept_at);
@@ -501,6 +502,24 @@ int RawBatchStage::fill(const RawBatchJob *jobs, unsigned char *arena) {
     if (rc) return rc;
   }
   return kScanOk;
+}
+
+void RawBatchStage::entry(int c, const unsigned char *arena, const ScanTablePlanes &tab, double *dst_base,
+                          ScanAssembleArgs *out) const {
+  const RawBatchPlan &p = plan[c];
+  ScanAssembleArgs as{};
+  as.h_range = reinterpret_cast<const double *>(arena + p.off_range);
+  if (p.off_kept != kNoRow) as.h_kept = reinterpret_cast<const int *>(arena + p.off_kept);
+  if (p.off_factor != kNoRow) as.h_factor = reinterpret_cast<const double *>(arena + p.off_factor);
+  if (p.off_weight != kNoRow) as.h_weight = reinterpret_cast<const double *>(arena + p.off_weight);
+  as.tab_cos = tab.cos_a;
+  as.tab_sin = tab.sin_a;
+  if (p.weighting == 1) as.tab_viny = tab.viny_f;
+  as.dst = dst_base + p.dst_at;
+  as.stride = p.stride;
+  as.n = p.k;
+  as.w_even = p.w_even;
+  *out = as;
 }
 
 }  // namespace slamhip

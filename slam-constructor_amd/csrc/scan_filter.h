@@ -95,8 +95,33 @@ int scan_stage_rows(const ScanTables &t, int n, const double *range, const doubl
                     int weighting, int k, const int *kept, const ScanStageRows &rows, double *w_viny,
                     ScanStageScratch &s, double *w_even, double *tot_w);
 
-// ---- K raw scans of one call (slamhip_matcher_process_raw_scan_batch): the filter and the rows per job, the scanners'
-// tables kept between calls, ONE arena in pinned memory laid out for one assembly launch.
+// What the assembly kernels are launched with (score_kernels.hip, scan_assemble_device.h).  The scan block `dst` (five
+// rows of `stride` doubles) from n kept points' ranges in pinned memory and the scanner's resident per-beam tables;
+// h_kept (raw index per point) null = every beam kept, h_factor null = 1.0, h_weight null = tab_viny[i] * sqrt(range)
+// where tab_viny is given, else w_even.
+struct ScanAssembleArgs {
+  const double *h_range;
+  const int *h_kept;
+  const double *h_factor, *h_weight;
+  const double *tab_cos, *tab_sin, *tab_viny;
+  double *dst;
+  size_t stride;
+  int n;
+  double w_even;
+};
+// ... with a sixth row, angle[kept[q]] from the scanner's angle plane in HBM (six rows of `stride` doubles at a.dst)
+struct ScanAssembleEachArgs {
+  ScanAssembleArgs a;
+  const double *tab_angle;
+};
+// the planes of a scanner's tables in HBM (ScanTablesDevice, hip_block.h); angle null where nobody keeps that plane
+struct ScanTablePlanes {
+  const double *cos_a, *sin_a, *viny_f, *angle;
+};
+
+// ---- K raw scans of one call (slamhip_matcher_process_raw_scan_batch, slamhip_matcher_m3rsm_match_each_raw): the filter
+// and the rows per job, the scanners' tables kept between calls, ONE arena in pinned memory laid out for one assembly
+// launch.
 struct RawBatchJob {
   int n;
   const double *range, *angle;
@@ -115,6 +140,7 @@ struct RawBatchPlan {
   int k = 0;       // points kept; 0: the job takes no part in the launches (nothing of it is in the arena)
   int table = -1;  // its scanner's slot
   int live = -1;   // its place among the jobs that kept something (its entry of the args table)
+  int weighting = 0;
   size_t kept_at = 0;                                                               // its kept list in RawBatchStage::kept
   size_t off_range = kNoRow, off_kept = kNoRow, off_factor = kNoRow, off_weight = kNoRow;  // bytes into the arena
   size_t dst_at = 0, stride = 0;  // its block of dst_rows rows, doubles into the batch's arena in HBM
@@ -142,6 +168,19 @@ struct RawBatchStage {
   int prepare(int n_jobs, const RawBatchJob *jobs, size_t args_entry_bytes, int dst_rows = 5);
   // Pass 2: the rows of every live job written into `arena` (arena_bytes long), weights and their sums made.
   int fill(const RawBatchJob *jobs, unsigned char *arena);
+  // Live job c's entry of the args table: its rows in `arena`, its scanner's planes, its block at dst_base + dst_at.
+  void entry(int c, const unsigned char *arena, const ScanTablePlanes &tab, double *dst_base, ScanAssembleArgs *out) const;
+  void entry(int c, const unsigned char *arena, const ScanTablePlanes &tab, double *dst_base, ScanAssembleEachArgs *out) const {
+    entry(c, arena, tab, dst_base, &out->a);
+    out->tab_angle = tab.angle;
+  }
+  // a raw scan as the C-ABI states it (slamhip_raw_scan), matched from `pose` on a map with window `win`
+  template <class Scan>
+  static RawBatchJob job_of(const Scan &s, const double pose[3], const ScanWindow &win) {
+    return RawBatchJob{s.n,     s.range, s.angle,     s.is_occ,    s.factor,          s.trig_mode, s.a_min,
+                       s.a_max, s.a_inc, s.skip_rate, s.max_range, s.bounded ? 1 : 0, s.weighting, {pose[0], pose[1], pose[2]},
+                       win};
+  }
 };
 
 }  // namespace slamhip

@@ -37,6 +37,7 @@
 
 
 #include <algorithm>
+#include <type_traits>
 
 #include "gm_score_device.h"
 #include "kernel_pick.h"
@@ -107,17 +108,22 @@ hipError_t launch_scan_pull(const double *h_src, double *d_dst, size_t n_doubles
 // sin, the viny weighting's angular factor: ScanTables, indexed by raw beam) is resident and gathered here.  One thread
 // per point of the scan block's stride; the block comes out as k_scan_pull leaves it (the rows' pads hold zeros
 // instead of whatever the staging buffer held), and the staging buffer is handed back the same way.
+// scan_assemble_store: the five rows of point q of a scan block, q below the stride -- what scan_assemble_point makes of
+// a kept point (the ONE statement of that arithmetic, scan_assemble_device.h, shared with the chain that assembles for
+// itself), zeros in the rows' pads.  The lone kernel's and the table kernel's stores.
+__device__ __forceinline__ void scan_assemble_store(const ScanAssembleArgs &a, int q) {
+  ScanPoint p{0.0, 0.0, 0.0, 0.0, 0.0};
+  if (q < a.n) p = scan_assemble_point(a, q);
+  a.dst[q] = p.range;
+  a.dst[a.stride + q] = p.cos_a;
+  a.dst[2 * a.stride + q] = p.sin_a;
+  a.dst[3 * a.stride + q] = p.weight;
+  a.dst[4 * a.stride + q] = p.factor;
+}
+
 __global__ __launch_bounds__(256) void k_scan_assemble(ScanAssembleArgs a, unsigned *counter, unsigned *h_flag, unsigned seq) {
   const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q < (int)a.stride) {
-    ScanPoint p{0.0, 0.0, 0.0, 0.0, 0.0};
-    if (q < a.n) p = scan_assemble_point(a, q);  // (scan_assemble_device.h: shared with the chain that assembles for itself)
-    a.dst[q] = p.range;
-    a.dst[a.stride + q] = p.cos_a;
-    a.dst[2 * a.stride + q] = p.sin_a;
-    a.dst[3 * a.stride + q] = p.weight;
-    a.dst[4 * a.stride + q] = p.factor;
-  }
+  if (q < (int)a.stride) scan_assemble_store(a, q);
   __syncthreads();  // (every load of the workgroup from the staging buffer has returned: its values went into stores)
   if (threadIdx.x == 0) {
     const unsigned before = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -134,59 +140,37 @@ hipError_t launch_scan_assemble(const ScanAssembleArgs &a, unsigned *counter, un
   return hipGetLastError();
 }
 
-// K raw scans of one call (slamhip_matcher_process_raw_scan_batch): grid.y = job, grid.x over the widest job's block
-// stride.  `table` lies in the call's pinned arena next to the rows it points at: every thread reads its job's entry (a
-// uniform address: scalar loads) and does what k_scan_assemble does for a lone scan -- scan_assemble_point is the one
-// statement of the arithmetic, the pads of the five rows come out zero.  Plain loads and stores, 8 bytes per thread
-// and row as in k_scan_assemble; nobody is told that the arena has been read: the host refills it only after the
-// chains launched behind this kernel have reported their results.
-__global__ __launch_bounds__(256) void k_scan_assemble_batch(const ScanAssembleArgs *__restrict__ table) {
-  const ScanAssembleArgs a = table[blockIdx.y];
+// K raw scans of one call (RawDeviceStage::assemble: slamhip_matcher_process_raw_scan_batch with Entry =
+// ScanAssembleArgs, slamhip_matcher_m3rsm_match_each_raw with ScanAssembleEachArgs): grid.y = job, grid.x over the
+// widest job's block stride.  `table` lies in the call's pinned arena next to the rows it points at: every thread reads
+// its job's entry (a uniform address: scalar loads) and does what k_scan_assemble does for a lone scan.  The six-row
+// entry adds a SIXTH row, the kept points' angles -- angle[kept[q]] from the angle plane kept with the scanner's table --
+// which SLAMHIP_POSE_TRIG_RAW_EXACT tabulates its beam directions from (PyrSource::angle); its pad comes out zero too and
+// the writes stay inside [dst, dst + 6 * stride).  Plain loads and stores, 8 bytes per thread and row; nobody is told
+// that the arena has been read: the host refills it only after what was launched behind this kernel has reported its
+// results.
+__device__ __forceinline__ const ScanAssembleArgs &five_rows_of(const ScanAssembleArgs &e) { return e; }
+__device__ __forceinline__ const ScanAssembleArgs &five_rows_of(const ScanAssembleEachArgs &e) { return e.a; }
+
+template <class Entry>
+__global__ __launch_bounds__(256) void k_scan_assemble_table(const Entry *__restrict__ table) {
+  const Entry e = table[blockIdx.y];
+  const ScanAssembleArgs &a = five_rows_of(e);
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= (int)a.stride) return;
-  ScanPoint p{0.0, 0.0, 0.0, 0.0, 0.0};
-  if (q < a.n) p = scan_assemble_point(a, q);
-  a.dst[q] = p.range;
-  a.dst[a.stride + q] = p.cos_a;
-  a.dst[2 * a.stride + q] = p.sin_a;
-  a.dst[3 * a.stride + q] = p.weight;
-  a.dst[4 * a.stride + q] = p.factor;
+  scan_assemble_store(a, q);
+  if constexpr (std::is_same<Entry, ScanAssembleEachArgs>::value)
+    a.dst[5 * a.stride + q] = q < a.n ? e.tab_angle[a.h_kept ? a.h_kept[q] : q] : 0.0;
 }
 
-hipError_t launch_scan_assemble_batch(const ScanAssembleArgs *table, int n_jobs, int max_stride, hipStream_t stream) {
+template <class Entry>
+hipError_t launch_scan_assemble_table(const Entry *table, int n_jobs, int max_stride, hipStream_t stream) {
   if (n_jobs <= 0 || max_stride <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_scan_assemble_batch, dim3((max_stride + 255) / 256, n_jobs), dim3(256), 0, stream, table);
+  hipLaunchKernelGGL(k_scan_assemble_table<Entry>, dim3((max_stride + 255) / 256, n_jobs), dim3(256), 0, stream, table);
   return hipGetLastError();
 }
-
-// K raw scans of one slamhip_matcher_m3rsm_match_each_raw call: k_scan_assemble_batch's five rows by the same per-element
-// expressions (scan_assemble_point) and a SIXTH row, the kept points' angles -- angle[kept[q]] from the angle plane
-// kept with the scanner's table -- which SLAMHIP_POSE_TRIG_RAW_EXACT tabulates its beam directions from
-// (PyrSource::angle).  The pads of all six rows come out zero.  Writes stay inside [dst, dst + 6 * stride).
-__global__ __launch_bounds__(256) void k_scan_assemble_each(const ScanAssembleEachArgs *__restrict__ table) {
-  const ScanAssembleEachArgs e = table[blockIdx.y];
-  const ScanAssembleArgs &a = e.a;
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= (int)a.stride) return;
-  ScanPoint p{0.0, 0.0, 0.0, 0.0, 0.0};
-  double angle = 0.0;
-  if (q < a.n) {
-    p = scan_assemble_point(a, q);
-    angle = e.tab_angle[a.h_kept ? a.h_kept[q] : q];
-  }
-  a.dst[q] = p.range;
-  a.dst[a.stride + q] = p.cos_a;
-  a.dst[2 * a.stride + q] = p.sin_a;
-  a.dst[3 * a.stride + q] = p.weight;
-  a.dst[4 * a.stride + q] = p.factor;
-  a.dst[5 * a.stride + q] = angle;
-}
-
-hipError_t launch_scan_assemble_each(const ScanAssembleEachArgs *table, int n_jobs, int max_stride, hipStream_t stream) {
-  if (n_jobs <= 0 || max_stride <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_scan_assemble_each, dim3((max_stride + 255) / 256, n_jobs), dim3(256), 0, stream, table);
-  return hipGetLastError();
-}
+template hipError_t launch_scan_assemble_table(const ScanAssembleArgs *, int, int, hipStream_t);
+template hipError_t launch_scan_assemble_table(const ScanAssembleEachArgs *, int, int, hipStream_t);
 
 // The same for a launch's small argument blocks (job tables, initial poses, a zeroed counter): ONE pull of the pinned
 // block in front of the launch instead of several hipMemcpyAsync / hipMemsetAsync calls (each ~6 us of host time and

@@ -809,7 +809,6 @@ int slamhip_ctx_destroy(slamhip_ctx *ctx) {
     if (m.d_prob) hipFree(m.d_prob);
   }
   if (ctx->d_scan) hipFree(ctx->d_scan);
-  if (ctx->d_scan_tab) hipFree(ctx->d_scan_tab);
   if (ctx->d_scan_angle) hipFree(ctx->d_scan_angle);
   if (ctx->d_exact_trig) hipFree(ctx->d_exact_trig);
   if (ctx->d_gm_exact_cache) hipFree(ctx->d_gm_exact_cache);
@@ -1337,23 +1336,9 @@ int slamhip_scan_weights(int kind, int n, const double *range, const double *ang
 // the context's stream, behind every assembly that still reads the old ones.  Only when scan_prep has recomputed them
 // -- a scanner's angles do not change --, so the call waits for the copies instead of keeping the sources alive.
 static int scan_tables_upload(slamhip_ctx *ctx) {
-  const slamhip_ctx::ScanPrep &sp = ctx->scan_prep;
-  const int n = (int)sp.cos_a.size();
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  if (n > ctx->scan_tab_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_scan_tab) hipFree(ctx->d_scan_tab);
-    ctx->d_scan_tab = nullptr;
-    ctx->scan_tab_cap = 0;
-    int cap = 2048;
-    while (cap < n) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&ctx->d_scan_tab, sizeof(double) * 3 * cap));
-    ctx->scan_tab_cap = cap;
-  }
-  const size_t cap = (size_t)ctx->scan_tab_cap, bytes = sizeof(double) * n;
-  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_scan_tab, sp.cos_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_scan_tab + cap, sp.sin_a.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_scan_tab + 2 * cap, sp.viny_f.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  const int rc = ctx->scan_tab.upload(ctx->stream, ctx->scan_prep, 3);
+  if (rc) return rc;
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   ++ctx->scan_tab_uploads;
   return SLAMHIP_OK;
@@ -1476,9 +1461,9 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
   as.h_kept = k == n ? nullptr : rows.kept;
   as.h_factor = factor ? rows.factor : nullptr;
   as.h_weight = weighting == 2 ? rows.weight : nullptr;
-  if (weighting == 1) as.tab_viny = ctx->d_scan_tab + 2 * (size_t)ctx->scan_tab_cap;
-  as.tab_cos = ctx->d_scan_tab;
-  as.tab_sin = ctx->d_scan_tab + (size_t)ctx->scan_tab_cap;
+  if (weighting == 1) as.tab_viny = ctx->scan_tab.viny();
+  as.tab_cos = ctx->scan_tab.cos();
+  as.tab_sin = ctx->scan_tab.sin();
   as.dst = ctx->d_scan;
   as.stride = c;
   as.n = k;

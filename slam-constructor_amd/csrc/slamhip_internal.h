@@ -224,32 +224,15 @@ hipError_t launch_stall(int ms, hipStream_t stream);  // testing
 hipError_t launch_block_pull(const void *h_src, void *d_dst, size_t bytes, hipStream_t stream);
 hipError_t launch_scan_pull(const double *h_src, double *d_dst, size_t n_doubles, unsigned *counter, unsigned *h_flag,
                             unsigned seq, hipStream_t stream);
-// k_scan_assemble: the scan block `dst` (five rows of `stride` doubles) from n kept points' ranges in pinned memory and
-// the context's resident per-beam tables; h_kept (raw index per point) null = every beam kept, h_factor null = 1.0,
-// h_weight null = tab_viny[i] * sqrt(range) where tab_viny is given, else w_even.  *h_flag = seq once the pinned
-// arrays have been read.
-struct ScanAssembleArgs {
-  const double *h_range;
-  const int *h_kept;
-  const double *h_factor, *h_weight;
-  const double *tab_cos, *tab_sin, *tab_viny;
-  double *dst;
-  size_t stride;
-  int n;
-  double w_even;
-};
+// k_scan_assemble: one scan block from ScanAssembleArgs (scan_filter.h) and the context's resident per-beam tables.
+// *h_flag = seq once the pinned arrays have been read.
 hipError_t launch_scan_assemble(const ScanAssembleArgs &a, unsigned *counter, unsigned *h_flag, unsigned seq,
                                 hipStream_t stream);
-// k_scan_assemble_batch: n_jobs scan blocks in one launch, job c from table[c] (a table in pinned memory; grid.y = job,
-// max_stride = the widest block's stride)
-hipError_t launch_scan_assemble_batch(const ScanAssembleArgs *table, int n_jobs, int max_stride, hipStream_t stream);
-// k_scan_assemble_each: the same with a sixth row, angle[kept[q]] from the scanner's angle plane in HBM (six rows of
-// `stride` doubles at a.dst)
-struct ScanAssembleEachArgs {
-  ScanAssembleArgs a;
-  const double *tab_angle;
-};
-hipError_t launch_scan_assemble_each(const ScanAssembleEachArgs *table, int n_jobs, int max_stride, hipStream_t stream);
+// k_scan_assemble_table: n_jobs scan blocks in one launch, job c from table[c] (a table in pinned memory; grid.y = job,
+// max_stride = the widest block's stride).  Entry: ScanAssembleArgs (five rows) or ScanAssembleEachArgs (a sixth row,
+// the kept points' angles).
+template <class Entry>
+hipError_t launch_scan_assemble_table(const Entry *table, int n_jobs, int max_stride, hipStream_t stream);
 // (both uploads write the host's stride_host doubles of a cell and leave the rest of it alone -- a GMAPPING cell's pad)
 hipError_t launch_scatter_cells(double *payload, int pitch, int cell_dbl, int stride_host, int n,
                                 const int *d_coords, const double *d_vals, hipStream_t stream);
@@ -354,6 +337,8 @@ hipError_t refuse_launch(const char *why);  // hipErrorInvalidValue; hip_fail ap
     if (_e != hipSuccess) return slamhip::hip_fail(_e, #expr);     \
   } while (0)
 
+#include "hip_block.h"
+
 struct slamhip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -398,10 +383,9 @@ struct slamhip_ctx {
                                         // SLAMHIP_TRIG_RAW on a bounded map
     slamhip::ScanStageScratch stage;    // ... the filtered scan's angles / ranges / weights where the weighting asks
   } scan_prep;
-  // ... and the same three per-beam arrays resident in HBM (cos | sin | viny_f, scan_tab_cap doubles each), where
-  // k_scan_assemble gathers them: uploaded when scan_prep recomputes, never by a context that is not given raw scans
-  double *d_scan_tab = nullptr;
-  int scan_tab_cap = 0;
+  // ... and the same three per-beam arrays resident in HBM (cos | sin | viny_f), where k_scan_assemble gathers them:
+  // uploaded when scan_prep recomputes, never by a context that is not given raw scans
+  slamhip::ScanTablesDevice scan_tab;
   long long scan_tab_uploads = 0;
   std::vector<double> h_weight, h_factor;  // host copies for GMapping carry-in fix-ups
   // The raw scan between its two halves (slamhip::scan_filter_stage / scan_assemble_now).  `active`: the current scan

@@ -81,7 +81,7 @@ static RawBatchJob view(const Job &j) {
   return r;
 }
 
-constexpr size_t kEntry = 88;  // (any entry size: the args table is the caller's)
+constexpr size_t kEntry = sizeof(ScanAssembleArgs);
 
 // one job of a prepared and filled stage against the public host functions
 static void check_job(const RawBatchStage &st, int c, const Job &j, const unsigned char *arena,
@@ -166,31 +166,84 @@ static void check_job(const RawBatchStage &st, int c, const Job &j, const unsign
   REQUIRE(p.stride >= (size_t)k && p.stride % 8 == 0 && p.stride < (size_t)k + 8, "job %d: stride", c);
 }
 
-static void check_stage(RawBatchStage &st, const std::vector<Job> &jobs) {
+static const ScanAssembleArgs &five_rows_of(const ScanAssembleArgs &e) { return e; }
+static const ScanAssembleArgs &five_rows_of(const ScanAssembleEachArgs &e) { return e.a; }
+static const double *angle_plane_of(const ScanAssembleArgs &) { return nullptr; }
+static const double *angle_plane_of(const ScanAssembleEachArgs &e) { return e.tab_angle; }
+
+// live job c's entry of the args table, as RawBatchStage::entry builds it over the filled arena, a scanner's table of
+// four planes of `cap` doubles at `tab` and the arena in HBM at `dst_base`
+template <class Entry>
+static void check_entry(const RawBatchStage &st, int c, const Job &j, const unsigned char *arena, const double *tab, size_t cap,
+                        double *dst_base, int rows, std::vector<std::pair<size_t, size_t>> &blocks) {
+  const RawBatchPlan &p = st.plan[c];
+  const size_t k = (size_t)p.k, n = j.range.size();
+  Entry e;
+  std::memset(&e, 0xa5, sizeof e);
+  st.entry(c, arena, ScanTablePlanes{tab, tab + cap, tab + 2 * cap, tab + 3 * cap}, dst_base, &e);
+  const ScanAssembleArgs &a = five_rows_of(e);
+  const size_t table_end = sizeof(Entry) * (size_t)st.n_live;
+  auto pinned = [&](const void *ptr, size_t elem, const char *what) {
+    const unsigned char *b = static_cast<const unsigned char *>(ptr);
+    REQUIRE((uintptr_t)b % 16 == 0, "job %d: %s row is not 16-byte aligned", c, what);
+    REQUIRE(b >= arena + table_end && b + elem * k <= arena + st.arena_bytes, "job %d: %s row leaves the arena", c, what);
+  };
+  REQUIRE(a.h_range != nullptr, "job %d: no range row", c);
+  pinned(a.h_range, 8, "range");
+  for (size_t q = 0; q < k; ++q)
+    REQUIRE(same_bytes(&a.h_range[q], &j.range[st.kept[p.kept_at + q]], 8), "job %d: h_range[%zu]", c, q);
+  REQUIRE((a.h_kept == nullptr) == (k == n), "job %d: kept row of %zu of %zu beams", c, k, n);
+  if (a.h_kept) pinned(a.h_kept, 4, "kept");
+  REQUIRE((a.h_factor == nullptr) == !j.has_factor, "job %d: factor row", c);
+  if (a.h_factor) pinned(a.h_factor, 8, "factor");
+  REQUIRE((a.h_weight != nullptr) == (j.weighting == 2), "job %d: weight row under weighting %d", c, j.weighting);
+  if (a.h_weight) pinned(a.h_weight, 8, "weight");
+  REQUIRE(a.tab_viny == (j.weighting == 1 ? tab + 2 * cap : nullptr), "job %d: viny plane under weighting %d", c, j.weighting);
+  REQUIRE(a.tab_cos == tab && a.tab_sin == tab + cap, "job %d: cos / sin planes", c);
+  REQUIRE(angle_plane_of(e) == (rows == 6 ? tab + 3 * cap : nullptr), "job %d: angle plane", c);
+  REQUIRE(a.n == p.k && a.stride == p.stride && same_bytes(&a.w_even, &p.w_even, 8), "job %d: n, stride, w_even", c);
+  REQUIRE(a.dst >= dst_base && (size_t)(a.dst - dst_base) + (size_t)rows * a.stride <= st.dst_doubles, "job %d: block leaves the arena in HBM", c);
+  blocks.push_back({(size_t)(a.dst - dst_base), (size_t)(a.dst - dst_base) + (size_t)rows * a.stride});
+}
+
+template <class Entry>
+static void check_stage_rows(RawBatchStage &st, const std::vector<Job> &jobs) {
+  constexpr int rows = sizeof(Entry) == sizeof(ScanAssembleEachArgs) ? 6 : 5;
   std::vector<RawBatchJob> in;
   for (const Job &j : jobs) in.push_back(view(j));
-  REQUIRE(st.prepare((int)in.size(), in.data(), kEntry) == kScanOk, "prepare");
+  REQUIRE(st.prepare((int)in.size(), in.data(), sizeof(Entry), rows) == kScanOk, "prepare");
   // exactly arena_bytes on the heap: the sanitizer sees a byte too many
   unsigned char *arena = static_cast<unsigned char *>(std::malloc(st.arena_bytes ? st.arena_bytes : 1));
   std::memset(arena, 0xa5, st.arena_bytes);
   REQUIRE(st.fill(in.data(), arena) == kScanOk, "fill");
-  std::vector<std::pair<size_t, size_t>> spans;
-  spans.push_back({0, kEntry * (size_t)st.n_live});  // the args table
+  std::vector<std::pair<size_t, size_t>> spans, blocks;
+  spans.push_back({0, sizeof(Entry) * (size_t)st.n_live});  // the args table
+  const size_t cap = 512;
+  std::vector<double> tab(4 * cap), hbm(st.dst_doubles ? st.dst_doubles : 1);
   size_t dst = 0;
   int live = 0;
   for (int c = 0; c < (int)jobs.size(); ++c) {
     check_job(st, c, jobs[c], arena, spans);
+    REQUIRE(st.plan[c].weighting == jobs[c].weighting, "job %d: the plan's weighting", c);
     if (st.plan[c].k > 0) {
       REQUIRE(st.plan[c].live == live++, "live places in job order");
       REQUIRE(st.plan[c].dst_at == dst, "job %d: block at %zu, the blocks before end at %zu", c, st.plan[c].dst_at, dst);
-      dst += 5 * st.plan[c].stride;
+      dst += (size_t)rows * st.plan[c].stride;
+      check_entry<Entry>(st, c, jobs[c], arena, tab.data(), cap, hbm.data(), rows, blocks);
     }
   }
   REQUIRE(dst == st.dst_doubles && live == st.n_live, "arena in HBM: %zu doubles, the blocks need %zu", st.dst_doubles, dst);
-  for (size_t x = 0; x < spans.size(); ++x)
-    for (size_t y = x + 1; y < spans.size(); ++y)
-      REQUIRE(spans[x].second <= spans[y].first || spans[y].second <= spans[x].first, "rows %zu and %zu overlap", x, y);
+  for (const auto *v : {&spans, &blocks})
+    for (size_t x = 0; x < v->size(); ++x)
+      for (size_t y = x + 1; y < v->size(); ++y)
+        REQUIRE((*v)[x].second <= (*v)[y].first || (*v)[y].second <= (*v)[x].first, "rows / blocks %zu and %zu overlap", x, y);
   std::free(arena);
+}
+
+// (six rows first: the stage is left as a five-row call leaves it, which is what the callers look at)
+static void check_stage(RawBatchStage &st, const std::vector<Job> &jobs) {
+  check_stage_rows<ScanAssembleEachArgs>(st, jobs);
+  check_stage_rows<ScanAssembleArgs>(st, jobs);
 }
 
 int main() {
@@ -311,6 +364,24 @@ int main() {
     for (int q = 0; q < 70; ++q) wide.push_back(random_job(&many[q]));
     check_stage(st, wide);
     n_jobs += 70;
+  }
+  {
+    // ---- a job from the C-ABI's raw scan, a pose and a window: every field lands in its place
+    Job j = random_job(&scanners[1]);
+    j.has_occ = j.has_factor = true;
+    j.skip_rate = 3;
+    j.bounded = 7;  // (any non-zero value means bounded)
+    const RawBatchJob want = view(j);
+    const slamhip_raw_scan raw{want.n,     want.range, want.angle,     want.is_occ,    want.factor, want.trig_mode, want.a_min,
+                               want.a_max, want.a_inc, want.skip_rate, want.max_range, j.bounded,   want.weighting};
+    const RawBatchJob got = RawBatchStage::job_of(raw, j.pose, j.win);
+    REQUIRE(got.n == want.n && got.range == want.range && got.angle == want.angle && got.is_occ == want.is_occ &&
+                got.factor == want.factor && got.trig_mode == want.trig_mode && got.skip_rate == 3u && got.bounded == 1 &&
+                got.weighting == want.weighting, "job_of: the scan's fields");
+    REQUIRE(same_bytes(&got.a_min, &want.a_min, 8) && same_bytes(&got.a_max, &want.a_max, 8) && same_bytes(&got.a_inc, &want.a_inc, 8) &&
+                same_bytes(&got.max_range, &want.max_range, 8) && same_bytes(got.pose, want.pose, 24), "job_of: the doubles");
+    REQUIRE(got.win.scale == j.win.scale && got.win.origin_x == j.win.origin_x && got.win.origin_y == j.win.origin_y &&
+                got.win.width == j.win.width && got.win.height == j.win.height, "job_of: the window");
   }
   {
     // ---- errors: found in pass 1, with the lone call's texts

@@ -3,6 +3,7 @@
 // into this program; tests/test_pyr_refresh_plan_host.py runs it plainly and under -fsanitize=address,undefined, where
 // the pinned arena and the arena in HBM are heap blocks of exactly arena_bytes / dst_doubles, written the way the
 // assembly kernel writes them.
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -97,9 +98,36 @@ static void run(int rows) {
   CHECK(st.fill(jobs.data(), arena.data()) == kScanOk);
   std::vector<double> dst(st.dst_doubles, 0.0);
   std::vector<unsigned char> written(st.dst_doubles, 0);
+  const size_t cap = 1024;
+  std::vector<double> tab(4 * cap);
+  const ScanTablePlanes planes{tab.data(), tab.data() + cap, tab.data() + 2 * cap, tab.data() + 3 * cap};
   for (int c = 0; c < 4; ++c) {
     const RawBatchPlan &p = st.plan[c];
     if (p.k == 0) continue;
+    // the job's entry of the args table, as RawBatchStage::entry builds it: the kernel's view of the same rows and block
+    ScanAssembleEachArgs e;
+    std::memset(&e, 0xee, sizeof e);
+    if (rows == 6) {
+      st.entry(c, arena.data(), planes, dst.data(), &e);
+      CHECK(e.tab_angle == planes.angle);
+    } else {
+      st.entry(c, arena.data(), planes, dst.data(), &e.a);
+    }
+    const ScanAssembleArgs &a = e.a;
+    CHECK(a.h_range == reinterpret_cast<const double *>(arena.data() + p.off_range) && (uintptr_t)a.h_range % 16 == 0);
+    CHECK((a.h_kept == nullptr) == (p.k == jobs[c].n) && (uintptr_t)a.h_kept % 16 == 0);
+    CHECK((a.h_factor == nullptr) == (jobs[c].factor == nullptr) && (uintptr_t)a.h_factor % 16 == 0);
+    CHECK((a.h_weight != nullptr) == (jobs[c].weighting == 2) && (uintptr_t)a.h_weight % 16 == 0);
+    for (const void *row : {(const void *)a.h_kept, (const void *)a.h_factor, (const void *)a.h_weight}) {
+      const unsigned char *b = static_cast<const unsigned char *>(row);
+      const size_t elem = row == a.h_kept ? sizeof(int) : sizeof(double);
+      if (b) CHECK(b >= arena.data() + kEntry * 3 && b + elem * p.k <= arena.data() + st.arena_bytes);
+    }
+    for (int q = 0; q < p.k; ++q) CHECK(std::memcmp(&a.h_range[q], &reqs[c].range[st.kept[p.kept_at + q]], 8) == 0);
+    CHECK(a.tab_cos == planes.cos_a && a.tab_sin == planes.sin_a && a.tab_viny == (jobs[c].weighting == 1 ? planes.viny_f : nullptr));
+    CHECK(a.dst == dst.data() + p.dst_at && a.stride == p.stride && a.n == p.k && a.w_even == p.w_even);
+    CHECK(p.dst_at + (size_t)rows * a.stride <= st.dst_doubles);  // (disjoint: the `written` marks below)
+    CHECK(p.weighting == jobs[c].weighting);
     CHECK(p.off_range >= kEntry * 3 && p.off_range % 16 == 0 && p.off_range + sizeof(double) * p.k <= st.arena_bytes);
     const double *h_range = reinterpret_cast<const double *>(arena.data() + p.off_range);
     const int *h_kept = p.off_kept == kNoRow ? nullptr : reinterpret_cast<const int *>(arena.data() + p.off_kept);

@@ -1,5 +1,5 @@
 """GPU suite (-m gpu): K RAW scans in, K multi-resolution matches (slamhip_matcher_m3rsm_match_each_raw: the host filter per
-request through RawBatchStage, ONE k_scan_assemble_each launch for all six-row blocks, the lock-step searches of
+request through RawBatchStage, ONE k_scan_assemble_table launch for all six-row blocks, the lock-step searches of
 m3rsm_match_each over those blocks) against a lone slamhip_matcher_process_raw_scan per request on a matcher over the
 request's pyramid -- delta, probability, kept count, committed calls and counters, bit for bit -- and against the stored
 route (host filter + scan_store (+ angles) + m3rsm_match_each).  Scenes as tests/test_gpu_m3rsm_many.py::kernel_scene sets
@@ -371,3 +371,103 @@ def test_a_request_far_from_the_world_origin(pkg, ctx, form):
     finally:
         far.close()
         ctx.map_release(60)
+
+
+# ---- 8. the one device stage under both of its users ------------------------------------------------------------------
+HC_PRM = [24, 0.1, 0.1]
+
+
+def route_matcher(pkg, ctx, sc, route):
+    """the chains' batch (an HC matcher over map 0) or the fleet call (a BF_M3RSM matcher over pyramid 0, built on map 0)"""
+    if route == "chain":
+        return pkg.Matcher(ctx, "HC", pkg.spe_cfg(), HC_PRM)
+    return matcher(pkg, ctx, sc, cfg_of(pkg, sc.s.oie, "default"), 0, SHAPES[2])
+
+
+def route_lone(pkg, ctx, sc, route, job):
+    """the job's lone raw call on a fresh matcher of the route's kind, and the context's scan block after it"""
+    m = route_matcher(pkg, ctx, sc, route)
+    r = lone_raw(pkg, m, job, trace=False)
+    out = dict(delta=r["delta"], prob=r["prob"], kept=r["kept"], block=download(ctx) if r["kept"] else None)
+    m.close()
+    return out
+
+
+def route_call(route, m, jobs):
+    got = m.process_raw_scan_batch(jobs) if route == "chain" else m.m3rsm_match_each_raw(jobs)
+    if route == "chain":
+        assert all(m.batch_stats(c)["on_device_chain"] for c in range(len(jobs)))  # (nobody went through the lone call)
+    return got
+
+
+def route_block(route, m, k):
+    """job k's block of the last call: (five rows, the sixth row or None)"""
+    return (m.batch_scan_download(k), None) if route == "chain" else m.m3rsm_each_scan_download(k)
+
+
+def same_result(got, want):
+    return (got["kept"] == want["kept"] and np.array_equal(bits(got["delta"]), bits(want["delta"]))
+            and np.array_equal(bits([got["prob"]]), bits([want["prob"]])))
+
+
+@pytest.mark.parametrize("weighting", WEIGHTINGS)
+def test_both_routes_write_the_same_block(pkg, ctx, sc, weighting):
+    """three raw scans on map 0 whose kept counts lie around a 256-thread workgroup (and the stride's rounding to 8
+    doubles: 256, 256, 264): one with a kept list from skip_rate 2, one of the raw provider, one with factors"""
+    rq = [request(pkg, sc, 0, 600, 255, (0.21, -0.33, 0.4), "cached", weighting, 21, skip_rate=2),
+          request(pkg, sc, 0, 300, 256, (0.1, -0.1, 1.0), "raw", weighting, 22),
+          request(pkg, sc, 0, 300, 257, (0.3, -0.2, 2.9), "cached", weighting, 23, factor=True)]
+    assert rq[0]["others_drop"] == 300 and rq[1]["others_drop"] == rq[2]["others_drop"] == 0
+    hc, m = route_matcher(pkg, ctx, sc, "chain"), route_matcher(pkg, ctx, sc, "fleet")
+    try:
+        chain, fleet = route_call("chain", hc, rq), route_call("fleet", m, rq)
+        assert [g["kept"] for g in chain] == [g["kept"] for g in fleet] == [255, 256, 257]
+        for k, j in enumerate(rq):
+            five, _ = route_block("chain", hc, k)
+            rows, angle = route_block("fleet", m, k)
+            assert five.shape == rows.shape == (5, 255 + k)
+            np.testing.assert_array_equal(bits(rows), bits(five), err_msg="rows 0-4 of job %d" % k)
+            np.testing.assert_array_equal(bits(angle), bits(j["angle"][j["is_occ"] == 1]), err_msg="sixth row of job %d" % k)
+            np.testing.assert_array_equal(bits(rows[0]), bits(j["range"][j["is_occ"] == 1]))
+    finally:
+        hc.close()
+        m.close()
+
+
+@pytest.mark.parametrize("route", ["chain", "fleet"])
+def test_arenas_that_regrow_between_calls(pkg, ctx, sc, route):
+    """a small call, one that outgrows both arenas' floors (65536 bytes pinned, 16384 doubles in HBM), the small one again"""
+    rows = 5 if route == "chain" else 6
+    rs = np.random.RandomState(31)
+    pose = lambda: np.array([*rs.uniform(-0.3, 0.3, 2), rs.uniform(-3.0, 3.0)])  # noqa: E731
+    small = [request(pkg, sc, 0, 300, 40, pose(), "cached", "viny", 41, factor=True),
+             request(pkg, sc, 0, 300, 65, pose(), "cached", "ahr", 42)]
+    large = [request(pkg, sc, 0, 900, 891 + i, pose(), "cached", WEIGHTINGS[i % 3], 50 + i, factor=True) for i in range(10)]
+    want_small = [route_lone(pkg, ctx, sc, route, j) for j in small]
+    want_large = [route_lone(pkg, ctx, sc, route, j) for j in large]
+    m = route_matcher(pkg, ctx, sc, route)
+    try:
+        first = route_call(route, m, small)
+        second = route_call(route, m, large)
+        block0 = route_block(route, m, 0)
+        third = route_call(route, m, small)
+        # the second call did outgrow what the first one had allocated, the first one did not
+        for got, grows in ((first, False), (second, True)):
+            kept = np.array([g["kept"] for g in got])
+            assert (8 * kept.sum() > 65536) == grows, kept
+            assert (rows * ((kept + 7) & ~7).sum() > 16384) == grows, kept
+        for got, want in ((first, want_small), (second, want_large), (third, want_small)):
+            assert [g["kept"] for g in got] == [w["kept"] for w in want] and all(w["kept"] > 0 for w in want)
+            for k, (g, w) in enumerate(zip(got, want)):
+                assert same_result(g, w), (k, g, w)
+        for g, f in zip(third, first):
+            assert same_result(g, f)
+        # after the second call job 0's block is that call's: the lone call's scan block, and the kept angles behind it
+        np.testing.assert_array_equal(block0[0].view(np.uint64), want_large[0]["block"])
+        if route == "fleet":
+            np.testing.assert_array_equal(bits(block0[1]), bits(large[0]["angle"][large[0]["is_occ"] == 1]))
+        # ... and after the third, that one's (the arenas stay as large as they have grown)
+        for k, w in enumerate(want_small):
+            np.testing.assert_array_equal(route_block(route, m, k)[0].view(np.uint64), w["block"])
+    finally:
+        m.close()

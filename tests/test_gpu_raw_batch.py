@@ -1,5 +1,5 @@
 """GPU suite: slamhip_matcher_process_raw_scan_batch -- K raw scans in, K matches in the shared launches, the scans
-assembled by ONE launch of k_scan_assemble_batch (csrc/score_kernels.hip) from the call's pinned arena and the
+assembled by ONE launch of k_scan_assemble_table (csrc/score_kernels.hip) from the call's pinned arena and the
 scanners' resident tables.  No tolerance anywhere: every job must be, bit for bit, (i) a lone
 slamhip_matcher_process_raw_scan on a fresh matcher and (ii) slamhip_matcher_process_scan_batch fed with the public host
 filter's outputs -- pose delta, probability, points kept, scorer calls, observer trace, and the scan block in HBM.
