@@ -639,6 +639,36 @@ int slamhip_score_poses(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg
 /* Same with device-resident poses/scores, asynchronous on the context stream (sweep mode) */
 int slamhip_score_poses_device(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg,
                                int n_poses, const double *d_poses_xyt, double *d_scores_out);
+/* The pose sets of K jobs -- K robots, K map hypotheses under one scan, K heat maps -- in ONE call: job k scores its
+ * poses over its own map and its own scan, and its n_poses scores land in scores_out behind those of the jobs before it.
+ * Job k's scores are BIT-EQUAL to slamhip_scan_select of its slot followed by slamhip_score_poses of its map and
+ * poses, in every mode that call has (NaN where the scan's weights add up to 0); they depend neither on the other jobs
+ * nor on the route the call takes.  The context's current scan and its angles are what they were before the call.
+ *   Shared launches: SLAMHIP_OOPE_OBSTACLE / _MAX / _MEAN / _OVERLAP, both OIEs, OCC / TBM / CREDIBILIST maps (through
+ *   the probability plane wherever the lone call goes through it), both sum orders, pose_trig DEVICE and HOST; maps of
+ *   any size, scale and origin and scans of any length per job.  One scoring launch per call whatever K; with
+ *   SLAMHIP_SUM_SEQUENTIAL a beam-order summing launch behind it.  The jobs' views must share one effective cell model
+ *   and OIE (a belief map scored through its plane counts as OCC under the occupancy OIE): else SLAMHIP_ERR_INVALID.
+ *   Lone route (select + score, job after job in job order, the current scan put back afterwards):
+ *   SLAMHIP_OOPE_GMAPPING (its run cache sees ONE call sequence: the cache ends as the lone calls leave it),
+ *   SLAMHIP_POSE_TRIG_RAW_EXACT, a call with a single job that has poses, and a SLAMHIP_SUM_SEQUENTIAL call whose terms
+ *   -- the sum of n_poses x scan points over the jobs -- exceed 2^24 doubles (128 MiB of scratch).
+ * n_jobs 0 and jobs with n_poses 0 are legal and score nothing (such a job's map and slot are not looked at).  Errors
+ * are found before anything is staged or launched and leave scores_out, the stats and the current scan as they were:
+ * null arguments, an unknown map, whatever slamhip_score_poses refuses for the configuration, a slot out of range
+ * (SLAMHIP_ERR_INVALID); a slot nothing is stored in, scan_slot -1 without a current scan (SLAMHIP_ERR_STATE). */
+typedef struct {
+  int map_id;
+  int scan_slot;           /* 0..4095: a stored scan (slamhip_scan_store); -1: the context's current scan */
+  int n_poses;             /* >= 0 */
+  const double *poses_xyt; /* n_poses x (x, y, theta), host */
+} slamhip_score_job;
+int slamhip_score_poses_batch(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_jobs, const slamhip_score_job *jobs,
+                              double *scores_out /* sum of n_poses, job after job */);
+/* of the last slamhip_score_poses_batch that was not refused: jobs with poses that went through the shared launches,
+ * those that went through the lone call, and the kernels the shared route launched to score and sum (1, or 2 with
+ * SLAMHIP_SUM_SEQUENTIAL; 0 where every job went lone) */
+int slamhip_score_poses_batch_stats(slamhip_ctx *ctx, int *jobs_in_shared_launches, int *jobs_lone, int *launches);
 /* GMapping OOPE run-cache state carried between calls (gmapping_occupancy_observation_pe.h:21-24,
  * 36-37,43-44): {cell x, cell y} + cached probability (-1 = empty).  Used by score_poses when
  * cfg->oope == SLAMHIP_OOPE_GMAPPING: poses are scored as ONE call sequence in the given order. */

@@ -77,7 +77,8 @@ slamhip_matcher_set_bf_streams slamhip_matcher_set_bf_job_streams slamhip_matche
 slamhip_map_append_scan_batch slamhip_map_update_batch_stats slamhip_map_update_batch_tables
 slamhip_gmapping_particle_generate_scans slamhip_scan_generate_host_tiled
 slamhip_pyramid_refresh_batch slamhip_pyramid_refresh_batch_stats
-slamhip_matcher_m3rsm_match_each_raw slamhip_matcher_m3rsm_each_scan_download""".split()
+slamhip_matcher_m3rsm_match_each_raw slamhip_matcher_m3rsm_each_scan_download
+slamhip_score_poses_batch slamhip_score_poses_batch_stats""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -97,6 +98,11 @@ class ShardMsg(C.Structure):
 class PyramidRefreshJob(C.Structure):
     """slamhip_pyramid_refresh_job: one refresh of slamhip_pyramid_refresh_batch."""
     _fields_ = [("pyramid", C.c_void_p), ("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
+class ScoreJob(C.Structure):
+    """slamhip_score_job: one pose set of slamhip_score_poses_batch."""
+    _fields_ = [("map_id", C.c_int), ("scan_slot", C.c_int), ("n_poses", C.c_int), ("poses_xyt", _dp)]
 
 
 class MatchJob(C.Structure):
@@ -946,6 +952,17 @@ class Context:
         if rc:
             _check(rc)
 
+    def scan_download(self):
+        """The CURRENT scan as the scorers read it, back from HBM (slamhip_scan_download): [5, n] rows range, cos, sin,
+        weight, factor; n = 0 where there is none."""
+        n = C.c_int(0)
+        self.L.slamhip_scan_download.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
+        _check(self.L.slamhip_scan_download(self.h, 0, None, C.byref(n)))
+        out = np.zeros((5, max(n.value, 0)))
+        if n.value > 0:
+            _check(self.L.slamhip_scan_download(self.h, n.value, _d(out), C.byref(n)))
+        return out
+
     # scoring
     def score_poses(self, map_id, cfg, poses):
         poses = _f64(poses).reshape(-1, 3)
@@ -953,6 +970,39 @@ class Context:
         _check(self.L.slamhip_score_poses(self.h, map_id, C.byref(cfg), poses.shape[0], _d(poses),
                                           _d(out)))
         return out
+
+    def score_poses_batch(self, cfg, jobs, out=None):
+        """slamhip_score_poses_batch: jobs = [(map_id, scan_slot, poses), ...] (scan_slot -1: the current scan; poses
+        (n, 3), n >= 0, or None with a pose count in its place to hand the library a null pointer) scored in one call;
+        returns one array of scores per job, each bit-equal to scan_select(scan_slot) + score_poses(map_id, cfg, poses).
+        out: a flat array that receives the scores job after job (the returned arrays are views of it)."""
+        jobs = list(jobs)
+        table = (ScoreJob * max(len(jobs), 1))()
+        keep, counts = [], []
+        for k, (map_id, slot, poses) in enumerate(jobs):
+            table[k].map_id, table[k].scan_slot = int(map_id), int(slot)
+            if isinstance(poses, (int, np.integer)):  # (a count without poses: the refusal's test)
+                table[k].n_poses, table[k].poses_xyt = int(poses), None
+            else:
+                p = _f64(poses).reshape(-1, 3)
+                keep.append(p)
+                table[k].n_poses, table[k].poses_xyt = p.shape[0], _d(p)
+            counts.append(table[k].n_poses)
+        total = int(sum(max(c, 0) for c in counts))
+        flat = np.zeros(total) if out is None else out
+        assert flat.dtype == np.float64 and flat.flags.c_contiguous and flat.size >= total
+        self.L.slamhip_score_poses_batch.argtypes = [C.c_void_p, C.POINTER(SpeCfg), C.c_int, C.POINTER(ScoreJob), _dp]
+        _check(self.L.slamhip_score_poses_batch(self.h, C.byref(cfg), len(jobs), table, _d(flat)))
+        edges = np.concatenate([[0], np.cumsum(np.maximum(counts, 0))]).astype(int) if counts else np.zeros(1, int)
+        return [flat[edges[k]:edges[k + 1]] for k in range(len(jobs))]
+
+    def score_poses_batch_stats(self):
+        """of the last score_poses_batch that was not refused: jobs (with poses) in the shared launches, jobs through
+        the lone call, kernels the shared route launched to score and sum"""
+        v = [C.c_int() for _ in range(3)]
+        self.L.slamhip_score_poses_batch_stats.argtypes = [C.c_void_p] + [_ip] * 3
+        _check(self.L.slamhip_score_poses_batch_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(jobs_shared=v[0].value, jobs_lone=v[1].value, launches=v[2].value)
 
     def score_poses_device(self, map_id, cfg, n, d_poses_ptr, d_scores_ptr):
         _check(self.L.slamhip_score_poses_device(self.h, map_id, C.byref(cfg), n,

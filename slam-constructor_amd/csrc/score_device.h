@@ -336,4 +336,52 @@ __device__ __forceinline__ void score_point_body(const MapView &map, const ScanV
   }
 }
 
+// ---- K2's scoring body (k_score_window, score_kernels.hip; k_score_window_batch, score_batch.hip) -----------------
+// The npb poses staged in s_pose through a window OOPE: thread t walks its beams t, t + 256, ... in ascending order
+// (constants re-read per pose: the per-beam window walk dwarfs them), the canonical sum and the fingerprint of
+// score_point_body (same multipliers; fprints null: none).  terms (null: none) is pose-major, n per pose; pose p0 + j
+// goes to scores[p0 + j].  The caller has put a barrier behind its stores to s_pose.
+template <int MODEL>
+__device__ __forceinline__ void score_window_body(const MapView &map, const ScanView &scan, int oie, int oope, double half_v,
+                                                  double half_h, int n, int p0, int npb, const double (*s_pose)[4],
+                                                  double (*s_part)[4], unsigned long long (*s_hpart)[4], double *terms,
+                                                  double *scores, unsigned long long *fprints) {
+  constexpr int kBlock = kScoreBlock;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  // (the checked default mode over the window OOPEs, r05: K1's term-vector fingerprint, same multipliers)
+  const bool fprint = fprints != nullptr;
+  const unsigned fk_lo = (2u * (unsigned)t + 1u) * 0x9E3779B1u, fk_hi = (2u * (unsigned)t + 1u) * 0x85EBCA6Bu;
+  for (int j = 0; j < npb; ++j) {
+    const double x = s_pose[j][0], y = s_pose[j][1], sn = s_pose[j][2], cs = s_pose[j][3];
+    double acc = 0.0;
+    unsigned long long h = 0ull;
+    for (int b = t; b < n; b += kBlock) {
+      const double ca = scan.cos_a[b], sa = scan.sin_a[b], r = scan.range[b];
+      const double c = cs * ca - sn * sa;
+      const double s = sn * ca + cs * sa;
+      const double ox = x + r * c, oy = y + r * s;
+      const double pr = window_probability<MODEL>(map, oie, oope, half_v, half_h, ox, oy);
+      const double term = pr * scan.weight[b] * scan.factor[b];
+      if (terms) terms[(size_t)(p0 + j) * n + b] = term;
+      acc = acc + term;
+      if (fprint) {
+        const unsigned kq = (unsigned)(b / kBlock);
+        h += term_fingerprint(term, fk_lo + kq * (2u * kBlock * 0x9E3779B1u), fk_hi + kq * (2u * kBlock * 0x85EBCA6Bu));
+      }
+    }
+    wave_xor_sum_with(acc, h);  // (the butterfly of wave_xor_sum with the fingerprint riding along: same sum bits)
+    if (lane == 0) {
+      s_part[j][wave] = acc;
+      s_hpart[j][wave] = h;
+    }
+  }
+  __syncthreads();
+  if (t < npb) {
+    const double total = (s_part[t][0] + s_part[t][1]) + (s_part[t][2] + s_part[t][3]);
+    scores[p0 + t] = (scan.tot_w == 0.0) ? __builtin_nan("") : total / scan.tot_w;
+    if (fprint) fprints[p0 + t] = s_hpart[t][0] + s_hpart[t][1] + s_hpart[t][2] + s_hpart[t][3];
+  }
+}
+
 }  // namespace slamhip

@@ -13,8 +13,10 @@
 #include <random>
 
 #include "slamhip_internal.h"
+#include "kernel_pick.h"
 #include "libm_exact.h"
 #include "scan_filter.h"
+#include "score_batch.h"
 
 namespace slamhip {
 
@@ -844,6 +846,7 @@ int slamhip_ctx_destroy(slamhip_ctx *ctx) {
     hipHostFree(ctx->h_done_flag_b);
     hipEventDestroy(ctx->ev_fork);
   }
+  score_batch_release(ctx);
   mu_release(ctx);
   render_release(ctx);
   scan_gen_release(ctx);
@@ -1563,6 +1566,277 @@ int slamhip_score_poses(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg
   if (rc) return rc;
   if (cfg->oope == SLAMHIP_OOPE_GMAPPING) gm_carry_fixup(ctx, n_poses);
   std::memcpy(scores_out, ctx->h_scores, sizeof(double) * n_poses);
+  return SLAMHIP_OK;
+}
+
+// ---- the pose sets of K jobs in one scoring launch (score_batch.hip; the planning: score_batch_plan.h) ----------------
+}  // extern "C"
+
+namespace slamhip {
+
+// what the shared route keeps between calls: the arena (pinned and in HBM), the results, the last call's stats
+struct ScoreBatchStage {
+  PinnedBuf<unsigned char> h_arena;
+  DeviceBuf<unsigned char> d_arena;
+  size_t h_arena_cap = 0, d_arena_cap = 0;
+  PinnedBuf<double> h_scores;  // pinned and coherent: the kernels write it on the zero-copy path
+  DeviceBuf<double> d_scores;  // ... and this one where that path is off
+  size_t h_scores_cap = 0, d_scores_cap = 0;
+  int jobs_shared = 0, jobs_lone = 0, launches = 0;
+};
+
+// The lone route works on the context's CURRENT scan: each of its jobs selects its slot into that place.  What was
+// there goes back when the call ends -- error returns included -- and in front of a job that scores through it.
+struct CurrentScan {
+  slamhip_ctx *ctx;
+  const double *ptr;
+  size_t stride;
+  int n;
+  double tot_w;
+  std::vector<double> w, f, angle;
+  bool lazy, on_device, moved = false;
+  explicit CurrentScan(slamhip_ctx *c)
+      : ctx(c), ptr(c->scan_ptr), stride(c->scan_stride), n(c->scan_n), tot_w(c->scan_tot_w), w(c->h_weight), f(c->h_factor),
+        angle(c->h_scan_angle), lazy(c->scan_angle_lazy), on_device(c->scan_angle_on_device) {}
+  CurrentScan(const CurrentScan &) = delete;
+  CurrentScan &operator=(const CurrentScan &) = delete;
+  void put_back() {
+    if (!moved) return;
+    ctx->scan_ptr = ptr;
+    ctx->scan_stride = stride;
+    ctx->scan_n = n;
+    ctx->scan_tot_w = tot_w;
+    ctx->h_weight = w;
+    ctx->h_factor = f;
+    ctx->h_scan_angle = angle;
+    ctx->scan_angle_lazy = lazy;
+    ctx->scan_angle_on_device = false;  // (a job's exact mode may have sent its slot's angles to the one block in HBM)
+    moved = false;
+  }
+  ~CurrentScan() { put_back(); }
+};
+
+static int score_batch_shared(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_jobs, const slamhip_score_job *jobs,
+                              const score_plan::Plan &plan, double *scores_out) {
+  ScoreBatchStage *s = static_cast<ScoreBatchStage *>(ctx->score_batch);  // (made by the entry point)
+  const hipStream_t st = ctx->stream;
+  const bool host_trig = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST;
+  const bool seq_order = cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL;
+  const score_plan::Arena L = score_plan::arena_of(plan, (size_t)n_jobs, sizeof(ScoreJobView), host_trig);
+  int rc = grow_block(st, s->h_arena, s->h_arena_cap, L.bytes, 1 << 16, 1, hipHostMallocDefault);
+  if (!rc) rc = grow_block(st, s->d_arena, s->d_arena_cap, L.bytes, 1 << 16);
+  const size_t total = (size_t)plan.total_poses;
+  if (!rc) rc = grow_block(st, s->h_scores, s->h_scores_cap, total, 1 << 12, 1, kPinned);
+  if (!rc && !ctx->low_latency) rc = grow_block(st, s->d_scores, s->d_scores_cap, total, 1 << 12);
+  if (rc) return rc;
+  if (seq_order && (size_t)plan.total_terms > ctx->terms_cap) {  // (the lone call's block, grown the way fill_args grows it)
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+    if (ctx->stream_b) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream_b));
+    if (ctx->d_terms) hipFree(ctx->d_terms);
+    ctx->d_terms = nullptr;
+    ctx->terms_cap = 0;
+    SLAMHIP_CHECK(hipMalloc(&ctx->d_terms, sizeof(double) * (size_t)plan.total_terms));
+    ctx->terms_cap = (size_t)plan.total_terms;
+  }
+  // the views a lone call of each job would score through (validated by the caller: one effective model and OIE)
+  unsigned char *h = s->h_arena.get();
+  ScoreJobView *views = reinterpret_cast<ScoreJobView *>(h + L.jobs);
+  double *h_poses = reinterpret_cast<double *>(h + L.poses), *h_sc = reinterpret_cast<double *>(h + L.pose_sc);
+  int cell_model = -1, oie_eff = cfg->oie;
+  bool current_scan = false;
+  for (int k = 0; k < n_jobs; ++k) current_scan = current_scan || (jobs[k].n_poses > 0 && jobs[k].scan_slot < 0);
+  if (current_scan) {
+    rc = scan_assemble_now(ctx);
+    if (rc) return rc;
+  }
+  long long units = 0;
+  for (int k = 0; k < n_jobs; ++k) {
+    ScoreJobView &v = views[k];
+    std::memset(&v, 0, sizeof(v));
+    v.at = plan.pose_at[(size_t)k];
+    v.term_at = plan.term_at[(size_t)k];
+    const slamhip_score_job &j = jobs[k];
+    if (j.n_poses <= 0) continue;  // (no workgroup reads an empty job's entry)
+    rc = score_map_view(ctx, j.map_id, cfg, &v.map, &cell_model, &oie_eff);
+    if (rc) return rc;
+    if (j.scan_slot >= 0) {
+      const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[(size_t)j.scan_slot];
+      v.scan = scan_view_of(sl.d, (size_t)sl.cap, sl.n, sl.tot_w);
+    } else {
+      v.scan = scan_view_of(ctx->scan_ptr, ctx->scan_stride, ctx->scan_n, ctx->scan_tot_w);
+    }
+    v.n_poses = j.n_poses;
+    units += (long long)j.n_poses * v.scan.n;
+    std::memcpy(h_poses + 3 * (size_t)v.at, j.poses_xyt, sizeof(double) * 3 * (size_t)j.n_poses);
+    if (host_trig) {
+      // one sincos call per pose, as the lone call makes them (score_staged)
+      for (int p = 0; p < j.n_poses; ++p)
+        ::sincos(j.poses_xyt[3 * (size_t)p + 2], &h_sc[2 * ((size_t)v.at + p)], &h_sc[2 * ((size_t)v.at + p) + 1]);
+    }
+  }
+  std::memcpy(h + L.pose_at, plan.pose_at.data(), sizeof(long long) * plan.pose_at.size());
+  std::memcpy(h + L.blocks, plan.blocks.data(), sizeof(score_plan::Block) * plan.blocks.size());
+  unsigned char *d = s->d_arena.get();
+  SLAMHIP_CHECK(hipMemcpyAsync(d, h, L.bytes, hipMemcpyHostToDevice, st));
+  ScoreBatchArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.jobs = reinterpret_cast<const ScoreJobView *>(d + L.jobs);
+  a.blocks = reinterpret_cast<const score_plan::Block *>(d + L.blocks);
+  a.pose_at = reinterpret_cast<const long long *>(d + L.pose_at);
+  a.poses = reinterpret_cast<const double *>(d + L.poses);
+  a.pose_sc = host_trig ? reinterpret_cast<const double *>(d + L.pose_sc) : nullptr;
+  a.scores = ctx->low_latency ? s->h_scores.get() : s->d_scores.get();
+  a.terms = seq_order ? ctx->d_terms : nullptr;
+  a.fprints = nullptr;
+  a.total_poses = plan.total_poses;
+  a.n_jobs = n_jobs;
+  a.n_blocks = (int)plan.blocks.size();
+  a.poses_per_block = plan.poses_per_block;
+  a.oie = oie_eff;
+  a.oope = cfg->oope;
+  a.half_v = (cfg->area[1] - cfg->area[0]) / 2;
+  a.half_h = (cfg->area[3] - cfg->area[2]) / 2;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  rc = profile_event_pair(ctx, &e0, &e1);
+  if (rc) return rc;
+  if (e0) SLAMHIP_CHECK(hipEventRecord(e0, st));
+  int launches = 0;
+  const hipError_t le = launch_score_batch(a, cell_model, cfg->sum_order, plan.max_beams, st, &launches);
+  if (e1) (void)hipEventRecord(e1, st);  // (the pair is closed whatever the launch said: slamhip_profile_read resolves it)
+  SLAMHIP_CHECK(le);
+  if (ctx->low_latency) {
+    unsigned seq = ++ctx->seq;
+    if (seq == 0) seq = ++ctx->seq;
+    SLAMHIP_CHECK(launch_publish(ctx->h_done_flag, seq, st));
+    rc = score_wait(ctx, seq, 0);
+    if (rc) return rc;
+  } else {
+    SLAMHIP_CHECK(hipMemcpyAsync(s->h_scores.get(), s->d_scores.get(), sizeof(double) * total, hipMemcpyDeviceToHost, st));
+    SLAMHIP_CHECK(hipStreamSynchronize(st));
+  }
+  std::memcpy(scores_out, s->h_scores.get(), sizeof(double) * total);
+  if (ctx->profile) {
+    ctx->prof_launches += 1;
+    ctx->prof_units += units;
+  }
+  s->jobs_shared = plan.non_empty;
+  s->jobs_lone = 0;
+  s->launches = launches;
+  return SLAMHIP_OK;
+}
+
+void score_batch_release(slamhip_ctx *ctx) {
+  delete static_cast<ScoreBatchStage *>(ctx->score_batch);
+  ctx->score_batch = nullptr;
+}
+
+}  // namespace slamhip
+
+extern "C" {
+
+int slamhip_score_poses_batch(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_jobs, const slamhip_score_job *jobs,
+                              double *scores_out) {
+  if (!ctx) return invalid("null ctx");
+  if (!cfg) return invalid("null spe cfg");
+  if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return invalid("bad job list");
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST &&
+      cfg->pose_trig != SLAMHIP_POSE_TRIG_RAW_EXACT)
+    return invalid("unknown pose_trig");
+  const bool gm = cfg->oope == SLAMHIP_OOPE_GMAPPING;
+  const bool raw = cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT;
+  const bool seq_order = cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL;
+  // ---- everything that can be wrong with the arguments, before anything is staged, selected or launched.  A job without
+  // poses is not looked at any further: the lone call returns at once for it too.
+  std::vector<score_plan::JobShape> shapes((size_t)n_jobs, score_plan::JobShape{0, 0});
+  int cell_model = -1, oie_eff = -1;
+  for (int k = 0; k < n_jobs; ++k) {
+    const slamhip_score_job &j = jobs[k];
+    if (j.n_poses < 0 || (j.n_poses > 0 && !j.poses_xyt)) return invalid("bad pose batch in a score job");
+    if (j.n_poses == 0) continue;
+    if (!scores_out) return invalid("null scores_out");
+    DeviceMap *m = get_map(ctx, j.map_id);
+    if (!m) return invalid("unknown map id");
+    const int rc = check_cfg(*m, cfg);
+    if (rc) return rc;
+    const slamhip_ctx::ScanSlot *sl = nullptr;
+    if (j.scan_slot >= 0) {
+      if (j.scan_slot >= 4096) return invalid("scan slot out of range (0..4095)");
+      if (j.scan_slot >= (int)ctx->scan_slots.size() || !ctx->scan_slots[(size_t)j.scan_slot].d ||
+          ctx->scan_slots[(size_t)j.scan_slot].n <= 0) {
+        g_last_error = "a score job names a scan slot nothing is stored in";
+        return SLAMHIP_ERR_STATE;
+      }
+      sl = &ctx->scan_slots[(size_t)j.scan_slot];
+    } else if (j.scan_slot != -1) {
+      return invalid("a score job's scan_slot is 0..4095 or -1");
+    } else if (ctx->scan_n <= 0) {
+      g_last_error = "no scan uploaded";
+      return SLAMHIP_ERR_STATE;
+    }
+    const int beams = sl ? sl->n : ctx->scan_n;
+    // (what the lone call would refuse half-way through the list is refused here)
+    if (gm && beams > ((raw || seq_order) ? 3840 : 2048))
+      return invalid(raw || seq_order ? "the exact GMapping kernel holds at most 3840 filtered beams per scan"
+                                      : "the GMapping kernel holds at most 2048 filtered beams per scan");
+    if (raw && !(sl ? (int)sl->angle.size() == sl->n : scan_angles_known(ctx))) {
+      g_last_error = "SLAMHIP_POSE_TRIG_RAW_EXACT needs the angles of every job's scan points: slamhip_scan_store_angles / "
+                     "slamhip_scan_set_angles";
+      return SLAMHIP_ERR_STATE;
+    }
+    // one effective cell model and OIE per call (score_map_view: a belief map goes through its probability plane)
+    const bool plane = wants_prob_plane(ctx, *m, cfg);
+    const int model = plane ? SLAMHIP_CELL_OCC : m->cell_model, oie = plane ? SLAMHIP_OIE_OCCUPANCY : cfg->oie;
+    if (cell_model >= 0 && (model != cell_model || oie != oie_eff)) return invalid("the maps of one batch must share a cell model");
+    cell_model = model;
+    oie_eff = oie;
+    shapes[(size_t)k] = score_plan::JobShape{j.n_poses, beams};
+  }
+  if ((raw || (gm && seq_order)) && cell_model >= 0 && libm_variant() < 0) {
+    g_last_error = "this host's libm matches neither build of glibc's sin / cos / exp restated in csrc/libm_exact.h: the exact "
+                   "modes are not available here";
+    return SLAMHIP_ERR_UNSUPPORTED;
+  }
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  const score_plan::Plan plan =
+      score_plan::make_plan(shapes, pick_poses_per_block(score_plan::total_poses_of(shapes)), gm || raw, seq_order);
+  if (!ctx->score_batch) ctx->score_batch = new ScoreBatchStage();
+  ScoreBatchStage *s = static_cast<ScoreBatchStage *>(ctx->score_batch);
+  if (plan.route == score_plan::kRouteNothing) {
+    s->jobs_shared = s->jobs_lone = s->launches = 0;
+    return SLAMHIP_OK;
+  }
+  if (plan.route == score_plan::kRouteShared) return score_batch_shared(ctx, cfg, n_jobs, jobs, plan, scores_out);
+  // ---- the lone route: select + score, job after job (the GMapping OOPE's run cache sees ONE call sequence)
+  std::vector<double> scores((size_t)plan.total_poses);
+  {
+    CurrentScan keep(ctx);
+    for (int k = 0; k < n_jobs; ++k) {
+      const slamhip_score_job &j = jobs[k];
+      if (j.n_poses <= 0) continue;
+      if (j.scan_slot >= 0) {
+        keep.moved = true;
+        const int rc = slamhip_scan_select(ctx, j.scan_slot);
+        if (rc) return rc;
+      } else {
+        keep.put_back();
+      }
+      const int rc = slamhip_score_poses(ctx, j.map_id, cfg, j.n_poses, j.poses_xyt, scores.data() + plan.pose_at[(size_t)k]);
+      if (rc) return rc;
+    }
+  }
+  std::memcpy(scores_out, scores.data(), sizeof(double) * scores.size());
+  s->jobs_shared = 0;
+  s->jobs_lone = plan.non_empty;
+  s->launches = 0;
+  return SLAMHIP_OK;
+}
+
+int slamhip_score_poses_batch_stats(slamhip_ctx *ctx, int *jobs_in_shared_launches, int *jobs_lone, int *launches) {
+  if (!ctx || !jobs_in_shared_launches || !jobs_lone || !launches) return invalid("null argument");
+  const ScoreBatchStage *s = static_cast<const ScoreBatchStage *>(ctx->score_batch);
+  *jobs_in_shared_launches = s ? s->jobs_shared : 0;
+  *jobs_lone = s ? s->jobs_lone : 0;
+  *launches = s ? s->launches : 0;
   return SLAMHIP_OK;
 }
 

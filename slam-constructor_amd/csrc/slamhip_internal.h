@@ -325,6 +325,7 @@ void shard_release(slamhip_ctx *ctx);                 // shard.cpp: leaves the R
 void render_release(slamhip_ctx *ctx);                // map_render.hip: frees the context's render buffer
 void scan_gen_release(slamhip_ctx *ctx);              // scan_generate.hip: frees the context's scan-generation block
 void pyramids_release(slamhip_ctx *ctx);              // map_pyramid.hip: frees what the context's pyramids hold in HBM
+void score_batch_release(slamhip_ctx *ctx);           // slamhip_api.cpp: frees slamhip_score_poses_batch's staging
 void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 hipError_t refuse_launch(const char *why);  // hipErrorInvalidValue; hip_fail appends `why` to the failed call's text
@@ -423,6 +424,7 @@ struct slamhip_ctx {
   int pose_cap = 0;
   double *d_terms = nullptr;
   size_t terms_cap = 0;
+  void *score_batch = nullptr;  // ScoreBatchStage: slamhip_score_poses_batch's arena, results and last stats (slamhip_api.cpp)
   // dirty-cell staging
   int *d_dirty_xy = nullptr;
   double *d_dirty_val = nullptr;

@@ -20,6 +20,8 @@
 //                          HipGridScanMatcher::process_raw_scan does for one scan, for K of them
 //   HipScanProbabilityEstimator  ScanProbabilityEstimator whose estimate_scan_probability is one
 //                          slamhip_score_poses call (used by code that scores single poses)
+//   hip_estimate_scan_probabilities  K (filtered scan, map, pose list) triples through ONE
+//                          slamhip_score_poses_batch call: K score vectors
 //
 // Error convention of the reference (no exceptions; bad config -> message + std::exit(-1),
 // init_scan_matching.h:39-43): a failing slamhip call prints slamhip_last_error() and exits.
@@ -731,6 +733,76 @@ private:
   int _weighting;
   HipScanTrig _trig;
 };
+
+// ------------------------------------------------------------------------------------------------
+// ScanProbabilityEstimator::estimate_scan_probability for K (filtered scan, map, pose list) triples -- K robots, K map
+// hypotheses under one scan, K heat maps -- in ONE slamhip_score_poses_batch call: what HipScanProbabilityEstimator does
+// per pose, for all poses of all triples.  The scan of triple k must be the FILTERED one (filter_scan's result); it is
+// stored in scan slot first_slot + k with its points' angles, the map goes through its mirror, and scores[k][i] is the
+// probability of poses[i] (bit-equal to HipScanProbabilityEstimator's under the same configuration).  A scan without
+// points scores NaN at every pose.  The context's current scan is left as it was.
+struct HipScoreJob {
+  const LaserScan2D *scan;  // filtered
+  const GridMap *map;
+  HipMapMirror *mirror;     // the map's mirror (two jobs on one map: the same mirror)
+  std::vector<RobotPose> poses;
+};
+
+inline std::vector<std::vector<double>> hip_estimate_scan_probabilities(slamhip_ctx *ctx, slamhip_spe_cfg cfg,
+                                                                        const ScanProbabilityEstimator::SPEParams &params,
+                                                                        const std::vector<HipScoreJob> &jobs, int weighting,
+                                                                        const HipScanTrig &trig = {}, int first_slot = 0) {
+  cfg.area[0] = params.sp_analysis_area.bot();
+  cfg.area[1] = params.sp_analysis_area.top();
+  cfg.area[2] = params.sp_analysis_area.left();
+  cfg.area[3] = params.sp_analysis_area.right();
+  const int K = int(jobs.size());
+  std::vector<slamhip_score_job> table(K);
+  std::vector<std::vector<double>> xyt(K);
+  size_t total = 0;
+  for (int k = 0; k < K; ++k) {
+    const HipScoreJob &j = jobs[k];
+    const auto &pts = j.scan->points();
+    const int n = int(pts.size());
+    table[k] = slamhip_score_job{j.mirror->id(), first_slot + k, 0, nullptr};
+    if (n == 0 || j.poses.empty()) continue;
+    j.mirror->sync(*j.map);
+    std::vector<double> r(n), a(n), f(n), w(n), c(n), s(n);
+    for (int i = 0; i < n; ++i) {
+      r[i] = pts[i].range();
+      a[i] = pts[i].angle();
+      f[i] = pts[i].factor();
+    }
+    slamhip_or_die(slamhip_scan_weights(weighting, n, r.data(), a.data(), w.data()), "scan_weights");
+    if (trig.mode == SLAMHIP_TRIG_CACHED)
+      slamhip_or_die(slamhip_beam_trig_cached(n, a.data(), trig.a_min, trig.a_max, trig.a_inc, c.data(), s.data()), "beam_trig_cached");
+    else
+      slamhip_or_die(slamhip_beam_trig_raw(n, a.data(), c.data(), s.data()), "beam_trig_raw");
+    slamhip_or_die(slamhip_scan_store(ctx, first_slot + k, n, r.data(), c.data(), s.data(), w.data(), f.data()), "scan_store");
+    slamhip_or_die(slamhip_scan_store_angles(ctx, first_slot + k, n, a.data()), "scan_store_angles");
+    for (const RobotPose &p : j.poses) {
+      xyt[k].push_back(p.x);
+      xyt[k].push_back(p.y);
+      xyt[k].push_back(p.theta);
+    }
+    table[k].n_poses = int(j.poses.size());
+    table[k].poses_xyt = xyt[k].data();
+    total += j.poses.size();
+  }
+  std::vector<double> flat(total);
+  slamhip_or_die(slamhip_score_poses_batch(ctx, &cfg, K, table.data(), flat.data()), "score_poses_batch");
+  std::vector<std::vector<double>> scores(K);
+  size_t at = 0;
+  for (int k = 0; k < K; ++k) {
+    if (table[k].n_poses == 0) {
+      scores[k].assign(jobs[k].poses.size(), std::numeric_limits<double>::quiet_NaN());
+      continue;
+    }
+    scores[k].assign(flat.begin() + at, flat.begin() + at + table[k].n_poses);
+    at += size_t(table[k].n_poses);
+  }
+  return scores;
+}
 
 // ------------------------------------------------------------------------------------------------
 // read-only GridMap over a device window: occupancy() of the cell kinds the path holds -- the payload double of
