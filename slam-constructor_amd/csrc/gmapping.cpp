@@ -258,9 +258,9 @@ int run_jobs(slamhip_gmapping *g, int map_id, std::vector<MatchJob *> &act, int 
     int total = 0;
     for (int k = G.lo; k < G.hi; ++k) {
       off[k] = G.base + total;
-      cnt[k] = act[k]->done ? 0 : act[k]->plan(per_job_budget, ctx->h_poses + 3 * (size_t)off[k]);
+      cnt[k] = act[k]->done ? 0 : act[k]->plan(per_job_budget, ctx->h_poses.get() + 3 * (size_t)off[k]);
       if (slots)
-        for (int q = 0; q < cnt[k]; ++q) ctx->h_pose_slot[off[k] + q] = slots[k];
+        for (int q = 0; q < cnt[k]; ++q) ctx->h_pose_slot.get()[off[k] + q] = slots[k];
       total += cnt[k];
     }
     G.total = total;
@@ -287,7 +287,7 @@ int run_jobs(slamhip_gmapping *g, int map_id, std::vector<MatchJob *> &act, int 
       if (rc) return rc;
       for (int k = G.lo; k < G.hi; ++k) {
         if (cnt[k] == 0) continue;
-        rc = act[k]->consume(ctx->h_scores + off[k], ctx->h_gm_info + off[k], ctx);
+        rc = act[k]->consume(ctx->h_scores.get() + off[k], ctx->h_gm_info.get() + off[k], ctx);
         if (rc) return rc;
       }
       rc = plan_and_submit(G);

@@ -1,10 +1,12 @@
-// hip_block.h -- owners of hipMalloc / hipHostMalloc blocks, the one way such a block grows, and a scanner's per-beam
-// tables resident in HBM.  Part of slamhip_internal.h, which includes it behind SLAMHIP_CHECK: include that one.
+// hip_block.h -- owners of hipMalloc / hipHostMalloc blocks and the one way such blocks grow: the only way the library
+// holds a block (the three planes of a DeviceMap, which change hands, excepted).  Needs the runtime header, SLAMHIP_OK
+// and SLAMHIP_CHECK and nothing else; slamhip_internal.h includes it behind SLAMHIP_CHECK: include that one.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include "scan_filter.h"
+#include <cstddef>
+#include <initializer_list>
 
 namespace slamhip {
 
@@ -50,49 +52,31 @@ template <class T>
 using PinnedBuf = HipBlock<T, true>;
 constexpr unsigned kPinnedCoherent = hipHostMallocMapped | hipHostMallocCoherent;
 
-// A block that holds `cap` units of `per` elements and has to hold `need`: nothing, or the stream waited for (what runs
-// on it may read the block that goes away) and `floor` doubled up to `need` units allocated in its place.  alloc frees
-// first and a failed one leaves the owner empty, so the stored capacity is zero from the free to the success: an error
-// return never leaves an old capacity over a null block.
-template <class T, bool kPinned, class Cap>
-int grow_block(hipStream_t stream, HipBlock<T, kPinned> &block, Cap &cap, size_t need, size_t floor, size_t per = 1,
-               unsigned pinned_flags = 0) {
+// Blocks that share the capacity `cap` and have to hold `need` units: nothing, or the streams waited for (what runs on
+// them may read the blocks that go away), `floor` doubled up to `need`, and `body(grown)` -- the callers' alloc,
+// hipMemsetAsync and host memset calls -- run under a stored capacity of zero.  alloc frees first and a failed one
+// leaves its owner empty, so an error return never leaves an old capacity over a null block: the capacity is stored
+// only behind a body that returned SLAMHIP_OK.
+template <class Cap, class Body>
+int grow_blocks(std::initializer_list<hipStream_t> streams, Cap &cap, size_t need, size_t floor, Body &&body) {
   if (need <= (size_t)cap) return SLAMHIP_OK;
-  SLAMHIP_CHECK(hipStreamSynchronize(stream));
+  for (hipStream_t s : streams) SLAMHIP_CHECK(hipStreamSynchronize(s));
   size_t grown = floor;
   while (grown < need) grown *= 2;
   cap = 0;
-  SLAMHIP_CHECK(block.alloc(per * grown, pinned_flags));
-  cap = (Cap)grown;
-  return SLAMHIP_OK;
+  const int rc = body(grown);
+  if (rc == SLAMHIP_OK) cap = (Cap)grown;
+  return rc;
 }
 
-// A scanner's per-beam tables (ScanTables, scan_filter.h) resident in HBM, where the assembly kernels gather them: ONE
-// block of `planes` planes of cap() doubles, cos | sin | viny_f [| angle].
-class ScanTablesDevice {
-  DeviceBuf<double> d_;
-  int cap_ = 0, planes_ = 0;
-  const double *plane(int q) const { return q < planes_ ? d_.get() + (size_t)q * (size_t)cap_ : nullptr; }
-
- public:
-  // `t` to HBM on `stream`, behind what still reads the tables held so far; 3 planes, or 4 with the angles.  The copies
-  // are asynchronous from pageable memory: the caller waits for the stream before `t` may change.
-  int upload(hipStream_t stream, const ScanTables &t, int planes) {
-    const size_t n = t.cos_a.size(), bytes = sizeof(double) * n;
-    if (planes != planes_) cap_ = 0;
-    const int rc = grow_block(stream, d_, cap_, n, 2048, planes);
-    if (rc) return rc;
-    planes_ = planes;
-    const std::vector<double> *src[4] = {&t.cos_a, &t.sin_a, &t.viny_f, &t.angle};
-    for (int q = 0; q < planes; ++q)
-      SLAMHIP_CHECK(hipMemcpyAsync(d_.get() + (size_t)q * (size_t)cap_, src[q]->data(), bytes, hipMemcpyHostToDevice, stream));
+// ... and the lone block of `per` elements a unit
+template <class T, bool kPinned, class Cap>
+int grow_block(hipStream_t stream, HipBlock<T, kPinned> &block, Cap &cap, size_t need, size_t floor, size_t per = 1,
+               unsigned pinned_flags = 0) {
+  return grow_blocks({stream}, cap, need, floor, [&](size_t grown) -> int {
+    SLAMHIP_CHECK(block.alloc(per * grown, pinned_flags));
     return SLAMHIP_OK;
-  }
-  size_t cap() const { return (size_t)cap_; }
-  const double *cos() const { return plane(0); }
-  const double *sin() const { return plane(1); }
-  const double *viny() const { return plane(2); }
-  const double *angle() const { return plane(3); }  // (null where the block holds three planes)
-};
+  });
+}
 
 }  // namespace slamhip

@@ -228,28 +228,24 @@ int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const s
   }
   const int slots = m3rsm::slots_of(depth);
   const size_t n_out = (size_t)n * slots;
-  if (n > p->x_parent_cap || n_out > p->x_slot_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (p->d_x_in) (void)hipFree(p->d_x_in);
-    if (p->d_x_out) (void)hipFree(p->d_x_out);
-    if (p->h_x) (void)hipHostFree(p->h_x);
-    p->d_x_in = p->d_x_out = p->h_x = nullptr;
+  // (the parents' block and the slots' are sized anew together, whichever ran out: 256 and 2048 doubled)
+  if (n > p->x_parent_cap) p->x_slot_cap = 0;
+  rc = grow_blocks({ctx->stream}, p->x_slot_cap, n_out, 2048, [&](size_t scap) -> int {
     p->x_parent_cap = 0;
-    p->x_slot_cap = 0;
     int pcap = 256;
     while (pcap < n) pcap *= 2;
-    size_t scap = 2048;
-    while (scap < n_out) scap *= 2;
     // per slot 4 doubles of rectangle, the score and the level (an int behind the doubles): one block, one copy back;
     // the host side is pinned, parents in front of the results
-    SLAMHIP_CHECK(hipMalloc(&p->d_x_in, sizeof(double) * 7 * pcap));
-    SLAMHIP_CHECK(hipMalloc(&p->d_x_out, (sizeof(double) * 5 + sizeof(int)) * scap));
-    SLAMHIP_CHECK(hipHostMalloc(&p->h_x, sizeof(double) * 7 * pcap + (sizeof(double) * 5 + sizeof(int)) * scap, hipHostMallocDefault));
+    const size_t slot_doubles = 5 * scap + scap / 2;  // (5 doubles and an int per slot; scap is a power of two)
+    SLAMHIP_CHECK(p->d_x_in.alloc(7 * (size_t)pcap));
+    SLAMHIP_CHECK(p->d_x_out.alloc(slot_doubles));
+    SLAMHIP_CHECK(p->h_x.alloc(7 * (size_t)pcap + slot_doubles));
     p->x_parent_cap = pcap;
-    p->x_slot_cap = scap;
-  }
+    return SLAMHIP_OK;
+  });
+  if (rc) return rc;
   const bool host_trig = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST;
-  double *stage = p->h_x, *h_out = p->h_x + 7 * (size_t)p->x_parent_cap;
+  double *stage = p->h_x.get(), *h_out = p->h_x.get() + 7 * (size_t)p->x_parent_cap;
   std::memcpy(stage, rotation, sizeof(double) * n);
   std::memcpy(stage + n, rect, sizeof(double) * 4 * n);
   if (host_trig)  // (one sincos call per parent: its children share the heading)
@@ -261,20 +257,20 @@ int slamhip_pyramid_expand_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const s
     pyr_raw_rows(n, rotation, reinterpret_cast<int *>(stage + 6 * (size_t)n), &rot_rows);
     std::memcpy(stage + 5 * (size_t)n, rot_rows.data(), sizeof(double) * rot_rows.size());
   }
-  SLAMHIP_CHECK(hipMemcpyAsync(p->d_x_in, stage, sizeof(double) * (host_trig || raw ? 7 : 5) * n, hipMemcpyHostToDevice,
+  SLAMHIP_CHECK(hipMemcpyAsync(p->d_x_in.get(), stage, sizeof(double) * (host_trig || raw ? 7 : 5) * n, hipMemcpyHostToDevice,
                                ctx->stream));
   RawTrig rt{};
   if (raw) {
-    rc = pyr_raw_queue_table(p, fma, p->d_x_in + 5 * (size_t)n, (int)rot_rows.size(), base_pose[2], d_angle, ctx->scan_n, &rt);
+    rc = pyr_raw_queue_table(p, fma, p->d_x_in.get() + 5 * (size_t)n, (int)rot_rows.size(), base_pose[2], d_angle, ctx->scan_n, &rt);
     if (rc) return rc;
-    rt.row = reinterpret_cast<const int *>(p->d_x_in + 6 * (size_t)n);
+    rt.row = reinterpret_cast<const int *>(p->d_x_in.get() + 6 * (size_t)n);
   }
-  double *d_rect_out = p->d_x_out, *d_scores = p->d_x_out + 4 * n_out;
-  int *d_levels = reinterpret_cast<int *>(p->d_x_out + 5 * n_out);
-  rc = queue_expand(p, cfg, base_pose, n, p->d_x_in, p->d_x_in + n, host_trig ? p->d_x_in + 5 * (size_t)n : nullptr,
+  double *d_rect_out = p->d_x_out.get(), *d_scores = p->d_x_out.get() + 4 * n_out;
+  int *d_levels = reinterpret_cast<int *>(p->d_x_out.get() + 5 * n_out);
+  rc = queue_expand(p, cfg, base_pose, n, p->d_x_in.get(), p->d_x_in.get() + n, host_trig ? p->d_x_in.get() + 5 * (size_t)n : nullptr,
                     raw ? &rt : nullptr, translation_step, depth, d_rect_out, d_scores, d_levels);
   if (rc) return rc;
-  SLAMHIP_CHECK(hipMemcpyAsync(h_out, p->d_x_out, (sizeof(double) * 5 + sizeof(int)) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(h_out, p->d_x_out.get(), (sizeof(double) * 5 + sizeof(int)) * n_out, hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   std::memcpy(rect_out, h_out, sizeof(double) * 4 * n_out);
   std::memcpy(score_out, h_out + 4 * n_out, sizeof(double) * n_out);

@@ -137,7 +137,7 @@ int queue_levels(slamhip_pyramid *p, int x0, int y0, int w, int h) {
     const int cw = cx1 - cx0 + 1, ch = cy1 - cy0 + 1;
     const bool top = lv == pl.n;
     const int bias_x = top ? 0 : src.origin_x - 2 * dst.origin_x, bias_y = top ? 0 : src.origin_y - 2 * dst.origin_y;
-    const pyr::Level s = level_of(src, lv == 1 ? nullptr : p->d_coord[lv - 2]), d = level_of(dst, p->d_coord[lv - 1]);
+    const pyr::Level s = level_of(src, lv == 1 ? nullptr : p->d_coord[lv - 2].get()), d = level_of(dst, p->d_coord[lv - 1].get());
     const dim3 grid((cw + kPyrThreads - 1) / kPyrThreads, std::min(ch, kMaxGridY));
     const auto kernel = cell_doubles(p->cell_model) == 1 ? k_pyr_reduce<1> : k_pyr_reduce<4>;
     SLAMHIP_CHECK(launch_kernel(kernel, grid, dim3(kPyrThreads), 0, ctx->stream, nullptr, nullptr, s, d, bias_x, bias_y,
@@ -165,12 +165,9 @@ void free_levels(slamhip_pyramid *p, bool release_maps) {
         if (m && m->d_payload == p->lv_payload[lv]) (void)slamhip_map_release(ctx, p->first_id + lv - 1);
       }
   }
-  for (int *c : p->d_coord)
-    if (c) (void)hipFree(c);
   p->d_coord.clear();
   p->lv_payload.clear();
-  if (p->d_views) (void)hipFree(p->d_views);
-  p->d_views = nullptr;
+  p->d_views.reset();
   p->plan.n = 0;
 }
 
@@ -195,7 +192,8 @@ int make_levels(slamhip_pyramid *p) {
   for (int k = 0; k < 4; ++k) unknown[k] = fine->unknown[k];
   p->cell_model = model;
   p->plan = pl;
-  p->d_coord.assign(pl.n, nullptr);
+  p->d_coord.clear();
+  p->d_coord.resize(pl.n);
   p->lv_payload.assign(pl.n + 1, nullptr);
   for (int lv = 1; lv <= pl.n; ++lv) {
     const int rc = slamhip_map_bind(ctx, p->first_id + lv - 1, model, pl.width[lv - 1], pl.height[lv - 1], pl.origin_x[lv - 1],
@@ -203,7 +201,7 @@ int make_levels(slamhip_pyramid *p) {
     if (rc) return rc;
     const DeviceMap &m = ctx->maps[p->first_id + lv - 1];
     p->lv_payload[lv] = m.d_payload;
-    SLAMHIP_CHECK(hipMalloc(&p->d_coord[lv - 1], sizeof(int) * 2 * (size_t)m.pitch * m.height));
+    SLAMHIP_CHECK(p->d_coord[lv - 1].alloc(2 * (size_t)m.pitch * m.height));
   }
   fine = bound_map(ctx, p->fine_id);  // (binding may have moved the context's map table)
   p->fine_w = fine->width;
@@ -214,8 +212,8 @@ int make_levels(slamhip_pyramid *p) {
   std::vector<MapView> views(pl.n + 1);
   views[0] = view_of(*fine);
   for (int lv = 1; lv <= pl.n; ++lv) views[lv] = view_of(ctx->maps[p->first_id + lv - 1]);
-  SLAMHIP_CHECK(hipMalloc(&p->d_views, sizeof(MapView) * views.size()));
-  SLAMHIP_CHECK(hipMemcpy(p->d_views, views.data(), sizeof(MapView) * views.size(), hipMemcpyHostToDevice));
+  SLAMHIP_CHECK(p->d_views.alloc(views.size()));
+  SLAMHIP_CHECK(hipMemcpy(p->d_views.get(), views.data(), sizeof(MapView) * views.size(), hipMemcpyHostToDevice));
   return queue_levels(p, 0, 0, p->fine_w, p->fine_h);
 }
 
@@ -289,20 +287,6 @@ __global__ __launch_bounds__(256) void k_pyr_raw_table_many(const double *__rest
     const PyrSource &q = table[row_request[r]];
     raw_row_fill<FMA>(rot_rows[r] + q.base[2], q.angle, q.scan.n, out_cos + (size_t)r * stride, out_sin + (size_t)r * stride);
   }
-}
-
-// grows a table of beam directions to `need` doubles: synchronise, free, allocate
-int raw_table_room(slamhip_ctx *ctx, double **d_raw, size_t *cap, size_t need) {
-  if (need <= *cap) return SLAMHIP_OK;
-  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (*d_raw) (void)hipFree(*d_raw);
-  *d_raw = nullptr;
-  *cap = 0;
-  size_t c = 1 << 14;
-  while (c < need) c *= 2;
-  SLAMHIP_CHECK(hipMalloc(d_raw, sizeof(double) * c));
-  *cap = c;
-  return SLAMHIP_OK;
 }
 
 dim3 raw_table_grid(int max_beams, int n_rows) { return dim3((max_beams + 255) / 256, std::min(n_rows, kMaxGridY)); }
@@ -416,9 +400,9 @@ int pyr_raw_queue_table(slamhip_pyramid *p, bool fma, const double *d_rot_rows, 
                         const double *d_angle, int n_beams, RawTrig *out) {
   slamhip_ctx *ctx = p->ctx;
   const size_t stride = (size_t)((n_beams + 7) & ~7);
-  const int rc = raw_table_room(ctx, &p->d_raw, &p->raw_cap, 2 * stride * (size_t)n_rows);
+  const int rc = grow_block(ctx->stream, p->d_raw, p->raw_cap, 2 * stride * (size_t)n_rows, 1 << 14);
   if (rc) return rc;
-  double *d_cos = p->d_raw, *d_sin = p->d_raw + stride * (size_t)n_rows;
+  double *d_cos = p->d_raw.get(), *d_sin = p->d_raw.get() + stride * (size_t)n_rows;
   const auto kernel = fma ? k_pyr_raw_table<true> : k_pyr_raw_table<false>;
   SLAMHIP_CHECK(launch_kernel(kernel, raw_table_grid(n_beams, n_rows), dim3(256), 0, ctx->stream, nullptr, nullptr, d_rot_rows,
                               n_rows, base_theta, d_angle, n_beams, stride, d_cos, d_sin));
@@ -436,7 +420,7 @@ int pyr_fill_args(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double b
   if (ctx->scan_n <= 0) return pyr_state("no scan uploaded");
   MatchArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.levels = p->d_views;
+  a.levels = p->d_views.get();
   a.n_levels = p->plan.n + 1;
   const size_t c = ctx->scan_stride;
   a.scan.range = ctx->scan_ptr;
@@ -451,15 +435,9 @@ int pyr_fill_args(slamhip_pyramid *p, const slamhip_spe_cfg *cfg, const double b
   a.oope = cfg->oope;
   if (cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL) {
     const size_t need = n_out * (size_t)ctx->scan_n;
-    if (need > p->terms_cap) {
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (p->d_terms) (void)hipFree(p->d_terms);
-      p->d_terms = nullptr;
-      p->terms_cap = 0;
-      SLAMHIP_CHECK(hipMalloc(&p->d_terms, sizeof(double) * need));
-      p->terms_cap = need;
-    }
-    a.terms = p->d_terms;
+    const int rc = grow_block(ctx->stream, p->d_terms, p->terms_cap, need, need);  // (exactly the terms of the call)
+    if (rc) return rc;
+    a.terms = p->d_terms.get();
   }
   *out = a;
   return SLAMHIP_OK;
@@ -479,13 +457,7 @@ int pyr_launch_sum_sequential_many(const ManyArgs &a, size_t n_out, int slots, h
 
 // ---- several requests in one launch ----------------------------------------------------------------
 void pyr_many_release(slamhip_ctx *ctx) {
-  PyrManyStage *st = static_cast<PyrManyStage *>(ctx->pyr_many);
-  if (!st) return;
-  if (st->h) (void)hipHostFree(st->h);
-  if (st->d) (void)hipFree(st->d);
-  if (st->d_terms) (void)hipFree(st->d_terms);
-  if (st->d_raw) (void)hipFree(st->d_raw);
-  delete st;
+  delete static_cast<PyrManyStage *>(ctx->pyr_many);
   ctx->pyr_many = nullptr;
 }
 
@@ -513,7 +485,7 @@ int pyr_source_begin(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, slamhip_pyram
   if (p->cell_model != (*first)->cell_model || p->oie != (*first)->oie)
     return pyr_invalid("the pyramids of one call share the cell model and the OIE");
   std::memset(q, 0, sizeof(*q));
-  q->levels = p->d_views;
+  q->levels = p->d_views.get();
   q->n_levels = p->plan.n + 1;
   return SLAMHIP_OK;
 }
@@ -549,7 +521,8 @@ int pyr_many_sources(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int n_request
     if (cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT && ((int)sl.angle.size() != sl.n || !sl.d_angle))
       return pyr_state("SLAMHIP_POSE_TRIG_RAW_EXACT needs the angles of every request's stored scan: "
                        "slamhip_scan_store_angles after slamhip_scan_store");
-    pyr_source_block(sl.d, (size_t)sl.cap, sl.n, sl.tot_w, cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT ? sl.d_angle : nullptr, &q);
+    pyr_source_block(sl.d.get(), (size_t)sl.cap, sl.n, sl.tot_w, cfg->pose_trig == SLAMHIP_POSE_TRIG_RAW_EXACT ? sl.d_angle.get() : nullptr,
+                     &q);
     out->push_back(q);
   }
   return SLAMHIP_OK;
@@ -575,26 +548,22 @@ int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vect
   if (!ctx->pyr_many) ctx->pyr_many = new PyrManyStage;
   PyrManyStage *st = static_cast<PyrManyStage *>(ctx->pyr_many);
   const size_t in_bytes = many_in_bytes(n_src, n), need = in_bytes + many_out_bytes(n_out);
-  if (need > st->cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (st->h) (void)hipHostFree(st->h);
-    if (st->d) (void)hipFree(st->d);
-    st->h = st->d = nullptr;
-    st->cap = 0;
-    size_t cap = 1 << 16;
-    while (cap < need) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&st->d, cap));
-    SLAMHIP_CHECK(hipHostMalloc(&st->h, cap, hipHostMallocDefault));
-    st->cap = cap;
+  {
+    const int rc = grow_blocks({ctx->stream}, st->cap, need, 1 << 16, [&](size_t cap) -> int {
+      SLAMHIP_CHECK(st->d.alloc(cap));
+      SLAMHIP_CHECK(st->h.alloc(cap));
+      return SLAMHIP_OK;
+    });
+    if (rc) return rc;
   }
   const bool host_trig = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST, terms = cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL;
   // table | terms offsets | rotation | rect | sin, cos | request: every part starts on 8 bytes
   size_t at = 0;
   const size_t table_at = at;
-  std::memcpy(st->h + at, src.data(), sizeof(PyrSource) * n_src);
+  std::memcpy(st->h.get() + at, src.data(), sizeof(PyrSource) * n_src);
   at += up8(sizeof(PyrSource) * n_src);
   const size_t off_at = at;
-  long long *h_off = reinterpret_cast<long long *>(st->h + at);
+  long long *h_off = reinterpret_cast<long long *>(st->h.get() + at);
   size_t total_terms = 0;
   for (int i = 0; i < n; ++i) {
     h_off[i] = (long long)total_terms;
@@ -602,13 +571,13 @@ int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vect
   }
   at += sizeof(long long) * n;
   const size_t rot_at = at;
-  std::memcpy(st->h + at, rotation, sizeof(double) * n);
+  std::memcpy(st->h.get() + at, rotation, sizeof(double) * n);
   at += sizeof(double) * n;
   const size_t rect_at = at;
-  std::memcpy(st->h + at, rect, sizeof(double) * 4 * n);
+  std::memcpy(st->h.get() + at, rect, sizeof(double) * 4 * n);
   at += sizeof(double) * 4 * n;
   const size_t sc_at = at;
-  double *h_sc = reinterpret_cast<double *>(st->h + at);
+  double *h_sc = reinterpret_cast<double *>(st->h.get() + at);
   // RAW_EXACT: the part holds the rows instead -- the distinct (request, rotation bits) pairs in order of first
   // appearance: rotation per row (at most n doubles) | request per row | row per candidate (n ints each)
   int n_rows = 0, max_beams = 0;
@@ -635,28 +604,24 @@ int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vect
   }
   at += sizeof(double) * 2 * n;
   const size_t req_at = at;
-  std::memcpy(st->h + at, request, sizeof(int) * n);
-  if (terms && total_terms > st->terms_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (st->d_terms) (void)hipFree(st->d_terms);
-    st->d_terms = nullptr;
-    st->terms_cap = 0;
-    SLAMHIP_CHECK(hipMalloc(&st->d_terms, sizeof(double) * total_terms));
-    st->terms_cap = total_terms;
+  std::memcpy(st->h.get() + at, request, sizeof(int) * n);
+  if (terms) {  // (exactly the terms of the call)
+    const int rc = grow_block(ctx->stream, st->d_terms, st->terms_cap, total_terms, total_terms);
+    if (rc) return rc;
   }
   const size_t raw_stride = (size_t)((max_beams + 7) & ~7);
   if (raw) {
-    const int rc = raw_table_room(ctx, &st->d_raw, &st->raw_cap, 2 * raw_stride * (size_t)n_rows);
+    const int rc = grow_block(ctx->stream, st->d_raw, st->raw_cap, 2 * raw_stride * (size_t)n_rows, 1 << 14);
     if (rc) return rc;
   }
-  SLAMHIP_CHECK(hipMemcpyAsync(st->d, st->h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(st->d.get(), st->h.get(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
   ManyArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.table = reinterpret_cast<const PyrSource *>(st->d + table_at);
+  a.table = reinterpret_cast<const PyrSource *>(st->d.get() + table_at);
   if (raw) {
-    const double *d_rot_rows = reinterpret_cast<const double *>(st->d + sc_at);
+    const double *d_rot_rows = reinterpret_cast<const double *>(st->d.get() + sc_at);
     const int *d_row_req = reinterpret_cast<const int *>(d_rot_rows + n);
-    double *d_cos = st->d_raw, *d_sin = st->d_raw + raw_stride * (size_t)n_rows;
+    double *d_cos = st->d_raw.get(), *d_sin = st->d_raw.get() + raw_stride * (size_t)n_rows;
     const auto kernel = fma ? k_pyr_raw_table_many<true> : k_pyr_raw_table_many<false>;
     SLAMHIP_CHECK(launch_kernel(kernel, raw_table_grid(max_beams, n_rows), dim3(256), 0, ctx->stream, nullptr, nullptr, d_rot_rows,
                                 d_row_req, n_rows, a.table, raw_stride, d_cos, d_sin));
@@ -665,17 +630,17 @@ int pyr_many_stage(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, const std::vect
     a.m.raw.row = d_row_req + n;
     a.m.raw.stride = raw_stride;
   }
-  a.terms_off = reinterpret_cast<const long long *>(st->d + off_at);
-  a.request = reinterpret_cast<const int *>(st->d + req_at);
-  a.m.rotation = reinterpret_cast<const double *>(st->d + rot_at);
-  a.m.rect = reinterpret_cast<const double *>(st->d + rect_at);
-  a.m.pose_sc = host_trig ? reinterpret_cast<const double *>(st->d + sc_at) : nullptr;
+  a.terms_off = reinterpret_cast<const long long *>(st->d.get() + off_at);
+  a.request = reinterpret_cast<const int *>(st->d.get() + req_at);
+  a.m.rotation = reinterpret_cast<const double *>(st->d.get() + rot_at);
+  a.m.rect = reinterpret_cast<const double *>(st->d.get() + rect_at);
+  a.m.pose_sc = host_trig ? reinterpret_cast<const double *>(st->d.get() + sc_at) : nullptr;
   st->out_at = in_bytes;
-  double *d_out = reinterpret_cast<double *>(st->d + in_bytes);
+  double *d_out = reinterpret_cast<double *>(st->d.get() + in_bytes);
   *d_rect_out = d_out;
   a.m.scores = d_out + 4 * n_out;
   a.m.level_out = reinterpret_cast<int *>(d_out + 5 * n_out);
-  a.m.terms = terms ? st->d_terms : nullptr;
+  a.m.terms = terms ? st->d_terms.get() : nullptr;
   a.m.n = n;
   a.m.oie = cfg->oie;
   a.m.oope = cfg->oope;
@@ -687,37 +652,25 @@ int pyr_many_fetch(slamhip_ctx *ctx, size_t n_out, bool with_rect, double *rect_
   PyrManyStage *st = static_cast<PyrManyStage *>(ctx->pyr_many);
   // rect | score | level per output, as the kernels wrote them; the rectangles are skipped where nobody wrote them
   const size_t skip = with_rect ? 0 : sizeof(double) * 4 * n_out;
-  SLAMHIP_CHECK(hipMemcpyAsync(st->h + st->out_at + skip, st->d + st->out_at + skip, many_out_bytes(n_out) - skip,
+  SLAMHIP_CHECK(hipMemcpyAsync(st->h.get() + st->out_at + skip, st->d.get() + st->out_at + skip, many_out_bytes(n_out) - skip,
                                hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  const double *h_out = reinterpret_cast<const double *>(st->h + st->out_at);
+  const double *h_out = reinterpret_cast<const double *>(st->h.get() + st->out_at);
   if (with_rect) std::memcpy(rect_out, h_out, sizeof(double) * 4 * n_out);
   std::memcpy(score_out, h_out + 4 * n_out, sizeof(double) * n_out);
   std::memcpy(level_out, h_out + 5 * n_out, sizeof(int) * n_out);
   return SLAMHIP_OK;
 }
 
-void pyr_free_staging(slamhip_pyramid *p) {
-  if (p->d_in) (void)hipFree(p->d_in);
-  if (p->d_scores) (void)hipFree(p->d_scores);
-  if (p->d_levels) (void)hipFree(p->d_levels);
-  if (p->d_terms) (void)hipFree(p->d_terms);
-  if (p->d_x_in) (void)hipFree(p->d_x_in);
-  if (p->d_x_out) (void)hipFree(p->d_x_out);
-  if (p->h_x) (void)hipHostFree(p->h_x);
-  if (p->d_raw) (void)hipFree(p->d_raw);
-  p->d_in = p->d_scores = p->d_terms = p->d_x_in = p->d_x_out = p->h_x = p->d_raw = nullptr;
-  p->d_levels = nullptr;
-  p->in_cap = p->x_parent_cap = 0;
-  p->terms_cap = p->x_slot_cap = p->raw_cap = 0;
-}
+void pyr_free_staging(slamhip_pyramid *p) { static_cast<slamhip_pyramid_staging &>(*p) = slamhip_pyramid_staging(); }
 
 // slamhip_pyramid_refresh_batch's job tables, kept by the context: one block in HBM and two pinned ones taking turns.
 // The call does not wait, so the copy of a table may still be pending when the next call fills one: a pinned block is
 // written only after the event behind its last copy has passed (the block in HBM is rewritten in stream order, behind
 // the kernels that read it).
 struct PyrRefreshStage {
-  char *h[2] = {nullptr, nullptr}, *d = nullptr;
+  PinnedBuf<char> h[2];
+  DeviceBuf<char> d;
   hipEvent_t copied[2] = {nullptr, nullptr};
   bool pending[2] = {false, false};
   size_t cap = 0;
@@ -725,22 +678,10 @@ struct PyrRefreshStage {
   pyr_plan::Plan plan;  // of the last call that was not refused
 };
 
-static void pyr_refresh_free_blocks(PyrRefreshStage *st) {
-  for (int k = 0; k < 2; ++k) {
-    if (st->h[k]) (void)hipHostFree(st->h[k]);
-    st->h[k] = nullptr;
-    st->pending[k] = false;
-  }
-  if (st->d) (void)hipFree(st->d);
-  st->d = nullptr;
-  st->cap = 0;
-}
-
 static void pyr_refresh_release(slamhip_ctx *ctx) {
   PyrRefreshStage *st = static_cast<PyrRefreshStage *>(ctx->pyr_refresh);
   if (!st) return;
   (void)hipStreamSynchronize(ctx->stream);
-  pyr_refresh_free_blocks(st);
   for (int k = 0; k < 2; ++k)
     if (st->copied[k]) (void)hipEventDestroy(st->copied[k]);
   delete st;
@@ -880,18 +821,18 @@ int slamhip_pyramid_refresh_batch(slamhip_ctx *ctx, int n_jobs, const slamhip_py
   PyrRefreshStage *st = static_cast<PyrRefreshStage *>(ctx->pyr_refresh);
   for (int k = 0; k < 2; ++k)
     if (!st->copied[k]) SLAMHIP_CHECK(hipEventCreateWithFlags(&st->copied[k], hipEventDisableTiming));
-  if (plan.table_bytes > st->cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    pyr_refresh_free_blocks(st);
-    size_t cap = 1 << 14;
-    while (cap < plan.table_bytes) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&st->d, cap));
-    for (int k = 0; k < 2; ++k) SLAMHIP_CHECK(hipHostMalloc(&st->h[k], cap, hipHostMallocDefault));
-    st->cap = cap;
+  {
+    const int rc = grow_blocks({ctx->stream}, st->cap, plan.table_bytes, 1 << 14, [&](size_t cap) -> int {
+      st->pending[0] = st->pending[1] = false;  // (the stream has been waited for)
+      SLAMHIP_CHECK(st->d.alloc(cap));
+      for (int k = 0; k < 2; ++k) SLAMHIP_CHECK(st->h[k].alloc(cap));
+      return SLAMHIP_OK;
+    });
+    if (rc) return rc;
   }
-  const PyrReduceEntry *d_entries = reinterpret_cast<const PyrReduceEntry *>(st->d);
-  const unsigned *d_off = reinterpret_cast<const unsigned *>(st->d + plan.off_bytes_at);
-  const int *d_runs = reinterpret_cast<const int *>(st->d + plan.run_bytes_at);
+  const PyrReduceEntry *d_entries = reinterpret_cast<const PyrReduceEntry *>(st->d.get());
+  const unsigned *d_off = reinterpret_cast<const unsigned *>(st->d.get() + plan.off_bytes_at);
+  const int *d_runs = reinterpret_cast<const int *>(st->d.get() + plan.run_bytes_at);
   if (plan.table_bytes) {
     const int turn = st->turn;
     st->turn ^= 1;
@@ -899,7 +840,7 @@ int slamhip_pyramid_refresh_batch(slamhip_ctx *ctx, int n_jobs, const slamhip_py
       SLAMHIP_CHECK(hipEventSynchronize(st->copied[turn]));
       st->pending[turn] = false;
     }
-    char *h = st->h[turn];
+    char *h = st->h[turn].get();
     std::memset(h, 0, plan.table_bytes);
     PyrReduceEntry *h_entries = reinterpret_cast<PyrReduceEntry *>(h);
     for (size_t i = 0; i < plan.entries.size(); ++i) {
@@ -910,8 +851,8 @@ int slamhip_pyramid_refresh_batch(slamhip_ctx *ctx, int n_jobs, const slamhip_py
       const DeviceMap &dst = ctx->maps[p->first_id + lv - 1];
       const bool top = lv == p->plan.n;
       PyrReduceEntry &e = h_entries[i];
-      e.src = level_of(src, lv == 1 ? nullptr : p->d_coord[lv - 2]);
-      e.dst = level_of(dst, p->d_coord[lv - 1]);
+      e.src = level_of(src, lv == 1 ? nullptr : p->d_coord[lv - 2].get());
+      e.dst = level_of(dst, p->d_coord[lv - 1].get());
       e.bias_x = top ? 0 : src.origin_x - 2 * dst.origin_x;
       e.bias_y = top ? 0 : src.origin_y - 2 * dst.origin_y;
       e.cx0 = r.win.cx0;
@@ -932,7 +873,7 @@ int slamhip_pyramid_refresh_batch(slamhip_ctx *ctx, int n_jobs, const slamhip_py
         h_runs[2 * (s.run_at + k) + 1] = s.tail[k].n_entries;
       }
     }
-    SLAMHIP_CHECK(hipMemcpyAsync(st->d, h, plan.table_bytes, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(st->d.get(), h, plan.table_bytes, hipMemcpyHostToDevice, ctx->stream));
     SLAMHIP_CHECK(hipEventRecord(st->copied[turn], ctx->stream));
     st->pending[turn] = true;
   }
@@ -1036,21 +977,13 @@ int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const sl
     rc = pyr_raw_prepare(ctx, &fma, &d_angle);
     if (rc) return rc;
   }
-  if (n > p->in_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (p->d_in) (void)hipFree(p->d_in);
-    if (p->d_scores) (void)hipFree(p->d_scores);
-    if (p->d_levels) (void)hipFree(p->d_levels);
-    p->d_in = p->d_scores = nullptr;
-    p->d_levels = nullptr;
-    p->in_cap = 0;
-    int cap = 256;
-    while (cap < n) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&p->d_in, sizeof(double) * 7 * cap));
-    SLAMHIP_CHECK(hipMalloc(&p->d_scores, sizeof(double) * cap));
-    SLAMHIP_CHECK(hipMalloc(&p->d_levels, sizeof(int) * cap));
-    p->in_cap = cap;
-  }
+  rc = grow_blocks({ctx->stream}, p->in_cap, (size_t)n, 256, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(p->d_in.alloc(7 * cap));
+    SLAMHIP_CHECK(p->d_scores.alloc(cap));
+    SLAMHIP_CHECK(p->d_levels.alloc(cap));
+    return SLAMHIP_OK;
+  });
+  if (rc) return rc;
   const bool host_trig = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST;
   std::vector<double> stage((size_t)n * 7);
   std::memcpy(stage.data(), rotation, sizeof(double) * n);
@@ -1063,19 +996,19 @@ int slamhip_pyramid_score_matches(slamhip_ctx *ctx, slamhip_pyramid *p, const sl
     pyr_raw_rows(n, rotation, reinterpret_cast<int *>(stage.data() + 6 * (size_t)n), &rot_rows);
     std::memcpy(stage.data() + 5 * (size_t)n, rot_rows.data(), sizeof(double) * rot_rows.size());
   }
-  SLAMHIP_CHECK(hipMemcpyAsync(p->d_in, stage.data(), sizeof(double) * (host_trig || raw ? 7 : 5) * n, hipMemcpyHostToDevice,
+  SLAMHIP_CHECK(hipMemcpyAsync(p->d_in.get(), stage.data(), sizeof(double) * (host_trig || raw ? 7 : 5) * n, hipMemcpyHostToDevice,
                                ctx->stream));
   RawTrig rt{};
   if (raw) {
-    rc = pyr_raw_queue_table(p, fma, p->d_in + 5 * (size_t)n, (int)rot_rows.size(), base_pose[2], d_angle, ctx->scan_n, &rt);
+    rc = pyr_raw_queue_table(p, fma, p->d_in.get() + 5 * (size_t)n, (int)rot_rows.size(), base_pose[2], d_angle, ctx->scan_n, &rt);
     if (rc) return rc;
-    rt.row = reinterpret_cast<const int *>(p->d_in + 6 * (size_t)n);
+    rt.row = reinterpret_cast<const int *>(p->d_in.get() + 6 * (size_t)n);
   }
-  rc = queue_score(p, cfg, base_pose, n, p->d_in, p->d_in + n, host_trig ? p->d_in + 5 * (size_t)n : nullptr,
-                   raw ? &rt : nullptr, p->d_scores, p->d_levels);
+  rc = queue_score(p, cfg, base_pose, n, p->d_in.get(), p->d_in.get() + n, host_trig ? p->d_in.get() + 5 * (size_t)n : nullptr,
+                   raw ? &rt : nullptr, p->d_scores.get(), p->d_levels.get());
   if (rc) return rc;
-  SLAMHIP_CHECK(hipMemcpyAsync(score_out, p->d_scores, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(level_out, p->d_levels, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(score_out, p->d_scores.get(), sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(level_out, p->d_levels.get(), sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return SLAMHIP_OK;
 }

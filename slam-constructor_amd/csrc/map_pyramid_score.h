@@ -7,7 +7,27 @@
 #include "map_pyramid_device.h"
 #include "score_device.h"
 
-struct slamhip_pyramid {
+// a pyramid's staging in HBM and pinned memory, apart from the levels: gone with the pyramid, or -- the object outlives
+// its context -- when the context goes (pyr_free_staging assigns an empty one)
+struct slamhip_pyramid_staging {
+  // slamhip_pyramid_score_matches' staging in HBM: rotation | rect | sin, cos per candidate; scores; levels; terms
+  slamhip::DeviceBuf<double> d_in, d_scores, d_terms;
+  slamhip::DeviceBuf<int> d_levels;
+  int in_cap = 0;
+  size_t terms_cap = 0;
+  // slamhip_pyramid_expand_matches' staging (m3rsm.hip): parents as above; per slot rect | score | level in one block;
+  // h_x: the pinned host side of both
+  slamhip::DeviceBuf<double> d_x_in, d_x_out;
+  slamhip::PinnedBuf<double> h_x;
+  int x_parent_cap = 0;
+  size_t x_slot_cap = 0;
+  // SLAMHIP_POSE_TRIG_RAW_EXACT: the table of exact beam directions of the launch under way (RawTrig), cos rows in front
+  // of the sin rows
+  slamhip::DeviceBuf<double> d_raw;
+  size_t raw_cap = 0;
+};
+
+struct slamhip_pyramid : slamhip_pyramid_staging {
   slamhip_ctx *ctx = nullptr;  // null once the context has gone
   int fine_id = -1, first_id = -1, oie = 0;
   int cell_model = 0;
@@ -15,23 +35,9 @@ struct slamhip_pyramid {
   int fine_w = 0, fine_h = 0, fine_ox = 0, fine_oy = 0;
   const double *fine_payload = nullptr;
   slamhip::pyr::Plan plan{};
-  std::vector<int *> d_coord;               // per level: the fine coordinate of every cell's winner (x, y)
-  std::vector<const double *> lv_payload;   // per level: the payload the table below points at
-  slamhip::MapView *d_views = nullptr;      // plan.n + 1 views, the fine map first
-  // slamhip_pyramid_score_matches' staging in HBM: rotation | rect | sin, cos per candidate; scores; levels; terms
-  double *d_in = nullptr, *d_scores = nullptr, *d_terms = nullptr;
-  int *d_levels = nullptr;
-  int in_cap = 0;
-  size_t terms_cap = 0;
-  // slamhip_pyramid_expand_matches' staging (m3rsm.hip): parents as above; per slot rect | score | level in one block;
-  // h_x: the pinned host side of both
-  double *d_x_in = nullptr, *d_x_out = nullptr, *h_x = nullptr;
-  int x_parent_cap = 0;
-  size_t x_slot_cap = 0;
-  // SLAMHIP_POSE_TRIG_RAW_EXACT: the table of exact beam directions of the launch under way (RawTrig), cos rows in front
-  // of the sin rows
-  double *d_raw = nullptr;
-  size_t raw_cap = 0;
+  std::vector<slamhip::DeviceBuf<int>> d_coord;  // per level: the fine coordinate of every cell's winner (x, y)
+  std::vector<const double *> lv_payload;        // per level: the payload the table below points at
+  slamhip::DeviceBuf<slamhip::MapView> d_views;  // plan.n + 1 views, the fine map first
 };
 
 namespace slamhip {
@@ -110,11 +116,12 @@ int pyr_raw_queue_table(slamhip_pyramid *p, bool fma, const double *d_rot_rows, 
 // one pinned block and one block in HBM, each the inputs (table | terms offsets | rotation | rect | sin, cos | request)
 // in front of the outputs (rect | score | level per slot), and the terms.
 struct PyrManyStage {
-  char *h = nullptr, *d = nullptr;
+  PinnedBuf<char> h;
+  DeviceBuf<char> d;
   size_t cap = 0, out_at = 0;  // out_at: where the outputs of the launch staged last begin
-  double *d_terms = nullptr;
+  DeviceBuf<double> d_terms;
   size_t terms_cap = 0;
-  double *d_raw = nullptr;  // SLAMHIP_POSE_TRIG_RAW_EXACT: the launch's table of beam directions (RawTrig)
+  DeviceBuf<double> d_raw;  // SLAMHIP_POSE_TRIG_RAW_EXACT: the launch's table of beam directions (RawTrig)
   size_t raw_cap = 0;
 };
 void pyr_many_release(slamhip_ctx *ctx);

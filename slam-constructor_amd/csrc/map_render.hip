@@ -140,15 +140,8 @@ bool format_ok(int format) { return format == SLAMHIP_RENDER_OCCGRID || format =
 
 // room for `bytes` in the context's render buffer (kept between calls; a larger request replaces it)
 int render_reserve(slamhip_ctx *ctx, size_t bytes) {
-  if (bytes <= ctx->render_cap) return SLAMHIP_OK;
-  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_render) hipFree(ctx->d_render);
-  ctx->d_render = nullptr;
-  ctx->render_cap = 0;
-  const size_t cap = (bytes + 65535) & ~(size_t)65535;
-  SLAMHIP_CHECK(hipMalloc(&ctx->d_render, cap));
-  ctx->render_cap = cap;
-  return SLAMHIP_OK;
+  // (whole 64 KiB: the floor is the rounded size itself)
+  return grow_block(ctx->stream, ctx->d_render, ctx->render_cap, bytes, (bytes + 65535) & ~(size_t)65535);
 }
 
 dim3 render_grid(int w, int h, int pack) {
@@ -160,18 +153,12 @@ dim3 render_grid(int w, int h, int pack) {
 int render_fetch(slamhip_ctx *ctx, hipEvent_t e1, size_t bytes, void *out) {
   SLAMHIP_CHECK(hipGetLastError());
   if (e1) SLAMHIP_CHECK(hipEventRecord(e1, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(out, ctx->d_render, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(out, ctx->d_render.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return SLAMHIP_OK;
 }
 
 }  // namespace
-
-void render_release(slamhip_ctx *ctx) {
-  if (ctx->d_render) hipFree(ctx->d_render);
-  ctx->d_render = nullptr;
-  ctx->render_cap = 0;
-}
 
 int tile_pool_render(TilePool *tp, int slot, int format, int x0, int y0, int w, int h, void *out) {
   if (!tp || slot < 0 || slot >= tp->n_slots) return render_invalid("bad slot");
@@ -189,7 +176,7 @@ int tile_pool_render(TilePool *tp, int slot, int format, int x0, int y0, int w, 
   if (e0) SLAMHIP_CHECK(hipEventRecord(e0, ctx->stream));
   hipLaunchKernelGGL(k_render_tiled, render_grid(w, h, kTiledPack), dim3(kRenderThreads), 0, ctx->stream, tp->d_pool,
                      tp->d_table() + (size_t)slot * tp->table_stride(), tp->tiles_x, tp->tiles_y,
-                     (long long)x0 + tp->origin_x, (long long)y0 + tp->origin_y, w, h, format, tp->unknown[0], ctx->d_render);
+                     (long long)x0 + tp->origin_x, (long long)y0 + tp->origin_y, w, h, format, tp->unknown[0], ctx->d_render.get());
   return render_fetch(ctx, e1, bytes, out);
 }
 
@@ -216,10 +203,10 @@ int slamhip_map_render(slamhip_ctx *ctx, int map_id, int format, int occ_kind, i
   if (e0) SLAMHIP_CHECK(hipEventRecord(e0, ctx->stream));
   if (cell_doubles(m.cell_model) == 1)
     hipLaunchKernelGGL(k_render_dense<1>, render_grid(w, h, RenderPack<1>::n), dim3(kRenderThreads), 0, ctx->stream, m.d_payload,
-                       m.pitch, m.cell_model, occ_kind, format, x0, y0, w, h, ctx->d_render);
+                       m.pitch, m.cell_model, occ_kind, format, x0, y0, w, h, ctx->d_render.get());
   else
     hipLaunchKernelGGL(k_render_dense<4>, render_grid(w, h, RenderPack<4>::n), dim3(kRenderThreads), 0, ctx->stream, m.d_payload,
-                       m.pitch, m.cell_model, occ_kind, format, x0, y0, w, h, ctx->d_render);
+                       m.pitch, m.cell_model, occ_kind, format, x0, y0, w, h, ctx->d_render.get());
   return render_fetch(ctx, e1, bytes, out);
 }
 

@@ -74,35 +74,35 @@ namespace {
 constexpr int kNearR = 16, kNearSide = 2 * kNearR + 1, kNearMaxWords = 64;
 struct MuScratch {
   size_t cap_records = 0, cap_beams = 0, temp_bytes = 0;
-  unsigned *counts = nullptr, *offsets = nullptr, *keys = nullptr, *keys_sorted = nullptr;
-  unsigned *order = nullptr, *order_sorted = nullptr;  // the beam of every record, before / after the sort
-  double *beam_end = nullptr, *scan = nullptr;
-  MuBeam *beam_info = nullptr;
-  double *srt_prob = nullptr, *srt_qual = nullptr;  // sorted records
-  int *occ = nullptr, *error_flag = nullptr;
-  unsigned long long *n_updates = nullptr;  // one word: padding records of the update
-  unsigned long long *h_status = nullptr;   // pinned: (error flag, padding records) of the last update
-  void *temp = nullptr;
+  DeviceBuf<unsigned> counts, offsets, keys, keys_sorted;
+  DeviceBuf<unsigned> order, order_sorted;  // the beam of every record, before / after the sort
+  DeviceBuf<double> beam_end, scan;
+  DeviceBuf<MuBeam> beam_info;
+  DeviceBuf<double> srt_prob, srt_qual;  // sorted records
+  DeviceBuf<int> occ, error_flag;
+  DeviceBuf<unsigned long long> n_updates;  // one word: padding records of the update
+  PinnedBuf<unsigned long long> h_status;   // (error flag, padding records) of the last update
+  DeviceBuf<unsigned char> temp;
   // counting sort of a plain call's records (k_mu_rank): per-cell record counts of the key window (all zero between
   // updates), chain starts, the records as scattered
   size_t cap_bins = 0, scan_temp_bytes = 0;
-  unsigned *bins = nullptr, *offs = nullptr;
-  uint2 *srec = nullptr;  // (key, beam) of every record, as scattered into its cell's chain
-  unsigned *h_offsets = nullptr;  // pinned: first record slot of every beam, computed by the host (x offset_slots)
+  DeviceBuf<unsigned> bins, offs;
+  DeviceBuf<uint2> srec;  // (key, beam) of every record, as scattered into its cell's chain
+  PinnedBuf<unsigned> h_offsets;  // first record slot of every beam, computed by the host (x offset_slots)
   int offset_slots = 1;
   long long carried_updates = 0;   // cell updates of queued updates the ring collected by itself when it was full
-  double *h_scan_stage = nullptr;  // pinned, kRing x 3 cap_beams (scans of up to 8192 points)
-  int *h_occ_stage = nullptr;
-  unsigned long long *near_bits = nullptr;  // [kNearSide^2][64] words: beams (up to 4096) visiting the cells next to the robot
-  void *scan_temp = nullptr;
+  PinnedBuf<double> h_scan_stage;  // kRing x 3 cap_beams (scans of up to 8192 points)
+  PinnedBuf<int> h_occ_stage;
+  DeviceBuf<unsigned long long> near_bits;  // [kNearSide^2][64] words: beams (up to 4096) visiting the cells next to the robot
+  DeviceBuf<unsigned char> scan_temp;
   // the gather form of a plain call (map_update_gather.h): per-beam closed forms, the irregular-cell bitmap of the key
   // window (all zero between updates), the workgroup counter of k_mu_cells, and what is known about the scanner's
   // beam directions -- analysed when they change (a scanner's angles do not change from scan to scan)
   int force_path = 0;  // SLAMHIP_OPT_K6_PATH of the context: 0 the fastest that applies, 1 counting sort, 2 radix sort
-  MuLine *lines = nullptr;
+  DeviceBuf<MuLine> lines;
   size_t cap_lines = 0, cap_irr_words = 0;
-  unsigned *irr_bits = nullptr, *d_lut = nullptr;
-  unsigned char *bad = nullptr;
+  DeviceBuf<unsigned> irr_bits, d_lut;
+  DeviceBuf<unsigned char> bad;
   std::vector<double> geo_cos, geo_sin;
   bool geo_ok = false;
   double geo_a0 = 0.0;
@@ -111,12 +111,12 @@ struct MuScratch {
   // a pinned ring and are summed up by mu_drain
   bool deferred = false;
   int pending = 0;
-  unsigned long long *h_ring = nullptr;  // kRing x (error flag, padding records)
+  PinnedBuf<unsigned long long> h_ring;  // kRing x (error flag, padding records)
   unsigned ring_total[64] = {0};
   // ... written by the update kernels into slot `pending` of these device arrays and handed over by ONE
   // k_mu_finish_ring per drain (a finish kernel per update was 4.3 us of every particle's turn)
-  int *d_ring_err = nullptr;
-  unsigned long long *d_ring_pad = nullptr;
+  DeviceBuf<int> d_ring_err;
+  DeviceBuf<unsigned long long> d_ring_pad;
   // scan re-use (see slamhip_map_append_scan)
   bool reuse_ok = false;
   std::vector<double> raw_cos, raw_sin;  // slamhip_map_append_scan_raw: cos / sin(theta + a) of the call
@@ -158,8 +158,8 @@ int mu_drain(slamhip_ctx *ctx, long long *n_updates, int *err) {
   }
   unsigned seq = ++ctx->seq;
   if (seq == 0) seq = ++ctx->seq;
-  hipLaunchKernelGGL(k_mu_finish_ring, dim3(1), dim3(64), 0, ctx->stream, sc.d_ring_err, sc.d_ring_pad, sc.pending,
-                     sc.h_ring, ctx->h_done_flag, seq);
+  hipLaunchKernelGGL(k_mu_finish_ring, dim3(1), dim3(64), 0, ctx->stream, sc.d_ring_err.get(), sc.d_ring_pad.get(), sc.pending,
+                     sc.h_ring.get(), ctx->h_done_flag.get(), seq);
   SLAMHIP_CHECK(hipGetLastError());
   const int rc = score_wait(ctx, seq);
   if (rc) {
@@ -169,8 +169,8 @@ int mu_drain(slamhip_ctx *ctx, long long *n_updates, int *err) {
   long long nu = 0;
   int e = 0;
   for (int k = 0; k < sc.pending; ++k) {
-    const unsigned long long fl = ((volatile unsigned long long *)sc.h_ring)[2 * k];
-    const unsigned long long pad = ((volatile unsigned long long *)sc.h_ring)[2 * k + 1];
+    const unsigned long long fl = ((volatile unsigned long long *)sc.h_ring.get())[2 * k];
+    const unsigned long long pad = ((volatile unsigned long long *)sc.h_ring.get())[2 * k + 1];
     if (fl) e = (int)fl;
     nu += (long long)sc.ring_total[k] - (long long)pad;
   }
@@ -204,7 +204,7 @@ int mu_finish(slamhip_ctx *ctx, const int *d_error_flag, const unsigned long lon
     unsigned seq = ++ctx->seq;
     if (seq == 0) seq = ++ctx->seq;
     hipLaunchKernelGGL(k_mu_finish, dim3(1), dim3(1), 0, ctx->stream, d_error_flag, d_n_padding, h_status,
-                       ctx->h_done_flag, seq);
+                       ctx->h_done_flag.get(), seq);
     SLAMHIP_CHECK(hipGetLastError());
     const int rc = score_wait(ctx, seq);
     if (rc) return rc;
@@ -285,9 +285,9 @@ int mu_scan_geometry(slamhip_ctx *ctx, MuScratch &sc, int n, const double *cos_a
   double a0 = 0.0;
   int near_r = 8;
   if (!mu_analyse_directions(n, cos_a, sin_a, lut, &a0, &near_r)) return SLAMHIP_OK;
-  if (!sc.d_lut) SLAMHIP_CHECK(hipMalloc(&sc.d_lut, sizeof(unsigned) * (kGatherLut + 1)));
+  if (!sc.d_lut) SLAMHIP_CHECK(sc.d_lut.alloc(kGatherLut + 1));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));  // (queued updates may still read the old table)
-  SLAMHIP_CHECK(hipMemcpy(sc.d_lut, lut.data(), sizeof(unsigned) * (kGatherLut + 1), hipMemcpyHostToDevice));
+  SLAMHIP_CHECK(hipMemcpy(sc.d_lut.get(), lut.data(), sizeof(unsigned) * (kGatherLut + 1), hipMemcpyHostToDevice));
   sc.geo_a0 = a0;
   sc.geo_near_r = near_r;
   sc.geo_ok = true;
@@ -310,14 +310,16 @@ struct MuScannerTable {
   bool ok = false;
   double a0 = 0.0;
   int near_r = 8;
-  unsigned *d_lut = nullptr;
+  DeviceBuf<unsigned> d_lut;
   unsigned long long used = 0, used_call = 0;  // least recently used goes first; never a table of the running call
 };
 struct MuFleetScratch {
-  unsigned char *arena = nullptr, *h_stage = nullptr, *d_table = nullptr, *h_table = nullptr;
+  DeviceBuf<unsigned char> arena, d_table;
+  PinnedBuf<unsigned char> h_stage, h_table;
   size_t cap_arena = 0, cap_stage = 0, cap_table = 0, cap_htable = 0, cap_irr = 0, cap_status = 0;
-  unsigned *irr = nullptr;  // the marker words of all jobs' key windows: all zero between calls
-  unsigned long long *d_status = nullptr, *h_status = nullptr;  // per job (padding records, error flag)
+  DeviceBuf<unsigned> irr;  // the marker words of all jobs' key windows: all zero between calls
+  DeviceBuf<unsigned long long> d_status;  // per job (padding records, error flag)
+  PinnedBuf<unsigned long long> h_status;
   std::vector<MuScannerTable> scanners;
   unsigned long long tick = 0, call = 0;
   long long table_uploads = 0;
@@ -371,8 +373,8 @@ int mu_scanner_table(MuFleetScratch &fs, int n, bool from_angle, const double *k
   }
   if (t.ok) {
     // (no kernel of an earlier batch is in flight -- the call is awaited -- and lone updates read their own table)
-    if (!t.d_lut) SLAMHIP_CHECK(hipMalloc(&t.d_lut, sizeof(unsigned) * (kGatherLut + 1)));
-    SLAMHIP_CHECK(hipMemcpy(t.d_lut, lut.data(), sizeof(unsigned) * (kGatherLut + 1), hipMemcpyHostToDevice));
+    if (!t.d_lut) SLAMHIP_CHECK(t.d_lut.alloc(kGatherLut + 1));
+    SLAMHIP_CHECK(hipMemcpy(t.d_lut.get(), lut.data(), sizeof(unsigned) * (kGatherLut + 1), hipMemcpyHostToDevice));
     ++fs.table_uploads;
   }
   *index = slot;
@@ -394,19 +396,16 @@ struct MuFleetJob {
   int scanner = -1;
 };
 
-template <typename T>
-int mu_fleet_reserve(T **p, size_t *cap, size_t need, size_t floor_, bool pinned) {
-  if (need <= *cap) return SLAMHIP_OK;
-  const size_t ncap = mu_plan::grow_capacity(*cap, need, floor_);
-  if (*p) {
-    if (pinned) hipHostFree(*p);
-    else hipFree(*p);
-  }
-  *p = nullptr;
-  *cap = 0;
-  if (pinned) SLAMHIP_CHECK(hipHostMalloc((void **)p, ncap, hipHostMallocDefault));
-  else SLAMHIP_CHECK(hipMalloc((void **)p, ncap));
-  *cap = ncap;
+// The update-only plane of a map (DeviceMap::d_aux), made -- all zero -- by the first update whose rule keeps counters.
+// A DeviceMap's planes change hands in slamhip_map_bind, which frees them: they stay raw pointers.
+int mu_aux_plane(slamhip_ctx *ctx, DeviceMap &m, int aux_stride) {
+  if (!aux_stride || (m.aux_stride == aux_stride && m.d_aux)) return SLAMHIP_OK;
+  if (m.d_aux) hipFree(m.d_aux);
+  m.d_aux = nullptr;
+  const size_t bytes = (size_t)m.pitch * m.height * aux_stride * sizeof(double);
+  SLAMHIP_CHECK(hipMalloc(&m.d_aux, bytes));
+  SLAMHIP_CHECK(hipMemsetAsync(m.d_aux, 0, bytes, ctx->stream));
+  m.aux_stride = aux_stride;
   return SLAMHIP_OK;
 }
 
@@ -436,15 +435,8 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
       if (rc) return rc;
       ctx->maps[jb.map_id].grown = grown;
     }
-    DeviceMap &m = ctx->maps[jb.map_id];
-    if (aux_stride && (m.aux_stride != aux_stride || !m.d_aux)) {
-      if (m.d_aux) hipFree(m.d_aux);
-      m.d_aux = nullptr;
-      const size_t bytes = (size_t)m.pitch * m.height * aux_stride * sizeof(double);
-      SLAMHIP_CHECK(hipMalloc(&m.d_aux, bytes));
-      SLAMHIP_CHECK(hipMemsetAsync(m.d_aux, 0, bytes, ctx->stream));
-      m.aux_stride = aux_stride;
-    }
+    const int arc = mu_aux_plane(ctx, ctx->maps[jb.map_id], aux_stride);
+    if (arc) return arc;
   }
   // arena, grids
   std::vector<mu_plan::JobShape> shapes;
@@ -459,35 +451,27 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
   if (!gp.fits) return fail("the batch needs more than 2^31 workgroups in one launch: split it");
   const size_t table_bytes = mu_plan::align_up(sizeof(MuBatchJob) * K) + 2 * sizeof(unsigned) * (K + 1);
   {
-    int rc = mu_fleet_reserve(&fs.arena, &fs.cap_arena, lay.arena_bytes, (size_t)1 << 20, false);
-    if (!rc) rc = mu_fleet_reserve(&fs.h_stage, &fs.cap_stage, lay.upload_bytes, (size_t)1 << 18, true);
-    if (!rc) rc = mu_fleet_reserve(&fs.d_table, &fs.cap_table, table_bytes, (size_t)1 << 14, false);
-    if (!rc) rc = mu_fleet_reserve(&fs.h_table, &fs.cap_htable, table_bytes, (size_t)1 << 14, true);
+    hipStream_t st = ctx->stream;
+    int rc = grow_block(st, fs.arena, fs.cap_arena, lay.arena_bytes, (size_t)1 << 20);
+    if (!rc) rc = grow_block(st, fs.h_stage, fs.cap_stage, lay.upload_bytes, (size_t)1 << 18);
+    if (!rc) rc = grow_block(st, fs.d_table, fs.cap_table, table_bytes, (size_t)1 << 14);
+    if (!rc) rc = grow_block(st, fs.h_table, fs.cap_htable, table_bytes, (size_t)1 << 14);
+    if (!rc) rc = grow_blocks({st}, fs.cap_irr, lay.irr_words, (size_t)1 << 16, [&](size_t cap) -> int {
+      SLAMHIP_CHECK(fs.irr.alloc(cap));  // (all zero: nothing to carry over)
+      SLAMHIP_CHECK(hipMemsetAsync(fs.irr.get(), 0, sizeof(unsigned) * cap, st));
+      return SLAMHIP_OK;
+    });
+    if (!rc) rc = grow_blocks({st}, fs.cap_status, (size_t)K, 64, [&](size_t cap) -> int {
+      SLAMHIP_CHECK(fs.d_status.alloc(2 * cap));
+      SLAMHIP_CHECK(hipMemsetAsync(fs.d_status.get(), 0, 2 * sizeof(unsigned long long) * cap, st));
+      SLAMHIP_CHECK(fs.h_status.alloc(2 * cap));
+      return SLAMHIP_OK;
+    });
     if (rc) return rc;
   }
-  if (lay.irr_words > fs.cap_irr) {
-    const size_t cap = mu_plan::grow_capacity(fs.cap_irr, lay.irr_words, (size_t)1 << 16);
-    if (fs.irr) hipFree(fs.irr);  // (all zero: nothing to carry over)
-    fs.irr = nullptr;
-    fs.cap_irr = 0;
-    SLAMHIP_CHECK(hipMalloc(&fs.irr, sizeof(unsigned) * cap));
-    SLAMHIP_CHECK(hipMemsetAsync(fs.irr, 0, sizeof(unsigned) * cap, ctx->stream));
-    fs.cap_irr = cap;
-  }
-  if ((size_t)K > fs.cap_status) {
-    const size_t cap = mu_plan::grow_capacity(fs.cap_status, (size_t)K, 64);
-    if (fs.d_status) hipFree(fs.d_status);
-    if (fs.h_status) hipHostFree(fs.h_status);
-    fs.d_status = fs.h_status = nullptr;
-    fs.cap_status = 0;
-    SLAMHIP_CHECK(hipMalloc(&fs.d_status, 2 * sizeof(unsigned long long) * cap));
-    SLAMHIP_CHECK(hipMemsetAsync(fs.d_status, 0, 2 * sizeof(unsigned long long) * cap, ctx->stream));
-    SLAMHIP_CHECK(hipHostMalloc(&fs.h_status, 2 * sizeof(unsigned long long) * cap, hipHostMallocDefault));
-    fs.cap_status = cap;
-  }
   // staging: all scans of the round in one block, one copy
-  MuBatchJob *tj = reinterpret_cast<MuBatchJob *>(fs.h_table);
-  unsigned *t_line = reinterpret_cast<unsigned *>(fs.h_table + mu_plan::align_up(sizeof(MuBatchJob) * K));
+  MuBatchJob *tj = reinterpret_cast<MuBatchJob *>(fs.h_table.get());
+  unsigned *t_line = reinterpret_cast<unsigned *>(fs.h_table.get() + mu_plan::align_up(sizeof(MuBatchJob) * K));
   unsigned *t_cell = t_line + (K + 1);
   for (int i = 0; i < K; ++i) {
     const int k = round[i];
@@ -495,13 +479,13 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
     const MuFleetJob &pj = prep[k];
     const mu_plan::JobSlices &sl = lay.jobs[i];
     const size_t n = (size_t)jb.n;
-    double *st = reinterpret_cast<double *>(fs.h_stage + sl.scan);
+    double *st = reinterpret_cast<double *>(fs.h_stage.get() + sl.scan);
     std::memcpy(st, jb.range, sizeof(double) * n);
     std::memcpy(st + n, pj.cos_a, sizeof(double) * n);
     std::memcpy(st + 2 * n, pj.sin_a, sizeof(double) * n);
     if (jb.quality) std::memcpy(st + 3 * n, jb.quality, sizeof(double) * n);
-    if (jb.is_occ) std::memcpy(fs.h_stage + sl.occ, jb.is_occ, sizeof(int) * n);
-    std::memcpy(fs.h_stage + sl.host_offsets, pj.h_off.data(), sizeof(unsigned) * n);
+    if (jb.is_occ) std::memcpy(fs.h_stage.get() + sl.occ, jb.is_occ, sizeof(int) * n);
+    std::memcpy(fs.h_stage.get() + sl.host_offsets, pj.h_off.data(), sizeof(unsigned) * n);
 
     const DeviceMap &m = ctx->maps[jb.map_id];
     const MuScannerTable &tab = fs.scanners[pj.scanner];
@@ -523,11 +507,11 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
     a.cell_dbl = cell_doubles(m.cell_model);
     a.aux_stride = aux_stride;
     a.scale = m.scale;
-    const double *d_scan = reinterpret_cast<const double *>(fs.arena + sl.scan);
+    const double *d_scan = reinterpret_cast<const double *>(fs.arena.get() + sl.scan);
     a.range = d_scan;
     a.cos_a = d_scan + n;
     a.sin_a = d_scan + 2 * n;
-    a.is_occ = jb.is_occ ? reinterpret_cast<const int *>(fs.arena + sl.occ) : nullptr;
+    a.is_occ = jb.is_occ ? reinterpret_cast<const int *>(fs.arena.get() + sl.occ) : nullptr;
     a.beam_quality = jb.quality ? d_scan + 3 * n : nullptr;
     a.n = jb.n;
     a.px = pj.pose[0];
@@ -543,16 +527,16 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
     a.base_empty_qual = jc->base_empty_qual;
     a.blur = jc->blur;
     a.max_range_sq = jc->max_range * jc->max_range;
-    a.counts = reinterpret_cast<unsigned *>(fs.arena + sl.counts);
-    a.offsets = reinterpret_cast<unsigned *>(fs.arena + sl.offsets);
-    a.beam_end = reinterpret_cast<double *>(fs.arena + sl.beam_end);
-    a.beam_inv = reinterpret_cast<double *>(fs.arena + sl.beam_inv);
-    a.beam_info = reinterpret_cast<MuBeam *>(fs.arena + sl.beam_info);
-    a.n_padding = fs.d_status + 2 * i;
-    a.error_flag = reinterpret_cast<int *>(fs.d_status + 2 * i + 1);
-    a.host_offsets = reinterpret_cast<const unsigned *>(fs.arena + sl.host_offsets);
+    a.counts = reinterpret_cast<unsigned *>(fs.arena.get() + sl.counts);
+    a.offsets = reinterpret_cast<unsigned *>(fs.arena.get() + sl.offsets);
+    a.beam_end = reinterpret_cast<double *>(fs.arena.get() + sl.beam_end);
+    a.beam_inv = reinterpret_cast<double *>(fs.arena.get() + sl.beam_inv);
+    a.beam_info = reinterpret_cast<MuBeam *>(fs.arena.get() + sl.beam_info);
+    a.n_padding = fs.d_status.get() + 2 * i;
+    a.error_flag = reinterpret_cast<int *>(fs.d_status.get() + 2 * i + 1);
+    a.host_offsets = reinterpret_cast<const unsigned *>(fs.arena.get() + sl.host_offsets);
     a.near_words = (jb.n + 63) / 64;
-    a.keys = fs.arena + sl.keys;
+    a.keys = fs.arena.get() + sl.keys;
     a.keys_cap = (unsigned long long)pj.total;
     a.key_x0 = pj.kw.x0;
     a.key_y0 = pj.kw.y0;
@@ -562,12 +546,12 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
     a.near_r = tab.near_r;
     a.robot_ix = (int)std::floor(a.px / a.scale) + m.origin_x;
     a.robot_iy = (int)std::floor(a.py / a.scale) + m.origin_y;
-    a.lines = reinterpret_cast<MuLine *>(fs.arena + sl.lines);
-    a.lut = tab.d_lut;
+    a.lines = reinterpret_cast<MuLine *>(fs.arena.get() + sl.lines);
+    a.lut = tab.d_lut.get();
     a.lut_bins = kGatherLut;
     ::sincos(pj.heading + tab.a0, &a.rot_s, &a.rot_c);
-    a.irr_bits = fs.irr + sl.irr;
-    a.bad = fs.arena + sl.bad;
+    a.irr_bits = fs.irr.get() + sl.irr;
+    a.bad = fs.arena.get() + sl.bad;
     tj[i].near_blocks = grids[i].near_blocks;
     tj[i].far_blocks = grids[i].far_blocks;
     t_line[i] = gp.line_off[i];
@@ -575,11 +559,11 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
   }
   t_line[K] = gp.line_off[K];
   t_cell[K] = gp.cell_off[K];
-  SLAMHIP_CHECK(hipMemcpyAsync(fs.arena, fs.h_stage, lay.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(fs.d_table, fs.h_table, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(fs.arena.get(), fs.h_stage.get(), lay.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+  SLAMHIP_CHECK(hipMemcpyAsync(fs.d_table.get(), fs.h_table.get(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
   MuBatchTable tb;
-  tb.jobs = reinterpret_cast<const MuBatchJob *>(fs.d_table);
-  tb.line_off = reinterpret_cast<const unsigned *>(fs.d_table + mu_plan::align_up(sizeof(MuBatchJob) * K));
+  tb.jobs = reinterpret_cast<const MuBatchJob *>(fs.d_table.get());
+  tb.line_off = reinterpret_cast<const unsigned *>(fs.d_table.get() + mu_plan::align_up(sizeof(MuBatchJob) * K));
   tb.cell_off = tb.line_off + (K + 1);
   tb.n_jobs = K;
   const dim3 lgrid(gp.line_off[K]), cgrid(gp.cell_off[K]), block(256);
@@ -602,7 +586,7 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
 #undef SLAMHIP_MU_CELLS_BATCH
   unsigned seq = ++ctx->seq;
   if (seq == 0) seq = ++ctx->seq;
-  hipLaunchKernelGGL(k_mu_finish_batch, dim3(1), block, 0, ctx->stream, fs.d_status, 2 * K, fs.h_status, ctx->h_done_flag, seq);
+  hipLaunchKernelGGL(k_mu_finish_batch, dim3(1), block, 0, ctx->stream, fs.d_status.get(), 2 * K, fs.h_status.get(), ctx->h_done_flag.get(), seq);
   SLAMHIP_CHECK(hipGetLastError());
   fs.launches += 3;
   fs.rounds += 1;
@@ -611,15 +595,15 @@ int mu_fleet_round(slamhip_ctx *ctx, MuFleetScratch &fs, const slamhip_scan_adde
   if (wrc) {
     // (what the kernels left behind is unknown: the marker words and status pairs start from zero again)
     hipStreamSynchronize(ctx->stream);
-    hipMemset(fs.irr, 0, sizeof(unsigned) * fs.cap_irr);
-    hipMemset(fs.d_status, 0, 2 * sizeof(unsigned long long) * fs.cap_status);
+    hipMemset(fs.irr.get(), 0, sizeof(unsigned) * fs.cap_irr);
+    hipMemset(fs.d_status.get(), 0, 2 * sizeof(unsigned long long) * fs.cap_status);
     return wrc;
   }
   bool internal = false;
   for (int i = 0; i < K; ++i) {
     const int k = round[i];
-    const unsigned long long pad = ((volatile unsigned long long *)fs.h_status)[2 * i];
-    const int err = (int)((volatile unsigned long long *)fs.h_status)[2 * i + 1];
+    const unsigned long long pad = ((volatile unsigned long long *)fs.h_status.get())[2 * i];
+    const int err = (int)((volatile unsigned long long *)fs.h_status.get())[2 * i + 1];
     n_updates[k] = (long long)((unsigned long long)prep[k].total - pad);
     if (err == 2) internal = true;
     else if (err) {
@@ -689,63 +673,50 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   if (!ok_model) return fail("cell update rule does not fit the map's payload model");
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
   const int aux_stride = rule == SLAMHIP_RULE_MEAN ? 1 : (rule == SLAMHIP_RULE_GMAPPING ? 2 : 0);
-  if (aux_stride && (m.aux_stride != aux_stride || !m.d_aux)) {
-    if (m.d_aux) hipFree(m.d_aux);
-    m.d_aux = nullptr;
-    const size_t bytes = (size_t)m.pitch * m.height * aux_stride * sizeof(double);
-    SLAMHIP_CHECK(hipMalloc(&m.d_aux, bytes));
-    SLAMHIP_CHECK(hipMemsetAsync(m.d_aux, 0, bytes, ctx->stream));
-    m.aux_stride = aux_stride;
+  {
+    const int arc = mu_aux_plane(ctx, m, aux_stride);
+    if (arc) return arc;
   }
   MuScratch &sc = scratch_of(ctx);
-  if ((size_t)n > sc.cap_beams) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (void *p : {(void *)sc.counts, (void *)sc.offsets, (void *)sc.beam_end, (void *)sc.scan, (void *)sc.occ,
-                    (void *)sc.beam_info})
-      if (p) hipFree(p);
-    size_t cap = 2048;
-    while (cap < (size_t)n) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&sc.counts, sizeof(unsigned) * cap));
-    SLAMHIP_CHECK(hipMalloc(&sc.offsets, sizeof(unsigned) * (cap + 1)));
-    SLAMHIP_CHECK(hipMalloc(&sc.beam_end, sizeof(double) * 4 * cap));  // end point + (1/dx, 1/dy)
-    SLAMHIP_CHECK(hipMalloc(&sc.beam_info, sizeof(MuBeam) * cap));
-    SLAMHIP_CHECK(hipMalloc(&sc.scan, sizeof(double) * 4 * cap));  // range | cos | sin | per-point quality
-    SLAMHIP_CHECK(hipMalloc(&sc.occ, sizeof(int) * cap));
+  const int brc = grow_blocks({ctx->stream}, sc.cap_beams, (size_t)n, 2048, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(sc.counts.alloc(cap));
+    SLAMHIP_CHECK(sc.offsets.alloc(cap + 1));
+    SLAMHIP_CHECK(sc.beam_end.alloc(4 * cap));  // end point + (1/dx, 1/dy)
+    SLAMHIP_CHECK(sc.beam_info.alloc(cap));
+    SLAMHIP_CHECK(sc.scan.alloc(4 * cap));  // range | cos | sin | per-point quality
+    SLAMHIP_CHECK(sc.occ.alloc(cap));
     if (!sc.error_flag) {
-      SLAMHIP_CHECK(hipMalloc(&sc.error_flag, sizeof(int)));
-      SLAMHIP_CHECK(hipMemsetAsync(sc.error_flag, 0, sizeof(int), ctx->stream));
+      SLAMHIP_CHECK(sc.error_flag.alloc(1));
+      SLAMHIP_CHECK(hipMemsetAsync(sc.error_flag.get(), 0, sizeof(int), ctx->stream));
     }
     // (queued updates: one slot per update in flight -- the kernels of an update read their slot when they run,
     // not when they are queued; scans too large for 64 slots are awaited)
-    if (sc.h_offsets) hipHostFree(sc.h_offsets);
     sc.offset_slots = cap <= 65536 ? kRing : 1;
-    SLAMHIP_CHECK(hipHostMalloc(&sc.h_offsets, sizeof(unsigned) * (cap + 1) * sc.offset_slots, hipHostMallocDefault));
+    SLAMHIP_CHECK(sc.h_offsets.alloc((cap + 1) * sc.offset_slots));
     // ... and of the scan itself (lidar-sized scans): range | cos | sin packed in pinned memory and sent with one
     // asynchronous copy instead of three staged ones, the point flags with a second
-    if (sc.h_scan_stage) hipHostFree(sc.h_scan_stage);
-    if (sc.h_occ_stage) hipHostFree(sc.h_occ_stage);
-    sc.h_scan_stage = nullptr;
-    sc.h_occ_stage = nullptr;
+    sc.h_scan_stage.reset();
+    sc.h_occ_stage.reset();
     if (cap <= 8192) {
-      SLAMHIP_CHECK(hipHostMalloc(&sc.h_scan_stage, sizeof(double) * 4 * cap * kRing, hipHostMallocDefault));
-      SLAMHIP_CHECK(hipHostMalloc(&sc.h_occ_stage, sizeof(int) * cap * kRing, hipHostMallocDefault));
+      SLAMHIP_CHECK(sc.h_scan_stage.alloc(4 * cap * kRing));
+      SLAMHIP_CHECK(sc.h_occ_stage.alloc(cap * kRing));
     }
-    if (!sc.near_bits)
-      SLAMHIP_CHECK(hipMalloc(&sc.near_bits, sizeof(unsigned long long) * kNearSide * kNearSide * kNearMaxWords));
+    if (!sc.near_bits) SLAMHIP_CHECK(sc.near_bits.alloc((size_t)kNearSide * kNearSide * kNearMaxWords));
     if (!sc.n_updates) {
-      SLAMHIP_CHECK(hipMalloc(&sc.n_updates, sizeof(unsigned long long)));
-      SLAMHIP_CHECK(hipMemsetAsync(sc.n_updates, 0, sizeof(unsigned long long), ctx->stream));
+      SLAMHIP_CHECK(sc.n_updates.alloc(1));
+      SLAMHIP_CHECK(hipMemsetAsync(sc.n_updates.get(), 0, sizeof(unsigned long long), ctx->stream));
     }
-    if (!sc.h_status) SLAMHIP_CHECK(hipHostMalloc(&sc.h_status, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-    if (!sc.h_ring) SLAMHIP_CHECK(hipHostMalloc(&sc.h_ring, 2 * kRing * sizeof(unsigned long long), hipHostMallocDefault));
-    if (!sc.d_ring_err) {
-      SLAMHIP_CHECK(hipMalloc(&sc.d_ring_err, kRing * sizeof(int)));
-      SLAMHIP_CHECK(hipMalloc(&sc.d_ring_pad, kRing * sizeof(unsigned long long)));
-      SLAMHIP_CHECK(hipMemsetAsync(sc.d_ring_err, 0, kRing * sizeof(int), ctx->stream));
-      SLAMHIP_CHECK(hipMemsetAsync(sc.d_ring_pad, 0, kRing * sizeof(unsigned long long), ctx->stream));
+    if (!sc.h_status) SLAMHIP_CHECK(sc.h_status.alloc(2));
+    if (!sc.h_ring) SLAMHIP_CHECK(sc.h_ring.alloc(2 * kRing));
+    if (!sc.d_ring_err || !sc.d_ring_pad) {
+      SLAMHIP_CHECK(sc.d_ring_err.alloc(kRing));
+      SLAMHIP_CHECK(sc.d_ring_pad.alloc(kRing));
+      SLAMHIP_CHECK(hipMemsetAsync(sc.d_ring_err.get(), 0, kRing * sizeof(int), ctx->stream));
+      SLAMHIP_CHECK(hipMemsetAsync(sc.d_ring_pad.get(), 0, kRing * sizeof(unsigned long long), ctx->stream));
     }
-    sc.cap_beams = cap;
-  }
+    return SLAMHIP_OK;
+  });
+  if (brc) return brc;
   const size_t cb = sc.cap_beams;
   // the GMapping filter appends the SAME raw scan once per particle: it brackets its loop with
   // mu_allow_scan_reuse(), and identical host arrays are then uploaded only once
@@ -760,26 +731,26 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
     sc.carried_updates += dn;
     if (de) return fail("a deferred map update reported an error (beam outside the window?)", SLAMHIP_ERR_STATE);
   }
-  if (!reuse && sc.h_scan_stage) {
+  if (!reuse && sc.h_scan_stage.get()) {
     // (slot `pending` while updates are queued -- its last user has been drained; slot 0 otherwise: awaited)
     const size_t slot = deferred ? (size_t)sc.pending : 0;
-    double *st = sc.h_scan_stage + slot * 4 * cb;
+    double *st = sc.h_scan_stage.get() + slot * 4 * cb;
     std::memcpy(st, range, sizeof(double) * n);
     std::memcpy(st + cb, cos_a, sizeof(double) * n);
     std::memcpy(st + 2 * cb, sin_a, sizeof(double) * n);
     if (quality) std::memcpy(st + 3 * cb, quality, sizeof(double) * n);
-    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan, st, sizeof(double) * ((quality ? 3 : 2) * cb + n), hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get(), st, sizeof(double) * ((quality ? 3 : 2) * cb + n), hipMemcpyHostToDevice, ctx->stream));
     if (is_occ) {
-      int *so = sc.h_occ_stage + slot * cb;
+      int *so = sc.h_occ_stage.get() + slot * cb;
       std::memcpy(so, is_occ, sizeof(int) * n);
-      SLAMHIP_CHECK(hipMemcpyAsync(sc.occ, so, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+      SLAMHIP_CHECK(hipMemcpyAsync(sc.occ.get(), so, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
     }
   } else if (!reuse) {
-    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan, range, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan + cb, cos_a, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan + 2 * cb, sin_a, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (quality) SLAMHIP_CHECK(hipMemcpyAsync(sc.scan + 3 * cb, quality, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (is_occ) SLAMHIP_CHECK(hipMemcpyAsync(sc.occ, is_occ, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get(), range, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get() + cb, cos_a, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get() + 2 * cb, sin_a, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    if (quality) SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get() + 3 * cb, quality, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    if (is_occ) SLAMHIP_CHECK(hipMemcpyAsync(sc.occ.get(), is_occ, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
   }
   if (!reuse) {
     sc.last_range = range;
@@ -811,13 +782,13 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   a.cell_dbl = cell_doubles(m.cell_model);
   a.aux_stride = aux_stride;
   a.scale = m.scale;
-  a.range = sc.scan;
-  a.cos_a = sc.scan + cb;
-  a.sin_a = sc.scan + 2 * cb;
-  a.is_occ = is_occ ? sc.occ : nullptr;
+  a.range = sc.scan.get();
+  a.cos_a = sc.scan.get() + cb;
+  a.sin_a = sc.scan.get() + 2 * cb;
+  a.is_occ = is_occ ? sc.occ.get() : nullptr;
   // per-point observation quality (ObservationMappingQualityEstimator::quality, grid_map_scan_adders.h:17-43):
   // a cell update's quality is scan_quality x the value of ITS beam; null = IdleOMQE
-  a.beam_quality = quality ? sc.scan + 3 * cb : nullptr;
+  a.beam_quality = quality ? sc.scan.get() + 3 * cb : nullptr;
   a.n = n;
   a.px = pose[0];
   a.py = pose[1];
@@ -832,16 +803,16 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   a.base_empty_qual = cfg->base_empty_qual;
   a.blur = cfg->blur;
   a.max_range_sq = cfg->max_range * cfg->max_range;
-  a.counts = sc.counts;
-  a.offsets = sc.offsets;
-  a.beam_end = sc.beam_end;
-  a.beam_inv = sc.beam_end + 2 * sc.cap_beams;
-  a.beam_info = sc.beam_info;
-  a.error_flag = sc.error_flag;
-  a.n_padding = sc.n_updates;
+  a.counts = sc.counts.get();
+  a.offsets = sc.offsets.get();
+  a.beam_end = sc.beam_end.get();
+  a.beam_inv = sc.beam_end.get() + 2 * sc.cap_beams;
+  a.beam_info = sc.beam_info.get();
+  a.error_flag = sc.error_flag.get();
+  a.n_padding = sc.n_updates.get();
   if (deferred) {  // queued, not awaited: the status words go to slot `pending` of the ring (mu_drain)
-    a.error_flag = sc.d_ring_err + sc.pending;
-    a.n_padding = sc.d_ring_pad + sc.pending;
+    a.error_flag = sc.d_ring_err.get() + sc.pending;
+    a.n_padding = sc.d_ring_pad.get() + sc.pending;
   }
 
   const dim3 bgrid((n + 255) / 256);
@@ -850,11 +821,11 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
     const int prc = prof.open(ctx, ctx->stream, 1);
     if (prc) return prc;
   }
-  unsigned *const h_off = sc.h_offsets + (deferred ? (size_t)sc.pending * (sc.cap_beams + 1) : 0);
+  unsigned *const h_off = sc.h_offsets.get() + (deferred ? (size_t)sc.pending * (sc.cap_beams + 1) : 0);
   a.host_offsets = h_off;
   const int near_words = (n + 63) / 64;
   if (near_words <= kNearMaxWords) {
-    a.near_bits = sc.near_bits;
+    a.near_bits = sc.near_bits.get();
     a.near_r = kNearR;
     a.near_words = near_words;
   }
@@ -926,27 +897,22 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
     if (n_updates_out) *n_updates_out = 0;
     return SLAMHIP_OK;
   }
-  if (total > sc.cap_records) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (void *p : {(void *)sc.keys, (void *)sc.keys_sorted, (void *)sc.order, (void *)sc.order_sorted,
-                    (void *)sc.srt_prob, (void *)sc.srt_qual, sc.temp, (void *)sc.srec})
-      if (p) hipFree(p);
-    sc.srec = nullptr;
-    size_t cap = 1 << 16;
-    while (cap < total) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&sc.keys, sizeof(unsigned) * cap));
-    SLAMHIP_CHECK(hipMalloc(&sc.keys_sorted, sizeof(unsigned) * cap));
-    SLAMHIP_CHECK(hipMalloc(&sc.order, sizeof(unsigned) * cap));
-    SLAMHIP_CHECK(hipMalloc(&sc.order_sorted, sizeof(unsigned) * cap));
-    SLAMHIP_CHECK(hipMalloc(&sc.srt_prob, sizeof(double) * cap));
-    SLAMHIP_CHECK(hipMalloc(&sc.srt_qual, sizeof(double) * cap));
+  const int rrc = grow_blocks({ctx->stream}, sc.cap_records, (size_t)total, (size_t)1 << 16, [&](size_t cap) -> int {
+    sc.srec.reset();  // (made at the new capacity by the next counting-sorted update)
+    SLAMHIP_CHECK(sc.keys.alloc(cap));
+    SLAMHIP_CHECK(sc.keys_sorted.alloc(cap));
+    SLAMHIP_CHECK(sc.order.alloc(cap));
+    SLAMHIP_CHECK(sc.order_sorted.alloc(cap));
+    SLAMHIP_CHECK(sc.srt_prob.alloc(cap));
+    SLAMHIP_CHECK(sc.srt_qual.alloc(cap));
     sc.temp_bytes = 0;
-    SLAMHIP_CHECK(rocprim::radix_sort_pairs(nullptr, sc.temp_bytes, sc.keys, sc.keys_sorted, sc.order,
-                                            sc.order_sorted, cap, 0, 32, ctx->stream));
-    SLAMHIP_CHECK(hipMalloc(&sc.temp, sc.temp_bytes));
-    sc.cap_records = cap;
-  }
-  a.keys = sc.keys;
+    SLAMHIP_CHECK(rocprim::radix_sort_pairs(nullptr, sc.temp_bytes, sc.keys.get(), sc.keys_sorted.get(), sc.order.get(),
+                                            sc.order_sorted.get(), cap, 0, 32, ctx->stream));
+    SLAMHIP_CHECK(sc.temp.alloc(sc.temp_bytes));
+    return SLAMHIP_OK;
+  });
+  if (rrc) return rrc;
+  a.keys = sc.keys.get();
   a.keys_cap = (unsigned long long)sc.cap_records;
   // the key window: the cells between the robot's and the beams' end cells, clipped to the map (a walk is monotone
   // between its two ends; cells outside the map become padding).  Small enough -- a few hundred thousand cells for
@@ -959,23 +925,18 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   const long long wy1 = std::min((long long)m.height - 1, (long long)bb_hi_y + m.origin_y);
   const long long n_bins = (wx1 >= wx0 && wy1 >= wy0) ? (wx1 - wx0 + 1) * (wy1 - wy0 + 1) : 0;
   const bool counting = !force_radix && n_bins > 0 && n_bins <= (1ll << 23) && near_words <= kNearMaxWords;
-  if (counting && (size_t)n_bins + 1 > sc.cap_bins) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (void *p : {(void *)sc.bins, (void *)sc.offs, sc.scan_temp})
-      if (p) hipFree(p);
-    sc.bins = sc.offs = nullptr;
-    sc.scan_temp = nullptr;
-    size_t cap = 1 << 18;
-    while (cap < (size_t)n_bins + 1) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&sc.bins, sizeof(unsigned) * cap));
-    SLAMHIP_CHECK(hipMemsetAsync(sc.bins, 0, sizeof(unsigned) * cap, ctx->stream));
-    SLAMHIP_CHECK(hipMalloc(&sc.offs, sizeof(unsigned) * cap));
+  const size_t bins_need = counting ? (size_t)n_bins + 1 : 0;
+  const int nrc = grow_blocks({ctx->stream}, sc.cap_bins, bins_need, (size_t)1 << 18, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(sc.bins.alloc(cap));
+    SLAMHIP_CHECK(hipMemsetAsync(sc.bins.get(), 0, sizeof(unsigned) * cap, ctx->stream));
+    SLAMHIP_CHECK(sc.offs.alloc(cap));
     sc.scan_temp_bytes = 0;
-    SLAMHIP_CHECK(rocprim::exclusive_scan(nullptr, sc.scan_temp_bytes, sc.bins, sc.offs, 0u, cap, rocprim::plus<unsigned>(),
-                                          ctx->stream));
-    SLAMHIP_CHECK(hipMalloc(&sc.scan_temp, sc.scan_temp_bytes));
-    sc.cap_bins = cap;
-  }
+    SLAMHIP_CHECK(rocprim::exclusive_scan(nullptr, sc.scan_temp_bytes, sc.bins.get(), sc.offs.get(), 0u, cap,
+                                          rocprim::plus<unsigned>(), ctx->stream));
+    SLAMHIP_CHECK(sc.scan_temp.alloc(sc.scan_temp_bytes));
+    return SLAMHIP_OK;
+  });
+  if (nrc) return nrc;
   // The GATHER form (map_update_gather.h, the default wherever it applies): two kernels, no records.
   // SLAMHIP_OPT_K6_PATH = 1 / 2 keep the record pipelines (the parity tests run all three).
   const bool force_counting = sc.force_path == 1;
@@ -985,28 +946,22 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
     if (grc) return grc;
   }
   if (gather) {
-    if ((size_t)n > sc.cap_lines) {
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (sc.lines) hipFree(sc.lines);
-      sc.lines = nullptr;
-      SLAMHIP_CHECK(hipMalloc(&sc.lines, sizeof(MuLine) * sc.cap_beams));
-      if (sc.bad) hipFree(sc.bad);
-      sc.bad = nullptr;
-      SLAMHIP_CHECK(hipMalloc(&sc.bad, sc.cap_beams + 8));
-      SLAMHIP_CHECK(hipMemsetAsync(sc.bad, 0, sc.cap_beams + 8, ctx->stream));
-      sc.cap_lines = sc.cap_beams;
-    }
-    const size_t words = (size_t)n_bins + 1;  // (a marker word per window cell)
-    if (words > sc.cap_irr_words) {
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (sc.irr_bits) hipFree(sc.irr_bits);
-      sc.irr_bits = nullptr;
-      size_t cap = 1 << 14;
-      while (cap < words) cap *= 2;
-      SLAMHIP_CHECK(hipMalloc(&sc.irr_bits, sizeof(unsigned) * cap));
-      SLAMHIP_CHECK(hipMemsetAsync(sc.irr_bits, 0, sizeof(unsigned) * cap, ctx->stream));
-      sc.cap_irr_words = cap;
-    }
+    // (the per-beam blocks of this form follow cap_beams -- 2048 doubled -- once a scan outgrows them)
+    const size_t lines_need = (size_t)n > sc.cap_lines ? sc.cap_beams : 0;
+    int lrc = grow_blocks({ctx->stream}, sc.cap_lines, lines_need, 2048, [&](size_t cap) -> int {
+      SLAMHIP_CHECK(sc.lines.alloc(cap));
+      SLAMHIP_CHECK(sc.bad.alloc(cap + 8));
+      SLAMHIP_CHECK(hipMemsetAsync(sc.bad.get(), 0, cap + 8, ctx->stream));
+      return SLAMHIP_OK;
+    });
+    // a marker word per window cell
+    const size_t irr_need = (size_t)n_bins + 1;
+    if (!lrc) lrc = grow_blocks({ctx->stream}, sc.cap_irr_words, irr_need, (size_t)1 << 14, [&](size_t cap) -> int {
+      SLAMHIP_CHECK(sc.irr_bits.alloc(cap));
+      SLAMHIP_CHECK(hipMemsetAsync(sc.irr_bits.get(), 0, sizeof(unsigned) * cap, ctx->stream));
+      return SLAMHIP_OK;
+    });
+    if (lrc) return lrc;
     a.key_x0 = (int)wx0;
     a.key_y0 = (int)wy0;
     a.key_w = (int)(wx1 - wx0 + 1);
@@ -1017,12 +972,12 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
     a.near_r = sc.geo_near_r;
     a.robot_ix = (int)std::floor(a.px / a.scale) + m.origin_x;
     a.robot_iy = (int)std::floor(a.py / a.scale) + m.origin_y;
-    a.lines = sc.lines;
-    a.lut = sc.d_lut;
+    a.lines = sc.lines.get();
+    a.lut = sc.d_lut.get();
     a.lut_bins = kGatherLut;
     ::sincos(pose[2] + sc.geo_a0, &a.rot_s, &a.rot_c);
-    a.irr_bits = sc.irr_bits;
-    a.bad = sc.bad;
+    a.irr_bits = sc.irr_bits.get();
+    a.bad = sc.bad.get();
     if (a.est_kind == 1) hipLaunchKernelGGL(k_mu_lines<1>, dim3(n), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(k_mu_lines<0>, dim3(n), dim3(256), 0, ctx->stream, a);
     const unsigned far_blocks = (unsigned)(((a.key_w + 15) / 16) * ((a.key_h + 15) / 16));
@@ -1061,7 +1016,7 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
     // the one-thread kernel behind the update is 4)
     int gerr = 0;
     unsigned long long gpad = 0;
-    const int wrc = mu_finish(ctx, sc.error_flag, sc.n_updates, sc.h_status, &gerr, &gpad);
+    const int wrc = mu_finish(ctx, sc.error_flag.get(), sc.n_updates.get(), sc.h_status.get(), &gerr, &gpad);
     if (wrc) return wrc;
     if (n_updates_out) *n_updates_out = (long long)((unsigned long long)total - gpad);
     if (gerr == 2) return fail("internal: the device counted more cell updates than the host sized the buffers for", SLAMHIP_ERR_STATE);
@@ -1070,14 +1025,14 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
                   "cells inside the window were updated", SLAMHIP_ERR_STATE);
     return SLAMHIP_OK;
   }
-  if (counting && !sc.srec) SLAMHIP_CHECK(hipMalloc(&sc.srec, sizeof(uint2) * sc.cap_records));
+  if (counting && !sc.srec) SLAMHIP_CHECK(sc.srec.alloc(sc.cap_records));
   if (counting) {
     a.key_x0 = (int)wx0;
     a.key_y0 = (int)wy0;
     a.key_w = (int)(wx1 - wx0 + 1);
-    a.bins = sc.bins;
+    a.bins = sc.bins.get();
     a.n_bins = (unsigned)n_bins;
-    a.near_bits = sc.near_bits;
+    a.near_bits = sc.near_bits.get();
     a.near_r = kNearR;
     a.near_words = near_words;
     a.robot_ix = (int)std::floor(a.px / a.scale) + m.origin_x;
@@ -1091,44 +1046,44 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   // update before cleared the status word
   const bool fused = counting && ctx->low_latency;
   if (!fused) launch_count();
-  if (!fused) hipLaunchKernelGGL((k_mu_emit<unsigned, -1>), dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, sc.order);
-  else if (a.est_kind == 1) hipLaunchKernelGGL((k_mu_emit<unsigned, 1>), dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, sc.order);
-  else hipLaunchKernelGGL((k_mu_emit<unsigned, 0>), dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, sc.order);
+  if (!fused) hipLaunchKernelGGL((k_mu_emit<unsigned, -1>), dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, sc.order.get());
+  else if (a.est_kind == 1) hipLaunchKernelGGL((k_mu_emit<unsigned, 1>), dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, sc.order.get());
+  else hipLaunchKernelGGL((k_mu_emit<unsigned, 0>), dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, sc.order.get());
   if (counting) {
     hipLaunchKernelGGL(k_mu_near_bits, dim3(near_words, kNearSide), dim3(64), 0, ctx->stream, a);
     size_t tb = sc.scan_temp_bytes;
-    SLAMHIP_CHECK(rocprim::exclusive_scan(sc.scan_temp, tb, sc.bins, sc.offs, 0u, (size_t)n_bins + 1, rocprim::plus<unsigned>(),
+    SLAMHIP_CHECK(rocprim::exclusive_scan(sc.scan_temp.get(), tb, sc.bins.get(), sc.offs.get(), 0u, (size_t)n_bins + 1, rocprim::plus<unsigned>(),
                                           ctx->stream));
     const dim3 rgrid((total + 255) / 256);
-    hipLaunchKernelGGL(k_mu_scatter, rgrid, dim3(256), 0, ctx->stream, a, (const unsigned *)sc.keys, (const unsigned *)sc.order,
-                       total, (const unsigned *)sc.offs, sc.srec);
+    hipLaunchKernelGGL(k_mu_scatter, rgrid, dim3(256), 0, ctx->stream, a, (const unsigned *)sc.keys.get(), (const unsigned *)sc.order.get(),
+                       total, (const unsigned *)sc.offs.get(), sc.srec.get());
     if (a.est_kind == 1)
-      hipLaunchKernelGGL(k_mu_rank<1>, rgrid, dim3(256), 0, ctx->stream, a, (const uint2 *)sc.srec,
-                         (const unsigned *)sc.offs, total, sc.keys_sorted, sc.order_sorted, sc.srt_prob, sc.srt_qual);
+      hipLaunchKernelGGL(k_mu_rank<1>, rgrid, dim3(256), 0, ctx->stream, a, (const uint2 *)sc.srec.get(),
+                         (const unsigned *)sc.offs.get(), total, sc.keys_sorted.get(), sc.order_sorted.get(), sc.srt_prob.get(), sc.srt_qual.get());
     else
-      hipLaunchKernelGGL(k_mu_rank<0>, rgrid, dim3(256), 0, ctx->stream, a, (const uint2 *)sc.srec,
-                         (const unsigned *)sc.offs, total, sc.keys_sorted, sc.order_sorted, sc.srt_prob, sc.srt_qual);
+      hipLaunchKernelGGL(k_mu_rank<0>, rgrid, dim3(256), 0, ctx->stream, a, (const uint2 *)sc.srec.get(),
+                         (const unsigned *)sc.offs.get(), total, sc.keys_sorted.get(), sc.order_sorted.get(), sc.srt_prob.get(), sc.srt_qual.get());
   } else {
     size_t tb = sc.temp_bytes;
     // sort only the bits a cell key can occupy; the invalid key (all ones) still sorts last because
     // every valid key is < 2^nbits - 1
     unsigned nbits = 1;
     while (nbits < 32 && ((1ull << nbits) - 1) <= (unsigned long long)m.pitch * m.height) ++nbits;
-    SLAMHIP_CHECK(rocprim::radix_sort_pairs(sc.temp, tb, sc.keys, sc.keys_sorted, sc.order, sc.order_sorted,
+    SLAMHIP_CHECK(rocprim::radix_sort_pairs(sc.temp.get(), tb, sc.keys.get(), sc.keys_sorted.get(), sc.order.get(), sc.order_sorted.get(),
                                             total, 0, nbits, ctx->stream));
     if (a.est_kind == 1)
       hipLaunchKernelGGL((k_mu_gather<unsigned, 1>), dim3((total + 255) / 256), dim3(256), 0, ctx->stream, a,
-                         (const unsigned *)sc.keys_sorted, (const unsigned *)sc.order_sorted, total, sc.srt_prob,
-                         sc.srt_qual);
+                         (const unsigned *)sc.keys_sorted.get(), (const unsigned *)sc.order_sorted.get(), total, sc.srt_prob.get(),
+                         sc.srt_qual.get());
     else
       hipLaunchKernelGGL((k_mu_gather<unsigned, 0>), dim3((total + 255) / 256), dim3(256), 0, ctx->stream, a,
-                         (const unsigned *)sc.keys_sorted, (const unsigned *)sc.order_sorted, total, sc.srt_prob,
-                         sc.srt_qual);
+                         (const unsigned *)sc.keys_sorted.get(), (const unsigned *)sc.order_sorted.get(), total, sc.srt_prob.get(),
+                         sc.srt_qual.get());
   }
-  a.rec_prob = sc.srt_prob;
-  a.rec_qual = sc.srt_qual;
-  a.rec_beam = sc.order_sorted;
-  mu_launch_apply<unsigned>(a, (const unsigned *)sc.keys_sorted, total, ctx->stream);
+  a.rec_prob = sc.srt_prob.get();
+  a.rec_qual = sc.srt_qual.get();
+  a.rec_beam = sc.order_sorted.get();
+  mu_launch_apply<unsigned>(a, (const unsigned *)sc.keys_sorted.get(), total, ctx->stream);
   SLAMHIP_CHECK(hipGetLastError());
   if (prof.on()) {
     const int prc = prof.close();
@@ -1145,7 +1100,7 @@ int slamhip_map_append_scan_q(slamhip_ctx *ctx, int map_id, const slamhip_scan_a
   int err = 0;
   unsigned long long nu = 0;  // padding records
   {
-    const int rc = mu_finish(ctx, sc.error_flag, sc.n_updates, sc.h_status, &err, &nu);
+    const int rc = mu_finish(ctx, sc.error_flag.get(), sc.n_updates.get(), sc.h_status.get(), &err, &nu);
     if (rc) return rc;
   }
   nu = (unsigned long long)total - nu;
@@ -1343,31 +1298,25 @@ int slamhip_map_download_aux(slamhip_ctx *ctx, int map_id, int x0, int y0, int w
 namespace {
 struct MuBatchScratch {
   size_t cap_beams = 0, cap_records = 0, cap_jobs = 0, cap_scan = 0, temp_bytes = 0;
-  unsigned *counts = nullptr, *offsets = nullptr, *order = nullptr, *order_sorted = nullptr;
-  unsigned long long *keys = nullptr, *keys_sorted = nullptr;
-  double *beam_end = nullptr, *scan = nullptr;
-  MuBeam *beam_info = nullptr;
-  double *srt_prob = nullptr;
-  int *occ = nullptr, *error_flag = nullptr;
-  MuJob *d_jobs = nullptr;
-  int *d_bbox = nullptr;
-  unsigned long long *n_updates = nullptr, *d_total = nullptr, *h_status = nullptr;
-  void *temp = nullptr, *scan_temp = nullptr;
+  DeviceBuf<unsigned> counts, offsets, order, order_sorted;
+  DeviceBuf<unsigned long long> keys, keys_sorted;
+  DeviceBuf<double> beam_end, scan;
+  DeviceBuf<MuBeam> beam_info;
+  DeviceBuf<double> srt_prob;
+  DeviceBuf<int> occ, error_flag;
+  DeviceBuf<MuJob> d_jobs;
+  DeviceBuf<int> d_bbox;
+  DeviceBuf<unsigned long long> n_updates, d_total;
+  PinnedBuf<unsigned long long> h_status;
+  DeviceBuf<unsigned char> temp, scan_temp;
   size_t scan_temp_bytes = 0;
   // free-space fast path (mu_batch_fast_tail): the marked cells, per-beam count / place of the records left to sort
-  unsigned *special = nullptr, *slow_cnt = nullptr, *slow_off = nullptr;
+  DeviceBuf<unsigned> special, slow_cnt, slow_off;
   size_t special_words = 0, cap_slow = 0;
 };
 MuBatchScratch &bscratch_of(slamhip_ctx *ctx) {
   if (!ctx->mu_bscratch) ctx->mu_bscratch = new MuBatchScratch;
   return *static_cast<MuBatchScratch *>(ctx->mu_bscratch);
-}
-
-template <typename T>
-hipError_t regrow(T *&p, size_t count) {
-  if (p) hipFree(p);
-  p = nullptr;
-  return hipMalloc(&p, sizeof(T) * count);
 }
 
 // rocprim's onesweep for the batch sort.  4-byte keys: 8 bits per pass, 1024 x 8 items per block, `match`
@@ -1390,19 +1339,19 @@ using BatchSortConfig = typename BatchSortConfigOf<Key>::type;
 // walk, sort, evaluate, apply -- with the key width the batch's (job, window cell) pairs need
 template <typename Key>
 int mu_batch_tail(const MuArgs &a, MuBatchScratch &sc, unsigned total, size_t beams, unsigned end_bit, hipStream_t st) {
-  Key *keys = (Key *)sc.keys, *keys_sorted = (Key *)sc.keys_sorted;
+  Key *keys = (Key *)sc.keys.get(), *keys_sorted = (Key *)sc.keys_sorted.get();
   const dim3 bgrid((unsigned)((beams + 255) / 256)), rgrid((total + 255) / 256);
-  hipLaunchKernelGGL((k_mu_emit<Key, -1>), dim3((unsigned)((beams + 3) / 4)), dim3(256), 0, st, a, sc.order);
+  hipLaunchKernelGGL((k_mu_emit<Key, -1>), dim3((unsigned)((beams + 3) / 4)), dim3(256), 0, st, a, sc.order.get());
   size_t tb = sc.temp_bytes;
-  SLAMHIP_CHECK(rocprim::radix_sort_pairs<BatchSortConfig<Key>>(sc.temp, tb, keys, keys_sorted, sc.order,
-                                                                sc.order_sorted, total, 0,
+  SLAMHIP_CHECK(rocprim::radix_sort_pairs<BatchSortConfig<Key>>(sc.temp.get(), tb, keys, keys_sorted, sc.order.get(),
+                                                                sc.order_sorted.get(), total, 0,
                                                                 std::min(end_bit, (unsigned)(8 * sizeof(Key))), st));
   if (a.est_kind == 1)
     hipLaunchKernelGGL((k_mu_gather<Key, 1>), rgrid, dim3(256), 0, st, a, (const Key *)keys_sorted,
-                       (const unsigned *)sc.order_sorted, total, sc.srt_prob, (double *)nullptr);
+                       (const unsigned *)sc.order_sorted.get(), total, sc.srt_prob.get(), (double *)nullptr);
   else
     hipLaunchKernelGGL((k_mu_gather<Key, 0>), rgrid, dim3(256), 0, st, a, (const Key *)keys_sorted,
-                       (const unsigned *)sc.order_sorted, total, sc.srt_prob, (double *)nullptr);
+                       (const unsigned *)sc.order_sorted.get(), total, sc.srt_prob.get(), (double *)nullptr);
   mu_launch_apply<Key>(a, (const Key *)keys_sorted, total, st);
   return SLAMHIP_OK;
 }
@@ -1411,61 +1360,53 @@ int mu_batch_tail(const MuArgs &a, MuBatchScratch &sc, unsigned total, size_t be
 // updates are applied there), compact what is left, and sort / evaluate / apply only that.  32-bit keys.
 int mu_batch_fast_tail(MuArgs &a, MuBatchScratch &sc, size_t beams, unsigned end_bit, hipStream_t st) {
   const size_t words = (((size_t)1 << (end_bit - 1)) / 32 + 4) & ~(size_t)3;  // one bit per valid key, whole uint4s
-  if (words > sc.special_words) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    SLAMHIP_CHECK(regrow(sc.special, words));
-    sc.special_words = words;
-  }
-  if (sc.cap_beams > sc.cap_slow) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    SLAMHIP_CHECK(regrow(sc.slow_cnt, sc.cap_beams));
-    SLAMHIP_CHECK(regrow(sc.slow_off, sc.cap_beams));
-    sc.cap_slow = sc.cap_beams;
-  }
+  // (exactly `words`, and the batch's own cap_beams -- 4096 doubled)
+  int grc = grow_block(st, sc.special, sc.special_words, words, words);
+  if (!grc) grc = grow_blocks({st}, sc.cap_slow, sc.cap_beams, 4096, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(sc.slow_cnt.alloc(cap));
+    SLAMHIP_CHECK(sc.slow_off.alloc(cap));
+    return SLAMHIP_OK;
+  });
+  if (grc) return grc;
   hipLaunchKernelGGL(k_mu_clear_marks, dim3((unsigned)std::min<size_t>((words / 4 + 255) / 256, 4096)), dim3(256), 0, st,
-                     (uint4 *)sc.special, words / 4);
-  a.special = sc.special;
+                     (uint4 *)sc.special.get(), words / 4);
+  a.special = sc.special.get();
   a.lazy_keys = 1;
-  a.walk_flag = sc.slow_cnt;  // (read by k_mu_classify before it leaves the beam's count of sorted records there)
-  unsigned *keys = (unsigned *)sc.keys, *keys_c = (unsigned *)sc.keys_sorted;
+  a.walk_flag = sc.slow_cnt.get();  // (read by k_mu_classify before it leaves the beam's count of sorted records there)
+  unsigned *keys = (unsigned *)sc.keys.get(), *keys_c = (unsigned *)sc.keys_sorted.get();
   const dim3 wgrid((unsigned)((beams + 3) / 4));  // a wave per beam
   hipLaunchKernelGGL((k_mu_emit<unsigned, -1>), wgrid, dim3(256), 0, st, a, (unsigned *)nullptr);
   const dim3 cgrid((unsigned)((beams + kClassifyBeams - 1) / kClassifyBeams)), cblock(64 * kClassifyBeams);
-  if (a.est_kind == 1) hipLaunchKernelGGL(k_mu_classify<1>, cgrid, cblock, 0, st, a, sc.slow_cnt);
-  else hipLaunchKernelGGL(k_mu_classify<0>, cgrid, cblock, 0, st, a, sc.slow_cnt);
+  if (a.est_kind == 1) hipLaunchKernelGGL(k_mu_classify<1>, cgrid, cblock, 0, st, a, sc.slow_cnt.get());
+  else hipLaunchKernelGGL(k_mu_classify<0>, cgrid, cblock, 0, st, a, sc.slow_cnt.get());
   {
     size_t need = 0;
-    SLAMHIP_CHECK(rocprim::exclusive_scan(nullptr, need, sc.slow_cnt, sc.slow_off, 0u, beams, rocprim::plus<unsigned>(), st));
-    if (need > sc.scan_temp_bytes) {
-      SLAMHIP_CHECK(hipStreamSynchronize(st));
-      if (sc.scan_temp) hipFree(sc.scan_temp);
-      sc.scan_temp = nullptr;
-      SLAMHIP_CHECK(hipMalloc(&sc.scan_temp, need));
-      sc.scan_temp_bytes = need;
-    }
-    SLAMHIP_CHECK(rocprim::exclusive_scan(sc.scan_temp, need, sc.slow_cnt, sc.slow_off, 0u, beams, rocprim::plus<unsigned>(), st));
+    SLAMHIP_CHECK(rocprim::exclusive_scan(nullptr, need, sc.slow_cnt.get(), sc.slow_off.get(), 0u, beams, rocprim::plus<unsigned>(), st));
+    const int trc = grow_block(st, sc.scan_temp, sc.scan_temp_bytes, need, need);  // (exactly what rocprim asks for)
+    if (trc) return trc;
+    SLAMHIP_CHECK(rocprim::exclusive_scan(sc.scan_temp.get(), need, sc.slow_cnt.get(), sc.slow_off.get(), 0u, beams, rocprim::plus<unsigned>(), st));
   }
-  hipLaunchKernelGGL(k_mu_total, dim3(1), dim3(1), 0, st, (const unsigned *)sc.slow_cnt, (const unsigned *)sc.slow_off,
-                     beams, sc.d_total);
+  hipLaunchKernelGGL(k_mu_total, dim3(1), dim3(1), 0, st, (const unsigned *)sc.slow_cnt.get(), (const unsigned *)sc.slow_off.get(),
+                     beams, sc.d_total.get());
   unsigned long long n_slow64 = 0;
-  SLAMHIP_CHECK(hipMemcpyAsync(&n_slow64, sc.d_total, sizeof(n_slow64), hipMemcpyDeviceToHost, st));
-  hipLaunchKernelGGL(k_mu_compact, wgrid, dim3(256), 0, st, a, (const unsigned *)sc.slow_cnt,
-                     (const unsigned *)sc.slow_off, keys_c, sc.order_sorted);
+  SLAMHIP_CHECK(hipMemcpyAsync(&n_slow64, sc.d_total.get(), sizeof(n_slow64), hipMemcpyDeviceToHost, st));
+  hipLaunchKernelGGL(k_mu_compact, wgrid, dim3(256), 0, st, a, (const unsigned *)sc.slow_cnt.get(),
+                     (const unsigned *)sc.slow_off.get(), keys_c, sc.order_sorted.get());
   SLAMHIP_CHECK(hipStreamSynchronize(st));
   const unsigned n_slow = (unsigned)n_slow64;
   if (n_slow == 0) return SLAMHIP_OK;
   // the compacted records go back into the buffers the walk filled (dead by now), sorted
   size_t tb = sc.temp_bytes;
-  SLAMHIP_CHECK(rocprim::radix_sort_pairs<BatchSortConfig<unsigned>>(sc.temp, tb, keys_c, keys, sc.order_sorted, sc.order,
+  SLAMHIP_CHECK(rocprim::radix_sort_pairs<BatchSortConfig<unsigned>>(sc.temp.get(), tb, keys_c, keys, sc.order_sorted.get(), sc.order.get(),
                                                                      n_slow, 0, std::min(end_bit, 32u), st));
-  a.rec_beam = sc.order;
+  a.rec_beam = sc.order.get();
   const dim3 sgrid((n_slow + 255) / 256);
   if (a.est_kind == 1)
     hipLaunchKernelGGL((k_mu_gather<unsigned, 1>), sgrid, dim3(256), 0, st, a, (const unsigned *)keys,
-                       (const unsigned *)sc.order, n_slow, sc.srt_prob, (double *)nullptr);
+                       (const unsigned *)sc.order.get(), n_slow, sc.srt_prob.get(), (double *)nullptr);
   else
     hipLaunchKernelGGL((k_mu_gather<unsigned, 0>), sgrid, dim3(256), 0, st, a, (const unsigned *)keys,
-                       (const unsigned *)sc.order, n_slow, sc.srt_prob, (double *)nullptr);
+                       (const unsigned *)sc.order.get(), n_slow, sc.srt_prob.get(), (double *)nullptr);
   mu_launch_apply<unsigned>(a, (const unsigned *)keys, n_slow, st);
   return SLAMHIP_OK;
 }
@@ -1522,70 +1463,58 @@ int mu_append_batch(slamhip_ctx *ctx, TilePool *tp, const slamhip_scan_adder_cfg
   unsigned total = 0;
 
   const size_t beams = (size_t)n_jobs * n;
-  if ((size_t)n > sc.cap_scan) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    size_t cap = 2048;
-    while (cap < (size_t)n) cap *= 2;
-    SLAMHIP_CHECK(regrow(sc.scan, 3 * cap));
-    SLAMHIP_CHECK(regrow(sc.occ, cap));
-    sc.cap_scan = cap;
-  }
-  if (beams > sc.cap_beams) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    size_t cap = 4096;
-    while (cap < beams) cap *= 2;
-    SLAMHIP_CHECK(regrow(sc.counts, cap));
-    SLAMHIP_CHECK(regrow(sc.offsets, cap + 1));
-    SLAMHIP_CHECK(regrow(sc.beam_end, 4 * cap));  // end point + (1/dx, 1/dy)
-    SLAMHIP_CHECK(regrow(sc.beam_info, cap));
-    sc.cap_beams = cap;
-  }
-  if ((size_t)n_jobs > sc.cap_jobs) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    size_t cap = 64;
-    while (cap < (size_t)n_jobs) cap *= 2;
-    SLAMHIP_CHECK(regrow(sc.d_jobs, cap));
-    SLAMHIP_CHECK(regrow(sc.d_bbox, 4 * cap));
-    sc.cap_jobs = cap;
-  }
-  if (!sc.error_flag) SLAMHIP_CHECK(hipMalloc(&sc.error_flag, sizeof(int)));
-  if (!sc.n_updates) SLAMHIP_CHECK(hipMalloc(&sc.n_updates, sizeof(unsigned long long)));
-  if (!sc.h_status) SLAMHIP_CHECK(hipHostMalloc(&sc.h_status, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-  if (!sc.d_total) SLAMHIP_CHECK(hipMalloc(&sc.d_total, sizeof(unsigned long long)));
-  auto ensure_records = [&](unsigned need_records) -> int {
-    if (need_records <= sc.cap_records) return SLAMHIP_OK;
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    size_t cap = 1 << 18;
-    while (cap < need_records) cap *= 2;
-    SLAMHIP_CHECK(regrow(sc.keys, cap));
-    SLAMHIP_CHECK(regrow(sc.keys_sorted, cap));
-    SLAMHIP_CHECK(regrow(sc.order, cap));
-    SLAMHIP_CHECK(regrow(sc.order_sorted, cap));
-    SLAMHIP_CHECK(regrow(sc.srt_prob, cap));
-    if (sc.temp) hipFree(sc.temp);
-    sc.temp = nullptr;
-    sc.temp_bytes = 0;
-    size_t tb32 = 0;  // the key buffers serve both key widths
-    SLAMHIP_CHECK(rocprim::radix_sort_pairs(nullptr, sc.temp_bytes, sc.keys, sc.keys_sorted, sc.order,
-                                            sc.order_sorted, cap, 0, 64, st));
-    SLAMHIP_CHECK(rocprim::radix_sort_pairs<BatchSortConfig<unsigned>>(
-        nullptr, tb32, (unsigned *)sc.keys, (unsigned *)sc.keys_sorted, sc.order, sc.order_sorted, cap, 0, 32, st));
-    sc.temp_bytes = std::max(sc.temp_bytes, tb32);
-    SLAMHIP_CHECK(hipMalloc(&sc.temp, sc.temp_bytes));
-    sc.cap_records = cap;
+  int grc = grow_blocks({st}, sc.cap_scan, (size_t)n, 2048, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(sc.scan.alloc(3 * cap));
+    SLAMHIP_CHECK(sc.occ.alloc(cap));
     return SLAMHIP_OK;
+  });
+  if (!grc) grc = grow_blocks({st}, sc.cap_beams, beams, 4096, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(sc.counts.alloc(cap));
+    SLAMHIP_CHECK(sc.offsets.alloc(cap + 1));
+    SLAMHIP_CHECK(sc.beam_end.alloc(4 * cap));  // end point + (1/dx, 1/dy)
+    SLAMHIP_CHECK(sc.beam_info.alloc(cap));
+    return SLAMHIP_OK;
+  });
+  if (!grc) grc = grow_blocks({st}, sc.cap_jobs, (size_t)n_jobs, 64, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(sc.d_jobs.alloc(cap));
+    SLAMHIP_CHECK(sc.d_bbox.alloc(4 * cap));
+    return SLAMHIP_OK;
+  });
+  if (grc) return grc;
+  if (!sc.error_flag) SLAMHIP_CHECK(sc.error_flag.alloc(1));
+  if (!sc.n_updates) SLAMHIP_CHECK(sc.n_updates.alloc(1));
+  if (!sc.h_status) SLAMHIP_CHECK(sc.h_status.alloc(2));
+  if (!sc.d_total) SLAMHIP_CHECK(sc.d_total.alloc(1));
+  auto ensure_records = [&](unsigned need_records) -> int {
+    return grow_blocks({st}, sc.cap_records, (size_t)need_records, (size_t)1 << 18, [&](size_t cap) -> int {
+      SLAMHIP_CHECK(sc.keys.alloc(cap));
+      SLAMHIP_CHECK(sc.keys_sorted.alloc(cap));
+      SLAMHIP_CHECK(sc.order.alloc(cap));
+      SLAMHIP_CHECK(sc.order_sorted.alloc(cap));
+      SLAMHIP_CHECK(sc.srt_prob.alloc(cap));
+      sc.temp_bytes = 0;
+      size_t tb32 = 0;  // the key buffers serve both key widths
+      SLAMHIP_CHECK(rocprim::radix_sort_pairs(nullptr, sc.temp_bytes, sc.keys.get(), sc.keys_sorted.get(), sc.order.get(),
+                                              sc.order_sorted.get(), cap, 0, 64, st));
+      SLAMHIP_CHECK(rocprim::radix_sort_pairs<BatchSortConfig<unsigned>>(
+          nullptr, tb32, (unsigned *)sc.keys.get(), (unsigned *)sc.keys_sorted.get(), sc.order.get(), sc.order_sorted.get(), cap,
+          0, 32, st));
+      sc.temp_bytes = std::max(sc.temp_bytes, tb32);
+      SLAMHIP_CHECK(sc.temp.alloc(sc.temp_bytes));
+      return SLAMHIP_OK;
+    });
   };
   const size_t cs = sc.cap_scan;
-  SLAMHIP_CHECK(hipMemcpyAsync(sc.scan, range, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  SLAMHIP_CHECK(hipMemcpyAsync(sc.scan + cs, cos_a, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  SLAMHIP_CHECK(hipMemcpyAsync(sc.scan + 2 * cs, sin_a, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  if (is_occ) SLAMHIP_CHECK(hipMemcpyAsync(sc.occ, is_occ, sizeof(int) * n, hipMemcpyHostToDevice, st));
-  SLAMHIP_CHECK(hipMemcpyAsync(sc.d_jobs, jobs.data(), sizeof(MuJob) * n_jobs, hipMemcpyHostToDevice, st));
-  SLAMHIP_CHECK(hipMemcpyAsync(sc.d_bbox, bbox.data(), sizeof(int) * 4 * n_jobs, hipMemcpyHostToDevice, st));
+  SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get(), range, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get() + cs, cos_a, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  SLAMHIP_CHECK(hipMemcpyAsync(sc.scan.get() + 2 * cs, sin_a, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  if (is_occ) SLAMHIP_CHECK(hipMemcpyAsync(sc.occ.get(), is_occ, sizeof(int) * n, hipMemcpyHostToDevice, st));
+  SLAMHIP_CHECK(hipMemcpyAsync(sc.d_jobs.get(), jobs.data(), sizeof(MuJob) * n_jobs, hipMemcpyHostToDevice, st));
+  SLAMHIP_CHECK(hipMemcpyAsync(sc.d_bbox.get(), bbox.data(), sizeof(int) * 4 * n_jobs, hipMemcpyHostToDevice, st));
 
   MuArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.jobs = sc.d_jobs;
+  a.jobs = sc.d_jobs.get();
   a.n_jobs = n_jobs;
   auto bind_extent = [&]() {  // (again after the extent grew)
     a.tables = tp->d_table();
@@ -1609,10 +1538,10 @@ int mu_append_batch(slamhip_ctx *ctx, TilePool *tp, const slamhip_scan_adder_cfg
   a.cell_dbl = 4;
   a.aux_stride = 2;
   a.scale = scale;
-  a.range = sc.scan;
-  a.cos_a = sc.scan + cs;
-  a.sin_a = sc.scan + 2 * cs;
-  a.is_occ = is_occ ? sc.occ : nullptr;
+  a.range = sc.scan.get();
+  a.cos_a = sc.scan.get() + cs;
+  a.sin_a = sc.scan.get() + 2 * cs;
+  a.is_occ = is_occ ? sc.occ.get() : nullptr;
   a.n = n;
   a.rule = SLAMHIP_RULE_GMAPPING;
   a.est_kind = cfg->occupancy_estimator;
@@ -1624,16 +1553,16 @@ int mu_append_batch(slamhip_ctx *ctx, TilePool *tp, const slamhip_scan_adder_cfg
   a.base_empty_qual = cfg->base_empty_qual;
   a.blur = cfg->blur;
   a.max_range_sq = max_range_sq;
-  a.counts = sc.counts;
-  a.offsets = sc.offsets;
-  a.beam_end = sc.beam_end;
-  a.beam_inv = sc.beam_end + 2 * sc.cap_beams;
-  a.beam_info = sc.beam_info;
-  a.error_flag = sc.error_flag;
-  a.n_padding = sc.n_updates;
+  a.counts = sc.counts.get();
+  a.offsets = sc.offsets.get();
+  a.beam_end = sc.beam_end.get();
+  a.beam_inv = sc.beam_end.get() + 2 * sc.cap_beams;
+  a.beam_info = sc.beam_info.get();
+  a.error_flag = sc.error_flag.get();
+  a.n_padding = sc.n_updates.get();
 
   const dim3 bgrid((unsigned)((beams + 255) / 256));
-  a.job_bbox = sc.d_bbox;
+  a.job_bbox = sc.d_bbox.get();
   ProfilePairGuard prof;  // slamhip_profile_read_map_update: the whole pipeline (closed on every exit)
   {
     const int prc = prof.open(ctx, st, 1);
@@ -1644,20 +1573,15 @@ int mu_append_batch(slamhip_ctx *ctx, TilePool *tp, const slamhip_scan_adder_cfg
   {  // offsets: device-wide exclusive scan (the one-workgroup scan of the single-scan path takes 160 us
      // for 100 x 1080 beams)
     size_t need = 0;
-    SLAMHIP_CHECK(rocprim::exclusive_scan(nullptr, need, sc.counts, sc.offsets, 0u, beams, rocprim::plus<unsigned>(), st));
-    if (need > sc.scan_temp_bytes) {
-      SLAMHIP_CHECK(hipStreamSynchronize(st));
-      if (sc.scan_temp) hipFree(sc.scan_temp);
-      sc.scan_temp = nullptr;
-      SLAMHIP_CHECK(hipMalloc(&sc.scan_temp, need));
-      sc.scan_temp_bytes = need;
-    }
-    SLAMHIP_CHECK(rocprim::exclusive_scan(sc.scan_temp, need, sc.counts, sc.offsets, 0u, beams, rocprim::plus<unsigned>(), st));
+    SLAMHIP_CHECK(rocprim::exclusive_scan(nullptr, need, sc.counts.get(), sc.offsets.get(), 0u, beams, rocprim::plus<unsigned>(), st));
+    const int trc = grow_block(st, sc.scan_temp, sc.scan_temp_bytes, need, need);  // (exactly what rocprim asks for)
+    if (trc) return trc;
+    SLAMHIP_CHECK(rocprim::exclusive_scan(sc.scan_temp.get(), need, sc.counts.get(), sc.offsets.get(), 0u, beams, rocprim::plus<unsigned>(), st));
   }
-  hipLaunchKernelGGL(k_mu_total, dim3(1), dim3(1), 0, st, sc.counts, sc.offsets, beams, sc.d_total);
+  hipLaunchKernelGGL(k_mu_total, dim3(1), dim3(1), 0, st, sc.counts.get(), sc.offsets.get(), beams, sc.d_total.get());
   unsigned long long total64 = 0;
-  SLAMHIP_CHECK(hipMemcpyAsync(&total64, sc.d_total, sizeof(total64), hipMemcpyDeviceToHost, st));
-  SLAMHIP_CHECK(hipMemcpyAsync(bbox.data(), sc.d_bbox, sizeof(int) * 4 * n_jobs, hipMemcpyDeviceToHost, st));
+  SLAMHIP_CHECK(hipMemcpyAsync(&total64, sc.d_total.get(), sizeof(total64), hipMemcpyDeviceToHost, st));
+  SLAMHIP_CHECK(hipMemcpyAsync(bbox.data(), sc.d_bbox.get(), sizeof(int) * 4 * n_jobs, hipMemcpyDeviceToHost, st));
   SLAMHIP_CHECK(hipStreamSynchronize(st));
   if (total64 == 0) return SLAMHIP_OK;
   if (total64 >= 0xfffffff0ull) return fail("more than 2^32 cell updates in one batch: split the batch");
@@ -1700,10 +1624,10 @@ int mu_append_batch(slamhip_ctx *ctx, TilePool *tp, const slamhip_scan_adder_cfg
   while ((1u << job_bits) < (unsigned)n_jobs) ++job_bits;
   if (cell_bits + job_bits > 62) return fail("batch too large");
   a.cell_bits = (int)cell_bits;
-  a.keys = sc.keys;
+  a.keys = sc.keys.get();
   a.keys_cap = (unsigned long long)sc.cap_records;
-  a.rec_prob = sc.srt_prob;
-  a.rec_beam = sc.order_sorted;
+  a.rec_prob = sc.srt_prob.get();
+  a.rec_beam = sc.order_sorted.get();
   // the invalid key (all ones) must still sort last: include one more bit than the valid keys use
   const unsigned end_bit = cell_bits + job_bits + 1;
   // (sorting by the cell bits alone -- one pass less, chains then ordered (cell, job) -- was measured: the
@@ -1730,7 +1654,7 @@ int mu_append_batch(slamhip_ctx *ctx, TilePool *tp, const slamhip_scan_adder_cfg
   }
   int err = 0;
   unsigned long long nu = 0;  // padding records
-  rc = mu_finish(ctx, sc.error_flag, sc.n_updates, sc.h_status, &err, &nu);
+  rc = mu_finish(ctx, sc.error_flag.get(), sc.n_updates.get(), sc.h_status.get(), &err, &nu);
   if (rc) return rc;
   nu = (unsigned long long)total - nu;
   if (n_updates_out) *n_updates_out = (long long)nu;
@@ -1743,46 +1667,11 @@ int mu_append_batch(slamhip_ctx *ctx, TilePool *tp, const slamhip_scan_adder_cfg
 
 // called by slamhip_ctx_destroy: the K6 scratch buffers of a context live as long as it does
 void mu_release(slamhip_ctx *ctx) {
-  if (ctx->mu_scratch) {
-    MuScratch &s = *static_cast<MuScratch *>(ctx->mu_scratch);
-    for (void *p : {(void *)s.counts, (void *)s.offsets, (void *)s.keys, (void *)s.keys_sorted, (void *)s.order,
-                    (void *)s.order_sorted, (void *)s.beam_info, (void *)s.beam_end, (void *)s.scan,
-                    (void *)s.srt_prob, (void *)s.srt_qual, (void *)s.occ, (void *)s.error_flag,
-                    (void *)s.n_updates, s.temp, (void *)s.bins, (void *)s.offs, (void *)s.srec, s.scan_temp, (void *)s.near_bits})
-      if (p) hipFree(p);
-    if (s.h_status) hipHostFree(s.h_status);
-    if (s.h_ring) hipHostFree(s.h_ring);
-    if (s.d_ring_err) hipFree(s.d_ring_err);
-    if (s.d_ring_pad) hipFree(s.d_ring_pad);
-    if (s.h_offsets) hipHostFree(s.h_offsets);
-    if (s.h_scan_stage) hipHostFree(s.h_scan_stage);
-    if (s.h_occ_stage) hipHostFree(s.h_occ_stage);
-    delete &s;
-    ctx->mu_scratch = nullptr;
-  }
-  if (ctx->mu_kscratch) {
-    MuFleetScratch &s = *static_cast<MuFleetScratch *>(ctx->mu_kscratch);
-    for (void *p : {(void *)s.arena, (void *)s.d_table, (void *)s.irr, (void *)s.d_status})
-      if (p) hipFree(p);
-    for (void *p : {(void *)s.h_stage, (void *)s.h_table, (void *)s.h_status})
-      if (p) hipHostFree(p);
-    for (MuScannerTable &t : s.scanners)
-      if (t.d_lut) hipFree(t.d_lut);
-    delete &s;
-    ctx->mu_kscratch = nullptr;
-  }
-  if (ctx->mu_bscratch) {
-    MuBatchScratch &s = *static_cast<MuBatchScratch *>(ctx->mu_bscratch);
-    for (void *p : {(void *)s.counts, (void *)s.offsets, (void *)s.order, (void *)s.order_sorted, (void *)s.keys,
-                    (void *)s.keys_sorted, (void *)s.beam_info, (void *)s.beam_end, (void *)s.scan,
-                    (void *)s.srt_prob, (void *)s.occ, (void *)s.error_flag,
-                    (void *)s.d_jobs, (void *)s.d_bbox, (void *)s.n_updates, (void *)s.d_total, s.temp, s.scan_temp,
-                    (void *)s.special, (void *)s.slow_cnt, (void *)s.slow_off})
-      if (p) hipFree(p);
-    if (s.h_status) hipHostFree(s.h_status);
-    delete &s;
-    ctx->mu_bscratch = nullptr;
-  }
+  hipSetDevice(ctx->device);
+  delete static_cast<MuScratch *>(ctx->mu_scratch);
+  delete static_cast<MuFleetScratch *>(ctx->mu_kscratch);
+  delete static_cast<MuBatchScratch *>(ctx->mu_bscratch);
+  ctx->mu_scratch = ctx->mu_kscratch = ctx->mu_bscratch = nullptr;
 }
 
 }  // namespace slamhip

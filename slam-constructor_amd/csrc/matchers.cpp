@@ -838,22 +838,15 @@ int many_chains_prepare(slamhip_ctx *ctx, Set &s, int n, int want, double reach,
   }
   const int total = n * (6 * s.shapes.max_inst + 1);
   s.nt = total <= 256 ? 1024 : (total <= 512 ? 512 : 256);
-  if (n > s.cap) {  // (three blocks and what clears them: not grow_block's one)
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return grow_blocks({ctx->stream}, s.cap, (size_t)n, (size_t)cap0, [&](size_t cap) -> int {
     s.d_rctl.reset();
     s.rctl_grid = s.rctl_chains = 0;
-    int cap = cap0;
-    while (cap < n) cap *= 2;
-    s.cap = 0;
     SLAMHIP_CHECK(s.d_ctl.alloc(cap));
     SLAMHIP_CHECK(hipMemsetAsync(s.d_ctl.get(), 0, sizeof(HcChainCtl) * cap, ctx->stream));
     SLAMHIP_CHECK(s.h_out.alloc(cap, kPinnedCoherent));
     std::memset(s.h_out.get(), 0, sizeof(HcHostOut) * cap);
-    const int rc = s.stage.alloc(cap, ctx->stream);
-    if (rc) return rc;
-    s.cap = cap;
-  }
-  return SLAMHIP_OK;
+    return s.stage.alloc((int)cap, ctx->stream);
+  });
 }
 
 // what every many-chains call puts into its arguments: blocks, shapes, a new epoch; the chains' result blocks re-armed
@@ -966,7 +959,7 @@ int run_many_chains(slamhip_ctx *ctx, ResidentPolicy &policy, Set &s, HcChainArg
       ++launched;
     }
     const unsigned seq = next_epoch(ctx->seq);
-    SLAMHIP_CHECK(launch_chain_marker(s.stage.d_n_done(), s.h_done_count.get(), ctx->h_done_flag, seq, st));
+    SLAMHIP_CHECK(launch_chain_marker(s.stage.d_n_done(), s.h_done_count.get(), ctx->h_done_flag.get(), seq, st));
     *seq_out = seq;
     return SLAMHIP_OK;
   };
@@ -1082,7 +1075,7 @@ int hc_batch_stage_scans(slamhip_matcher *m, int n, const slamhip_match_job *job
     BatchScanBlock &k = blocks[c];
     if (j.scan_slot >= 0) {
       const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[j.scan_slot];
-      k.d = sl.d;
+      k.d = sl.d.get();
       k.stride = (size_t)sl.cap;
       k.n = sl.n;
       k.tot_w = sl.tot_w;
@@ -1619,13 +1612,14 @@ int mc_chain_process_scan(slamhip_matcher *m, int map_id, const double init_pose
     mc.tape_owner = pe;
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
     SLAMHIP_CHECK(hipStreamSynchronize(mc.tape_stream));
-    const size_t cap = std::max<size_t>(64 * need, 1 << 16);
-    if (cap > mc.tape_cap) {
-      static_assert(sizeof(McPair) == 2 * sizeof(double), "the pinned staging holds pairs as two doubles");
+    static_assert(sizeof(McPair) == 2 * sizeof(double), "the pinned staging holds pairs as two doubles");
+    const size_t want = std::max<size_t>(64 * need, 1 << 16);  // (exactly: the floor is the size itself)
+    const int grc = grow_blocks({ctx->stream, mc.tape_stream}, mc.tape_cap, want, want, [&](size_t cap) -> int {
       SLAMHIP_CHECK(mc.d_tape.alloc(cap));
       SLAMHIP_CHECK(mc.h_tape.alloc(2 * cap, hipHostMallocDefault));
-      mc.tape_cap = cap;
-    }
+      return SLAMHIP_OK;
+    });
+    if (grc) return grc;
     mc.tape_base = pos;
     mc.tape_filled = 0;
   }
@@ -1794,21 +1788,15 @@ int mc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
   const unsigned max_failed = pe0->max_failed(), max_poses = pe0->max_poses();
   const size_t need = mc_tape_need(pe0);
   if (!s->h_done_count) SLAMHIP_CHECK(s->h_done_count.alloc(1, kPinnedCoherent));
-  if (n > s->cap) {  // (three blocks and what clears them: not grow_block's one)
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    int cap = 8;
-    while (cap < n) cap *= 2;
-    s->cap = 0;
+  int grc = grow_blocks({st}, s->cap, (size_t)n, 8, [&](size_t cap) -> int {
     SLAMHIP_CHECK(s->d_ctl.alloc(cap));
     SLAMHIP_CHECK(hipMemsetAsync(s->d_ctl.get(), 0, sizeof(McChainCtl) * cap, st));
     SLAMHIP_CHECK(s->h_out.alloc(cap, kPinnedCoherent));
     std::memset(s->h_out.get(), 0, sizeof(McHostOut) * cap);
-    const int rc = s->stage.alloc(cap, st);
-    if (rc) return rc;
-    s->cap = cap;
-  }
+    return s->stage.alloc((int)cap, st);
+  });
   static_assert(sizeof(McPair) == 2 * sizeof(double), "the pinned staging holds pairs as two doubles");
-  int grc = grow_block(st, s->d_tape, s->tape_cap, (size_t)n * need, 1 << 14);
+  if (!grc) grc = grow_block(st, s->d_tape, s->tape_cap, (size_t)n * need, 1 << 14);
   if (!grc) grc = grow_block(st, s->h_tape, s->h_tape_cap, (size_t)n * need, 1 << 14, 2, hipHostMallocDefault);
   if (grc) return grc;
   const size_t trace_need = (size_t)max_poses + 2;
@@ -1872,7 +1860,7 @@ int mc_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
       ++launched;
     }
     const unsigned seq = next_epoch(ctx->seq);
-    SLAMHIP_CHECK(launch_chain_marker(s->stage.d_n_done(), s->h_done_count.get(), ctx->h_done_flag, seq, st));
+    SLAMHIP_CHECK(launch_chain_marker(s->stage.d_n_done(), s->h_done_count.get(), ctx->h_done_flag.get(), seq, st));
     *seq_out = seq;
     return SLAMHIP_OK;
   };
@@ -1989,11 +1977,7 @@ int bf_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
   BfBatch *s = m->bf_batch.get();
   const long long np = 1 + (long long)bf.nx * bf.ny * bf.nt;
   const long long per_blk = (np - 1 + 1023) / 1024;
-  if (n > s->job_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    int cap = 8;
-    while (cap < n) cap *= 2;
-    s->job_cap = 0;
+  int grc = grow_blocks({st}, s->job_cap, (size_t)n, 8, [&](size_t cap) -> int {
     SLAMHIP_CHECK(s->h_jobs.alloc(cap, hipHostMallocDefault));
     SLAMHIP_CHECK(s->d_jobs.alloc(cap));
     SLAMHIP_CHECK(s->d_counters.alloc(3 * (size_t)cap + 1));
@@ -2004,28 +1988,21 @@ int bf_batch_run(slamhip_matcher *m, int n, const Job *jobs, const BatchScanBloc
       SLAMHIP_CHECK(s->h_done.alloc(1, kPinnedCoherent));
       *s->h_done.get() = 0;
     }
-    s->job_cap = cap;
-  }
+    return SLAMHIP_OK;
+  });
   // (the jobs-done word lies behind the LAST job's counters of the call: zero, as every word of the block between calls)
-  if ((long long)n * np > s->pose_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    s->pose_cap = 0;
-    long long cap = 1 << 14;
-    while (cap < (long long)n * np) cap *= 2;
+  if (!grc) grc = grow_blocks({st}, s->pose_cap, (size_t)(n * np), 1 << 14, [&](size_t cap) -> int {
     SLAMHIP_CHECK(s->d_scores.alloc(cap));
     SLAMHIP_CHECK(s->d_fp.alloc(cap));
     SLAMHIP_CHECK(s->d_pidx.alloc(cap));
-    s->pose_cap = cap;
-  }
-  if ((long long)n * per_blk > s->blk_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    s->blk_cap = 0;
-    long long cap = 64;
-    while (cap < (long long)n * per_blk) cap *= 2;
+    return SLAMHIP_OK;
+  });
+  if (!grc) grc = grow_blocks({st}, s->blk_cap, (size_t)(n * per_blk), 64, [&](size_t cap) -> int {
     SLAMHIP_CHECK(s->d_agg_s.alloc(cap));
     SLAMHIP_CHECK(s->d_agg_i.alloc(cap));
-    s->blk_cap = cap;
-  }
+    return SLAMHIP_OK;
+  });
+  if (grc) return grc;
   // the views a lone sweep of each job would score through; one effective cell model and OIE for the launch
   int cell_model = -1, oie_eff = m->cfg.oie, max_n = 0;
   std::vector<double> inits(3 * (size_t)n);
@@ -2211,7 +2188,7 @@ struct ScanKeeper {
     saved_n = ctx->scan_n;
     saved_tot_w = ctx->scan_tot_w;
     // (asked now: a lone call may replace the upload buffer by a larger one)
-    saved_is_upload = !saved_ptr || saved_ptr == ctx->d_scan;
+    saved_is_upload = !saved_ptr || saved_ptr == ctx->d_scan.get();
     saved_w = ctx->h_weight;
     saved_f = ctx->h_factor;
   }
@@ -2228,7 +2205,7 @@ struct ScanKeeper {
       ctx->h_factor.swap(saved_f);
       ctx->h_scan_angle.clear();  // (a stored scan has its slot's, if any, as slamhip_scan_select leaves it)
       for (const slamhip_ctx::ScanSlot &sl : ctx->scan_slots)
-        if (sl.d == saved_ptr) ctx->h_scan_angle = sl.angle;
+        if (sl.d.get() == saved_ptr) ctx->h_scan_angle = sl.angle;
       ctx->scan_angle_on_device = false;
     }
     ctx->scan_angle_lazy = false;
@@ -3631,7 +3608,7 @@ static int process_scan_body(slamhip_matcher *m, int map_id, const double init_p
               carry, m->p_accept0);
     bool redo = false;
     while (!job.done) {
-      const int n = job.plan(budget, ctx->h_poses);
+      const int n = job.plan(budget, ctx->h_poses.get());
       if (n == 0) break;
       const double t0 = MatchJob::now_us();
       unsigned seq = 0;
@@ -3643,18 +3620,18 @@ static int process_scan_body(slamhip_matcher *m, int map_id, const double init_p
       rc = score_wait(ctx, seq);
       if (rc) return rc;
       m->t_score_us += MatchJob::now_us() - t0;
-      if (gm && gm_checked && pe_at_start && job.gm_unsettled(ctx->h_scores, ctx->h_gm_info, ctx)) {
+      if (gm && gm_checked && pe_at_start && job.gm_unsettled(ctx->h_scores.get(), ctx->h_gm_info.get(), ctx)) {
         redo = true;
         break;
       }
-      if (checked && job.ambiguous(ctx->h_scores, ctx->h_fprints)) {
+      if (checked && job.ambiguous(ctx->h_scores.get(), ctx->h_fprints.get())) {
         // a comparison the tree sums cannot settle: the same batch (and the pose that is the best so far) once more,
         // summed in the reference's beam order; those sums decide, the canonical sums stay what is reported
-        m->keep_scores.assign(ctx->h_scores, ctx->h_scores + n);
-        m->keep_fprints.assign(ctx->h_fprints, ctx->h_fprints + n);
-        ctx->h_poses[3 * n] = job.best.x;
-        ctx->h_poses[3 * n + 1] = job.best.y;
-        ctx->h_poses[3 * n + 2] = job.best.theta;
+        m->keep_scores.assign(ctx->h_scores.get(), ctx->h_scores.get() + n);
+        m->keep_fprints.assign(ctx->h_fprints.get(), ctx->h_fprints.get() + n);
+        ctx->h_poses.get()[3 * n] = job.best.x;
+        ctx->h_poses.get()[3 * n + 1] = job.best.y;
+        ctx->h_poses.get()[3 * n + 2] = job.best.theta;
         slamhip_spe_cfg seq_cfg = m->cfg;
         seq_cfg.sum_order = SLAMHIP_SUM_SEQUENTIAL;
         rc = score_staged(ctx, map_id, &seq_cfg, n + 1, nullptr, 0, &seq);
@@ -3663,9 +3640,9 @@ static int process_scan_body(slamhip_matcher *m, int map_id, const double init_p
         if (rc) return rc;
         ++m->chain_rescored;
         m->rescored_poses += n + 1;
-        rc = job.consume(m->keep_scores.data(), ctx->h_gm_info, ctx, m->keep_fprints.data(), ctx->h_scores, ctx->h_scores[n]);
+        rc = job.consume(m->keep_scores.data(), ctx->h_gm_info.get(), ctx, m->keep_fprints.data(), ctx->h_scores.get(), ctx->h_scores.get()[n]);
       } else {
-        rc = job.consume(ctx->h_scores, ctx->h_gm_info, ctx, checked ? ctx->h_fprints : nullptr);
+        rc = job.consume(ctx->h_scores.get(), ctx->h_gm_info.get(), ctx, checked ? ctx->h_fprints.get() : nullptr);
       }
       if (rc) return rc;
     }

@@ -114,7 +114,7 @@ struct ScanAssembleEachArgs {
   ScanAssembleArgs a;
   const double *tab_angle;
 };
-// the planes of a scanner's tables in HBM (ScanTablesDevice, hip_block.h); angle null where nobody keeps that plane
+// the planes of a scanner's tables in HBM (ScanTablesDevice, scan_tables_device.h); angle null where nobody keeps that plane
 struct ScanTablePlanes {
   const double *cos_a, *sin_a, *viny_f, *angle;
 };

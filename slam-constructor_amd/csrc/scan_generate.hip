@@ -202,26 +202,13 @@ const char *sg_check_call(int model, int occ_kind, int variant, int n_poses, con
 
 // room for `bytes` in the context's scan-generation buffer (kept between calls; a larger request replaces it)
 int sg_reserve(slamhip_ctx *ctx, size_t bytes) {
-  if (bytes <= ctx->scan_gen_cap) return SLAMHIP_OK;
-  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_scan_gen) hipFree(ctx->d_scan_gen);
-  ctx->d_scan_gen = nullptr;
-  ctx->scan_gen_cap = 0;
-  const size_t cap = (bytes + 65535) & ~(size_t)65535;
-  SLAMHIP_CHECK(hipMalloc(&ctx->d_scan_gen, cap));
-  ctx->scan_gen_cap = cap;
-  return SLAMHIP_OK;
+  // (whole 64 KiB: the floor is the rounded size itself)
+  return grow_block(ctx->stream, ctx->d_scan_gen, ctx->scan_gen_cap, bytes, (bytes + 65535) & ~(size_t)65535);
 }
 
 size_t round8(size_t v) { return (v + 7) & ~(size_t)7; }
 
 }  // namespace
-
-void scan_gen_release(slamhip_ctx *ctx) {
-  if (ctx->d_scan_gen) hipFree(ctx->d_scan_gen);
-  ctx->d_scan_gen = nullptr;
-  ctx->scan_gen_cap = 0;
-}
 
 // n_jobs x n_angles beams, job k over slot slots[k] from pose k: slamhip_gmapping_particle_generate_scans behind its
 // particle checks.  Nothing is queued before every argument has passed.
@@ -254,7 +241,7 @@ int tile_pool_generate_scans(TilePool *tp, int variant, int flags, int n_jobs, c
   std::memcpy(stage.data() + 3 * (size_t)n_jobs, angles, sizeof(double) * (size_t)n_angles);
   stage[in_doubles - 1] = 0.0;  // (the pad behind an odd number of slots)
   std::memcpy(stage.data() + 3 * (size_t)n_jobs + (size_t)n_angles, slots, sizeof(int) * (size_t)n_jobs);
-  double *d_in = static_cast<double *>(ctx->d_scan_gen);
+  double *d_in = reinterpret_cast<double *>(ctx->d_scan_gen.get());
   double *d_range = d_in + in_doubles;
   unsigned char *d_status = reinterpret_cast<unsigned char *>(d_range + n_beams);
   SLAMHIP_CHECK(hipMemcpyAsync(d_in, stage.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -368,7 +355,7 @@ int slamhip_map_generate_scans(slamhip_ctx *ctx, int map_id, int occ_kind, int v
   stage.resize(std::max(in_doubles, out_bytes / sizeof(double)));
   std::memcpy(stage.data(), poses_xyt, sizeof(double) * 3 * (size_t)n_poses);
   std::memcpy(stage.data() + 3 * (size_t)n_poses, angles, sizeof(double) * (size_t)n_angles);
-  double *d_in = static_cast<double *>(ctx->d_scan_gen);
+  double *d_in = reinterpret_cast<double *>(ctx->d_scan_gen.get());
   double *d_range = d_in + in_doubles;
   unsigned char *d_status = reinterpret_cast<unsigned char *>(d_range + n_beams);
   SLAMHIP_CHECK(hipMemcpyAsync(d_in, stage.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));

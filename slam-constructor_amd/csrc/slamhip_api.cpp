@@ -57,45 +57,34 @@ static DeviceMap *get_map(slamhip_ctx *ctx, int map_id) {
   return &ctx->maps[map_id];
 }
 
+// the stream of the second launch lane (the first's, where no second lane has been forked): a block that kernels of both
+// lanes read or write grows behind {ctx->stream, second_lane(ctx)}
+static hipStream_t second_lane(const slamhip_ctx *ctx) { return ctx->stream_b ? ctx->stream_b : ctx->stream; }
+
 int ensure_pose_capacity(slamhip_ctx *ctx, int n) {
-  if (n <= ctx->pose_cap) return SLAMHIP_OK;
-  int cap = 256;
-  while (cap < n) cap *= 2;
   // kernels of BOTH launch lanes read and write the staging buffers
-  SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (ctx->stream_b) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream_b));
-  if (ctx->d_poses) {
-    hipFree(ctx->d_poses);
-    hipFree(ctx->d_scores);
-    hipFree(ctx->d_pose_sc);
-    hipFree(ctx->d_gm_info);
-    hipHostFree(ctx->h_poses);
-    hipHostFree(ctx->h_scores);
-    hipHostFree(ctx->h_pose_sc);
-    hipHostFree(ctx->h_gm_info);
-    hipHostFree(ctx->h_pose_slot);
-    hipHostFree(ctx->h_fprints);
-    ctx->h_fprints = nullptr;
-    // a failed allocation below must not leave pointers that ctx_destroy (or the next call) frees again
-    ctx->d_poses = ctx->d_scores = ctx->d_pose_sc = nullptr;
-    ctx->d_gm_info = nullptr;
-    ctx->h_poses = ctx->h_scores = ctx->h_pose_sc = nullptr;
-    ctx->h_gm_info = nullptr;
-    ctx->h_pose_slot = nullptr;
-    ctx->pose_cap = 0;
-  }
-  SLAMHIP_CHECK(hipHostMalloc(&ctx->h_pose_slot, sizeof(int) * cap, kPinned));
-  SLAMHIP_CHECK(hipHostMalloc(&ctx->h_fprints, sizeof(unsigned long long) * cap, kPinned));
-  SLAMHIP_CHECK(hipMalloc(&ctx->d_poses, sizeof(double) * 3 * cap));
-  SLAMHIP_CHECK(hipMalloc(&ctx->d_scores, sizeof(double) * cap));
-  SLAMHIP_CHECK(hipMalloc(&ctx->d_pose_sc, sizeof(double) * 2 * cap));
-  SLAMHIP_CHECK(hipMalloc(&ctx->d_gm_info, sizeof(GmPoseInfo) * cap));
-  SLAMHIP_CHECK(hipHostMalloc(&ctx->h_poses, sizeof(double) * 3 * cap, kPinned));
-  SLAMHIP_CHECK(hipHostMalloc(&ctx->h_scores, sizeof(double) * cap, kPinned));
-  SLAMHIP_CHECK(hipHostMalloc(&ctx->h_pose_sc, sizeof(double) * 2 * cap, kPinned));
-  SLAMHIP_CHECK(hipHostMalloc(&ctx->h_gm_info, sizeof(GmPoseInfo) * cap, kPinned));
-  ctx->pose_cap = cap;
-  return SLAMHIP_OK;
+  return grow_blocks({ctx->stream, second_lane(ctx)}, ctx->pose_cap, (size_t)(n > 0 ? n : 0), 256,
+                     [&](size_t cap) -> int {
+    SLAMHIP_CHECK(ctx->h_pose_slot.alloc(cap, kPinned));
+    SLAMHIP_CHECK(ctx->h_fprints.alloc(cap, kPinned));
+    SLAMHIP_CHECK(ctx->d_poses.alloc(3 * cap));
+    SLAMHIP_CHECK(ctx->d_scores.alloc(cap));
+    SLAMHIP_CHECK(ctx->d_pose_sc.alloc(2 * cap));
+    SLAMHIP_CHECK(ctx->d_gm_info.alloc(cap));
+    SLAMHIP_CHECK(ctx->h_poses.alloc(3 * cap, kPinned));
+    SLAMHIP_CHECK(ctx->h_scores.alloc(cap, kPinned));
+    SLAMHIP_CHECK(ctx->h_pose_sc.alloc(2 * cap, kPinned));
+    SLAMHIP_CHECK(ctx->h_gm_info.alloc(cap, kPinned));
+    return SLAMHIP_OK;
+  });
+}
+
+// room for `need` per-beam terms of the beam-order sum (exactly: no doubling), which kernels of both lanes write
+static int terms_room(slamhip_ctx *ctx, size_t need) {
+  return grow_blocks({ctx->stream, second_lane(ctx)}, ctx->terms_cap, need, need, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(ctx->d_terms.alloc(cap));
+    return SLAMHIP_OK;
+  });
 }
 
 static int check_cfg(const DeviceMap &m, const slamhip_spe_cfg *cfg) {
@@ -209,16 +198,9 @@ static int fill_args(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cfg,
   }
   if (cfg->sum_order == SLAMHIP_SUM_SEQUENTIAL && cfg->oope != SLAMHIP_OOPE_GMAPPING) {
     const size_t need = (size_t)n_poses * ctx->scan_n;
-    if (need > ctx->terms_cap) {
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (ctx->stream_b) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream_b));
-      if (ctx->d_terms) hipFree(ctx->d_terms);
-      ctx->d_terms = nullptr;
-      ctx->terms_cap = 0;
-      SLAMHIP_CHECK(hipMalloc(&ctx->d_terms, sizeof(double) * need));
-      ctx->terms_cap = need;
-    }
-    a->terms = ctx->d_terms;
+    const int trc = terms_room(ctx, need);
+    if (trc) return trc;
+    a->terms = ctx->d_terms.get();
   }
   return SLAMHIP_OK;
 }
@@ -385,7 +367,7 @@ static void gm_carry_fixup(slamhip_ctx *ctx, int n_poses) {
   if (ctx->gm_exact_last) return;  // (k_score_gmapping_exact applied the cache itself, pose after pose)
   const double tot_w = ctx->scan_tot_w;
   for (int p = 0; p < n_poses; ++p) {
-    GmPoseInfo &gi = ctx->h_gm_info[p];
+    GmPoseInfo &gi = ctx->h_gm_info.get()[p];
     double last_v = gi.last_v;
     if (ctx->gm_prob != -1.0 && gi.first_cx == ctx->gm_cx && gi.first_cy == ctx->gm_cy) {
       const double c = ctx->gm_prob;
@@ -393,7 +375,7 @@ static void gm_carry_fixup(slamhip_ctx *ctx, int n_poses) {
         double delta = 0.0;
         for (int b = 0; b < gi.run0_len; ++b)
           delta += (c * ctx->h_weight[b]) * ctx->h_factor[b] - (gi.v0 * ctx->h_weight[b]) * ctx->h_factor[b];
-        if (tot_w != 0.0) ctx->h_scores[p] += delta / tot_w;
+        if (tot_w != 0.0) ctx->h_scores.get()[p] += delta / tot_w;
       }
       if (gi.last_head == 0) last_v = c;
     }
@@ -406,8 +388,8 @@ static void gm_carry_fixup(slamhip_ctx *ctx, int n_poses) {
 int lane_fork(slamhip_ctx *ctx) {
   if (!ctx->stream_b) {
     SLAMHIP_CHECK(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
-    SLAMHIP_CHECK(hipHostMalloc(&ctx->h_done_flag_b, sizeof(unsigned), kPinned));
-    *ctx->h_done_flag_b = 0;
+    SLAMHIP_CHECK(ctx->h_done_flag_b.alloc(1, kPinned));
+    *ctx->h_done_flag_b.get() = 0;
     SLAMHIP_CHECK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
   }
   SLAMHIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -417,7 +399,7 @@ int lane_fork(slamhip_ctx *ctx) {
 
 int score_wait(slamhip_ctx *ctx, unsigned seq, int lane) {
   if (seq == 0) return SLAMHIP_OK;  // the launch was synchronous
-  volatile unsigned *flag = lane ? ctx->h_done_flag_b : ctx->h_done_flag;
+  volatile unsigned *flag = lane ? ctx->h_done_flag_b.get() : ctx->h_done_flag.get();
   const hipStream_t stream = lane ? ctx->stream_b : ctx->stream;
   unsigned long long spins = 0;
   // launches publish increasing numbers on one stream: "reached seq" = the signed distance is >= 0
@@ -497,20 +479,14 @@ int scan_exact_angles(slamhip_ctx *ctx, const double **d_angle) {
     return SLAMHIP_ERR_STATE;
   }
   if (!ctx->scan_angle_on_device) {
-    if (n > ctx->scan_angle_cap) {
-      SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (ctx->d_scan_angle) hipFree(ctx->d_scan_angle);
-      ctx->d_scan_angle = nullptr;
-      ctx->scan_angle_cap = 0;
-      const int cap = (n + 2047) & ~2047;
-      SLAMHIP_CHECK(hipMalloc(&ctx->d_scan_angle, sizeof(double) * cap));
-      ctx->scan_angle_cap = cap;
-    }
+    // (whole 2048s: the floor is the rounded size itself)
+    const int grc = grow_block(ctx->stream, ctx->d_scan_angle, ctx->scan_angle_cap, (size_t)n, (size_t)((n + 2047) & ~2047));
+    if (grc) return grc;
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));  // (an earlier exact call may still read the old angles)
-    SLAMHIP_CHECK(hipMemcpy(ctx->d_scan_angle, ctx->h_scan_angle.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    SLAMHIP_CHECK(hipMemcpy(ctx->d_scan_angle.get(), ctx->h_scan_angle.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     ctx->scan_angle_on_device = true;
   }
-  *d_angle = ctx->d_scan_angle;
+  *d_angle = ctx->d_scan_angle.get();
   return SLAMHIP_OK;
 }
 
@@ -535,37 +511,37 @@ static int score_exact(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cf
     const int rc = scan_exact_angles(ctx, &d_angle);
     if (rc) return rc;
   }
-  const double *poses_src = ctx->h_poses + 3 * (size_t)off;
-  const double *sc_src = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST ? ctx->h_pose_sc + 2 * (size_t)off : nullptr;
+  const double *poses_src = ctx->h_poses.get() + 3 * (size_t)off;
+  const double *sc_src = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST ? ctx->h_pose_sc.get() + 2 * (size_t)off : nullptr;
   ScoreArgs a;
-  int rc = fill_args(ctx, m, cfg, n_poses, poses_src, sc_src, ctx->h_scores + off, &a);
+  int rc = fill_args(ctx, m, cfg, n_poses, poses_src, sc_src, ctx->h_scores.get() + off, &a);
   if (rc) return rc;
   const int n = ctx->scan_n;
   if (gm) {
     if (tiled) {
       a.tables = tiled->tables;
-      a.pose_slot = ctx->h_pose_slot + off;
+      a.pose_slot = ctx->h_pose_slot.get() + off;
       a.table_stride = tiled->table_stride;
     }
-    if (!ctx->d_gm_exact_cache) SLAMHIP_CHECK(hipMalloc(&ctx->d_gm_exact_cache, 16));
+    if (!ctx->d_gm_exact_cache) SLAMHIP_CHECK(ctx->d_gm_exact_cache.alloc(16));
     struct {
       int cx, cy;
       double prob;
     } c = {ctx->gm_cx, ctx->gm_cy, ctx->gm_prob};
-    SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_gm_exact_cache, &c, sizeof c, hipMemcpyHostToDevice, ctx->stream));
-    hipError_t e = launch_score_gmapping_exact(fma, a, d_angle, raw ? 1 : 0, ctx->d_gm_exact_cache, ctx->stream);
+    SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_gm_exact_cache.get(), &c, sizeof c, hipMemcpyHostToDevice, ctx->stream));
+    hipError_t e = launch_score_gmapping_exact(fma, a, d_angle, raw ? 1 : 0, ctx->d_gm_exact_cache.get(), ctx->stream);
     if (e != hipSuccess) {
       if (e == hipErrorInvalidValue) return invalid("the exact GMapping kernel holds at most 3840 filtered beams per scan");
       return hip_fail(e, "k_score_gmapping_exact");
     }
-    SLAMHIP_CHECK(hipMemcpyAsync(&c, ctx->d_gm_exact_cache, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
+    SLAMHIP_CHECK(hipMemcpyAsync(&c, ctx->d_gm_exact_cache.get(), sizeof c, hipMemcpyDeviceToHost, ctx->stream));
     SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
     ctx->gm_cx = c.cx;
     ctx->gm_cy = c.cy;
     ctx->gm_prob = c.prob;
     ctx->gm_exact_last = true;
     // (no per-pose side outputs: a caller that replays them finds "no carry-in, nothing to fix")
-    for (int p = 0; p < n_poses; ++p) std::memset(&ctx->h_gm_info[off + p], 0, sizeof(GmPoseInfo));
+    for (int p = 0; p < n_poses; ++p) std::memset(&ctx->h_gm_info.get()[off + p], 0, sizeof(GmPoseInfo));
     if (ctx->profile) {
       ctx->prof_launches += 1;
       ctx->prof_units += (long long)n_poses * n;
@@ -574,17 +550,13 @@ static int score_exact(slamhip_ctx *ctx, DeviceMap &m, const slamhip_spe_cfg *cf
   }
   const size_t stride = (size_t)((n + 7) & ~7);
   const size_t need = 2 * stride * (size_t)n_poses + 2 * (size_t)n_poses;
-  if (need > ctx->exact_trig_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_exact_trig) hipFree(ctx->d_exact_trig);
-    ctx->d_exact_trig = nullptr;
-    ctx->exact_trig_cap = 0;
-    SLAMHIP_CHECK(hipMalloc(&ctx->d_exact_trig, sizeof(double) * need));
-    ctx->exact_trig_cap = need;
+  {
+    const int grc = grow_block(ctx->stream, ctx->d_exact_trig, ctx->exact_trig_cap, need, need);  // (exactly the call's)
+    if (grc) return grc;
   }
-  double *d_cos = ctx->d_exact_trig, *d_sin = d_cos + stride * (size_t)n_poses, *d_id = d_sin + stride * (size_t)n_poses;
+  double *d_cos = ctx->d_exact_trig.get(), *d_sin = d_cos + stride * (size_t)n_poses, *d_id = d_sin + stride * (size_t)n_poses;
   SLAMHIP_CHECK(launch_exact_beam_trig(fma, poses_src, n_poses, d_angle, n, stride, d_cos, d_sin, d_id, ctx->stream));
-  if (ctx->want_fprints && cfg->sum_order == SLAMHIP_SUM_TREE256) a.fprints = ctx->h_fprints + off;
+  if (ctx->want_fprints && cfg->sum_order == SLAMHIP_SUM_TREE256) a.fprints = ctx->h_fprints.get() + off;
   for (int p = 0; p < n_poses; ++p) {
     ScoreArgs ap = a;
     ap.n_poses = 1;
@@ -638,7 +610,7 @@ int score_staged(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, int n
       // one sincos call per pose: the reference build (g++ -O3) fuses the sin/cos pair of
       // set_base_angle (trigonometry_utils.h:57-60) into glibc's sincos, whose last bit can
       // differ from separate sin()/cos() calls
-      ::sincos(ctx->h_poses[3 * p + 2], &ctx->h_pose_sc[2 * p], &ctx->h_pose_sc[2 * p + 1]);
+      ::sincos(ctx->h_poses.get()[3 * p + 2], &ctx->h_pose_sc.get()[2 * p], &ctx->h_pose_sc.get()[2 * p + 1]);
     }
   }
   const bool gm = cfg->oope == SLAMHIP_OOPE_GMAPPING;
@@ -653,26 +625,26 @@ int score_staged(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, int n
     // 1-thread kernel behind it publishes the launch number in pinned memory; the host spins.
     // `off` selects a window of the staging buffers, so two launches can be in flight (the filter
     // plans one half of its particles while the GPU scores the other).
-    const double *poses_src = ctx->h_poses + 3 * (size_t)off;
-    const double *sc_src = host_trig ? ctx->h_pose_sc + 2 * (size_t)off : nullptr;
+    const double *poses_src = ctx->h_poses.get() + 3 * (size_t)off;
+    const double *sc_src = host_trig ? ctx->h_pose_sc.get() + 2 * (size_t)off : nullptr;
     if (ctx->stage_poses) {
-      SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_poses, ctx->h_poses, sizeof(double) * 3 * n_poses,
+      SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_poses.get(), ctx->h_poses.get(), sizeof(double) * 3 * n_poses,
                                    hipMemcpyHostToDevice, ctx->stream));
-      poses_src = ctx->d_poses;
+      poses_src = ctx->d_poses.get();
       if (host_trig) {
-        SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_pose_sc, ctx->h_pose_sc, sizeof(double) * 2 * n_poses,
+        SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_pose_sc.get(), ctx->h_pose_sc.get(), sizeof(double) * 2 * n_poses,
                                      hipMemcpyHostToDevice, ctx->stream));
-        sc_src = ctx->d_pose_sc;
+        sc_src = ctx->d_pose_sc.get();
       }
     }
-    rc = fill_args(ctx, *m, cfg, n_poses, poses_src, sc_src, ctx->h_scores + off, &a);
+    rc = fill_args(ctx, *m, cfg, n_poses, poses_src, sc_src, ctx->h_scores.get() + off, &a);
     if (rc) return rc;
-    if (gm) a.gm_info = ctx->h_gm_info + off;
+    if (gm) a.gm_info = ctx->h_gm_info.get() + off;
     if (ctx->want_fprints && cfg->oope != SLAMHIP_OOPE_GMAPPING && cfg->sum_order == SLAMHIP_SUM_TREE256)
-      a.fprints = ctx->h_fprints + off;
+      a.fprints = ctx->h_fprints.get() + off;
     if (tiled) {
       a.tables = tiled->tables;
-      a.pose_slot = ctx->h_pose_slot + off;
+      a.pose_slot = ctx->h_pose_slot.get() + off;
       a.table_stride = tiled->table_stride;
     }
     unsigned &counter = lane ? ctx->seq_b : ctx->seq;
@@ -681,7 +653,7 @@ int score_staged(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, int n
     const hipStream_t stream = lane ? ctx->stream_b : ctx->stream;
     rc = launch_timed(ctx, a, *m, cfg, stream);
     if (rc) return rc;
-    SLAMHIP_CHECK(launch_publish(lane ? ctx->h_done_flag_b : ctx->h_done_flag, seq, stream));
+    SLAMHIP_CHECK(launch_publish(lane ? ctx->h_done_flag_b.get() : ctx->h_done_flag.get(), seq, stream));
     if (async_seq) {
       *async_seq = seq;
       return SLAMHIP_OK;
@@ -689,20 +661,20 @@ int score_staged(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg, int n
     return score_wait(ctx, seq, lane);
   }
   if (host_trig)
-    SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_pose_sc, ctx->h_pose_sc, sizeof(double) * 2 * n_poses,
+    SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_pose_sc.get(), ctx->h_pose_sc.get(), sizeof(double) * 2 * n_poses,
                                  hipMemcpyHostToDevice, ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_poses, ctx->h_poses, sizeof(double) * 3 * n_poses,
+  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_poses.get(), ctx->h_poses.get(), sizeof(double) * 3 * n_poses,
                                hipMemcpyHostToDevice, ctx->stream));
-  rc = fill_args(ctx, *m, cfg, n_poses, ctx->d_poses, host_trig ? ctx->d_pose_sc : nullptr,
-                 ctx->d_scores, &a);
+  rc = fill_args(ctx, *m, cfg, n_poses, ctx->d_poses.get(), host_trig ? ctx->d_pose_sc.get() : nullptr,
+                 ctx->d_scores.get(), &a);
   if (rc) return rc;
-  if (gm) a.gm_info = ctx->d_gm_info;
+  if (gm) a.gm_info = ctx->d_gm_info.get();
   rc = launch_timed(ctx, a, *m, cfg, ctx->stream);
   if (rc) return rc;
-  SLAMHIP_CHECK(hipMemcpyAsync(ctx->h_scores, ctx->d_scores, sizeof(double) * n_poses,
+  SLAMHIP_CHECK(hipMemcpyAsync(ctx->h_scores.get(), ctx->d_scores.get(), sizeof(double) * n_poses,
                                hipMemcpyDeviceToHost, ctx->stream));
   if (gm)
-    SLAMHIP_CHECK(hipMemcpyAsync(ctx->h_gm_info, ctx->d_gm_info, sizeof(GmPoseInfo) * n_poses,
+    SLAMHIP_CHECK(hipMemcpyAsync(ctx->h_gm_info.get(), ctx->d_gm_info.get(), sizeof(GmPoseInfo) * n_poses,
                                  hipMemcpyDeviceToHost, ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return SLAMHIP_OK;
@@ -745,13 +717,13 @@ int slamhip_ctx_create(int device, slamhip_ctx **out) {
     delete ctx;
     return hip_fail(e, "hipStreamCreate");
   }
-  e = hipHostMalloc(&ctx->h_done_flag, sizeof(unsigned), kPinned);
+  e = ctx->h_done_flag.alloc(1, kPinned);
   if (e != hipSuccess) {
     hipStreamDestroy(ctx->stream);
     delete ctx;
     return hip_fail(e, "completion flag allocation");
   }
-  *ctx->h_done_flag = 0;
+  *ctx->h_done_flag.get() = 0;
   *out = ctx;
   return SLAMHIP_OK;
 }
@@ -804,55 +776,25 @@ int slamhip_ctx_destroy(slamhip_ctx *ctx) {
   if (!ctx) return SLAMHIP_OK;
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
+  if (ctx->stream_b) hipStreamSynchronize(ctx->stream_b);
   pyramids_release(ctx);
-  for (auto &m : ctx->maps) {
+  for (auto &m : ctx->maps) {  // (a map's planes change hands in slamhip_map_bind: raw pointers)
     if (m.d_payload) hipFree(m.d_payload);
     if (m.d_aux) hipFree(m.d_aux);
     if (m.d_prob) hipFree(m.d_prob);
   }
-  if (ctx->d_scan) hipFree(ctx->d_scan);
-  if (ctx->d_scan_angle) hipFree(ctx->d_scan_angle);
-  if (ctx->d_exact_trig) hipFree(ctx->d_exact_trig);
-  if (ctx->d_gm_exact_cache) hipFree(ctx->d_gm_exact_cache);
-  for (auto &sl : ctx->scan_slots)
-    if (sl.d_angle) hipFree(sl.d_angle);
-  for (auto &sl : ctx->scan_slots)
-    if (sl.d) hipFree(sl.d);
-  for (int k = 0; k < 2; ++k) {
-    if (ctx->h_scan_stage[k]) hipHostFree(ctx->h_scan_stage[k]);
-    if (ctx->scan_stage_done[k]) hipEventDestroy(ctx->scan_stage_done[k]);
-    if (k == 0 && ctx->h_scan_pulled) hipHostFree(ctx->h_scan_pulled);
-    if (k == 0 && ctx->d_scan_pull_count) hipFree(ctx->d_scan_pull_count);
-  }
-  if (ctx->d_poses) hipFree(ctx->d_poses);
-  if (ctx->d_scores) hipFree(ctx->d_scores);
-  if (ctx->d_pose_sc) hipFree(ctx->d_pose_sc);
-  if (ctx->d_gm_info) hipFree(ctx->d_gm_info);
-  if (ctx->h_poses) hipHostFree(ctx->h_poses);
-  if (ctx->h_scores) hipHostFree(ctx->h_scores);
-  if (ctx->h_pose_sc) hipHostFree(ctx->h_pose_sc);
-  if (ctx->h_gm_info) hipHostFree(ctx->h_gm_info);
-  if (ctx->h_fprints) hipHostFree(ctx->h_fprints);
-  if (ctx->h_pose_slot) hipHostFree(ctx->h_pose_slot);
-  if (ctx->d_terms) hipFree(ctx->d_terms);
-  if (ctx->d_dirty_xy) hipFree(ctx->d_dirty_xy);
-  if (ctx->d_dirty_val) hipFree(ctx->d_dirty_val);
-  for (hipEvent_t ev : ctx->ev_pool)
-    if (ev) hipEventDestroy(ev);
-  if (ctx->h_done_flag) hipHostFree(ctx->h_done_flag);
-  if (ctx->stream_b) {
-    hipStreamSynchronize(ctx->stream_b);
-    hipStreamDestroy(ctx->stream_b);
-    hipHostFree(ctx->h_done_flag_b);
-    hipEventDestroy(ctx->ev_fork);
-  }
   score_batch_release(ctx);
   mu_release(ctx);
-  render_release(ctx);
-  scan_gen_release(ctx);
   shard_release(ctx);
-  hipStreamDestroy(ctx->stream);
+  // the context's own blocks go with it; only then its streams and events
+  std::vector<hipEvent_t> events = ctx->ev_pool;
+  events.insert(events.end(), {ctx->scan_stage_done[0], ctx->scan_stage_done[1], ctx->ev_fork});
+  const hipStream_t stream = ctx->stream, stream_b = ctx->stream_b;
   delete ctx;
+  for (hipEvent_t ev : events)
+    if (ev) hipEventDestroy(ev);
+  if (stream_b) hipStreamDestroy(stream_b);
+  hipStreamDestroy(stream);
   return SLAMHIP_OK;
 }
 
@@ -1001,8 +943,9 @@ int slamhip_map_upload_window(slamhip_ctx *ctx, int map_id, int x0, int y0, int 
     return invalid("window outside the bound map");
   const int sh = cell_stride_host(m->cell_model), cd = cell_doubles(m->cell_model);
   const size_t bytes = (size_t)w * h * sh * sizeof(double);
-  double *d_tmp = nullptr;
-  SLAMHIP_CHECK(hipMalloc(&d_tmp, bytes));
+  DeviceBuf<double> tmp;
+  SLAMHIP_CHECK(tmp.alloc((size_t)w * h * sh));
+  double *const d_tmp = tmp.get();
   hipError_t e = hipMemcpyAsync(d_tmp, payload, bytes, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess)
     e = launch_repack_window(m->d_payload, m->pitch, cd, d_tmp, sh, x0, y0, w, h, ctx->stream);
@@ -1011,7 +954,6 @@ int slamhip_map_upload_window(slamhip_ctx *ctx, int map_id, int x0, int y0, int 
   if (e == hipSuccess && m->prob_ok)  // the probability plane of the written cells
     e = launch_prob_build(m->cell_model, m->d_payload, m->d_prob, m->width, m->height, m->pitch, x0, y0, w, h, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d_tmp);
   if (e != hipSuccess) return hip_fail(e, "map_upload_window");
   return SLAMHIP_OK;
 }
@@ -1044,29 +986,22 @@ int slamhip_map_apply_dirty(slamhip_ctx *ctx, int map_id, int n, const int *coor
         coords_xy[2 * i + 1] >= m->height)
       return invalid("dirty cell outside the bound window (re-bind the grown map first)");
   const int sh = cell_stride_host(m->cell_model), cd = cell_doubles(m->cell_model);
-  if (n > ctx->dirty_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_dirty_xy) hipFree(ctx->d_dirty_xy);
-    if (ctx->d_dirty_val) hipFree(ctx->d_dirty_val);
-    ctx->d_dirty_xy = nullptr;
-    ctx->d_dirty_val = nullptr;
-    ctx->dirty_cap = 0;
-    int cap = 1024;
-    while (cap < n) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&ctx->d_dirty_xy, sizeof(int) * 2 * cap));
-    SLAMHIP_CHECK(hipMalloc(&ctx->d_dirty_val, sizeof(double) * 4 * cap));
-    ctx->dirty_cap = cap;
-  }
-  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_dirty_xy, coords_xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice,
+  const int grc = grow_blocks({ctx->stream}, ctx->dirty_cap, (size_t)n, 1024, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(ctx->d_dirty_xy.alloc(2 * cap));
+    SLAMHIP_CHECK(ctx->d_dirty_val.alloc(4 * cap));
+    return SLAMHIP_OK;
+  });
+  if (grc) return grc;
+  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_dirty_xy.get(), coords_xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice,
                                ctx->stream));
-  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_dirty_val, payloads, sizeof(double) * sh * n,
+  SLAMHIP_CHECK(hipMemcpyAsync(ctx->d_dirty_val.get(), payloads, sizeof(double) * sh * n,
                                hipMemcpyHostToDevice, ctx->stream));
-  SLAMHIP_CHECK(launch_scatter_cells(m->d_payload, m->pitch, cd, sh, n, ctx->d_dirty_xy,
-                                     ctx->d_dirty_val, ctx->stream));
+  SLAMHIP_CHECK(launch_scatter_cells(m->d_payload, m->pitch, cd, sh, n, ctx->d_dirty_xy.get(),
+                                     ctx->d_dirty_val.get(), ctx->stream));
   if (m->nbr_ok)
-    SLAMHIP_CHECK(launch_nbr_cells(m->d_payload, m->width, m->height, m->pitch, m->nbr_th, n, ctx->d_dirty_xy, ctx->stream));
+    SLAMHIP_CHECK(launch_nbr_cells(m->d_payload, m->width, m->height, m->pitch, m->nbr_th, n, ctx->d_dirty_xy.get(), ctx->stream));
   if (m->prob_ok)
-    SLAMHIP_CHECK(launch_prob_cells(m->cell_model, m->d_payload, m->d_prob, m->width, m->height, m->pitch, n, ctx->d_dirty_xy, ctx->stream));
+    SLAMHIP_CHECK(launch_prob_cells(m->cell_model, m->d_payload, m->d_prob, m->width, m->height, m->pitch, n, ctx->d_dirty_xy.get(), ctx->stream));
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   return SLAMHIP_OK;
 }
@@ -1079,35 +1014,29 @@ int slamhip_map_apply_dirty(slamhip_ctx *ctx, int map_id, int n, const int *coor
 // kernel queued on the context's stream.
 static int scan_stage_acquire(slamhip_ctx *ctx, int n_max, double **st, size_t *stride) {
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  if (n_max > ctx->scan_cap) {
-    SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->stream_b) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream_b));
-    if (ctx->d_scan) hipFree(ctx->d_scan);
-    ctx->d_scan = nullptr;
-    ctx->scan_cap = 0;
-    int cap = 2048;
-    while (cap < n_max) cap *= 2;
-    SLAMHIP_CHECK(hipMalloc(&ctx->d_scan, sizeof(double) * 5 * cap));
+  // (kernels of both launch lanes read the scan block)
+  const int grc = grow_blocks({ctx->stream, second_lane(ctx)}, ctx->scan_cap,
+                              (size_t)(n_max > 0 ? n_max : 0), 2048, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(ctx->d_scan.alloc(5 * cap));
     for (int k = 0; k < 2; ++k) {
-      if (ctx->h_scan_stage[k]) hipHostFree(ctx->h_scan_stage[k]);
-      ctx->h_scan_stage[k] = nullptr;
-      SLAMHIP_CHECK(hipHostMalloc(&ctx->h_scan_stage[k], sizeof(double) * 5 * cap, hipHostMallocMapped));
+      SLAMHIP_CHECK(ctx->h_scan_stage[k].alloc(5 * cap, hipHostMallocMapped));
       if (!ctx->scan_stage_done[k]) SLAMHIP_CHECK(hipEventCreateWithFlags(&ctx->scan_stage_done[k], hipEventDisableTiming));
       ctx->scan_pull_seq[k] = 0;
     }
-    if (!ctx->h_scan_pulled) {
-      SLAMHIP_CHECK(hipHostMalloc(&ctx->h_scan_pulled, sizeof(unsigned) * 2, hipHostMallocMapped | hipHostMallocCoherent));
-      ctx->h_scan_pulled[0] = ctx->h_scan_pulled[1] = 0;
-      SLAMHIP_CHECK(hipMalloc(&ctx->d_scan_pull_count, sizeof(unsigned)));
+    if (!ctx->h_scan_pulled || !ctx->d_scan_pull_count) {
+      SLAMHIP_CHECK(ctx->h_scan_pulled.alloc(2, kPinned));
+      ctx->h_scan_pulled.get()[0] = ctx->h_scan_pulled.get()[1] = 0;
+      SLAMHIP_CHECK(ctx->d_scan_pull_count.alloc(1));
       // (on the context's stream: hipMemset on the null stream is not ordered with it -- the first pull's workgroups
       // were seen counting into a word that was cleared under them)
-      SLAMHIP_CHECK(hipMemsetAsync(ctx->d_scan_pull_count, 0, sizeof(unsigned), ctx->stream));
+      SLAMHIP_CHECK(hipMemsetAsync(ctx->d_scan_pull_count.get(), 0, sizeof(unsigned), ctx->stream));
     }
-    ctx->scan_cap = cap;
-  }
+    return SLAMHIP_OK;
+  });
+  if (grc) return grc;
   const int turn = ctx->scan_stage_turn;
   if (ctx->scan_pull_seq[turn] != 0) {
-    volatile unsigned *pulled = ctx->h_scan_pulled + turn;
+    volatile unsigned *pulled = ctx->h_scan_pulled.get() + turn;
     unsigned long long spins = 0;
     while (*pulled != ctx->scan_pull_seq[turn]) {
       __builtin_ia32_pause();
@@ -1117,13 +1046,13 @@ static int scan_stage_acquire(slamhip_ctx *ctx, int n_max, double **st, size_t *
         if (qe == hipSuccess && *pulled != ctx->scan_pull_seq[turn]) {
           char msg[200];
           std::snprintf(msg, sizeof msg, "internal: a scan pull never reported back (buffer %d: pull %u queued, %u / %u reported, %u pulls so far)",
-                        turn, ctx->scan_pull_seq[turn], ctx->h_scan_pulled[0], ctx->h_scan_pulled[1], ctx->scan_pull_next);
+                        turn, ctx->scan_pull_seq[turn], ctx->h_scan_pulled.get()[0], ctx->h_scan_pulled.get()[1], ctx->scan_pull_next);
           return invalid(msg);
         }
       }
     }
   }
-  *st = ctx->h_scan_stage[turn];
+  *st = ctx->h_scan_stage[turn].get();
   *stride = (size_t)((n_max + 7) & ~7);
   return SLAMHIP_OK;
 }
@@ -1136,7 +1065,7 @@ static int scan_stage_acquire(slamhip_ctx *ctx, int n_max, double **st, size_t *
 static unsigned scan_stage_turnover(slamhip_ctx *ctx, int n, size_t stride, double tot_w, int *turn_out) {
   ctx->scan_tot_w = tot_w;
   ctx->scan_n = n;
-  ctx->scan_ptr = ctx->d_scan;
+  ctx->scan_ptr = ctx->d_scan.get();
   ctx->scan_stride = stride;
   ctx->h_scan_angle.clear();  // (the angles of the scan before: slamhip_scan_set_angles)
   ctx->scan_angle_lazy = false;
@@ -1166,8 +1095,8 @@ static int scan_stage_commit(slamhip_ctx *ctx, int n, double *st, size_t stride)
   int turn = 0;
   const unsigned seq = scan_stage_turnover(ctx, n, stride, scan_total_weight(weight, n), &turn);
   // (one pull over the five stretches, gaps included: 5 x stride doubles are 43 KB at 1080 beams)
-  SLAMHIP_CHECK(launch_scan_pull(st, ctx->d_scan, 4 * stride + (size_t)n, ctx->d_scan_pull_count,
-                                 ctx->h_scan_pulled + turn, seq, ctx->stream));
+  SLAMHIP_CHECK(launch_scan_pull(st, ctx->d_scan.get(), 4 * stride + (size_t)n, ctx->d_scan_pull_count.get(),
+                                 ctx->h_scan_pulled.get() + turn, seq, ctx->stream));
   return scan_stage_fork(ctx, turn);
 }
 
@@ -1200,15 +1129,11 @@ int slamhip_scan_store(slamhip_ctx *ctx, int slot, int n, const double *range, c
   // work queued on the context may still read the slot (or the scan it is selected as)
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (ctx->stream_b) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream_b));
-  if (n > sl.cap) {
-    const bool selected = ctx->scan_ptr == sl.d && sl.d;
-    if (sl.d) hipFree(sl.d);
-    sl.d = nullptr;
-    sl.cap = 0;
-    const int cap = (n + 7) & ~7;
-    SLAMHIP_CHECK(hipMalloc(&sl.d, sizeof(double) * 5 * cap));
-    sl.cap = cap;
-    if (selected) ctx->scan_ptr = sl.d;
+  {  // (five rows of whole eights: the floor is the rounded size itself)
+    const bool selected = sl.d && ctx->scan_ptr == sl.d.get();
+    const int grc = grow_block(ctx->stream, sl.d, sl.cap, (size_t)n, (size_t)((n + 7) & ~7), 5);
+    if (selected) ctx->scan_ptr = sl.d.get();
+    if (grc) return grc;
   }
   sl.n = n;
   sl.angle.clear();  // (the angles of the scan before: slamhip_scan_store_angles)
@@ -1219,12 +1144,12 @@ int slamhip_scan_store(slamhip_ctx *ctx, int slot, int n, const double *range, c
   for (int i = 0; i < n; ++i) tot_w += weight[i];
   sl.tot_w = tot_w;
   const size_t bytes = sizeof(double) * n, c = (size_t)sl.cap;
-  SLAMHIP_CHECK(hipMemcpy(sl.d, range, bytes, hipMemcpyHostToDevice));
-  SLAMHIP_CHECK(hipMemcpy(sl.d + c, cos_a, bytes, hipMemcpyHostToDevice));
-  SLAMHIP_CHECK(hipMemcpy(sl.d + 2 * c, sin_a, bytes, hipMemcpyHostToDevice));
-  SLAMHIP_CHECK(hipMemcpy(sl.d + 3 * c, weight, bytes, hipMemcpyHostToDevice));
-  SLAMHIP_CHECK(hipMemcpy(sl.d + 4 * c, sl.f.data(), bytes, hipMemcpyHostToDevice));
-  if (ctx->scan_ptr == sl.d) {  // the selected scan was rewritten in place
+  SLAMHIP_CHECK(hipMemcpy(sl.d.get(), range, bytes, hipMemcpyHostToDevice));
+  SLAMHIP_CHECK(hipMemcpy(sl.d.get() + c, cos_a, bytes, hipMemcpyHostToDevice));
+  SLAMHIP_CHECK(hipMemcpy(sl.d.get() + 2 * c, sin_a, bytes, hipMemcpyHostToDevice));
+  SLAMHIP_CHECK(hipMemcpy(sl.d.get() + 3 * c, weight, bytes, hipMemcpyHostToDevice));
+  SLAMHIP_CHECK(hipMemcpy(sl.d.get() + 4 * c, sl.f.data(), bytes, hipMemcpyHostToDevice));
+  if (ctx->scan_ptr == sl.d.get()) {  // the selected scan was rewritten in place
     ctx->h_scan_angle.clear();
     ctx->scan_angle_lazy = false;
     ctx->scan_angle_on_device = false;
@@ -1242,7 +1167,7 @@ int slamhip_scan_select(slamhip_ctx *ctx, int slot) {
   if (slot < 0 || slot >= (int)ctx->scan_slots.size() || !ctx->scan_slots[slot].d || ctx->scan_slots[slot].n <= 0)
     return invalid("no scan stored in that slot");
   const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[slot];
-  ctx->scan_ptr = sl.d;
+  ctx->scan_ptr = sl.d.get();
   ctx->scan_stride = (size_t)sl.cap;
   ctx->scan_n = sl.n;
   ctx->h_scan_angle = sl.angle;  // (none unless slamhip_scan_store_angles gave the slot some)
@@ -1263,17 +1188,13 @@ int slamhip_scan_store_angles(slamhip_ctx *ctx, int slot, int n, const double *a
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
   // work queued on the context may still read the slot's angles
   SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (n > sl.angle_cap) {
-    if (sl.d_angle) hipFree(sl.d_angle);
-    sl.d_angle = nullptr;
-    sl.angle_cap = 0;
-    const int cap = (n + 7) & ~7;
-    SLAMHIP_CHECK(hipMalloc(&sl.d_angle, sizeof(double) * cap));
-    sl.angle_cap = cap;
+  {
+    const int grc = grow_block(ctx->stream, sl.d_angle, sl.angle_cap, (size_t)n, (size_t)((n + 7) & ~7));
+    if (grc) return grc;
   }
-  SLAMHIP_CHECK(hipMemcpy(sl.d_angle, angle, sizeof(double) * n, hipMemcpyHostToDevice));
+  SLAMHIP_CHECK(hipMemcpy(sl.d_angle.get(), angle, sizeof(double) * n, hipMemcpyHostToDevice));
   sl.angle.assign(angle, angle + n);
-  if (ctx->scan_ptr == sl.d) {  // the slot is the current scan
+  if (ctx->scan_ptr == sl.d.get()) {  // the slot is the current scan
     ctx->h_scan_angle = sl.angle;
     ctx->scan_angle_lazy = false;
     ctx->scan_angle_on_device = false;
@@ -1384,7 +1305,7 @@ int scan_assemble_now(slamhip_ctx *ctx) {
   slamhip_ctx::ScanPending &sp = ctx->scan_pending;
   if (!sp.active) return SLAMHIP_OK;
   sp.active = false;
-  const hipError_t e = launch_scan_assemble(sp.as, ctx->d_scan_pull_count, ctx->h_scan_pulled + sp.turn, sp.seq, ctx->stream);
+  const hipError_t e = launch_scan_assemble(sp.as, ctx->d_scan_pull_count.get(), ctx->h_scan_pulled.get() + sp.turn, sp.seq, ctx->stream);
   scan_record_finish(ctx);
   SLAMHIP_CHECK(e);
   return scan_stage_fork(ctx, sp.turn);
@@ -1397,7 +1318,7 @@ int scan_fused_done(slamhip_ctx *ctx) {
   ++ctx->raw_prologue_matches;
   scan_record_finish(ctx);
   // the staging buffer has been read: what the assembly kernel's last workgroup would have told scan_stage_acquire
-  __atomic_store_n(ctx->h_scan_pulled + sp.turn, sp.seq, __ATOMIC_RELAXED);
+  __atomic_store_n(ctx->h_scan_pulled.get() + sp.turn, sp.seq, __ATOMIC_RELAXED);
   return scan_stage_fork(ctx, sp.turn);
 }
 
@@ -1467,7 +1388,7 @@ int scan_filter_stage(slamhip_ctx *ctx, int map_id, int n, const double *range, 
   if (weighting == 1) as.tab_viny = ctx->scan_tab.viny();
   as.tab_cos = ctx->scan_tab.cos();
   as.tab_sin = ctx->scan_tab.sin();
-  as.dst = ctx->d_scan;
+  as.dst = ctx->d_scan.get();
   as.stride = c;
   as.n = k;
   int turn = 0;
@@ -1528,13 +1449,13 @@ int slamhip_libm_eval(slamhip_ctx *ctx, int variant, int fn, int n, const double
     return invalid("bad arguments");
   if (n == 0) return SLAMHIP_OK;
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
-  double *d = nullptr;
-  SLAMHIP_CHECK(hipMalloc(&d, sizeof(double) * 2 * (size_t)n));
+  DeviceBuf<double> both;  // x | f(x)
+  SLAMHIP_CHECK(both.alloc(2 * (size_t)n));
+  double *const d = both.get();
   hipError_t e = hipMemcpyAsync(d, x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = launch_libm_eval(variant == 1, fn, d, d + n, n, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out, d + n, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d);
   if (e != hipSuccess) return hip_fail(e, "slamhip_libm_eval");
   return SLAMHIP_OK;
 }
@@ -1561,11 +1482,11 @@ int slamhip_score_poses(slamhip_ctx *ctx, int map_id, const slamhip_spe_cfg *cfg
   SLAMHIP_CHECK(hipSetDevice(ctx->device));
   int rc = ensure_pose_capacity(ctx, n_poses);
   if (rc) return rc;
-  std::memcpy(ctx->h_poses, poses_xyt, sizeof(double) * 3 * n_poses);
+  std::memcpy(ctx->h_poses.get(), poses_xyt, sizeof(double) * 3 * n_poses);
   rc = score_staged(ctx, map_id, cfg, n_poses);
   if (rc) return rc;
   if (cfg->oope == SLAMHIP_OOPE_GMAPPING) gm_carry_fixup(ctx, n_poses);
-  std::memcpy(scores_out, ctx->h_scores, sizeof(double) * n_poses);
+  std::memcpy(scores_out, ctx->h_scores.get(), sizeof(double) * n_poses);
   return SLAMHIP_OK;
 }
 
@@ -1629,15 +1550,8 @@ static int score_batch_shared(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int 
   if (!rc) rc = grow_block(st, s->h_scores, s->h_scores_cap, total, 1 << 12, 1, kPinned);
   if (!rc && !ctx->low_latency) rc = grow_block(st, s->d_scores, s->d_scores_cap, total, 1 << 12);
   if (rc) return rc;
-  if (seq_order && (size_t)plan.total_terms > ctx->terms_cap) {  // (the lone call's block, grown the way fill_args grows it)
-    SLAMHIP_CHECK(hipStreamSynchronize(st));
-    if (ctx->stream_b) SLAMHIP_CHECK(hipStreamSynchronize(ctx->stream_b));
-    if (ctx->d_terms) hipFree(ctx->d_terms);
-    ctx->d_terms = nullptr;
-    ctx->terms_cap = 0;
-    SLAMHIP_CHECK(hipMalloc(&ctx->d_terms, sizeof(double) * (size_t)plan.total_terms));
-    ctx->terms_cap = (size_t)plan.total_terms;
-  }
+  if (seq_order) rc = terms_room(ctx, (size_t)plan.total_terms);  // (the lone call's block)
+  if (rc) return rc;
   // the views a lone call of each job would score through (validated by the caller: one effective model and OIE)
   unsigned char *h = s->h_arena.get();
   ScoreJobView *views = reinterpret_cast<ScoreJobView *>(h + L.jobs);
@@ -1661,7 +1575,7 @@ static int score_batch_shared(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int 
     if (rc) return rc;
     if (j.scan_slot >= 0) {
       const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[(size_t)j.scan_slot];
-      v.scan = scan_view_of(sl.d, (size_t)sl.cap, sl.n, sl.tot_w);
+      v.scan = scan_view_of(sl.d.get(), (size_t)sl.cap, sl.n, sl.tot_w);
     } else {
       v.scan = scan_view_of(ctx->scan_ptr, ctx->scan_stride, ctx->scan_n, ctx->scan_tot_w);
     }
@@ -1686,7 +1600,7 @@ static int score_batch_shared(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int 
   a.poses = reinterpret_cast<const double *>(d + L.poses);
   a.pose_sc = host_trig ? reinterpret_cast<const double *>(d + L.pose_sc) : nullptr;
   a.scores = ctx->low_latency ? s->h_scores.get() : s->d_scores.get();
-  a.terms = seq_order ? ctx->d_terms : nullptr;
+  a.terms = seq_order ? ctx->d_terms.get() : nullptr;
   a.fprints = nullptr;
   a.total_poses = plan.total_poses;
   a.n_jobs = n_jobs;
@@ -1707,7 +1621,7 @@ static int score_batch_shared(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, int 
   if (ctx->low_latency) {
     unsigned seq = ++ctx->seq;
     if (seq == 0) seq = ++ctx->seq;
-    SLAMHIP_CHECK(launch_publish(ctx->h_done_flag, seq, st));
+    SLAMHIP_CHECK(launch_publish(ctx->h_done_flag.get(), seq, st));
     rc = score_wait(ctx, seq, 0);
     if (rc) return rc;
   } else {

@@ -322,8 +322,6 @@ bool mu_set_deferred(slamhip_ctx *ctx, bool on);      // map_update.hip: queue p
 int mu_drain(slamhip_ctx *ctx, long long *n_updates, int *err);
 void mu_release(slamhip_ctx *ctx);                    // map_update.hip: frees the context's K6 scratch
 void shard_release(slamhip_ctx *ctx);                 // shard.cpp: leaves the RCCL group, frees its staging
-void render_release(slamhip_ctx *ctx);                // map_render.hip: frees the context's render buffer
-void scan_gen_release(slamhip_ctx *ctx);              // scan_generate.hip: frees the context's scan-generation block
 void pyramids_release(slamhip_ctx *ctx);              // map_pyramid.hip: frees what the context's pyramids hold in HBM
 void score_batch_release(slamhip_ctx *ctx);           // slamhip_api.cpp: frees slamhip_score_poses_batch's staging
 void set_error(const std::string &msg);
@@ -339,37 +337,38 @@ hipError_t refuse_launch(const char *why);  // hipErrorInvalidValue; hip_fail ap
   } while (0)
 
 #include "hip_block.h"
+#include "scan_tables_device.h"
 
 struct slamhip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   std::vector<slamhip::DeviceMap> maps;
   // scan
-  double *d_scan = nullptr;  // 5 arrays of scan_cap doubles
+  slamhip::DeviceBuf<double> d_scan;  // 5 arrays of scan_cap doubles
   // slamhip_scan_upload: the five arrays packed in pinned memory (two buffers taking turns, an event each) and
   // sent with ONE asynchronous copy -- no wait for the stream, which may still be busy with a queued map update
-  double *h_scan_stage[2] = {nullptr, nullptr};
+  slamhip::PinnedBuf<double> h_scan_stage[2];
   hipEvent_t scan_stage_done[2] = {nullptr, nullptr};  // (recorded for the second launch lane only)
   int scan_stage_turn = 0;
   // ... pulled into HBM by a kernel (k_scan_pull): the sequence number of the pull that last read each buffer, what
   // the kernel reported back (pinned), its arrival counter
   unsigned scan_pull_seq[2] = {0, 0}, scan_pull_next = 0;
-  unsigned *h_scan_pulled = nullptr;
-  unsigned *d_scan_pull_count = nullptr;
+  slamhip::PinnedBuf<unsigned> h_scan_pulled;
+  slamhip::DeviceBuf<unsigned> d_scan_pull_count;
   int scan_cap = 0, scan_n = 0;
   double scan_tot_w = 0.0;
   // the scan the kernels read: d_scan after slamhip_scan_upload, a stored scan after slamhip_scan_select
   const double *scan_ptr = nullptr;
   size_t scan_stride = 0;
   struct ScanSlot {  // slamhip_scan_store: a filtered scan kept resident in HBM (five arrays of `cap` doubles)
-    double *d = nullptr;
+    slamhip::DeviceBuf<double> d;
     int cap = 0, n = 0;
     double tot_w = 0.0;
     std::vector<double> w, f;
     // slamhip_scan_store_angles: the points' angles (SLAMHIP_POSE_TRIG_RAW_EXACT), on the host and in HBM; empty after
     // a slamhip_scan_store into the slot
     std::vector<double> angle;
-    double *d_angle = nullptr;
+    slamhip::DeviceBuf<double> d_angle;
     int angle_cap = 0;
   };
   std::vector<ScanSlot> scan_slots;
@@ -407,46 +406,47 @@ struct slamhip_ctx {
   // after slamhip_scan_filter_upload they are scan_prep.angle[scan_prep.kept[q]] and are written out only when somebody
   // asks (slamhip::scan_angles_materialise): the default scoring modes never do
   bool scan_angle_lazy = false;
-  double *d_scan_angle = nullptr;
+  slamhip::DeviceBuf<double> d_scan_angle;
   int scan_angle_cap = 0;
   bool scan_angle_on_device = false;
-  double *d_exact_trig = nullptr;
+  slamhip::DeviceBuf<double> d_exact_trig;
   size_t exact_trig_cap = 0;
-  void *d_gm_exact_cache = nullptr;
+  slamhip::DeviceBuf<unsigned char> d_gm_exact_cache;
   bool gm_exact_last = false;  // the last scoring call applied the GMapping cache itself: no host fix-up after it
   // pose / score staging
-  double *d_poses = nullptr, *d_scores = nullptr, *d_pose_sc = nullptr;
-  double *h_poses = nullptr, *h_scores = nullptr, *h_pose_sc = nullptr;  // pinned
-  slamhip::GmPoseInfo *d_gm_info = nullptr, *h_gm_info = nullptr;
-  unsigned long long *h_fprints = nullptr;  // pinned, next to h_scores
+  slamhip::DeviceBuf<double> d_poses, d_scores, d_pose_sc;
+  slamhip::PinnedBuf<double> h_poses, h_scores, h_pose_sc;
+  slamhip::DeviceBuf<slamhip::GmPoseInfo> d_gm_info;
+  slamhip::PinnedBuf<slamhip::GmPoseInfo> h_gm_info;
+  slamhip::PinnedBuf<unsigned long long> h_fprints;  // next to h_scores
   bool want_fprints = false;      // the next score_staged() asks K1 for fingerprints (matchers' checked mode)
-  int *h_pose_slot = nullptr;  // pinned: map slot of every staged pose (per-particle maps only)
+  slamhip::PinnedBuf<int> h_pose_slot;  // map slot of every staged pose (per-particle maps only)
   int pose_cap = 0;
-  double *d_terms = nullptr;
+  slamhip::DeviceBuf<double> d_terms;
   size_t terms_cap = 0;
   void *score_batch = nullptr;  // ScoreBatchStage: slamhip_score_poses_batch's arena, results and last stats (slamhip_api.cpp)
   // dirty-cell staging
-  int *d_dirty_xy = nullptr;
-  double *d_dirty_val = nullptr;
+  slamhip::DeviceBuf<int> d_dirty_xy;
+  slamhip::DeviceBuf<double> d_dirty_val;
   int dirty_cap = 0;
   // GMapping OOPE cache (gmapping_occupancy_observation_pe.h:43-44)
   int gm_cx = 0, gm_cy = 0;
   double gm_prob = -1.0;
   // low-latency completion flag (k_publish in score_kernels.hip)
-  unsigned *h_done_flag = nullptr;  // pinned, coherent
+  slamhip::PinnedBuf<unsigned> h_done_flag;  // coherent
   unsigned seq = 0;
   // second launch lane (stream + completion flag): the filter's two job groups score on one lane each,
   // so that one group's kernel can start while the other's is still draining / publishing
   hipStream_t stream_b = nullptr;
-  unsigned *h_done_flag_b = nullptr;
+  slamhip::PinnedBuf<unsigned> h_done_flag_b;
   unsigned seq_b = 0;
   hipEvent_t ev_fork = nullptr;
   void *shard = nullptr;  // RCCL group of the context (shard.cpp), or null
   void *mu_scratch = nullptr, *mu_bscratch = nullptr;  // K6 work buffers (map_update.hip), owned by the context
   void *mu_kscratch = nullptr;  // ... of slamhip_map_append_scan_batch: the per-job arena, staging, direction tables
-  unsigned char *d_render = nullptr;  // the render kernels' output (map_render.hip): grows on demand, freed with the context
+  slamhip::DeviceBuf<unsigned char> d_render;  // the render kernels' output (map_render.hip): grows on demand
   size_t render_cap = 0;
-  void *d_scan_gen = nullptr;  // slamhip_map_generate_scans' block in HBM (scan_generate.hip): grows on demand, freed with the context
+  slamhip::DeviceBuf<unsigned char> d_scan_gen;  // slamhip_map_generate_scans' block in HBM (scan_generate.hip): grows on demand
   size_t scan_gen_cap = 0;
   std::vector<double> scan_gen_stage;  // ... and its host side: what goes up and what comes back, one copy each
   std::vector<void *> pyramids;  // the slamhip_pyramid objects made over this context's maps (map_pyramid.hip)
