@@ -1181,6 +1181,52 @@ int slamhip_gmapping_particle_map_render(slamhip_gmapping *g, int particle, int 
 int slamhip_gmapping_particle_generate_scans(slamhip_gmapping *g, int variant, int flags, int n_jobs, const int *particles,
                                              const double *poses_xyt, int n_angles, const double *angles, double max_dist,
                                              double occ_threshold, double *range_out, unsigned char *status_out);
+/* Pose sets scored over the particles' OWN maps: job k = n_poses poses under one scan over the map of LOCAL particle
+ * `particle` (indices as slamhip_gmapping_particle_map_download takes them; a particle may be named by several jobs;
+ * scan_slot as in slamhip_score_job: a scan of slamhip_scan_store on the filter's context, or -1 for its current scan),
+ * all jobs through ONE scoring launch over the tile pool and ONE launch that carries each job's run cache from pose to
+ * pose -- a heat map over the heaviest particle's map, likelihoods of poses sampled around every particle's pose, "which
+ * particle's map explains this scan", without the 40-byte-per-cell download and dense re-upload.  scores_out: the jobs'
+ * scores one job after the other, sum of n_poses doubles.
+ * Configuration: cfg->oope must be SLAMHIP_OOPE_GMAPPING (the pool holds GMAPPING cells); gm_window 0..4, any
+ * gm_fullness_th; sum_order SLAMHIP_SUM_TREE256; pose_trig SLAMHIP_POSE_TRIG_DEVICE or _HOST.
+ * Value: job k's scores are bit-equal to slamhip_gmapping_particle_map_download of a window that covers the pool's
+ * extent, that window bound and uploaded as a dense SLAMHIP_CELL_GMAPPING map, slamhip_gm_cache_reset,
+ * slamhip_scan_select(scan_slot) and slamhip_score_poses(that map, cfg, the job's poses) -- whatever the other jobs are,
+ * whichever kernel form runs and however poses are dealt to workgroups.  NaN where the scan's weights add up to 0.  A
+ * cell outside the pool's extent and the shared unknown tile both read as the never-observed cell, as in the render and
+ * scan-generation calls above.
+ * Run cache: GmappingOccupancyObservationPE's _cached_coord / _cached_prob (gmapping_occupancy_observation_pe.h:21-24,
+ * 36-37) starts EMPTY for every job and is carried from pose to pose within the job, in the order given: a job is one
+ * estimator object scoring its list.  The context's own cache (slamhip_gm_cache_get) and its current scan are what
+ * they were before the call.
+ * Neighbourhood masks: the tiles' masks are used only when the pool's masks are valid for cfg->gm_fullness_th and
+ * gm_window == 1 (the filter's own matching configuration); the call never re-derives them for another threshold --
+ * such a call reads the nine cells.
+ * Queued on the context's stream behind every queued pool operation (clones, table patches, appends); writes nothing to
+ * the pool; returns with scores_out filled.  A call with at least one pose makes exactly TWO launches, scoring and
+ * carry, whatever the number of jobs, and ONE host-to-device copy (a pinned arena: job table, block table, poses and,
+ * under SLAMHIP_POSE_TRIG_HOST, their sin / cos).  n_jobs == 0 and jobs with n_poses == 0 are legal and launch nothing;
+ * such a job's particle and slot are not looked at.  While slamhip_profile_enable is on, both kernels' time is added
+ * to kernel_ms_total.
+ * Errors are found before anything is staged or queued and leave scores_out, the stats below, the current scan and
+ * the cache untouched.  SLAMHIP_ERR_INVALID: null arguments, a filter without particle maps, a particle out of range,
+ * a slot out of range, another OOPE, SLAMHIP_SUM_SEQUENTIAL or SLAMHIP_POSE_TRIG_RAW_EXACT (not built: the exact
+ * modes stay with the filter's own path), a scan above 2048 points ("the GMapping kernel holds at most 2048 filtered
+ * beams per scan").  SLAMHIP_ERR_STATE: an empty slot, slot -1 without a current scan. */
+typedef struct {
+  int particle;            /* LOCAL particle index; may repeat over jobs */
+  int scan_slot;           /* 0..4095: a scan of slamhip_scan_store on the filter's context; -1: its current scan */
+  int n_poses;             /* >= 0 */
+  const double *poses_xyt; /* n_poses x (x, y, theta), host */
+} slamhip_particle_score_job;
+int slamhip_gmapping_particle_score_poses(slamhip_gmapping *g, const slamhip_spe_cfg *cfg, int n_jobs,
+                                          const slamhip_particle_score_job *jobs,
+                                          double *scores_out /* sum of n_poses, job after job */);
+/* Of the last slamhip_gmapping_particle_score_poses that was not refused: jobs with poses, poses, kernels launched
+ * (2, or 0 for a call without poses), and the poses whose first run took the carried value instead of its fresh one. */
+int slamhip_gmapping_particle_score_stats(slamhip_gmapping *g, int *jobs_scored, long long *poses_scored,
+                                          int *launches, long long *poses_carried);
 /* The append half of GmappingWorld::handle_observation (gmapping_world.h:93-97) for a set of local
  * particles at once: the raw scan is appended to the map of particle particles[k] from poses3[3k..3k+2] --
  * ONE batched K6 over all (particle, beam) pairs, copy-on-write first.  The filter step does this itself for

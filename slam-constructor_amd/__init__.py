@@ -78,7 +78,8 @@ slamhip_map_append_scan_batch slamhip_map_update_batch_stats slamhip_map_update_
 slamhip_gmapping_particle_generate_scans slamhip_scan_generate_host_tiled
 slamhip_pyramid_refresh_batch slamhip_pyramid_refresh_batch_stats
 slamhip_matcher_m3rsm_match_each_raw slamhip_matcher_m3rsm_each_scan_download
-slamhip_score_poses_batch slamhip_score_poses_batch_stats""".split()
+slamhip_score_poses_batch slamhip_score_poses_batch_stats
+slamhip_gmapping_particle_score_poses slamhip_gmapping_particle_score_stats""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -103,6 +104,11 @@ class PyramidRefreshJob(C.Structure):
 class ScoreJob(C.Structure):
     """slamhip_score_job: one pose set of slamhip_score_poses_batch."""
     _fields_ = [("map_id", C.c_int), ("scan_slot", C.c_int), ("n_poses", C.c_int), ("poses_xyt", _dp)]
+
+
+class ParticleScoreJob(C.Structure):
+    """slamhip_particle_score_job: one pose set of slamhip_gmapping_particle_score_poses."""
+    _fields_ = [("particle", C.c_int), ("scan_slot", C.c_int), ("n_poses", C.c_int), ("poses_xyt", _dp)]
 
 
 class MatchJob(C.Structure):
@@ -1961,6 +1967,42 @@ class GmappingFilter:
                                                                _d(angles), float(max_dist), float(occ_threshold), _d(rng),
                                                                status.ctypes.data))
         return rng, status
+
+    def score_particle_poses(self, jobs, cfg):
+        """slamhip_gmapping_particle_score_poses: jobs = [dict(particle=, scan_slot=, poses=), ...] (particle: a LOCAL
+        index, may repeat; scan_slot -1: the context's current scan; poses (n, 3), n >= 0, or a pose count without poses
+        to hand the library a null pointer) scored over the particles' own maps in one scoring launch and one carry
+        launch.  Returns one array of scores per job, each bit-equal to the job's map downloaded, uploaded as a dense map
+        and scored by gm_cache_reset + scan_select(scan_slot) + score_poses."""
+        jobs = list(jobs)
+        table = (ParticleScoreJob * max(len(jobs), 1))()
+        keep, counts = [], []
+        for k, job in enumerate(jobs):
+            table[k].particle, table[k].scan_slot = int(job["particle"]), int(job.get("scan_slot", -1))
+            poses = job["poses"]
+            if isinstance(poses, (int, np.integer)):
+                table[k].n_poses, table[k].poses_xyt = int(poses), None
+            else:
+                p = _f64(poses).reshape(-1, 3)
+                keep.append(p)
+                table[k].n_poses, table[k].poses_xyt = p.shape[0], _d(p)
+            counts.append(table[k].n_poses)
+        total = int(sum(max(c, 0) for c in counts))
+        flat = np.zeros(total)
+        self.L.slamhip_gmapping_particle_score_poses.argtypes = [C.c_void_p, C.POINTER(SpeCfg), C.c_int,
+                                                                 C.POINTER(ParticleScoreJob), _dp]
+        _check(self.L.slamhip_gmapping_particle_score_poses(self.h, C.byref(cfg), len(jobs), table, _d(flat)))
+        edges = np.concatenate([[0], np.cumsum(np.maximum(counts, 0))]).astype(int) if counts else np.zeros(1, int)
+        return [flat[edges[k]:edges[k + 1]] for k in range(len(jobs))]
+
+    def particle_score_stats(self):
+        """of the last score_particle_poses that was not refused: jobs with poses, poses, kernels launched, poses whose
+        first run took the value carried over from the pose before"""
+        js, ps, la, pc = C.c_int(), C.c_longlong(), C.c_int(), C.c_longlong()
+        self.L.slamhip_gmapping_particle_score_stats.argtypes = [C.c_void_p, _ip, C.POINTER(C.c_longlong), _ip,
+                                                                 C.POINTER(C.c_longlong)]
+        _check(self.L.slamhip_gmapping_particle_score_stats(self.h, C.byref(js), C.byref(ps), C.byref(la), C.byref(pc)))
+        return dict(jobs_scored=js.value, poses_scored=ps.value, launches=la.value, poses_carried=pc.value)
 
     def export_particle_map(self, particle):
         """The LOCAL particle's map as one uint8 array (tile positions + tiles) for another rank."""

@@ -36,6 +36,7 @@
 #include <string>
 #include <type_traits>
 
+#include "gm_score_batch.h"
 #include "matchers.h"
 #include "tile_pool.h"
 
@@ -97,6 +98,17 @@ static void copy_as_duplicate(GmParticle &dst, const GmParticle &src) {
   dst.is_master = 0;
 }
 
+// what slamhip_gmapping_particle_score_poses keeps between calls: the arena (pinned and in HBM: one copy up), the
+// results (scores | per-job carry counts: one copy back), the side outputs between its two launches, the last call's stats
+struct ParticleScoreStage {
+  PinnedBuf<unsigned char> h_arena, h_out;
+  DeviceBuf<unsigned char> d_arena, d_out;
+  DeviceBuf<GmPoseInfo> d_info;
+  size_t h_arena_cap = 0, d_arena_cap = 0, h_out_cap = 0, d_out_cap = 0, info_cap = 0;
+  int jobs_scored = 0, launches = 0;
+  long long poses_scored = 0, poses_carried = 0;
+};
+
 }  // namespace slamhip
 
 using namespace slamhip;
@@ -129,6 +141,7 @@ struct slamhip_gmapping {
   // in lock-step and the map updates of all matched particles run as ONE batched K6
   TilePool *tp = nullptr;
   TiledTarget tt{};
+  ParticleScoreStage pscore;  // slamhip_gmapping_particle_score_poses
   bool maps_handled_by_caller = false;  // set by slamhip_gmapping_import_maps around the particle import
   // a step in three phases (slamhip_gmapping_match_begin / _carry_fix / _match_finish): what the first
   // leaves for the others
@@ -931,6 +944,180 @@ int slamhip_gmapping_particle_generate_scans(slamhip_gmapping *g, int variant, i
     if (particles[k] < 0 || particles[k] >= g->count) return bad("particle index out of range");
   return tile_pool_generate_scans(g->tp, variant, flags, n_jobs, particles, poses_xyt, n_angles, angles, max_dist,
                                   occ_threshold, range_out, status_out);
+}
+
+// ---- pose sets over the particles' own maps: one scoring launch, one carry launch (gm_score_batch.hip) ----------------
+static int state_error(const char *msg) {
+  set_error(msg);
+  return SLAMHIP_ERR_STATE;
+}
+
+int slamhip_gmapping_particle_score_poses(slamhip_gmapping *g, const slamhip_spe_cfg *cfg, int n_jobs,
+                                          const slamhip_particle_score_job *jobs, double *scores_out) {
+  if (!g || !cfg) return bad("null argument");
+  if (!g->tp || !g->ctx) return bad("per-particle maps are not enabled");
+  if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return bad("bad job list");
+  if (cfg->oope != SLAMHIP_OOPE_GMAPPING) return bad("per-particle maps are scored by the GMapping OOPE only");
+  if (cfg->gm_window < 0 || cfg->gm_window > 4) return bad("gm_window out of range");
+  if (cfg->sum_order != SLAMHIP_SUM_TREE256)
+    return bad("slamhip_gmapping_particle_score_poses sums in SLAMHIP_SUM_TREE256 order only (the exact modes stay with the "
+               "filter's own path)");
+  if (cfg->pose_trig != SLAMHIP_POSE_TRIG_DEVICE && cfg->pose_trig != SLAMHIP_POSE_TRIG_HOST)
+    return bad("slamhip_gmapping_particle_score_poses takes SLAMHIP_POSE_TRIG_DEVICE or _HOST (the exact modes stay with the "
+               "filter's own path)");
+  slamhip_ctx *ctx = g->ctx;
+  TilePool *tp = g->tp;
+  ParticleScoreStage &s = g->pscore;
+  // ---- everything that can be wrong with the jobs, before anything is staged or queued.  A job without poses is not
+  // looked at any further.
+  std::vector<score_plan::JobShape> shapes((size_t)n_jobs, score_plan::JobShape{0, 0});
+  bool current_scan = false;
+  long long total_ll = 0;
+  for (int k = 0; k < n_jobs; ++k) {
+    const slamhip_particle_score_job &j = jobs[k];
+    if (j.n_poses < 0 || (j.n_poses > 0 && !j.poses_xyt)) return bad("bad pose list in a particle score job");
+    if (j.n_poses == 0) continue;
+    if (!scores_out) return bad("null scores_out");
+    if (j.particle < 0 || j.particle >= g->count) return bad("particle index out of range");
+    int beams = 0;
+    if (j.scan_slot >= 0) {
+      if (j.scan_slot >= 4096) return bad("scan slot out of range (0..4095)");
+      if (j.scan_slot >= (int)ctx->scan_slots.size() || !ctx->scan_slots[(size_t)j.scan_slot].d ||
+          ctx->scan_slots[(size_t)j.scan_slot].n <= 0)
+        return state_error("a particle score job names a scan slot nothing is stored in");
+      beams = ctx->scan_slots[(size_t)j.scan_slot].n;
+    } else if (j.scan_slot != -1) {
+      return bad("a particle score job's scan_slot is 0..4095 or -1");
+    } else if (ctx->scan_n <= 0) {
+      return state_error("no scan uploaded");
+    } else {
+      beams = ctx->scan_n;
+      current_scan = true;
+    }
+    if (beams > 2048) return bad("the GMapping kernel holds at most 2048 filtered beams per scan");
+    shapes[(size_t)k] = score_plan::JobShape{j.n_poses, beams};
+    total_ll += j.n_poses;
+  }
+  if (total_ll > (1ll << 24)) return bad("more than 2^24 poses in one call");
+  // one pose per workgroup: the block table lists every pose of every job, job after job (jobs that name one particle
+  // next to each other stay next to each other)
+  score_plan::Plan plan = score_plan::make_plan(shapes, 1, false, false);
+  if (plan.route != score_plan::kRouteShared) {  // (a lone job: the plan leaves its blocks to the lone call)
+    plan.blocks.clear();
+    for (int k = 0; k < n_jobs; ++k)
+      for (int at = 0; at < shapes[(size_t)k].n_poses; ++at) plan.blocks.push_back(score_plan::Block{k, at});
+  }
+  if (plan.total_poses == 0) {
+    s.jobs_scored = s.launches = 0;
+    s.poses_scored = s.poses_carried = 0;
+    return SLAMHIP_OK;
+  }
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  const hipStream_t st = ctx->stream;
+  const bool host_trig = cfg->pose_trig == SLAMHIP_POSE_TRIG_HOST;
+  const size_t total = (size_t)plan.total_poses;
+  const score_plan::Arena L = score_plan::arena_of(plan, (size_t)n_jobs, sizeof(GmScoreJob), host_trig);
+  const size_t out_bytes = (total * sizeof(double) + (size_t)n_jobs * sizeof(int) + 15) / 16 * 16;
+  int rc = grow_block(st, s.h_arena, s.h_arena_cap, L.bytes, 1 << 16, 1, hipHostMallocDefault);
+  if (!rc) rc = grow_block(st, s.d_arena, s.d_arena_cap, L.bytes, 1 << 16);
+  if (!rc) rc = grow_block(st, s.h_out, s.h_out_cap, out_bytes, 1 << 12, 1, hipHostMallocDefault);
+  if (!rc) rc = grow_block(st, s.d_out, s.d_out_cap, out_bytes, 1 << 12);
+  if (!rc) rc = grow_block(st, s.d_info, s.info_cap, total, 1 << 10);
+  if (rc) return rc;
+  // behind the queued copy-on-write clones and table patches; tables, extent and origin are the pool's own from here on
+  rc = tile_pool_flush(tp);
+  if (rc) return rc;
+  if (current_scan) {  // (a raw scan still staged: its block in HBM is written now, as in front of every scoring launch)
+    rc = scan_assemble_now(ctx);
+    if (rc) return rc;
+  }
+  unsigned char *h = s.h_arena.get();
+  GmScoreJob *views = reinterpret_cast<GmScoreJob *>(h + L.jobs);
+  double *h_poses = reinterpret_cast<double *>(h + L.poses), *h_sc = reinterpret_cast<double *>(h + L.pose_sc);
+  long long units = 0;
+  for (int k = 0; k < n_jobs; ++k) {
+    GmScoreJob &v = views[k];
+    std::memset(&v, 0, sizeof(v));
+    v.at = plan.pose_at[(size_t)k];
+    const slamhip_particle_score_job &j = jobs[k];
+    if (j.n_poses <= 0) continue;
+    if (j.scan_slot >= 0) {
+      const slamhip_ctx::ScanSlot &sl = ctx->scan_slots[(size_t)j.scan_slot];
+      v.scan = scan_view_of(sl.d.get(), (size_t)sl.cap, sl.n, sl.tot_w);
+    } else {
+      v.scan = scan_view_of(ctx->scan_ptr, ctx->scan_stride, ctx->scan_n, ctx->scan_tot_w);
+    }
+    v.n_poses = j.n_poses;
+    v.slot = j.particle;  // (particle i owns slot i of the pool)
+    units += (long long)j.n_poses * v.scan.n;
+    std::memcpy(h_poses + 3 * (size_t)v.at, j.poses_xyt, sizeof(double) * 3 * (size_t)j.n_poses);
+    if (host_trig) {
+      // one sincos call per pose, as the lone call makes them (score_staged)
+      for (int p = 0; p < j.n_poses; ++p)
+        ::sincos(j.poses_xyt[3 * (size_t)p + 2], &h_sc[2 * ((size_t)v.at + p)], &h_sc[2 * ((size_t)v.at + p) + 1]);
+    }
+  }
+  std::memcpy(h + L.pose_at, plan.pose_at.data(), sizeof(long long) * plan.pose_at.size());
+  std::memcpy(h + L.blocks, plan.blocks.data(), sizeof(score_plan::Block) * plan.blocks.size());
+  unsigned char *d = s.d_arena.get();
+  SLAMHIP_CHECK(hipMemcpyAsync(d, h, L.bytes, hipMemcpyHostToDevice, st));
+  GmScoreBatchArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.map.payload = tp->d_pool;
+  a.map.width = tp->width();
+  a.map.height = tp->height();
+  a.map.pitch = tp->tiles_x;
+  a.map.origin_x = tp->origin_x;
+  a.map.origin_y = tp->origin_y;
+  a.map.scale = tp->scale;
+  a.map.inv_scale = 1.0 / tp->scale;
+  for (int k = 0; k < 4; ++k) a.map.unknown[k] = tp->unknown[k];
+  // the tiles' masks as they are, for the threshold they were derived for (bind_tiled_target's condition); never re-derived
+  a.map.nbr_ok = (tp->nbr_ok && cfg->gm_window == 1 && tp->nbr_th == cfg->gm_fullness_th) ? 1 : 0;
+  a.gm.fullness_th = cfg->gm_fullness_th;
+  a.gm.window = cfg->gm_window;
+  a.tables = tp->d_table();
+  a.table_stride = tp->table_stride();
+  a.n_jobs = n_jobs;
+  a.n_blocks = (int)plan.blocks.size();
+  a.jobs = reinterpret_cast<const GmScoreJob *>(d + L.jobs);
+  a.blocks = reinterpret_cast<const score_plan::Block *>(d + L.blocks);
+  a.poses = reinterpret_cast<const double *>(d + L.poses);
+  a.pose_sc = host_trig ? reinterpret_cast<const double *>(d + L.pose_sc) : nullptr;
+  a.scores = reinterpret_cast<double *>(s.d_out.get());
+  a.info = s.d_info.get();
+  a.carried = reinterpret_cast<int *>(s.d_out.get() + total * sizeof(double));
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  rc = profile_event_pair(ctx, &ev[0], &ev[1]);
+  if (!rc) rc = profile_event_pair(ctx, &ev[2], &ev[3]);
+  if (rc) return rc;
+  int launches = 0;
+  SLAMHIP_CHECK(launch_gm_score_batch(a, plan.total_poses, plan.max_beams, st, ev, &launches));
+  SLAMHIP_CHECK(hipMemcpyAsync(s.h_out.get(), s.d_out.get(), out_bytes, hipMemcpyDeviceToHost, st));
+  SLAMHIP_CHECK(hipStreamSynchronize(st));
+  std::memcpy(scores_out, s.h_out.get(), sizeof(double) * total);
+  const int *h_carried = reinterpret_cast<const int *>(s.h_out.get() + total * sizeof(double));
+  long long carried = 0;
+  for (int k = 0; k < n_jobs; ++k) carried += h_carried[k];
+  if (ctx->profile) {
+    ctx->prof_launches += launches;
+    ctx->prof_units += units;
+  }
+  s.jobs_scored = plan.non_empty;
+  s.poses_scored = plan.total_poses;
+  s.launches = launches;
+  s.poses_carried = carried;
+  return SLAMHIP_OK;
+}
+
+int slamhip_gmapping_particle_score_stats(slamhip_gmapping *g, int *jobs_scored, long long *poses_scored, int *launches,
+                                          long long *poses_carried) {
+  if (!g) return bad("null filter");
+  if (jobs_scored) *jobs_scored = g->pscore.jobs_scored;
+  if (poses_scored) *poses_scored = g->pscore.poses_scored;
+  if (launches) *launches = g->pscore.launches;
+  if (poses_carried) *poses_carried = g->pscore.poses_carried;
+  return SLAMHIP_OK;
 }
 
 int slamhip_gmapping_particle_maps_append(slamhip_gmapping *g, int n_jobs, const int *particles,

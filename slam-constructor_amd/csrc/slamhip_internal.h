@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "gm_carry.h"
 #include "scan_filter.h"
 #include "slamhip.h"
 
@@ -146,15 +147,7 @@ struct GmParams {
   int window;
 };
 
-// per-pose side outputs of the GMapping kernel for the host carry-in fix-up
-struct GmPoseInfo {
-  int first_cx, first_cy;  // cell of beam 0
-  int last_cx, last_cy;    // cell of the last beam
-  double v0;               // fresh value of the first run
-  double last_v;           // resolved value of the last run (before any carry-in)
-  int run0_len;            // beams in the first run (they all hold v0)
-  int last_head;           // beam index heading the last run (0 => the last run is run 0)
-};
+// (GmPoseInfo, the per-pose side outputs of the GMapping kernel for the carry-in fix-up: gm_carry.h, included above)
 
 struct ScoreArgs {
   MapView map;

@@ -16,6 +16,8 @@
 //                              (particle_filter.h:114-121).  Map modes: the reference's shared map
 //                              with the update inside the step (default), or per-particle
 //                              copy-on-write maps.
+//   hip_estimate_particle_scan_probabilities  K (particle, filtered scan, pose list) triples over the particles' own
+//                              maps through ONE slamhip_gmapping_particle_score_poses call: K score vectors
 #ifndef SLAMHIP_GMAPPING_ADAPTER_H
 #define SLAMHIP_GMAPPING_ADAPTER_H
 
@@ -257,5 +259,79 @@ private:
   RobotPose _pose{0, 0, 0};
   std::shared_ptr<HipDeviceGridMap> _view;
 };
+
+// ------------------------------------------------------------------------------------------------
+// ScanProbabilityEstimator::estimate_scan_probability of K (particle, filtered scan, pose list) triples over the
+// particles' OWN maps in ONE slamhip_gmapping_particle_score_poses call (GmappingOccupancyObservationPE over even or
+// weighted points, one estimator object per triple: its run cache starts empty and is carried through the triple's
+// poses): the counterpart of hip_estimate_scan_probabilities (slamhip_reference_adapter.h) for the maps that live in the
+// filter's tile pool -- a heat map over the heaviest particle's map, likelihoods of poses sampled around every
+// particle's pose, which particle's map explains a scan.  `particle` is a LOCAL index of `filter`, whose context is
+// `ctx`; the scan of triple k must be the FILTERED one and is stored in scan slot first_slot + k (triples that hand in
+// the same LaserScan2D object share the first one's slot); scores[k][i] is the probability of poses[i].  A scan without
+// points scores NaN at every pose.  The context's current scan and its own cache are left as they were.
+struct HipParticleScoreJob {
+  int particle;
+  const LaserScan2D *scan;  // filtered
+  std::vector<RobotPose> poses;
+};
+
+inline std::vector<std::vector<double>> hip_estimate_particle_scan_probabilities(slamhip_ctx *ctx, slamhip_gmapping *filter,
+                                                                                 slamhip_spe_cfg cfg,
+                                                                                 const std::vector<HipParticleScoreJob> &jobs,
+                                                                                 int weighting = 0, int first_slot = 0) {
+  cfg.oope = SLAMHIP_OOPE_GMAPPING;
+  const int K = int(jobs.size());
+  std::vector<slamhip_particle_score_job> table(K);
+  std::vector<std::vector<double>> xyt(K);
+  size_t total = 0;
+  for (int k = 0; k < K; ++k) {
+    const HipParticleScoreJob &j = jobs[k];
+    const auto &pts = j.scan->points();
+    const int n = int(pts.size());
+    int slot = first_slot + k;
+    bool stored = false;
+    for (int q = 0; q < k && !stored; ++q) {
+      if (jobs[q].scan == j.scan && table[q].n_poses > 0) {
+        slot = table[q].scan_slot;
+        stored = true;
+      }
+    }
+    table[k] = slamhip_particle_score_job{j.particle, slot, 0, nullptr};
+    if (n == 0 || j.poses.empty()) continue;
+    if (!stored) {
+      std::vector<double> r(n), a(n), f(n), w(n), c(n), s(n);
+      for (int i = 0; i < n; ++i) {
+        r[i] = pts[i].range();
+        a[i] = pts[i].angle();
+        f[i] = pts[i].factor();
+      }
+      slamhip_or_die(slamhip_scan_weights(weighting, n, r.data(), a.data(), w.data()), "scan_weights");
+      slamhip_or_die(slamhip_beam_trig_raw(n, a.data(), c.data(), s.data()), "beam_trig_raw");
+      slamhip_or_die(slamhip_scan_store(ctx, slot, n, r.data(), c.data(), s.data(), w.data(), f.data()), "scan_store");
+    }
+    for (const RobotPose &p : j.poses) {
+      xyt[k].push_back(p.x);
+      xyt[k].push_back(p.y);
+      xyt[k].push_back(p.theta);
+    }
+    table[k].n_poses = int(j.poses.size());
+    table[k].poses_xyt = xyt[k].data();
+    total += j.poses.size();
+  }
+  std::vector<double> flat(total);
+  slamhip_or_die(slamhip_gmapping_particle_score_poses(filter, &cfg, K, table.data(), flat.data()), "gmapping_particle_score_poses");
+  std::vector<std::vector<double>> scores(K);
+  size_t at = 0;
+  for (int k = 0; k < K; ++k) {
+    if (table[k].n_poses > 0) {
+      scores[k].assign(flat.begin() + at, flat.begin() + at + table[k].n_poses);
+      at += size_t(table[k].n_poses);
+    } else {
+      scores[k].assign(jobs[k].poses.size(), std::nan(""));  // (a scan without points)
+    }
+  }
+  return scores;
+}
 
 #endif  // SLAMHIP_GMAPPING_ADAPTER_H
