@@ -1049,6 +1049,61 @@ int slamhip_matcher_set_bf_job_streams(slamhip_matcher *m, int n, const int *str
 /* a stream's enumerator: whether its base is latched, the base (zeros while it is not), the matches run on it.  Outputs
  * may be NULL.  stream = -1: the matcher's own enumerator, the one the lone calls use. */
 int slamhip_matcher_bf_stream_info(slamhip_matcher *m, int stream, int *base_set, double base[3], long long *matches);
+/* The peaks of a brute-force sweep's score landscape, picked on the device.  A matcher answers with one pose; in a
+ * corridor or a symmetric room the landscape has a ridge or several maxima and a second pose is as good as the first.
+ * These calls score the lattice a BruteForcePoseEnumerator hands out when `centre` is its latched base -- the matcher's
+ * own offsets, pose bits made by the enumerator's additions, x fastest, then y, then theta; the initial-pose call 0 of a
+ * match is not part of it: lattice index j is call j + 1 of a sweep -- and return its local maxima above two floors, best
+ * first.  The rule, one text for host and device (csrc/bf_peaks.h):
+ *  - key order: a beats b iff score a > score b, or the scores are equal and a < b (the pose handed out first, the
+ *    matcher's own "first pose holding the maximum").  A NaN score is absent: it beats nothing and is never a peak.
+ *  - window of i: |dx| <= radius[0], |dy| <= radius[1], |dtheta| <= radius[2] in lattice steps, clipped at the faces of
+ *    the volume (theta does not wrap); 0 <= radius <= 32.  i is a peak iff its score is not NaN and nothing else in its
+ *    window beats it.  Radius (0, 0, 0): every non-NaN point, i.e. the N best poses.
+ *  - floors: with s_max the largest non-NaN score of the lattice, a peak is kept iff
+ *    score >= min_score && score >= min_ratio * s_max.  An all-NaN lattice has no peaks.
+ *  - result: kept peaks in descending score, ties by ascending index; *n_found = how many were kept, *n_written =
+ *    min(*n_found, max_peaks) entries of peaks_out.  max_peaks = 0 counts only (peaks_out may be NULL).
+ *  - bound: two peaks never lie in each other's window, so at most B = ceil(nx / (rx + 1)) ceil(ny / (ry + 1))
+ *    ceil(nt / (rt + 1)) exist.  B > 8192 is SLAMHIP_ERR_INVALID: widen the radius or narrow the sweep.
+ * Peaks are those of the canonical sums -- bit-equal to slamhip_score_poses on the same poses; the checked default mode's
+ * tie check (slamhip_matcher_set_tie_check) is NOT applied.  The lone call scores the context's current scan; in the
+ * batch, job k's init_pose is its centre and map and scan come per job as in slamhip_matcher_process_scan_batch, job k
+ * equals the lone call on its inputs, K x (1 + nx ny nt) <= 2^24.  The jobs are scored in ONE shared launch where the
+ * batched sweep's scoring kernel covers them (1-cell OOPE, one effective cell model, at most 4096 beams a job), else job
+ * after job; three more launches, whatever n, K and the radius, pick the peaks of all jobs, and only the counts and the
+ * written peaks cross the bus.
+ *  - State: the enumerator and its latch, the enumerator streams, the observer and every counter of
+ *    slamhip_matcher_stats are neither read nor written; the context's current scan stays what it was.  For the
+ *    landscape of the next process_scan pass the base slamhip_matcher_bf_stream_info(m, -1, ...) reports, or the initial
+ *    pose while none is latched.
+ *  - Covered: point and window OOPEs, OCC / TBM / CREDIBILIST maps (through the probability plane where the sweep goes
+ *    through it), SLAMHIP_SUM_TREE256, device pose trigonometry, at most 2^26 poses.  The GMapping OOPE, the beam-order
+ *    sum and host or RAW_EXACT pose trigonometry: SLAMHIP_ERR_UNSUPPORTED.
+ *  - SLAMHIP_ERR_INVALID: a matcher that is not brute force, a radius outside 0 ... 32, B > 8192, max_peaks outside
+ *    0 ... 8192, min_ratio outside [0, 1], a NaN min_score, null arguments (shape_out may be NULL), a batch beyond 2^24
+ *    poses.  Every refusal comes before anything is launched.
+ * shape_out: (nx, ny, nt).  index: ix + nx (iy + ny it). */
+typedef struct {
+  double pose[3];
+  double score;
+  long long index;
+} slamhip_bf_peak;
+int slamhip_matcher_bf_peaks(slamhip_matcher *m, int map_id, const double centre[3], const int radius[3], double min_ratio,
+                             double min_score, int max_peaks, slamhip_bf_peak *peaks_out, int *n_written, long long *n_found,
+                             int shape_out[3]);
+int slamhip_matcher_bf_peaks_batch(slamhip_matcher *m, int n_jobs, const slamhip_match_job *jobs, const int radius[3],
+                                   double min_ratio, double min_score, int max_peaks,
+                                   slamhip_bf_peak *peaks_out /* n_jobs x max_peaks */, int *n_written /* n_jobs */,
+                                   long long *n_found /* n_jobs */);
+/* the last peaks call that got as far as launching: the kernels it launched, counted where they are launched (pose and
+ * scoring kernels included; not among them: the one-off derivation of a TBM / CREDIBILIST map's probability plane, which
+ * the first scoring call of any kind over such a map makes), its bound B, and whether its jobs were scored in the shared
+ * launch.  A refused call leaves all three as they were.  Zeros before the first. */
+int slamhip_matcher_bf_peaks_stats(slamhip_matcher *m, long long *launches, long long *survivors_bound, int *on_shared_launch);
+/* the rule on the host, no GPU: the peaks of scores[ix + nx (iy + ny it)]; index_out / score_out: max_peaks entries */
+int slamhip_bf_peaks_host(const double *scores, int nx, int ny, int nt, const int radius[3], double min_ratio, double min_score,
+                          int max_peaks, long long *index_out, double *score_out, int *n_written, long long *n_found);
 /* counters of the last process_scan: scorer calls the reference would have made
  * (= on_scan_test events), poses actually evaluated on the GPU, launches */
 int slamhip_matcher_stats(slamhip_matcher *m, long long *scorer_calls, long long *poses_evaluated,

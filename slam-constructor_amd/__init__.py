@@ -79,7 +79,8 @@ slamhip_gmapping_particle_generate_scans slamhip_scan_generate_host_tiled
 slamhip_pyramid_refresh_batch slamhip_pyramid_refresh_batch_stats
 slamhip_matcher_m3rsm_match_each_raw slamhip_matcher_m3rsm_each_scan_download
 slamhip_score_poses_batch slamhip_score_poses_batch_stats
-slamhip_gmapping_particle_score_poses slamhip_gmapping_particle_score_stats""".split()
+slamhip_gmapping_particle_score_poses slamhip_gmapping_particle_score_stats
+slamhip_matcher_bf_peaks slamhip_matcher_bf_peaks_batch slamhip_matcher_bf_peaks_stats slamhip_bf_peaks_host""".split()
 
 SHARD_ID_BYTES = 128
 
@@ -115,6 +116,11 @@ class MatchJob(C.Structure):
     """slamhip_match_job: one match of slamhip_matcher_process_scan_batch."""
     _fields_ = [("map_id", C.c_int), ("scan_slot", C.c_int), ("n", C.c_int), ("range", _dp), ("cos_a", _dp), ("sin_a", _dp),
                 ("weight", _dp), ("factor", _dp), ("init_pose", C.c_double * 3)]
+
+
+class BfPeak(C.Structure):
+    """slamhip_bf_peak: one local maximum of a sweep's score landscape."""
+    _fields_ = [("pose", C.c_double * 3), ("score", C.c_double), ("index", C.c_longlong)]
 
 
 class CarryRecord(C.Structure):
@@ -349,8 +355,28 @@ def load(testing=False):
     L.slamhip_matcher_set_bf_streams.argtypes = [vp, i]
     L.slamhip_matcher_set_bf_job_streams.argtypes = [vp, i, _ip]
     L.slamhip_matcher_bf_stream_info.argtypes = [vp, i, _ip, _dp, ll]
+    pk = C.POINTER(BfPeak)
+    L.slamhip_matcher_bf_peaks.argtypes = [vp, i, _dp, _ip, d, d, i, pk, _ip, ll, _ip]
+    L.slamhip_matcher_bf_peaks_batch.argtypes = [vp, i, C.POINTER(MatchJob), _ip, d, d, i, pk, _ip, ll]
+    L.slamhip_matcher_bf_peaks_stats.argtypes = [vp, ll, ll, _ip]
+    L.slamhip_bf_peaks_host.argtypes = [_dp, i, i, i, _ip, d, d, i, ll, _dp, _ip, ll]
     _libs[testing] = L
     return L
+
+
+def bf_peaks_host(scores, shape, radius=(1, 1, 1), min_ratio=0.0, min_score=0.0, max_peaks=16):
+    """The peaks rule on the host (slamhip_bf_peaks_host, no GPU) over scores[ix + nx (iy + ny it)], shape = (nx, ny, nt):
+    dict(index, scores, n_found) -- kept local maxima in descending score, ties by ascending index, the first max_peaks."""
+    sc = _f64(scores).ravel()
+    nx, ny, nt = [int(v) for v in shape]
+    if sc.size != nx * ny * nt:
+        raise ValueError("scores do not fill the shape")
+    rad = (C.c_int * 3)(*[int(v) for v in radius])
+    idx, out = np.zeros(max(1, int(max_peaks)), np.int64), np.zeros(max(1, int(max_peaks)))
+    nw, nf = C.c_int(), C.c_longlong()
+    _check(load().slamhip_bf_peaks_host(_d(sc), nx, ny, nt, rad, float(min_ratio), float(min_score), int(max_peaks),
+                                        idx.ctypes.data_as(C.POINTER(C.c_longlong)), _d(out), C.byref(nw), C.byref(nf)))
+    return dict(index=idx[:nw.value].copy(), scores=out[:nw.value].copy(), n_found=nf.value)
 
 
 def omqe_quality(kind, rng, ang):
@@ -1341,6 +1367,48 @@ class Matcher:
         bs, base, matches = C.c_int(), (C.c_double * 3)(), C.c_longlong()
         _check(self.L.slamhip_matcher_bf_stream_info(self.h, int(stream), C.byref(bs), base, C.byref(matches)))
         return dict(base_set=bool(bs.value), base=np.array(list(base)), matches=matches.value)
+
+    @staticmethod
+    def _peaks_arrays(buf, n_written):
+        rec = np.frombuffer(buf, dtype=np.dtype([("pose", np.float64, 3), ("score", np.float64), ("index", np.int64)]))
+        rec = rec[:n_written]
+        return rec["pose"].copy().reshape(-1, 3), rec["score"].copy(), rec["index"].copy()
+
+    def bf_peaks(self, map_id, centre, radius=(1, 1, 1), min_ratio=0.0, min_score=0.0, max_peaks=16):
+        """The local maxima of the sweep's score landscape around `centre` over the context's current scan
+        (slamhip_matcher_bf_peaks): dict(poses, scores, index, n_found, shape) -- kept peaks in descending score, ties by
+        ascending lattice index, the first max_peaks.  The matcher's own state is not touched."""
+        c3 = (C.c_double * 3)(*[float(v) for v in centre])
+        rad = (C.c_int * 3)(*[int(v) for v in radius])
+        buf = (BfPeak * max(1, int(max_peaks)))()
+        nw, nf, shape = C.c_int(), C.c_longlong(), (C.c_int * 3)()
+        _check(self.L.slamhip_matcher_bf_peaks(self.h, int(map_id), c3, rad, float(min_ratio), float(min_score), int(max_peaks),
+                                               buf if max_peaks > 0 else None, C.byref(nw), C.byref(nf), shape))
+        poses, scores, index = self._peaks_arrays(buf, nw.value)
+        return dict(poses=poses, scores=scores, index=index, n_found=nf.value, shape=tuple(shape))
+
+    def bf_peaks_batch(self, jobs, radius=(1, 1, 1), min_ratio=0.0, min_score=0.0, max_peaks=16):
+        """K robots' peaks in one call (slamhip_matcher_bf_peaks_batch).  jobs as for process_scan_batch, a job's
+        init_pose being its centre.  Returns a list of dicts like bf_peaks', one per job."""
+        blk = jobs if isinstance(jobs, dict) and "arr" in jobs else self.make_batch(jobs)
+        k, mp = blk["n"], int(max_peaks)
+        rad = (C.c_int * 3)(*[int(v) for v in radius])
+        buf = (BfPeak * max(1, k * mp))()
+        nw, nf = (C.c_int * max(1, k))(), (C.c_longlong * max(1, k))()
+        _check(self.L.slamhip_matcher_bf_peaks_batch(self.h, k, blk["arr"], rad, float(min_ratio), float(min_score), mp,
+                                                     buf if mp > 0 else None, nw, nf))
+        out = []
+        for c in range(k):
+            sl = (BfPeak * max(1, mp)).from_buffer(buf, C.sizeof(BfPeak) * c * mp) if mp > 0 else buf
+            poses, scores, index = self._peaks_arrays(sl, nw[c])
+            out.append(dict(poses=poses, scores=scores, index=index, n_found=nf[c]))
+        return out
+
+    def bf_peaks_stats(self):
+        """The last peaks call that went through: launches (scoring included), the survivor bound B, shared launch?"""
+        a, b, c = C.c_longlong(), C.c_longlong(), C.c_int()
+        _check(self.L.slamhip_matcher_bf_peaks_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(launches=a.value, survivors_bound=b.value, on_shared_launch=bool(c.value))
 
     def chain_stats(self):
         kl, rs = C.c_longlong(), C.c_longlong()

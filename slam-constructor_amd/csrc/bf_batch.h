@@ -47,5 +47,7 @@ constexpr long long kBfBatchMaxPoses = 1ll << 24;
 // score, scan, decide: three launches on `stream`.  cell_model: the effective model of every job's view; max_beams: the
 // most beams of a job.
 hipError_t launch_bf_batch(const BfBatchArgs &a, int cell_model, int max_beams, hipStream_t stream);
+// the first of the three alone (slamhip_matcher_bf_peaks_batch: its own kernels read the scores); verify 0, a.n >= 2
+hipError_t launch_bf_batch_score(const BfBatchArgs &a, int cell_model, int max_beams, hipStream_t stream);
 
 }  // namespace slamhip

@@ -87,14 +87,19 @@ static BfScoreKernel bf_score_kernel(int kb) {
   }
 }
 
-hipError_t launch_bf_batch(const BfBatchArgs &args, int cell_model, int max_beams, hipStream_t stream) {
+// what every launch of a call checks first, in this order, and the arguments as launched (poses_per_block picked)
+static hipError_t bf_batch_checked(const BfBatchArgs &args, int max_beams, BfBatchArgs *out) {
   BfBatchArgs a = args;
   if (a.n_jobs <= 0 || a.n_jobs > 65535 || a.n < 2 || max_beams <= 0) return hipErrorInvalidValue;
   if ((long long)a.n_jobs * a.n > kBfBatchMaxPoses) return refuse_launch("the batch's sweeps outgrow the scratch budget");
-  const unsigned blocks = (unsigned)((a.n - 1 + kBfBlock - 1) / kBfBlock);
-  if (blocks == 0 || blocks > (unsigned)kBfMaxBlocks) return hipErrorInvalidValue;
   if (a.poses_per_block <= 0) a.poses_per_block = pick_poses_per_block((long long)a.n_jobs * a.n);
   if (a.poses_per_block > kScoreMaxPosesPerBlock) a.poses_per_block = kScoreMaxPosesPerBlock;
+  *out = a;
+  return hipSuccess;
+}
+
+// the scoring launch of checked arguments
+static hipError_t bf_batch_score(const BfBatchArgs &a, int cell_model, int max_beams, hipStream_t stream) {
   const int kb = (max_beams + kScoreBlock - 1) / kScoreBlock;
   const bool fp = a.verify != 0;
   const BfScoreKernel score = pick_cell_model(cell_model, [&](auto m) -> BfScoreKernel {
@@ -102,7 +107,23 @@ hipError_t launch_bf_batch(const BfBatchArgs &args, int cell_model, int max_beam
     return fp ? bf_score_kernel<M, true>(kb) : bf_score_kernel<M, false>(kb);
   });
   const dim3 grid_score((unsigned)((a.n + a.poses_per_block - 1) / a.poses_per_block), (unsigned)a.n_jobs);
-  hipError_t e = launch_kernel(score, grid_score, dim3(kScoreBlock), 0, stream, nullptr, nullptr, a, a.jobs);
+  return launch_kernel(score, grid_score, dim3(kScoreBlock), 0, stream, nullptr, nullptr, a, a.jobs);
+}
+
+hipError_t launch_bf_batch_score(const BfBatchArgs &args, int cell_model, int max_beams, hipStream_t stream) {
+  BfBatchArgs a;
+  const hipError_t e = bf_batch_checked(args, max_beams, &a);
+  if (e != hipSuccess) return e;
+  return bf_batch_score(a, cell_model, max_beams, stream);
+}
+
+hipError_t launch_bf_batch(const BfBatchArgs &args, int cell_model, int max_beams, hipStream_t stream) {
+  BfBatchArgs a;
+  hipError_t e = bf_batch_checked(args, max_beams, &a);
+  if (e != hipSuccess) return e;
+  const unsigned blocks = (unsigned)((a.n - 1 + kBfBlock - 1) / kBfBlock);
+  if (blocks == 0 || blocks > (unsigned)kBfMaxBlocks) return hipErrorInvalidValue;
+  e = bf_batch_score(a, cell_model, max_beams, stream);
   if (e != hipSuccess) return e;
   e = launch_kernel(k_bf_scan_batch, dim3(blocks, (unsigned)a.n_jobs), dim3(kBfBlock), 0, stream, nullptr, nullptr, a, a.jobs);
   if (e != hipSuccess) return e;

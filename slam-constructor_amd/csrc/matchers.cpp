@@ -9,6 +9,7 @@
 #include "bf_batch.h"
 #include "bf_batch_plan.h"
 #include "bf_device.h"
+#include "bf_peaks_device.h"
 #include "hc_chain_device.h"
 #include "hc_shape.h"
 #include "m3rsm_each.h"
@@ -146,6 +147,29 @@ struct BfBatch {
   std::vector<double> scores_host;  // the last call's K x n scores (observer attached only)
 };
 
+// The peaks of K score landscapes (bf_peaks_run): the volumes (job j's np = 1 + nx ny nt scores, the volume behind its
+// first), the poses of a lone call, the staged job table of the shared scoring launch, the peaks kernels' scratch and the
+// pinned block their results arrive in.  The matcher's sweeps and their counters never see any of it.
+struct BfPeaksScratch {
+  long long pose_cap = 0, lone_cap = 0, surv_cap = 0, out_cap = 0;
+  int job_cap = 0;
+  slamhip::DeviceBuf<double> d_scores, d_poses, d_plane_s;
+  slamhip::DeviceBuf<int> d_plane_i;
+  slamhip::PinnedBuf<slamhip::BfJobView> h_jobs;
+  slamhip::DeviceBuf<slamhip::BfJobView> d_jobs;
+  slamhip::DeviceBuf<unsigned long long> d_job_max;
+  slamhip::DeviceBuf<unsigned> d_job_count;
+  slamhip::DeviceBuf<slamhip::BfPeakKey> d_surv;
+  slamhip::PinnedBuf<slamhip::BfPeaksHostOut> h_hdr;
+  slamhip::PinnedBuf<slamhip::BfPeakKey> h_out;
+  // the two scratch words of a job are zero between calls because k_bf_peaks_order clears them; a call whose launches
+  // went out and whose wait did not come back leaves them unknown: the next call clears them first
+  bool words_unknown = false;
+  // slamhip_matcher_bf_peaks_stats: the last call that launched anything -- kernels counted where they are launched
+  long long launches = 0, bound = 0;
+  int shared = 0;
+};
+
 struct slamhip_matcher {
   // ---- what every kind of matcher has
   slamhip_ctx *ctx = nullptr;
@@ -254,6 +278,7 @@ struct slamhip_matcher {
   slamhip::BfStreams bf_streams;
   long long bf_matches = 0;  // matches run on the matcher's own enumerator
   std::unique_ptr<BfBatch> bf_batch;
+  std::unique_ptr<BfPeaksScratch> bf_peaks;  // slamhip_matcher_bf_peaks / _batch
   // ---- the multi-resolution matcher (BF_M3RSM): the best-first engine of m3rsm_engine.h over a pyramid's expand launches
   struct M3rsm {
     slamhip_pyramid *pyr = nullptr;  // the caller's; must outlive the matcher's matches
@@ -2962,7 +2987,7 @@ int slamhip_matcher_create_bf(slamhip_ctx *ctx, const slamhip_spe_cfg *cfg, cons
 
 int slamhip_matcher_destroy(slamhip_matcher *m) {
   if (m) {
-    if (m->hc.d_chain || m->batch || m->bf.d_poses || m->bf_batch) {
+    if (m->hc.d_chain || m->batch || m->bf.d_poses || m->bf_batch || m->bf_peaks) {
       // run-ahead kernels of the last chain may still read the blocks; the context may already be gone
       // (destroying it synchronised its stream), so wait on the device, not on the context's stream
       hipSetDevice(m->device);
@@ -3222,6 +3247,325 @@ int slamhip_matcher_bf_stream_info(slamhip_matcher *m, int stream, int *base_set
   if (base)
     for (int q = 0; q < 3; ++q) base[q] = k.base_set ? k.base[q] : 0.0;
   if (matches) *matches = k.matches;
+  return SLAMHIP_OK;
+}
+
+// ---- the peaks of a sweep's score landscape (bf_peaks.h, bf_peaks.hip) ---------------------------------------------
+// The lattice a BruteForcePoseEnumerator with base `centre` hands out, scored as the sweep scores it, and reduced on the
+// device to its local maxima above the floors, best first.  Nothing of the matcher's own state takes part: not the
+// enumerator or its latch, not the enumerator streams, the observer or a counter of slamhip_matcher_stats.
+namespace {
+
+int unsupported(const char *msg) {
+  set_error(msg);
+  return SLAMHIP_ERR_UNSUPPORTED;
+}
+
+// the rule's own arguments (both the host entry and the device calls)
+int bf_peaks_rule_args(const int radius[3], double min_ratio, double min_score, int max_peaks) {
+  for (int k = 0; k < 3; ++k)
+    if (radius[k] < 0 || radius[k] > kBfPeaksMaxRadius) return invalid_arg("a peak window's radius lies in 0 ... 32 on every axis");
+  if (max_peaks < 0 || max_peaks > kBfPeaksMaxSurvivors) return invalid_arg("max_peaks lies in 0 ... 8192");
+  if (!(min_ratio >= 0.0 && min_ratio <= 1.0)) return invalid_arg("min_ratio lies in [0, 1]");
+  if (min_score != min_score) return invalid_arg("min_score is NaN");
+  return SLAMHIP_OK;
+}
+
+// everything a peaks call is refused for before the device is asked for anything but the matcher's offsets; *bound: B
+int bf_peaks_check(slamhip_matcher *m, const int radius[3], double min_ratio, double min_score, int max_peaks, long long *bound) {
+  if (!m->is_bf) return invalid_arg("the peaks of a sweep belong to a brute-force matcher");
+  int rc = bf_peaks_rule_args(radius, min_ratio, min_score, max_peaks);
+  if (rc) return rc;
+  if (m->cfg.oope == SLAMHIP_OOPE_GMAPPING) return unsupported("the peaks of a sweep: the GMapping OOPE is not covered");
+  if (m->cfg.sum_order != SLAMHIP_SUM_TREE256) return unsupported("the peaks of a sweep: the beam-order sum is not covered");
+  if (m->cfg.pose_trig != SLAMHIP_POSE_TRIG_DEVICE) return unsupported("the peaks of a sweep: device pose trigonometry only");
+  rc = bf_sweep_offsets(m);
+  if (rc == kChainNeedsHost) return unsupported("the peaks of a sweep: an axis of the sweep is too long");
+  if (rc) return rc;
+  const slamhip_matcher::BfSweep &bf = m->bf;
+  if (bf.nx <= 0 || bf.ny <= 0 || bf.nt <= 0) return invalid_arg("the sweep is empty");
+  if (1 + (long long)bf.nx * bf.ny * bf.nt > (1ll << 26)) return unsupported("the peaks of a sweep: more than 2^26 poses");
+  *bound = bf_peaks_bound(bf.nx, bf.ny, bf.nt, radius);
+  if (*bound > kBfPeaksMaxSurvivors)
+    return invalid_arg("more than 8192 peaks are possible: widen the radius or narrow the sweep");
+  return SLAMHIP_OK;
+}
+
+// the scratch of n_jobs volumes of np scores each (lone_poses: a pose array for launch_score as well)
+int bf_peaks_room(slamhip_matcher *m, int n_jobs, long long np, long long bound, int max_peaks, bool lone_poses) {
+  hipStream_t st = m->ctx->stream;
+  if (!m->bf_peaks) m->bf_peaks = std::make_unique<BfPeaksScratch>();
+  BfPeaksScratch *s = m->bf_peaks.get();
+  int rc = grow_blocks({st}, s->job_cap, (size_t)n_jobs, 8, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(s->h_jobs.alloc(cap, hipHostMallocDefault));
+    SLAMHIP_CHECK(s->d_jobs.alloc(cap));
+    SLAMHIP_CHECK(s->d_job_max.alloc(cap));
+    SLAMHIP_CHECK(s->d_job_count.alloc(cap));
+    // (zero between calls: k_bf_peaks_order clears what its call used)
+    SLAMHIP_CHECK(hipMemsetAsync(s->d_job_max.get(), 0, sizeof(unsigned long long) * cap, st));
+    SLAMHIP_CHECK(hipMemsetAsync(s->d_job_count.get(), 0, sizeof(unsigned) * cap, st));
+    SLAMHIP_CHECK(s->h_hdr.alloc(cap, kPinnedCoherent));
+    return SLAMHIP_OK;
+  });
+  if (!rc) rc = grow_blocks({st}, s->pose_cap, (size_t)(n_jobs * np), 1 << 14, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(s->d_scores.alloc(cap));
+    SLAMHIP_CHECK(s->d_plane_s.alloc(cap));
+    SLAMHIP_CHECK(s->d_plane_i.alloc(cap));
+    return SLAMHIP_OK;
+  });
+  if (!rc) rc = grow_blocks({st}, s->surv_cap, (size_t)(n_jobs * bound), 1 << 10, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(s->d_surv.alloc(cap));
+    return SLAMHIP_OK;
+  });
+  if (!rc) rc = grow_blocks({st}, s->out_cap, (size_t)n_jobs * (size_t)std::max(max_peaks, 1), 1 << 8, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(s->h_out.alloc(cap, kPinnedCoherent));
+    return SLAMHIP_OK;
+  });
+  if (!rc && lone_poses) rc = grow_blocks({st}, s->lone_cap, (size_t)np, 1 << 14, [&](size_t cap) -> int {
+    SLAMHIP_CHECK(s->d_poses.alloc(3 * cap));
+    return SLAMHIP_OK;
+  });
+  return rc;
+}
+
+// Behind the last refusal of a call and in front of its first launch: the stats become this call's, and scratch words a
+// failed call left behind are cleared.
+int bf_peaks_begin(slamhip_matcher *m, long long bound, bool shared) {
+  BfPeaksScratch *s = m->bf_peaks.get();
+  if (s->words_unknown) {
+    SLAMHIP_CHECK(hipMemsetAsync(s->d_job_max.get(), 0, sizeof(unsigned long long) * (size_t)s->job_cap, m->ctx->stream));
+    SLAMHIP_CHECK(hipMemsetAsync(s->d_job_count.get(), 0, sizeof(unsigned) * (size_t)s->job_cap, m->ctx->stream));
+    s->words_unknown = false;
+  }
+  s->launches = 0;
+  s->bound = bound;
+  s->shared = shared ? 1 : 0;
+  return SLAMHIP_OK;
+}
+
+// one job's np poses -- the centre, then the lattice around it, by the sweep's own kernel -- scored through launch_score
+// into its slab, as bf_device_process_scan scores a sweep
+int bf_peaks_score_job(slamhip_matcher *m, ScoreArgs a, int cell_model, int oie_eff, const double centre[3], long long np,
+                       double *slab) {
+  BfPeaksScratch *s = m->bf_peaks.get();
+  BfPoseArgs pa;
+  for (int k = 0; k < 3; ++k) pa.init[k] = pa.base[k] = centre[k];
+  pa.off = m->bf.d_off.get();
+  pa.nx = m->bf.nx;
+  pa.ny = m->bf.ny;
+  pa.nt = m->bf.nt;
+  pa.n = np;
+  pa.poses = s->d_poses.get();
+  SLAMHIP_CHECK(launch_bf_poses(pa, m->ctx->stream));
+  ++s->launches;
+  a.poses = s->d_poses.get();
+  a.pose_sc = nullptr;
+  a.scores = slab;
+  a.n_poses = (int)np;
+  a.poses_per_block = 0;
+  a.oie = oie_eff;
+  for (int k = 0; k < 4; ++k) a.area[k] = m->cfg.area[k];
+  a.gm.fullness_th = m->cfg.gm_fullness_th;
+  a.gm.window = m->cfg.gm_window;
+  a.fprints = nullptr;
+  SLAMHIP_CHECK(launch_score(a, cell_model, m->cfg.oope, m->cfg.sum_order, m->ctx->stream));
+  ++s->launches;
+  return SLAMHIP_OK;
+}
+
+// the peaks kernels over the n_jobs volumes that lie scored in the scratch, the wait, and the hand-over: per job its
+// counts and its first max_peaks peaks, their poses made by the enumerator's additions around the job's centre
+int bf_peaks_reduce(slamhip_matcher *m, int n_jobs, long long np, long long bound, const int radius[3], double min_ratio,
+                    double min_score, int max_peaks, const double *centres, slamhip_bf_peak *peaks_out, int *n_written,
+                    long long *n_found) {
+  BfPeaksScratch *s = m->bf_peaks.get();
+  const slamhip_matcher::BfSweep &bf = m->bf;
+  BfPeaksArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.volumes = s->d_scores.get() + 1;  // (score 0 of a slab is the centre's own: not part of the lattice)
+  a.job_stride = np;
+  a.nx = bf.nx;
+  a.ny = bf.ny;
+  a.nt = bf.nt;
+  a.rx = radius[0];
+  a.ry = radius[1];
+  a.rt = radius[2];
+  a.n_jobs = n_jobs;
+  a.max_peaks = max_peaks;
+  a.min_ratio = min_ratio;
+  a.min_score = min_score;
+  a.bound = bound;
+  a.plane_s = s->d_plane_s.get();
+  a.plane_i = s->d_plane_i.get();
+  a.job_max = s->d_job_max.get();
+  a.job_count = s->d_job_count.get();
+  a.survivors = s->d_surv.get();
+  a.out_hdr = s->h_hdr.get();
+  a.out = s->h_out.get();
+  s->words_unknown = true;
+  SLAMHIP_CHECK(launch_bf_peaks(a, m->ctx->stream, &s->launches));
+  SLAMHIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  s->words_unknown = false;
+  for (int c = 0; c < n_jobs; ++c) {
+    const BfPeaksHostOut &h = s->h_hdr.get()[c];
+    n_found[c] = h.n_found;
+    n_written[c] = (int)h.n_written;
+    for (long long q = 0; q < h.n_written; ++q) {
+      const BfPeakKey &k = s->h_out.get()[(size_t)c * (size_t)max_peaks + (size_t)q];
+      slamhip_bf_peak &p = peaks_out[(size_t)c * (size_t)max_peaks + (size_t)q];
+      bf_pose_of_host(bf, centres + 3 * c, centres + 3 * c, k.index + 1, p.pose);
+      p.score = k.score;
+      p.index = k.index;
+    }
+  }
+  return SLAMHIP_OK;
+}
+
+}  // namespace
+
+int slamhip_bf_peaks_host(const double *scores, int nx, int ny, int nt, const int radius[3], double min_ratio, double min_score,
+                          int max_peaks, long long *index_out, double *score_out, int *n_written, long long *n_found) {
+  if (!scores || !radius || !n_written || !n_found || (max_peaks > 0 && (!index_out || !score_out))) return invalid_arg("null argument");
+  if (nx <= 0 || ny <= 0 || nt <= 0 || (long long)nx * ny * nt > (1ll << 26)) return invalid_arg("bad volume shape");
+  const int rc = bf_peaks_rule_args(radius, min_ratio, min_score, max_peaks);
+  if (rc) return rc;
+  if (bf_peaks_bound(nx, ny, nt, radius) > kBfPeaksMaxSurvivors)
+    return invalid_arg("more than 8192 peaks are possible: widen the radius or narrow the sweep");
+  std::vector<BfPeakKey> kept;
+  bf_peaks_separable(scores, nx, ny, nt, radius, min_ratio, min_score, &kept);
+  *n_found = (long long)kept.size();
+  *n_written = (int)std::min<size_t>(kept.size(), (size_t)max_peaks);
+  for (int q = 0; q < *n_written; ++q) {
+    index_out[q] = kept[(size_t)q].index;
+    score_out[q] = kept[(size_t)q].score;
+  }
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_bf_peaks(slamhip_matcher *m, int map_id, const double centre[3], const int radius[3], double min_ratio,
+                             double min_score, int max_peaks, slamhip_bf_peak *peaks_out, int *n_written, long long *n_found,
+                             int shape_out[3]) {
+  if (!m || !centre || !radius || !n_written || !n_found || (max_peaks > 0 && !peaks_out)) return invalid_arg("null argument");
+  slamhip_ctx *ctx = m->ctx;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  long long bound = 0;
+  int rc = bf_peaks_check(m, radius, min_ratio, min_score, max_peaks, &bound);
+  if (rc) return rc;
+  const long long np = 1 + (long long)m->bf.nx * m->bf.ny * m->bf.nt;
+  ScoreArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int cell_model = 0, oie_eff = m->cfg.oie;
+  rc = score_views(ctx, map_id, &m->cfg, &a.map, &a.scan, &cell_model, nullptr, &oie_eff);  // (TBM: through the plane)
+  if (rc) return rc;
+  rc = bf_peaks_room(m, 1, np, bound, max_peaks, true);
+  if (!rc) rc = bf_peaks_begin(m, bound, false);
+  if (rc) return rc;
+  rc = bf_peaks_score_job(m, a, cell_model, oie_eff, centre, np, m->bf_peaks->d_scores.get());
+  if (rc) return rc;
+  rc = bf_peaks_reduce(m, 1, np, bound, radius, min_ratio, min_score, max_peaks, centre, peaks_out, n_written, n_found);
+  if (rc) return rc;
+  if (shape_out) {
+    shape_out[0] = m->bf.nx;
+    shape_out[1] = m->bf.ny;
+    shape_out[2] = m->bf.nt;
+  }
+  return SLAMHIP_OK;
+}
+
+int slamhip_matcher_bf_peaks_batch(slamhip_matcher *m, int n_jobs, const slamhip_match_job *jobs, const int radius[3],
+                                   double min_ratio, double min_score, int max_peaks, slamhip_bf_peak *peaks_out, int *n_written,
+                                   long long *n_found) {
+  if (!m || n_jobs < 0 || !radius || (n_jobs > 0 && (!jobs || !n_written || !n_found || (max_peaks > 0 && !peaks_out))))
+    return invalid_arg("null argument");
+  if (n_jobs > 65535) return invalid_arg("more than 65535 jobs");
+  slamhip_ctx *ctx = m->ctx;
+  SLAMHIP_CHECK(hipSetDevice(ctx->device));
+  long long bound = 0;
+  int rc = bf_peaks_check(m, radius, min_ratio, min_score, max_peaks, &bound);
+  if (rc) return rc;
+  if (n_jobs == 0) return SLAMHIP_OK;
+  const long long np = 1 + (long long)m->bf.nx * m->bf.ny * m->bf.nt;
+  if ((long long)n_jobs * np > kBfBatchMaxPoses) return invalid_arg("the batch's sweeps hold more than 2^24 poses");
+  int max_n = 0;
+  for (int c = 0; c < n_jobs; ++c) {
+    const slamhip_match_job &j = jobs[c];
+    if (j.scan_slot >= 0) {
+      if (j.scan_slot >= (int)ctx->scan_slots.size() || !ctx->scan_slots[j.scan_slot].d)
+        return invalid_arg("a match job names a scan slot nothing is stored in");
+    } else if (j.n <= 0 || !j.range || !j.cos_a || !j.sin_a || !j.weight) {
+      return invalid_arg("bad scan in a match job");
+    }
+    max_n = std::max(max_n, j.scan_slot >= 0 ? ctx->scan_slots[j.scan_slot].n : j.n);
+  }
+  rc = batch_maps_check(ctx, n_jobs, jobs, nullptr);
+  if (rc) return rc;
+  // the views a lone call of each job scores through; ONE launch scores all jobs where k_bf_score_batch covers them: the
+  // 1-cell OOPE, one effective cell model and OIE, at most 4096 beams a job
+  std::vector<MapView> maps(n_jobs);
+  std::vector<int> models(n_jobs), oies(n_jobs);
+  std::vector<double> centres(3 * (size_t)n_jobs);
+  bool shared = m->cfg.oope == SLAMHIP_OOPE_OBSTACLE && max_n <= kBfBatchMaxBeams;
+  for (int c = 0; c < n_jobs; ++c) {
+    rc = score_map_view(ctx, jobs[c].map_id, &m->cfg, &maps[c], &models[c], &oies[c]);
+    if (rc) return rc;
+    if (models[c] != models[0] || oies[c] != oies[0]) shared = false;
+    for (int q = 0; q < 3; ++q) centres[3 * (size_t)c + q] = jobs[c].init_pose[q];
+  }
+  rc = bf_peaks_room(m, n_jobs, np, bound, max_peaks, !shared);
+  if (rc) return rc;
+  if (!m->batch) m->batch = std::make_unique<HcBatch>();  // (its scan arena: hc_batch_stage_scans)
+  std::vector<BatchScanBlock> blocks(n_jobs);
+  rc = hc_batch_stage_scans(m, n_jobs, jobs, blocks.data());
+  if (rc) return rc;
+  BfPeaksScratch *s = m->bf_peaks.get();
+  rc = bf_peaks_begin(m, bound, shared);
+  if (rc) return rc;
+  if (shared) {
+    for (int c = 0; c < n_jobs; ++c) {
+      BfJobView &v = s->h_jobs.get()[c];
+      std::memset(&v, 0, sizeof(v));
+      v.map = maps[c];
+      v.scan = scan_view_of(blocks[c].d, blocks[c].stride, blocks[c].n, blocks[c].tot_w);
+      for (int q = 0; q < 3; ++q) v.init[q] = v.base[q] = centres[3 * (size_t)c + q];
+      v.at = (long long)c * np;
+    }
+    SLAMHIP_CHECK(hipMemcpyAsync(s->d_jobs.get(), s->h_jobs.get(), sizeof(BfJobView) * (size_t)n_jobs, hipMemcpyHostToDevice,
+                                 ctx->stream));
+    BfBatchArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.jobs = s->d_jobs.get();
+    a.off = m->bf.d_off.get();
+    a.nx = m->bf.nx;
+    a.ny = m->bf.ny;
+    a.nt = m->bf.nt;
+    a.n = (int)np;
+    a.n_jobs = n_jobs;
+    a.oie = oies[0];
+    a.scores = s->d_scores.get();
+    SLAMHIP_CHECK(launch_bf_batch_score(a, models[0], max_n, ctx->stream));
+    ++s->launches;
+  } else {
+    for (int c = 0; c < n_jobs; ++c) {
+      ScoreArgs a;
+      std::memset(&a, 0, sizeof(a));
+      a.map = maps[c];
+      a.scan = scan_view_of(blocks[c].d, blocks[c].stride, blocks[c].n, blocks[c].tot_w);
+      rc = bf_peaks_score_job(m, a, models[c], oies[c], &centres[3 * (size_t)c], np, s->d_scores.get() + (size_t)c * (size_t)np);
+      if (rc) return rc;
+    }
+  }
+  rc = bf_peaks_reduce(m, n_jobs, np, bound, radius, min_ratio, min_score, max_peaks, centres.data(), peaks_out, n_written,
+                       n_found);
+  return rc;
+}
+
+int slamhip_matcher_bf_peaks_stats(slamhip_matcher *m, long long *launches, long long *survivors_bound, int *on_shared_launch) {
+  if (!m || !m->is_bf) return invalid_arg("the peaks of a sweep belong to a brute-force matcher");
+  const BfPeaksScratch none;
+  const BfPeaksScratch &s = m->bf_peaks ? *m->bf_peaks : none;
+  if (launches) *launches = s.launches;
+  if (survivors_bound) *survivors_bound = s.bound;
+  if (on_shared_launch) *on_shared_launch = s.shared;
   return SLAMHIP_OK;
 }
 

@@ -805,6 +805,42 @@ inline std::vector<std::vector<double>> hip_estimate_scan_probabilities(slamhip_
 }
 
 // ------------------------------------------------------------------------------------------------
+// The ambiguity report of a brute-force match: the local maxima of the score landscape BruteForceScanMatcher sweeps when
+// `centre` is its enumerator's base, best first (slamhip_matcher_bf_peaks) -- what ConnectTheDotsAmbiguousDriftDetector's
+// "the two best scores are equal" (connect_the_dots_ambiguous_drift_detector.h:83-88) and VinyXWorld::detect_peaks'
+// "finest matches within 3 % of the best" (vinyx_world.h:80-111; min_ratio = 0.97) ask of a landscape.  `scan` must be
+// the FILTERED one (filter_scan's result); it becomes the context's current scan, the map goes through its mirror.  `m`
+// is a matcher made by slamhip_matcher_create_bf: its enumerator, latch and counters are not touched.
+struct HipBfPeak {
+  RobotPose pose;
+  double score;
+  long long index;  // ix + nx (iy + ny it) on the enumerator's lattice
+};
+struct HipBfPeaks {
+  std::vector<HipBfPeak> peaks;  // at most max_peaks of them
+  long long n_found = 0;         // all that passed the floors
+  int shape[3] = {0, 0, 0};      // nx, ny, nt
+};
+
+inline HipBfPeaks hip_bf_match_peaks(slamhip_ctx *ctx, slamhip_matcher *m, HipMapMirror &mirror, const GridMap &map,
+                                     const LaserScan2D &scan, int weighting, const RobotPose &centre, const int radius[3],
+                                     double min_ratio, double min_score, int max_peaks, const HipScanTrig &trig = {}) {
+  HipBfPeaks out;
+  if (scan.points().empty()) return out;  // (nothing to score: no peaks, as for an all-NaN landscape)
+  mirror.sync(map);
+  hip_upload_filtered_scan(ctx, scan, weighting, trig);
+  std::vector<slamhip_bf_peak> buf(max_peaks > 0 ? size_t(max_peaks) : 1);
+  const double c3[3] = {centre.x, centre.y, centre.theta};
+  int n_written = 0;
+  slamhip_or_die(slamhip_matcher_bf_peaks(m, mirror.id(), c3, radius, min_ratio, min_score, max_peaks,
+                                          max_peaks > 0 ? buf.data() : nullptr, &n_written, &out.n_found, out.shape),
+                 "bf_peaks");
+  for (int q = 0; q < n_written; ++q)
+    out.peaks.push_back(HipBfPeak{RobotPose{buf[q].pose[0], buf[q].pose[1], buf[q].pose[2]}, buf[q].score, buf[q].index});
+  return out;
+}
+
+// ------------------------------------------------------------------------------------------------
 // read-only GridMap over a device window: occupancy() of the cell kinds the path holds -- the payload double of
 // OCC cells; for TBM cells the conversion of the cell class the map was configured with (TbmOccConsistentCell /
 // TbmUnknownEvenOccCell::tbm2occ, src/core/maps/tbm_grid_cells.h:76-100; a cell that was never updated still

@@ -11,10 +11,14 @@ tests/golden/make_golden_search_space.py; the scenes are therefore taken from a 
 by call through the compiled reference.)
 
     p2d_ss_evaluator_hip.py [--fixture tests/golden/search_space.npz] [--scene closed|open|several|all]
-                            [--out DIR] [--generate-scan]
+                            [--out DIR] [--generate-scan] [--peaks N]
 
 --generate-scan: the scan is not read from the fixture but ray-cast on the device from the uploaded map, with the
 reference CLI's scanner (to_lsp(100, 270, 1000), pose2D_search_space_evaluator.cpp:159) and occupancy threshold 1.
+
+--peaks N: also print the N best local maxima of the swept landscape (Matcher.bf_peaks: windows of 7 x 7 poses, scores
+within 3 % of the best -- VinyXWorld::detect_peaks' margin), picked on the device from the canonical sums of the default
+mode.  Two lines with equal scores are what ConnectTheDotsAmbiguousDriftDetector raises its alarm for.
 
 Needs a GPU: there is no CPU fallback.
 """
@@ -56,8 +60,8 @@ def generate_scan(sh, ctx, map_id, pose):
     return scan
 
 
-def evaluate(sh, fx, ctx, g, scene, strict=True, generate=False):
-    """-> dict(scores, poses, prob, delta, n_calls, seconds, sss_prob, sss_geometry)"""
+def evaluate(sh, fx, ctx, g, scene, strict=True, generate=False, peaks=0):
+    """-> dict(scores, poses, prob, delta, n_calls, seconds, sss_prob, sss_geometry[, peaks])"""
     m = Window(g[scene + "_map_payload"], g[scene + "_map_origin"], 0.1)
     pose, res = g["pose"], float(g["resolution"])
     if generate:
@@ -91,6 +95,10 @@ def evaluate(sh, fx, ctx, g, scene, strict=True, generate=False):
         prob[y + win.origin[1], x + win.origin[0]] = s
     t.update(seconds=seconds, sss_prob=prob, sss_geometry=(win.width, win.height, win.origin[0], win.origin[1]),
              input_prob=m.payload[..., 0], beams=len(kept))
+    if peaks > 0:  # (the sweep's base is the pose of its first match: the same lattice)
+        pm = sh.Matcher(ctx, "BF", sh.spe_cfg(), g["params"])
+        t["peaks"] = pm.bf_peaks(0, pose, radius=(3, 3, 0), min_ratio=0.97, max_peaks=peaks)
+        pm.close()
     return t
 
 
@@ -101,6 +109,7 @@ def main():
     ap.add_argument("--out", default=".")
     ap.add_argument("--default-mode", action="store_true", help="tree sum + device sincos instead of strict")
     ap.add_argument("--generate-scan", action="store_true", help="ray-cast the scan on the device instead of reading it")
+    ap.add_argument("--peaks", type=int, default=0, help="print the N best local maxima of the landscape")
     args = ap.parse_args()
     sh = _pkg()
     from importlib import import_module
@@ -110,7 +119,7 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     for scene in (["closed", "open", "several"] if args.scene == "all" else [args.scene]):
         print(TITLES[scene])
-        t = evaluate(sh, fx, ctx, g, scene, strict=not args.default_mode, generate=args.generate_scan)
+        t = evaluate(sh, fx, ctx, g, scene, strict=not args.default_mode, generate=args.generate_scan, peaks=args.peaks)
         print("BF: %g" % t["seconds"])
         with open(os.path.join(args.out, "input_map_0.pgm"), "wb") as f:
             f.write(fx.pgm_bytes(t["input_prob"]))
@@ -119,6 +128,11 @@ def main():
         print("  %d poses x %d beams, %.3g pose-candidates*beams/s; best %.6g at delta (%g, %g, %g)"
               % (t["n_calls"], t["beams"], t["n_calls"] * t["beams"] / t["seconds"], t["prob"], *t["delta"]),
               file=sys.stderr)
+        if args.peaks > 0:
+            pk = t["peaks"]
+            print("peaks: %d within 3 %% of the best, %d shown" % (pk["n_found"], len(pk["index"])))
+            for p3, sc, ix in zip(pk["poses"], pk["scores"], pk["index"]):
+                print("  %.17g at (%g, %g, %g), lattice index %d" % (sc, p3[0], p3[1], p3[2], ix))
     return 0
 
 
