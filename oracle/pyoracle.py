@@ -398,6 +398,15 @@ class OrcGmappingHandle:
                                            idx.ctypes.data_as(_up))
         return bool(res), idx
 
+    def set(self, poses=None, weights=None):
+        """every particle's pose [n, 3] and / or weight [n], as GmappingFilter.set of the device side"""
+        p = f64(poses) if poses is not None else None
+        w = f64(weights) if weights is not None else None
+        assert (p is None or p.size == 3 * self.n) and (w is None or w.size == self.n)
+        self.o.lib.orc_gmapping_set.argtypes = [C.c_void_p, _dp, _dp]
+        self.o.lib.orc_gmapping_set.restype = None
+        self.o.lib.orc_gmapping_set(self.h, _d(p) if p is not None else None, _d(w) if w is not None else None)
+
     def state(self):
         poses, w, ms = np.zeros((self.n, 3)), np.zeros(self.n), np.zeros(self.n, np.int32)
         self.o.lib.orc_gmapping_get(self.h, _d(poses), _d(w), _i(ms))

@@ -177,6 +177,8 @@ int orc_gmapping_step(orc_gmapping *g, const orc_map *map, int n_raw, const doub
                       uint32_t resample_seed, int n_extra, const uint32_t *extra_seeds,
                       unsigned *idx_out);
 void orc_gmapping_get(const orc_gmapping *g, double *poses, double *weights, int *is_master);
+/* overwrite every particle's pose and / or weight (either may be NULL) */
+void orc_gmapping_set(orc_gmapping *g, const double *poses, const double *weights);
 long long orc_gmapping_scorer_calls(const orc_gmapping *g);
 void orc_gmapping_set_update(orc_gmapping *g, const orc_adder *upd, double *payload, double *aux);
 /* every particle gets its own copy of (payload, aux); updates inside the step go to the copies */
